@@ -1,6 +1,7 @@
 """Headline benchmark: utterance-seconds enhanced per second (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3] [--full]
+                    [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 may be started either way:
 
@@ -20,7 +21,12 @@ of the elapsed time and (through its TCP store) the shared work counter of
     A "step" is one pass of the whole hot path (STFT -> WPE -> CACGMM EM -> MVDR+BAN ->
     iSTFT) over one synthetic 24-microphone 15 s utterance whose samples and activity
     are resident in HBM when the timed region starts (`value`).  Every rank times its
-    own K steps ("weak" scaling).  Besides `value` the line carries
+    own K steps ("weak" scaling).  A plain run does only that: set-up, W warm-up steps,
+    the K timed steps, the result line.  ``--dump-outputs DIR`` then writes what the last
+    timed step computed (rank 0's enhanced signal, float64) to DIR/x_hat.npy; the inputs
+    are seeded, so two builds can be compared output for output.  With ``--full`` the
+    line also carries
+      kernels           the per-kernel table of an untimed pass with events around every launch
       value_incl_pcie   the session driver's mode: two utterances in flight per GPU,
                         PCM16 upload (H2D) and result download (D2H) inside the wall clock
       configs           in-process timings of the other BASELINE configs (1, one dev-shaped
@@ -31,9 +37,9 @@ of the elapsed time and (through its TCP store) the shared work counter of
                         24 channels and for one array (4 channels)
       roofline          the dominant kernel, timed with HIP events inside the timed region
       cpu_baseline      the NumPy oracle on W = physical cores - 1 worker processes
-    ``--only-headline`` skips everything but `value` / `roofline` / `kernels` (the command
-    the rocprofv3 summaries under profiles/ are taken with: back-to-back launches of one
-    stream and one shape only).
+    ``--only-headline`` runs `value` / `roofline` / `kernels` and nothing else of ``--full``
+    (the command the rocprofv3 summaries under profiles/ are taken with: back-to-back
+    launches of one stream and one shape only).
 
 --config 3
     The sharded session alone: `value` = sum of utterance seconds / wall clock over all
@@ -597,7 +603,17 @@ def parse_args():
     ap.add_argument('--pool', type=int, default=2, help='config-3 base recordings')
     ap.add_argument('--inflight', type=int, default=2)
     ap.add_argument('--static', action='store_true', help='config 3: static instead of dynamic sharding')
-    ap.add_argument('--only-headline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='config 2: everything besides the headline -- the per-kernel pass '
+                         '(`kernels`, `roofline`, `em_loop`), one-at-a-time and session modes, the '
+                         'other BASELINE configs, the sharded config 3, the config-4 stand-in and the '
+                         'CPU baseline.  Off: the headline alone')
+    ap.add_argument('--only-headline', action='store_true',
+                    help='config 2: the headline and its per-kernel pass (`kernels`, `roofline`), '
+                         'nothing else of --full')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='config 2: after the timed steps write what the last one computed (the '
+                         'enhanced signal of rank 0, float64) as DIR/x_hat.npy')
     ap.add_argument('--workload', default='2', choices=('2', '5', '3i', '1a'),
                     help="what the headline section times (anything but '2' implies "
                          "--only-headline): 2 = BASELINE configs[1]; 5 = configs[4] (12 ch, 120 s, "
@@ -608,13 +624,20 @@ def parse_args():
                     help="the same workload's `value` at --gpus 1 (a BENCH record): the line then "
                          "carries scaling_efficiency_vs_n1 = value / (N x n1) beside value_per_gpu")
     ap.add_argument('--one-at-a-time', action='store_true',
-                    help='with --only-headline / --workload: also time the loop with the WPE stage on two '
-                         'streams (value_one_at_a_time_api); off by default so that a profile of the '
-                         'command sees one-stream launches only')
+                    help='without --full (or with --only-headline / --workload): also time the loop '
+                         'with the WPE stage on two streams (value_one_at_a_time_api); off by default '
+                         'so that a profile of the command sees one-stream launches only')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-bins', type=int, default=24)
     ap.add_argument('--cpu-workers', type=int, default=None)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
+    if args.dump_outputs is not None and args.config != '2':
+        ap.error('--dump-outputs writes the outputs of the --config 2 timed path only')
+    return args
 
 
 def main():
@@ -989,24 +1012,31 @@ def main():
     def step():
         resident.enqueue(utt.target_index, ctx_samples, end_samples)
 
+    # the per-kernel pass and `roofline`: with --full, and in --only-headline / --workload runs
+    profiled = args.full or args.only_headline
+    if not profiled:
+        # untimed: the first call sizes the workspace and loads the code objects, which the
+        # per-kernel pass below absorbs when it runs (so `value` never includes them)
+        step()
     for _ in range(args.warmup):
         step()
     barrier()
-    # Untimed pass with HIP events around EVERY launch: the per-kernel table and the
-    # name of the dominant kernel.  (Two events per launch cost ~4 us of stream time
-    # each; around all ~260 launches of an utterance that is 6 % of the step, so the
-    # timed region below only carries events around the dominant kernel.)
-    prof_all = profile_kernels(ctx, resident, utt, PROFILE_STEPS)
-    dominant = max(prof_all, key=lambda k: prof_all[k]['ms'])
-    if dist is not None:       # every rank times the same kernel
-        names = sorted(prof_all)
-        idx = torch.tensor([names.index(dominant)], device=coll_device)
-        dist.broadcast(idx, src=0)
-        dominant = names[int(idx.item())]
-    ctx.profile_filter(dominant)
-    ctx.profile_enable(True)
-    ctx.profile_reset()
-    barrier()
+    if profiled:
+        # Untimed pass with HIP events around EVERY launch: the per-kernel table and the
+        # name of the dominant kernel.  (Two events per launch cost ~4 us of stream time
+        # each; around all ~260 launches of an utterance that is 6 % of the step, so the
+        # timed region below only carries events around the dominant kernel.)
+        prof_all = profile_kernels(ctx, resident, utt, PROFILE_STEPS)
+        dominant = max(prof_all, key=lambda k: prof_all[k]['ms'])
+        if dist is not None:       # every rank times the same kernel
+            names = sorted(prof_all)
+            idx = torch.tensor([names.index(dominant)], device=coll_device)
+            dist.broadcast(idx, src=0)
+            dominant = names[int(idx.item())]
+        ctx.profile_filter(dominant)
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
@@ -1014,16 +1044,23 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
-    prof = ctx.profile_report()
-    ctx.profile_enable(False)
-    ctx.profile_filter(None)
+    if profiled:
+        prof = ctx.profile_report()
+        ctx.profile_enable(False)
+        ctx.profile_filter(None)
     x_hat = resident.result()
     assert np.all(np.isfinite(x_hat)) and x_hat.shape[0] == resident.n_out
+    if args.dump_outputs is not None and rank == 0:
+        # the enhanced signal the last timed step left (float64, what ResidentUtterance.result
+        # hands a caller); the inputs are seeded, so two builds compare output for output
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        np.save(out_dir / 'x_hat.npy', np.asarray(x_hat, dtype=np.float64))
     elapsed_local = elapsed
     elapsed = max_over_ranks(elapsed)
     headline_rows = gather_over_ranks([elapsed_local])
 
-    extras = not args.only_headline
+    extras = args.full and not args.only_headline
     # ---- the same timed loop the way Enhancer.enhance_example runs an utterance: the caller has
     # said "one utterance at a time" and the WPE stage's frequencies go in two sets on two
     # streams (gss_set_utterances_in_flight(ctx, 1); same bits).  NOT the headline: overlapped
@@ -1155,18 +1192,22 @@ def main():
     if rank == 0:
         size = dict(F=F, T=resident.T, D=resident.D, K=resident.K, taps=workload['wpe_taps'],
                     N=resident.N, iterations=workload['bss_iterations'])
-        total_ms = sum(v['ms'] for v in prof_all.values())
-        kernels = {}
-        for name, v in sorted(prof_all.items(), key=lambda kv: -kv[1]['ms']):
-            avg = v['ms'] / max(v['calls'], 1)
-            entry = roofline.roofline_entry(name, avg, **size)
-            kernels[name] = {
-                'calls_per_step': v['calls'] / PROFILE_STEPS, 'avg_ms': round(avg, 5),
-                'share': round(v['ms'] / total_ms, 4),
-                'frac_of_roof': round(entry['frac'], 4) if entry else None,
-                'bound': entry['bound'] if entry else None}
-        roof = roofline.roofline_entry(dominant, prof[dominant]['ms'] / prof[dominant]['calls'],
-                                       **size)
+        total_ms = kernels = roof = kernel_ms = None
+        if profiled:
+            total_ms = sum(v['ms'] for v in prof_all.values())
+            kernels = {}
+            for name, v in sorted(prof_all.items(), key=lambda kv: -kv[1]['ms']):
+                avg = v['ms'] / max(v['calls'], 1)
+                entry = roofline.roofline_entry(name, avg, **size)
+                kernels[name] = {
+                    'calls_per_step': v['calls'] / PROFILE_STEPS, 'avg_ms': round(avg, 5),
+                    'share': round(v['ms'] / total_ms, 4),
+                    'frac_of_roof': round(entry['frac'], 4) if entry else None,
+                    'bound': entry['bound'] if entry else None}
+            kernel_ms = {k: round(v['ms'] / PROFILE_STEPS, 4) for k, v in
+                         sorted(prof_all.items(), key=lambda kv: -kv[1]['ms'])}
+            roof = roofline.roofline_entry(dominant, prof[dominant]['ms'] / prof[dominant]['calls'],
+                                           **size)
         traffic_file = REPO / 'profiles' / ('traffic.json' if args.workload == '2'
                                             else f'traffic_{args.workload}.json')
         if roof is not None and traffic_file.exists():
@@ -1190,7 +1231,7 @@ def main():
                         'hashes as the loaded library\'s: ' + ', '.join(roofline.kernel_sources(dominant)) + ')')
             except Exception as e:      # noqa: BLE001
                 roof['traffic_stale'] = {'error': f'{type(e).__name__}: {e}'}
-        if args.workload != '2':
+        if args.workload != '2' and profiled:
             # the EM loop of this shape against both roofs, from the same untimed pass
             em_loop = {f'D{resident.D}_T{resident.T}': em_loop_entry(
                 prof_all, PROFILE_STEPS, workload['bss_iterations'], F=F, T=resident.T,
@@ -1229,13 +1270,13 @@ def main():
             'session_mode': incl,
             'roofline': roof,
             'kernels': kernels,
-            'kernel_ms_per_utterance': {k: round(v['ms'] / PROFILE_STEPS, 4) for k, v in
-                                        sorted(prof_all.items(), key=lambda kv: -kv[1]['ms'])},
+            'kernel_ms_per_utterance': kernel_ms,
             'kernels_note': (f'per-kernel table from an untimed pass of {PROFILE_STEPS} steps with HIP '
                              'events around every launch; `roofline` is the dominant kernel timed '
                              'inside the timed region; frac_of_roof prices the minimum flops / bytes '
-                             'of each kernel\'s formulation (pb_chime5_amd/roofline.py)'),
-            'device_ms_per_step': total_ms / PROFILE_STEPS,
+                             'of each kernel\'s formulation (pb_chime5_amd/roofline.py)') if profiled
+                            else 'no per-kernel pass (run with --full or --only-headline)',
+            'device_ms_per_step': total_ms / PROFILE_STEPS if profiled else None,
             # the whole step against the chip's f64 peak: executed flops / duration / 78.6 TFLOP/s
             'f64_peak_frac': roofline.step_peak_frac(
                 1e3 * elapsed / steps, F=F, T=resident.T, D=resident.D, K=resident.K,

@@ -3,7 +3,7 @@
 # command and the --pmc passes behind profiles/ (each counter group in its own run, with
 # --kernel-trace only).  Output under gpurun_out/; summaries: tools/pmc_traffic.py,
 # tools/pmc_mfma.py, tools/pmc_summary.py.
-#   tools/collect_profiles.sh TAG                      the headline (config 2) + the full default line
+#   tools/collect_profiles.sh TAG                      the headline (config 2) + the --full line
 #   tools/collect_profiles.sh TAG --workload 5         another BASELINE shape (5, 3i, 1a): no full line
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-r03c}
@@ -40,8 +40,8 @@ cp $O/traffic_$TAG.json $R/profiles/$TF
 # ONE stream and ONE shape, so that per-kernel averages mean something) ...
 (cd /tmp && bench) > $O/bench_${TAG}_headline.json 2>> $O/bench_$TAG.err
 if [ -z "$W" ]; then
-  # ... and the full default line (session mode, configs table, sharded config 3, CPU baseline)
-  (cd /tmp && python $R/bench.py) > $O/bench_$TAG.json 2>> $O/bench_$TAG.err
+  # ... and the --full line (session mode, configs table, sharded config 3, CPU baseline)
+  (cd /tmp && python $R/bench.py --full) > $O/bench_$TAG.json 2>> $O/bench_$TAG.err
 fi
 tail -n 1 $O/bench_${TAG}_headline.json | cut -c1-300
 cc() { find $O/$1 -name "*counter_collection.csv" | head -1; }

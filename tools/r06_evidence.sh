@@ -13,7 +13,7 @@ bash tools/collect_profiles.sh r06a > $O/collect_r06a.log 2>&1
 bash tools/collect_profiles.sh r06b_cfg5 --workload 5 > $O/collect_r06b_cfg5.log 2>&1
 bash tools/collect_profiles.sh r06b_1a --workload 1a > $O/collect_r06b_1a.log 2>&1
 bash tools/collect_profiles.sh r06b_3i --workload 3i > $O/collect_r06b_3i.log 2>&1
-python bench.py --gpus 8 --n1-value 1085 > $O/r06_headline_g8_shared.json 2> $O/r06_headline_g8_shared.err
+python bench.py --gpus 8 --full --n1-value 1085 > $O/r06_headline_g8_shared.json 2> $O/r06_headline_g8_shared.err
 python bench.py --gpus 8 --config 3 > $O/r06_config3_g8_shared.json 2> $O/r06_config3_g8_shared.err
 python bench.py --gpus 8 --config 4s > $O/r06_config4s_g8_shared.json 2> $O/r06_config4s_g8_shared.err
 python bench.py --config 4s > $O/r06_config4s_g1.json 2> $O/r06_config4s_g1.err
