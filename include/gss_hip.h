@@ -67,9 +67,10 @@ typedef enum {
 
 /* ABI revision of this header.  Bumped whenever an entry point changes its argument list
  * or a struct its layout (round 2 added `psd_context` to gss_wpe and `wpe_psd_context` to
- * gss_params: revision 2; rounds 3, 4 and 5 added entry points only: revisions 3, 4, 5).  A binder compares
+ * gss_params: revision 2; rounds 3, 4 and 5 added entry points only: revisions 3, 4, 5;
+ * revision 7 appended `wpe_arrays` to gss_params and added gss_wpe_arrays).  A binder compares
  * gss_abi_version() with the GSS_ABI_VERSION it was written against before any other call. */
-#define GSS_ABI_VERSION 6
+#define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
 /* ---- context ----------------------------------------------------------- */
@@ -167,6 +168,18 @@ int gss_activity_time_to_frequency(gss_ctx *ctx, const uint8_t *act_dev, int K,
  * default.  Y (F,T,D) -> X (F,T,D); X must not alias Y unless iterations == 0. */
 int gss_wpe(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
             int taps, int delay, int iterations, int psd_context, gss_cplx *X_dev);
+
+/* Per-array WPE: WPE.__call__(Obs, stack=False) (core.py:71-79) -- one wpe_v8 per microphone
+ * array -- on the pipeline's layout.  Y (F,T,A*C) holds A arrays of C channels each, array-major
+ * (the morph('ACN->A*CN') order of enhance_example, core.py:428-441): channels a*C ... a*C+C-1
+ * are array a, and each array is dereverberated on its own (its own inverse power, the mean
+ * over ITS C channels, its own (C taps) x (C taps) system per frequency).  Y (F,T,A*C) ->
+ * X (F,T,A*C): gss_wpe on the (A*F, T, C) regrouping, bit-identical up to one choice -- where
+ * F*A bins make four or more rounds of single correlation waves (config 2: 3078 bins of 4
+ * channels) their frames are not split over waves, which gss_wpe does at every size (the same
+ * sums in another order).  A = 1 is gss_wpe.  X must not alias Y unless iterations == 0 or A > 1. */
+int gss_wpe_arrays(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int A, int C,
+                   int taps, int delay, int iterations, int psd_context, gss_cplx *X_dev);
 
 /* The weights of one WPE iteration on their own: nara_wpe.wpe.get_power_inverse(Y,
  * psd_context) as wpe_v6 calls it (mean over channels of |Y|^2, optionally averaged over
@@ -267,6 +280,10 @@ typedef struct {
                               /* 3 = 'gev_ban' (not in the reference's dispatch) */
     int postfilter;           /* 0 = None, 1 = 'mask_mul'                      */
     int wpe_psd_context;      /* 0: frames either side averaged into the WPE power */
+    int wpe_arrays;           /* 0 or 1: one joint WPE over all D channels;        */
+                              /* A > 1: WPE per array on D / A channels each, in   */
+                              /* array-major channel order (gss_wpe_arrays); A     */
+                              /* must divide D (GSS_ERR_INVALID); unread if !wpe   */
 } gss_params;
 
 /* Optional taps into the pipeline's intermediates (device pointers; any may be

@@ -18,7 +18,7 @@ GSS_ERR_INVALID = -1
 GSS_ERR_HIP = -2
 GSS_ERR_NOMEM = -3
 GSS_ERR_UNSUPPORTED = -4
-GSS_ABI_VERSION = 6       # include/gss_hip.h revision these prototypes are written against
+GSS_ABI_VERSION = 7       # include/gss_hip.h revision these prototypes are written against
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -30,7 +30,7 @@ class GssParams(ctypes.Structure):
     _fields_ = [(n, c_int) for n in (
         'stft_size', 'stft_shift', 'stft_fading', 'wpe', 'wpe_taps', 'wpe_delay',
         'wpe_iterations', 'bss_iterations', 'bss_iterations_post',
-        'bf_drop_context', 'bf', 'postfilter', 'wpe_psd_context')]
+        'bf_drop_context', 'bf', 'postfilter', 'wpe_psd_context', 'wpe_arrays')]
 
 
 class GssDebugTaps(ctypes.Structure):
@@ -74,6 +74,8 @@ SIGNATURES = {
         c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
     'gss_wpe': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int,
                         c_int, c_int, c_void_p]),
+    'gss_wpe_arrays': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int,
+                               c_int, c_int, c_void_p]),
     'gss_wpe_inverse_power': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
                                       c_void_p]),
     'gss_cacgmm': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p,

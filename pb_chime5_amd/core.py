@@ -46,7 +46,11 @@ class WPE:
                 Obs = ops.wpe_dtf(Obs, **kw)
                 Obs = morph('A*CTF->ACTF', Obs, A=_A)
             elif stack is False:
-                Obs = np.array([ops.wpe_dtf(o, **kw) for o in Obs])
+                # one wpe_v8 per array (core.py:71-79), all arrays in one device call
+                _A = Obs.shape[0]
+                Obs = morph('ACTF->A*CTF', Obs)
+                Obs = ops.wpe_arrays_dtf(Obs, _A, **kw)
+                Obs = morph('A*CTF->ACTF', Obs, A=_A)
             else:
                 raise NotImplementedError(stack)
         else:
@@ -239,6 +243,32 @@ class Enhancer:
     iterator_factory: object = field(default=None, repr=False)
     inflight: int = 2        # utterances kept in flight per GPU by enhance_session
     loaders: int = 3         # host threads that read the next examples' audio ahead of the GPU
+    # WPE per microphone array (WPE.__call__(Obs, stack=False), core.py:71-79), then GSS and the
+    # beamformer on all channels together; only with a multiarray mode and WPE (otherwise no
+    # effect).  Off: the reference's joint WPE over all channels.
+    wpe_per_array: bool = False
+
+    # channels per array that each multiarray mode loads (core.py:428-441)
+    _ARRAY_CHANNELS = {True: 4, 'outer_array_mics': 2, 'first_array_mics': 1}
+
+    def wpe_arrays(self, ex, num_channels):
+        """The number of arrays A of the per-array WPE for an observation of ``num_channels``
+        channels (1 = one joint WPE): the arrays of ``ex['audio_path']['observation']`` (a
+        flat list of channel files, as in the RTTM database, or no example: num_channels / C),
+        C channels each as the multiarray mode loads them.  ValueError when A C differs from
+        num_channels."""
+        if not self.wpe_per_array or self.wpe_block is None or self.multiarray is False:
+            return 1
+        if self.multiarray not in self._ARRAY_CHANNELS:
+            raise ValueError(self.multiarray)
+        C = self._ARRAY_CHANNELS[self.multiarray]
+        observation = (ex or {}).get('audio_path', {})
+        observation = observation.get('observation') if isinstance(observation, dict) else None
+        A = len(observation) if isinstance(observation, dict) else num_channels // C
+        if A * C != num_channels:
+            raise ValueError(f'wpe_per_array: {num_channels} channels are not {A} arrays of {C} '
+                             f'(multiarray={self.multiarray!r})')
+        return A
 
     # ------------------------------------------------------------------ STFT
     def stft(self, x):
@@ -420,7 +450,8 @@ class Enhancer:
                     pop_and_write()
                 t0 = time.perf_counter()
                 try:
-                    pipe.enqueue_staged(ex, *prepared)
+                    pipe.enqueue_staged(ex, *prepared, wpe_arrays=self.wpe_arrays(
+                        ex, prepared[0].obs.shape[0]))
                 except BaseException:
                     pipe.release_staging(prepared[0])
                     raise
@@ -636,14 +667,18 @@ class Enhancer:
             postfilter=self.bf_block.postfilter)
 
     def enhance_observation(self, obs, ex_array_activity, speaker_id, ex=None,
-                            debug=False, fused=None):
+                            debug=False, fused=None, wpe_arrays=None):
         """core.py:514-571.  obs (D,N) float64, ex_array_activity dict
-        speaker -> bool (N,), returns x_hat (N',) float64."""
+        speaker -> bool (N,), returns x_hat (N',) float64.  ``wpe_arrays``: the number of
+        microphone arrays of a per-array WPE (None: `wpe_arrays(ex, D)`)."""
+        if wpe_arrays is None:
+            wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
+        wpe_arrays = ops.check_wpe_arrays(wpe_arrays, np.shape(obs)[0])
         if fused is None:
             fused = self._fusable()
         if not fused:
             return self._enhance_observation_blocks(obs, ex_array_activity, speaker_id,
-                                                    ex, debug)
+                                                    ex, debug, wpe_arrays)
         target_speaker_index = tuple(ex_array_activity.keys()).index(speaker_id)
         activity = np.array(list(ex_array_activity.values()))
         start_ctx = end_ctx = 0
@@ -657,7 +692,7 @@ class Enhancer:
         try:
             res = ops.enhance_observation(
                 obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
-                debug=debug, ctx=ctx)
+                debug=debug, ctx=ctx, wpe_arrays=wpe_arrays)
         finally:
             ctx.set_utterances_in_flight(0)
         if not debug:
@@ -678,11 +713,17 @@ class Enhancer:
         self.enhance_observation_locals = locals()
         return x_hat
 
-    def _enhance_observation_blocks(self, obs, ex_array_activity, speaker_id, ex, debug):
+    def _enhance_observation_blocks(self, obs, ex_array_activity, speaker_id, ex, debug,
+                                    wpe_arrays=1):
         """Block-by-block path with the reference's control flow (one device
         round trip per block); used when a block was swapped out."""
         Obs = self.stft(obs)
-        if self.wpe_block is not None:
+        if self.wpe_block is not None and wpe_arrays > 1:
+            _A = wpe_arrays
+            Obs = morph('A*CTF->ACTF', Obs, A=_A)
+            Obs = self.wpe_block(Obs, stack=False, debug=debug)
+            Obs = morph('ACTF->A*CTF', Obs)
+        elif self.wpe_block is not None:
             Obs = self.wpe_block(Obs, debug=debug)
         acitivity_freq = activity_time_to_frequency(
             np.array(list(ex_array_activity.values())),
@@ -739,9 +780,13 @@ def get_enhancer(
     activity_store=None,
     iterator_factory=None,
     device_id=None,
+    wpe_per_array=False,
 ):
     """core.py:574-637 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory`` and ``device_id`` are additions)."""
+    ``iterator_factory``, ``device_id`` and ``wpe_per_array`` are additions).
+    ``wpe_per_array=True``: with a multiarray mode, WPE runs on each microphone array on its
+    own (the reference's ``WPE(..., stack=False)``), GSS and the beamformer on all channels;
+    no effect with ``multiarray=False`` or ``wpe=False``."""
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
 
@@ -763,4 +808,5 @@ def get_enhancer(
         stft_fading=stft_fading,
         device_id=device_id,
         iterator_factory=iterator_factory,
+        wpe_per_array=bool(wpe_per_array),
     )

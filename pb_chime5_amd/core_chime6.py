@@ -140,6 +140,7 @@ def get_enhancer(
     activity_store=None,
     iterator_factory=None,
     device_id=None,
+    wpe_per_array=False,
 ):
     """core_chime6.py:572-635 (same keyword arguments and defaults; the last three are
     additions)."""
@@ -163,4 +164,5 @@ def get_enhancer(
         stft_fading=stft_fading,
         device_id=device_id,
         iterator_factory=iterator_factory,
+        wpe_per_array=bool(wpe_per_array),
     )

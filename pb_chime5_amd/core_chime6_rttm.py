@@ -150,6 +150,7 @@ def get_enhancer(
     postfilter=None,
 
     device_id=None,
+    wpe_per_array=False,
 ):
     """core_chime6_rttm.py:360-422 (same keyword arguments and defaults)."""
     assert wpe is True or wpe is False, wpe
@@ -170,4 +171,5 @@ def get_enhancer(
         stft_shift=stft_shift,
         stft_fading=stft_fading,
         device_id=device_id,
+        wpe_per_array=bool(wpe_per_array),
     )

@@ -553,6 +553,38 @@ extern "C" int gss_wpe(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
                    psd_context, reinterpret_cast<cplx *>(X));
 }
 
+extern "C" int gss_wpe_arrays(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int A, int C,
+                              int taps, int delay, int iterations, int psd_context, gss_cplx *X) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, Y && X && F >= 1 && T >= 1 && A >= 1 && C >= 1, GSS_ERR_INVALID,
+                "gss_wpe_arrays: bad arguments");
+    const int D = A * C;
+    GSS_REQUIRE(ctx, D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
+                "gss_wpe_arrays: A * C = %d outside [1, %d]", D, GSS_MAX_CHANNELS);
+    GSS_REQUIRE(ctx, taps >= 1 && delay >= 0 && iterations >= 0 && psd_context >= 0,
+                GSS_ERR_INVALID, "gss_wpe_arrays: taps=%d delay=%d iterations=%d psd_context=%d",
+                taps, delay, iterations, psd_context);
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    if (A == 1) {       // one array: gss_wpe itself
+        GSS_REQUIRE(ctx, X != Y || iterations == 0, GSS_ERR_INVALID,
+                    "gss_wpe_arrays: X must not alias Y");
+        GSS_TRY(arena_reserve(ctx, wpe_workspace_bytes(F, T, D, taps, delay)));
+        return wpe_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, taps, delay, iterations,
+                       psd_context, reinterpret_cast<cplx *>(X));
+    }
+    const size_t ftd = (size_t)F * T * D;
+    GSS_TRY(arena_reserve(ctx, 2 * align_up(sizeof(cplx) * ftd) +
+                                   wpe_workspace_bytes(F * A, T, C, taps, delay) + (1 << 16)));
+    cplx *Yg = arena_alloc_t<cplx>(ctx, ftd);
+    cplx *Xg = arena_alloc_t<cplx>(ctx, ftd);
+    GSS_REQUIRE(ctx, Yg && Xg, GSS_ERR_NOMEM, "gss_wpe_arrays workspace");
+    GSS_TRY(wpe_arrays_regroup_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, A, C, true, Yg));
+    GSS_TRY(wpe_run(ctx, Yg, F * A, T, C, taps, delay, iterations, psd_context, Xg, -1, F * A));
+    return wpe_arrays_regroup_run(ctx, Xg, F, T, A, C, false, reinterpret_cast<cplx *>(X));
+}
+
 extern "C" int gss_wpe_inverse_power(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
                                      int psd_context, double *inverse_power) {
     GSS_ENTER_VARIANTS(ctx);
@@ -687,8 +719,57 @@ static int check_params(gss_ctx *ctx, const gss_params *p) {
     return GSS_OK;
 }
 
+// Arrays of the WPE stage: 0 and 1 = one joint WPE over all D channels; A > 1 = A independent
+// WPEs of D / A channels each (gss_params.wpe_arrays)
+static int wpe_arrays_of(const gss_params *p) { return p->wpe_arrays > 1 ? p->wpe_arrays : 1; }
+
+static int check_wpe_arrays(gss_ctx *ctx, const gss_params *p, int D) {
+    GSS_REQUIRE(ctx, p->wpe_arrays >= 0 && D % wpe_arrays_of(p) == 0, GSS_ERR_INVALID,
+                "wpe_arrays=%d does not divide the %d channels into arrays of equal size",
+                p->wpe_arrays, D);
+    return GSS_OK;
+}
+
+// The WPE stage of the pipeline on Fv (virtual) bins of Dv channels, Y -> X.  After
+// gss_set_utterances_in_flight(ctx, 1) it runs as two sets of bins side by side on the
+// context's stream and its internal second stream -- one set's solve (a chain of latency-bound
+// launches, MFMA busy 0.3) under the other's correlation.  Bins are independent: the same bits.
+// Measured +1.1 ... +2.1 % at 4 / 12 / 20 / 24 channels for a single utterance and -1.6 %
+// when two utterances are in flight anyway (EXPERIMENTS round 6, item 8), hence the hint;
+// not the default because overlapped launches no longer have durations of their own (the
+// per-kernel table and the roofline of a profile are taken on one stream).  GSS_VARIANT
+// wpe_halves=0 / 1 forces it off / on, wpe_halves=n (n > 1) puts 8 n bins into the first set.
+static int pipeline_wpe(gss_ctx *ctx, const gss_params *p, const cplx *Y, int Fv, int64_t T,
+                        int Dv, cplx *X) {
+    const int array_bins = wpe_arrays_of(p) > 1 ? Fv : 0;
+    const int halves = gss_variant("wpe_halves", ctx->utterances_in_flight == 1 ? 1 : 0);
+    if (!(halves > 0 && Fv >= 32 && p->wpe_iterations > 0))
+        return wpe_run(ctx, Y, Fv, T, Dv, p->wpe_taps, p->wpe_delay, p->wpe_iterations,
+                       p->wpe_psd_context, X, -1, array_bins);
+    GSS_TRY(aux_stream_ready(ctx));
+    hipStream_t const main_stream = ctx->stream;
+    const int F0 = halves > 1 ? std::min(halves * 8, Fv - 8) : (Fv / 2 + 7) / 8 * 8, F1 = Fv - F0;
+    const size_t off = (size_t)F0 * T * Dv;
+    int st = wpe_run(ctx, Y, F0, T, Dv, p->wpe_taps, p->wpe_delay, p->wpe_iterations,
+                     p->wpe_psd_context, X, 0, array_bins);
+    if (st == GSS_OK) {
+        GSS_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
+        ctx->stream = ctx->aux_stream;
+        st = wpe_run(ctx, Y + off, F1, T, Dv, p->wpe_taps, p->wpe_delay, p->wpe_iterations,
+                     p->wpe_psd_context, X + off, 1, array_bins);
+        ctx->stream = main_stream;
+        // (joined even when the second part failed to enqueue: nothing may be left running
+        // on the internal stream when the call returns)
+        GSS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join, ctx->aux_stream));
+        GSS_HIP_CHECK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
+    }
+    GSS_TRY(st);
+    return wpe_copy_zero_pivots(ctx);
+}
+
 static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
                                  int K) {
+    const int A = wpe_arrays_of(p);
     size_t b = 0;
     size_t ftd = align_up(sizeof(cplx) * (size_t)F * T * D);
     b += 2 * ftd;                                            // Y, X
@@ -698,7 +779,9 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
     b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
     b += 4096;
     size_t stage = 0;
-    if (p->wpe) stage = std::max(stage, wpe_workspace_bytes(F, T, D, p->wpe_taps, p->wpe_delay) + (1 << 16));
+    // (per-array WPE: R is F A (C taps)^2, C = D / A)
+    if (p->wpe)
+        stage = std::max(stage, wpe_workspace_bytes(F * A, T, D / A, p->wpe_taps, p->wpe_delay) + (1 << 16));
     stage = std::max(stage, cacgmm_workspace_bytes(F, T, D, K));
     stage = std::max(stage, mvdr_workspace_bytes(F, T, D));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
@@ -721,6 +804,7 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
                 "assert context samples >= 0 failed: %lld %lld", (long long)start_ctx,
                 (long long)end_ctx);
     GSS_TRY(check_cacgmm_args(ctx, D, K, p->bss_iterations, p->bss_iterations_post));
+    if (p->wpe) GSS_TRY(check_wpe_arrays(ctx, p, D));   // (no WPE: the field is not read)
     if (p->bf == 0 || p->bf == 3)
         GSS_REQUIRE(ctx, D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
     if (p->bf == 1)
@@ -755,41 +839,17 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     GSS_TRY(stft_run(ctx, obs, obs_type, D, N, fading, Y));
     if (!p->wpe)    // no solve in this call: clear the count an earlier utterance left behind
         GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + 2, 0, sizeof(int32_t), ctx->stream));
-    // The caller said "one utterance at a time on this GPU" (gss_set_utterances_in_flight(ctx, 1)):
-    // the WPE stage runs as two sets of frequencies side by side on the context's stream and
-    // its internal second stream -- one set's solve (a chain of latency-bound launches, MFMA
-    // busy 0.3) under the other's correlation.  Frequencies are independent: the same bits.
-    // Measured +1.1 ... +2.1 % at 4 / 12 / 20 / 24 channels for a single utterance and -1.6 %
-    // when two utterances are in flight anyway (EXPERIMENTS round 6, item 8), hence the hint;
-    // not the default because overlapped launches no longer have durations of their own (the
-    // per-kernel table and the roofline of a profile are taken on one stream).  GSS_VARIANT
-    // wpe_halves=0 / 1 forces it off / on, wpe_halves=n (n > 1) puts 8 n frequencies into the
-    // first set.
-    const int halves = gss_variant("wpe_halves", ctx->utterances_in_flight == 1 ? 1 : 0);
-    if (p->wpe && halves > 0 && F >= 32 && p->wpe_iterations > 0) {
-        GSS_TRY(aux_stream_ready(ctx));
-        hipStream_t const main_stream = ctx->stream;
-        const int F0 = halves > 1 ? std::min(halves * 8, F - 8) : (F / 2 + 7) / 8 * 8, F1 = F - F0;
-        const size_t off = (size_t)F0 * T * D;
-        int st = wpe_run(ctx, Y, F0, T, D, p->wpe_taps, p->wpe_delay, p->wpe_iterations,
-                         p->wpe_psd_context, X, 0);
-        if (st == GSS_OK) {
-            GSS_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
-            ctx->stream = ctx->aux_stream;
-            st = wpe_run(ctx, Y + off, F1, T, D, p->wpe_taps, p->wpe_delay, p->wpe_iterations,
-                         p->wpe_psd_context, X + off, 1);
-            ctx->stream = main_stream;
-            // (joined even when the second part failed to enqueue: nothing may be left running
-            // on the internal stream when the call returns)
-            GSS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join, ctx->aux_stream));
-            GSS_HIP_CHECK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
-        }
-        GSS_TRY(st);
-        GSS_TRY(wpe_copy_zero_pivots(ctx));
+    const int A = wpe_arrays_of(p);
+    if (p->wpe && A == 1) {
+        GSS_TRY(pipeline_wpe(ctx, p, Y, F, T, D, X));
         ctx->arena_off = mark;
     } else if (p->wpe) {
-        GSS_TRY(wpe_run(ctx, Y, F, T, D, p->wpe_taps, p->wpe_delay, p->wpe_iterations,
-                        p->wpe_psd_context, X));
+        // per-array WPE: Y (F, T, A C) is regrouped into X's buffer as (F A, T, C), WPE writes
+        // (F A, T, C) into Y's buffer (Y is not read after this stage), and that is scattered
+        // back into X as (F, T, A C) for GSS and the beamformer
+        GSS_TRY(wpe_arrays_regroup_run(ctx, Y, F, T, A, D / A, true, X));
+        GSS_TRY(pipeline_wpe(ctx, p, X, F * A, T, D / A, Y));
+        GSS_TRY(wpe_arrays_regroup_run(ctx, Y, F, T, A, D / A, false, X));
         ctx->arena_off = mark;
     }
     GSS_TRY(activity_run(ctx, act, K, N_act, fading, actf));

@@ -238,10 +238,15 @@ int wpe_inverse_power_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, 
 // ctx->stream / ctx->aux_stream (gss_enhance_observation, GSS_VARIANT wpe_halves): part 0 zeroes
 // the pivot counter and records ctx->ev_fork behind it, neither part copies the count to the
 // host, each has its own correlation work queues.
+// array_bins > 0: the call is (part of) a per-array WPE stage over array_bins virtual bins of
+// one array each (picks the correlation geometry for the whole stage; 0 = joint WPE).
 int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int delay,
-            int iterations, int psd_context, cplx *X, int part = -1);
+            int iterations, int psd_context, cplx *X, int part = -1, int array_bins = 0);
 // the pivot count of the last wpe_run parts -> the context's status word (after the join)
 int wpe_copy_zero_pivots(gss_ctx *ctx);
+// per-array WPE: (F, T, A C) -> (F A, T, C) (to_arrays) or back; src and dst must not alias
+int wpe_arrays_regroup_run(gss_ctx *ctx, const cplx *src, int F, int64_t T, int A, int C,
+                           bool to_arrays, cplx *dst);
 // second stream + fork / join events of a context, created on first use
 int aux_stream_ready(gss_ctx *ctx);
 

@@ -1824,7 +1824,65 @@ __global__ void mfma_selftest_kernel(double *out) {
     }
 }
 
+// ------------------------------------------------------------------ per-array regroup
+// Per-array WPE (gss_params.wpe_arrays = A > 1) runs wpe_run on F A virtual bins of C = D / A
+// channels: (F, T, A C) <-> (F A, T, C).  One workgroup moves REGROUP_FRAMES frames of one
+// frequency.  On the (F, T, A C) side that tile is one contiguous run of frames * D elements,
+// on the (F A, T, C) side it is A contiguous runs of frames * C elements, so both sides are
+// read and written with consecutive 16-byte loads / stores from consecutive lanes; the
+// transposition in between goes through LDS (at most 32 x 32 x 16 B = 16 KB).
+constexpr int REGROUP_FRAMES = 32;
+constexpr int REGROUP_THREADS = 256;
+
+// to_arrays = true: src (F, T, A C) -> dst (F A, T, C); false: the inverse
+template <bool to_arrays>
+__global__ __launch_bounds__(REGROUP_THREADS) void wpe_arrays_regroup_kernel(
+    const cplx *__restrict__ src, int64_t T, int A, int C, cplx *__restrict__ dst) {
+    __shared__ cplx tile[REGROUP_FRAMES * GSS_MAX_CHANNELS];
+    const int D = A * C;
+    const int64_t f = blockIdx.y;
+    const int64_t t0 = (int64_t)blockIdx.x * REGROUP_FRAMES;
+    const int nt = (int)std::min<int64_t>(REGROUP_FRAMES, T - t0);
+    // the (F, T, D) side: frames t0 .. t0 + nt of frequency f, contiguous
+    const int64_t ftd0 = (f * T + t0) * D;
+    const int n_ftd = nt * D;
+    if (to_arrays) {
+        for (int k = threadIdx.x; k < n_ftd; k += REGROUP_THREADS) tile[k] = src[ftd0 + k];
+    } else {
+        for (int k = threadIdx.x; k < n_ftd; k += REGROUP_THREADS) {
+            const int a = k / (nt * C), r = k - a * nt * C;
+            const int t = r / C, c = r - t * C;
+            tile[t * D + a * C + c] = src[((f * A + a) * T + t0) * C + r];
+        }
+    }
+    __syncthreads();
+    if (to_arrays) {
+        for (int k = threadIdx.x; k < n_ftd; k += REGROUP_THREADS) {
+            const int a = k / (nt * C), r = k - a * nt * C;
+            const int t = r / C, c = r - t * C;
+            dst[((f * A + a) * T + t0) * C + r] = tile[t * D + a * C + c];
+        }
+    } else {
+        for (int k = threadIdx.x; k < n_ftd; k += REGROUP_THREADS) dst[ftd0 + k] = tile[k];
+    }
+}
+
 }  // namespace
+
+int wpe_arrays_regroup_run(gss_ctx *ctx, const cplx *src, int F, int64_t T, int A, int C,
+                           bool to_arrays, cplx *dst) {
+    GSS_REQUIRE(ctx, A * C <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED, "regroup: D=%d", A * C);
+    const dim3 grid((unsigned)((T + REGROUP_FRAMES - 1) / REGROUP_FRAMES), (unsigned)F);
+    GSS_PROF(ctx, "wpe_arrays_regroup");
+    if (to_arrays)
+        hipLaunchKernelGGL(wpe_arrays_regroup_kernel<true>, grid, dim3(REGROUP_THREADS), 0,
+                           ctx->stream, src, T, A, C, dst);
+    else
+        hipLaunchKernelGGL(wpe_arrays_regroup_kernel<false>, grid, dim3(REGROUP_THREADS), 0,
+                           ctx->stream, src, T, A, C, dst);
+    GSS_LAUNCH_CHECK(ctx, "wpe_arrays_regroup_kernel");
+    return GSS_OK;
+}
 
 static int corr_tiles(int n, int D, int c, int ct, std::vector<CorrTile> &tiles) {
     // R: every ct x ct tile that reaches the upper triangle; P: all rows x D columns.
@@ -1919,7 +1977,7 @@ int wpe_inverse_power_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, 
 }
 
 int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int delay,
-            int iterations, int psd_context, cplx *X, int part) {
+            int iterations, int psd_context, cplx *X, int part, int array_bins) {
     const int n = taps * D;
     const int c = delay + taps - 1;
     if (iterations == 0) {
@@ -2058,7 +2116,21 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
     // few channels, single-wave workgroups: the waves of a workgroup split the frames of one
     // sub-tile instead (wpe_corr_ksplit_kernel; GSS_VARIANT corr_ksplit=1: single waves)
     const int ksplit_forced = gss_variant("corr_ksplit", 0);
-    const int corr_ks = (corr_ts == 1 && corr_nw == 1 && ksplit_forced != 1)
+    // Per-array WPE (array_bins = F A virtual bins in the whole stage, of which this call may be
+    // one part): the frame split exists because one array's 513 x 6 = 3078 single waves do not
+    // fill the 4096 wave slots of 1024 SIMDs.  Over F A bins there are many more; once they are
+    // four or more rounds of those slots single waves win: config 2 per array (3078 bins, 6
+    // sub-tiles = 18468 waves) 1.49 ms per launch against 1.54 for the split; at 2 channels
+    // (3 sub-tiles = 9234 waves) the split stays (T = 7503: 6.30 ms against 6.68 for single
+    // waves; T = 941: the same).  The choice depends on the stage, not on the part, so that the
+    // two sets of bins of the pipeline take the same arithmetic as one call.  Joint WPE keeps
+    // the split at every size (array_bins = 0: its bits are not changed by this rule).
+    int cus = 0;
+    if (array_bins > 0)
+        GSS_HIP_CHECK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const bool arrays_single_waves = array_bins > 0 && (int64_t)ntiles * array_bins >= 4LL * 16 * cus;
+    const bool corr_split = ksplit_forced ? ksplit_forced != 1 : !arrays_single_waves;
+    const int corr_ks = (corr_ts == 1 && corr_nw == 1 && corr_split)
                             ? (ksplit_forced == 2 ? 2 : 4) : 1;      // (8: 0.687 vs 0.667 ms per utterance)
     using corr_fn_t = void (*)(const cplx *, const double *, int, int64_t, int, int, int, int,
                                const CorrTile *, int, cplx *, cplx *);

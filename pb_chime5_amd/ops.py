@@ -180,6 +180,37 @@ def wpe_dtf(Obs, taps=10, delay=2, iterations=3, psd_context=0, *, ctx=None):
     return _ftd_to_host_dtf(ctx, X_d, D, T, F)
 
 
+def wpe_arrays_dtf(Obs, arrays, taps=10, delay=2, iterations=3, psd_context=0, *, ctx=None):
+    """WPE per microphone array on the reference's (A*C, T, F) layout: the ``arrays`` groups
+    of C = D / arrays consecutive channels (array-major, the morph('ACN->A*CN') order of
+    enhance_example) are dereverberated independently, in ONE device call (gss_wpe_arrays) --
+    ``WPE.__call__(Obs.reshape(A, C, T, F), stack=False).reshape(A * C, T, F)``."""
+    psd_context = check_psd_context(psd_context)
+    ctx = ctx or default_context()
+    D = np.shape(Obs)[0]
+    A = check_wpe_arrays(arrays, D)
+    Y_d, (D, T, F) = _obs_to_device_ftd(ctx, Obs)
+    X_d = ctx.empty(16 * F * T * D)
+    ctx._check(ctx.lib.gss_wpe_arrays(ctx.handle, c_void_p(Y_d.ptr), F, T, A, D // A, int(taps),
+                                      int(delay), int(iterations), int(psd_context),
+                                      c_void_p(X_d.ptr)), 'gss_wpe_arrays')
+    return _ftd_to_host_dtf(ctx, X_d, D, T, F)
+
+
+def check_wpe_arrays(arrays, num_channels=None):
+    """The number of microphone arrays of a per-array WPE (0, 1 or None: one joint WPE -> 1).
+    It must split ``num_channels`` into arrays of equal size: ValueError otherwise."""
+    if arrays is None:
+        arrays = 0
+    if isinstance(arrays, bool) or not isinstance(arrays, (int, np.integer)) or arrays < 0:
+        raise ValueError(f'wpe_arrays={arrays!r}: a non-negative integer')
+    A = max(int(arrays), 1)
+    if num_channels is not None and num_channels % A:
+        raise ValueError(f'wpe_arrays={A} does not divide the {num_channels} channels into '
+                         'arrays of equal size')
+    return A
+
+
 def get_power_inverse(signal, psd_context=0, *, ctx=None):
     """nara_wpe.wpe.get_power_inverse: signal (F, D, T) -> (F, T), the weights of one WPE
     iteration (mean channel power, smoothed over [t - psd_context, t + psd_context], floored
@@ -323,7 +354,10 @@ def activity_time_to_frequency_device(time_activity, size, shift, fading, *, ctx
 def make_params(*, stft_size=1024, stft_shift=256, stft_fading=True, wpe=True, wpe_taps=10,
                 wpe_delay=2, wpe_iterations=3, wpe_psd_context=0, bss_iterations=20,
                 bss_iterations_post=1, bf_drop_context=True, bf='mvdrSouden_ban',
-                postfilter=None):
+                postfilter=None, wpe_arrays=0):
+    """gss_params.  ``wpe_arrays``: 0 or 1 = one joint WPE over all channels (the reference's
+    multiarray pipeline); A > 1 = WPE per microphone array, A arrays of D / A channels in
+    array-major order (checked against D when an utterance is enhanced)."""
     if bf not in _BF_CODES:
         raise NotImplementedError(bf)
     if postfilter not in _POSTFILTER_CODES:
@@ -334,20 +368,35 @@ def make_params(*, stft_size=1024, stft_shift=256, stft_fading=True, wpe=True, w
         wpe_iterations=wpe_iterations, bss_iterations=bss_iterations,
         bss_iterations_post=bss_iterations_post, bf_drop_context=int(bool(bf_drop_context)),
         bf=_BF_CODES[bf], postfilter=_POSTFILTER_CODES[postfilter],
-        wpe_psd_context=check_psd_context(wpe_psd_context))
+        wpe_psd_context=check_psd_context(wpe_psd_context),
+        wpe_arrays=check_wpe_arrays(wpe_arrays) and int(wpe_arrays or 0))
+
+
+def params_for(params, num_channels, wpe_arrays=None):
+    """``params`` for one utterance of ``num_channels`` channels with ``wpe_arrays`` microphone
+    arrays (None: as ``params`` says).  Raises ValueError when the arrays do not divide the
+    channels and WPE runs (without WPE the field is not read)."""
+    if wpe_arrays is None:
+        wpe_arrays = params.wpe_arrays
+    check_wpe_arrays(wpe_arrays, num_channels if params.wpe else None)
+    if int(wpe_arrays) == params.wpe_arrays:
+        return params
+    p = GssParams.from_buffer_copy(params)
+    p.wpe_arrays = int(wpe_arrays)
+    return p
 
 
 class ResidentUtterance:
     """An utterance whose inputs already sit in HBM (what bench.py times)."""
 
-    def __init__(self, ctx, obs, activity, params):
+    def __init__(self, ctx, obs, activity, params, wpe_arrays=None):
         obs = np.ascontiguousarray(obs, dtype=np.float64)
         act = np.ascontiguousarray((np.asarray(activity) != 0).astype(np.uint8))
         self.ctx = ctx
         self.D, self.N = obs.shape
         self.K = act.shape[0]
         self.N_act = act.shape[1]
-        self.params = params
+        self.params = params = params_for(params, self.D, wpe_arrays)
         self.T = stft_frames(self.N, params.stft_size, params.stft_shift,
                              params.stft_fading)
         self.n_out = int(ctx.lib.gss_istft_num_samples(
@@ -461,15 +510,19 @@ class UtterancePipeline:
             buf = self._bufs[slot][name] = self.slots[slot].empty(max(int(nbytes * 1.25), 16))
         return buf
 
-    def enqueue(self, tag, obs, activity, target_index, start_context, end_context):
+    def enqueue(self, tag, obs, activity, target_index, start_context, end_context,
+                wpe_arrays=None):
+        """``wpe_arrays``: microphone arrays of this utterance for a per-array WPE (None: as
+        the pipeline's params say)."""
         assert not self.full(), 'pop() the oldest utterance first'
-        slot = self._next
-        self._next = (self._next + 1) % len(self.slots)
-        ctx, p = self.slots[slot], self.params
         # int16 = PCM straight from the WAV files: converted on the device
         pcm = np.asarray(obs).dtype == np.int16
         obs = np.ascontiguousarray(obs, dtype=np.int16 if pcm else np.float64)
         act = np.ascontiguousarray((np.asarray(activity) != 0).astype(np.uint8))
+        p = params_for(self.params, obs.shape[0], wpe_arrays)
+        slot = self._next
+        self._next = (self._next + 1) % len(self.slots)
+        ctx = self.slots[slot]
         D, N = obs.shape
         K, N_act = act.shape
         T = stft_frames(N, p.stft_size, p.stft_shift, p.stft_fading)
@@ -494,15 +547,17 @@ class UtterancePipeline:
     def release_staging(self, staging):
         self._staging.put(staging)
 
-    def enqueue_staged(self, tag, staging, target_index, start_context, end_context, keep=None):
+    def enqueue_staged(self, tag, staging, target_index, start_context, end_context, keep=None,
+                       wpe_arrays=None):
         """Like enqueue() for inputs sitting in a HostStaging set: two asynchronous DMAs, the
         kernels behind them, and an asynchronous D2H of the samples ``keep = (a, b)`` of the
         result (default: all) into page-locked memory -- the host thread does not wait for any
         of it.  The set goes back to the free list when the utterance is popped."""
         assert not self.full(), 'pop() the oldest utterance first'
+        p = params_for(self.params, staging.obs.shape[0], wpe_arrays)
         slot = self._next
         self._next = (self._next + 1) % len(self.slots)
-        ctx, p = self.slots[slot], self.params
+        ctx = self.slots[slot]
         obs, act = staging.obs, staging.act
         D, N = obs.shape
         K, N_act = act.shape
@@ -593,15 +648,17 @@ class UtterancePipeline:
 
 def enhance_observation(obs, activity, target_index, start_context_samples,
                         end_context_samples, *, params=None, window=None, debug=False,
-                        ctx=None, **param_kwargs):
+                        ctx=None, wpe_arrays=None, **param_kwargs):
     """Fused per-utterance pipeline (core.py:514-571), intermediates resident in HBM.
 
     obs (D,N) float64, activity (K,N) bool in dict order.  Returns x_hat, or
     (x_hat, details) with ``debug=True`` where details holds the reference's
-    debug locals in the reference's layouts."""
-    ctx = ctx or default_context()
+    debug locals in the reference's layouts.  ``wpe_arrays`` = A > 1: WPE per microphone
+    array (A arrays of D / A channels, array-major) instead of one joint WPE."""
     if params is None:
         params = make_params(**param_kwargs)
+    params = params_for(params, np.shape(obs)[0], wpe_arrays)
+    ctx = ctx or default_context()
     _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
     utt = ResidentUtterance(ctx, obs, activity, params)
     D, K, T = utt.D, utt.K, utt.T

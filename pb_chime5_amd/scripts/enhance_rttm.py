@@ -28,6 +28,8 @@ def main(argv=None):
     ap.add_argument('--wpe-tabs', type=int, default=10)
     ap.add_argument('--wpe-delay', type=int, default=2)
     ap.add_argument('--wpe-iterations', type=int, default=3)
+    ap.add_argument('--wpe-per-array', action='store_true',
+                    help='WPE on each microphone array on its own (get_enhancer(wpe_per_array=True))')
     ap.add_argument('--bss-iterations', type=int, default=20)
     ap.add_argument('--bss-iterations-post', type=int, default=1)
     ap.add_argument('--bf', default='mvdrSouden_ban')
@@ -49,7 +51,7 @@ def main(argv=None):
         wpe_delay=args.wpe_delay, wpe_iterations=args.wpe_iterations,
         bss_iterations=args.bss_iterations, bss_iterations_post=args.bss_iterations_post,
         bf_drop_context=not args.no_bf_drop_context, bf=args.bf, postfilter=args.postfilter,
-        device_id=parallel.device_index())
+        device_id=parallel.device_index(), wpe_per_array=args.wpe_per_array)
     if parallel.is_master():
         Path(args.out).mkdir(parents=True, exist_ok=True)
     parallel.barrier()
