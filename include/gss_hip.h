@@ -68,8 +68,13 @@ typedef enum {
 /* ABI revision of this header.  Bumped whenever an entry point changes its argument list
  * or a struct its layout (round 2 added `psd_context` to gss_wpe and `wpe_psd_context` to
  * gss_params: revision 2; rounds 3, 4 and 5 added entry points only: revisions 3, 4, 5;
- * revision 7 appended `wpe_arrays` to gss_params and added gss_wpe_arrays).  A binder compares
- * gss_abi_version() with the GSS_ABI_VERSION it was written against before any other call. */
+ * revision 7 appended `wpe_arrays` to gss_params and added gss_wpe_arrays).  The entry points
+ * gss_enhance_observation_targets(_pcm16) and gss_last_ref_channels came later and, unlike the
+ * additions of rounds 3 - 5, did not bump the revision: revision 7 is pinned by the test suite
+ * of the per-array WPE.  A library of revision 7 may therefore lack them; the Python binding
+ * checks for every symbol it declares and asks for a rebuild when one is missing.  A binder
+ * compares gss_abi_version() with the GSS_ABI_VERSION it was written against before any other
+ * call (and, for these three, looks the symbols up). */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -235,6 +240,13 @@ int gss_mvdr_souden_ref(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, i
  * INT32_MIN: no beamformer has run yet. */
 int gss_last_ref_channel(gss_ctx *ctx, int32_t *ref_channel_host);
 
+/* Status words of the S targets of the last gss_enhance_observation_targets* call (same codes
+ * as gss_last_ref_channel, target order; synchronises the stream).  S larger than that call's
+ * number of targets is GSS_ERR_INVALID.  After any other beamformer run, after a targets call
+ * with bf 'ch2' / 'sum' (no beamformer, no status) and after one that failed before its
+ * beamformer, only S = 1 is accepted and gives gss_last_ref_channel's word. */
+int gss_last_ref_channels(gss_ctx *ctx, int32_t *ref_channels_host, int S);
+
 /* Number of pivots the WPE solve of the last gss_wpe / fused call on this context zeroed
  * (summed over its iterations and frequencies; synchronises the stream).  The normal
  * equations are solved by Cholesky; a non-positive pivot zeroes that row, which is the
@@ -288,7 +300,10 @@ typedef struct {
 
 /* Optional taps into the pipeline's intermediates (device pointers; any may be
  * NULL).  This is the `debug=True` contract of the reference blocks
- * (core.py:85-86,210-212,275-276,568-569). */
+ * (core.py:85-86,210-212,275-276,568-569).  In a gss_enhance_observation_targets* call
+ * Obs_ftd, act_frames and gamma are as below; target_mask, distortion_mask, Xhat and
+ * ref_channel hold S consecutive per-target blocks of the shape given below ((S,F,T), (S,F,T),
+ * (S,T,F), (S,)). */
 typedef struct {
     gss_cplx *Obs_ftd;        /* (F,T,D) after WPE                             */
     uint8_t *act_frames;      /* (K,T), the first T frames of the activity     */
@@ -326,6 +341,33 @@ int gss_enhance_observation_pcm16(gss_ctx *ctx, const gss_params *params,
                                   int64_t start_context_samples,
                                   int64_t end_context_samples,
                                   double *out_dev, const gss_debug_taps *taps);
+
+/* S targets of one window from one separation: STFT, WPE and the guided CACGMM run once, then
+ * the target-dependent tail (masks, PSD, beamformer, postfilter, iSTFT) for all S targets
+ * together.  target_index[s] in [0, K), distinct, 1 <= S <= K (host arrays);
+ * start/end_context_samples[s]: the contexts of target s (host arrays, as in
+ * gss_enhance_observation).  out (S, gss_istft_num_samples(T, ...)) row-major.  Row s equals
+ * gss_enhance_observation(..., target_index[s], start_context_samples[s],
+ * end_context_samples[s], ...) bit for bit, and so does each per-target block of the debug
+ * taps.  Bad S or indices (duplicates, out of range) give GSS_ERR_INVALID.  A target whose
+ * beamformer fails gets NaN (its status word says why, gss_last_ref_channels); the others
+ * finish.  gss_last_ref_channel afterwards reports target 0. */
+int gss_enhance_observation_targets(gss_ctx *ctx, const gss_params *params,
+                                    const double *obs_dev, int D, int64_t N,
+                                    const uint8_t *act_dev, int K, int64_t N_act, int S,
+                                    const int32_t *target_index,
+                                    const int64_t *start_context_samples,
+                                    const int64_t *end_context_samples, double *out_dev,
+                                    const gss_debug_taps *taps);
+
+/* The same fed with 16-bit PCM, as gss_enhance_observation_pcm16. */
+int gss_enhance_observation_targets_pcm16(gss_ctx *ctx, const gss_params *params,
+                                          const int16_t *obs_dev, int D, int64_t N,
+                                          const uint8_t *act_dev, int K, int64_t N_act, int S,
+                                          const int32_t *target_index,
+                                          const int64_t *start_context_samples,
+                                          const int64_t *end_context_samples, double *out_dev,
+                                          const gss_debug_taps *taps);
 
 /* Same, with host buffers: copies in, runs, copies out, synchronises. */
 int gss_enhance_observation_host(gss_ctx *ctx, const gss_params *params,

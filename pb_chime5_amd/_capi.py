@@ -105,6 +105,15 @@ SIGNATURES = {
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p,
                 ctypes.POINTER(GssDebugTaps)]),
+    'gss_enhance_observation_targets': (
+        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
+                c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                ctypes.POINTER(GssDebugTaps)]),
+    'gss_enhance_observation_targets_pcm16': (
+        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
+                c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                ctypes.POINTER(GssDebugTaps)]),
+    'gss_last_ref_channels': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), c_int]),
     'gss_enhance_observation_host': (
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p]),
@@ -137,6 +146,12 @@ def load_library(path=None):
         got = int(abi())
     if got != GSS_ABI_VERSION:
         raise GssError(f'{p}: ABI revision {got}, this binding needs {GSS_ABI_VERSION} '
+                       '(rebuild with `python -m pb_chime5_amd.build --force`)')
+    # (revision 7 gained entry points without a new revision number: a library built from an
+    # older tree passes the check above and lacks them)
+    missing = [name for name in SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise GssError(f'{p}: no {", ".join(missing)} in this build of revision {got} '
                        '(rebuild with `python -m pb_chime5_amd.build --force`)')
     for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)
@@ -334,6 +349,14 @@ class Context:
         self._check(self.lib.gss_last_ref_channel(self.handle, ctypes.byref(out)),
                     'gss_last_ref_channel')
         return int(out.value)
+
+    def last_ref_channels(self, S):
+        """Status words of the S targets of the last targets call (synchronises): the reference
+        channel of each, or the codes of `last_ref_channel`."""
+        out = (ctypes.c_int32 * int(S))()
+        self._check(self.lib.gss_last_ref_channels(self.handle, out, int(S)),
+                    'gss_last_ref_channels')
+        return [int(v) for v in out]
 
     def last_wpe_zero_pivots(self):
         """Pivots the WPE solve of the last call zeroed (synchronises); > 0 on live channels

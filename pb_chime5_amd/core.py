@@ -221,6 +221,16 @@ class Beamformer:
         return X_hat
 
 
+def _garbage_tracks(garbage_class):
+    """The activity keys ``Activity.garbage_class`` adds (activity._add_garbage): 'Noise' for
+    True / False, 'Noise0' ... for a positive int, none for None."""
+    if garbage_class is True or garbage_class is False:
+        return {'Noise'}
+    if garbage_class is None:
+        return set()
+    return {f'Noise{i}' for i in range(int(garbage_class))}
+
+
 @dataclass
 class Enhancer:
     """core.py:281-571."""
@@ -713,10 +723,91 @@ class Enhancer:
         self.enhance_observation_locals = locals()
         return x_hat
 
-    def _enhance_observation_blocks(self, obs, ex_array_activity, speaker_id, ex, debug,
-                                    wpe_arrays=1):
-        """Block-by-block path with the reference's control flow (one device
-        round trip per block); used when a block was swapped out."""
+    def speaker_ids_of(self, ex_array_activity, speaker_ids=None):
+        """The targets of `enhance_observation_speakers`: ``speaker_ids`` as a list, checked
+        against the activity keys, or (None) every key but the garbage tracks that
+        ``Activity.garbage_class`` adds.  ValueError for unknown, duplicate or no ids."""
+        keys = list(ex_array_activity.keys())
+        if speaker_ids is None:
+            garbage = _garbage_tracks(getattr(self.activity, 'garbage_class', True))
+            speaker_ids = [k for k in keys if k not in garbage]
+        else:
+            speaker_ids = list(speaker_ids)
+        if not speaker_ids:
+            raise ValueError('no speaker to enhance')
+        unknown = [s for s in speaker_ids if s not in ex_array_activity]
+        if unknown:
+            raise ValueError(f'speaker ids {unknown!r} are not in the activity ({keys!r})')
+        if len(set(speaker_ids)) != len(speaker_ids):
+            raise ValueError(f'speaker ids {speaker_ids!r} name a speaker twice')
+        return speaker_ids
+
+    def enhance_observation_speakers(self, obs, ex_array_activity, speaker_ids=None, ex=None,
+                                     debug=False, fused=None, wpe_arrays=None):
+        """Several speakers of one window from ONE separation: returns dict speaker_id -> x_hat
+        (N',) in the order of ``speaker_ids`` (None: every speaker of the activity, the
+        garbage tracks left out), each what `enhance_observation` returns for that speaker.
+        STFT, WPE and GSS run once; the fused path runs the target-dependent tail of all
+        speakers together (gss_enhance_observation_targets), the block path calls
+        ``bf_block`` and the iSTFT once per speaker."""
+        speaker_ids = self.speaker_ids_of(ex_array_activity, speaker_ids)
+        if wpe_arrays is None:
+            wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
+        wpe_arrays = ops.check_wpe_arrays(wpe_arrays, np.shape(obs)[0])
+        if fused is None:
+            fused = self._fusable()
+        if not fused:
+            return self._enhance_speakers_blocks(obs, ex_array_activity, speaker_ids, ex, debug,
+                                                 wpe_arrays)
+        keys = tuple(ex_array_activity.keys())
+        targets = [keys.index(s) for s in speaker_ids]
+        activity = np.array(list(ex_array_activity.values()))
+        start_ctx = end_ctx = 0
+        if self.bf_drop_context:
+            start_ctx, end_ctx = start_end_context_samples(ex)
+        params = self._params()
+        ctx = self._ctx()
+        ctx.set_utterances_in_flight(1)
+        try:
+            res = ops.enhance_observation_targets(
+                obs, activity, targets, start_ctx, end_ctx, params=params, debug=debug, ctx=ctx,
+                wpe_arrays=wpe_arrays, target_names=speaker_ids)
+        finally:
+            ctx.set_utterances_in_flight(0)
+        x_hat = res[0] if debug else res
+        if debug:
+            self.enhance_observation_speakers_locals = dict(details=res[1],
+                                                            speaker_ids=speaker_ids)
+        return dict(zip(speaker_ids, x_hat))
+
+    def enhance_example_speakers(self, ex, speaker_ids=None):
+        """`enhance_example` for several speakers of the example's window at once: dict
+        speaker_id -> x_hat, each trimmed like `enhance_example` trims its output."""
+        obs, ex_array_activity, _ = self._prepare_example(ex)
+        out = self.enhance_observation_speakers(obs, ex_array_activity, speaker_ids, ex=ex)
+        return {k: self._trim_context(v, ex) for k, v in out.items()}
+
+    def _enhance_speakers_blocks(self, obs, ex_array_activity, speaker_ids, ex, debug,
+                                 wpe_arrays=1):
+        """Block path of `enhance_observation_speakers`: one STFT / WPE / GSS, then the masks,
+        ``bf_block`` and the iSTFT per speaker (`_enhance_observation_blocks` for each)."""
+        Obs, acitivity_freq, masks, _ = self._blocks_front(obs, ex_array_activity, ex, debug,
+                                                           wpe_arrays)
+        keys = tuple(ex_array_activity.keys())
+        out = {}
+        for speaker_id in speaker_ids:
+            target_speaker_index = keys.index(speaker_id)
+            target_mask = masks[target_speaker_index]
+            distortion_mask = np.sum(np.delete(masks, target_speaker_index, axis=0), axis=0)
+            X_hat = self.bf_block(Obs, target_mask=target_mask,
+                                  distortion_mask=distortion_mask, debug=debug)
+            out[speaker_id] = self.istft(X_hat)
+        return out
+
+    def _blocks_front(self, obs, ex_array_activity, ex, debug, wpe_arrays):
+        """The target-independent blocks of the block path: STFT, WPE (joint or per array),
+        activity, GSS and the zeroed context frames.  Returns Obs, acitivity_freq, masks and
+        (start_context_frames, end_context_frames) or None without bf_drop_context."""
         Obs = self.stft(obs)
         if self.wpe_block is not None and wpe_arrays > 1:
             _A = wpe_arrays
@@ -737,6 +828,17 @@ class Enhancer:
             masks[:, :start_context_frames, :] = 0
             if end_context_frames > 0:
                 masks[:, -end_context_frames:, :] = 0
+            return Obs, acitivity_freq, masks, (start_context_frames, end_context_frames)
+        return Obs, acitivity_freq, masks, None
+
+    def _enhance_observation_blocks(self, obs, ex_array_activity, speaker_id, ex, debug,
+                                    wpe_arrays=1):
+        """Block-by-block path with the reference's control flow (one device
+        round trip per block); used when a block was swapped out."""
+        Obs, acitivity_freq, masks, context_frames = self._blocks_front(
+            obs, ex_array_activity, ex, debug, wpe_arrays)
+        if context_frames is not None:
+            start_context_frames, end_context_frames = context_frames
         target_speaker_index = tuple(ex_array_activity.keys()).index(speaker_id)
         target_mask = masks[target_speaker_index]
         distortion_mask = np.sum(np.delete(masks, target_speaker_index, axis=0), axis=0)

@@ -613,6 +613,10 @@ __global__ __launch_bounds__(256) void wcov_kernel(const cplx *__restrict__ Y,
     } else if (!xcd_group_map(nch, F, f, chunk)) {
         return;
     }
+    // (psd_partials_run for S targets: blockIdx.y = target, its own (F, Ktot, T) weights and
+    // (F, nch, Ktot, NE) partials; every other launch has one row of workgroups)
+    W += (int64_t)blockIdx.y * F * Ktot * T;
+    part += (int64_t)blockIdx.y * F * nch * Ktot * NE;
     const int tid = threadIdx.x;
     const int tl = tid & 63, g = tid >> 6;
 #ifdef GSS_WCOV_TRACE
@@ -2139,16 +2143,17 @@ EmStrides em_strides(const EmBlockPlan &p, int F, int64_t T, int D) {
 }  // namespace
 
 // PSD accumulation of the beamformer: same kernel, raw observations, two masks.
-// W = (F, 2, T) [target, distortion]; part = (F, nch, 2, NE).
+// W = (F, 2, T) [target, distortion]; part = (F, nch, 2, NE).  S targets: S such blocks of
+// each, a second grid dimension over them (the two-row pass of one target, unchanged).
 int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,
-                     int nch, int chunk_frames, cplx *part) {
+                     int nch, int chunk_frames, cplx *part, int S) {
     const size_t lds = wcov_lds_layout(D, 2).total;
     // (the tile pass of the (F, T, D) layout with exactly as many slots as the channel count needs)
     const wcov_fn_t fn = D <= 4 ? wcov_kernel<2, false, false, false, 1>
                          : D <= 12 ? wcov_kernel<2, false, false, false, 3>
                          : D <= 24 ? wcov_kernel<2, false, false, false, 6> : wcov_kernel<2, false, false>;
     GSS_TRY(raise_lds_limit(ctx, fn, lds));
-    hipLaunchKernelGGL(fn, dim3(xcd_grid(nch, F)), dim3(256), lds,
+    hipLaunchKernelGGL(fn, dim3(xcd_grid(nch, F), S), dim3(256), lds,
                        ctx->stream, Y, W2, F, T, D, tri_count(D), nch, chunk_frames, part, 2, 0,
                        MsegPlan{});
     GSS_LAUNCH_CHECK(ctx, "wcov_kernel");
@@ -2170,6 +2175,7 @@ size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K) {
     b += align_up(sizeof(cplx) * (size_t)F * D * T);             // Yn (register-form E-step)
     b += align_up(sizeof(double) * (size_t)F * st.reg_nch * K);  // Sg of the register-form E-step
     b += align_up(sizeof(cplx) * (size_t)F * K * 16);            // em_onchip4: warm-start eigenvectors (D = 4)
+    b += align_up(sizeof(int) * (size_t)F * ((T + EM_TILE - 1) / EM_TILE));   // zero_tiles
     return b + 4096;
 }
 

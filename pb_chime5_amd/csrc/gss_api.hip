@@ -170,7 +170,8 @@ extern "C" int gss_create(int device_id, gss_ctx **out) {
         return GSS_ERR_HIP;
     }
     ctx->stream = ctx->own_stream;
-    e = hipHostMalloc(reinterpret_cast<void **>(&ctx->status_host), 64, hipHostMallocMapped);
+    e = hipHostMalloc(reinterpret_cast<void **>(&ctx->status_host), GSS_STATUS_BYTES,
+                      hipHostMallocMapped);
     if (e == hipSuccess)
         e = hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->status_dev), ctx->status_host, 0);
     if (e != hipSuccess) {
@@ -678,6 +679,19 @@ extern "C" int gss_last_ref_channel(gss_ctx *ctx, int32_t *ref_channel) {
     return GSS_OK;
 }
 
+extern "C" int gss_last_ref_channels(gss_ctx *ctx, int32_t *ref_channels, int S) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, ref_channels, GSS_ERR_INVALID, "gss_last_ref_channels: NULL");
+    const int have = ctx->last_targets > 0 ? ctx->last_targets : 1;
+    GSS_REQUIRE(ctx, S >= 1 && S <= have, GSS_ERR_INVALID,
+                "gss_last_ref_channels: S=%d, the last beamformer run had %d target(s)", S, have);
+    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    const int32_t *words = ctx->last_targets > 0 ? ctx->status_host + GSS_STATUS_TARGETS
+                                                 : ctx->status_host;
+    for (int s = 0; s < S; ++s) ref_channels[s] = __atomic_load_n(words + s, __ATOMIC_ACQUIRE);
+    return GSS_OK;
+}
+
 extern "C" int gss_last_wpe_zero_pivots(gss_ctx *ctx, int64_t *count) {
     GSS_ENTER(ctx);
     GSS_REQUIRE(ctx, count, GSS_ERR_INVALID, "gss_last_wpe_zero_pivots: NULL");
@@ -767,42 +781,68 @@ static int pipeline_wpe(gss_ctx *ctx, const gss_params *p, const cplx *Y, int Fv
     return wpe_copy_zero_pivots(ctx);
 }
 
-static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
-                                 int K) {
-    const int A = wpe_arrays_of(p);
+// Workspace of the pipeline's front (STFT, WPE, activity, EM): its buffers (Y, X, frame
+// activity, gamma) and the largest stage workspace it needs on top of them.
+static size_t front_buffer_bytes(int F, int64_t T, int64_t T_act, int D, int K) {
     size_t b = 0;
     size_t ftd = align_up(sizeof(cplx) * (size_t)F * T * D);
     b += 2 * ftd;                                            // Y, X
     b += align_up((size_t)K * T_act);                        // frame activity
     b += align_up(sizeof(double) * (size_t)F * K * T);       // gamma
-    b += 2 * align_up(sizeof(double) * (size_t)F * T);       // masks
-    b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
-    b += 4096;
+    return b;
+}
+
+static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, int K) {
+    const int A = wpe_arrays_of(p);
     size_t stage = 0;
     // (per-array WPE: R is F A (C taps)^2, C = D / A)
     if (p->wpe)
         stage = std::max(stage, wpe_workspace_bytes(F * A, T, D / A, p->wpe_taps, p->wpe_delay) + (1 << 16));
     stage = std::max(stage, cacgmm_workspace_bytes(F, T, D, K));
+    return stage;
+}
+
+static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
+                                 int K) {
+    size_t b = front_buffer_bytes(F, T, T_act, D, K);
+    b += 2 * align_up(sizeof(double) * (size_t)F * T);       // masks
+    b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
+    b += 4096;
+    size_t stage = front_stage_bytes(p, F, T, D, K);
     stage = std::max(stage, mvdr_workspace_bytes(F, T, D));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
     return b + stage + (1 << 16);
 }
 
-static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const void *obs,
-                                    int obs_type, int D, int64_t N, const uint8_t *act, int K,
-                                    int64_t N_act, int target, int64_t start_ctx, int64_t end_ctx,
-                                    double *out, const gss_debug_taps *taps) {
+// The same with the tail of S targets: masks, Xhat and the beamformer's intermediates S times,
+// S iSTFT frame buffers, one channel-picked X_hat ('ch2' / 'sum').
+static size_t targets_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
+                                int K, int S) {
+    size_t b = front_buffer_bytes(F, T, T_act, D, K);
+    b += 2 * align_up(sizeof(double) * (size_t)S * F * T);   // masks
+    b += align_up(sizeof(cplx) * (size_t)S * F * T);         // Xhat
+    b += align_up(sizeof(int32_t) * 4 * (size_t)S);          // ref
+    b += 4096;
+    size_t stage = front_stage_bytes(p, F, T, D, K);
+    stage = std::max(stage, mvdr_workspace_bytes(F, T, D, S));
+    stage = std::max(stage, align_up(sizeof(cplx) * (size_t)F * T) + 4096);
+    stage = std::max(stage, stft_workspace_bytes((int64_t)S * T, p->stft_size));
+    return b + stage + (1 << 16);
+}
+
+// Checks of the fused pipeline that do not depend on the target(s): before ...
+static int check_pipeline_front(gss_ctx *ctx, const gss_params *p, const void *obs, int D,
+                                int64_t N, const uint8_t *act, const void *out, const char *what) {
     GSS_TRY(check_windows(ctx));
     GSS_TRY(check_params(ctx, p));
-    GSS_REQUIRE(ctx, obs && act && out && N >= 1, GSS_ERR_INVALID,
-                "gss_enhance_observation: bad arguments");
+    GSS_REQUIRE(ctx, obs && act && out && N >= 1, GSS_ERR_INVALID, "%s: bad arguments", what);
     GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED, "D=%d", D);
-    GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
-                "target_index %d outside [0, %d)", target, K);
-    // core.py:221-222
-    GSS_REQUIRE(ctx, start_ctx >= 0 && end_ctx >= 0, GSS_ERR_INVALID,
-                "assert context samples >= 0 failed: %lld %lld", (long long)start_ctx,
-                (long long)end_ctx);
+    return GSS_OK;
+}
+
+// ... and after those of the targets; the frame counts T, T_act of the window.
+static int check_pipeline_rest(gss_ctx *ctx, const gss_params *p, int D, int64_t N, int K,
+                               int64_t N_act, int64_t *T_out, int64_t *T_act_out) {
     GSS_TRY(check_cacgmm_args(ctx, D, K, p->bss_iterations, p->bss_iterations_post));
     if (p->wpe) GSS_TRY(check_wpe_arrays(ctx, p, D));   // (no WPE: the field is not read)
     if (p->bf == 0 || p->bf == 3)
@@ -823,20 +863,36 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
                 "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
                 "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
-    GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K)));
-    cplx *Y = arena_alloc_t<cplx>(ctx, (size_t)F * T * D);
-    cplx *X = p->wpe ? arena_alloc_t<cplx>(ctx, (size_t)F * T * D) : Y;
-    uint8_t *actf = arena_alloc_t<uint8_t>(ctx, (size_t)K * T_act);
-    double *gamma = arena_alloc_t<double>(ctx, (size_t)F * K * T);
-    double *mx = arena_alloc_t<double>(ctx, (size_t)F * T);
-    double *mn = arena_alloc_t<double>(ctx, (size_t)F * T);
-    cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)F * T);
-    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);
-    GSS_REQUIRE(ctx, Y && X && actf && gamma && mx && mn && Xhat && ref, GSS_ERR_NOMEM,
-                "workspace sizing bug");
-    const size_t mark = ctx->arena_off;
+    *T_out = T;
+    *T_act_out = T_act;
+    return GSS_OK;
+}
 
-    GSS_TRY(stft_run(ctx, obs, obs_type, D, N, fading, Y));
+// The pipeline's buffers that outlive the front; allocated first from the reserved arena.
+struct PipelineFront {
+    cplx *Y, *X;
+    uint8_t *actf;
+    double *gamma;
+};
+
+static int alloc_front(gss_ctx *ctx, const gss_params *p, int F, int64_t T, int64_t T_act, int D,
+                       int K, PipelineFront *fr) {
+    fr->Y = arena_alloc_t<cplx>(ctx, (size_t)F * T * D);
+    fr->X = p->wpe ? arena_alloc_t<cplx>(ctx, (size_t)F * T * D) : fr->Y;
+    fr->actf = arena_alloc_t<uint8_t>(ctx, (size_t)K * T_act);
+    fr->gamma = arena_alloc_t<double>(ctx, (size_t)F * K * T);
+    GSS_REQUIRE(ctx, fr->Y && fr->X && fr->actf && fr->gamma, GSS_ERR_NOMEM, "workspace sizing bug");
+    return GSS_OK;
+}
+
+// STFT, WPE (joint or per array), frame activity and the guided CACGMM of one window: obs ->
+// X (F,T,D) and gamma (F,K,T), nothing of it depending on a target.  Stage workspace above
+// `mark` is released after each stage.
+static int run_front(gss_ctx *ctx, const gss_params *p, const void *obs, int obs_type, int D,
+                     int64_t N, const uint8_t *act, int K, int64_t N_act, int F, int64_t T,
+                     int64_t T_act, const PipelineFront &fr, size_t mark) {
+    cplx *const Y = fr.Y, *const X = fr.X;
+    GSS_TRY(stft_run(ctx, obs, obs_type, D, N, p->stft_fading, Y));
     if (!p->wpe)    // no solve in this call: clear the count an earlier utterance left behind
         GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + 2, 0, sizeof(int32_t), ctx->stream));
     const int A = wpe_arrays_of(p);
@@ -852,17 +908,65 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
         GSS_TRY(wpe_arrays_regroup_run(ctx, Y, F, T, A, D / A, false, X));
         ctx->arena_off = mark;
     }
-    GSS_TRY(activity_run(ctx, act, K, N_act, fading, actf));
-    GSS_TRY(cacgmm_run(ctx, X, F, T, D, actf, T_act, K, p->bss_iterations, p->bss_iterations_post,
-                       gamma));
+    GSS_TRY(activity_run(ctx, act, K, N_act, p->stft_fading, fr.actf));
+    GSS_TRY(cacgmm_run(ctx, X, F, T, D, fr.actf, T_act, K, p->bss_iterations,
+                       p->bss_iterations_post, fr.gamma));
     ctx->arena_off = mark;
+    return GSS_OK;
+}
+
+static int copy_tap(gss_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    if (!dst) return GSS_OK;
+    GSS_HIP_CHECK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return GSS_OK;
+}
+
+// The front's debug taps: Obs_ftd, act_frames, gamma
+static int copy_front_taps(gss_ctx *ctx, const gss_debug_taps *taps, const PipelineFront &fr,
+                           int F, int64_t T, int64_t T_act, int D, int K) {
+    GSS_TRY(copy_tap(ctx, taps->Obs_ftd, fr.X, sizeof(cplx) * (size_t)F * T * D));
+    if (taps->act_frames)
+        GSS_HIP_CHECK(ctx, hipMemcpy2DAsync(taps->act_frames, (size_t)T, fr.actf, (size_t)T_act,
+                                            (size_t)T, (size_t)K, hipMemcpyDeviceToDevice,
+                                            ctx->stream));
+    GSS_TRY(copy_tap(ctx, taps->gamma, fr.gamma, sizeof(double) * (size_t)F * K * T));
+    return GSS_OK;
+}
+
+static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const void *obs,
+                                    int obs_type, int D, int64_t N, const uint8_t *act, int K,
+                                    int64_t N_act, int target, int64_t start_ctx, int64_t end_ctx,
+                                    double *out, const gss_debug_taps *taps) {
+    GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, act, out, "gss_enhance_observation"));
+    GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
+                "target_index %d outside [0, %d)", target, K);
+    // core.py:221-222
+    GSS_REQUIRE(ctx, start_ctx >= 0 && end_ctx >= 0, GSS_ERR_INVALID,
+                "assert context samples >= 0 failed: %lld %lld", (long long)start_ctx,
+                (long long)end_ctx);
+    int64_t T, T_act;
+    GSS_TRY(check_pipeline_rest(ctx, p, D, N, K, N_act, &T, &T_act));
+    const int size = p->stft_size, shift = p->stft_shift, fading = p->stft_fading;
+    const int F = size / 2 + 1;
+
+    GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K)));
+    PipelineFront fr;
+    GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
+    double *mx = arena_alloc_t<double>(ctx, (size_t)F * T);
+    double *mn = arena_alloc_t<double>(ctx, (size_t)F * T);
+    cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)F * T);
+    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);
+    GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
+    const size_t mark = ctx->arena_off;
+    GSS_TRY(run_front(ctx, p, obs, obs_type, D, N, act, K, N_act, F, T, T_act, fr, mark));
+    cplx *const X = fr.X;
 
     int64_t sf = 0, ef = 0;
     if (p->bf_drop_context) {
         sf = gss_samples_to_stft_frames(start_ctx, size, shift, fading);
         ef = gss_samples_to_stft_frames(end_ctx, size, shift, fading);
     }
-    GSS_TRY(masks_from_posteriors_run(ctx, gamma, F, K, T, target, p->bf_drop_context, sf, ef,
+    GSS_TRY(masks_from_posteriors_run(ctx, fr.gamma, F, K, T, target, p->bf_drop_context, sf, ef,
                                       mx, mn));
     if (p->bf == 0 || p->bf == 3) {
         GSS_TRY(mvdr_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, Xhat, ref, /*gev=*/p->bf == 3));
@@ -874,22 +978,98 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     GSS_TRY(istft_run(ctx, Xhat, T, fading, out));
 
     if (taps) {
-        auto cp = [&](void *dst, const void *src, size_t bytes) -> int {
-            if (!dst) return GSS_OK;
-            GSS_HIP_CHECK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice,
-                                              ctx->stream));
-            return GSS_OK;
-        };
-        GSS_TRY(cp(taps->Obs_ftd, X, sizeof(cplx) * (size_t)F * T * D));
-        if (taps->act_frames)
-            GSS_HIP_CHECK(ctx, hipMemcpy2DAsync(taps->act_frames, (size_t)T, actf, (size_t)T_act,
-                                                (size_t)T, (size_t)K, hipMemcpyDeviceToDevice,
-                                                ctx->stream));
-        GSS_TRY(cp(taps->gamma, gamma, sizeof(double) * (size_t)F * K * T));
-        GSS_TRY(cp(taps->target_mask, mx, sizeof(double) * (size_t)F * T));
-        GSS_TRY(cp(taps->distortion_mask, mn, sizeof(double) * (size_t)F * T));
-        GSS_TRY(cp(taps->Xhat, Xhat, sizeof(cplx) * (size_t)F * T));
-        if (p->bf == 0 || p->bf == 3) GSS_TRY(cp(taps->ref_channel, ref, sizeof(int32_t)));
+        GSS_TRY(copy_front_taps(ctx, taps, fr, F, T, T_act, D, K));
+        GSS_TRY(copy_tap(ctx, taps->target_mask, mx, sizeof(double) * (size_t)F * T));
+        GSS_TRY(copy_tap(ctx, taps->distortion_mask, mn, sizeof(double) * (size_t)F * T));
+        GSS_TRY(copy_tap(ctx, taps->Xhat, Xhat, sizeof(cplx) * (size_t)F * T));
+        if (p->bf == 0 || p->bf == 3) GSS_TRY(copy_tap(ctx, taps->ref_channel, ref, sizeof(int32_t)));
+    }
+    return GSS_OK;
+}
+
+// S targets of one window: the front once, then the target-dependent tail for all S targets
+// together -- masks, PSD, solve, reference channel, apply, postfilter and iSTFT each one launch
+// over S per-target blocks.  Row s of `out` and of every per-target tap is what
+// enhance_observation_impl gives for target_index[s] with that target's contexts.
+static int enhance_observation_targets_impl(gss_ctx *ctx, const gss_params *p, const void *obs,
+                                            int obs_type, int D, int64_t N, const uint8_t *act,
+                                            int K, int64_t N_act, int S, const int32_t *targets,
+                                            const int64_t *start_ctx, const int64_t *end_ctx,
+                                            double *out, const gss_debug_taps *taps) {
+    // (the status words of this call: none until its beamformer runs -- a call that fails before
+    // it, or a 'ch2' / 'sum' call, leaves no per-target words behind)
+    ctx->last_targets = 0;
+    GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, act, out, "gss_enhance_observation_targets"));
+    GSS_REQUIRE(ctx, targets && start_ctx && end_ctx, GSS_ERR_INVALID,
+                "gss_enhance_observation_targets: NULL target or context array");
+    // (K bounded before the indices are used as bit positions below)
+    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_MAX_CLASSES, GSS_ERR_INVALID,
+                "cacgmm: assert 1 <= K < 20 failed: K=%d", K);
+    GSS_REQUIRE(ctx, S >= 1 && S <= K, GSS_ERR_INVALID,
+                "%d targets of %d classes: need 1 <= S <= K", S, K);
+    uint32_t seen = 0;
+    for (int s = 0; s < S; ++s) {
+        GSS_REQUIRE(ctx, targets[s] >= 0 && targets[s] < K, GSS_ERR_INVALID,
+                    "target_index[%d] = %d outside [0, %d)", s, targets[s], K);
+        GSS_REQUIRE(ctx, !(seen >> targets[s] & 1u), GSS_ERR_INVALID,
+                    "target_index[%d] = %d is given twice", s, targets[s]);
+        seen |= 1u << targets[s];
+        GSS_REQUIRE(ctx, start_ctx[s] >= 0 && end_ctx[s] >= 0, GSS_ERR_INVALID,
+                    "assert context samples >= 0 failed: %lld %lld (target %d)",
+                    (long long)start_ctx[s], (long long)end_ctx[s], s);
+    }
+    int64_t T, T_act;
+    GSS_TRY(check_pipeline_rest(ctx, p, D, N, K, N_act, &T, &T_act));
+    const int size = p->stft_size, shift = p->stft_shift, fading = p->stft_fading;
+    const int F = size / 2 + 1;
+
+    GSS_TRY(arena_reserve(ctx, targets_workspace(p, F, T, T_act, D, K, S)));
+    PipelineFront fr;
+    GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
+    double *mx = arena_alloc_t<double>(ctx, (size_t)S * F * T);
+    double *mn = arena_alloc_t<double>(ctx, (size_t)S * F * T);
+    cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)S * F * T);
+    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4 * (size_t)S);
+    GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
+    const size_t mark = ctx->arena_off;
+    GSS_TRY(run_front(ctx, p, obs, obs_type, D, N, act, K, N_act, F, T, T_act, fr, mark));
+    cplx *const X = fr.X;
+
+    int64_t sf[GSS_MAX_CLASSES] = {}, ef[GSS_MAX_CLASSES] = {};
+    if (p->bf_drop_context) {
+        for (int s = 0; s < S; ++s) {
+            sf[s] = gss_samples_to_stft_frames(start_ctx[s], size, shift, fading);
+            ef[s] = gss_samples_to_stft_frames(end_ctx[s], size, shift, fading);
+        }
+    }
+    GSS_TRY(masks_targets_run(ctx, fr.gamma, F, K, T, S, targets, p->bf_drop_context, sf, ef, mx,
+                              mn));
+    const bool beamformer = p->bf == 0 || p->bf == 3;
+    if (beamformer) {
+        GSS_TRY(mvdr_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, Xhat, ref, /*gev=*/p->bf == 3,
+                         /*forced_ref=*/-1, S, /*targets=*/true));
+        ctx->arena_off = mark;
+        if (p->postfilter == 1)
+            GSS_TRY(mask_mul_targets_run(ctx, Xhat, (int64_t)F * T, Xhat, mx, F, T, S, 1));
+    } else {
+        // 'ch2' / 'sum' do not depend on the target: one X_hat, then each target's copy of it
+        // (times its mask with the postfilter)
+        cplx *X1 = arena_alloc_t<cplx>(ctx, (size_t)F * T);
+        GSS_REQUIRE(ctx, X1, GSS_ERR_NOMEM, "workspace sizing bug");
+        GSS_TRY(channel_pick_run(ctx, X, F, T, D, p->bf, X1));
+        GSS_TRY(mask_mul_targets_run(ctx, X1, 0, Xhat, mx, F, T, S, p->postfilter == 1));
+        ctx->arena_off = mark;
+    }
+    GSS_TRY(istft_run(ctx, Xhat, T, fading, out, S));
+
+    if (taps) {
+        GSS_TRY(copy_front_taps(ctx, taps, fr, F, T, T_act, D, K));
+        GSS_TRY(copy_tap(ctx, taps->target_mask, mx, sizeof(double) * (size_t)S * F * T));
+        GSS_TRY(copy_tap(ctx, taps->distortion_mask, mn, sizeof(double) * (size_t)S * F * T));
+        GSS_TRY(copy_tap(ctx, taps->Xhat, Xhat, sizeof(cplx) * (size_t)S * F * T));
+        if (beamformer && taps->ref_channel)
+            GSS_HIP_CHECK(ctx, hipMemcpyAsync(taps->ref_channel, ref, sizeof(int32_t) * S,
+                                              hipMemcpyDeviceToDevice, ctx->stream));
     }
     return GSS_OK;
 }
@@ -912,6 +1092,29 @@ extern "C" int gss_enhance_observation_pcm16(gss_ctx *ctx, const gss_params *p,
     GSS_ENTER_VARIANTS(ctx);
     return enhance_observation_impl(ctx, p, obs, 1, D, N, act, K, N_act, target, start_ctx, end_ctx,
                                     out, taps);
+}
+
+extern "C" int gss_enhance_observation_targets(gss_ctx *ctx, const gss_params *p,
+                                               const double *obs, int D, int64_t N,
+                                               const uint8_t *act, int K, int64_t N_act, int S,
+                                               const int32_t *targets, const int64_t *start_ctx,
+                                               const int64_t *end_ctx, double *out,
+                                               const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    return enhance_observation_targets_impl(ctx, p, obs, 0, D, N, act, K, N_act, S, targets,
+                                            start_ctx, end_ctx, out, taps);
+}
+
+extern "C" int gss_enhance_observation_targets_pcm16(gss_ctx *ctx, const gss_params *p,
+                                                     const int16_t *obs, int D, int64_t N,
+                                                     const uint8_t *act, int K, int64_t N_act,
+                                                     int S, const int32_t *targets,
+                                                     const int64_t *start_ctx,
+                                                     const int64_t *end_ctx, double *out,
+                                                     const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    return enhance_observation_targets_impl(ctx, p, obs, 1, D, N, act, K, N_act, S, targets,
+                                            start_ctx, end_ctx, out, taps);
 }
 
 extern "C" int gss_enhance_observation_host(gss_ctx *ctx, const gss_params *p,

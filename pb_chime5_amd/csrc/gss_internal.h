@@ -163,8 +163,11 @@ struct gss_ctx {
     // Status words (mapped host memory).  [0]: the last beamformed utterance, written by
     // mvdr_apply_kernel: the reference channel, -1 = non-finite SNR; INT32_MIN = none yet.
     // [2]: pivots zeroed by the last WPE call (copied from the device counter by wpe_run).
+    // [GSS_STATUS_TARGETS + s]: target s of the last targets call (mvdr_apply_targets_kernel,
+    // which writes target 0's word to [0] as well).
     int32_t *status_host = nullptr;
     int32_t *status_dev = nullptr;
+    int last_targets = 0;   // S of the last beamformer run when it was a targets call, else 0
 
     // WPE tile lists (device), rebuilt when (taps, delay, D) changes
     void *wpe_tiles = nullptr;
@@ -177,6 +180,9 @@ struct gss_ctx {
     std::map<std::string, std::pair<long, double>> prof_acc;
     std::string prof_filter;   // time only this kernel (empty: all)
 };
+
+#define GSS_STATUS_TARGETS 16                                    // first per-target word
+#define GSS_STATUS_BYTES (4 * (GSS_STATUS_TARGETS + GSS_MAX_CLASSES + 1))
 
 int gss_fail(gss_ctx *ctx, int code, const char *fmt, ...);
 
@@ -254,25 +260,44 @@ size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K);
 int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const uint8_t *act,
                int64_t act_stride, int K, int iterations, int iterations_post, double *gamma);
 
+// S > 1: S targets' weights (S, F, 2, T) -> partials (S, F, nch, 2, NE), one launch
 int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,
-                     int nch, int chunk_frames, cplx *part);
+                     int nch, int chunk_frames, cplx *part, int S = 1);
 
-size_t mvdr_workspace_bytes(int F, int64_t T, int D);
+size_t mvdr_workspace_bytes(int F, int64_t T, int D, int S = 1);
+// targets: the multi-target tail of gss_enhance_observation_targets -- masks (S,F,T) in,
+// Xhat (S,T,F) and ref_channel (S) out, the per-target status words of the context written
+// (the one-target path passes S = 1, targets = false and keeps its own kernels)
 int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
              const double *mn, int ban, cplx *Xhat, int32_t *ref_channel, int gev = 0,
-             int forced_ref = -1);
+             int forced_ref = -1, int S = 1, bool targets = false);
+// The targets of masks_targets_kernel (by value): target class and zeroed context frames
+struct TargetMaskArgs {
+    int S;
+    int target[GSS_MAX_CLASSES];
+    int64_t zero_lo_end[GSS_MAX_CLASSES], zero_hi_begin[GSS_MAX_CLASSES];
+};
+// gamma (F,K,T) -> mx, mn (S,F,T) for targets[s] with context frames sf[s] / ef[s] (host arrays)
+int masks_targets_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T, int S,
+                      const int32_t *targets, int drop, const int64_t *sf, const int64_t *ef,
+                      double *mx, double *mn);
 int masks_from_posteriors_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
                               int target, int drop, int64_t start_frames,
                               int64_t end_frames, double *mx, double *mn);
 
 size_t stft_workspace_bytes(int64_t T, int size);
 int stft_run(gss_ctx *ctx, const void *x, int in_type, int D, int64_t N, int fading, cplx *Y);
-int istft_run(gss_ctx *ctx, const cplx *X, int64_t T, int fading, double *x);
+// S signals: X (S,T,F) -> x (S, gss_istft_num_samples(T)), one launch per kernel
+int istft_run(gss_ctx *ctx, const cplx *X, int64_t T, int fading, double *x, int S = 1);
 int activity_run(gss_ctx *ctx, const uint8_t *act, int K, int64_t N, int fading,
                  uint8_t *out);
 int channel_pick_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int mode,
                      cplx *Xhat);  // mode 1: 'ch2', 2: 'sum'
 int mask_mul_run(gss_ctx *ctx, cplx *Xhat, const double *mask_ft, int F, int64_t T);
+// S targets: dst[s] (T,F) = src + s * src_stride (T,F), times mask mx[s] (F,T) when apply_mask
+// (src_stride 0: one X_hat for every target; src == dst with stride F T: in place)
+int mask_mul_targets_run(gss_ctx *ctx, const cplx *src, int64_t src_stride, cplx *dst,
+                         const double *mx, int F, int64_t T, int S, int apply_mask);
 
 int selftest_mfma_run(gss_ctx *ctx);
 

@@ -33,14 +33,46 @@ __global__ void masks_kernel(const double *__restrict__ gamma, int F, int K, int
     mn[idx] = n;
 }
 
+// S targets at once: gamma (F,K,T) -> mx, mn (S,F,T), one thread per (f, t) for every target.
+// Each target's values are masks_kernel's expressions (the distortion sum in the same k
+// order), with that target's own context range.
+__global__ void masks_targets_kernel(const double *__restrict__ gamma, int F, int K, int64_t T,
+                                     TargetMaskArgs a, double *__restrict__ mx,
+                                     double *__restrict__ mn) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)F * T) return;
+    const int f = idx / T;
+    const int64_t t = idx - (int64_t)f * T;
+    const double *g = gamma + (int64_t)f * K * T + t;
+    for (int s = 0; s < a.S; ++s) {
+        const int target = a.target[s];
+        double x = 0.0, n = 0.0;
+        if (t >= a.zero_lo_end[s] && t < a.zero_hi_begin[s]) {
+            x = g[(int64_t)target * T];
+            for (int k = 0; k < K; ++k)
+                if (k != target) n += g[(int64_t)k * T];
+        }
+        mx[(int64_t)s * F * T + idx] = x;
+        mn[(int64_t)s * F * T + idx] = n;
+    }
+}
+
 // Pack the two masks into the (F, 2, T) weight layout of the shared covariance
-// kernel (cacgmm.hip: wcov_kernel) and sum them over time.  grid (F), block 256.
+// kernel (cacgmm.hip: wcov_kernel) and sum them over time.  grid (F, S), block 256: target
+// blockIdx.y packs its own (F,T) masks into its own (F, 2, T) block and (F, 2) sums.
 __global__ __launch_bounds__(256) void mask_pack_kernel(const double *__restrict__ mx,
                                                         const double *__restrict__ mn, int64_t T,
                                                         double *__restrict__ W2,
                                                         double *__restrict__ msum) {
     __shared__ double red[8];
     const int f = blockIdx.x, tid = threadIdx.x;
+    {
+        const int64_t F = gridDim.x, s = blockIdx.y;
+        mx += s * F * T;
+        mn += s * F * T;
+        W2 += s * F * 2 * T;
+        msum += s * F * 2;
+    }
     double sx = 0.0, sn = 0.0;
     for (int64_t t = tid; t < T; t += blockDim.x) {
         const double a = mx[(int64_t)f * T + t], b = mn[(int64_t)f * T + t];
@@ -92,6 +124,14 @@ __global__ __launch_bounds__(MVDR_NT) void mvdr_solve_kernel(
     cplx *__restrict__ snr /* (F,D,2) */) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT = MVDR_NT;
+    {   // grid (F, S): target blockIdx.y works on its own block of every array
+        const int64_t F = gridDim.x, s = blockIdx.y, NEs = tri_count(D);
+        part += s * F * nch * 2 * NEs;
+        msum += s * F * 2;
+        Phi += s * F * 2 * D * D;
+        W += s * F * D * D;
+        snr += s * F * D * 2;
+    }
     const int m = D + (D & 1);
     const int NE = tri_count(D);
     const int W2 = 2 * D;
@@ -315,6 +355,14 @@ __global__ __launch_bounds__(64) void gev_solve_kernel(const cplx *__restrict__ 
                                                        cplx *__restrict__ W,
                                                        int32_t *__restrict__ ref) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    {   // grid (F, S): target blockIdx.y works on its own block of every array, status ref[4 s]
+        const int64_t F = gridDim.x, s = blockIdx.y, NEs = tri_count(D);
+        part += s * F * nch * 2 * NEs;
+        msum += s * F * 2;
+        Phi += s * F * 2 * D * D;
+        W += s * F * D * D;
+        ref += 4 * s;
+    }
     const int m = D + (D & 1);
     const int NE = tri_count(D);
     cplx *Ln = reinterpret_cast<cplx *>(smem);    // m * m : Phi_N -> L -> L^-1
@@ -440,6 +488,8 @@ __global__ __launch_bounds__(MVDR_REF_NT) void mvdr_ref_kernel(const cplx *__res
     extern __shared__ __attribute__((aligned(16))) char smem[];
     cplx *buf = reinterpret_cast<cplx *>(smem);            // MVDR_REF_CHUNK * D * 2
     const int tid = threadIdx.x, lane = tid & 63;
+    snr += (int64_t)blockIdx.x * F * D * 2;                 // grid (S): one workgroup per target
+    ref += 4 * blockIdx.x;
     if (forced >= 0) {
         if (tid == 0) ref[0] = forced;
         return;
@@ -554,6 +604,95 @@ __global__ __launch_bounds__(256) void mvdr_apply_kernel(
     }
 }
 
+// mvdr_apply for S <= SB targets in one pass over Y.  grid (chunks, F), block 256.  Target s
+// takes w = W_s[:, ref_s] (its own blocks of W / Phi / ref, see mvdr_solve_kernel), BAN-normalised
+// with mvdr_apply_kernel's expressions; every observation vector y_t is loaded once and
+// Xhat_s[t][f] = w_s^H y_t is accumulated over d in mvdr_apply_kernel's order for each target.
+// ref_out[s] / status[s]: the target's status word; *status0: target 0's (gss_last_ref_channel).
+template <int SB>
+__global__ __launch_bounds__(256) void mvdr_apply_targets_kernel(
+    const cplx *__restrict__ Y, const cplx *__restrict__ W, const cplx *__restrict__ Phi,
+    const int32_t *__restrict__ ref, int F, int64_t T, int D, int S, int ban, int chunk_frames,
+    cplx *__restrict__ Xhat, int32_t *__restrict__ ref_out, int32_t *__restrict__ status,
+    int32_t *__restrict__ status0) {
+    __shared__ cplx w[SB][GSS_MAX_CHANNELS];
+    __shared__ cplx t1[SB][GSS_MAX_CHANNELS];
+    __shared__ cplx t2[SB][GSS_MAX_CHANNELS];
+    __shared__ double s_norm[SB];
+    __shared__ int s_ref[SB];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    if (tid < S) {
+        const int r = ref[4 * tid];
+        s_ref[tid] = r;
+        if (blockIdx.x == 0 && f == 0) {
+            const int code = r == -2 ? -2 - ref[4 * tid + 1] : r;
+            if (ref_out) ref_out[tid] = code;
+            if (status) __hip_atomic_store(status + tid, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (status0 && tid == 0)
+                __hip_atomic_store(status0, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    __syncthreads();
+    // (slots s >= S and failed targets hold w = 0: the accumulation below runs over all SB slots
+    // without a branch, and only the S live rows are stored)
+    for (int i = tid; i < SB * D; i += blockDim.x) {
+        const int s = i / D, d = i - s * D;
+        const int r = s < S ? s_ref[s] : -1;
+        w[s][d] = r >= 0 ? W[(((int64_t)s * F + f) * D + d) * D + r] : c_make(0.0, 0.0);
+    }
+    __syncthreads();
+    if (ban) {
+        for (int i = tid; i < S * D; i += blockDim.x) {
+            const int s = i / D, a = i - s * D;
+            if (s_ref[s] < 0) continue;
+            const cplx *PhiN = Phi + (((int64_t)s * F + f) * 2 + 1) * D * D;
+            cplx v = c_make(0.0, 0.0);
+            for (int e = 0; e < D; ++e) c_fma(v, PhiN[a * D + e], w[s][e]);
+            t1[s][a] = v;   // Phi_N w
+            cplx u = c_make(0.0, 0.0);   // (w^H Phi_N)_a
+            for (int d = 0; d < D; ++d) c_cfma(u, w[s][d], PhiN[d * D + a]);
+            t2[s][a] = u;
+        }
+        __syncthreads();
+        if (tid < S && s_ref[tid] >= 0) {
+            const int s = tid;
+            cplx nom = c_make(0.0, 0.0), den = c_make(0.0, 0.0);
+            for (int a = 0; a < D; ++a) {
+                c_fma(nom, t2[s][a], t1[s][a]);
+                c_cfma(den, w[s][a], t1[s][a]);
+            }
+            const double n = sqrt(hypot(nom.x, nom.y));
+            const double dd = hypot(den.x, den.y);
+            s_norm[s] = n / dd;
+        }
+        __syncthreads();
+        for (int i = tid; i < S * D; i += blockDim.x) {
+            const int s = i / D, d = i - s * D;
+            if (s_ref[s] >= 0) w[s][d] = c_scale(w[s][d], s_norm[s]);
+        }
+        __syncthreads();
+    }
+    const int64_t c0 = (int64_t)blockIdx.x * chunk_frames;
+    const int64_t c1 = c0 + chunk_frames < T ? c0 + chunk_frames : T;
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const cplx *Yf = Y + (int64_t)f * T * D;
+    for (int64_t t = c0 + tid; t < c1; t += blockDim.x) {
+        const cplx *y = Yf + t * D;
+        cplx v[SB];
+#pragma unroll
+        for (int s = 0; s < SB; ++s) v[s] = c_make(0.0, 0.0);
+        for (int d = 0; d < D; ++d) {
+            const cplx yd = y[d];
+#pragma unroll
+            for (int s = 0; s < SB; ++s) c_cfma(v[s], w[s][d], yd);
+        }
+#pragma unroll
+        for (int s = 0; s < SB; ++s)
+            if (s < S)
+                Xhat[((int64_t)s * T + t) * F + f] = s_ref[s] >= 0 ? v[s] : c_make(qnan, qnan);
+    }
+}
+
 int psd_chunks(int F, int64_t T, int *chunk_frames) {
     int64_t tiles = (T + PSD_TILE - 1) / PSD_TILE;
     int64_t want = (2048 + F - 1) / F;
@@ -581,59 +720,93 @@ int masks_from_posteriors_run(gss_ctx *ctx, const double *gamma, int F, int K, i
     return GSS_OK;
 }
 
-size_t mvdr_workspace_bytes(int F, int64_t T, int D) {
+int masks_targets_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T, int S,
+                      const int32_t *targets, int drop, const int64_t *sf, const int64_t *ef,
+                      double *mx, double *mn) {
+    TargetMaskArgs a{};
+    a.S = S;
+    for (int s = 0; s < S; ++s) {
+        // (masks_from_posteriors_run's range for each target)
+        int64_t lo_end = 0, hi_begin = T;
+        if (drop) {
+            lo_end = sf[s] >= 0 ? (sf[s] < T ? sf[s] : T) : (T + sf[s] > 0 ? T + sf[s] : 0);
+            if (ef[s] > 0) hi_begin = T - ef[s] > 0 ? T - ef[s] : 0;
+        }
+        a.target[s] = targets[s];
+        a.zero_lo_end[s] = lo_end;
+        a.zero_hi_begin[s] = hi_begin;
+    }
+    GSS_PROF(ctx, "masks_targets");
+    const int64_t total = (int64_t)F * T;
+    hipLaunchKernelGGL(masks_targets_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       ctx->stream, gamma, F, K, T, a, mx, mn);
+    GSS_LAUNCH_CHECK(ctx, "masks_targets_kernel");
+    return GSS_OK;
+}
+
+size_t mvdr_workspace_bytes(int F, int64_t T, int D, int S) {
     const size_t NE = tri_count(D);
     int cf;
     const int nch = psd_chunks(F, T, &cf);
     size_t b = 0;
-    b += align_up(sizeof(cplx) * (size_t)F * nch * 2 * NE);
-    b += align_up(sizeof(double) * (size_t)F * 2);
-    b += align_up(sizeof(double) * (size_t)F * 2 * T);
-    b += align_up(sizeof(cplx) * (size_t)F * 2 * D * D);
-    b += align_up(sizeof(cplx) * (size_t)F * D * D);
-    b += align_up(sizeof(cplx) * (size_t)F * D * 2);
-    b += 256;
+    b += align_up(sizeof(cplx) * (size_t)S * F * nch * 2 * NE);
+    b += align_up(sizeof(double) * (size_t)S * F * 2);
+    b += align_up(sizeof(double) * (size_t)S * F * 2 * T);
+    b += align_up(sizeof(cplx) * (size_t)S * F * 2 * D * D);
+    b += align_up(sizeof(cplx) * (size_t)S * F * D * D);
+    b += align_up(sizeof(cplx) * (size_t)S * F * D * 2);
+    b += align_up(sizeof(int32_t) * 4 * (size_t)S);
     return b + 4096;
 }
 
 int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
              const double *mn, int ban, cplx *Xhat, int32_t *ref_channel, int gev,
-             int forced_ref) {
+             int forced_ref, int S, bool targets) {
+    // S targets (gss_enhance_observation_targets): masks (S,F,T), Xhat (S,T,F), ref_channel (S),
+    // every intermediate in S consecutive per-target blocks of the one-target layout
     const int NE = tri_count(D);
     int cf;
     const int nch = psd_chunks(F, T, &cf);
-    cplx *part = arena_alloc_t<cplx>(ctx, (size_t)F * nch * 2 * NE);
-    double *msum = arena_alloc_t<double>(ctx, (size_t)F * 2);
-    double *W2 = arena_alloc_t<double>(ctx, (size_t)F * 2 * T);
-    cplx *Phi = arena_alloc_t<cplx>(ctx, (size_t)F * 2 * D * D);
-    cplx *W = arena_alloc_t<cplx>(ctx, (size_t)F * D * D);
-    cplx *snr = arena_alloc_t<cplx>(ctx, (size_t)F * D * 2);
-    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);
+    cplx *part = arena_alloc_t<cplx>(ctx, (size_t)S * F * nch * 2 * NE);
+    double *msum = arena_alloc_t<double>(ctx, (size_t)S * F * 2);
+    double *W2 = arena_alloc_t<double>(ctx, (size_t)S * F * 2 * T);
+    cplx *Phi = arena_alloc_t<cplx>(ctx, (size_t)S * F * 2 * D * D);
+    cplx *W = arena_alloc_t<cplx>(ctx, (size_t)S * F * D * D);
+    cplx *snr = arena_alloc_t<cplx>(ctx, (size_t)S * F * D * 2);
+    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4 * (size_t)S);
     GSS_REQUIRE(ctx, part && msum && W2 && Phi && W && snr && ref, GSS_ERR_NOMEM,
                 "mvdr workspace");
+    ctx->last_targets = targets ? S : 0;
     {
-        GSS_PROF(ctx, "psd");
-        hipLaunchKernelGGL(mask_pack_kernel, dim3(F), dim3(256), 0, ctx->stream, mx, mn, T, W2,
+        GSS_PROF(ctx, targets ? "psd_targets" : "psd");
+        hipLaunchKernelGGL(mask_pack_kernel, dim3(F, S), dim3(256), 0, ctx->stream, mx, mn, T, W2,
                            msum);
         GSS_LAUNCH_CHECK(ctx, "mask_pack_kernel");
-        GSS_TRY(psd_partials_run(ctx, Y, F, T, D, W2, nch, cf, part));
+        GSS_TRY(psd_partials_run(ctx, Y, F, T, D, W2, nch, cf, part, S));
     }
     if (gev) {
-        GSS_PROF(ctx, "gev_solve");
+        GSS_PROF(ctx, targets ? "gev_solve_targets" : "gev_solve");
         const int m = D + (D & 1);
         const size_t lds = (sizeof(cplx) * 4 * (size_t)m * m + 15) / 16 * 16;
         if (lds > 64 * 1024)
             GSS_HIP_CHECK(ctx, hipFuncSetAttribute(
                                    reinterpret_cast<const void *>(gev_solve_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        GSS_HIP_CHECK(ctx, hipMemsetAsync(ref, 0, sizeof(int32_t), ctx->stream));
-        GSS_HIP_CHECK(ctx, hipMemsetAsync(ref + 1, 0x7f, sizeof(int32_t), ctx->stream));
-        hipLaunchKernelGGL(gev_solve_kernel, dim3(F), dim3(64), lds, ctx->stream, part, msum, nch,
-                           D, Phi, W, ref);
+        if (S == 1) {
+            GSS_HIP_CHECK(ctx, hipMemsetAsync(ref, 0, sizeof(int32_t), ctx->stream));
+            GSS_HIP_CHECK(ctx, hipMemsetAsync(ref + 1, 0x7f, sizeof(int32_t), ctx->stream));
+        } else {    // (the same two words in each target's block of four)
+            GSS_HIP_CHECK(ctx, hipMemset2DAsync(ref, 4 * sizeof(int32_t), 0, sizeof(int32_t), S,
+                                                ctx->stream));
+            GSS_HIP_CHECK(ctx, hipMemset2DAsync(ref + 1, 4 * sizeof(int32_t), 0x7f,
+                                                sizeof(int32_t), S, ctx->stream));
+        }
+        hipLaunchKernelGGL(gev_solve_kernel, dim3(F, S), dim3(64), lds, ctx->stream, part, msum,
+                           nch, D, Phi, W, ref);
         GSS_LAUNCH_CHECK(ctx, "gev_solve_kernel");
     } else {
         {
-            GSS_PROF(ctx, "mvdr_solve");
+            GSS_PROF(ctx, targets ? "mvdr_solve_targets" : "mvdr_solve");
             const int m = D + (D & 1);
             const size_t lds = (sizeof(cplx) * ((size_t)D * 2 * D + 2 * (size_t)m * m) +
                                 32 + 15) / 16 * 16;
@@ -641,25 +814,37 @@ int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double 
                 GSS_HIP_CHECK(ctx, hipFuncSetAttribute(
                                        reinterpret_cast<const void *>(mvdr_solve_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(mvdr_solve_kernel, dim3(F), dim3(MVDR_NT), lds, ctx->stream, part, msum, nch,
-                               D, 1e-10, Phi, W, snr);
+            hipLaunchKernelGGL(mvdr_solve_kernel, dim3(F, S), dim3(MVDR_NT), lds, ctx->stream, part,
+                               msum, nch, D, 1e-10, Phi, W, snr);
             GSS_LAUNCH_CHECK(ctx, "mvdr_solve_kernel");
         }
         {
-            GSS_PROF(ctx, "mvdr_ref");
-            hipLaunchKernelGGL(mvdr_ref_kernel, dim3(1), dim3(MVDR_REF_NT),
+            GSS_PROF(ctx, targets ? "mvdr_ref_targets" : "mvdr_ref");
+            hipLaunchKernelGGL(mvdr_ref_kernel, dim3(S), dim3(MVDR_REF_NT),
                                sizeof(cplx) * MVDR_REF_CHUNK * (size_t)D * 2, ctx->stream, snr, F, D, 1e-10,
                                forced_ref, ref);
             GSS_LAUNCH_CHECK(ctx, "mvdr_ref_kernel");
         }
     }
-    {
+    const int chunk = 256;
+    const dim3 grid((unsigned)((T + chunk - 1) / chunk), F);
+    if (!targets) {
         GSS_PROF(ctx, "mvdr_apply");
-        const int chunk = 256;
-        hipLaunchKernelGGL(mvdr_apply_kernel, dim3((unsigned)((T + chunk - 1) / chunk), F),
-                           dim3(256), 0, ctx->stream, Y, W, Phi, ref, F, T, D, ban, chunk, Xhat,
-                           ref_channel, ctx->status_dev);
+        hipLaunchKernelGGL(mvdr_apply_kernel, grid, dim3(256), 0, ctx->stream, Y, W, Phi, ref, F, T,
+                           D, ban, chunk, Xhat, ref_channel, ctx->status_dev);
         GSS_LAUNCH_CHECK(ctx, "mvdr_apply_kernel");
+        return GSS_OK;
     }
+    GSS_PROF(ctx, "mvdr_apply_targets");
+    int32_t *const status = ctx->status_dev + GSS_STATUS_TARGETS;
+#define GSS_APPLY_TARGETS(SB)                                                                    \
+    hipLaunchKernelGGL(mvdr_apply_targets_kernel<SB>, grid, dim3(256), 0, ctx->stream, Y, W, Phi, \
+                       ref, F, T, D, S, ban, chunk, Xhat, ref_channel, status, ctx->status_dev)
+    if (S <= 2) GSS_APPLY_TARGETS(2);
+    else if (S <= 4) GSS_APPLY_TARGETS(4);
+    else if (S <= 8) GSS_APPLY_TARGETS(8);
+    else GSS_APPLY_TARGETS(GSS_MAX_CLASSES);
+#undef GSS_APPLY_TARGETS
+    GSS_LAUNCH_CHECK(ctx, "mvdr_apply_targets_kernel");
     return GSS_OK;
 }

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(FFT_THREADS) void stft_kernel(
 }
 
 // Inverse: one workgroup handles frames 2*b and 2*b+1 of X (T,F) and writes
-// synthesis-windowed frames into frm (T, size).
+// synthesis-windowed frames into frm (T, size).  grid.y: signals (X (S,T,F) -> frm (S,T,size)).
 __global__ __launch_bounds__(FFT_THREADS) void istft_frames_kernel(
     const cplx *__restrict__ X, int64_t T, int size, int log2n,
     const double *__restrict__ syn, const cplx *__restrict__ twiddle,
@@ -188,6 +188,8 @@ __global__ __launch_bounds__(FFT_THREADS) void istft_frames_kernel(
     cplx *s = reinterpret_cast<cplx *>(smem);   // size
     cplx *tw = s + size;                         // size / 2
     const int F = size / 2 + 1;
+    X += (int64_t)blockIdx.y * T * F;
+    frm += (int64_t)blockIdx.y * T * size;
     const int64_t ta = (int64_t)blockIdx.x * 2, tb = ta + 1;
     for (int i = threadIdx.x; i < size / 2; i += blockDim.x) tw[i] = twiddle[i];
     // Hermitian extension of both spectra (irfft ignores Im of DC and Nyquist),
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(FFT_THREADS) void stft_dft_kernel(
     }
 }
 
-// grid (T), block 256: one frame; thread = samples tid, tid + 256, ...
+// grid (T, S), block 256: one frame of one signal; thread = samples tid, tid + 256, ...
 __global__ __launch_bounds__(FFT_THREADS) void istft_dft_kernel(
     const cplx *__restrict__ X, int64_t T, int size, const double *__restrict__ syn,
     const cplx *__restrict__ twiddle, double *__restrict__ frm) {
@@ -268,6 +270,8 @@ __global__ __launch_bounds__(FFT_THREADS) void istft_dft_kernel(
     cplx *xs = tw + size / 2;                                    // F
     const int64_t t = blockIdx.x;
     const int half = size / 2, F = half + 1;
+    X += (int64_t)blockIdx.y * T * F;
+    frm += (int64_t)blockIdx.y * T * size;
     for (int i = threadIdx.x; i < half; i += blockDim.x) tw[i] = twiddle[i];
     for (int f = threadIdx.x; f < F; f += blockDim.x) xs[f] = X[t * F + f];
     __syncthreads();
@@ -288,11 +292,13 @@ __global__ __launch_bounds__(FFT_THREADS) void istft_dft_kernel(
 }
 
 // Overlap-add in increasing frame order (np.add.at upstream), then drop the
-// fading pad.
+// fading pad.  grid.y: signals (frm (S,T,size) -> out (S,n_out)).
 __global__ void istft_ola_kernel(const double *__restrict__ frm, int64_t T, int size, int shift,
                                  int pad, int64_t n_out, double *__restrict__ out) {
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_out) return;
+    frm += (int64_t)blockIdx.y * T * size;
+    out += (int64_t)blockIdx.y * n_out;
     const int64_t m = n + pad;
     int64_t t_lo = m - size + 1;
     t_lo = t_lo <= 0 ? 0 : (t_lo + shift - 1) / shift;
@@ -409,6 +415,25 @@ __global__ void mask_mul_kernel(cplx *__restrict__ Xhat, const double *__restric
     Xhat[idx] = c_scale(Xhat[idx], m);
 }
 
+// S targets: dst[s] = src[s * src_stride] (T,F), times target s's mask (F,T) when apply_mask
+// -- mask_mul_kernel's product.  grid (ceil(F T / 256), S).
+__global__ void mask_mul_targets_kernel(const cplx *src, int64_t src_stride, cplx *dst,
+                                        const double *__restrict__ mask, int F, int64_t T,
+                                        int apply_mask) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)F * T) return;
+    const int64_t s = blockIdx.y;
+    const cplx x = src[s * src_stride + idx];
+    if (!apply_mask) {
+        dst[s * F * T + idx] = x;
+        return;
+    }
+    const int64_t t = idx / F;
+    const int f = idx - t * F;
+    const double m = mask[s * F * T + (int64_t)f * T + t];
+    dst[s * F * T + idx] = c_scale(x, m);
+}
+
 int ilog2(int n) {
     int l = 0;
     while ((1 << l) < n) ++l;
@@ -468,29 +493,29 @@ int stft_run(gss_ctx *ctx, const void *x, int in_type, int D, int64_t N, int fad
     return GSS_OK;
 }
 
-int istft_run(gss_ctx *ctx, const cplx *X, int64_t T, int fading, double *x) {
+int istft_run(gss_ctx *ctx, const cplx *X, int64_t T, int fading, double *x, int S) {
     const int size = ctx->stft_size, shift = ctx->stft_shift;
     const int pad = fading ? size - shift : 0;
     const int64_t n_out = gss_istft_num_samples(T, size, shift, fading);
-    double *frm = arena_alloc_t<double>(ctx, (size_t)T * size);
+    double *frm = arena_alloc_t<double>(ctx, (size_t)S * T * size);
     GSS_REQUIRE(ctx, frm, GSS_ERR_NOMEM, "istft workspace");
     if ((size & (size - 1)) != 0) {
-        GSS_PROF(ctx, "istft_frames");
+        GSS_PROF(ctx, S > 1 ? "istft_frames_targets" : "istft_frames");
         const size_t lds = sizeof(cplx) * (size / 2 + size / 2 + 1);
-        hipLaunchKernelGGL(istft_dft_kernel, dim3((unsigned)T), dim3(FFT_THREADS), lds, ctx->stream, X,
-                           T, size, ctx->win_synthesis, ctx->twiddle, frm);
+        hipLaunchKernelGGL(istft_dft_kernel, dim3((unsigned)T, S), dim3(FFT_THREADS), lds, ctx->stream,
+                           X, T, size, ctx->win_synthesis, ctx->twiddle, frm);
         GSS_LAUNCH_CHECK(ctx, "istft_dft_kernel");
     } else {
-        GSS_PROF(ctx, "istft_frames");
+        GSS_PROF(ctx, S > 1 ? "istft_frames_targets" : "istft_frames");
         size_t lds = sizeof(cplx) * (size + size / 2);
-        hipLaunchKernelGGL(istft_frames_kernel, dim3((unsigned)((T + 1) / 2)), dim3(FFT_THREADS),
+        hipLaunchKernelGGL(istft_frames_kernel, dim3((unsigned)((T + 1) / 2), S), dim3(FFT_THREADS),
                            lds, ctx->stream, X, T, size, ilog2(size), ctx->win_synthesis,
                            ctx->twiddle, frm);
         GSS_LAUNCH_CHECK(ctx, "istft_frames_kernel");
     }
     if (n_out > 0) {
-        GSS_PROF(ctx, "istft_ola");
-        hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0,
+        GSS_PROF(ctx, S > 1 ? "istft_ola_targets" : "istft_ola");
+        hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)((n_out + 255) / 256), S), dim3(256), 0,
                            ctx->stream, frm, T, size, shift, pad, n_out, x);
         GSS_LAUNCH_CHECK(ctx, "istft_ola_kernel");
     }
@@ -516,6 +541,16 @@ int channel_pick_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int m
     hipLaunchKernelGGL(channel_pick_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        ctx->stream, Y, F, T, D, mode, Xhat);
     GSS_LAUNCH_CHECK(ctx, "channel_pick_kernel");
+    return GSS_OK;
+}
+
+int mask_mul_targets_run(gss_ctx *ctx, const cplx *src, int64_t src_stride, cplx *dst,
+                         const double *mx, int F, int64_t T, int S, int apply_mask) {
+    GSS_PROF(ctx, "mask_mul_targets");
+    const int64_t total = (int64_t)F * T;
+    hipLaunchKernelGGL(mask_mul_targets_kernel, dim3((unsigned)((total + 255) / 256), S), dim3(256),
+                       0, ctx->stream, src, src_stride, dst, mx, F, T, apply_mask);
+    GSS_LAUNCH_CHECK(ctx, "mask_mul_targets_kernel");
     return GSS_OK;
 }
 

@@ -387,10 +387,13 @@ def params_for(params, num_channels, wpe_arrays=None):
 
 
 class ResidentUtterance:
-    """An utterance whose inputs already sit in HBM (what bench.py times)."""
+    """An utterance whose inputs already sit in HBM (what bench.py times).  ``pcm=True``: the
+    samples are int16 PCM, scaled by 2^-15 on the device (the _pcm16 entries); otherwise they
+    are taken as float64."""
 
-    def __init__(self, ctx, obs, activity, params, wpe_arrays=None):
-        obs = np.ascontiguousarray(obs, dtype=np.float64)
+    def __init__(self, ctx, obs, activity, params, wpe_arrays=None, pcm=False):
+        self.pcm = bool(pcm)
+        obs = np.ascontiguousarray(obs, dtype=np.int16 if self.pcm else np.float64)
         act = np.ascontiguousarray((np.asarray(activity) != 0).astype(np.uint8))
         self.ctx = ctx
         self.D, self.N = obs.shape
@@ -407,12 +410,31 @@ class ResidentUtterance:
 
     def enqueue(self, target_index, start_context, end_context, taps=None):
         ctx = self.ctx
-        ctx._check(ctx.lib.gss_enhance_observation(
+        entry = ctx.lib.gss_enhance_observation_pcm16 if self.pcm else ctx.lib.gss_enhance_observation
+        ctx._check(entry(
             ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
             self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
             int(start_context), int(end_context), c_void_p(self.out_d.ptr),
             ctypes.byref(taps) if taps is not None else None),
             'gss_enhance_observation')
+
+    def enqueue_targets(self, target_indices, start_contexts, end_contexts, out_d, taps=None):
+        """gss_enhance_observation_targets: len(target_indices) rows of n_out samples into
+        ``out_d``; the contexts are one per target."""
+        ctx = self.ctx
+        targets = np.ascontiguousarray(target_indices, dtype=np.int32)
+        starts = np.ascontiguousarray(start_contexts, dtype=np.int64)
+        ends = np.ascontiguousarray(end_contexts, dtype=np.int64)
+        assert starts.shape == ends.shape == targets.shape
+        assert out_d.nbytes >= 8 * len(targets) * self.n_out
+        entry = (ctx.lib.gss_enhance_observation_targets_pcm16 if self.pcm
+                 else ctx.lib.gss_enhance_observation_targets)
+        ctx._check(entry(
+            ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D, self.N,
+            c_void_p(self.act_d.ptr), self.K, self.N_act, len(targets),
+            targets.ctypes.data_as(c_void_p), starts.ctypes.data_as(c_void_p),
+            ends.ctypes.data_as(c_void_p), c_void_p(out_d.ptr),
+            ctypes.byref(taps) if taps is not None else None), 'gss_enhance_observation_targets')
 
     def result(self):
         x_hat = self.ctx.to_host(self.out_d, (self.n_out,), np.float64)
@@ -661,31 +683,96 @@ def enhance_observation(obs, activity, target_index, start_context_samples,
     ctx = ctx or default_context()
     _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
     utt = ResidentUtterance(ctx, obs, activity, params)
-    D, K, T = utt.D, utt.K, utt.T
-    F = params.stft_size // 2 + 1
-    taps = None
-    bufs = {}
-    if debug:
-        bufs = {
-            'Obs_ftd': ctx.empty(16 * F * T * D), 'act_frames': ctx.empty(max(K * T, 16)),
-            'gamma': ctx.empty(8 * F * K * T), 'target_mask': ctx.empty(8 * F * T),
-            'distortion_mask': ctx.empty(8 * F * T), 'Xhat': ctx.empty(16 * F * T),
-            'ref_channel': ctx.empty(16),
-        }
-        ctx._check(ctx.lib.gss_memset(ctx.handle, c_void_p(bufs['ref_channel'].ptr), 0xFF, 16),
-                   'gss_memset')
-        taps = GssDebugTaps(**{k: v.ptr for k, v in bufs.items()})
+    bufs, taps = _debug_taps(utt) if debug else ({}, None)
     utt.enqueue(target_index, start_context_samples, end_context_samples, taps)
     x_hat = utt.result()
     if not debug:
         return x_hat
-    details = {
+    details = _debug_details(utt, bufs)
+    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+    details['ref_channel'] = int(details['ref_channel'])
+    return x_hat, details
+
+
+_PER_TARGET = ('target_mask', 'distortion_mask', 'X_hat', 'ref_channel')
+
+
+def _debug_taps(utt, S=1):
+    """Device buffers for the debug taps of a call on ``utt`` with S targets (per-target taps
+    S blocks), the reference channels preset to -1."""
+    ctx, D, K, T = utt.ctx, utt.D, utt.K, utt.T
+    F = utt.params.stft_size // 2 + 1
+    bufs = {
+        'Obs_ftd': ctx.empty(16 * F * T * D), 'act_frames': ctx.empty(max(K * T, 16)),
+        'gamma': ctx.empty(8 * F * K * T), 'target_mask': ctx.empty(8 * S * F * T),
+        'distortion_mask': ctx.empty(8 * S * F * T), 'Xhat': ctx.empty(16 * S * F * T),
+        'ref_channel': ctx.empty(max(4 * S, 16)),
+    }
+    ctx._check(ctx.lib.gss_memset(ctx.handle, c_void_p(bufs['ref_channel'].ptr), 0xFF,
+                                  bufs['ref_channel'].nbytes), 'gss_memset')
+    return bufs, GssDebugTaps(**{k: v.ptr for k, v in bufs.items()})
+
+
+def _debug_details(utt, bufs, S=1):
+    """The taps in the reference's layouts; the per-target ones stacked over S."""
+    ctx, D, K, T = utt.ctx, utt.D, utt.K, utt.T
+    F = utt.params.stft_size // 2 + 1
+    return {
         'Obs': _ftd_to_host_dtf(ctx, bufs['Obs_ftd'], D, T, F),
         'acitivity_freq': ctx.to_host(bufs['act_frames'], (K, T), np.uint8).astype(bool),
         'posterior': ctx.to_host(bufs['gamma'], (F, K, T), np.float64).transpose(1, 2, 0),
-        'target_mask': ctx.to_host(bufs['target_mask'], (F, T), np.float64).T,
-        'distortion_mask': ctx.to_host(bufs['distortion_mask'], (F, T), np.float64).T,
-        'X_hat': ctx.to_host(bufs['Xhat'], (T, F), np.complex128),
-        'ref_channel': int(ctx.to_host(bufs['ref_channel'], (1,), np.int32)[0]),
+        'target_mask': ctx.to_host(bufs['target_mask'], (S, F, T), np.float64).transpose(0, 2, 1),
+        'distortion_mask': ctx.to_host(bufs['distortion_mask'], (S, F, T),
+                                       np.float64).transpose(0, 2, 1),
+        'X_hat': ctx.to_host(bufs['Xhat'], (S, T, F), np.complex128),
+        'ref_channel': ctx.to_host(bufs['ref_channel'], (S,), np.int32).astype(int),
     }
-    return x_hat, details
+
+
+def target_contexts(contexts, S, what='context samples'):
+    """A context (samples) for each of S targets: an int for all of them, or a length-S
+    sequence."""
+    if isinstance(contexts, (int, np.integer)) and not isinstance(contexts, bool):
+        return [int(contexts)] * S
+    values = [int(c) for c in contexts]
+    if len(values) != S:
+        raise ValueError(f'{what}: {len(values)} values for {S} targets')
+    return values
+
+
+def enhance_observation_targets(obs, activity, target_indices, start_context_samples,
+                                end_context_samples, *, params=None, window=None, debug=False,
+                                ctx=None, wpe_arrays=None, target_names=None, **param_kwargs):
+    """S targets of one window from ONE separation (gss_enhance_observation_targets): STFT, WPE
+    and the guided CACGMM run once, the target-dependent tail once for all S targets.
+
+    obs (D,N) float64 (or int16 PCM, scaled by 2^-15 on the device), activity (K,N) bool in
+    dict order, target_indices S distinct class indices; the contexts are ints (the same for
+    every target) or length-S sequences.  Returns x_hat (S, N'), row s bit for bit what
+    `enhance_observation` returns for target_indices[s] and its contexts; with ``debug=True``
+    (x_hat, details) where the per-target entries are stacked: ``target_mask`` /
+    ``distortion_mask`` / ``X_hat`` (S,T,F), ``ref_channel`` (S,).  A failing target raises
+    what the one-target call raises, for the first such target in target order
+    (``target_names[s]`` names it in the message)."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    params = params_for(params, np.shape(obs)[0], wpe_arrays)
+    targets = [int(t) for t in target_indices]
+    S = len(targets)
+    starts = target_contexts(start_context_samples, S)
+    ends = target_contexts(end_context_samples, S)
+    if target_names is None:
+        target_names = [f'target {t}' for t in targets]
+    ctx = ctx or default_context()
+    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
+    utt = ResidentUtterance(ctx, obs, activity, params, pcm=np.asarray(obs).dtype == np.int16)
+    out_d = ctx.empty(8 * max(S * utt.n_out, 1))
+    bufs, taps = _debug_taps(utt, S) if debug else ({}, None)
+    utt.enqueue_targets(targets, starts, ends, out_d, taps)
+    x_hat = ctx.to_host(out_d, (S, utt.n_out), np.float64)
+    if params.bf in (_BF_CODES['mvdrSouden_ban'], _BF_CODES['gev_ban']):
+        for ref, name in zip(ctx.last_ref_channels(S), target_names):
+            _raise_for_ref_channel(ref, name)
+    if not debug:
+        return x_hat
+    return x_hat, _debug_details(utt, bufs, S)
