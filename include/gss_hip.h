@@ -74,7 +74,9 @@ typedef enum {
  * of the per-array WPE.  A library of revision 7 may therefore lack them; the Python binding
  * checks for every symbol it declares and asks for a rebuild when one is missing.  A binder
  * compares gss_abi_version() with the GSS_ABI_VERSION it was written against before any other
- * call (and, for these three, looks the symbols up). */
+ * call (and, for these three, looks the symbols up).  gss_cacgmm_guided and
+ * gss_enhance_observation_guided (with the gss_guidance descriptor) were added the same way:
+ * entry points only, no struct or argument list of an existing one changed, revision still 7. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -201,6 +203,31 @@ int gss_wpe_inverse_power(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T,
 int gss_cacgmm(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
                const uint8_t *act_frames_dev, int K, int iterations,
                int iterations_post, double *gamma_dev);
+
+/* What guides the mixture model, as pb_bss takes it: CACGMMTrainer.fit(y, initialization,
+ * source_activity_mask=...) with any (F,K,T) initialisation and any (F,K,T) boolean mask, or
+ * no mask.  Element (f, k, t) of a table sits at [f * f_stride + k * k_stride + t]. */
+typedef struct {
+    const double *init_dev;   /* initial affiliations, used as given (not renormalised, like
+                                 pb_bss); NULL: derived from mask_dev as core.py:156-159:
+                                 where(mask, 1, 1e-10) / sum over k                          */
+    const uint8_t *mask_dev;  /* source_activity_mask, nonzero = active; NULL: no mask
+                                 (fit(..., source_activity_mask=None), unmasked predict)     */
+    int64_t init_f_stride;    /* elements between frequencies; 0 = one table for every f     */
+    int64_t init_k_stride;    /* elements between classes, >= T                              */
+    int64_t mask_f_stride;    /* likewise for the mask (strides of a NULL table are unread)  */
+    int64_t mask_k_stride;
+} gss_guidance;
+
+/* gss_cacgmm with weights and per-frequency guidance.  The schedule is gss_cacgmm's:
+ * `iterations` masked fits from the initialisation, then iterations_post as there; with
+ * mask_dev == NULL every step is unmasked.  {NULL, act_frames_dev, 0, 0, 0, T} is gss_cacgmm
+ * bit for bit.  GSS_ERR_INVALID: guidance NULL, both tables NULL, a non-zero f stride smaller
+ * than K * k_stride, a k stride smaller than T.  The values are not validated: NaN or negative
+ * weights propagate as they do upstream. */
+int gss_cacgmm_guided(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                      const gss_guidance *guidance, int K, int iterations,
+                      int iterations_post, double *gamma_dev);
 
 /* A0  mask post-processing of enhance_observation (core.py:537-554): zero the
  * context frames, pick the target class, sum the others.
@@ -329,6 +356,19 @@ int gss_enhance_observation(gss_ctx *ctx, const gss_params *params,
                             int64_t start_context_samples,
                             int64_t end_context_samples,
                             double *out_dev, const gss_debug_taps *taps);
+
+/* gss_enhance_observation guided per STFT frame instead of per sample: the tables of
+ * `guidance` cover T = gss_stft_num_frames(N, ...) frames and F = stft_size / 2 + 1
+ * frequencies, and replace the time-domain activity and its conversion to frames.  STFT, WPE
+ * (joint or per array), beamformer, postfilter, iSTFT and the taps are those of
+ * gss_enhance_observation; taps->act_frames must be NULL (there is no frame activity to
+ * report).  Errors of the guidance as gss_cacgmm_guided. */
+int gss_enhance_observation_guided(gss_ctx *ctx, const gss_params *params,
+                                   const double *obs_dev, int D, int64_t N,
+                                   const gss_guidance *guidance, int K, int target_index,
+                                   int64_t start_context_samples,
+                                   int64_t end_context_samples,
+                                   double *out_dev, const gss_debug_taps *taps);
 
 /* Same pipeline fed with the 16-bit PCM samples as they sit in the WAV files: the
  * conversion of the reference's loader, float64(sample) / 2^15 (io/audioread.py:34-226 via

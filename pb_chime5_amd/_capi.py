@@ -39,6 +39,13 @@ class GssDebugTaps(ctypes.Structure):
         'Xhat', 'ref_channel')]
 
 
+class GssGuidance(ctypes.Structure):
+    """gss_guidance: element (f, k, t) of a table at [f * f_stride + k * k_stride + t]."""
+    _fields_ = [('init_dev', c_void_p), ('mask_dev', c_void_p),
+                ('init_f_stride', c_int64), ('init_k_stride', c_int64),
+                ('mask_f_stride', c_int64), ('mask_k_stride', c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/gss_hip.h declares
 SIGNATURES = {
     'gss_device_count': (c_int, []),
@@ -80,6 +87,8 @@ SIGNATURES = {
                                       c_void_p]),
     'gss_cacgmm': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p,
                            c_int, c_int, c_int, c_void_p]),
+    'gss_cacgmm_guided': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
+                                  ctypes.POINTER(GssGuidance), c_int, c_int, c_int, c_void_p]),
     'gss_masks_from_posteriors': (
         c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_int64,
                 c_int64, c_void_p, c_void_p]),
@@ -100,6 +109,10 @@ SIGNATURES = {
     'gss_enhance_observation': (
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p,
+                ctypes.POINTER(GssDebugTaps)]),
+    'gss_enhance_observation_guided': (
+        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
+                ctypes.POINTER(GssGuidance), c_int, c_int, c_int64, c_int64, c_void_p,
                 ctypes.POINTER(GssDebugTaps)]),
     'gss_enhance_observation_pcm16': (
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,

@@ -146,15 +146,27 @@ class GSS:
     iterations_post: int
     verbose: bool = True
 
-    def __call__(self, Obs, acitivity_freq, debug=False):
-        posterior = ops.cacgmm_posteriors(
-            Obs, acitivity_freq, iterations=self.iterations,
-            iterations_post=self.iterations_post)
+    def __call__(self, Obs, acitivity_freq, debug=False, *, initialization=None):
+        """``acitivity_freq`` (K,T), or (K,T,F) for guidance that differs by frequency: zero =
+        the class is off (source activity mask), any other value its weight in the initial
+        affiliations, as in the reference (core.py:156-163).  ``initialization`` (K,T) or
+        (K,T,F): initial affiliations used as given instead of the ones derived from the
+        activity (a neural mask, the posteriors of an earlier pass).  A 0/1 activity without
+        ``initialization`` takes the unweighted call; everything else the guided one."""
+        if ops.activity_is_binary(acitivity_freq, initialization):
+            posterior = ops.cacgmm_posteriors(
+                Obs, acitivity_freq, iterations=self.iterations,
+                iterations_post=self.iterations_post)
+            if debug:
+                initialization, source_active_mask = ops.guidance_from_activity(acitivity_freq)
+        else:
+            derived, source_active_mask = ops.guidance_from_activity(acitivity_freq)
+            if initialization is None:
+                initialization = derived
+            posterior = ops.cacgmm_posteriors_guided(
+                Obs, initialization, source_active_mask, iterations=self.iterations,
+                iterations_post=self.iterations_post)
         if debug:
-            initialization = np.asarray(acitivity_freq, dtype=np.float64)
-            initialization = np.where(initialization == 0, 1e-10, initialization)
-            initialization = initialization / np.sum(initialization, keepdims=True, axis=0)
-            source_active_mask = np.asarray(acitivity_freq, dtype=bool)
             self.locals = locals()
         return posterior
 
@@ -723,6 +735,83 @@ class Enhancer:
         self.enhance_observation_locals = locals()
         return x_hat
 
+    def enhance_observation_guided(self, obs, frame_guidance, speaker_id, ex=None, *,
+                                   initialization=None, debug=False, fused=None,
+                                   wpe_arrays=None):
+        """`enhance_observation` guided per STFT frame.  ``frame_guidance``: dict speaker ->
+        (T,) or (T,F) array over the frames of the observation's STFT, in the key order of
+        ``ex_array_activity``: zero = the speaker is off, any other value the weight of the
+        speaker in the initial affiliations (diarisation posteriors, annotation confidence).
+        ``initialization``: optional dict of the same shape with initial affiliations used as
+        given (a neural mask estimator's output).  ``fused=False`` runs the blocks."""
+        if wpe_arrays is None:
+            wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
+        wpe_arrays = ops.check_wpe_arrays(wpe_arrays, np.shape(obs)[0])
+        if fused is None:
+            fused = self._fusable()
+        target_speaker_index = tuple(frame_guidance.keys()).index(speaker_id)
+        acitivity_freq = np.array(list(frame_guidance.values()))
+        if initialization is not None:
+            if tuple(initialization.keys()) != tuple(frame_guidance.keys()):
+                raise ValueError('initialization and frame_guidance name different speakers: '
+                                 f'{tuple(initialization)} != {tuple(frame_guidance)}')
+            initialization = np.array(list(initialization.values()))
+        if not fused:
+            return self._enhance_guided_blocks(obs, acitivity_freq, initialization,
+                                               target_speaker_index, ex, debug, wpe_arrays)
+        derived, source_active_mask = ops.guidance_from_activity(acitivity_freq)
+        if initialization is None:
+            initialization = derived
+        start_ctx = end_ctx = 0
+        if self.bf_drop_context:
+            start_ctx, end_ctx = start_end_context_samples(ex)
+        ctx = self._ctx()
+        ctx.set_utterances_in_flight(1)
+        try:
+            res = ops.enhance_observation_guided(
+                obs, initialization, source_active_mask, target_speaker_index, start_ctx,
+                end_ctx, params=self._params(), debug=debug, ctx=ctx, wpe_arrays=wpe_arrays)
+        finally:
+            ctx.set_utterances_in_flight(0)
+        if not debug:
+            return res
+        x_hat, details = res
+        Obs = details['Obs']
+        target_mask = details['target_mask']
+        distortion_mask = details['distortion_mask']
+        X_hat = details['X_hat']
+        masks = details['posterior'].copy()
+        if self.bf_drop_context:
+            start_context_frames, end_context_frames = start_end_context_frames(
+                ex, self.stft_size, self.stft_shift, self.stft_fading)
+            masks[:, :start_context_frames, :] = 0
+            if end_context_frames > 0:
+                masks[:, -end_context_frames:, :] = 0
+        self.enhance_observation_locals = locals()
+        return x_hat
+
+    def _enhance_guided_blocks(self, obs, acitivity_freq, initialization,
+                               target_speaker_index, ex, debug, wpe_arrays):
+        """The guided call block by block: `_enhance_observation_blocks` with the frame
+        guidance in the place of the converted activity."""
+        Obs = self._blocks_wpe(self.stft(obs), debug, wpe_arrays)
+        masks = self.gss_block(Obs, acitivity_freq, debug=debug, initialization=initialization)
+        if self.bf_drop_context:
+            start_context_frames, end_context_frames = start_end_context_frames(
+                ex, stft_size=self.stft_size, stft_shift=self.stft_shift,
+                stft_fading=self.stft_fading)
+            masks[:, :start_context_frames, :] = 0
+            if end_context_frames > 0:
+                masks[:, -end_context_frames:, :] = 0
+        target_mask = masks[target_speaker_index]
+        distortion_mask = np.sum(np.delete(masks, target_speaker_index, axis=0), axis=0)
+        X_hat = self.bf_block(Obs, target_mask=target_mask,
+                              distortion_mask=distortion_mask, debug=debug)
+        x_hat = self.istft(X_hat)
+        if debug:
+            self.enhance_observation_locals = locals()
+        return x_hat
+
     def speaker_ids_of(self, ex_array_activity, speaker_ids=None):
         """The targets of `enhance_observation_speakers`: ``speaker_ids`` as a list, checked
         against the activity keys, or (None) every key but the garbage tracks that
@@ -804,11 +893,8 @@ class Enhancer:
             out[speaker_id] = self.istft(X_hat)
         return out
 
-    def _blocks_front(self, obs, ex_array_activity, ex, debug, wpe_arrays):
-        """The target-independent blocks of the block path: STFT, WPE (joint or per array),
-        activity, GSS and the zeroed context frames.  Returns Obs, acitivity_freq, masks and
-        (start_context_frames, end_context_frames) or None without bf_drop_context."""
-        Obs = self.stft(obs)
+    def _blocks_wpe(self, Obs, debug, wpe_arrays):
+        """The WPE block on an STFT (D,T,F): joint, per array, or none."""
         if self.wpe_block is not None and wpe_arrays > 1:
             _A = wpe_arrays
             Obs = morph('A*CTF->ACTF', Obs, A=_A)
@@ -816,6 +902,13 @@ class Enhancer:
             Obs = morph('ACTF->A*CTF', Obs)
         elif self.wpe_block is not None:
             Obs = self.wpe_block(Obs, debug=debug)
+        return Obs
+
+    def _blocks_front(self, obs, ex_array_activity, ex, debug, wpe_arrays):
+        """The target-independent blocks of the block path: STFT, WPE (joint or per array),
+        activity, GSS and the zeroed context frames.  Returns Obs, acitivity_freq, masks and
+        (start_context_frames, end_context_frames) or None without bf_drop_context."""
+        Obs = self._blocks_wpe(self.stft(obs), debug, wpe_arrays)
         acitivity_freq = activity_time_to_frequency(
             np.array(list(ex_array_activity.values())),
             stft_window_length=self.stft_size, stft_shift=self.stft_shift,

@@ -80,8 +80,12 @@ __host__ __device__ __forceinline__ int mseg_count(const MsegPlan &p, int f) {
 
 struct EmArgs {
     const cplx *Y;          // (F,T,D)
-    const uint8_t *act;     // (K,act_stride), first T columns used
-    int64_t act_stride;
+    // guidance (EmGuide), offset to the block's first frequency: element (f, k, t) at
+    // [f * fstride + k * stride + t], fstride 0 = one (K, T) table for every frequency
+    const uint8_t *act;     // source activity mask; always readable, used when `masked`
+    int64_t act_stride, act_fstride;
+    const double *init;     // initial affiliations (MODE_FIRST), NULL = derived from the mask
+    int64_t init_stride, init_fstride;
     const double *logdet;   // (F,K)
     const double *pi;       // (F,K)
     double *W;              // (F,K,T) M-step weights gamma / q
@@ -183,6 +187,7 @@ __global__ __launch_bounds__(256) void em_estep_kernel(EmArgs a, const cplx *__r
     const int64_t c1 = c0 + a.chunk_frames < T ? c0 + a.chunk_frames : T;
     const cplx *Yf = a.Y + (int64_t)f * T * D;
     const cplx *Mf = Mq + (int64_t)f * NE * K;
+    const uint8_t *actf = a.act + (int64_t)f * a.act_fstride;
 
     if (MODE != MODE_FIRST && tid < K) {
         ldet[tid] = a.logdet[f * K + tid];
@@ -197,16 +202,30 @@ __global__ __launch_bounds__(256) void em_estep_kernel(EmArgs a, const cplx *__r
         const int64_t t = t0 + tl;
         const bool valid = t < c1;
         if (MODE == MODE_FIRST) {
+            if (a.init != nullptr) {
+                // fit(initialization=array): the affiliations as given, not renormalised
+                const double *initf = a.init + (int64_t)f * a.init_fstride;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int k = g + 4 * s;
+                    if (k < K && valid) {
+                        const double gk = initf[(int64_t)k * a.init_stride + t];
+                        sg[s] += gk;
+                        a.W[((int64_t)f * K + k) * T + t] = gk;      // quadratic form = 1
+                    }
+                }
+                continue;
+            }
             // GSS initialisation (core.py:156-160): where(act == 0, 1e-10, act) / sum_k
             double ssum = 0.0;
 #pragma unroll
             for (int k = 0; k < K; ++k)
-                ssum += (valid && a.act[(int64_t)k * a.act_stride + t]) ? 1.0 : 1e-10;
+                ssum += (valid && actf[(int64_t)k * a.act_stride + t]) ? 1.0 : 1e-10;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int k = g + 4 * s;
                 if (k < K && valid) {
-                    const double v = a.act[(int64_t)k * a.act_stride + t] ? 1.0 : 1e-10;
+                    const double v = actf[(int64_t)k * a.act_stride + t] ? 1.0 : 1e-10;
                     const double gk = v / ssum;
                     sg[s] += gk;
                     a.W[((int64_t)f * K + k) * T + t] = gk;          // quadratic form = 1
@@ -278,7 +297,7 @@ __global__ __launch_bounds__(256) void em_estep_kernel(EmArgs a, const cplx *__r
             const int k = g + 4 * s;
             if (k < K) {
                 double v = exp(lpS[k * EM_TILE + tl] - mx) * pis[k];
-                if (a.masked) v *= (valid && a.act[(int64_t)k * a.act_stride + t]) ? 1.0 : 0.0;
+                if (a.masked) v *= (valid && actf[(int64_t)k * a.act_stride + t]) ? 1.0 : 0.0;
                 vvS[k * EM_TILE + tl] = v;
             }
         }
@@ -480,7 +499,8 @@ __global__ __launch_bounds__(256) void em_estep_reg_kernel(EmArgs a, const cplx 
     }
     uint8_t act[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) act[k] = a.act[(int64_t)k * a.act_stride + (tcl < 0 ? 0 : tcl)];
+    for (int k = 0; k < K; ++k)
+        act[k] = a.act[(int64_t)f * a.act_fstride + (int64_t)k * a.act_stride + (tcl < 0 ? 0 : tcl)];
     double v[K], iq[K], ssum = 0.0;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -1373,9 +1393,14 @@ extern "C" int gss_debug_em4_phase(long long *host, int entries) {
 struct OnchipArgs {
     cplx *basis;            // (F, K, 16) eigenvectors of flagged classes, one EM iteration back
     const cplx *Yn;         // (F, 4, T) unit-normalised observation
-    const uint8_t *act;     // (K, act_stride)
-    int64_t act_stride, T;
+    // guidance (EmGuide): element (f, k, t) at [f * fstride + k * stride + t]
+    const uint8_t *act;     // source activity mask; always readable, used unless `unmasked`
+    int64_t act_stride, act_fstride;
+    const double *init;     // initial affiliations, NULL = derived from the mask
+    int64_t init_stride, init_fstride;
+    int64_t T;
     int F, iterations, iterations_post, force_eigh;
+    int unmasked;           // no source activity mask: every step is unmasked
     const int *zero_tiles;  // (F, ntile) em_prepare_kernel's flags: frames on the clamp
     int ntile;
     int cold_eigh;          // GSS_VARIANT em4_cold_eigh: every eigendecomposition from the identity
@@ -1521,6 +1546,7 @@ __global__ __launch_bounds__(256, 3) void em_onchip4_kernel(OnchipArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const cplx *yf = a.Yn + (int64_t)f * D * T;
+    const uint8_t *actf = a.act + (int64_t)f * a.act_fstride;
     double (*wS)[OC_LD] = ldsS[wave];                  // K weight rows of this wave
     double (*pS)[OC_LD] = ldsS[wave] + K;              // NP product rows of this wave
     const int nsub = (int)((T + OC_FRAMES - 1) / OC_FRAMES);
@@ -1541,7 +1567,7 @@ __global__ __launch_bounds__(256, 3) void em_onchip4_kernel(OnchipArgs a) {
     for (int it = 0; it <= n_fit; ++it) {
         const bool first = it == 0 && a.iterations > 0;
         const bool predict = it == n_fit;
-        const bool masked = predict ? a.iterations_post == 0 : it < a.iterations;
+        const bool masked = !a.unmasked && (predict ? a.iterations_post == 0 : it < a.iterations);
         const double aff_eps = predict ? 0.0 : 1e-10;
         // (the two workgroups of a CU end together: the older one ran 19 % ahead)
         if (GSS_EM4_PRIO) set_progress_priority(it, n_fit + 1);
@@ -1558,7 +1584,7 @@ __global__ __launch_bounds__(256, 3) void em_onchip4_kernel(OnchipArgs a) {
 #pragma unroll
             for (int d = 0; d < D; ++d) yn[d] = yf[(int64_t)d * T + tc];
 #pragma unroll
-            for (int k = 0; k < K; ++k) an[k] = a.act[(int64_t)k * a.act_stride + tc];
+            for (int k = 0; k < K; ++k) an[k] = actf[(int64_t)k * a.act_stride + tc];
         };
         fetch(0);
         for (int sub = 0; sub < nsub; ++sub) {
@@ -1594,7 +1620,16 @@ __global__ __launch_bounds__(256, 3) void em_onchip4_kernel(OnchipArgs a) {
                     }
             }
             double q[K], gam[K], wgt[K];
-            if (first) {
+            if (first && a.init != nullptr) {
+                // fit(initialization=array): the affiliations as given, not renormalised; q = 1
+                // (one iteration of many: loaded here, not ahead with the frame)
+                const double *initf = a.init + (int64_t)f * a.init_fstride + (valid ? t : T - 1);
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    q[k] = 1.0;
+                    wgt[k] = gam[k] = initf[(int64_t)k * a.init_stride];
+                }
+            } else if (first) {
                 // GSS initialisation (core.py:156-160): where(act == 0, 1e-10, act) / sum_k; q = 1
                 double ssum = 0.0;
 #pragma unroll
@@ -2198,8 +2233,8 @@ struct StreamRestore {
 };
 }   // namespace
 
-int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const uint8_t *act,
-               int64_t act_stride, int K, int iterations, int iterations_post, double *gamma) {
+int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGuide &guide, int K,
+               int iterations, int iterations_post, double *gamma) {
     const int NE = tri_count(D);
     const bool reg = estep_reg_supported(D, K) && !gss_variant_set("estep_lds");
     // one array: the whole EM (all iterations + predict) in one launch (em_onchip4_kernel)
@@ -2230,6 +2265,12 @@ int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const uint8
     GSS_REQUIRE(ctx, em_estep_lds(D, K) <= 160 * 1024 &&
                          wcov_lds_layout(D, std::min(K, 8)).total <= 160 * 1024,
                 GSS_ERR_UNSUPPORTED, "cacgmm: D=%d K=%d LDS", D, K);
+    // No mask: every step is unmasked.  Two kernels fetch the mask bytes of a frame before they
+    // know whether the step uses them, so they get something readable: the first bytes of Yn.
+    const bool has_mask = guide.mask != nullptr;
+    const uint8_t *const act = has_mask ? guide.mask : reinterpret_cast<const uint8_t *>(Yn);
+    const int64_t act_stride = has_mask ? guide.mask_k_stride : 0;
+    const int64_t act_fstride = has_mask ? guide.mask_f_stride : 0;
     const int m = D + (D & 1);
     const size_t eigh_lds = (sizeof(cplx) * 2 * m * m + sizeof(double) * m + 15) / 16 * 16;
     const int force_eigh = gss_variant_set("force_eigh");
@@ -2245,8 +2286,12 @@ int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const uint8
         b.stream = stream;
         EmArgs &a = b.a;
         a.Y = Y + (int64_t)f0 * T * D;
-        a.act = act;
+        a.act = act + (int64_t)f0 * act_fstride;
         a.act_stride = act_stride;
+        a.act_fstride = act_fstride;
+        a.init = guide.init ? guide.init + (int64_t)f0 * guide.init_f_stride : nullptr;
+        a.init_stride = guide.init_k_stride;
+        a.init_fstride = guide.init_f_stride;
         a.T = T;
         a.F = Fb;
         a.D = D;
@@ -2335,6 +2380,11 @@ int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const uint8
         o.Yn = Yn;
         o.act = act;
         o.act_stride = act_stride;
+        o.act_fstride = act_fstride;
+        o.init = guide.init;
+        o.init_stride = guide.init_k_stride;
+        o.init_fstride = guide.init_f_stride;
+        o.unmasked = has_mask ? 0 : 1;
         o.T = T;
         o.F = F;
         o.iterations = iterations;
@@ -2387,7 +2437,7 @@ int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const uint8
         GSS_TRY(each([&](EmBlock &b) { return prepare(b); }));
         for (int it = 0; it < iterations; ++it)
             GSS_TRY(each([&](EmBlock &b) {
-                b.a.masked = 1;
+                b.a.masked = has_mask ? 1 : 0;
                 b.a.aff_eps = 1e-10;
                 return em_iteration(b, it == 0);
             }));
@@ -2400,7 +2450,7 @@ int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const uint8
             }));
         // predict: affiliation_eps = 0; mask only when iterations_post == 0
         GSS_TRY(each([&](EmBlock &b) {
-            b.a.masked = iterations_post == 0 ? 1 : 0;
+            b.a.masked = has_mask && iterations_post == 0 ? 1 : 0;
             b.a.aff_eps = 0.0;
             return estep(b, MODE_PREDICT);
         }));

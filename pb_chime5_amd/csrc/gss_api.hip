@@ -623,8 +623,55 @@ extern "C" int gss_cacgmm(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int
                 "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
                 "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
     GSS_TRY(arena_reserve(ctx, cacgmm_workspace_bytes(F, T, D, K)));
-    return cacgmm_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, act, T, K, iterations,
-                      post, gamma);
+    return cacgmm_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D,
+                      em_guide_from_activity(act, T), K, iterations, post, gamma);
+}
+
+// The descriptor's rules (include/gss_hip.h) -> the EM's view of it.  The values behind the
+// pointers are not looked at.
+static int check_guidance(gss_ctx *ctx, const gss_guidance *g, int K, int64_t T, EmGuide *out) {
+    GSS_REQUIRE(ctx, g, GSS_ERR_INVALID, "guidance is NULL");
+    GSS_REQUIRE(ctx, g->init_dev || g->mask_dev, GSS_ERR_INVALID,
+                "guidance: init_dev and mask_dev are both NULL");
+    if (g->init_dev) {
+        GSS_REQUIRE(ctx, g->init_k_stride >= T, GSS_ERR_INVALID,
+                    "guidance: init_k_stride %lld is smaller than T = %lld",
+                    (long long)g->init_k_stride, (long long)T);
+        GSS_REQUIRE(ctx, g->init_f_stride == 0 || g->init_f_stride >= K * g->init_k_stride,
+                    GSS_ERR_INVALID, "guidance: init_f_stride %lld is smaller than K * "
+                    "init_k_stride = %lld", (long long)g->init_f_stride,
+                    (long long)(K * g->init_k_stride));
+    }
+    if (g->mask_dev) {
+        GSS_REQUIRE(ctx, g->mask_k_stride >= T, GSS_ERR_INVALID,
+                    "guidance: mask_k_stride %lld is smaller than T = %lld",
+                    (long long)g->mask_k_stride, (long long)T);
+        GSS_REQUIRE(ctx, g->mask_f_stride == 0 || g->mask_f_stride >= K * g->mask_k_stride,
+                    GSS_ERR_INVALID, "guidance: mask_f_stride %lld is smaller than K * "
+                    "mask_k_stride = %lld", (long long)g->mask_f_stride,
+                    (long long)(K * g->mask_k_stride));
+    }
+    *out = EmGuide{g->init_dev, g->mask_dev, g->init_dev ? g->init_f_stride : 0,
+                   g->init_dev ? g->init_k_stride : 0, g->mask_dev ? g->mask_f_stride : 0,
+                   g->mask_dev ? g->mask_k_stride : 0};
+    return GSS_OK;
+}
+
+extern "C" int gss_cacgmm_guided(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                                 const gss_guidance *g, int K, int iterations, int post,
+                                 double *gamma) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, Y && gamma && F >= 1 && T >= 1, GSS_ERR_INVALID,
+                "gss_cacgmm_guided: bad arguments");
+    GSS_TRY(check_cacgmm_args(ctx, D, K, iterations, post));
+    EmGuide guide;
+    GSS_TRY(check_guidance(ctx, g, K, T, &guide));
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(arena_reserve(ctx, cacgmm_workspace_bytes(F, T, D, K)));
+    return cacgmm_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, guide, K, iterations, post,
+                      gamma);
 }
 
 extern "C" int gss_masks_from_posteriors(gss_ctx *ctx, const double *gamma, int F, int K,
@@ -832,9 +879,10 @@ static size_t targets_workspace(const gss_params *p, int F, int64_t T, int64_t T
 
 // Checks of the fused pipeline that do not depend on the target(s): before ...
 static int check_pipeline_front(gss_ctx *ctx, const gss_params *p, const void *obs, int D,
-                                int64_t N, const uint8_t *act, const void *out, const char *what) {
+                                int64_t N, const void *act, const void *out, const char *what) {
     GSS_TRY(check_windows(ctx));
     GSS_TRY(check_params(ctx, p));
+    // (`act`: the time-domain activity, or the descriptor of a guided call)
     GSS_REQUIRE(ctx, obs && act && out && N >= 1, GSS_ERR_INVALID, "%s: bad arguments", what);
     GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED, "D=%d", D);
     return GSS_OK;
@@ -887,10 +935,12 @@ static int alloc_front(gss_ctx *ctx, const gss_params *p, int F, int64_t T, int6
 
 // STFT, WPE (joint or per array), frame activity and the guided CACGMM of one window: obs ->
 // X (F,T,D) and gamma (F,K,T), nothing of it depending on a target.  Stage workspace above
-// `mark` is released after each stage.
+// `mark` is released after each stage.  `guide` (a guided call): the model's guidance per STFT
+// frame as the caller gives it, instead of the frame activity made from `act`.
 static int run_front(gss_ctx *ctx, const gss_params *p, const void *obs, int obs_type, int D,
                      int64_t N, const uint8_t *act, int K, int64_t N_act, int F, int64_t T,
-                     int64_t T_act, const PipelineFront &fr, size_t mark) {
+                     int64_t T_act, const PipelineFront &fr, size_t mark,
+                     const EmGuide *guide = nullptr) {
     cplx *const Y = fr.Y, *const X = fr.X;
     GSS_TRY(stft_run(ctx, obs, obs_type, D, N, p->stft_fading, Y));
     if (!p->wpe)    // no solve in this call: clear the count an earlier utterance left behind
@@ -908,9 +958,9 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const void *obs, int obs
         GSS_TRY(wpe_arrays_regroup_run(ctx, Y, F, T, A, D / A, false, X));
         ctx->arena_off = mark;
     }
-    GSS_TRY(activity_run(ctx, act, K, N_act, p->stft_fading, fr.actf));
-    GSS_TRY(cacgmm_run(ctx, X, F, T, D, fr.actf, T_act, K, p->bss_iterations,
-                       p->bss_iterations_post, fr.gamma));
+    if (!guide) GSS_TRY(activity_run(ctx, act, K, N_act, p->stft_fading, fr.actf));
+    GSS_TRY(cacgmm_run(ctx, X, F, T, D, guide ? *guide : em_guide_from_activity(fr.actf, T_act), K,
+                       p->bss_iterations, p->bss_iterations_post, fr.gamma));
     ctx->arena_off = mark;
     return GSS_OK;
 }
@@ -936,8 +986,17 @@ static int copy_front_taps(gss_ctx *ctx, const gss_debug_taps *taps, const Pipel
 static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const void *obs,
                                     int obs_type, int D, int64_t N, const uint8_t *act, int K,
                                     int64_t N_act, int target, int64_t start_ctx, int64_t end_ctx,
-                                    double *out, const gss_debug_taps *taps) {
-    GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, act, out, "gss_enhance_observation"));
+                                    double *out, const gss_debug_taps *taps,
+                                    bool guided = false,
+                                    const gss_guidance *guidance = nullptr) {
+    GSS_REQUIRE(ctx, !guided || guidance, GSS_ERR_INVALID,
+                "gss_enhance_observation_guided: guidance is NULL");
+    GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, guided ? (const void *)guidance : act, out,
+                                 guided ? "gss_enhance_observation_guided"
+                                        : "gss_enhance_observation"));
+    GSS_REQUIRE(ctx, !guided || !taps || !taps->act_frames, GSS_ERR_INVALID,
+                "gss_enhance_observation_guided: taps->act_frames must be NULL (a guided call "
+                "has no frame activity)");
     GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
                 "target_index %d outside [0, %d)", target, K);
     // core.py:221-222
@@ -948,6 +1007,8 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     GSS_TRY(check_pipeline_rest(ctx, p, D, N, K, N_act, &T, &T_act));
     const int size = p->stft_size, shift = p->stft_shift, fading = p->stft_fading;
     const int F = size / 2 + 1;
+    EmGuide guide{};
+    if (guided) GSS_TRY(check_guidance(ctx, guidance, K, T, &guide));
 
     GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K)));
     PipelineFront fr;
@@ -958,7 +1019,8 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);
     GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
     const size_t mark = ctx->arena_off;
-    GSS_TRY(run_front(ctx, p, obs, obs_type, D, N, act, K, N_act, F, T, T_act, fr, mark));
+    GSS_TRY(run_front(ctx, p, obs, obs_type, D, N, act, K, N_act, F, T, T_act, fr, mark,
+                      guided ? &guide : nullptr));
     cplx *const X = fr.X;
 
     int64_t sf = 0, ef = 0;
@@ -1082,6 +1144,17 @@ extern "C" int gss_enhance_observation(gss_ctx *ctx, const gss_params *p, const 
     GSS_ENTER_VARIANTS(ctx);
     return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
                                     out, taps);
+}
+
+extern "C" int gss_enhance_observation_guided(gss_ctx *ctx, const gss_params *p,
+                                              const double *obs, int D, int64_t N,
+                                              const gss_guidance *guidance, int K, int target,
+                                              int64_t start_ctx, int64_t end_ctx, double *out,
+                                              const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    // (the frame counts of observation and guidance are one: N_act = N)
+    return enhance_observation_impl(ctx, p, obs, 0, D, N, nullptr, K, N, target, start_ctx,
+                                    end_ctx, out, taps, /*guided=*/true, guidance);
 }
 
 extern "C" int gss_enhance_observation_pcm16(gss_ctx *ctx, const gss_params *p,

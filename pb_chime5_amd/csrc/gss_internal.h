@@ -257,8 +257,21 @@ int wpe_arrays_regroup_run(gss_ctx *ctx, const cplx *src, int F, int64_t T, int 
 int aux_stream_ready(gss_ctx *ctx);
 
 size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K);
-int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const uint8_t *act,
-               int64_t act_stride, int K, int iterations, int iterations_post, double *gamma);
+// What guides the mixture model (gss_guidance on the device side): initial affiliations and
+// source activity mask, element (f, k, t) at [f * f_stride + k * k_stride + t]; f stride 0 =
+// one (K, T) table for every frequency.  init NULL: the initialisation is derived from the mask
+// (core.py:156-160); mask NULL: every step is unmasked.
+struct EmGuide {
+    const double *init;
+    const uint8_t *mask;
+    int64_t init_f_stride, init_k_stride, mask_f_stride, mask_k_stride;
+};
+// the (K, act_stride) frame activity of the unweighted calls
+static inline EmGuide em_guide_from_activity(const uint8_t *act, int64_t act_stride) {
+    return EmGuide{nullptr, act, 0, 0, 0, act_stride};
+}
+int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGuide &guide, int K,
+               int iterations, int iterations_post, double *gamma);
 
 // S > 1: S targets' weights (S, F, 2, T) -> partials (S, F, nch, 2, NE), one launch
 int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,

@@ -9,6 +9,7 @@ here                        reference call (file:line)
 ``stft`` / ``istft``        nara_wpe.utils.stft / istft   (core.py:305-321)
 ``wpe_v8``                  nara_wpe.wpe.wpe_v8           (core.py:52-58)
 ``cacgmm_posteriors``       CACGMMTrainer.fit + predict   (core.py:165-208)
+``cacgmm_posteriors_guided``  the same from any initialisation / source_activity_mask
 ``mvdr_souden_from_masks``  pb_bss beamformer chain       (beamforming_wrapper.py:51-97)
 ``enhance_observation``     Enhancer.enhance_observation  (core.py:514-571)
 =========================  ====================================================
@@ -20,7 +21,7 @@ import ctypes
 import numpy as np
 
 from . import _capi
-from ._capi import Context, GssDebugTaps, GssParams, c_void_p, default_context
+from ._capi import Context, GssDebugTaps, GssGuidance, GssParams, c_void_p, default_context
 
 _BF_CODES = {'mvdrSouden_ban': 0, 'ch2': 1, 'sum': 2, 'gev_ban': 3}
 _POSTFILTER_CODES = {None: 0, 'mask_mul': 1}
@@ -255,6 +256,106 @@ def cacgmm_posteriors(Obs, activity_freq, iterations=20, iterations_post=1, *, c
     ctx._check(ctx.lib.gss_cacgmm(ctx.handle, c_void_p(Y_d.ptr), F, T, D, c_void_p(act_d.ptr),
                                   K, int(iterations), int(iterations_post),
                                   c_void_p(g_d.ptr)), 'gss_cacgmm')
+    # (F, K*T) -> (K*T, F)
+    ctx._check(ctx.lib.gss_layout_permute_f64(ctx.handle, c_void_p(g_d.ptr), F, K * T, 1, 2,
+                                              c_void_p(o_d.ptr)), 'gss_layout_permute_f64')
+    return ctx.to_host(o_d, (K, T, F), np.float64)
+
+
+def guidance_from_activity(activity_freq):
+    """core.py:156-163 on the host: activity (K,T) or (K,T,F), any dtype -> (initialization
+    float64, source_activity_mask bool) of the same shape.  The initialisation is computed
+    from the activity AS FLOAT64, so a value of 0.3 is a weight of 0.3:
+    ``where(a == 0, 1e-10, a) / sum_k``; the mask is ``a != 0``."""
+    initialization = np.asarray(activity_freq, dtype=np.float64)
+    initialization = np.where(initialization == 0, 1e-10, initialization)
+    initialization = initialization / np.sum(initialization, keepdims=True, axis=0)
+    return initialization, np.asarray(activity_freq, dtype=bool)
+
+
+def activity_is_binary(activity_freq, initialization=None):
+    """Whether ``GSS.__call__`` may take the unweighted call (`cacgmm_posteriors`): a (K,T)
+    activity whose non-zero values are all 1 (bool, uint8, 0/1 floats) and no explicit
+    initialisation.  Weights, NaN, a per-frequency (K,T,F) activity or an initialisation need
+    the guided call -- the unweighted one would binarise them."""
+    if initialization is not None:
+        return False
+    a = np.asarray(activity_freq)
+    if a.ndim != 2:
+        return False
+    if a.dtype == bool:
+        return True
+    return bool(np.all((a == 0) | (a == 1)))
+
+
+def guidance_tables(initialization, source_activity_mask, T, F):
+    """Shape rules of the guided calls.  Each table is (K,T') for all frequencies or
+    (K,T',F) -- the layout posteriors come out in --, T' >= T (cut to T like the activity:
+    core.py:177-184); at least one is given.  Returns (init, mask, K): float64 / uint8 arrays,
+    C-contiguous, (K,T) or (F,K,T), or None.  ValueError for anything else."""
+    if initialization is None and source_activity_mask is None:
+        raise ValueError('guidance: initialization and source_activity_mask are both None')
+    out, K = [], None
+    for name, table, dtype in (('initialization', initialization, np.float64),
+                               ('source_activity_mask', source_activity_mask, np.uint8)):
+        if table is None:
+            out.append(None)
+            continue
+        a = np.asarray(table)
+        if dtype is np.uint8:
+            a = a != 0
+        if a.ndim not in (2, 3):
+            raise ValueError(f'{name}: shape {a.shape} is neither (K,T) nor (K,T,F)')
+        if a.shape[1] < T:
+            raise ValueError(f'{name}: {a.shape[1]} frames but the observation has {T}')
+        if a.ndim == 3 and a.shape[2] != F:
+            raise ValueError(f'{name}: {a.shape[2]} frequencies but the observation has {F}')
+        if K is not None and a.shape[0] != K:
+            raise ValueError(f'{name}: {a.shape[0]} classes but initialization has {K}')
+        K = a.shape[0]
+        a = a[:, :T]
+        if a.ndim == 3:
+            a = a.transpose(2, 0, 1)     # (F,K,T)
+        out.append(np.ascontiguousarray(a, dtype=dtype))
+    return out[0], out[1], K
+
+
+class DeviceGuidance:
+    """Guidance tables (as `guidance_tables` returns them) in HBM and their gss_guidance."""
+
+    def __init__(self, ctx, init, mask, T):
+        self.init_d = ctx.to_device(init) if init is not None else None
+        self.mask_d = ctx.to_device(mask) if mask is not None else None
+        K = (init if init is not None else mask).shape[-2]
+
+        def f_stride(a):
+            return K * T if a is not None and a.ndim == 3 else 0
+        self.struct = GssGuidance(
+            init_dev=self.init_d.ptr if self.init_d else None,
+            mask_dev=self.mask_d.ptr if self.mask_d else None,
+            init_f_stride=f_stride(init), init_k_stride=T,
+            mask_f_stride=f_stride(mask), mask_k_stride=T)
+
+
+def cacgmm_posteriors_guided(Obs, initialization=None, source_activity_mask=None,
+                             iterations=20, iterations_post=1, *, ctx=None):
+    """``CACGMMTrainer.fit(y, initialization, iterations, source_activity_mask=...)`` and the
+    post step of ``GSS.__call__`` for every frequency: Obs (D,T,F) complex; initialization
+    (K,T) or (K,T,F) float, used as given (None: derived from the mask as core.py:156-159);
+    source_activity_mask (K,T) or (K,T,F), non-zero = active (None: every step unmasked)
+    -> posterior (K,T,F) float64.  Tables longer than T are cut."""
+    Obs = np.asarray(Obs)
+    if Obs.ndim != 3:
+        raise ValueError(f'Obs: shape {Obs.shape} is not (D,T,F)')
+    init, mask, K = guidance_tables(initialization, source_activity_mask, *Obs.shape[1:])
+    ctx = ctx or default_context()
+    Y_d, (D, T, F) = _obs_to_device_ftd(ctx, Obs)
+    guide = DeviceGuidance(ctx, init, mask, T)
+    g_d = ctx.empty(8 * F * K * T)
+    o_d = ctx.empty(8 * F * K * T)
+    ctx._check(ctx.lib.gss_cacgmm_guided(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, ctypes.byref(guide.struct), K, int(iterations),
+        int(iterations_post), c_void_p(g_d.ptr)), 'gss_cacgmm_guided')
     # (F, K*T) -> (K*T, F)
     ctx._check(ctx.lib.gss_layout_permute_f64(ctx.handle, c_void_p(g_d.ptr), F, K * T, 1, 2,
                                               c_void_p(o_d.ptr)), 'gss_layout_permute_f64')
@@ -694,6 +795,66 @@ def enhance_observation(obs, activity, target_index, start_context_samples,
     return x_hat, details
 
 
+class GuidedUtterance:
+    """`ResidentUtterance` of a guided call: observation and per-frame guidance in HBM."""
+
+    def __init__(self, ctx, obs, initialization, source_activity_mask, params, wpe_arrays=None):
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2:
+            raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+        self.ctx = ctx
+        self.D, self.N = obs.shape
+        self.params = params = params_for(params, self.D, wpe_arrays)
+        self.T = stft_frames(self.N, params.stft_size, params.stft_shift, params.stft_fading)
+        init, mask, self.K = guidance_tables(initialization, source_activity_mask, self.T,
+                                             params.stft_size // 2 + 1)
+        self.n_out = int(ctx.lib.gss_istft_num_samples(
+            self.T, params.stft_size, params.stft_shift, params.stft_fading))
+        self.obs_d = ctx.to_device(obs)
+        self.guide = DeviceGuidance(ctx, init, mask, self.T)
+        self.out_d = ctx.empty(8 * max(self.n_out, 1))
+
+    def enqueue(self, target_index, start_context, end_context, taps=None):
+        ctx = self.ctx
+        ctx._check(ctx.lib.gss_enhance_observation_guided(
+            ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D, self.N,
+            ctypes.byref(self.guide.struct), self.K, int(target_index), int(start_context),
+            int(end_context), c_void_p(self.out_d.ptr),
+            ctypes.byref(taps) if taps is not None else None),
+            'gss_enhance_observation_guided')
+
+    result = ResidentUtterance.result
+
+
+def enhance_observation_guided(obs, initialization, source_activity_mask, target_index,
+                               start_context_samples, end_context_samples, *, params=None,
+                               window=None, debug=False, ctx=None, wpe_arrays=None,
+                               **param_kwargs):
+    """`enhance_observation` guided per STFT frame (gss_enhance_observation_guided): the tables
+    of `cacgmm_posteriors_guided`, (K,T) or (K,T,F) over the T frames of the observation's
+    STFT, take the place of the time-domain activity.  Everything else -- STFT, WPE,
+    beamformer, postfilter, iSTFT, ``debug`` details (without ``acitivity_freq``) -- as
+    there."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    params = params_for(params, np.shape(obs)[0], wpe_arrays)
+    ctx = ctx or default_context()
+    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
+    utt = GuidedUtterance(ctx, obs, initialization, source_activity_mask, params)
+    bufs, taps = _debug_taps(utt) if debug else ({}, None)
+    if debug:
+        del bufs['act_frames']
+        taps.act_frames = None
+    utt.enqueue(target_index, start_context_samples, end_context_samples, taps)
+    x_hat = utt.result()
+    if not debug:
+        return x_hat
+    details = _debug_details(utt, bufs)
+    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+    details['ref_channel'] = int(details['ref_channel'])
+    return x_hat, details
+
+
 _PER_TARGET = ('target_mask', 'distortion_mask', 'X_hat', 'ref_channel')
 
 
@@ -717,9 +878,12 @@ def _debug_details(utt, bufs, S=1):
     """The taps in the reference's layouts; the per-target ones stacked over S."""
     ctx, D, K, T = utt.ctx, utt.D, utt.K, utt.T
     F = utt.params.stft_size // 2 + 1
+    details = {}
+    if 'act_frames' in bufs:     # (a guided call has no frame activity)
+        details['acitivity_freq'] = ctx.to_host(bufs['act_frames'], (K, T), np.uint8).astype(bool)
     return {
         'Obs': _ftd_to_host_dtf(ctx, bufs['Obs_ftd'], D, T, F),
-        'acitivity_freq': ctx.to_host(bufs['act_frames'], (K, T), np.uint8).astype(bool),
+        **details,
         'posterior': ctx.to_host(bufs['gamma'], (F, K, T), np.float64).transpose(1, 2, 0),
         'target_mask': ctx.to_host(bufs['target_mask'], (S, F, T), np.float64).transpose(0, 2, 1),
         'distortion_mask': ctx.to_host(bufs['distortion_mask'], (S, F, T),

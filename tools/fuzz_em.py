@@ -12,7 +12,12 @@ yardstick was 30 x the distance between the oracle and a brute-force float64 EM 
 LAPACK's eigh with it -- a ratio between two float64 programs, with one case at 35.7 explained by
 hand two rounds running.)  The last line is a machine-written tally.
     python tools/fuzz_em.py [SEED] [CASES]
-GSS_FUZZ_ZEROS=1: every case with a block of frames that are zero in every channel."""
+GSS_FUZZ_ZEROS=1: every case with a block of frames that are zero in every channel.
+GSS_FUZZ_GUIDED=1: every case with weighted and per-frequency guidance (gss_cacgmm_guided): an
+(F,K,T) initialisation of random weights on the activity, for every frequency or one table for all,
+a mask with per-frequency holes, or no mask at all.  The referee takes a (K,T) activity only, so
+these cases are held to the oracle's last-bit movement alone (4 draws): GPU - oracle <= 5 x
+movement + 1e-9."""
 import os
 import sys
 import warnings
@@ -23,6 +28,33 @@ import numpy as np
 R = Path(__file__).resolve().parents[1]
 for p in (str(R), str(R / 'oracle'), str(R / 'tests')):
     sys.path.insert(0, p)
+
+
+def oracle_guided(oracle, obs, init, mask, it, post):
+    """obs (D,T,F), init (F,K,T), mask (F,K,T) bool or None -> (K,T,F): gss_block_batched's steps."""
+    trainer = oracle.CACGMMTrainer()
+    y = np.ascontiguousarray(obs.transpose(2, 1, 0))
+    cur = trainer.fit(y, init, iterations=it, source_activity_mask=mask)
+    if post == 0:
+        return cur.predict(y, source_activity_mask=mask).transpose(1, 2, 0)
+    if post != 1:
+        cur = trainer.fit(y, cur, iterations=post - 1)
+    return cur.predict(y).transpose(1, 2, 0)
+
+
+def draw_guidance(rng, act, F):
+    """Weighted, per-frequency guidance on the activity `act` (K,T): init (F,K,T), mask (F,K,T)
+    bool or None."""
+    K, T = act.shape
+    mask = np.repeat(act[None], F, axis=0)
+    if rng.integers(0, 2):
+        for f in range(F):                                       # holes that differ by frequency
+            a = int(rng.integers(0, T))
+            mask[f, int(rng.integers(0, K)), a:a + int(rng.integers(1, T))] = False
+    w = rng.uniform(0.05, 1.0, size=(F if rng.integers(0, 2) else 1, K, T))
+    init = np.repeat(w, F // w.shape[0], axis=0) * np.where(mask, 1.0, 1e-10)
+    init /= init.sum(axis=1, keepdims=True)
+    return init, (mask if rng.integers(0, 4) else None)
 
 
 def main():
@@ -83,8 +115,19 @@ def main():
         if os.environ.get('GSS_FUZZ_ONLY') and case != int(os.environ['GSS_FUZZ_ONLY']):
             continue
         res = {}
-        for side, fn in (('oracle', lambda: oracle.gss_block_batched(obs, act, iterations=it, iterations_post=post)),
-                         ('gpu', lambda: ops.cacgmm_posteriors(obs, act, it, post))):
+        sides = (('oracle', lambda: oracle.gss_block_batched(obs, act, iterations=it, iterations_post=post)),
+                 ('gpu', lambda: ops.cacgmm_posteriors(obs, act, it, post)))
+        guided = bool(os.environ.get('GSS_FUZZ_GUIDED'))
+        if guided:
+            # (a generator of its own: the stream above is the same with and without)
+            init, mask = draw_guidance(np.random.default_rng([seed, case, 13]), act, F)
+            tag['guided'] = dict(mask=mask is not None,
+                                 per_f=bool(F > 1 and not np.array_equal(init[0], init[-1])))
+            sides = (('oracle', lambda: oracle_guided(oracle, obs, init, mask, it, post)),
+                     ('gpu', lambda: ops.cacgmm_posteriors_guided(
+                         obs, init.transpose(1, 2, 0),
+                         None if mask is None else mask.transpose(1, 2, 0), it, post)))
+        for side, fn in sides:
             try:
                 res[side] = fn()
             except (AssertionError, NotImplementedError, np.linalg.LinAlgError) as e:
@@ -105,6 +148,21 @@ def main():
         if d_go < 1e-8:
             continue
         f = int(np.argmax(np.max(np.abs(g - o), axis=(0, 1))))
+        if guided:
+            eps, pr, yard = np.finfo(np.float64).eps, np.random.default_rng(20260929), 0.0
+            of = obs[..., f:f + 1]
+            for _ in range(4):
+                pert = of.real * (1 + eps * pr.choice([-1.0, 1.0], size=of.shape)) \
+                    + 1j * of.imag * (1 + eps * pr.choice([-1.0, 1.0], size=of.shape))
+                moved = oracle_guided(oracle, pert, init[f:f + 1],
+                                      None if mask is None else mask[f:f + 1], it, post)
+                yard = max(yard, float(np.max(np.abs(moved[..., 0] - o[..., f]))))
+            refereed += 1
+            worst_ratio = max(worst_ratio, d_go / max(yard, 1e-9))
+            if not d_go <= 5 * yard + 1e-9:
+                print('EM (guided): GPU-oracle', d_go, 'oracle last-bit movement', yard, 'frequency', f, tag)
+                bad += 1
+            continue
         r = ext_precision.guided_em(np.ascontiguousarray(obs[..., f].T), act, it, post)
         d_or = np.max(np.abs(o[..., f] - r))
         d_gr = np.max(np.abs(g[..., f] - r))
