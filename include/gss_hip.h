@@ -76,7 +76,10 @@ typedef enum {
  * compares gss_abi_version() with the GSS_ABI_VERSION it was written against before any other
  * call (and, for these three, looks the symbols up).  gss_cacgmm_guided and
  * gss_enhance_observation_guided (with the gss_guidance descriptor) were added the same way:
- * entry points only, no struct or argument list of an existing one changed, revision still 7. */
+ * entry points only, no struct or argument list of an existing one changed, revision still 7.
+ * So were gss_mvdr_souden_segments, gss_enhance_observation_segments and
+ * gss_last_segment_fallbacks with the gss_bf_segments descriptor (gss_params keeps its layout:
+ * the segment settings travel in a descriptor of their own). */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -283,6 +286,45 @@ int gss_last_ref_channels(gss_ctx *ctx, int32_t *ref_channels_host, int S);
  * (equally arbitrary) minimiser than this library. */
 int gss_last_wpe_zero_pivots(gss_ctx *ctx, int64_t *count_host);
 
+/* Segment-wise (piecewise time-invariant) MVDR: the time span of the beamformer statistics.
+ * The T frames are cut into B = ceil(T / segment_frames) segments, segment b = frames
+ * [b L, min(T, (b + 1) L)); its statistics window is segments max(0, b - context_segments) ..
+ * min(B - 1, b + context_segments).  Not in the reference, which has one window per call. */
+typedef struct {
+    int64_t segment_frames;   /* L: a positive multiple of 64 (the PSD kernel's frame tile)  */
+    int32_t context_segments; /* c >= 0: segments either side in a segment's statistics     */
+    double min_mass;          /* >= 0, finite: a window whose target or distortion mask sum */
+                              /* is below it takes the whole-window statistics (0: never)   */
+} gss_bf_segments;
+
+/* gss_mvdr_souden with one filter per segment.  Per (segment b, frequency f): Phi_X, Phi_N are
+ * the masked PSD matrices over the frames of b's statistics window (mask sum floored at 1e-10,
+ * as in gss_mvdr_souden), replaced by the whole-window matrices of f -- those of
+ * gss_mvdr_souden -- when min(sum of target mask, sum of distortion mask) over the window is
+ * below seg->min_mass; W[b,f] is the Souden solution of that pair (eps 1e-10, same LU / lstsq
+ * fallback).  ONE reference channel for the call: the SNR argmax with numerator and
+ * denominator summed over all (b, f), or ref_channel >= 0 as named by the caller (-1:
+ * choose).  w[b,f] = W[b,f][:, ref], with `ban` normalised against that segment's Phi_N, and
+ * Xhat[t,f] = w[t / L, f]^H y[f,t].  The observation is read once for the PSD accumulation
+ * and the number of launches does not depend on B or context_segments.
+ * Y (F,T,D), masks (F,T) -> Xhat (T,F); ref_channel_dev (device int32, may be NULL) receives
+ * the status word of gss_last_ref_channel, which works after this call (-1: non-finite SNR,
+ * Xhat filled with NaN).  With min_mass = 0 an empty window gives 0 / 0 = NaN under `ban`, as
+ * the reference's empty utterance does.
+ * GSS_ERR_INVALID (the message names the field): seg NULL, segment_frames < 64 or not a
+ * multiple of 64, context_segments < 0, min_mass negative or not finite, ref_channel outside
+ * [-1, D). */
+int gss_mvdr_souden_segments(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                             const double *target_mask_dev,
+                             const double *distortion_mask_dev, int ban, int ref_channel,
+                             const gss_bf_segments *seg, gss_cplx *Xhat_dev,
+                             int32_t *ref_channel_dev);
+
+/* Number of (segment, frequency) pairs of the last gss_mvdr_souden_segments /
+ * gss_enhance_observation_segments call on this context that fell back to the whole-window
+ * statistics (synchronises the stream, like gss_last_wpe_zero_pivots); 0 before any. */
+int gss_last_segment_fallbacks(gss_ctx *ctx, int64_t *count_host);
+
 /* beamform_gev_from_masks (beamforming_wrapper.py:77-89,192-208): masked PSD
  * matrices, principal generalised eigenvector of (Phi_X, Phi_N) with
  * w^H Phi_N w = 1 (phase arbitrary, as upstream), optional BAN, apply.
@@ -369,6 +411,21 @@ int gss_enhance_observation_guided(gss_ctx *ctx, const gss_params *params,
                                    int64_t start_context_samples,
                                    int64_t end_context_samples,
                                    double *out_dev, const gss_debug_taps *taps);
+
+/* gss_enhance_observation with the segment-wise beamformer in the place of the whole-window
+ * one: the masks (context frames zeroed) go through gss_mvdr_souden_segments with `ban`.
+ * Everything else, the debug taps and their shapes included, is gss_enhance_observation's;
+ * gss_last_ref_channel and gss_last_segment_fallbacks work afterwards.  params->bf must be 0
+ * ('mvdrSouden_ban'): GSS_ERR_UNSUPPORTED otherwise (the phase of a GEV filter is arbitrary per
+ * segment).  Errors of `seg` as gss_mvdr_souden_segments. */
+int gss_enhance_observation_segments(gss_ctx *ctx, const gss_params *params,
+                                     const double *obs_dev, int D, int64_t N,
+                                     const uint8_t *act_dev, int K, int64_t N_act,
+                                     int target_index,
+                                     int64_t start_context_samples,
+                                     int64_t end_context_samples,
+                                     const gss_bf_segments *seg,
+                                     double *out_dev, const gss_debug_taps *taps);
 
 /* Same pipeline fed with the 16-bit PCM samples as they sit in the WAV files: the
  * conversion of the reference's loader, float64(sample) / 2^15 (io/audioread.py:34-226 via

@@ -46,6 +46,12 @@ class GssGuidance(ctypes.Structure):
                 ('mask_f_stride', c_int64), ('mask_k_stride', c_int64)]
 
 
+class GssBfSegments(ctypes.Structure):
+    """gss_bf_segments: the time span of the beamformer statistics."""
+    _fields_ = [('segment_frames', c_int64), ('context_segments', ctypes.c_int32),
+                ('min_mass', ctypes.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/gss_hip.h declares
 SIGNATURES = {
     'gss_device_count': (c_int, []),
@@ -96,6 +102,10 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'gss_mvdr_souden_ref': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
                                     c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'gss_mvdr_souden_segments': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
+                                         c_void_p, c_void_p, c_int, c_int,
+                                         ctypes.POINTER(GssBfSegments), c_void_p, c_void_p]),
+    'gss_last_segment_fallbacks': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,
@@ -114,6 +124,10 @@ SIGNATURES = {
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 ctypes.POINTER(GssGuidance), c_int, c_int, c_int64, c_int64, c_void_p,
                 ctypes.POINTER(GssDebugTaps)]),
+    'gss_enhance_observation_segments': (
+        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
+                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
+                ctypes.POINTER(GssBfSegments), c_void_p, ctypes.POINTER(GssDebugTaps)]),
     'gss_enhance_observation_pcm16': (
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p,
@@ -377,6 +391,14 @@ class Context:
         out = ctypes.c_int64()
         self._check(self.lib.gss_last_wpe_zero_pivots(self.handle, ctypes.byref(out)),
                     'gss_last_wpe_zero_pivots')
+        return int(out.value)
+
+    def last_segment_fallbacks(self):
+        """(segment, frequency) pairs of the last segment-wise MVDR on this context that fell
+        back to the whole-window statistics (synchronises)."""
+        out = ctypes.c_int64()
+        self._check(self.lib.gss_last_segment_fallbacks(self.handle, ctypes.byref(out)),
+                    'gss_last_segment_fallbacks')
         return int(out.value)
 
     def workspace_bytes(self):

@@ -200,6 +200,31 @@ class Beamformer:
     """core.py:241-278."""
     type: str
     postfilter: str
+    # Time-varying MVDR (an addition): statistics per segment of ``segment_frames`` STFT frames
+    # (a positive multiple of 64) over ``segment_context`` segments either side, one reference
+    # channel per utterance; windows with less than ``segment_min_mass`` of target or
+    # distortion mask (None: 2 * channels) take the whole-utterance statistics.  None: one
+    # filter per utterance, the reference's beamformer.  Only 'mvdrSouden_ban' has it.
+    segment_frames: int = None
+    segment_context: int = 0
+    segment_min_mass: float = None
+
+    def __post_init__(self):
+        if self.segment_frames is None:
+            return
+        if self.type != 'mvdrSouden_ban':
+            raise NotImplementedError(
+                f"bf={self.type!r} with segment_frames: only 'mvdrSouden_ban' has a "
+                'segment-wise form')
+        ops.check_bf_segments(self.segment_frames, self.segment_context, self.segment_min_mass)
+
+    @property
+    def segments(self):
+        """The keyword arguments of the segment-wise calls in ``ops``, or None."""
+        if self.segment_frames is None:
+            return None
+        return dict(segment_frames=self.segment_frames, segment_context=self.segment_context,
+                    min_mass=self.segment_min_mass)
 
     def __call__(self, Obs, target_mask, distortion_mask, debug=False):
         bf = self.type
@@ -207,7 +232,9 @@ class Beamformer:
             from pb_chime5_amd.speech_enhancement.beamforming_wrapper import (
                 beamform_mvdr_souden_from_masks)
             X_hat = beamform_mvdr_souden_from_masks(
-                Y=Obs, X_mask=target_mask, N_mask=distortion_mask, ban=True)
+                Y=Obs, X_mask=target_mask, N_mask=distortion_mask, ban=True,
+                segment_frames=self.segment_frames, segment_context=self.segment_context,
+                segment_min_mass=self.segment_min_mass)
         elif bf == 'gev_ban':
             # not selectable in the reference's Beamformer.__call__ (core.py:246-266); the
             # GEV code path exists beside it (beamforming_wrapper.py:192-208)
@@ -376,7 +403,8 @@ class Enhancer:
         in flight on separate HIP streams: the host loads the next example's audio
         while the GPU works, and one utterance's latency-bound kernels overlap the
         other's compute-bound ones.  Results are identical to the one-at-a-time loop."""
-        if self.inflight <= 1 or not self._fusable():
+        # (a segment-wise beamformer has no pipelined pcm16 entry point: one at a time)
+        if self.inflight <= 1 or not self._fusable() or self._bf_segments() is not None:
             for ex in examples:
                 try:
                     self._write(ex, self.enhance_example(ex), audio_dir)
@@ -675,6 +703,16 @@ class Enhancer:
             and type(self.gss_block) is GSS and type(self.bf_block) is Beamformer
         )
 
+    def _bf_segments(self):
+        """The beamformer's segment settings (``Beamformer.segments``) or None."""
+        return getattr(getattr(self, 'bf_block', None), 'segments', None)
+
+    def _no_segments(self, what):
+        if self._bf_segments() is not None:
+            raise NotImplementedError(
+                f'{what} with bf_segment_frames: the segment-wise beamformer is built for '
+                'enhance_observation only')
+
     def _params(self):
         w = self.wpe_block
         return ops.make_params(
@@ -711,10 +749,16 @@ class Enhancer:
         # call may put half of the WPE stage's frequencies on the context's second stream
         ctx = self._ctx()
         ctx.set_utterances_in_flight(1)
+        segments = self._bf_segments()
         try:
-            res = ops.enhance_observation(
-                obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
-                debug=debug, ctx=ctx, wpe_arrays=wpe_arrays)
+            if segments is not None:
+                res = ops.enhance_observation_segments(
+                    obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
+                    debug=debug, ctx=ctx, wpe_arrays=wpe_arrays, **segments)
+            else:
+                res = ops.enhance_observation(
+                    obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
+                    debug=debug, ctx=ctx, wpe_arrays=wpe_arrays)
         finally:
             ctx.set_utterances_in_flight(0)
         if not debug:
@@ -744,6 +788,7 @@ class Enhancer:
         speaker in the initial affiliations (diarisation posteriors, annotation confidence).
         ``initialization``: optional dict of the same shape with initial affiliations used as
         given (a neural mask estimator's output).  ``fused=False`` runs the blocks."""
+        self._no_segments('enhance_observation_guided')
         if wpe_arrays is None:
             wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
         wpe_arrays = ops.check_wpe_arrays(wpe_arrays, np.shape(obs)[0])
@@ -839,6 +884,7 @@ class Enhancer:
         STFT, WPE and GSS run once; the fused path runs the target-dependent tail of all
         speakers together (gss_enhance_observation_targets), the block path calls
         ``bf_block`` and the iSTFT once per speaker."""
+        self._no_segments('enhance_observation_speakers')
         speaker_ids = self.speaker_ids_of(ex_array_activity, speaker_ids)
         if wpe_arrays is None:
             wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
@@ -872,6 +918,7 @@ class Enhancer:
     def enhance_example_speakers(self, ex, speaker_ids=None):
         """`enhance_example` for several speakers of the example's window at once: dict
         speaker_id -> x_hat, each trimmed like `enhance_example` trims its output."""
+        self._no_segments('enhance_example_speakers')
         obs, ex_array_activity, _ = self._prepare_example(ex)
         out = self.enhance_observation_speakers(obs, ex_array_activity, speaker_ids, ex=ex)
         return {k: self._trim_context(v, ex) for k, v in out.items()}
@@ -976,12 +1023,17 @@ def get_enhancer(
     iterator_factory=None,
     device_id=None,
     wpe_per_array=False,
+    bf_segment_frames=None,
+    bf_segment_context=0,
+    bf_segment_min_mass=None,
 ):
     """core.py:574-637 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory``, ``device_id`` and ``wpe_per_array`` are additions).
+    ``iterator_factory``, ``device_id``, ``wpe_per_array`` and ``bf_segment_*`` are additions).
     ``wpe_per_array=True``: with a multiarray mode, WPE runs on each microphone array on its
     own (the reference's ``WPE(..., stack=False)``), GSS and the beamformer on all channels;
-    no effect with ``multiarray=False`` or ``wpe=False``."""
+    no effect with ``multiarray=False`` or ``wpe=False``.
+    ``bf_segment_frames=L``: a time-varying 'mvdrSouden_ban' with statistics per segment of L
+    STFT frames (see `Beamformer`); None: one filter per utterance."""
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
 
@@ -997,7 +1049,9 @@ def get_enhancer(
         gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
                       verbose=False),
         bf_drop_context=bf_drop_context,
-        bf_block=Beamformer(type=bf, postfilter=postfilter),
+        bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
+                            segment_context=bf_segment_context,
+                            segment_min_mass=bf_segment_min_mass),
         stft_size=stft_size,
         stft_shift=stft_shift,
         stft_fading=stft_fading,

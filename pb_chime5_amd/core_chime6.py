@@ -141,9 +141,13 @@ def get_enhancer(
     iterator_factory=None,
     device_id=None,
     wpe_per_array=False,
+    bf_segment_frames=None,
+    bf_segment_context=0,
+    bf_segment_min_mass=None,
 ):
-    """core_chime6.py:572-635 (same keyword arguments and defaults; the last three are
-    additions)."""
+    """core_chime6.py:572-635 (same keyword arguments and defaults; ``activity_store``,
+    ``iterator_factory``, ``device_id``, ``wpe_per_array`` and ``bf_segment_*`` are additions,
+    see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
     return Enhancer(
@@ -158,7 +162,9 @@ def get_enhancer(
         gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
                       verbose=False),
         bf_drop_context=bf_drop_context,
-        bf_block=Beamformer(type=bf, postfilter=postfilter),
+        bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
+                            segment_context=bf_segment_context,
+                            segment_min_mass=bf_segment_min_mass),
         stft_size=stft_size,
         stft_shift=stft_shift,
         stft_fading=stft_fading,

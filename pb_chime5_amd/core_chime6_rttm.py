@@ -151,8 +151,12 @@ def get_enhancer(
 
     device_id=None,
     wpe_per_array=False,
+    bf_segment_frames=None,
+    bf_segment_context=0,
+    bf_segment_min_mass=None,
 ):
-    """core_chime6_rttm.py:360-422 (same keyword arguments and defaults)."""
+    """core_chime6_rttm.py:360-422 (same keyword arguments and defaults; ``device_id``,
+    ``wpe_per_array`` and ``bf_segment_*`` are additions, see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     db = get_database(chime6_dir, database_rttm, multiarray)
     return Enhancer(
@@ -166,7 +170,9 @@ def get_enhancer(
         gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
                       verbose=False),
         bf_drop_context=bf_drop_context,
-        bf_block=Beamformer(type=bf, postfilter=postfilter),
+        bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
+                            segment_context=bf_segment_context,
+                            segment_min_mass=bf_segment_min_mass),
         stft_size=stft_size,
         stft_shift=stft_shift,
         stft_fading=stft_fading,

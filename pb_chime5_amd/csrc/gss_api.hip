@@ -182,6 +182,7 @@ extern "C" int gss_create(int device_id, gss_ctx **out) {
     }
     ctx->status_host[0] = INT32_MIN;
     ctx->status_host[2] = 0;
+    ctx->status_host[GSS_STATUS_SEGMENT_FALLBACKS] = 0;
     *out = ctx;
     return GSS_OK;
 }
@@ -747,6 +748,45 @@ extern "C" int gss_last_wpe_zero_pivots(gss_ctx *ctx, int64_t *count) {
     return GSS_OK;
 }
 
+static int check_segments(gss_ctx *ctx, const gss_bf_segments *seg, const char *what) {
+    GSS_REQUIRE(ctx, seg, GSS_ERR_INVALID, "%s: seg is NULL", what);
+    GSS_REQUIRE(ctx, seg->segment_frames >= 64 && seg->segment_frames % 64 == 0, GSS_ERR_INVALID,
+                "%s: segment_frames = %lld is not a positive multiple of 64", what,
+                (long long)seg->segment_frames);
+    GSS_REQUIRE(ctx, seg->context_segments >= 0, GSS_ERR_INVALID,
+                "%s: context_segments = %d is negative", what, (int)seg->context_segments);
+    GSS_REQUIRE(ctx, std::isfinite(seg->min_mass) && seg->min_mass >= 0.0, GSS_ERR_INVALID,
+                "%s: min_mass = %g is negative or not finite", what, seg->min_mass);
+    return GSS_OK;
+}
+
+extern "C" int gss_mvdr_souden_segments(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                                        const double *mx, const double *mn, int ban,
+                                        int ref_channel, const gss_bf_segments *seg,
+                                        gss_cplx *Xhat, int32_t *ref) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, Y && mx && mn && Xhat && F >= 1 && T >= 1, GSS_ERR_INVALID,
+                "gss_mvdr_souden_segments: bad arguments");
+    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    GSS_REQUIRE(ctx, ref_channel >= -1 && ref_channel < D, GSS_ERR_INVALID,
+                "ref_channel %d outside [-1, %d)", ref_channel, D);
+    GSS_TRY(check_segments(ctx, seg, "gss_mvdr_souden_segments"));
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(arena_reserve(ctx, mvdr_segments_workspace_bytes(F, T, D, seg->segment_frames)));
+    return mvdr_segments_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mx, mn, ban, *seg,
+                             reinterpret_cast<cplx *>(Xhat), ref, ref_channel);
+}
+
+extern "C" int gss_last_segment_fallbacks(gss_ctx *ctx, int64_t *count) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, count, GSS_ERR_INVALID, "gss_last_segment_fallbacks: NULL");
+    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *count = __atomic_load_n(ctx->status_host + GSS_STATUS_SEGMENT_FALLBACKS, __ATOMIC_ACQUIRE);
+    return GSS_OK;
+}
+
 extern "C" int gss_gev(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D, const double *mx,
                        const double *mn, int ban, gss_cplx *Xhat) {
     GSS_ENTER(ctx);
@@ -849,14 +889,17 @@ static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, in
     return stage;
 }
 
+// (segment_frames > 0: the segment-wise beamformer in the place of the whole-window one)
 static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
-                                 int K) {
+                                 int K, int64_t segment_frames = 0) {
     size_t b = front_buffer_bytes(F, T, T_act, D, K);
     b += 2 * align_up(sizeof(double) * (size_t)F * T);       // masks
     b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
     b += 4096;
     size_t stage = front_stage_bytes(p, F, T, D, K);
-    stage = std::max(stage, mvdr_workspace_bytes(F, T, D));
+    stage = std::max(stage, segment_frames > 0
+                                ? mvdr_segments_workspace_bytes(F, T, D, segment_frames)
+                                : mvdr_workspace_bytes(F, T, D));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
     return b + stage + (1 << 16);
 }
@@ -988,7 +1031,8 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
                                     int64_t N_act, int target, int64_t start_ctx, int64_t end_ctx,
                                     double *out, const gss_debug_taps *taps,
                                     bool guided = false,
-                                    const gss_guidance *guidance = nullptr) {
+                                    const gss_guidance *guidance = nullptr,
+                                    const gss_bf_segments *seg = nullptr) {
     GSS_REQUIRE(ctx, !guided || guidance, GSS_ERR_INVALID,
                 "gss_enhance_observation_guided: guidance is NULL");
     GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, guided ? (const void *)guidance : act, out,
@@ -1010,7 +1054,8 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     EmGuide guide{};
     if (guided) GSS_TRY(check_guidance(ctx, guidance, K, T, &guide));
 
-    GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K)));
+    GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K,
+                                                  seg ? seg->segment_frames : 0)));
     PipelineFront fr;
     GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
     double *mx = arena_alloc_t<double>(ctx, (size_t)F * T);
@@ -1030,7 +1075,10 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     }
     GSS_TRY(masks_from_posteriors_run(ctx, fr.gamma, F, K, T, target, p->bf_drop_context, sf, ef,
                                       mx, mn));
-    if (p->bf == 0 || p->bf == 3) {
+    if (seg) {      // (bf == 0, checked by the entry point)
+        GSS_TRY(mvdr_segments_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, *seg, Xhat, ref));
+        ctx->arena_off = mark;
+    } else if (p->bf == 0 || p->bf == 3) {
         GSS_TRY(mvdr_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, Xhat, ref, /*gev=*/p->bf == 3));
         ctx->arena_off = mark;
     } else {
@@ -1155,6 +1203,21 @@ extern "C" int gss_enhance_observation_guided(gss_ctx *ctx, const gss_params *p,
     // (the frame counts of observation and guidance are one: N_act = N)
     return enhance_observation_impl(ctx, p, obs, 0, D, N, nullptr, K, N, target, start_ctx,
                                     end_ctx, out, taps, /*guided=*/true, guidance);
+}
+
+extern "C" int gss_enhance_observation_segments(gss_ctx *ctx, const gss_params *p,
+                                                const double *obs, int D, int64_t N,
+                                                const uint8_t *act, int K, int64_t N_act,
+                                                int target, int64_t start_ctx, int64_t end_ctx,
+                                                const gss_bf_segments *seg, double *out,
+                                                const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_TRY(check_segments(ctx, seg, "gss_enhance_observation_segments"));
+    GSS_REQUIRE(ctx, !p || p->bf == 0, GSS_ERR_UNSUPPORTED,
+                "gss_enhance_observation_segments: bf=%d, only 0 ('mvdrSouden_ban') has segments",
+                p->bf);
+    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, /*guided=*/false, nullptr, seg);
 }
 
 extern "C" int gss_enhance_observation_pcm16(gss_ctx *ctx, const gss_params *p,

@@ -163,6 +163,8 @@ struct gss_ctx {
     // Status words (mapped host memory).  [0]: the last beamformed utterance, written by
     // mvdr_apply_kernel: the reference channel, -1 = non-finite SNR; INT32_MIN = none yet.
     // [2]: pivots zeroed by the last WPE call (copied from the device counter by wpe_run).
+    // [3]: (segment, frequency) pairs of the last segment-wise MVDR that fell back to the
+    // whole-window statistics (copied from the device counter by mvdr_apply_kernel).
     // [GSS_STATUS_TARGETS + s]: target s of the last targets call (mvdr_apply_targets_kernel,
     // which writes target 0's word to [0] as well).
     int32_t *status_host = nullptr;
@@ -181,6 +183,7 @@ struct gss_ctx {
     std::string prof_filter;   // time only this kernel (empty: all)
 };
 
+#define GSS_STATUS_SEGMENT_FALLBACKS 3                           // see gss_ctx::status_host
 #define GSS_STATUS_TARGETS 16                                    // first per-target word
 #define GSS_STATUS_BYTES (4 * (GSS_STATUS_TARGETS + GSS_MAX_CLASSES + 1))
 
@@ -284,6 +287,14 @@ size_t mvdr_workspace_bytes(int F, int64_t T, int D, int S = 1);
 int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
              const double *mn, int ban, cplx *Xhat, int32_t *ref_channel, int gev = 0,
              int forced_ref = -1, int S = 1, bool targets = false);
+// Segment-wise (piecewise time-invariant) MVDR-Souden, include/gss_hip.h: gss_mvdr_souden_segments.
+// One pass over Y for the PSD partials of all segments, mvdr_solve_kernel on a (F, B) grid, one
+// reference channel over all (segment, frequency) pairs (forced_ref >= 0: the caller's), apply
+// with each segment's filter.  `seg` has been validated by the entry point.
+size_t mvdr_segments_workspace_bytes(int F, int64_t T, int D, int64_t segment_frames);
+int mvdr_segments_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
+                      const double *mn, int ban, const gss_bf_segments &seg, cplx *Xhat,
+                      int32_t *ref_channel, int forced_ref = -1);
 // The targets of masks_targets_kernel (by value): target class and zeroed context frames
 struct TargetMaskArgs {
     int S;

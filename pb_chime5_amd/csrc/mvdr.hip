@@ -544,10 +544,17 @@ __global__ __launch_bounds__(MVDR_REF_NT) void mvdr_ref_kernel(const cplx *__res
 }
 
 // w = W[:, ref] (optionally BAN-normalised), Xhat[t][f] = w^H y_t.  grid (chunks, F)
+// SEGMENTS (mvdr_segments_run): W (B,F,D,D) and Phi (B,F,2,D,D) hold one filter per segment
+// of seg_frames frames; chunk_frames divides seg_frames, so a workgroup's frames lie in one
+// segment and it takes that segment's w and Phi_N.  `fallbacks`: the call's device counter of
+// (segment, frequency) pairs that fell back, copied to its status word.  Without SEGMENTS
+// both arguments are unused: the whole-window instantiation is the kernel it always was.
+template <bool SEGMENTS>
 __global__ __launch_bounds__(256) void mvdr_apply_kernel(
     const cplx *__restrict__ Y, const cplx *__restrict__ W, const cplx *__restrict__ Phi,
     const int32_t *__restrict__ ref, int F, int64_t T, int D, int ban, int chunk_frames,
-    cplx *__restrict__ Xhat, int32_t *__restrict__ ref_out, int32_t *__restrict__ status) {
+    cplx *__restrict__ Xhat, int32_t *__restrict__ ref_out, int32_t *__restrict__ status,
+    int64_t seg_frames, const int32_t *__restrict__ fallbacks) {
     __shared__ cplx w[GSS_MAX_CHANNELS];
     __shared__ cplx t1[GSS_MAX_CHANNELS];
     __shared__ cplx t2[GSS_MAX_CHANNELS];
@@ -559,9 +566,17 @@ __global__ __launch_bounds__(256) void mvdr_apply_kernel(
         const int code = r == -2 ? -2 - ref[1] : r;
         if (ref_out) ref_out[0] = code;
         if (status) __hip_atomic_store(status, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (SEGMENTS)
+            __hip_atomic_store(status + GSS_STATUS_SEGMENT_FALLBACKS, fallbacks[0], __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
     }
     const int64_t c0 = (int64_t)blockIdx.x * chunk_frames;
     const int64_t c1 = c0 + chunk_frames < T ? c0 + chunk_frames : T;
+    if (SEGMENTS) {   // this workgroup's (segment, frequency) block of W and Phi
+        const int64_t blk = (c0 / seg_frames) * F;
+        W += blk * D * D;
+        Phi += blk * 2 * D * D;
+    }
     if (r < 0) {   // the reference raises (see above), nothing meaningful to write
         const double qnan = __longlong_as_double(0x7ff8000000000000LL);
         for (int64_t t = c0 + tid; t < c1; t += blockDim.x) Xhat[t * F + f] = c_make(qnan, qnan);
@@ -690,6 +705,117 @@ __global__ __launch_bounds__(256) void mvdr_apply_targets_kernel(
         for (int s = 0; s < SB; ++s)
             if (s < S)
                 Xhat[((int64_t)s * T + t) * F + f] = s_ref[s] >= 0 ? v[s] : c_make(qnan, qnan);
+    }
+}
+
+// ------------------------------------------------------------------ segment-wise MVDR
+// mask_pack_kernel with the mask sums per segment of seg_frames frames: grid (B, F), block
+// 256.  W2 (F, 2, T) as there; msum (F, B, 2).
+__global__ __launch_bounds__(256) void mask_pack_segments_kernel(
+    const double *__restrict__ mx, const double *__restrict__ mn, int64_t T, int64_t seg_frames,
+    double *__restrict__ W2, double *__restrict__ msum) {
+    __shared__ double red[8];
+    const int b = blockIdx.x, B = gridDim.x, f = blockIdx.y, tid = threadIdx.x;
+    const int64_t t0 = (int64_t)b * seg_frames;
+    const int64_t t1 = t0 + seg_frames < T ? t0 + seg_frames : T;
+    double sx = 0.0, sn = 0.0;
+    for (int64_t t = t0 + tid; t < t1; t += blockDim.x) {
+        const double a = mx[(int64_t)f * T + t], c = mn[(int64_t)f * T + t];
+        W2[((int64_t)f * 2) * T + t] = a;
+        W2[((int64_t)f * 2 + 1) * T + t] = c;
+        sx += a;
+        sn += c;
+    }
+    sx = wave_sum(sx);
+    sn = wave_sum(sn);
+    if ((tid & 63) == 0) {
+        red[tid >> 6] = sx;
+        red[4 + (tid >> 6)] = sn;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        msum[((int64_t)f * B + b) * 2] = (red[0] + red[1]) + (red[2] + red[3]);
+        msum[((int64_t)f * B + b) * 2 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+    }
+}
+
+// Statistics window of segment b at frequency f: the unnormalised sums of the PSD partials and
+// of the mask sums over segments max(0, b - ctx_seg) .. min(B - 1, b + ctx_seg), in ascending
+// order (a segment's partials are its nsub chunks of `part`, ascending).  A window whose target
+// or distortion mass is below min_mass takes the whole-window sums of its frequency instead
+// (`whole_*`, made by a first launch of this kernel with grid (F, 1), ctx_seg = B, min_mass = 0,
+// whole_part = NULL) and is counted in *fallbacks.  Output in the layout mvdr_solve_kernel
+// reads for "targets" b = 0 .. gridDim.y - 1 with one chunk each: wpart (B, F, 2, NE),
+// wmsum (B, F, 2).  grid (F, B or 1), block 256.
+__global__ __launch_bounds__(256) void mvdr_window_segments_kernel(
+    const cplx *__restrict__ part /* (F, nch, 2, NE) */,
+    const double *__restrict__ msum /* (F, B, 2) */, int nch, int nsub, int B, int ctx_seg, int NE,
+    double min_mass, const cplx *__restrict__ whole_part /* (F, 2, NE) */,
+    const double *__restrict__ whole_msum /* (F, 2) */, cplx *__restrict__ wpart,
+    double *__restrict__ wmsum, int32_t *__restrict__ fallbacks) {
+    __shared__ int s_fall;
+    const int f = blockIdx.x, b = blockIdx.y, F = gridDim.x, tid = threadIdx.x;
+    const int lo = b - ctx_seg > 0 ? b - ctx_seg : 0;
+    const int hi = b + ctx_seg < B - 1 ? b + ctx_seg : B - 1;
+    const int64_t out = (int64_t)b * F + f;
+    if (tid == 0) {
+        double sx = 0.0, sn = 0.0;
+        for (int s = lo; s <= hi; ++s) {
+            sx += msum[((int64_t)f * B + s) * 2];
+            sn += msum[((int64_t)f * B + s) * 2 + 1];
+        }
+        const bool fall = whole_part && (sx < min_mass || sn < min_mass);
+        if (fall) {
+            sx = whole_msum[f * 2];
+            sn = whole_msum[f * 2 + 1];
+            atomicAdd(fallbacks, 1);
+        }
+        wmsum[out * 2] = sx;
+        wmsum[out * 2 + 1] = sn;
+        s_fall = fall;
+    }
+    __syncthreads();
+    cplx *dst = wpart + out * 2 * NE;
+    if (s_fall) {
+        for (int e = tid; e < 2 * NE; e += blockDim.x) dst[e] = whole_part[(int64_t)f * 2 * NE + e];
+        return;
+    }
+    const int ch0 = lo * nsub, ch1 = (hi + 1) * nsub < nch ? (hi + 1) * nsub : nch;
+    for (int e = tid; e < 2 * NE; e += blockDim.x) {
+        cplx v = c_make(0.0, 0.0);
+        for (int c = ch0; c < ch1; ++c) v = c_add(v, part[((int64_t)f * nch + c) * 2 * NE + e]);
+        dst[e] = v;
+    }
+}
+
+// The SNR terms of mvdr_solve_kernel summed over the frequencies of one segment: snr (B, F, D, 2)
+// -> part (B, D, 2), block b its own segment, in mvdr_ref_kernel's way (MVDR_REF_CHUNK
+// frequencies staged in LDS at a time, lane r adds its channel's terms in ascending frequency).
+// mvdr_ref_kernel then adds the B partial sums in ascending order and picks the channel: one
+// workgroup walking all B F terms was the longest kernel of a call with many segments.
+__global__ __launch_bounds__(MVDR_REF_NT) void mvdr_snr_segments_kernel(
+    const cplx *__restrict__ snr, int F, int D, cplx *__restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    cplx *buf = reinterpret_cast<cplx *>(smem);            // MVDR_REF_CHUNK * D * 2
+    const int tid = threadIdx.x;
+    snr += (int64_t)blockIdx.x * F * D * 2;
+    cplx num = c_make(0.0, 0.0), den = c_make(0.0, 0.0);
+    for (int f0 = 0; f0 < F; f0 += MVDR_REF_CHUNK) {
+        const int nf = min(MVDR_REF_CHUNK, F - f0);
+        const int total = nf * D * 2;
+        __syncthreads();
+        for (int i = tid; i < total; i += MVDR_REF_NT) buf[i] = snr[(int64_t)f0 * D * 2 + i];
+        __syncthreads();
+        if (tid < D) {
+            for (int f = 0; f < nf; ++f) {
+                num = c_add(num, buf[(f * D + tid) * 2]);
+                den = c_add(den, buf[(f * D + tid) * 2 + 1]);
+            }
+        }
+    }
+    if (tid < D) {
+        part[((int64_t)blockIdx.x * D + tid) * 2] = num;
+        part[((int64_t)blockIdx.x * D + tid) * 2 + 1] = den;
     }
 }
 
@@ -830,8 +956,9 @@ int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double 
     const dim3 grid((unsigned)((T + chunk - 1) / chunk), F);
     if (!targets) {
         GSS_PROF(ctx, "mvdr_apply");
-        hipLaunchKernelGGL(mvdr_apply_kernel, grid, dim3(256), 0, ctx->stream, Y, W, Phi, ref, F, T,
-                           D, ban, chunk, Xhat, ref_channel, ctx->status_dev);
+        hipLaunchKernelGGL(mvdr_apply_kernel<false>, grid, dim3(256), 0, ctx->stream, Y, W, Phi, ref, F, T,
+                           D, ban, chunk, Xhat, ref_channel, ctx->status_dev, (int64_t)0,
+                           (const int32_t *)nullptr);
         GSS_LAUNCH_CHECK(ctx, "mvdr_apply_kernel");
         return GSS_OK;
     }
@@ -846,5 +973,129 @@ int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double 
     else GSS_APPLY_TARGETS(GSS_MAX_CLASSES);
 #undef GSS_APPLY_TARGETS
     GSS_LAUNCH_CHECK(ctx, "mvdr_apply_targets_kernel");
+    return GSS_OK;
+}
+
+// ------------------------------------------------------------------ segment-wise MVDR
+namespace {
+// Segments of L frames over the PSD pass: every segment is nsub chunks of cf frames (cf a
+// multiple of the 64-frame tile that divides L, at most the whole-window pass's chunk), nch
+// chunks in all -- the pass over Y is the whole-window one with chunk borders on segment borders.
+struct SegmentGeometry {
+    int64_t L;     // segment_frames, cut to one segment when it exceeds T
+    int B, nsub, nch, cf;
+};
+SegmentGeometry segment_geometry(int F, int64_t T, int64_t L) {
+    SegmentGeometry g;
+    const int64_t tiles = (T + PSD_TILE - 1) / PSD_TILE;
+    g.L = L < tiles * PSD_TILE ? L : tiles * PSD_TILE;
+    int cf_whole;
+    psd_chunks(F, T, &cf_whole);
+    const int64_t tiles_seg = g.L / PSD_TILE;
+    int64_t tpc = cf_whole / PSD_TILE < tiles_seg ? cf_whole / PSD_TILE : tiles_seg;
+    while (tiles_seg % tpc) --tpc;
+    g.cf = (int)(tpc * PSD_TILE);
+    g.nsub = (int)(tiles_seg / tpc);
+    g.nch = (int)((T + g.cf - 1) / g.cf);
+    g.B = (int)((T + g.L - 1) / g.L);
+    return g;
+}
+}  // namespace
+
+size_t mvdr_segments_workspace_bytes(int F, int64_t T, int D, int64_t segment_frames) {
+    const size_t NE = tri_count(D);
+    const SegmentGeometry g = segment_geometry(F, T, segment_frames);
+    const size_t B = g.B;
+    size_t b = 0;
+    b += align_up(sizeof(cplx) * (size_t)F * g.nch * 2 * NE);    // part
+    b += align_up(sizeof(double) * (size_t)F * B * 2);           // msum
+    b += align_up(sizeof(double) * (size_t)F * 2 * T);           // W2
+    b += align_up(sizeof(cplx) * (size_t)F * 2 * NE);            // whole_part
+    b += align_up(sizeof(double) * (size_t)F * 2);               // whole_msum
+    b += align_up(sizeof(cplx) * B * F * 2 * NE);                // wpart
+    b += align_up(sizeof(double) * B * F * 2);                   // wmsum
+    b += align_up(sizeof(cplx) * B * F * 2 * D * D);             // Phi
+    b += align_up(sizeof(cplx) * B * F * D * D);                 // W
+    b += align_up(sizeof(cplx) * B * F * D * 2);                 // snr
+    b += align_up(sizeof(cplx) * B * D * 2);                     // snr_part
+    b += align_up(sizeof(int32_t) * 4);                          // ref
+    return b + 4096;
+}
+
+int mvdr_segments_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
+                      const double *mn, int ban, const gss_bf_segments &seg, cplx *Xhat,
+                      int32_t *ref_channel, int forced_ref) {
+    const int NE = tri_count(D);
+    const SegmentGeometry g = segment_geometry(F, T, seg.segment_frames);
+    const size_t B = g.B;
+    cplx *part = arena_alloc_t<cplx>(ctx, (size_t)F * g.nch * 2 * NE);
+    double *msum = arena_alloc_t<double>(ctx, (size_t)F * B * 2);
+    double *W2 = arena_alloc_t<double>(ctx, (size_t)F * 2 * T);
+    cplx *whole_part = arena_alloc_t<cplx>(ctx, (size_t)F * 2 * NE);
+    double *whole_msum = arena_alloc_t<double>(ctx, (size_t)F * 2);
+    cplx *wpart = arena_alloc_t<cplx>(ctx, B * F * 2 * NE);
+    double *wmsum = arena_alloc_t<double>(ctx, B * F * 2);
+    cplx *Phi = arena_alloc_t<cplx>(ctx, B * F * 2 * D * D);
+    cplx *W = arena_alloc_t<cplx>(ctx, B * F * D * D);
+    cplx *snr = arena_alloc_t<cplx>(ctx, B * F * D * 2);
+    cplx *snr_part = arena_alloc_t<cplx>(ctx, B * D * 2);
+    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);   // [0]: reference channel, [2]: fallback counter
+    GSS_REQUIRE(ctx, part && msum && W2 && whole_part && whole_msum && wpart && wmsum && Phi && W &&
+                         snr && snr_part && ref, GSS_ERR_NOMEM, "mvdr segments workspace");
+    int32_t *const fallbacks = ref + 2;
+    ctx->last_targets = 0;
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(fallbacks, 0, sizeof(int32_t), ctx->stream));
+    {
+        GSS_PROF(ctx, "psd_segments");
+        hipLaunchKernelGGL(mask_pack_segments_kernel, dim3(g.B, F), dim3(256), 0, ctx->stream, mx,
+                           mn, T, g.L, W2, msum);
+        GSS_LAUNCH_CHECK(ctx, "mask_pack_segments_kernel");
+        GSS_TRY(psd_partials_run(ctx, Y, F, T, D, W2, g.nch, g.cf, part));
+    }
+    {
+        GSS_PROF(ctx, "mvdr_window_segments");
+        // the whole-window sums of every frequency first (what a window falls back to) ...
+        hipLaunchKernelGGL(mvdr_window_segments_kernel, dim3(F, 1), dim3(256), 0, ctx->stream, part,
+                           msum, g.nch, g.nsub, g.B, g.B, NE, 0.0, (const cplx *)nullptr,
+                           (const double *)nullptr, whole_part, whole_msum, fallbacks);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_window_segments_kernel");
+        // ... then every segment's window
+        const int ctx_seg = seg.context_segments < g.B ? seg.context_segments : g.B;
+        hipLaunchKernelGGL(mvdr_window_segments_kernel, dim3(F, g.B), dim3(256), 0, ctx->stream,
+                           part, msum, g.nch, g.nsub, g.B, ctx_seg, NE, seg.min_mass, whole_part,
+                           whole_msum, wpart, wmsum, fallbacks);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_window_segments_kernel");
+    }
+    {
+        // mvdr_solve_kernel's (F, S) grid with the B segments as its "targets", one chunk each
+        GSS_PROF(ctx, "mvdr_solve_segments");
+        const int m = D + (D & 1);
+        const size_t lds = (sizeof(cplx) * ((size_t)D * 2 * D + 2 * (size_t)m * m) + 32 + 15) / 16 * 16;
+        if (lds > 64 * 1024)
+            GSS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(mvdr_solve_kernel),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)lds));
+        hipLaunchKernelGGL(mvdr_solve_kernel, dim3(F, g.B), dim3(MVDR_NT), lds, ctx->stream, wpart,
+                           wmsum, 1, D, 1e-10, Phi, W, snr);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_solve_kernel");
+    }
+    {
+        // one reference channel for the call: the SNR terms summed over all (b, f) -- over f
+        // within each segment, then mvdr_ref_kernel over the B partial sums as its "frequencies"
+        GSS_PROF(ctx, "mvdr_ref_segments");
+        const size_t lds = sizeof(cplx) * MVDR_REF_CHUNK * (size_t)D * 2;
+        hipLaunchKernelGGL(mvdr_snr_segments_kernel, dim3(g.B), dim3(MVDR_REF_NT), lds, ctx->stream,
+                           snr, F, D, snr_part);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_snr_segments_kernel");
+        hipLaunchKernelGGL(mvdr_ref_kernel, dim3(1), dim3(MVDR_REF_NT), lds, ctx->stream, snr_part,
+                           g.B, D, 1e-10, forced_ref, ref);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_ref_kernel");
+    }
+    GSS_PROF(ctx, "mvdr_apply_segments");
+    const int chunk = g.L % 256 == 0 ? 256 : g.L % 128 == 0 ? 128 : 64;
+    hipLaunchKernelGGL(mvdr_apply_kernel<true>, dim3((unsigned)((T + chunk - 1) / chunk), F), dim3(256), 0,
+                       ctx->stream, Y, W, Phi, ref, F, T, D, ban, chunk, Xhat, ref_channel,
+                       ctx->status_dev, g.L, (const int32_t *)fallbacks);
+    GSS_LAUNCH_CHECK(ctx, "mvdr_apply_kernel");
     return GSS_OK;
 }

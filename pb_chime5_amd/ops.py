@@ -11,6 +11,7 @@ here                        reference call (file:line)
 ``cacgmm_posteriors``       CACGMMTrainer.fit + predict   (core.py:165-208)
 ``cacgmm_posteriors_guided``  the same from any initialisation / source_activity_mask
 ``mvdr_souden_from_masks``  pb_bss beamformer chain       (beamforming_wrapper.py:51-97)
+``mvdr_souden_segments_from_masks``  the same with statistics per segment of frames
 ``enhance_observation``     Enhancer.enhance_observation  (core.py:514-571)
 =========================  ====================================================
 
@@ -21,7 +22,8 @@ import ctypes
 import numpy as np
 
 from . import _capi
-from ._capi import Context, GssDebugTaps, GssGuidance, GssParams, c_void_p, default_context
+from ._capi import (Context, GssBfSegments, GssDebugTaps, GssGuidance, GssParams, c_void_p,
+                    default_context)
 
 _BF_CODES = {'mvdrSouden_ban': 0, 'ch2': 1, 'sum': 2, 'gev_ban': 3}
 _POSTFILTER_CODES = {None: 0, 'mask_mul': 1}
@@ -415,6 +417,79 @@ def mvdr_souden_from_masks(Y, X_mask, N_mask, ban=False, *, ref_channel=None,
     return X_hat
 
 
+SEGMENT_TILE = 64       # frames: segment_frames is a multiple of the PSD kernel's frame tile
+
+
+def check_bf_segments(segment_frames, segment_context=0, min_mass=None, num_channels=None):
+    """The settings of the segment-wise beamformer as a gss_bf_segments, or ValueError naming
+    the argument: ``segment_frames`` a positive multiple of 64, ``segment_context`` an integer
+    >= 0, ``min_mass`` finite and >= 0.  ``min_mass=None`` is ``2 * num_channels`` (it stays
+    0 in the returned struct while ``num_channels`` is not known: checks without an
+    observation)."""
+    def integer(value):
+        return isinstance(value, (int, np.integer)) and not isinstance(value, bool)
+    if not integer(segment_frames) or segment_frames < SEGMENT_TILE \
+            or segment_frames % SEGMENT_TILE:
+        raise ValueError(f'segment_frames={segment_frames!r}: a positive multiple of '
+                         f'{SEGMENT_TILE} frames')
+    if not integer(segment_context) or segment_context < 0 or segment_context >= 2 ** 31:
+        raise ValueError(f'segment_context={segment_context!r}: a non-negative integer number '
+                         'of segments')
+    if min_mass is None:
+        min_mass = 2 * num_channels if num_channels is not None else 0
+    if isinstance(min_mass, bool) or not isinstance(min_mass, (int, float, np.integer,
+                                                               np.floating)) \
+            or not np.isfinite(min_mass) or min_mass < 0:
+        raise ValueError(f'min_mass={min_mass!r}: a finite number >= 0')
+    return GssBfSegments(segment_frames=int(segment_frames),
+                         context_segments=int(segment_context), min_mass=float(min_mass))
+
+
+def mvdr_souden_segments_from_masks(Y, X_mask, N_mask, ban=False, *, segment_frames,
+                                    segment_context=0, min_mass=None, ref_channel=None,
+                                    return_ref_channel=False, return_fallbacks=False, ctx=None):
+    """`mvdr_souden_from_masks` with a time-varying filter (gss_mvdr_souden_segments): the T
+    frames are cut into segments of ``segment_frames`` frames (a positive multiple of 64, the
+    last one may be short); segment b's PSD matrices are taken over segments
+    b - segment_context .. b + segment_context, its filter is applied to its own frames.  One
+    reference channel for the whole call (the SNR summed over all segments and frequencies, or
+    ``ref_channel``).  A window whose target or distortion mask sums to less than ``min_mass``
+    at a frequency takes the whole-window matrices there; ``min_mass=None`` is ``2 * D``: a
+    Phi_N from fewer than D frames' worth of mask is singular, and the factor 2 on top of that
+    is a choice, not a measurement.  ``min_mass=0`` never falls back.
+
+    Y (D,T,F), masks (T,F) -> X_hat (T,F); with ``return_ref_channel`` / ``return_fallbacks``
+    a tuple (X_hat[, ref_channel][, number of (segment, frequency) pairs that fell back]).
+    Argument errors are ValueError before any device work; a non-finite SNR raises
+    AssertionError like the whole-window call."""
+    Y = np.asarray(Y)
+    if Y.ndim != 3:
+        raise ValueError(f'Y: shape {Y.shape} is not (D,T,F)')
+    D, T, F = Y.shape
+    seg = check_bf_segments(segment_frames, segment_context, min_mass, D)
+    for name, m in (('X_mask', X_mask), ('N_mask', N_mask)):
+        if np.shape(m) != (T, F):
+            raise ValueError(f'{name}: shape {np.shape(m)} is not (T,F) = {(T, F)}')
+    if ref_channel is not None and not 0 <= int(ref_channel) < D:
+        raise ValueError(f'ref_channel={ref_channel!r} outside [0, {D})')
+    ctx = ctx or default_context()
+    Y_d, _ = _obs_to_device_ftd(ctx, Y)
+    mx = _mask_to_device_ft(ctx, X_mask, T, F)
+    mn = _mask_to_device_ft(ctx, N_mask, T, F)
+    X_d = ctx.empty(16 * F * T)
+    ctx._check(ctx.lib.gss_mvdr_souden_segments(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, c_void_p(mx.ptr), c_void_p(mn.ptr),
+        int(bool(ban)), -1 if ref_channel is None else int(ref_channel), ctypes.byref(seg),
+        c_void_p(X_d.ptr), None), 'gss_mvdr_souden_segments')
+    ref = _check_ref_channel(ctx)
+    out = (ctx.to_host(X_d, (T, F), np.complex128),)
+    if return_ref_channel:
+        out += (ref,)
+    if return_fallbacks:
+        out += (ctx.last_segment_fallbacks(),)
+    return out if len(out) > 1 else out[0]
+
+
 def gev_from_masks(Y, X_mask, N_mask, ban=True, *, ctx=None):
     """beamform_gev_from_masks: Y (D,T,F), 2-D masks (T,F) -> X_hat (T,F).  The phase
     of a generalised eigenvector is arbitrary (upstream too); magnitudes are defined.
@@ -509,8 +584,19 @@ class ResidentUtterance:
         self.act_d = ctx.to_device(act)
         self.out_d = ctx.empty(8 * max(self.n_out, 1))
 
-    def enqueue(self, target_index, start_context, end_context, taps=None):
+    def enqueue(self, target_index, start_context, end_context, taps=None, segments=None):
+        """``segments``: a gss_bf_segments (`check_bf_segments`) for the segment-wise
+        beamformer (gss_enhance_observation_segments; float64 samples only)."""
         ctx = self.ctx
+        if segments is not None:
+            assert not self.pcm, 'the segment-wise call has no pcm16 twin'
+            ctx._check(ctx.lib.gss_enhance_observation_segments(
+                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
+                self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
+                int(start_context), int(end_context), ctypes.byref(segments),
+                c_void_p(self.out_d.ptr), ctypes.byref(taps) if taps is not None else None),
+                'gss_enhance_observation_segments')
+            return
         entry = ctx.lib.gss_enhance_observation_pcm16 if self.pcm else ctx.lib.gss_enhance_observation
         ctx._check(entry(
             ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
@@ -792,6 +878,42 @@ def enhance_observation(obs, activity, target_index, start_context_samples,
     details = _debug_details(utt, bufs)
     details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
     details['ref_channel'] = int(details['ref_channel'])
+    return x_hat, details
+
+
+def enhance_observation_segments(obs, activity, target_index, start_context_samples,
+                                 end_context_samples, *, segment_frames, segment_context=0,
+                                 min_mass=None, params=None, window=None, debug=False, ctx=None,
+                                 wpe_arrays=None, **param_kwargs):
+    """`enhance_observation` with the segment-wise beamformer of
+    `mvdr_souden_segments_from_masks` (gss_enhance_observation_segments) in the place of the
+    whole-window one; everything else, the ``debug`` details included, as there, plus
+    ``details['segment_fallbacks']``.  Only ``bf='mvdrSouden_ban'`` has segments
+    (NotImplementedError otherwise); bad segment settings are ValueError, both before any
+    device work."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    if params.bf != _BF_CODES['mvdrSouden_ban']:
+        names = {v: k for k, v in _BF_CODES.items()}
+        raise NotImplementedError(f"bf={names[params.bf]!r} with segment_frames: only "
+                                  "'mvdrSouden_ban' has a segment-wise form")
+    obs = np.asarray(obs)
+    if obs.ndim != 2:
+        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    seg = check_bf_segments(segment_frames, segment_context, min_mass, obs.shape[0])
+    params = params_for(params, obs.shape[0], wpe_arrays)
+    ctx = ctx or default_context()
+    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
+    utt = ResidentUtterance(ctx, obs, activity, params)
+    bufs, taps = _debug_taps(utt) if debug else ({}, None)
+    utt.enqueue(target_index, start_context_samples, end_context_samples, taps, segments=seg)
+    x_hat = utt.result()
+    if not debug:
+        return x_hat
+    details = _debug_details(utt, bufs)
+    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+    details['ref_channel'] = int(details['ref_channel'])
+    details['segment_fallbacks'] = ctx.last_segment_fallbacks()
     return x_hat, details
 
 

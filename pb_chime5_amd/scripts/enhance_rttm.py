@@ -34,6 +34,11 @@ def main(argv=None):
     ap.add_argument('--bss-iterations-post', type=int, default=1)
     ap.add_argument('--bf', default='mvdrSouden_ban')
     ap.add_argument('--postfilter', default=None)
+    ap.add_argument('--bf-segment-frames', type=int, default=None,
+                    help='time-varying MVDR: beamformer statistics per segment of this many STFT '
+                         'frames, a multiple of 64 (get_enhancer(bf_segment_frames=...))')
+    ap.add_argument('--bf-segment-context', type=int, default=0,
+                    help='segments either side in the statistics of a segment')
     ap.add_argument('--no-bf-drop-context', action='store_true')
     ap.add_argument('--job-id', type=int, default=1)
     ap.add_argument('--number-of-jobs', type=int, default=1)
@@ -51,7 +56,8 @@ def main(argv=None):
         wpe_delay=args.wpe_delay, wpe_iterations=args.wpe_iterations,
         bss_iterations=args.bss_iterations, bss_iterations_post=args.bss_iterations_post,
         bf_drop_context=not args.no_bf_drop_context, bf=args.bf, postfilter=args.postfilter,
-        device_id=parallel.device_index(), wpe_per_array=args.wpe_per_array)
+        device_id=parallel.device_index(), wpe_per_array=args.wpe_per_array,
+        bf_segment_frames=args.bf_segment_frames, bf_segment_context=args.bf_segment_context)
     if parallel.is_master():
         Path(args.out).mkdir(parents=True, exist_ok=True)
     parallel.barrier()

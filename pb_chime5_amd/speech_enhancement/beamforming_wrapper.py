@@ -17,9 +17,12 @@ class _Beamformer:
     """Layout normalisation + lazily evaluated results, like the reference's
     helper class; the arithmetic is one ``gss_mvdr_souden`` call per variant."""
 
-    def __init__(self, Y, X_mask, N_mask, debug=False, ctx=None):
+    def __init__(self, Y, X_mask, N_mask, debug=False, ctx=None, segments=None):
         self.debug = debug
         self._ctx = ctx
+        # segments: keyword arguments of ops.mvdr_souden_segments_from_masks (the statistics
+        # per segment of frames) or None: one window, the reference's beamformer
+        self._segments = segments
         if np.ndim(Y) == 4:
             self.Y = morph('1DTF->FDT', Y)
         else:
@@ -45,7 +48,11 @@ class _Beamformer:
         self._cache = {}
 
     def _run(self, ban):
-        if ban not in self._cache:
+        if ban not in self._cache and self._segments is not None:
+            self._cache[ban] = ops.mvdr_souden_segments_from_masks(
+                self.Y.transpose(1, 2, 0), self.X_mask.T, self.N_mask.T, ban=ban,
+                return_ref_channel=True, ctx=self._ctx, **self._segments)
+        elif ban not in self._cache:
             self._cache[ban] = ops.mvdr_souden_from_masks(
                 self.Y.transpose(1, 2, 0), self.X_mask.T, self.N_mask.T, ban=ban,
                 return_ref_channel=True, ctx=self._ctx)
@@ -87,8 +94,19 @@ def beamform_gev_from_masks(Y, X_mask, N_mask, ban=True, debug=False, ctx=None):
     return bf.X_hat_gev
 
 
-def beamform_mvdr_souden_from_masks(Y, X_mask, N_mask, ban=False, debug=False, ctx=None):
-    bf = _Beamformer(Y=Y, X_mask=X_mask, N_mask=N_mask, debug=debug, ctx=ctx)
+def beamform_mvdr_souden_from_masks(Y, X_mask, N_mask, ban=False, debug=False, ctx=None, *,
+                                    segment_frames=None, segment_context=0,
+                                    segment_min_mass=None):
+    """``segment_frames`` (an addition; None: the reference's one window per call): a
+    time-varying filter with statistics per segment of that many frames, see
+    ``ops.mvdr_souden_segments_from_masks``."""
+    segments = None
+    if segment_frames is not None:
+        ops.check_bf_segments(segment_frames, segment_context, segment_min_mass)
+        segments = dict(segment_frames=segment_frames, segment_context=segment_context,
+                        min_mass=segment_min_mass)
+    bf = _Beamformer(Y=Y, X_mask=X_mask, N_mask=N_mask, debug=debug, ctx=ctx,
+                     segments=segments)
     if ban:
         return bf.X_hat_mvdr_souden_ban
     return bf.X_hat_mvdr_souden
