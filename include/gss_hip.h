@@ -79,7 +79,10 @@ typedef enum {
  * entry points only, no struct or argument list of an existing one changed, revision still 7.
  * So were gss_mvdr_souden_segments, gss_enhance_observation_segments and
  * gss_last_segment_fallbacks with the gss_bf_segments descriptor (gss_params keeps its layout:
- * the segment settings travel in a descriptor of their own). */
+ * the segment settings travel in a descriptor of their own).  So were gss_channel_scores,
+ * gss_select_channels, gss_last_selected_channels and gss_enhance_observation_select(_pcm16)
+ * with the gss_channel_select descriptor: entry points only, gss_params and gss_debug_taps keep
+ * their layouts, revision still 7. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -333,6 +336,45 @@ int gss_gev(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
             const double *target_mask_dev, const double *distortion_mask_dev,
             int ban, gss_cplx *Xhat_dev);
 
+/* Envelope-variance channel selection (Wolf & Nadeu 2014; not in the reference, whose
+ * `multiarray` modes pick microphones by position).  For an STFT Y (F,T,D) and a non-negative
+ * band table W (B,F):
+ *    E[b,t,d] = sum_f W[b,f] |Y[f,t,d]|^2, floored at floor * max_t E[b,t,d];
+ *    C = exp((log E - mean_t log E) / 3);   V[b,d] = mean_t (C - mean_t C)^2 (two passes),
+ *    0 where max_t E[b,t,d] == 0;   score[d] = sum_b V[b,d] / max_d' V[b,d'] (a band whose
+ *    maximum is 0 contributes 0).
+ * Scores lie in [0, B]; a channel that is zero in every frame scores 0.  The `keep` channels of
+ * highest score are kept -- equal scores in favour of the lower index, a non-finite score
+ * below every finite one -- and reported in ascending channel order.  The library holds no
+ * band policy: the host builds W (pb_chime5_amd.ops.mel_bank) as it builds the windows.  The
+ * sums have one fixed order (no floating-point atomics): the same call gives the same bits. */
+typedef struct {
+    const double *bank_dev;  /* (B, F) row-major, >= 0                     */
+    int32_t bands;           /* B, 1 .. 64                                  */
+    int32_t keep;            /* n, 1 .. D                                   */
+    double floor;            /* in [0, 1), finite                           */
+} gss_channel_select;
+
+/* Y (F,T,D) -> scores (D) and, unless NULL, the band variances V (B,D).  sel->keep is unread.
+ * GSS_ERR_INVALID (the message names the field): sel or bank_dev NULL, bands outside [1, 64],
+ * floor negative, >= 1 or not finite. */
+int gss_channel_scores(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                       const gss_channel_select *sel, double *scores_dev,
+                       double *band_var_dev);
+
+/* Y (F,T,D) -> Ysel (F,T,n), n = sel->keep: the kept channels in ascending channel order;
+ * channels_dev (device int32 (n,), may be NULL) receives their indices.  Asynchronous: n comes
+ * from the caller, which channels are kept is decided on the device.  Errors as
+ * gss_channel_scores, and keep outside [1, D]. */
+int gss_select_channels(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                        const gss_channel_select *sel, gss_cplx *Ysel_dev,
+                        int32_t *channels_dev);
+
+/* The first n channels (ascending) the last gss_select_channels / gss_enhance_observation_select*
+ * call on this context kept; synchronises the stream.  GSS_ERR_INVALID when n is smaller than 1
+ * or larger than that call's count (0 before any). */
+int gss_last_selected_channels(gss_ctx *ctx, int32_t *channels_host, int n);
+
 /* Layout helpers between the canonical device layouts and the reference's. */
 int gss_layout_dtf_to_ftd(gss_ctx *ctx, const gss_cplx *src_dev, int D, int64_t T,
                           int F, gss_cplx *dst_dev);
@@ -426,6 +468,36 @@ int gss_enhance_observation_segments(gss_ctx *ctx, const gss_params *params,
                                      int64_t end_context_samples,
                                      const gss_bf_segments *seg,
                                      double *out_dev, const gss_debug_taps *taps);
+
+/* gss_enhance_observation on the sel->keep channels the envelope-variance measure ranks best:
+ * the STFT runs on all D channels, then scores, pick and gather, then the unchanged pipeline
+ * (WPE, frame activity, CACGMM, masks, beamformer, postfilter, iSTFT) on n = sel->keep
+ * channels.  The limits of the pipeline apply to n (D < 30 of the MVDR / GEV, the CACGMM's
+ * D >= 2), D itself is limited by GSS_MAX_CHANNELS only.  With keep == D the gather is skipped
+ * and the output and every tap equal gss_enhance_observation bit for bit.  Taps: Obs_ftd is
+ * (F,T,n) and ref_channel an index into the kept channels (so is gss_last_ref_channel
+ * afterwards; gss_last_selected_channels maps it back); the others are unchanged.
+ * GSS_ERR_INVALID for a bad `sel` as gss_select_channels; GSS_ERR_UNSUPPORTED for
+ * params->wpe_arrays > 1 (a selection breaks the equal arrays of the per-array WPE) and
+ * params->bf == 1 ('ch2' names a physical channel). */
+int gss_enhance_observation_select(gss_ctx *ctx, const gss_params *params,
+                                   const double *obs_dev, int D, int64_t N,
+                                   const uint8_t *act_dev, int K, int64_t N_act,
+                                   int target_index,
+                                   int64_t start_context_samples,
+                                   int64_t end_context_samples,
+                                   const gss_channel_select *sel,
+                                   double *out_dev, const gss_debug_taps *taps);
+
+/* The same fed with 16-bit PCM, as gss_enhance_observation_pcm16. */
+int gss_enhance_observation_select_pcm16(gss_ctx *ctx, const gss_params *params,
+                                         const int16_t *obs_dev, int D, int64_t N,
+                                         const uint8_t *act_dev, int K, int64_t N_act,
+                                         int target_index,
+                                         int64_t start_context_samples,
+                                         int64_t end_context_samples,
+                                         const gss_channel_select *sel,
+                                         double *out_dev, const gss_debug_taps *taps);
 
 /* Same pipeline fed with the 16-bit PCM samples as they sit in the WAV files: the
  * conversion of the reference's loader, float64(sample) / 2^15 (io/audioread.py:34-226 via

@@ -52,6 +52,13 @@ class GssBfSegments(ctypes.Structure):
                 ('min_mass', ctypes.c_double)]
 
 
+class GssChannelSelect(ctypes.Structure):
+    """gss_channel_select: the band table and the settings of the envelope-variance channel
+    selection."""
+    _fields_ = [('bank_dev', c_void_p), ('bands', ctypes.c_int32), ('keep', ctypes.c_int32),
+                ('floor', ctypes.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/gss_hip.h declares
 SIGNATURES = {
     'gss_device_count': (c_int, []),
@@ -141,6 +148,19 @@ SIGNATURES = {
                 c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                 ctypes.POINTER(GssDebugTaps)]),
     'gss_last_ref_channels': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), c_int]),
+    'gss_channel_scores': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
+                                   ctypes.POINTER(GssChannelSelect), c_void_p, c_void_p]),
+    'gss_select_channels': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
+                                    ctypes.POINTER(GssChannelSelect), c_void_p, c_void_p]),
+    'gss_last_selected_channels': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), c_int]),
+    'gss_enhance_observation_select': (
+        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
+                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
+                ctypes.POINTER(GssChannelSelect), c_void_p, ctypes.POINTER(GssDebugTaps)]),
+    'gss_enhance_observation_select_pcm16': (
+        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
+                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
+                ctypes.POINTER(GssChannelSelect), c_void_p, ctypes.POINTER(GssDebugTaps)]),
     'gss_enhance_observation_host': (
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p]),
@@ -276,6 +296,7 @@ class Context:
         self.handle = h
         self.device_id = device_id
         self._windows = None
+        self.selected_count = 0     # n of the last channel selection enqueued through `ops`
 
     # -- plumbing ----------------------------------------------------------
     def _check(self, status, what):
@@ -384,6 +405,17 @@ class Context:
         self._check(self.lib.gss_last_ref_channels(self.handle, out, int(S)),
                     'gss_last_ref_channels')
         return [int(v) for v in out]
+
+    def last_selected_channels(self, n=None):
+        """The channels (ascending) the last channel selection on this context kept
+        (synchronises); ``n``: the first n of them (None: as many as the caller asked that
+        call to keep, which the binding remembers in ``selected_count``)."""
+        if n is None:
+            n = self.selected_count
+        out = (ctypes.c_int32 * max(int(n), 1))()
+        self._check(self.lib.gss_last_selected_channels(self.handle, out, int(n)),
+                    'gss_last_selected_channels')
+        return [int(v) for v in out[:int(n)]]
 
     def last_wpe_zero_pivots(self):
         """Pivots the WPE solve of the last call zeroed (synchronises); > 0 on live channels

@@ -296,6 +296,47 @@ class Enhancer:
     # beamformer on all channels together; only with a multiarray mode and WPE (otherwise no
     # effect).  Off: the reference's joint WPE over all channels.
     wpe_per_array: bool = False
+    # Envelope-variance channel selection ahead of WPE (an addition, see ops.select_channels):
+    # keep the ``channel_keep`` channels (an int: a count, a float in (0, 1]: a share of the
+    # channels of each utterance) that a mel bank of ``channel_bands`` filters ranks best.
+    # None: every channel, the reference's pipeline.
+    channel_keep: object = None
+    channel_bands: int = 40
+
+    def __post_init__(self):
+        if self.channel_keep is None:
+            return
+        ops.check_channel_keep(self.channel_keep)
+        ops.check_channel_bands(self.channel_bands)
+        if self.wpe_per_array:
+            raise NotImplementedError(
+                'channel_keep with wpe_per_array=True: a selection breaks the equal arrays of '
+                'the per-array WPE')
+        if getattr(self.bf_block, 'type', None) == 'ch2':
+            raise NotImplementedError(
+                "channel_keep with bf='ch2': 'ch2' names a physical channel")
+        if self._bf_segments() is not None:
+            raise NotImplementedError(
+                'channel_keep with bf_segment_frames: the segment-wise beamformer has no '
+                'selection')
+
+    def _channel_select(self):
+        """The `ops.ChannelSelect` of this enhancer (one object: its band table is copied to a
+        GPU once), or None without ``channel_keep``."""
+        if self.channel_keep is None:
+            return None
+        sel = getattr(self, '_channel_select_cache', None)
+        key = (self.channel_keep, self.channel_bands, self.stft_size)
+        if sel is None or sel[0] != key:
+            sel = self._channel_select_cache = (key, ops.ChannelSelect(
+                self.channel_keep, self.stft_size // 2 + 1, bands=self.channel_bands))
+        return sel[1]
+
+    def _no_channel_keep(self, what):
+        if self.channel_keep is not None:
+            raise NotImplementedError(
+                f'{what} with channel_keep: the channel selection is built for '
+                'enhance_observation and enhance_session only')
 
     # channels per array that each multiarray mode loads (core.py:428-441)
     _ARRAY_CHANNELS = {True: 4, 'outer_array_mics': 2, 'first_array_mics': 1}
@@ -501,7 +542,7 @@ class Enhancer:
                 t0 = time.perf_counter()
                 try:
                     pipe.enqueue_staged(ex, *prepared, wpe_arrays=self.wpe_arrays(
-                        ex, prepared[0].obs.shape[0]))
+                        ex, prepared[0].obs.shape[0]), channel_select=self._channel_select())
                 except BaseException:
                     pipe.release_staging(prepared[0])
                     raise
@@ -750,8 +791,14 @@ class Enhancer:
         ctx = self._ctx()
         ctx.set_utterances_in_flight(1)
         segments = self._bf_segments()
+        select = self._channel_select()
         try:
-            if segments is not None:
+            if select is not None:
+                res = ops.enhance_observation_select(
+                    obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
+                    debug=debug, ctx=ctx, keep=select.keep, bank=select.bank,
+                    floor=select.floor)
+            elif segments is not None:
                 res = ops.enhance_observation_segments(
                     obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
                     debug=debug, ctx=ctx, wpe_arrays=wpe_arrays, **segments)
@@ -765,6 +812,8 @@ class Enhancer:
             return res
         x_hat, details = res
         Obs = details['Obs']
+        if select is not None:
+            selected_channels = details['selected_channels']
         acitivity_freq = details['acitivity_freq']
         target_mask = details['target_mask']
         distortion_mask = details['distortion_mask']
@@ -789,6 +838,7 @@ class Enhancer:
         ``initialization``: optional dict of the same shape with initial affiliations used as
         given (a neural mask estimator's output).  ``fused=False`` runs the blocks."""
         self._no_segments('enhance_observation_guided')
+        self._no_channel_keep('enhance_observation_guided')
         if wpe_arrays is None:
             wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
         wpe_arrays = ops.check_wpe_arrays(wpe_arrays, np.shape(obs)[0])
@@ -885,6 +935,7 @@ class Enhancer:
         speakers together (gss_enhance_observation_targets), the block path calls
         ``bf_block`` and the iSTFT once per speaker."""
         self._no_segments('enhance_observation_speakers')
+        self._no_channel_keep('enhance_observation_speakers')
         speaker_ids = self.speaker_ids_of(ex_array_activity, speaker_ids)
         if wpe_arrays is None:
             wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
@@ -919,6 +970,7 @@ class Enhancer:
         """`enhance_example` for several speakers of the example's window at once: dict
         speaker_id -> x_hat, each trimmed like `enhance_example` trims its output."""
         self._no_segments('enhance_example_speakers')
+        self._no_channel_keep('enhance_example_speakers')
         obs, ex_array_activity, _ = self._prepare_example(ex)
         out = self.enhance_observation_speakers(obs, ex_array_activity, speaker_ids, ex=ex)
         return {k: self._trim_context(v, ex) for k, v in out.items()}
@@ -955,7 +1007,13 @@ class Enhancer:
         """The target-independent blocks of the block path: STFT, WPE (joint or per array),
         activity, GSS and the zeroed context frames.  Returns Obs, acitivity_freq, masks and
         (start_context_frames, end_context_frames) or None without bf_drop_context."""
-        Obs = self._blocks_wpe(self.stft(obs), debug, wpe_arrays)
+        Obs = self.stft(obs)
+        self._selected_channels = None
+        if self.channel_keep is not None:
+            select = self._channel_select()
+            Obs, self._selected_channels = ops.select_channels(
+                Obs, select.keep, bank=select.bank, floor=select.floor, ctx=self._ctx())
+        Obs = self._blocks_wpe(Obs, debug, wpe_arrays)
         acitivity_freq = activity_time_to_frequency(
             np.array(list(ex_array_activity.values())),
             stft_window_length=self.stft_size, stft_shift=self.stft_shift,
@@ -977,6 +1035,8 @@ class Enhancer:
         round trip per block); used when a block was swapped out."""
         Obs, acitivity_freq, masks, context_frames = self._blocks_front(
             obs, ex_array_activity, ex, debug, wpe_arrays)
+        if self._selected_channels is not None:
+            selected_channels = self._selected_channels
         if context_frames is not None:
             start_context_frames, end_context_frames = context_frames
         target_speaker_index = tuple(ex_array_activity.keys()).index(speaker_id)
@@ -1026,9 +1086,17 @@ def get_enhancer(
     bf_segment_frames=None,
     bf_segment_context=0,
     bf_segment_min_mass=None,
+    channel_keep=None,
+    channel_bands=40,
 ):
     """core.py:574-637 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory``, ``device_id``, ``wpe_per_array`` and ``bf_segment_*`` are additions).
+    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*`` and ``channel_*``
+    are additions).
+    ``channel_keep=n`` (a count) or a share in (0, 1]: keep the channels of each utterance that
+    the envelope-variance measure ranks best, chosen after the STFT from a mel bank of
+    ``channel_bands`` filters (see `ops.select_channels`); WPE, GSS and the beamformer run on
+    those.  None: all channels.  Not with ``wpe_per_array``, ``bf='ch2'`` or
+    ``bf_segment_frames`` (NotImplementedError).
     ``wpe_per_array=True``: with a multiarray mode, WPE runs on each microphone array on its
     own (the reference's ``WPE(..., stack=False)``), GSS and the beamformer on all channels;
     no effect with ``multiarray=False`` or ``wpe=False``.
@@ -1058,4 +1126,6 @@ def get_enhancer(
         device_id=device_id,
         iterator_factory=iterator_factory,
         wpe_per_array=bool(wpe_per_array),
+        channel_keep=channel_keep,
+        channel_bands=channel_bands,
     )

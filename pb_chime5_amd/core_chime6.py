@@ -144,9 +144,11 @@ def get_enhancer(
     bf_segment_frames=None,
     bf_segment_context=0,
     bf_segment_min_mass=None,
+    channel_keep=None,
+    channel_bands=40,
 ):
     """core_chime6.py:572-635 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory``, ``device_id``, ``wpe_per_array`` and ``bf_segment_*`` are additions,
+    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*`` and ``channel_*`` are additions,
     see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
@@ -171,4 +173,6 @@ def get_enhancer(
         device_id=device_id,
         iterator_factory=iterator_factory,
         wpe_per_array=bool(wpe_per_array),
+        channel_keep=channel_keep,
+        channel_bands=channel_bands,
     )

@@ -154,9 +154,11 @@ def get_enhancer(
     bf_segment_frames=None,
     bf_segment_context=0,
     bf_segment_min_mass=None,
+    channel_keep=None,
+    channel_bands=40,
 ):
     """core_chime6_rttm.py:360-422 (same keyword arguments and defaults; ``device_id``,
-    ``wpe_per_array`` and ``bf_segment_*`` are additions, see core.get_enhancer)."""
+    ``wpe_per_array``, ``bf_segment_*`` and ``channel_*`` are additions, see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     db = get_database(chime6_dir, database_rttm, multiarray)
     return Enhancer(
@@ -178,4 +180,6 @@ def get_enhancer(
         stft_fading=stft_fading,
         device_id=device_id,
         wpe_per_array=bool(wpe_per_array),
+        channel_keep=channel_keep,
+        channel_bands=channel_bands,
     )

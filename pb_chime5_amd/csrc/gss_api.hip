@@ -801,6 +801,68 @@ extern "C" int gss_gev(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
                     reinterpret_cast<cplx *>(Xhat), nullptr, /*gev=*/1);
 }
 
+// The descriptor's rules (include/gss_hip.h); `keep` is checked against D where it is read.
+static int check_channel_select(gss_ctx *ctx, const gss_channel_select *sel, int D, bool keep,
+                                const char *what) {
+    GSS_REQUIRE(ctx, sel, GSS_ERR_INVALID, "%s: sel is NULL", what);
+    GSS_REQUIRE(ctx, sel->bank_dev, GSS_ERR_INVALID, "%s: bank_dev is NULL", what);
+    GSS_REQUIRE(ctx, sel->bands >= 1 && sel->bands <= 64, GSS_ERR_INVALID,
+                "%s: bands = %d outside [1, 64]", what, (int)sel->bands);
+    GSS_REQUIRE(ctx, std::isfinite(sel->floor) && sel->floor >= 0.0 && sel->floor < 1.0,
+                GSS_ERR_INVALID, "%s: floor = %g is negative, >= 1 or not finite", what,
+                sel->floor);
+    if (keep)
+        GSS_REQUIRE(ctx, sel->keep >= 1 && sel->keep <= D, GSS_ERR_INVALID,
+                    "%s: keep = %d outside [1, %d]", what, (int)sel->keep, D);
+    return GSS_OK;
+}
+
+extern "C" int gss_channel_scores(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                                  const gss_channel_select *sel, double *scores,
+                                  double *band_var) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, Y && scores && F >= 1 && T >= 1, GSS_ERR_INVALID,
+                "gss_channel_scores: bad arguments");
+    GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
+                "gss_channel_scores: D=%d outside [1, %d]", D, GSS_MAX_CHANNELS);
+    GSS_TRY(check_channel_select(ctx, sel, D, false, "gss_channel_scores"));
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported",
+                (long long)((int64_t)F * T * D));
+    GSS_TRY(arena_reserve(ctx, chsel_workspace_bytes(F, T, D, sel->bands)));
+    return chsel_scores_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, *sel, scores,
+                            band_var);
+}
+
+extern "C" int gss_select_channels(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                                   const gss_channel_select *sel, gss_cplx *Ysel,
+                                   int32_t *channels) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, Y && Ysel && F >= 1 && T >= 1, GSS_ERR_INVALID,
+                "gss_select_channels: bad arguments");
+    GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
+                "gss_select_channels: D=%d outside [1, %d]", D, GSS_MAX_CHANNELS);
+    GSS_TRY(check_channel_select(ctx, sel, D, true, "gss_select_channels"));
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported",
+                (long long)((int64_t)F * T * D));
+    GSS_TRY(arena_reserve(ctx, chsel_workspace_bytes(F, T, D, sel->bands)));
+    return chsel_select_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, *sel,
+                            reinterpret_cast<cplx *>(Ysel), channels);
+}
+
+extern "C" int gss_last_selected_channels(gss_ctx *ctx, int32_t *channels, int n) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, channels, GSS_ERR_INVALID, "gss_last_selected_channels: NULL");
+    GSS_REQUIRE(ctx, n >= 1 && n <= ctx->last_selected, GSS_ERR_INVALID,
+                "gss_last_selected_channels: n=%d, the last selection kept %d channel(s)", n,
+                ctx->last_selected);
+    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    const int32_t *words = ctx->status_host + GSS_STATUS_CHANNELS;
+    for (int j = 0; j < n; ++j) channels[j] = __atomic_load_n(words + j, __ATOMIC_ACQUIRE);
+    return GSS_OK;
+}
+
 extern "C" int gss_selftest_mfma(gss_ctx *ctx) {
     GSS_ENTER(ctx);
     return selftest_mfma_run(ctx);
@@ -889,9 +951,12 @@ static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, in
     return stage;
 }
 
-// (segment_frames > 0: the segment-wise beamformer in the place of the whole-window one)
+// (segment_frames > 0: the segment-wise beamformer in the place of the whole-window one;
+// select_bands > 0: D is the number of channels kept out of select_D, and the selection stage
+// needs its own workspace and, when it gathers, the STFT of all select_D channels)
 static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
-                                 int K, int64_t segment_frames = 0) {
+                                 int K, int64_t segment_frames = 0, int select_bands = 0,
+                                 int select_D = 0) {
     size_t b = front_buffer_bytes(F, T, T_act, D, K);
     b += 2 * align_up(sizeof(double) * (size_t)F * T);       // masks
     b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
@@ -901,6 +966,10 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
                                 ? mvdr_segments_workspace_bytes(F, T, D, segment_frames)
                                 : mvdr_workspace_bytes(F, T, D));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
+    if (select_bands > 0)
+        stage = std::max(stage, chsel_workspace_bytes(F, T, select_D, select_bands) +
+                                    (select_D > D ? align_up(sizeof(cplx) * (size_t)F * T * select_D)
+                                                  : 0) + 4096);
     return b + stage + (1 << 16);
 }
 
@@ -983,9 +1052,25 @@ static int alloc_front(gss_ctx *ctx, const gss_params *p, int F, int64_t T, int6
 static int run_front(gss_ctx *ctx, const gss_params *p, const void *obs, int obs_type, int D,
                      int64_t N, const uint8_t *act, int K, int64_t N_act, int F, int64_t T,
                      int64_t T_act, const PipelineFront &fr, size_t mark,
-                     const EmGuide *guide = nullptr) {
+                     const EmGuide *guide = nullptr, const gss_channel_select *sel = nullptr,
+                     int D_all = 0) {
     cplx *const Y = fr.Y, *const X = fr.X;
-    GSS_TRY(stft_run(ctx, obs, obs_type, D, N, p->stft_fading, Y));
+    if (!sel) {
+        GSS_TRY(stft_run(ctx, obs, obs_type, D, N, p->stft_fading, Y));
+    } else if (D == D_all) {
+        // every channel is kept: ranked (the status words name them), nothing moves
+        GSS_TRY(stft_run(ctx, obs, obs_type, D, N, p->stft_fading, Y));
+        GSS_TRY(chsel_select_run(ctx, Y, F, T, D, *sel, nullptr, nullptr));
+        ctx->arena_off = mark;
+    } else {
+        // the STFT of all D_all channels lives above `mark` until the kept D = sel->keep of
+        // them are gathered into Y
+        cplx *Yall = arena_alloc_t<cplx>(ctx, (size_t)F * T * D_all);
+        GSS_REQUIRE(ctx, Yall, GSS_ERR_NOMEM, "workspace sizing bug");
+        GSS_TRY(stft_run(ctx, obs, obs_type, D_all, N, p->stft_fading, Yall));
+        GSS_TRY(chsel_select_run(ctx, Yall, F, T, D_all, *sel, Y, nullptr));
+        ctx->arena_off = mark;
+    }
     if (!p->wpe)    // no solve in this call: clear the count an earlier utterance left behind
         GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + 2, 0, sizeof(int32_t), ctx->stream));
     const int A = wpe_arrays_of(p);
@@ -1032,12 +1117,31 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
                                     double *out, const gss_debug_taps *taps,
                                     bool guided = false,
                                     const gss_guidance *guidance = nullptr,
-                                    const gss_bf_segments *seg = nullptr) {
+                                    const gss_bf_segments *seg = nullptr,
+                                    const gss_channel_select *sel = nullptr,
+                                    bool select = false) {
     GSS_REQUIRE(ctx, !guided || guidance, GSS_ERR_INVALID,
                 "gss_enhance_observation_guided: guidance is NULL");
     GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, guided ? (const void *)guidance : act, out,
                                  guided ? "gss_enhance_observation_guided"
-                                        : "gss_enhance_observation"));
+                                 : select ? "gss_enhance_observation_select"
+                                          : "gss_enhance_observation"));
+    // a selection: D_all channels come in, the pipeline below runs on the D = sel->keep kept
+    const int D_all = D;
+    if (select) {
+        GSS_TRY(check_channel_select(ctx, sel, D, true, "gss_enhance_observation_select"));
+        GSS_REQUIRE(ctx, !(p->wpe && p->wpe_arrays > 1), GSS_ERR_UNSUPPORTED,
+                    "gss_enhance_observation_select: wpe_arrays=%d, a selection breaks the equal "
+                    "arrays of the per-array WPE", p->wpe_arrays);
+        GSS_REQUIRE(ctx, p->bf != 1, GSS_ERR_UNSUPPORTED,
+                    "gss_enhance_observation_select: bf=1 ('ch2') names a physical channel");
+        const int64_t T_all = gss_stft_num_frames(N, p->stft_size, p->stft_shift, p->stft_fading);
+        GSS_REQUIRE(ctx, (int64_t)(p->stft_size / 2 + 1) * T_all * D_all < (1LL << 31),
+                    GSS_ERR_UNSUPPORTED,
+                    "F * T * D = %lld STFT bins: 2^31 or more are not supported",
+                    (long long)((int64_t)(p->stft_size / 2 + 1) * T_all * D_all));
+        D = sel->keep;
+    }
     GSS_REQUIRE(ctx, !guided || !taps || !taps->act_frames, GSS_ERR_INVALID,
                 "gss_enhance_observation_guided: taps->act_frames must be NULL (a guided call "
                 "has no frame activity)");
@@ -1055,7 +1159,8 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     if (guided) GSS_TRY(check_guidance(ctx, guidance, K, T, &guide));
 
     GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K,
-                                                  seg ? seg->segment_frames : 0)));
+                                                  seg ? seg->segment_frames : 0,
+                                                  select ? sel->bands : 0, D_all)));
     PipelineFront fr;
     GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
     double *mx = arena_alloc_t<double>(ctx, (size_t)F * T);
@@ -1065,7 +1170,7 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
     const size_t mark = ctx->arena_off;
     GSS_TRY(run_front(ctx, p, obs, obs_type, D, N, act, K, N_act, F, T, T_act, fr, mark,
-                      guided ? &guide : nullptr));
+                      guided ? &guide : nullptr, select ? sel : nullptr, D_all));
     cplx *const X = fr.X;
 
     int64_t sf = 0, ef = 0;
@@ -1228,6 +1333,29 @@ extern "C" int gss_enhance_observation_pcm16(gss_ctx *ctx, const gss_params *p,
     GSS_ENTER_VARIANTS(ctx);
     return enhance_observation_impl(ctx, p, obs, 1, D, N, act, K, N_act, target, start_ctx, end_ctx,
                                     out, taps);
+}
+
+extern "C" int gss_enhance_observation_select(gss_ctx *ctx, const gss_params *p,
+                                              const double *obs, int D, int64_t N,
+                                              const uint8_t *act, int K, int64_t N_act,
+                                              int target, int64_t start_ctx, int64_t end_ctx,
+                                              const gss_channel_select *sel, double *out,
+                                              const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, /*guided=*/false, nullptr, nullptr, sel, true);
+}
+
+extern "C" int gss_enhance_observation_select_pcm16(gss_ctx *ctx, const gss_params *p,
+                                                    const int16_t *obs, int D, int64_t N,
+                                                    const uint8_t *act, int K, int64_t N_act,
+                                                    int target, int64_t start_ctx,
+                                                    int64_t end_ctx,
+                                                    const gss_channel_select *sel, double *out,
+                                                    const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    return enhance_observation_impl(ctx, p, obs, 1, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, /*guided=*/false, nullptr, nullptr, sel, true);
 }
 
 extern "C" int gss_enhance_observation_targets(gss_ctx *ctx, const gss_params *p,

@@ -170,6 +170,9 @@ struct gss_ctx {
     int32_t *status_host = nullptr;
     int32_t *status_dev = nullptr;
     int last_targets = 0;   // S of the last beamformer run when it was a targets call, else 0
+    // [GSS_STATUS_CHANNELS + j]: the j-th channel (ascending) the last channel selection kept,
+    // written by chsel_pick_kernel
+    int last_selected = 0;  // n of the last channel selection on this context, 0 = none yet
 
     // WPE tile lists (device), rebuilt when (taps, delay, D) changes
     void *wpe_tiles = nullptr;
@@ -185,7 +188,9 @@ struct gss_ctx {
 
 #define GSS_STATUS_SEGMENT_FALLBACKS 3                           // see gss_ctx::status_host
 #define GSS_STATUS_TARGETS 16                                    // first per-target word
-#define GSS_STATUS_BYTES (4 * (GSS_STATUS_TARGETS + GSS_MAX_CLASSES + 1))
+#define GSS_STATUS_CHANNELS 40                                   // first selected-channel word
+#define GSS_STATUS_BYTES (4 * (GSS_STATUS_CHANNELS + GSS_MAX_CHANNELS))
+static_assert(GSS_STATUS_TARGETS + GSS_MAX_CLASSES + 1 <= GSS_STATUS_CHANNELS, "status words overlap");
 
 int gss_fail(gss_ctx *ctx, int code, const char *fmt, ...);
 
@@ -322,6 +327,17 @@ int mask_mul_run(gss_ctx *ctx, cplx *Xhat, const double *mask_ft, int F, int64_t
 // (src_stride 0: one X_hat for every target; src == dst with stride F T: in place)
 int mask_mul_targets_run(gss_ctx *ctx, const cplx *src, int64_t src_stride, cplx *dst,
                          const double *mx, int F, int64_t T, int S, int apply_mask);
+
+// Envelope-variance channel selection (chsel.hip; include/gss_hip.h: gss_channel_select).  `sel`
+// has been validated by the entry point; workspace from the arena (chsel_workspace_bytes).
+// scores_run: Y (F,T,D) -> scores (D), band variances (B,D) into band_var when given.
+// select_run: scores, then the sel.keep best channels in ascending order -> channels (device,
+// may be NULL) and the context's status words; Ysel (F,T,keep) gathered unless NULL.
+size_t chsel_workspace_bytes(int F, int64_t T, int D, int B);
+int chsel_scores_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
+                     const gss_channel_select &sel, double *scores, double *band_var);
+int chsel_select_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
+                     const gss_channel_select &sel, cplx *Ysel, int32_t *channels);
 
 int selftest_mfma_run(gss_ctx *ctx);
 

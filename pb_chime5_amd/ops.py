@@ -13,6 +13,9 @@ here                        reference call (file:line)
 ``mvdr_souden_from_masks``  pb_bss beamformer chain       (beamforming_wrapper.py:51-97)
 ``mvdr_souden_segments_from_masks``  the same with statistics per segment of frames
 ``enhance_observation``     Enhancer.enhance_observation  (core.py:514-571)
+``channel_scores`` / ``select_channels`` / ``enhance_observation_select``
+                            envelope-variance channel selection ahead of WPE (not in the
+                            reference, which picks microphones by position)
 =========================  ====================================================
 
 All of them raise if libgss_hip.so or a GPU is missing.
@@ -22,8 +25,8 @@ import ctypes
 import numpy as np
 
 from . import _capi
-from ._capi import (Context, GssBfSegments, GssDebugTaps, GssGuidance, GssParams, c_void_p,
-                    default_context)
+from ._capi import (Context, GssBfSegments, GssChannelSelect, GssDebugTaps, GssGuidance,
+                    GssParams, c_void_p, default_context)
 
 _BF_CODES = {'mvdrSouden_ban': 0, 'ch2': 1, 'sum': 2, 'gev_ban': 3}
 _POSTFILTER_CODES = {None: 0, 'mask_mul': 1}
@@ -525,6 +528,227 @@ def activity_time_to_frequency_device(time_activity, size, shift, fading, *, ctx
 
 
 # --------------------------------------------------------------------------
+# envelope-variance channel selection (gss_channel_select; Wolf & Nadeu 2014)
+# --------------------------------------------------------------------------
+MAX_BANDS = 64          # bands of a band table (the accumulators of chsel_bands)
+
+
+def _is_integer(value):
+    return isinstance(value, (int, np.integer)) and not isinstance(value, bool)
+
+
+def _is_real(value):
+    return isinstance(value, (int, float, np.integer, np.floating)) \
+        and not isinstance(value, bool)
+
+
+def check_channel_bands(bands):
+    if not _is_integer(bands) or not 1 <= bands <= MAX_BANDS:
+        raise ValueError(f'bands={bands!r}: an integer in [1, {MAX_BANDS}]')
+    return int(bands)
+
+
+def check_channel_floor(floor):
+    if not _is_real(floor) or not np.isfinite(floor) or not 0 <= floor < 1:
+        raise ValueError(f'floor={floor!r}: a finite number in [0, 1)')
+    return float(floor)
+
+
+def check_channel_keep(keep, num_channels=None):
+    """How many of ``num_channels`` channels a selection keeps.  An ``int`` >= 1 is a count (a
+    count >= D keeps all channels); a ``float`` in (0, 1] is a share, n = max(1, ceil(share *
+    D)), where a product within 1e-9 of an integer counts as that integer (0.8 of 20 channels
+    is 16, not the 17 that 16.000000000000004 rounds up to).  bool, strings, NaN, 0, negative
+    values and floats above 1 are ValueError.  Without ``num_channels`` the value is only
+    checked and returned as it is."""
+    if _is_integer(keep):
+        if keep < 1:
+            raise ValueError(f'keep={keep!r}: a count >= 1 or a share in (0, 1]')
+        return int(keep) if num_channels is None else min(int(keep), int(num_channels))
+    if isinstance(keep, (float, np.floating)) and 0 < keep <= 1:     # (NaN compares false)
+        if num_channels is None:
+            return float(keep)
+        return max(1, int(np.ceil(np.round(float(keep) * int(num_channels), 9))))
+    raise ValueError(f'keep={keep!r}: a count >= 1 or a share in (0, 1]')
+
+
+def mel_bank(bands, stft_size, sample_rate=16000):
+    """The default band table (B, F) of the channel selection, F = stft_size // 2 + 1: ``bands``
+    triangular filters equally spaced on the HTK mel scale, mel = 2595 log10(1 + f / 700),
+    between 0 and sample_rate / 2.  Filter b rises linearly (in Hz) from edge b to edge b + 1
+    and falls to edge b + 2; it is evaluated at the centre frequencies k * sample_rate /
+    stft_size of the F bins.  Built on the host, like the windows: the library holds no band
+    policy."""
+    bands = check_channel_bands(bands)
+    if not _is_integer(stft_size) or stft_size < 2 or stft_size % 2:
+        raise ValueError(f'stft_size={stft_size!r}: an even integer >= 2')
+    if not _is_real(sample_rate) or not np.isfinite(sample_rate) or sample_rate <= 0:
+        raise ValueError(f'sample_rate={sample_rate!r}: a positive number')
+    F = int(stft_size) // 2 + 1
+    top = 2595.0 * np.log10(1.0 + (float(sample_rate) / 2.0) / 700.0)
+    edges = 700.0 * (10.0 ** (np.linspace(0.0, top, bands + 2) / 2595.0) - 1.0)
+    freqs = np.arange(F) * (float(sample_rate) / int(stft_size))
+    lo, mid, hi = edges[:-2, None], edges[1:-1, None], edges[2:, None]
+    rise = (freqs[None, :] - lo) / (mid - lo)
+    fall = (hi - freqs[None, :]) / (hi - mid)
+    return np.maximum(0.0, np.minimum(rise, fall))
+
+
+def check_channel_bank(bank, bands, num_frequencies, sample_rate=16000):
+    """The band table of a selection on ``num_frequencies`` bins as a (B, F) float64 array:
+    ``bank`` checked (2-D, 1 .. 64 rows, F columns, finite, non-negative), or None: the
+    `mel_bank` of ``bands`` filters.  ValueError otherwise."""
+    F = int(num_frequencies)
+    if bank is None:
+        bands = check_channel_bands(bands)
+        if F < 2:
+            raise ValueError(f'bank: the default mel bank needs at least 2 frequencies, not {F}')
+        return mel_bank(bands, 2 * (F - 1), sample_rate)
+    try:
+        W = np.ascontiguousarray(bank, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('bank: not a real array') from None
+    if W.ndim != 2 or not 1 <= W.shape[0] <= MAX_BANDS or W.shape[1] != F:
+        raise ValueError(f'bank: shape {W.shape} is not (B, F) with 1 <= B <= {MAX_BANDS} '
+                         f'and F = {F}')
+    if not np.all(np.isfinite(W)) or np.any(W < 0):
+        raise ValueError('bank: weights must be finite and >= 0')
+    return W
+
+
+class ChannelSelect:
+    """The checked settings of a channel selection -- ``keep`` (count or share, see
+    `check_channel_keep`; None: scores only), the band table (B, F) and the relative floor --
+    and the table's copy in HBM per context.  `struct(ctx, D)` is the gss_channel_select of a
+    call on D channels."""
+
+    def __init__(self, keep, num_frequencies, bank=None, bands=40, floor=1e-10,
+                 sample_rate=16000):
+        self.keep = None if keep is None else check_channel_keep(keep)
+        self.floor = check_channel_floor(floor)
+        self.bank = check_channel_bank(bank, bands, num_frequencies, sample_rate)
+        self._device = {}
+
+    @property
+    def bands(self):
+        return self.bank.shape[0]
+
+    def count(self, num_channels):
+        return check_channel_keep(self.keep, num_channels)
+
+    def struct(self, ctx, num_channels):
+        buf = self._device.get(id(ctx))
+        if buf is None or buf[0] is not ctx or buf[1].ptr is None:
+            buf = self._device[id(ctx)] = (ctx, ctx.to_device(self.bank))
+        return GssChannelSelect(bank_dev=buf[1].ptr, bands=self.bands,
+                                keep=0 if self.keep is None else self.count(num_channels),
+                                floor=self.floor)
+
+
+def _check_obs_dtf(Obs):
+    Obs = np.asarray(Obs)
+    if Obs.ndim != 3:
+        raise ValueError(f'Obs: shape {Obs.shape} is not (D,T,F)')
+    if 0 in Obs.shape:
+        raise ValueError(f'Obs: shape {Obs.shape} has an empty axis')
+    return Obs
+
+
+def channel_scores(Obs, bank=None, bands=40, floor=1e-10, return_band_variances=False, *,
+                   sample_rate=16000, ctx=None):
+    """The envelope-variance score of every channel of an STFT (gss_channel_scores): Obs
+    (D,T,F) complex -> scores (D,) float64 in [0, B], high for channels that are close to the
+    speaker and dry, 0 for a channel that is zero in every frame.  ``bank`` (B,F) >= 0 is the
+    band table (None: `mel_bank` of ``bands`` filters for a ``sample_rate`` Hz signal),
+    ``floor`` the floor of a band energy relative to its maximum over time.  With
+    ``return_band_variances`` also V (B,D), the variance of the compressed envelope per band.
+    The measure is written down in tests/channel_select_reference.py.  Argument errors are
+    ValueError before any device work."""
+    Obs = _check_obs_dtf(Obs)
+    sel = ChannelSelect(None, Obs.shape[2], bank, bands, floor, sample_rate)
+    ctx = ctx or default_context()
+    Y_d, (D, T, F) = _obs_to_device_ftd(ctx, Obs)
+    st = sel.struct(ctx, D)
+    s_d = ctx.empty(8 * D)
+    v_d = ctx.empty(8 * sel.bands * D) if return_band_variances else None
+    ctx._check(ctx.lib.gss_channel_scores(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, ctypes.byref(st), c_void_p(s_d.ptr),
+        c_void_p(v_d.ptr) if v_d is not None else None), 'gss_channel_scores')
+    scores = ctx.to_host(s_d, (D,), np.float64)
+    if return_band_variances:
+        return scores, ctx.to_host(v_d, (sel.bands, D), np.float64)
+    return scores
+
+
+def select_channels(Obs, keep, bank=None, bands=40, floor=1e-10, *, sample_rate=16000,
+                    ctx=None):
+    """Keep the ``keep`` channels of highest `channel_scores` (gss_select_channels): Obs
+    (D,T,F) -> (Obs[channels] (n,T,F), channels (n,) int in ascending order -- the array-major
+    order of the observation survives).  ``keep``: a count or a share of D, see
+    `check_channel_keep`; equal scores go to the lower channel index.  Argument errors are
+    ValueError before any device work."""
+    Obs = _check_obs_dtf(Obs)
+    sel = ChannelSelect(keep, Obs.shape[2], bank, bands, floor, sample_rate)
+    n = sel.count(Obs.shape[0])
+    ctx = ctx or default_context()
+    Y_d, (D, T, F) = _obs_to_device_ftd(ctx, Obs)
+    st = sel.struct(ctx, D)
+    o_d = ctx.empty(16 * F * T * n)
+    c_d = ctx.empty(max(4 * n, 16))
+    ctx._check(ctx.lib.gss_select_channels(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, ctypes.byref(st), c_void_p(o_d.ptr),
+        c_void_p(c_d.ptr)), 'gss_select_channels')
+    ctx.selected_count = n
+    channels = ctx.to_host(c_d, (n,), np.int32).astype(int)
+    return _ftd_to_host_dtf(ctx, o_d, n, T, F), channels
+
+
+def _check_select_params(params, what):
+    """What a selection cannot be combined with, before any device work."""
+    if params.bf == _BF_CODES['ch2']:
+        raise NotImplementedError(f"{what} with bf='ch2': 'ch2' names a physical channel")
+    if params.wpe and params.wpe_arrays > 1:
+        raise NotImplementedError(f'{what} with wpe_arrays={params.wpe_arrays}: a selection '
+                                  'breaks the equal arrays of the per-array WPE')
+
+
+def enhance_observation_select(obs, activity, target_index, start_context_samples,
+                               end_context_samples, *, keep, bank=None, bands=40, floor=1e-10,
+                               sample_rate=16000, params=None, window=None, debug=False,
+                               ctx=None, **param_kwargs):
+    """`enhance_observation` on the ``keep`` channels the envelope-variance measure ranks best
+    (gss_enhance_observation_select): the STFT runs on all D channels, `select_channels` on the
+    device, then the unchanged pipeline on the kept n.  obs (D,N) float64 or int16 PCM.  With
+    n = D the result equals `enhance_observation` bit for bit.  ``debug=True`` details as
+    there -- ``Obs`` is (n,T,F) and ``ref_channel`` an index into the kept channels -- plus
+    ``selected_channels`` (n,), which maps it back.  The limits of the beamformers (fewer than
+    30 channels) apply to n, not D.  bf='ch2' and a per-array WPE are NotImplementedError, bad
+    settings ValueError, both before any device work."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    _check_select_params(params, 'channel selection')
+    obs = np.asarray(obs)
+    if obs.ndim != 2:
+        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    sel = ChannelSelect(keep, params.stft_size // 2 + 1, bank, bands, floor, sample_rate)
+    n = sel.count(obs.shape[0])
+    ctx = ctx or default_context()
+    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
+    utt = ResidentUtterance(ctx, obs, activity, params, pcm=obs.dtype == np.int16)
+    bufs, taps = _debug_taps(utt, D=n) if debug else ({}, None)
+    utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
+                channel_select=sel)
+    x_hat = utt.result()
+    if not debug:
+        return x_hat
+    details = _debug_details(utt, bufs, D=n)
+    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+    details['ref_channel'] = int(details['ref_channel'])
+    details['selected_channels'] = np.array(ctx.last_selected_channels(n), dtype=int)
+    return x_hat, details
+
+
+# --------------------------------------------------------------------------
 # fused pipeline
 # --------------------------------------------------------------------------
 def make_params(*, stft_size=1024, stft_shift=256, stft_fading=True, wpe=True, wpe_taps=10,
@@ -584,10 +808,26 @@ class ResidentUtterance:
         self.act_d = ctx.to_device(act)
         self.out_d = ctx.empty(8 * max(self.n_out, 1))
 
-    def enqueue(self, target_index, start_context, end_context, taps=None, segments=None):
+    def enqueue(self, target_index, start_context, end_context, taps=None, segments=None,
+                channel_select=None):
         """``segments``: a gss_bf_segments (`check_bf_segments`) for the segment-wise
-        beamformer (gss_enhance_observation_segments; float64 samples only)."""
+        beamformer (gss_enhance_observation_segments; float64 samples only).
+        ``channel_select``: a `ChannelSelect` for the envelope-variance selection ahead of WPE
+        (gss_enhance_observation_select / its pcm16 twin; not together with segments)."""
         ctx = self.ctx
+        if channel_select is not None:
+            assert segments is None, 'no selection inside the segment-wise call'
+            st = channel_select.struct(ctx, self.D)
+            entry = (ctx.lib.gss_enhance_observation_select_pcm16 if self.pcm
+                     else ctx.lib.gss_enhance_observation_select)
+            ctx._check(entry(
+                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
+                self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
+                int(start_context), int(end_context), ctypes.byref(st),
+                c_void_p(self.out_d.ptr), ctypes.byref(taps) if taps is not None else None),
+                'gss_enhance_observation_select')
+            ctx.selected_count = st.keep
+            return
         if segments is not None:
             assert not self.pcm, 'the segment-wise call has no pcm16 twin'
             ctx._check(ctx.lib.gss_enhance_observation_segments(
@@ -757,13 +997,17 @@ class UtterancePipeline:
         self._staging.put(staging)
 
     def enqueue_staged(self, tag, staging, target_index, start_context, end_context, keep=None,
-                       wpe_arrays=None):
+                       wpe_arrays=None, channel_select=None):
         """Like enqueue() for inputs sitting in a HostStaging set: two asynchronous DMAs, the
         kernels behind them, and an asynchronous D2H of the samples ``keep = (a, b)`` of the
         result (default: all) into page-locked memory -- the host thread does not wait for any
-        of it.  The set goes back to the free list when the utterance is popped."""
+        of it.  The set goes back to the free list when the utterance is popped.
+        ``channel_select``: a `ChannelSelect`; the utterance takes
+        gss_enhance_observation_select_pcm16, still without any wait."""
         assert not self.full(), 'pop() the oldest utterance first'
         p = params_for(self.params, staging.obs.shape[0], wpe_arrays)
+        if channel_select is not None:
+            _check_select_params(p, 'channel selection')
         slot = self._next
         self._next = (self._next + 1) % len(self.slots)
         ctx = self.slots[slot]
@@ -787,12 +1031,21 @@ class UtterancePipeline:
             out_h = self._out_host[slot] = ctx.pinned(
                 max(int(8 * (b - a) * 1.25) + 4096, 2 * have))
         out_view = out_h.view((b - a,), np.float64)
+        # (the band table of a selection is copied to the slot's GPU once, on its first use)
+        st = channel_select.struct(ctx, D) if channel_select is not None else None
         ctx.upload_async(obs_d, obs)
         ctx.upload_async(act_d, act)
-        ctx._check(ctx.lib.gss_enhance_observation_pcm16(
-            ctx.handle, ctypes.byref(p), c_void_p(obs_d.ptr), D, N, c_void_p(act_d.ptr), K,
-            N_act, int(target_index), int(start_context), int(end_context),
-            c_void_p(out_d.ptr), None), 'gss_enhance_observation')
+        if st is not None:
+            ctx._check(ctx.lib.gss_enhance_observation_select_pcm16(
+                ctx.handle, ctypes.byref(p), c_void_p(obs_d.ptr), D, N, c_void_p(act_d.ptr), K,
+                N_act, int(target_index), int(start_context), int(end_context),
+                ctypes.byref(st), c_void_p(out_d.ptr), None), 'gss_enhance_observation_select')
+            ctx.selected_count = st.keep
+        else:
+            ctx._check(ctx.lib.gss_enhance_observation_pcm16(
+                ctx.handle, ctypes.byref(p), c_void_p(obs_d.ptr), D, N, c_void_p(act_d.ptr), K,
+                N_act, int(target_index), int(start_context), int(end_context),
+                c_void_p(out_d.ptr), None), 'gss_enhance_observation')
         if b > a:
             ctx.download_async(out_view, out_d, offset=8 * a)
         self._pending.append((tag, slot, n_out, staging, out_view))
@@ -980,10 +1233,11 @@ def enhance_observation_guided(obs, initialization, source_activity_mask, target
 _PER_TARGET = ('target_mask', 'distortion_mask', 'X_hat', 'ref_channel')
 
 
-def _debug_taps(utt, S=1):
+def _debug_taps(utt, S=1, D=None):
     """Device buffers for the debug taps of a call on ``utt`` with S targets (per-target taps
-    S blocks), the reference channels preset to -1."""
-    ctx, D, K, T = utt.ctx, utt.D, utt.K, utt.T
+    S blocks), the reference channels preset to -1.  ``D``: the channels of the ``Obs_ftd`` tap
+    when a selection kept fewer than the utterance has."""
+    ctx, D, K, T = utt.ctx, utt.D if D is None else D, utt.K, utt.T
     F = utt.params.stft_size // 2 + 1
     bufs = {
         'Obs_ftd': ctx.empty(16 * F * T * D), 'act_frames': ctx.empty(max(K * T, 16)),
@@ -996,9 +1250,9 @@ def _debug_taps(utt, S=1):
     return bufs, GssDebugTaps(**{k: v.ptr for k, v in bufs.items()})
 
 
-def _debug_details(utt, bufs, S=1):
+def _debug_details(utt, bufs, S=1, D=None):
     """The taps in the reference's layouts; the per-target ones stacked over S."""
-    ctx, D, K, T = utt.ctx, utt.D, utt.K, utt.T
+    ctx, D, K, T = utt.ctx, utt.D if D is None else D, utt.K, utt.T
     F = utt.params.stft_size // 2 + 1
     details = {}
     if 'act_frames' in bufs:     # (a guided call has no frame activity)

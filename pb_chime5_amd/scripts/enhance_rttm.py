@@ -15,6 +15,14 @@ import argparse
 from pathlib import Path
 
 
+def _channel_keep(text):
+    """'20' -> 20 channels, '0.8' -> a share of the channels."""
+    try:
+        return int(text)
+    except ValueError:
+        return float(text)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument('--chime6-dir', required=True)
@@ -39,6 +47,11 @@ def main(argv=None):
                          'frames, a multiple of 64 (get_enhancer(bf_segment_frames=...))')
     ap.add_argument('--bf-segment-context', type=int, default=0,
                     help='segments either side in the statistics of a segment')
+    ap.add_argument('--channel-keep', type=_channel_keep, default=None,
+                    help='keep the channels the envelope-variance measure ranks best: a count '
+                         '(20) or a share (0.8) (get_enhancer(channel_keep=...))')
+    ap.add_argument('--channel-bands', type=int, default=40,
+                    help='mel filters of the channel selection')
     ap.add_argument('--no-bf-drop-context', action='store_true')
     ap.add_argument('--job-id', type=int, default=1)
     ap.add_argument('--number-of-jobs', type=int, default=1)
@@ -57,7 +70,8 @@ def main(argv=None):
         bss_iterations=args.bss_iterations, bss_iterations_post=args.bss_iterations_post,
         bf_drop_context=not args.no_bf_drop_context, bf=args.bf, postfilter=args.postfilter,
         device_id=parallel.device_index(), wpe_per_array=args.wpe_per_array,
-        bf_segment_frames=args.bf_segment_frames, bf_segment_context=args.bf_segment_context)
+        bf_segment_frames=args.bf_segment_frames, bf_segment_context=args.bf_segment_context,
+        channel_keep=args.channel_keep, channel_bands=args.channel_bands)
     if parallel.is_master():
         Path(args.out).mkdir(parents=True, exist_ok=True)
     parallel.barrier()
