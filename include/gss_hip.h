@@ -82,7 +82,8 @@ typedef enum {
  * the segment settings travel in a descriptor of their own).  So were gss_channel_scores,
  * gss_select_channels, gss_last_selected_channels and gss_enhance_observation_select(_pcm16)
  * with the gss_channel_select descriptor: entry points only, gss_params and gss_debug_taps keep
- * their layouts, revision still 7. */
+ * their layouts, revision still 7.  So were gss_cacgmm_fit and gss_cacgmm_predict with the
+ * gss_cacgmm_model descriptor. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -234,6 +235,68 @@ typedef struct {
 int gss_cacgmm_guided(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
                       const gss_guidance *guidance, int K, int iterations,
                       int iterations_post, double *gamma_dev);
+
+/* ---- the mixture model as an object ---------------------------------------
+ * A fitted CACGMM in caller-owned device buffers: exactly what predict needs, no eigenvector
+ * phases.  (Entry points only, looked up by the binding: revision still 7.)
+ *
+ * Scale.  The posteriors and the log-likelihood depend on (B_k^-1, ln det B_k) only through
+ * -D ln(y^H B_k^-1 y) - ln det B_k, which does not change when B_k is multiplied by a positive
+ * number.  pb_bss fixes that number by dividing the eigenvalues by their maximum.  The model
+ * update of this library takes a Cholesky factorisation wherever it can certify that no
+ * eigenvalue would be floored and then leaves B_k at the scale of D * sum(w y y^H) / sum(gamma);
+ * only the classes that take the eigendecomposition (a floored eigenvalue, an all-zero frame in
+ * the frequency) come out normalised.  gss_cacgmm_fit hands the model out as the EM holds it, so
+ * that a later predict or fit continues from the very same bits; to compare it with a pb_bss
+ * model, scale class k by c = 1 / lambda_min(precision): precision * c and log_det - D ln c
+ * (pb_chime5_amd.cacgmm.CACGMM.normalized() does that on the host).  A model given to
+ * gss_cacgmm_predict / gss_cacgmm_fit may have any scale, the normalised one of pb_bss
+ * included. */
+typedef struct {
+    gss_cplx *precision_dev;  /* (F,K,D,D) row-major: B_k^-1, Hermitian, both triangles stored
+                                 (a reader takes the upper one and the real part of the diagonal) */
+    double   *log_det_dev;    /* (F,K): ln det B_k at the scale of precision_dev (for a normalised
+                                 model: the sum of ln of the normalised, floored eigenvalues)      */
+    double   *weight_dev;     /* (F,K): pi_k */
+} gss_cacgmm_model;
+
+/* CACGMMTrainer.fit.  Y (F,T,D) -> model_out.
+ * init_model == NULL: fit(y, initialization=array, iterations, source_activity_mask):
+ *   `iterations` >= 1 M-steps from the guidance's initialisation; schedule, mask and the clip
+ *   1e-10 are the masked fit of gss_cacgmm_guided, and so are the errors of the guidance.
+ * init_model != NULL: fit(y, initialization=model, iterations, source_activity_mask): every
+ *   iteration is an E-step from the current model followed by an M-step, masked with
+ *   guidance->mask_dev (unmasked if guidance is NULL or has no mask); guidance->init_dev is not
+ *   read; iterations == 0 copies the model.  model_out may be the buffers of init_model.
+ * The launches are those of gss_cacgmm_guided, in its order, plus the conversions of the model,
+ * so  fit(I) + predict(mask) / fit(I) + predict() / fit(I) + fit(model, post - 1, no mask) +
+ * predict()  give the posteriors of gss_cacgmm_guided(I, post) for post 0 / 1 / 2+ bit for bit --
+ * except for one array (D == 4, 2 <= K <= 6), where gss_cacgmm_guided runs the whole EM in one
+ * launch that keeps its model on the chip: the model calls take the multi-launch path there
+ * (the one GSS_VARIANT=em_unfused selects for the closed call) and agree with the closed call to
+ * rounding, not to the bit.
+ * GSS_ERR_INVALID: model_out or one of its fields NULL, a field of init_model NULL,
+ * iterations < 0, iterations == 0 without init_model, the stride errors of gss_cacgmm_guided.
+ * D and K are limited as for gss_cacgmm. */
+int gss_cacgmm_fit(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                   const gss_guidance *guidance, int K, int iterations,
+                   const gss_cacgmm_model *init_model, const gss_cacgmm_model *model_out);
+
+/* CACGMM.predict with affiliation_eps = 0, and the log-likelihood of the frames.  Y (F,T,D) of
+ * any frame count (not necessarily the one the model was fitted on); guidance NULL or without a
+ * mask: unmasked, only the mask fields are read.  gamma_dev (F,K,T) or NULL, loglik_dev (F,T) or
+ * NULL, at least one of them.
+ *   loglik[f,t] = ln sum_k pi_k m_kt exp(-D ln q_kt - ln det B_k),
+ * q_kt = max(|y^H B_k^-1 y|, tiny) on the unit-normalised frame as the E-step forms it, m_kt the
+ * mask (or 1), evaluated as a max-shifted log-sum-exp.  The normalising constant of the complex
+ * angular central Gaussian density, ln((D-1)! / (2 pi^D)), does not depend on the data or the
+ * model and is LEFT OUT.  A frame with every class masked off gives -inf.  No atomics: the same
+ * call gives the same bits.
+ * GSS_ERR_INVALID: model or one of its fields NULL, both outputs NULL, the stride errors of the
+ * mask as gss_cacgmm_guided. */
+int gss_cacgmm_predict(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                       const gss_cacgmm_model *model, int K, const gss_guidance *guidance,
+                       double *gamma_dev, double *loglik_dev);
 
 /* A0  mask post-processing of enhance_observation (core.py:537-554): zero the
  * context frames, pick the target class, sum the others.

@@ -39,6 +39,11 @@ class GssDebugTaps(ctypes.Structure):
         'Xhat', 'ref_channel')]
 
 
+class GssCacgmmModel(ctypes.Structure):
+    """gss_cacgmm_model: precision (F,K,D,D) complex, log_det (F,K), weight (F,K) in HBM."""
+    _fields_ = [('precision_dev', c_void_p), ('log_det_dev', c_void_p), ('weight_dev', c_void_p)]
+
+
 class GssGuidance(ctypes.Structure):
     """gss_guidance: element (f, k, t) of a table at [f * f_stride + k * k_stride + t]."""
     _fields_ = [('init_dev', c_void_p), ('mask_dev', c_void_p),
@@ -102,6 +107,12 @@ SIGNATURES = {
                            c_int, c_int, c_int, c_void_p]),
     'gss_cacgmm_guided': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
                                   ctypes.POINTER(GssGuidance), c_int, c_int, c_int, c_void_p]),
+    'gss_cacgmm_fit': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
+                               ctypes.POINTER(GssGuidance), c_int, c_int,
+                               ctypes.POINTER(GssCacgmmModel), ctypes.POINTER(GssCacgmmModel)]),
+    'gss_cacgmm_predict': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
+                                   ctypes.POINTER(GssCacgmmModel), c_int,
+                                   ctypes.POINTER(GssGuidance), c_void_p, c_void_p]),
     'gss_masks_from_posteriors': (
         c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_int64,
                 c_int64, c_void_p, c_void_p]),

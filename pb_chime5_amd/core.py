@@ -139,6 +139,30 @@ class _ReferenceUnpickler(__import__('pickle').Unpickler):
         return super().find_class(module, name)
 
 
+class _DebugLocals(dict):
+    """``GSS.locals``: the locals of the call, and under 'learned' the fitted
+    `pb_chime5_amd.cacgmm.CACGMM`.  The model costs a fit, so it is fitted when the key is first
+    read with ``[]`` or ``get``; ``in`` knows the key without fitting.  Iteration, ``keys()``,
+    ``items()`` and ``dict(...)`` show 'learned' only once it has been read.  The mapping holds
+    the call's ``Obs`` -- as the reference's ``locals()`` does -- until ``GSS.locals`` is replaced."""
+
+    def __init__(self, values, learned):
+        super().__init__((k, v) for k, v in values.items() if k != 'learned')
+        self._learned = learned
+
+    def __missing__(self, key):
+        if key != 'learned':
+            raise KeyError(key)
+        self[key] = self._learned()
+        return self[key]
+
+    def __contains__(self, key):
+        return key == 'learned' or super().__contains__(key)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+
 @dataclass
 class GSS:
     """core.py:144-214 -> CACGMMTrainer.fit / predict for every frequency."""
@@ -153,7 +177,8 @@ class GSS:
         (K,T,F): initial affiliations used as given instead of the ones derived from the
         activity (a neural mask, the posteriors of an earlier pass).  A 0/1 activity without
         ``initialization`` takes the unweighted call; everything else the guided one."""
-        if ops.activity_is_binary(acitivity_freq, initialization):
+        binary = ops.activity_is_binary(acitivity_freq, initialization)
+        if binary:
             posterior = ops.cacgmm_posteriors(
                 Obs, acitivity_freq, iterations=self.iterations,
                 iterations_post=self.iterations_post)
@@ -167,7 +192,16 @@ class GSS:
                 Obs, initialization, source_active_mask, iterations=self.iterations,
                 iterations_post=self.iterations_post)
         if debug:
-            self.locals = locals()
+            # 'learned' (core.py:204-212): the model of the schedule's last fit -- the fits of the
+            # schedule once more, as calls that hand the model out, when the key is first read
+            # (a 0/1 activity: the initialisation derived on the device, as the call above did)
+            def learned():
+                model = ops.cacgmm_fit(Obs, None if binary else initialization, source_active_mask,
+                                       iterations=self.iterations)
+                if self.iterations_post > 1:
+                    model = ops.cacgmm_fit(Obs, iterations=self.iterations_post - 1, model=model)
+                return model
+            self.locals = _DebugLocals(locals(), learned)
         return posterior
 
 

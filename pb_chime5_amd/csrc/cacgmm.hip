@@ -2219,7 +2219,7 @@ namespace {
 // offset to the block's first frequency, strides from the block's own plan.
 struct EmBlock {
     EmArgs a;
-    int F;
+    int F, f0;
     cplx *Mq, *Yn;
     int *need_eigh, *zero_tiles;
     double *Sg_lds, *Sg_reg;
@@ -2235,10 +2235,26 @@ struct StreamRestore {
 
 int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGuide &guide, int K,
                int iterations, int iterations_post, double *gamma) {
+    EmSchedule s;
+    s.iterations = iterations;
+    // fit(initialization=model, iterations=post-1): no mask, default clip
+    s.model_iterations = std::max(iterations_post - 1, 0);
+    s.model_masked = false;
+    // predict: affiliation_eps = 0; mask only when iterations_post == 0
+    s.predict_masked = iterations_post == 0;
+    s.gamma = gamma;
+    s.onchip_allowed = true;
+    return cacgmm_schedule_run(ctx, Y, F, T, D, guide, K, s);
+}
+
+int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGuide &guide,
+                        int K, const EmSchedule &s) {
     const int NE = tri_count(D);
+    const int iterations = s.iterations;
+    double *const gamma = s.gamma;
     const bool reg = estep_reg_supported(D, K) && !gss_variant_set("estep_lds");
     // one array: the whole EM (all iterations + predict) in one launch (em_onchip4_kernel)
-    const bool onchip = D == 4 && K >= 2 && K <= 6 && reg && iterations > 0 &&
+    const bool onchip = s.onchip_allowed && D == 4 && K >= 2 && K <= 6 && reg && iterations > 0 &&
                         !gss_variant_set("em_unfused");
     const EmBlockPlan bplan = onchip ? EmBlockPlan{F, 1, 1} : em_block_plan(F, T, D, K);
     const EmStrides st = em_strides(bplan, F, T, D);
@@ -2278,11 +2294,15 @@ int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGui
         hipLaunchKernelGGL(tri_table_kernel, dim3(1), dim3(256), 0, ctx->stream, D, tri_tab);
         GSS_LAUNCH_CHECK(ctx, "tri_table_kernel");
     }
+    GSS_REQUIRE(ctx, !onchip || (!s.import_model && !s.export_model && !s.loglik), GSS_ERR_INVALID,
+                "cacgmm: the one-launch kernel keeps its model on the chip");
+    if (s.import_model) GSS_TRY(cacgmm_model_import(ctx, *s.import_model, F, K, D, Mq, logdet, pi));
 
     auto make_block = [&](int f0, int Fb, hipStream_t stream, EmBlock *blk) -> int {
         EmBlock &b = *blk;
         b = EmBlock{};
         b.F = Fb;
+        b.f0 = f0;
         b.stream = stream;
         EmArgs &a = b.a;
         a.Y = Y + (int64_t)f0 * T * D;
@@ -2313,7 +2333,7 @@ int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGui
         b.Sg_lds = Sg_lds + (int64_t)f0 * st.nch * K;
         b.Sg_reg = Sg_reg + (int64_t)f0 * st.reg_nch * K;
         a.Sg = b.Sg_lds;
-        a.gamma = gamma + (int64_t)f0 * K * T;
+        a.gamma = gamma ? gamma + (int64_t)f0 * K * T : nullptr;
         b.Yn = Yn + (int64_t)f0 * D * T;
         b.need_eigh = need_eigh + (int64_t)f0 * K;
         b.zero_tiles = zero_tiles + (int64_t)f0 * ntile;
@@ -2388,7 +2408,7 @@ int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGui
         o.T = T;
         o.F = F;
         o.iterations = iterations;
-        o.iterations_post = iterations_post;
+        o.iterations_post = s.predict_masked ? 0 : s.model_iterations + 1;
         o.force_eigh = force_eigh;
         o.zero_tiles = b.zero_tiles;
         o.ntile = ntile;
@@ -2441,24 +2461,32 @@ int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGui
                 b.a.aff_eps = 1e-10;
                 return em_iteration(b, it == 0);
             }));
-        // fit(initialization=model, iterations=post-1): no mask, default clip
-        for (int it = 0; it < iterations_post - 1; ++it)
+        // fit(initialization=model): every iteration an E-step from the current model, default clip
+        for (int it = 0; it < s.model_iterations; ++it)
             GSS_TRY(each([&](EmBlock &b) {
-                b.a.masked = 0;
+                b.a.masked = has_mask && s.model_masked ? 1 : 0;
                 b.a.aff_eps = 1e-10;
                 return em_iteration(b, false);
             }));
-        // predict: affiliation_eps = 0; mask only when iterations_post == 0
-        GSS_TRY(each([&](EmBlock &b) {
-            b.a.masked = has_mask && iterations_post == 0 ? 1 : 0;
-            b.a.aff_eps = 0.0;
-            return estep(b, MODE_PREDICT);
-        }));
+        // predict: affiliation_eps = 0
+        if (gamma)
+            GSS_TRY(each([&](EmBlock &b) {
+                b.a.masked = has_mask && s.predict_masked ? 1 : 0;
+                b.a.aff_eps = 0.0;
+                return estep(b, MODE_PREDICT);
+            }));
+        if (s.loglik)
+            GSS_TRY(each([&](EmBlock &b) {
+                return cacgmm_loglik_run(ctx, b.Yn, b.Mq, b.a.logdet, b.a.pi, b.a.act, act_stride,
+                                         act_fstride, has_mask && s.predict_masked ? 1 : 0, b.F, T, D,
+                                         K, s.loglik + (int64_t)b.f0 * T);
+            }));
     }
     ctx->stream = main_stream;
     if (group > 1) {
         GSS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join, ctx->aux_stream));
         GSS_HIP_CHECK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
     }
+    if (s.export_model) GSS_TRY(cacgmm_model_export(ctx, Mq, logdet, pi, F, K, D, *s.export_model));
     return GSS_OK;
 }

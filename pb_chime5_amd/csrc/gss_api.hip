@@ -675,6 +675,114 @@ extern "C" int gss_cacgmm_guided(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t
                       gamma);
 }
 
+// ------------------------------------------------------------------ the model as an object
+// The mask of a guidance that may be absent (fit(initialization=model), predict): NULL or no
+// mask = unmasked; the initialisation's fields are not read.
+static int check_mask_guidance(gss_ctx *ctx, const gss_guidance *g, int K, int64_t T, EmGuide *out) {
+    *out = EmGuide{};
+    if (!g || !g->mask_dev) return GSS_OK;
+    GSS_REQUIRE(ctx, g->mask_k_stride >= T, GSS_ERR_INVALID,
+                "guidance: mask_k_stride %lld is smaller than T = %lld",
+                (long long)g->mask_k_stride, (long long)T);
+    GSS_REQUIRE(ctx, g->mask_f_stride == 0 || g->mask_f_stride >= K * g->mask_k_stride,
+                GSS_ERR_INVALID, "guidance: mask_f_stride %lld is smaller than K * "
+                "mask_k_stride = %lld", (long long)g->mask_f_stride,
+                (long long)(K * g->mask_k_stride));
+    out->mask = g->mask_dev;
+    out->mask_f_stride = g->mask_f_stride;
+    out->mask_k_stride = g->mask_k_stride;
+    return GSS_OK;
+}
+
+static int check_model(gss_ctx *ctx, const gss_cacgmm_model *m, const char *name) {
+    GSS_REQUIRE(ctx, m, GSS_ERR_INVALID, "%s is NULL", name);
+    GSS_REQUIRE(ctx, m->precision_dev, GSS_ERR_INVALID, "%s: precision_dev is NULL", name);
+    GSS_REQUIRE(ctx, m->log_det_dev, GSS_ERR_INVALID, "%s: log_det_dev is NULL", name);
+    GSS_REQUIRE(ctx, m->weight_dev, GSS_ERR_INVALID, "%s: weight_dev is NULL", name);
+    return GSS_OK;
+}
+
+static EmModel em_model(const gss_cacgmm_model *m) {
+    return EmModel{reinterpret_cast<cplx *>(m->precision_dev), m->log_det_dev, m->weight_dev};
+}
+
+extern "C" int gss_cacgmm_fit(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                              const gss_guidance *g, int K, int iterations,
+                              const gss_cacgmm_model *init_model,
+                              const gss_cacgmm_model *model_out) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, Y && F >= 1 && T >= 1, GSS_ERR_INVALID, "gss_cacgmm_fit: bad arguments");
+    GSS_TRY(check_cacgmm_args(ctx, D, K, 1, 0));
+    GSS_REQUIRE(ctx, iterations >= 0 && (iterations >= 1 || init_model), GSS_ERR_INVALID,
+                "gss_cacgmm_fit: iterations=%d%s", iterations,
+                iterations == 0 ? " needs an init_model to copy" : "");
+    GSS_TRY(check_model(ctx, model_out, "model_out"));
+    EmGuide guide;
+    if (init_model) {
+        GSS_TRY(check_model(ctx, init_model, "init_model"));
+        GSS_TRY(check_mask_guidance(ctx, g, K, T, &guide));
+    } else {
+        GSS_TRY(check_guidance(ctx, g, K, T, &guide));
+    }
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    if (iterations == 0) {
+        // fit(initialization=model, iterations=0) is the model
+        const size_t fk = (size_t)F * K;
+        if (model_out->precision_dev != init_model->precision_dev)
+            GSS_HIP_CHECK(ctx, hipMemcpyAsync(model_out->precision_dev, init_model->precision_dev,
+                                              sizeof(cplx) * fk * D * D, hipMemcpyDeviceToDevice,
+                                              ctx->stream));
+        if (model_out->log_det_dev != init_model->log_det_dev)
+            GSS_HIP_CHECK(ctx, hipMemcpyAsync(model_out->log_det_dev, init_model->log_det_dev,
+                                              sizeof(double) * fk, hipMemcpyDeviceToDevice,
+                                              ctx->stream));
+        if (model_out->weight_dev != init_model->weight_dev)
+            GSS_HIP_CHECK(ctx, hipMemcpyAsync(model_out->weight_dev, init_model->weight_dev,
+                                              sizeof(double) * fk, hipMemcpyDeviceToDevice,
+                                              ctx->stream));
+        return GSS_OK;
+    }
+    GSS_TRY(arena_reserve(ctx, cacgmm_workspace_bytes(F, T, D, K)));
+    const EmModel in = init_model ? em_model(init_model) : EmModel{}, out = em_model(model_out);
+    EmSchedule s;
+    if (init_model) {
+        s.import_model = &in;
+        s.model_iterations = iterations;
+        s.model_masked = true;
+    } else {
+        s.iterations = iterations;
+    }
+    s.export_model = &out;
+    return cacgmm_schedule_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, guide, K, s);
+}
+
+extern "C" int gss_cacgmm_predict(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                                  const gss_cacgmm_model *model, int K, const gss_guidance *g,
+                                  double *gamma, double *loglik) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, Y && F >= 1 && T >= 1, GSS_ERR_INVALID, "gss_cacgmm_predict: bad arguments");
+    GSS_TRY(check_cacgmm_args(ctx, D, K, 1, 0));
+    GSS_TRY(check_model(ctx, model, "model"));
+    GSS_REQUIRE(ctx, gamma || loglik, GSS_ERR_INVALID,
+                "gss_cacgmm_predict: gamma_dev and loglik_dev are both NULL");
+    EmGuide guide;
+    GSS_TRY(check_mask_guidance(ctx, g, K, T, &guide));
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    // the workspace of THIS call's (F, T, D, K): a predict may see more frames than any fit did
+    GSS_TRY(arena_reserve(ctx, cacgmm_workspace_bytes(F, T, D, K)));
+    const EmModel in = em_model(model);
+    EmSchedule s;
+    s.import_model = &in;
+    s.predict_masked = true;
+    s.gamma = gamma;
+    s.loglik = loglik;
+    return cacgmm_schedule_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, guide, K, s);
+}
+
 extern "C" int gss_masks_from_posteriors(gss_ctx *ctx, const double *gamma, int F, int K,
                                          int64_t T, int target, int drop, int64_t sf,
                                          int64_t ef, double *mx, double *mn) {

@@ -281,6 +281,42 @@ static inline EmGuide em_guide_from_activity(const uint8_t *act, int64_t act_str
 int cacgmm_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGuide &guide, int K,
                int iterations, int iterations_post, double *gamma);
 
+// A fitted model in the public dense form (gss_cacgmm_model): precision (F,K,D,D), ln det and
+// weights (F,K).  The EM's own form is Mq (F,NE,K): the upper triangle of the precision with the
+// off-diagonals doubled.
+struct EmModel {
+    cplx *precision;
+    double *log_det, *weight;
+};
+// The steps of one EM run, in the order they are enqueued: import, `iterations` M-steps from the
+// guidance's initialisation (fit(initialization=array), masked where the guide has a mask),
+// `model_iterations` E-step + M-step pairs from the current model (fit(initialization=model)),
+// export, predict, log-likelihood.  cacgmm_run is {iterations, post - 1 unmasked, predict} with
+// the one-launch kernel allowed; the model calls (gss_cacgmm_fit / gss_cacgmm_predict) are
+// the other combinations, always on the multi-launch path.
+struct EmSchedule {
+    int iterations = 0;
+    int model_iterations = 0;
+    bool model_masked = false;       // the model iterations multiply the mask in (if there is one)
+    bool predict_masked = false;     // so do the predict step and the log-likelihood
+    double *gamma = nullptr;         // (F,K,T) posteriors of the predict step, NULL = no predict
+    double *loglik = nullptr;        // (F,T), NULL = none
+    const EmModel *import_model = nullptr, *export_model = nullptr;
+    bool onchip_allowed = false;
+};
+int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGuide &guide,
+                        int K, const EmSchedule &s);
+// cacgmm_model.hip: the conversions between the two forms (lossless: a factor 2) and the
+// log-likelihood of the frames under a model
+int cacgmm_model_import(gss_ctx *ctx, const EmModel &m, int F, int K, int D, cplx *Mq,
+                        double *logdet, double *pi);
+int cacgmm_model_export(gss_ctx *ctx, const cplx *Mq, const double *logdet, const double *pi, int F,
+                        int K, int D, const EmModel &m);
+int cacgmm_loglik_run(gss_ctx *ctx, const cplx *Yn, const cplx *Mq, const double *logdet,
+                      const double *pi, const uint8_t *act, int64_t act_stride,
+                      int64_t act_fstride, int masked, int F, int64_t T, int D, int K,
+                      double *loglik);
+
 // S > 1: S targets' weights (S, F, 2, T) -> partials (S, F, nch, 2, NE), one launch
 int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,
                      int nch, int chunk_frames, cplx *part, int S = 1);

@@ -25,8 +25,9 @@ import ctypes
 import numpy as np
 
 from . import _capi
-from ._capi import (Context, GssBfSegments, GssChannelSelect, GssDebugTaps, GssGuidance,
-                    GssParams, c_void_p, default_context)
+from ._capi import (Context, GssBfSegments, GssCacgmmModel, GssChannelSelect, GssDebugTaps,
+                    GssGuidance, GssParams, c_void_p, default_context)
+from .cacgmm import CACGMM
 
 _BF_CODES = {'mvdrSouden_ban': 0, 'ch2': 1, 'sum': 2, 'gev_ban': 3}
 _POSTFILTER_CODES = {None: 0, 'mask_mul': 1}
@@ -365,6 +366,122 @@ def cacgmm_posteriors_guided(Obs, initialization=None, source_activity_mask=None
     ctx._check(ctx.lib.gss_layout_permute_f64(ctx.handle, c_void_p(g_d.ptr), F, K * T, 1, 2,
                                               c_void_p(o_d.ptr)), 'gss_layout_permute_f64')
     return ctx.to_host(o_d, (K, T, F), np.float64)
+
+
+class DeviceModel:
+    """The three arrays of a `cacgmm.CACGMM` in HBM and their gss_cacgmm_model."""
+
+    def __init__(self, ctx, F, K, D, model=None):
+        self.shape = (F, K, D)
+        if model is not None:
+            self.precision_d = ctx.to_device(model.precision)
+            self.log_det_d = ctx.to_device(model.log_determinant)
+            self.weight_d = ctx.to_device(model.weight)
+        else:
+            self.precision_d = ctx.empty(16 * F * K * D * D)
+            self.log_det_d = ctx.empty(8 * F * K)
+            self.weight_d = ctx.empty(8 * F * K)
+        self.struct = GssCacgmmModel(precision_dev=self.precision_d.ptr,
+                                     log_det_dev=self.log_det_d.ptr,
+                                     weight_dev=self.weight_d.ptr)
+
+    def to_host(self, ctx):
+        F, K, D = self.shape
+        return CACGMM(ctx.to_host(self.precision_d, (F, K, D, D), np.complex128),
+                      ctx.to_host(self.log_det_d, (F, K), np.float64),
+                      ctx.to_host(self.weight_d, (F, K), np.float64))
+
+
+def _model_call_tables(model, Obs, source_activity_mask):
+    """Shape rules of a call that takes a model: ValueError before any device work.
+    Returns (mask (K,T) / (F,K,T) uint8 or None, K)."""
+    if not isinstance(model, CACGMM):
+        raise ValueError(f'model: a CACGMM, not {type(model).__name__}')
+    model.check_observation(Obs)
+    K = model.shape[1]
+    mask = None
+    if source_activity_mask is not None:
+        _, mask, mask_K = guidance_tables(None, source_activity_mask, *np.shape(Obs)[1:])
+        if mask_K != K:
+            raise ValueError(f'source_activity_mask: {mask_K} classes but the model has {K}')
+    return mask, K
+
+
+def _check_iterations(iterations):
+    if not _is_integer(iterations):
+        raise ValueError(f'iterations: {iterations!r} is not an integer')
+    return int(iterations)
+
+
+def cacgmm_fit(Obs, initialization=None, source_activity_mask=None, iterations=100, *,
+               model=None, ctx=None):
+    """``CACGMMTrainer.fit`` for every frequency -> `cacgmm.CACGMM`.  Obs (D,T,F) complex.
+    Without ``model``: ``iterations`` M-steps from the initialisation (K,T) / (K,T,F) (None:
+    derived from the mask as core.py:156-159), masked with ``source_activity_mask`` if given --
+    the fit of `cacgmm_posteriors_guided`.  With ``model`` (``fit(initialization=model)``):
+    ``iterations`` E-step + M-step pairs from it, masked if a mask is given; ``iterations=0``
+    returns the model's bits."""
+    Obs = np.asarray(Obs)
+    if Obs.ndim != 3:
+        raise ValueError(f'Obs: shape {Obs.shape} is not (D,T,F)')
+    iterations = _check_iterations(iterations)
+    if model is not None:
+        if initialization is not None:
+            raise ValueError('initialization: both an array and a model were given')
+        init, (mask, K) = None, _model_call_tables(model, Obs, source_activity_mask)
+    else:
+        init, mask, K = guidance_tables(initialization, source_activity_mask, *Obs.shape[1:])
+    ctx = ctx or default_context()
+    Y_d, (D, T, F) = _obs_to_device_ftd(ctx, Obs)
+    guide = DeviceGuidance(ctx, init, mask, T) if (init is not None or mask is not None) else None
+    start = DeviceModel(ctx, F, K, D, model) if model is not None else None
+    out = DeviceModel(ctx, F, K, D)
+    ctx._check(ctx.lib.gss_cacgmm_fit(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, ctypes.byref(guide.struct) if guide else None, K,
+        iterations, ctypes.byref(start.struct) if start else None, ctypes.byref(out.struct)),
+        'gss_cacgmm_fit')
+    return out.to_host(ctx)
+
+
+def _cacgmm_predict(model, Obs, source_activity_mask, want_gamma, want_loglik, ctx):
+    Obs = np.asarray(Obs)
+    mask, K = _model_call_tables(model, Obs, source_activity_mask)
+    ctx = ctx or default_context()
+    Y_d, (D, T, F) = _obs_to_device_ftd(ctx, Obs)
+    guide = DeviceGuidance(ctx, None, mask, T) if mask is not None else None
+    dev = DeviceModel(ctx, F, K, D, model)
+    g_d = ctx.empty(8 * F * K * T) if want_gamma else None
+    ll_d = ctx.empty(8 * F * T) if want_loglik else None
+    ctx._check(ctx.lib.gss_cacgmm_predict(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, ctypes.byref(dev.struct), K,
+        ctypes.byref(guide.struct) if guide else None, c_void_p(g_d.ptr if g_d else None),
+        c_void_p(ll_d.ptr if ll_d else None)), 'gss_cacgmm_predict')
+    posterior = loglik = None
+    if want_gamma:
+        o_d = ctx.empty(8 * F * K * T)
+        # (F, K*T) -> (K*T, F)
+        ctx._check(ctx.lib.gss_layout_permute_f64(ctx.handle, c_void_p(g_d.ptr), F, K * T, 1, 2,
+                                                  c_void_p(o_d.ptr)), 'gss_layout_permute_f64')
+        posterior = ctx.to_host(o_d, (K, T, F), np.float64)
+    if want_loglik:
+        loglik = np.ascontiguousarray(ctx.to_host(ll_d, (F, T), np.float64).T)
+    return posterior, loglik
+
+
+def cacgmm_predict(model, Obs, source_activity_mask=None, *, log_likelihood=False, ctx=None):
+    """``CACGMM.predict`` (affiliation_eps = 0) under a `cacgmm.CACGMM`: Obs (D,T,F) of any
+    frame count -> posterior (K,T,F); ``log_likelihood=True``: (posterior, log-likelihood
+    (T,F)) from the same call."""
+    posterior, loglik = _cacgmm_predict(model, Obs, source_activity_mask, True,
+                                        bool(log_likelihood), ctx)
+    return (posterior, loglik) if log_likelihood else posterior
+
+
+def cacgmm_log_likelihood(model, Obs, source_activity_mask=None, *, ctx=None):
+    """ln sum_k pi_k m_kt exp(-D ln q_kt - ln det B_k) per frame, (T,F): the log-likelihood of
+    the unit-normalised frames under the model up to the constant ln((D-1)! / (2 pi^D)); -inf
+    where the mask turns every class off.  No posteriors are computed."""
+    return _cacgmm_predict(model, Obs, source_activity_mask, False, True, ctx)[1]
 
 
 def _mask_to_device_ft(ctx, mask, T, F):
