@@ -83,7 +83,9 @@ typedef enum {
  * gss_select_channels, gss_last_selected_channels and gss_enhance_observation_select(_pcm16)
  * with the gss_channel_select descriptor: entry points only, gss_params and gss_debug_taps keep
  * their layouts, revision still 7.  So were gss_cacgmm_fit and gss_cacgmm_predict with the
- * gss_cacgmm_model descriptor. */
+ * gss_cacgmm_model descriptor.  So were gss_lcmv_souden, gss_lcmv_masks_from_posteriors,
+ * gss_enhance_observation_lcmv, gss_last_lcmv_interferer and gss_last_lcmv_fallbacks with the
+ * gss_bf_lcmv descriptor. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -391,6 +393,69 @@ int gss_mvdr_souden_segments(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t
  * statistics (synchronises the stream, like gss_last_wpe_zero_pivots); 0 before any. */
 int gss_last_segment_fallbacks(gss_ctx *ctx, int64_t *count_host);
 
+/* Interferer-nulling LCMV (Souden, Benesty, Affes 2010, "A study of the LCMV and MVDR noise
+ * reduction filters", eq. 51): beamform_lcmv_souden_from_masks (beamforming_wrapper.py:127-171)
+ * -> pb_bss get_lcmv_vector_souden.  Who the interferer is when the masks come from posteriors. */
+typedef struct {
+    int32_t interferer;      /* >= 0: that class; -1: choose among `candidates`   */
+    uint32_t candidates;     /* bit k: class k may be chosen; target bit ignored  */
+    double min_mass;         /* >= 0, finite                                      */
+} gss_bf_lcmv;
+
+/* gss_mvdr_souden with a null on one interferer.  Per frequency, with S_m = sum_t m_t y_t y_t^H
+ * and s_m = sum_t m_t for the target, interferer and noise masks m in {X, I, N}:
+ *    Phi_m = S_m / max(s_m, 1e-10);  A = solve(Phi_N, Phi_I), B = solve(Phi_N, Phi_X) (one LU
+ *    with partial pivoting for both, the minimum-norm lstsq answer on an exactly singular
+ *    Phi_N, as in gss_mvdr_souden);  g_in = tr A,  g = g_in tr B - tr(A B),
+ *    W = (g_in B - A B) / max(Re g, 1e-10);  distortion matrix Phi_D = Phi_I + Phi_N.
+ * On rank-one Phi_X, Phi_I column r of W is the LCMV filter that passes the target as channel r
+ * hears it and nulls the interferer.  A frequency with s_I < min_mass takes the MVDR of the
+ * merged mask instead -- Phi_D = (S_I + S_N) / max(s_I + s_N, 1e-10), W = Psi / max(Re tr Psi,
+ * 1e-10), Psi = solve(Phi_D, Phi_X): what gss_mvdr_souden computes for N + I -- and is counted
+ * (gss_last_lcmv_fallbacks); a frequency factors one matrix, never both.  With min_mass = 0
+ * nothing falls back and an empty interferer mask gives W = 0, NaN under `ban` (0 / 0), like
+ * the reference function.  ONE reference channel for the call: the argmax over r of
+ * sum_f w_r^H Phi_X w_r / max(sum_f w_r^H Phi_D w_r, 1e-10), or ref_channel >= 0 as named by
+ * the caller (-1: choose); the floor on g and this choice are this library's (upstream is
+ * believed to fix channel 0).  `ban` normalises against Phi_D.
+ * Y (F,T,D), masks (F,T) -> Xhat (T,F); ref_channel_dev (device int32, may be NULL) receives the
+ * status word of gss_last_ref_channel, which works after this call (-1: non-finite SNR, Xhat
+ * filled with NaN).
+ * GSS_ERR_INVALID (the message names the field): D < 2 (g is identically 0 on one channel),
+ * D >= 30, min_mass negative or not finite, ref_channel outside [-1, D). */
+int gss_lcmv_souden(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                    const double *target_mask_dev, const double *interferer_mask_dev,
+                    const double *noise_mask_dev, int ban, int ref_channel, double min_mass,
+                    gss_cplx *Xhat_dev, int32_t *ref_channel_dev);
+
+/* gss_masks_from_posteriors for the LCMV: gamma (F,K,T) -> target, interferer and noise masks
+ * (F,T).  The interferer is lcmv->interferer, or (-1) the class k with bit k of
+ * lcmv->candidates set (k != target_index) of largest mass sum_f sum_t gamma[f,k,t] over the
+ * frames the context zeroing keeps -- summed per frequency in a fixed order, then in ascending
+ * f; equal masses go to the lower index; -1 (no interferer) without a candidate or when the
+ * largest mass is 0.  X = gamma[target], I = gamma[interferer] (all zero for -1), N = the sum of
+ * the remaining classes in ascending k; all zeroed on the context frames as in
+ * gss_masks_from_posteriors.  interferer_dev (device int32, may be NULL) receives the class;
+ * gss_last_lcmv_interferer works afterwards.  lcmv->min_mass is checked, not used.  K <= 19.
+ * GSS_ERR_INVALID (the message names the field): lcmv NULL, interferer outside [-1, K) or equal
+ * to target_index, min_mass negative or not finite. */
+int gss_lcmv_masks_from_posteriors(gss_ctx *ctx, const double *gamma_dev, int F, int K,
+                                   int64_t T, int target_index, const gss_bf_lcmv *lcmv,
+                                   int drop_context, int64_t start_context_frames,
+                                   int64_t end_context_frames, double *target_mask_dev,
+                                   double *interferer_mask_dev, double *noise_mask_dev,
+                                   int32_t *interferer_dev);
+
+/* The interferer class of the last gss_lcmv_masks_from_posteriors /
+ * gss_enhance_observation_lcmv call on this context, -1 when it had none (synchronises the
+ * stream, like gss_last_segment_fallbacks); -1 before any. */
+int gss_last_lcmv_interferer(gss_ctx *ctx, int32_t *interferer_host);
+
+/* Number of frequencies of the last gss_lcmv_souden / gss_enhance_observation_lcmv call on this
+ * context that fell back to the MVDR of the merged mask (synchronises the stream); 0 before
+ * any. */
+int gss_last_lcmv_fallbacks(gss_ctx *ctx, int64_t *count_host);
+
 /* beamform_gev_from_masks (beamforming_wrapper.py:77-89,192-208): masked PSD
  * matrices, principal generalised eigenvector of (Phi_X, Phi_N) with
  * w^H Phi_N w = 1 (phase arbitrary, as upstream), optional BAN, apply.
@@ -531,6 +596,23 @@ int gss_enhance_observation_segments(gss_ctx *ctx, const gss_params *params,
                                      int64_t end_context_samples,
                                      const gss_bf_segments *seg,
                                      double *out_dev, const gss_debug_taps *taps);
+
+/* gss_enhance_observation with the interferer-nulling LCMV in the place of the MVDR: the
+ * posteriors go through gss_lcmv_masks_from_posteriors (context frames zeroed) and the three
+ * masks through gss_lcmv_souden with `ban` and lcmv->min_mass, the reference channel chosen.
+ * Everything else is gss_enhance_observation's; of the taps, distortion_mask receives I + N
+ * (what the postfilter and the reference's locals call the distortion).  gss_last_ref_channel,
+ * gss_last_lcmv_interferer and gss_last_lcmv_fallbacks work afterwards.  params->bf must be 0
+ * ('mvdrSouden_ban', i.e. ban = 1): GSS_ERR_UNSUPPORTED otherwise.  Errors of `lcmv` as
+ * gss_lcmv_masks_from_posteriors, of D as gss_lcmv_souden. */
+int gss_enhance_observation_lcmv(gss_ctx *ctx, const gss_params *params,
+                                 const double *obs_dev, int D, int64_t N,
+                                 const uint8_t *act_dev, int K, int64_t N_act,
+                                 int target_index,
+                                 int64_t start_context_samples,
+                                 int64_t end_context_samples,
+                                 const gss_bf_lcmv *lcmv,
+                                 double *out_dev, const gss_debug_taps *taps);
 
 /* gss_enhance_observation on the sel->keep channels the envelope-variance measure ranks best:
  * the STFT runs on all D channels, then scores, pick and gather, then the unchanged pipeline

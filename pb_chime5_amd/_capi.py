@@ -57,6 +57,12 @@ class GssBfSegments(ctypes.Structure):
                 ('min_mass', ctypes.c_double)]
 
 
+class GssBfLcmv(ctypes.Structure):
+    """gss_bf_lcmv: the interferer of the LCMV beamformer and its fallback threshold."""
+    _fields_ = [('interferer', ctypes.c_int32), ('candidates', ctypes.c_uint32),
+                ('min_mass', ctypes.c_double)]
+
+
 class GssChannelSelect(ctypes.Structure):
     """gss_channel_select: the band table and the settings of the envelope-variance channel
     selection."""
@@ -124,6 +130,13 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_int, c_int,
                                          ctypes.POINTER(GssBfSegments), c_void_p, c_void_p]),
     'gss_last_segment_fallbacks': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'gss_lcmv_souden': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
+                                c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
+    'gss_lcmv_masks_from_posteriors': (
+        c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, ctypes.POINTER(GssBfLcmv),
+                c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'gss_last_lcmv_interferer': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    'gss_last_lcmv_fallbacks': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,
@@ -146,6 +159,10 @@ SIGNATURES = {
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
                 ctypes.POINTER(GssBfSegments), c_void_p, ctypes.POINTER(GssDebugTaps)]),
+    'gss_enhance_observation_lcmv': (
+        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
+                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
+                ctypes.POINTER(GssBfLcmv), c_void_p, ctypes.POINTER(GssDebugTaps)]),
     'gss_enhance_observation_pcm16': (
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p,
@@ -442,6 +459,22 @@ class Context:
         out = ctypes.c_int64()
         self._check(self.lib.gss_last_segment_fallbacks(self.handle, ctypes.byref(out)),
                     'gss_last_segment_fallbacks')
+        return int(out.value)
+
+    def last_lcmv_interferer(self):
+        """The interferer class of the last LCMV mask / fused call on this context, -1 when it
+        had none (synchronises)."""
+        out = ctypes.c_int32()
+        self._check(self.lib.gss_last_lcmv_interferer(self.handle, ctypes.byref(out)),
+                    'gss_last_lcmv_interferer')
+        return int(out.value)
+
+    def last_lcmv_fallbacks(self):
+        """Frequencies of the last LCMV beamformer on this context that fell back to the MVDR of
+        the merged mask (synchronises)."""
+        out = ctypes.c_int64()
+        self._check(self.lib.gss_last_lcmv_fallbacks(self.handle, ctypes.byref(out)),
+                    'gss_last_lcmv_fallbacks')
         return int(out.value)
 
     def workspace_bytes(self):

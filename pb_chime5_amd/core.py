@@ -242,8 +242,31 @@ class Beamformer:
     segment_frames: int = None
     segment_context: int = 0
     segment_min_mass: float = None
+    # Interferer-nulling LCMV (beamform_lcmv_souden_from_masks, beamforming_wrapper.py:127-171;
+    # not reachable from the reference's Beamformer): distortionless for the target with a null
+    # on the competing talker named by ``interferer_mask``; frequencies where that mask sums to
+    # less than ``null_min_mass`` (None: 2 * channels; > 0) take the MVDR.  Only
+    # 'mvdrSouden_ban' has it, and not together with segments.
+    null_interferer: bool = False
+    null_min_mass: float = None
 
     def __post_init__(self):
+        if self.null_interferer:
+            if self.type != 'mvdrSouden_ban':
+                raise NotImplementedError(
+                    f"bf={self.type!r} with null_interferer: only 'mvdrSouden_ban' has an "
+                    'interferer-nulling form')
+            if self.segment_frames is not None:
+                raise NotImplementedError(
+                    'null_interferer with segment_frames: the interferer-nulling beamformer has '
+                    'one filter per utterance')
+            m = self.null_min_mass
+            if m is not None and (isinstance(m, bool)
+                                  or not isinstance(m, (int, float, np.integer, np.floating))
+                                  or not np.isfinite(m) or m <= 0):
+                raise ValueError(f'null_min_mass={m!r}: a finite number > 0')
+        elif self.null_min_mass is not None:
+            raise ValueError('null_min_mass without null_interferer')
         if self.segment_frames is None:
             return
         if self.type != 'mvdrSouden_ban':
@@ -260,9 +283,24 @@ class Beamformer:
         return dict(segment_frames=self.segment_frames, segment_context=self.segment_context,
                     min_mass=self.segment_min_mass)
 
-    def __call__(self, Obs, target_mask, distortion_mask, debug=False):
+    def __call__(self, Obs, target_mask, distortion_mask, debug=False, *, interferer_mask=None,
+                 noise_mask=None):
+        """``interferer_mask`` (with ``null_interferer``): the competing talker's mask, a part
+        of ``distortion_mask``; ``noise_mask``: the rest of it (None: their difference)."""
         bf = self.type
-        if bf == 'mvdrSouden_ban':
+        if self.null_interferer:
+            if interferer_mask is None:
+                raise ValueError('null_interferer: the beamformer needs interferer_mask')
+            if noise_mask is None:
+                noise_mask = distortion_mask - interferer_mask
+            min_mass = self.null_min_mass
+            if min_mass is None:
+                min_mass = 2 * np.shape(Obs)[0]
+            X_hat = ops.lcmv_souden_from_masks(
+                Obs, target_mask, interferer_mask, noise_mask, ban=True, min_mass=min_mass)
+        elif interferer_mask is not None or noise_mask is not None:
+            raise ValueError('interferer_mask / noise_mask without null_interferer')
+        elif bf == 'mvdrSouden_ban':
             from pb_chime5_amd.speech_enhancement.beamforming_wrapper import (
                 beamform_mvdr_souden_from_masks)
             X_hat = beamform_mvdr_souden_from_masks(
@@ -353,6 +391,10 @@ class Enhancer:
             raise NotImplementedError(
                 'channel_keep with bf_segment_frames: the segment-wise beamformer has no '
                 'selection')
+        if self._bf_null():
+            raise NotImplementedError(
+                'channel_keep with bf_null_interferer: the interferer-nulling beamformer has no '
+                'selection')
 
     def _channel_select(self):
         """The `ops.ChannelSelect` of this enhancer (one object: its band table is copied to a
@@ -427,6 +469,7 @@ class Enhancer:
         """core.py:333-394; examples are sharded over the visible GPUs by
         pb_chime5_amd.parallel when more than one process is running."""
         from pb_chime5_amd import parallel
+        self._no_null('enhance_session')
         audio_dir = Path(audio_dir)
         it = self.get_iterator(session_ids)
 
@@ -788,6 +831,24 @@ class Enhancer:
                 f'{what} with bf_segment_frames: the segment-wise beamformer is built for '
                 'enhance_observation only')
 
+    def _bf_null(self):
+        """Whether the beamformer nulls an interferer (``Beamformer.null_interferer``)."""
+        return bool(getattr(getattr(self, 'bf_block', None), 'null_interferer', False))
+
+    def _no_null(self, what):
+        if self._bf_null():
+            raise NotImplementedError(
+                f'{what} with bf_null_interferer: the interferer-nulling beamformer is built '
+                'for enhance_observation only')
+
+    def interferer_candidates(self, ex_array_activity, speaker_id):
+        """The classes the interferer of ``speaker_id`` is chosen from, as indices into the
+        activity keys: every key but the target and the garbage tracks that
+        ``Activity.garbage_class`` adds."""
+        garbage = _garbage_tracks(getattr(self.activity, 'garbage_class', True))
+        return [i for i, k in enumerate(ex_array_activity.keys())
+                if k != speaker_id and k not in garbage]
+
     def _params(self):
         w = self.wpe_block
         return ops.make_params(
@@ -827,7 +888,13 @@ class Enhancer:
         segments = self._bf_segments()
         select = self._channel_select()
         try:
-            if select is not None:
+            if self._bf_null():
+                res = ops.enhance_observation_lcmv(
+                    obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
+                    debug=debug, ctx=ctx, wpe_arrays=wpe_arrays,
+                    candidates=self.interferer_candidates(ex_array_activity, speaker_id),
+                    min_mass=self.bf_block.null_min_mass)
+            elif select is not None:
                 res = ops.enhance_observation_select(
                     obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
                     debug=debug, ctx=ctx, keep=select.keep, bank=select.bank,
@@ -851,6 +918,9 @@ class Enhancer:
         acitivity_freq = details['acitivity_freq']
         target_mask = details['target_mask']
         distortion_mask = details['distortion_mask']
+        if self._bf_null():
+            interferer_mask = details['interferer_mask']
+            interferer_index = details['interferer']
         X_hat = details['X_hat']
         masks = details['posterior'].copy()
         if self.bf_drop_context:
@@ -872,6 +942,7 @@ class Enhancer:
         ``initialization``: optional dict of the same shape with initial affiliations used as
         given (a neural mask estimator's output).  ``fused=False`` runs the blocks."""
         self._no_segments('enhance_observation_guided')
+        self._no_null('enhance_observation_guided')
         self._no_channel_keep('enhance_observation_guided')
         if wpe_arrays is None:
             wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
@@ -969,6 +1040,7 @@ class Enhancer:
         speakers together (gss_enhance_observation_targets), the block path calls
         ``bf_block`` and the iSTFT once per speaker."""
         self._no_segments('enhance_observation_speakers')
+        self._no_null('enhance_observation_speakers')
         self._no_channel_keep('enhance_observation_speakers')
         speaker_ids = self.speaker_ids_of(ex_array_activity, speaker_ids)
         if wpe_arrays is None:
@@ -1004,6 +1076,7 @@ class Enhancer:
         """`enhance_example` for several speakers of the example's window at once: dict
         speaker_id -> x_hat, each trimmed like `enhance_example` trims its output."""
         self._no_segments('enhance_example_speakers')
+        self._no_null('enhance_example_speakers')
         self._no_channel_keep('enhance_example_speakers')
         obs, ex_array_activity, _ = self._prepare_example(ex)
         out = self.enhance_observation_speakers(obs, ex_array_activity, speaker_ids, ex=ex)
@@ -1076,8 +1149,20 @@ class Enhancer:
         target_speaker_index = tuple(ex_array_activity.keys()).index(speaker_id)
         target_mask = masks[target_speaker_index]
         distortion_mask = np.sum(np.delete(masks, target_speaker_index, axis=0), axis=0)
-        X_hat = self.bf_block(Obs, target_mask=target_mask,
-                              distortion_mask=distortion_mask, debug=debug)
+        if self._bf_null():
+            # (`masks` has its context frames zeroed already; the device call zeroes them again
+            # by the same rule and leaves them out of the masses, as the fused call does)
+            sf, ef = context_frames if context_frames is not None else (0, 0)
+            _, interferer_mask, noise_mask, interferer_index = ops.lcmv_masks_from_posteriors(
+                masks, target_speaker_index, drop_context=context_frames is not None,
+                start_context_frames=sf, end_context_frames=ef, ctx=self._ctx(),
+                candidates=self.interferer_candidates(ex_array_activity, speaker_id))
+            X_hat = self.bf_block(Obs, target_mask=target_mask, distortion_mask=distortion_mask,
+                                  debug=debug, interferer_mask=interferer_mask,
+                                  noise_mask=noise_mask)
+        else:
+            X_hat = self.bf_block(Obs, target_mask=target_mask,
+                                  distortion_mask=distortion_mask, debug=debug)
         x_hat = self.istft(X_hat)
         if debug:
             self.enhance_observation_locals = locals()
@@ -1122,10 +1207,18 @@ def get_enhancer(
     bf_segment_min_mass=None,
     channel_keep=None,
     channel_bands=40,
+    bf_null_interferer=False,
+    bf_null_min_mass=None,
 ):
     """core.py:574-637 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*`` and ``channel_*``
-    are additions).
+    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*`` and
+    ``bf_null_*`` are additions).
+    ``bf_null_interferer=True``: 'mvdrSouden_ban' becomes the interferer-nulling LCMV (see
+    `Beamformer`): the competing speaker with the most posterior mass in the window -- the
+    garbage class is no candidate -- gets a null; where that speaker is next to silent at a
+    frequency (mask sum below ``bf_null_min_mass``, None: 2 * channels) the frequency keeps the
+    MVDR.  For `Enhancer.enhance_observation` / `enhance_example`; not with
+    ``bf_segment_frames`` or ``channel_keep`` (NotImplementedError).
     ``channel_keep=n`` (a count) or a share in (0, 1]: keep the channels of each utterance that
     the envelope-variance measure ranks best, chosen after the STFT from a mel bank of
     ``channel_bands`` filters (see `ops.select_channels`); WPE, GSS and the beamformer run on
@@ -1153,7 +1246,9 @@ def get_enhancer(
         bf_drop_context=bf_drop_context,
         bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
                             segment_context=bf_segment_context,
-                            segment_min_mass=bf_segment_min_mass),
+                            segment_min_mass=bf_segment_min_mass,
+                            null_interferer=bool(bf_null_interferer),
+                            null_min_mass=bf_null_min_mass),
         stft_size=stft_size,
         stft_shift=stft_shift,
         stft_fading=stft_fading,

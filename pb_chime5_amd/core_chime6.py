@@ -146,9 +146,11 @@ def get_enhancer(
     bf_segment_min_mass=None,
     channel_keep=None,
     channel_bands=40,
+    bf_null_interferer=False,
+    bf_null_min_mass=None,
 ):
     """core_chime6.py:572-635 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*`` and ``channel_*`` are additions,
+    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*`` and ``bf_null_*`` are additions,
     see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
@@ -166,7 +168,9 @@ def get_enhancer(
         bf_drop_context=bf_drop_context,
         bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
                             segment_context=bf_segment_context,
-                            segment_min_mass=bf_segment_min_mass),
+                            segment_min_mass=bf_segment_min_mass,
+                            null_interferer=bool(bf_null_interferer),
+                            null_min_mass=bf_null_min_mass),
         stft_size=stft_size,
         stft_shift=stft_shift,
         stft_fading=stft_fading,

@@ -156,9 +156,11 @@ def get_enhancer(
     bf_segment_min_mass=None,
     channel_keep=None,
     channel_bands=40,
+    bf_null_interferer=False,
+    bf_null_min_mass=None,
 ):
     """core_chime6_rttm.py:360-422 (same keyword arguments and defaults; ``device_id``,
-    ``wpe_per_array``, ``bf_segment_*`` and ``channel_*`` are additions, see core.get_enhancer)."""
+    ``wpe_per_array``, ``bf_segment_*``, ``channel_*`` and ``bf_null_*`` are additions, see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     db = get_database(chime6_dir, database_rttm, multiarray)
     return Enhancer(
@@ -174,7 +176,9 @@ def get_enhancer(
         bf_drop_context=bf_drop_context,
         bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
                             segment_context=bf_segment_context,
-                            segment_min_mass=bf_segment_min_mass),
+                            segment_min_mass=bf_segment_min_mass,
+                            null_interferer=bool(bf_null_interferer),
+                            null_min_mass=bf_null_min_mass),
         stft_size=stft_size,
         stft_shift=stft_shift,
         stft_fading=stft_fading,

@@ -2195,6 +2195,21 @@ int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const
     return GSS_OK;
 }
 
+// Three weight rows [target, interferer, noise] (the LCMV): the three-row instantiations of the
+// same kernel, chosen by the channel count as above.  W = (F, 3, T); part = (F, nch, 3, NE).
+int psd3_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W3,
+                      int nch, int chunk_frames, cplx *part) {
+    const size_t lds = wcov_lds_layout(D, 3).total;
+    const wcov_fn_t fn = D <= 4 ? wcov_kernel<3, false, false, false, 1>
+                         : D <= 12 ? wcov_kernel<3, false, false, false, 3>
+                         : D <= 24 ? wcov_kernel<3, false, false, false, 6> : wcov_kernel<3, false, false>;
+    GSS_TRY(raise_lds_limit(ctx, fn, lds));
+    hipLaunchKernelGGL(fn, dim3(xcd_grid(nch, F)), dim3(256), lds, ctx->stream, Y, W3, F, T, D,
+                       tri_count(D), nch, chunk_frames, part, 3, 0, MsegPlan{});
+    GSS_LAUNCH_CHECK(ctx, "wcov_kernel");
+    return GSS_OK;
+}
+
 size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K) {
     const size_t NE = tri_count(D);
     const EmBlockPlan bp = em_block_plan(F, T, D, K);

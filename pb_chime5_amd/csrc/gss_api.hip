@@ -183,6 +183,8 @@ extern "C" int gss_create(int device_id, gss_ctx **out) {
     ctx->status_host[0] = INT32_MIN;
     ctx->status_host[2] = 0;
     ctx->status_host[GSS_STATUS_SEGMENT_FALLBACKS] = 0;
+    ctx->status_host[GSS_STATUS_LCMV_INTERFERER] = -1;
+    ctx->status_host[GSS_STATUS_LCMV_FALLBACKS] = 0;
     *out = ctx;
     return GSS_OK;
 }
@@ -895,6 +897,78 @@ extern "C" int gss_last_segment_fallbacks(gss_ctx *ctx, int64_t *count) {
     return GSS_OK;
 }
 
+// The descriptor's rules (include/gss_hip.h); K bounds the class indices.
+static int check_lcmv(gss_ctx *ctx, const gss_bf_lcmv *lcmv, int K, int target, const char *what) {
+    GSS_REQUIRE(ctx, lcmv, GSS_ERR_INVALID, "%s: lcmv is NULL", what);
+    GSS_REQUIRE(ctx, std::isfinite(lcmv->min_mass) && lcmv->min_mass >= 0.0, GSS_ERR_INVALID,
+                "%s: min_mass = %g is negative or not finite", what, lcmv->min_mass);
+    GSS_REQUIRE(ctx, lcmv->interferer >= -1 && lcmv->interferer < K, GSS_ERR_INVALID,
+                "%s: interferer = %d outside [-1, %d)", what, (int)lcmv->interferer, K);
+    GSS_REQUIRE(ctx, lcmv->interferer != target, GSS_ERR_INVALID,
+                "%s: interferer = %d is the target", what, (int)lcmv->interferer);
+    return GSS_OK;
+}
+
+// (D < 2: g = tr A tr B - tr(A B) is identically 0 on one channel)
+static int check_lcmv_channels(gss_ctx *ctx, int D, const char *what) {
+    GSS_REQUIRE(ctx, D >= 2, GSS_ERR_INVALID, "%s: D = %d, the LCMV needs at least 2 channels",
+                what, D);
+    GSS_REQUIRE(ctx, D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    return GSS_OK;
+}
+
+extern "C" int gss_lcmv_souden(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                               const double *mx, const double *mi, const double *mn, int ban,
+                               int ref_channel, double min_mass, gss_cplx *Xhat, int32_t *ref) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, Y && mx && mi && mn && Xhat && F >= 1 && T >= 1, GSS_ERR_INVALID,
+                "gss_lcmv_souden: bad arguments");
+    GSS_TRY(check_lcmv_channels(ctx, D, "gss_lcmv_souden"));
+    GSS_REQUIRE(ctx, std::isfinite(min_mass) && min_mass >= 0.0, GSS_ERR_INVALID,
+                "gss_lcmv_souden: min_mass = %g is negative or not finite", min_mass);
+    GSS_REQUIRE(ctx, ref_channel >= -1 && ref_channel < D, GSS_ERR_INVALID,
+                "ref_channel %d outside [-1, %d)", ref_channel, D);
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(arena_reserve(ctx, lcmv_workspace_bytes(F, T, D)));
+    return lcmv_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mx, mi, mn, ban, ref_channel,
+                    min_mass, reinterpret_cast<cplx *>(Xhat), ref);
+}
+
+extern "C" int gss_lcmv_masks_from_posteriors(gss_ctx *ctx, const double *gamma, int F, int K,
+                                              int64_t T, int target, const gss_bf_lcmv *lcmv,
+                                              int drop, int64_t sf, int64_t ef, double *mx,
+                                              double *mi, double *mn, int32_t *interferer) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, gamma && mx && mi && mn && F >= 1 && T >= 1, GSS_ERR_INVALID,
+                "gss_lcmv_masks_from_posteriors: bad arguments");
+    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_MAX_CLASSES, GSS_ERR_INVALID,
+                "cacgmm: assert 1 <= K < 20 failed: K=%d", K);
+    GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
+                "target_index %d outside [0, %d)", target, K);
+    GSS_TRY(check_lcmv(ctx, lcmv, K, target, "gss_lcmv_masks_from_posteriors"));
+    GSS_TRY(arena_reserve(ctx, lcmv_masks_workspace_bytes(F, K)));
+    return lcmv_masks_run(ctx, gamma, F, K, T, target, *lcmv, drop, sf, ef, mx, mi, mn,
+                          interferer);
+}
+
+extern "C" int gss_last_lcmv_interferer(gss_ctx *ctx, int32_t *interferer) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, interferer, GSS_ERR_INVALID, "gss_last_lcmv_interferer: NULL");
+    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *interferer = __atomic_load_n(ctx->status_host + GSS_STATUS_LCMV_INTERFERER, __ATOMIC_ACQUIRE);
+    return GSS_OK;
+}
+
+extern "C" int gss_last_lcmv_fallbacks(gss_ctx *ctx, int64_t *count) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, count, GSS_ERR_INVALID, "gss_last_lcmv_fallbacks: NULL");
+    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *count = __atomic_load_n(ctx->status_host + GSS_STATUS_LCMV_FALLBACKS, __ATOMIC_ACQUIRE);
+    return GSS_OK;
+}
+
 extern "C" int gss_gev(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D, const double *mx,
                        const double *mn, int ban, gss_cplx *Xhat) {
     GSS_ENTER(ctx);
@@ -1059,20 +1133,24 @@ static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, in
     return stage;
 }
 
-// (segment_frames > 0: the segment-wise beamformer in the place of the whole-window one;
+// (segment_frames > 0: the segment-wise beamformer in the place of the whole-window one; lcmv:
+// the interferer-nulling one, with four mask buffers;
 // select_bands > 0: D is the number of channels kept out of select_D, and the selection stage
 // needs its own workspace and, when it gathers, the STFT of all select_D channels)
 static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
                                  int K, int64_t segment_frames = 0, int select_bands = 0,
-                                 int select_D = 0) {
+                                 int select_D = 0, bool lcmv = false) {
     size_t b = front_buffer_bytes(F, T, T_act, D, K);
-    b += 2 * align_up(sizeof(double) * (size_t)F * T);       // masks
+    b += (lcmv ? 4 : 2) * align_up(sizeof(double) * (size_t)F * T);   // masks (LCMV: X, I, N, I + N)
     b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
     b += 4096;
     size_t stage = front_stage_bytes(p, F, T, D, K);
     stage = std::max(stage, segment_frames > 0
                                 ? mvdr_segments_workspace_bytes(F, T, D, segment_frames)
                                 : mvdr_workspace_bytes(F, T, D));
+    if (lcmv)
+        stage = std::max(stage, std::max(lcmv_workspace_bytes(F, T, D),
+                                         lcmv_masks_workspace_bytes(F, K)));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
     if (select_bands > 0)
         stage = std::max(stage, chsel_workspace_bytes(F, T, select_D, select_bands) +
@@ -1227,7 +1305,8 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
                                     const gss_guidance *guidance = nullptr,
                                     const gss_bf_segments *seg = nullptr,
                                     const gss_channel_select *sel = nullptr,
-                                    bool select = false) {
+                                    bool select = false,
+                                    const gss_bf_lcmv *lcmv = nullptr) {
     GSS_REQUIRE(ctx, !guided || guidance, GSS_ERR_INVALID,
                 "gss_enhance_observation_guided: guidance is NULL");
     GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, guided ? (const void *)guidance : act, out,
@@ -1268,14 +1347,19 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
 
     GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K,
                                                   seg ? seg->segment_frames : 0,
-                                                  select ? sel->bands : 0, D_all)));
+                                                  select ? sel->bands : 0, D_all,
+                                                  lcmv != nullptr)));
     PipelineFront fr;
     GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
     double *mx = arena_alloc_t<double>(ctx, (size_t)F * T);
     double *mn = arena_alloc_t<double>(ctx, (size_t)F * T);
+    // (LCMV: mi, mnn = the interferer and noise masks, mn = their sum, the distortion mask)
+    double *mi = lcmv ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
+    double *mnn = lcmv ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
     cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)F * T);
     int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);
-    GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
+    GSS_REQUIRE(ctx, mx && mn && Xhat && ref && (!lcmv || (mi && mnn)), GSS_ERR_NOMEM,
+                "workspace sizing bug");
     const size_t mark = ctx->arena_off;
     GSS_TRY(run_front(ctx, p, obs, obs_type, D, N, act, K, N_act, F, T, T_act, fr, mark,
                       guided ? &guide : nullptr, select ? sel : nullptr, D_all));
@@ -1286,9 +1370,19 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
         sf = gss_samples_to_stft_frames(start_ctx, size, shift, fading);
         ef = gss_samples_to_stft_frames(end_ctx, size, shift, fading);
     }
-    GSS_TRY(masks_from_posteriors_run(ctx, fr.gamma, F, K, T, target, p->bf_drop_context, sf, ef,
-                                      mx, mn));
-    if (seg) {      // (bf == 0, checked by the entry point)
+    // (the LCMV takes its three masks below; mx, mn are the taps' masks there: the target and
+    // I + N, the sum over the other classes)
+    if (!lcmv || (taps && taps->distortion_mask))
+        GSS_TRY(masks_from_posteriors_run(ctx, fr.gamma, F, K, T, target, p->bf_drop_context, sf,
+                                          ef, mx, mn));
+    if (lcmv) {     // (bf == 0, checked by the entry point)
+        GSS_TRY(lcmv_masks_run(ctx, fr.gamma, F, K, T, target, *lcmv, p->bf_drop_context, sf, ef,
+                               mx, mi, mnn, nullptr));
+        ctx->arena_off = mark;
+        GSS_TRY(lcmv_run(ctx, X, F, T, D, mx, mi, mnn, /*ban=*/1, /*forced_ref=*/-1,
+                         lcmv->min_mass, Xhat, ref));
+        ctx->arena_off = mark;
+    } else if (seg) {      // (bf == 0, checked by the entry point)
         GSS_TRY(mvdr_segments_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, *seg, Xhat, ref));
         ctx->arena_off = mark;
     } else if (p->bf == 0 || p->bf == 3) {
@@ -1431,6 +1525,26 @@ extern "C" int gss_enhance_observation_segments(gss_ctx *ctx, const gss_params *
                 p->bf);
     return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
                                     out, taps, /*guided=*/false, nullptr, seg);
+}
+
+extern "C" int gss_enhance_observation_lcmv(gss_ctx *ctx, const gss_params *p, const double *obs,
+                                            int D, int64_t N, const uint8_t *act, int K,
+                                            int64_t N_act, int target, int64_t start_ctx,
+                                            int64_t end_ctx, const gss_bf_lcmv *lcmv,
+                                            double *out, const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, !p || p->bf == 0, GSS_ERR_UNSUPPORTED,
+                "gss_enhance_observation_lcmv: bf=%d, only 0 ('mvdrSouden_ban') has an "
+                "interferer-nulling form", p->bf);
+    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_MAX_CLASSES, GSS_ERR_INVALID,
+                "cacgmm: assert 1 <= K < 20 failed: K=%d", K);
+    GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
+                "target_index %d outside [0, %d)", target, K);
+    GSS_TRY(check_lcmv(ctx, lcmv, K, target, "gss_enhance_observation_lcmv"));
+    GSS_TRY(check_lcmv_channels(ctx, D, "gss_enhance_observation_lcmv"));
+    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, /*guided=*/false, nullptr, nullptr, nullptr, false,
+                                    lcmv);
 }
 
 extern "C" int gss_enhance_observation_pcm16(gss_ctx *ctx, const gss_params *p,

@@ -165,6 +165,9 @@ struct gss_ctx {
     // [2]: pivots zeroed by the last WPE call (copied from the device counter by wpe_run).
     // [3]: (segment, frequency) pairs of the last segment-wise MVDR that fell back to the
     // whole-window statistics (copied from the device counter by mvdr_apply_kernel).
+    // [4]: the interferer class of the last LCMV mask call (masks3_kernel), -1 = none.
+    // [5]: frequencies of the last LCMV beamformer that fell back to the MVDR of the merged mask
+    // (copied from the device counter by lcmv_run).
     // [GSS_STATUS_TARGETS + s]: target s of the last targets call (mvdr_apply_targets_kernel,
     // which writes target 0's word to [0] as well).
     int32_t *status_host = nullptr;
@@ -187,6 +190,8 @@ struct gss_ctx {
 };
 
 #define GSS_STATUS_SEGMENT_FALLBACKS 3                           // see gss_ctx::status_host
+#define GSS_STATUS_LCMV_INTERFERER 4
+#define GSS_STATUS_LCMV_FALLBACKS 5
 #define GSS_STATUS_TARGETS 16                                    // first per-target word
 #define GSS_STATUS_CHANNELS 40                                   // first selected-channel word
 #define GSS_STATUS_BYTES (4 * (GSS_STATUS_CHANNELS + GSS_MAX_CHANNELS))
@@ -321,6 +326,11 @@ int cacgmm_loglik_run(gss_ctx *ctx, const cplx *Yn, const cplx *Mq, const double
 int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,
                      int nch, int chunk_frames, cplx *part, int S = 1);
 
+// The same pass with three weight rows (the LCMV's target, interferer and noise masks):
+// W3 (F, 3, T) -> part (F, nch, 3, NE), the three-row instantiation of the kernel
+int psd3_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W3,
+                      int nch, int chunk_frames, cplx *part);
+
 size_t mvdr_workspace_bytes(int F, int64_t T, int D, int S = 1);
 // targets: the multi-target tail of gss_enhance_observation_targets -- masks (S,F,T) in,
 // Xhat (S,T,F) and ref_channel (S) out, the per-target status words of the context written
@@ -336,6 +346,20 @@ size_t mvdr_segments_workspace_bytes(int F, int64_t T, int D, int64_t segment_fr
 int mvdr_segments_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
                       const double *mn, int ban, const gss_bf_segments &seg, cplx *Xhat,
                       int32_t *ref_channel, int forced_ref = -1);
+// Interferer-nulling LCMV (Souden), include/gss_hip.h: gss_lcmv_souden.  Three masks (F,T) ->
+// three-row PSD pass, lcmv_solve_kernel (per frequency the LCMV, or the MVDR of the merged mask
+// where the interferer mask sums to less than min_mass), then the MVDR's reference-channel and
+// apply kernels.  The fallback count goes to the context's status word.
+size_t lcmv_workspace_bytes(int F, int64_t T, int D);
+int lcmv_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
+             const double *mi, const double *mn, int ban, int forced_ref, double min_mass,
+             cplx *Xhat, int32_t *ref_channel);
+// gamma (F,K,T) -> target, interferer and noise masks; the interferer is bf.interferer or the
+// candidate of largest mass (device int32 `interferer`, may be NULL, and the status word)
+size_t lcmv_masks_workspace_bytes(int F, int K);
+int lcmv_masks_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T, int target,
+                   const gss_bf_lcmv &bf, int drop, int64_t start_frames, int64_t end_frames,
+                   double *mx, double *mi, double *mn, int32_t *interferer);
 // The targets of masks_targets_kernel (by value): target class and zeroed context frames
 struct TargetMaskArgs {
     int S;

@@ -819,6 +819,413 @@ __global__ __launch_bounds__(MVDR_REF_NT) void mvdr_snr_segments_kernel(
     }
 }
 
+// ------------------------------------------------------------------ interferer-nulling LCMV
+// Per-frequency mass of every class over the frames the context zeroing keeps: gamma (F,K,T)
+// -> fmass (F,K).  grid (F, K), block 256; mask_pack_kernel's summation order.
+__global__ __launch_bounds__(256) void lcmv_mass_kernel(const double *__restrict__ gamma, int K,
+                                                        int64_t T, int64_t zero_lo_end,
+                                                        int64_t zero_hi_begin,
+                                                        double *__restrict__ fmass) {
+    __shared__ double red[4];
+    const int f = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
+    const double *g = gamma + ((int64_t)f * K + k) * T;
+    double s = 0.0;
+    for (int64_t t = zero_lo_end + tid; t < zero_hi_begin; t += blockDim.x) s += g[t];
+    s = wave_sum(s);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) fmass[(int64_t)f * K + k] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// The interferer of a call: forced >= 0 names it; otherwise the candidate class (bit k of
+// `candidates`, the target's bit ignored) of largest mass, the masses of lcmv_mass_kernel added
+// in ascending frequency, equal masses to the lower index; -1 without a candidate or when the
+// largest mass is 0.  One wave; pick[0] receives the class.
+__global__ __launch_bounds__(64) void lcmv_pick_kernel(const double *__restrict__ fmass, int F,
+                                                       int K, int target, uint32_t candidates,
+                                                       int forced, int32_t *__restrict__ pick) {
+    const int lane = threadIdx.x;
+    if (forced >= 0) {
+        if (lane == 0) pick[0] = forced;
+        return;
+    }
+    const bool cand = lane < K && lane != target && (candidates >> lane & 1u);
+    double best = -1.0;
+    int bi = 1 << 30;
+    if (cand) {
+        double s = 0.0;
+        for (int f = 0; f < F; ++f) s += fmass[(int64_t)f * K + lane];
+        // (a NaN mass never wins: the class is no candidate)
+        if (s == s) {
+            best = s;
+            bi = lane;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) {
+            best = ob;
+            bi = oi;
+        }
+    }
+    if (lane == 0) pick[0] = best > 0.0 ? bi : -1;
+}
+
+// gamma (F,K,T) -> target, interferer and noise masks (F,T): X = gamma[target], I =
+// gamma[pick[0]] (zero for -1), N = the remaining classes added in ascending k; all zero on the
+// context frames (masks_kernel's rule).  The first thread reports the interferer.
+__global__ void masks3_kernel(const double *__restrict__ gamma, int F, int K, int64_t T, int target,
+                              const int32_t *__restrict__ pick, int64_t zero_lo_end,
+                              int64_t zero_hi_begin, double *__restrict__ mx,
+                              double *__restrict__ mi, double *__restrict__ mn,
+                              int32_t *__restrict__ interferer_out, int32_t *__restrict__ status) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int interferer = pick[0];
+    if (idx == 0) {
+        if (interferer_out) interferer_out[0] = interferer;
+        __hip_atomic_store(status + GSS_STATUS_LCMV_INTERFERER, interferer, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (idx >= (int64_t)F * T) return;
+    const int f = idx / T;
+    const int64_t t = idx - (int64_t)f * T;
+    double x = 0.0, i = 0.0, n = 0.0;
+    if (t >= zero_lo_end && t < zero_hi_begin) {
+        const double *g = gamma + (int64_t)f * K * T + t;
+        x = g[(int64_t)target * T];
+        if (interferer >= 0) i = g[(int64_t)interferer * T];
+        for (int k = 0; k < K; ++k)
+            if (k != target && k != interferer) n += g[(int64_t)k * T];
+    }
+    mx[idx] = x;
+    mi[idx] = i;
+    mn[idx] = n;
+}
+
+// mask_pack_kernel for three masks: (F, 3, T) weights [target, interferer, noise] and (F, 3)
+// sums, in its summation order.  grid (F), block 256.
+__global__ __launch_bounds__(256) void mask_pack3_kernel(const double *__restrict__ mx,
+                                                         const double *__restrict__ mi,
+                                                         const double *__restrict__ mn, int64_t T,
+                                                         double *__restrict__ W3,
+                                                         double *__restrict__ msum) {
+    __shared__ double red[12];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    double sx = 0.0, si = 0.0, sn = 0.0;
+    for (int64_t t = tid; t < T; t += blockDim.x) {
+        const double a = mx[(int64_t)f * T + t], b = mi[(int64_t)f * T + t],
+                     c = mn[(int64_t)f * T + t];
+        W3[((int64_t)f * 3) * T + t] = a;
+        W3[((int64_t)f * 3 + 1) * T + t] = b;
+        W3[((int64_t)f * 3 + 2) * T + t] = c;
+        sx += a;
+        si += b;
+        sn += c;
+    }
+    sx = wave_sum(sx);
+    si = wave_sum(si);
+    sn = wave_sum(sn);
+    if ((tid & 63) == 0) {
+        red[tid >> 6] = sx;
+        red[4 + (tid >> 6)] = si;
+        red[8 + (tid >> 6)] = sn;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        msum[f * 3] = (red[0] + red[1]) + (red[2] + red[3]);
+        msum[f * 3 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+        msum[f * 3 + 2] = (red[8] + red[9]) + (red[10] + red[11]);
+    }
+}
+
+// Souden's LCMV with one null (Souden, Benesty, Affes 2010, eq. 51), per frequency (one
+// workgroup of MVDR_NT threads, shaped like mvdr_solve_kernel):
+//   Phi_m = S_m / max(s_m, 1e-10) for m in {X, I, N};  A = solve(Phi_N, Phi_I),
+//   B = solve(Phi_N, Phi_X) from ONE factorisation of the D x 3D block [Phi_N | Phi_I | Phi_X];
+//   g_in = tr A,  g = g_in tr B - tr(A B),  W = (g_in B - A B) / max(Re g, eps);
+//   distortion matrix Phi_D = Phi_I + Phi_N.
+// A frequency whose interferer mask sums to less than min_mass takes the MVDR of the merged
+// mask instead: Phi_D = (S_I + S_N) / max(s_I + s_N, 1e-10), the D x 2D block [Phi_D | Phi_X],
+// W = Psi / max(Re tr Psi, eps) -- every element by mvdr_solve_kernel's expressions -- and is
+// counted in *fallbacks.  s_I is known before the factorisation: a frequency factors one matrix.
+// LU with partial pivoting, the minimum-norm (lstsq) answer on an exactly singular matrix and the
+// SNR terms are mvdr_solve_kernel's.  Out: Phi (F,2,D,D) = [Phi_X, Phi_D], W (F,D,D), snr
+// (F,D,2): what mvdr_ref_kernel and mvdr_apply_kernel read.
+__global__ __launch_bounds__(MVDR_NT) void lcmv_solve_kernel(
+    const cplx *__restrict__ part /* (F,nch,3,NE) */, const double *__restrict__ msum /* (F,3) */,
+    int nch, int D, double eps, double min_mass, cplx *__restrict__ Phi, cplx *__restrict__ W,
+    cplx *__restrict__ snr, int32_t *__restrict__ fallbacks) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NT = MVDR_NT;
+    const int m = D + (D & 1);
+    const int NE = tri_count(D);
+    const int W3 = 3 * D;
+    cplx *aug = reinterpret_cast<cplx *>(smem);   // D x 3D : [Phi_N | Phi_I | Phi_X] -> [U | A | B]
+    cplx *JA = aug + D * W3;                       // m * m
+    cplx *JV = JA + m * m;                         // m * m
+    int *flags = reinterpret_cast<int *>(JV + m * m);   // (in the dynamic region: its alignment)
+    int &s_piv = flags[0];
+    int &s_singular = flags[1];
+    double *s_val = reinterpret_cast<double *>(flags + 2);   // 3 doubles
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const bool wave0 = tid < 64;                   // (D <= 32: one wave holds a column)
+
+    const double sx = msum[f * 3], si = msum[f * 3 + 1], sn = msum[f * 3 + 2];
+    const bool fall = si < min_mass;
+    // the columns in use: the matrix, then one (fallback) or two D x D right-hand sides; the
+    // solution for Phi_X sits at column cx
+    const int used = fall ? 2 * D : 3 * D, cx = used - D, nrhs = used - D;
+    const double dx = fmax(sx, 1e-10), di = fmax(si, 1e-10), dn = fmax(sn, 1e-10);
+    const double dd = fmax(si + sn, 1e-10);
+    cplx *PhiX = Phi + (int64_t)f * 2 * D * D;
+    cplx *PhiD = PhiX + D * D;
+    if (tid == 0 && fall) atomicAdd(fallbacks, 1);
+    // (called again on a singular matrix: the elimination has overwritten the block by then)
+    auto fill = [&]() {
+        for (int e = tid; e < NE; e += NT) {
+            int d1 = 0, rem = e;
+            while (rem >= D - d1) {
+                rem -= D - d1;
+                ++d1;
+            }
+            const int d2 = d1 + rem;
+            cplx vx = c_make(0.0, 0.0), vi = c_make(0.0, 0.0), vn = c_make(0.0, 0.0);
+            for (int c = 0; c < nch; ++c) {
+                const cplx *pp = part + ((int64_t)f * nch + c) * 3 * NE;
+                vx = c_add(vx, pp[e]);
+                vi = c_add(vi, pp[NE + e]);
+                vn = c_add(vn, pp[2 * NE + e]);
+            }
+            vx = c_make(vx.x / dx, vx.y / dx);
+            cplx vd;
+            if (fall) {
+                vn = c_add(vi, vn);
+                vn = c_make(vn.x / dd, vn.y / dd);
+                vd = vn;
+            } else {
+                vi = c_make(vi.x / di, vi.y / di);
+                vn = c_make(vn.x / dn, vn.y / dn);
+                vd = c_add(vi, vn);
+            }
+            if (d1 == d2) {
+                vx.y = 0.0;
+                vi.y = 0.0;
+                vn.y = 0.0;
+                vd.y = 0.0;
+            }
+            PhiX[d1 * D + d2] = vx;
+            PhiX[d2 * D + d1] = c_conj(vx);
+            PhiD[d1 * D + d2] = vd;
+            PhiD[d2 * D + d1] = c_conj(vd);
+            aug[d1 * W3 + d2] = vn;
+            aug[d2 * W3 + d1] = c_conj(vn);
+            if (!fall) {
+                aug[d1 * W3 + D + d2] = vi;
+                aug[d2 * W3 + D + d1] = c_conj(vi);
+            }
+            aug[d1 * W3 + cx + d2] = vx;
+            aug[d2 * W3 + cx + d1] = c_conj(vx);
+        }
+    };
+    fill();
+    if (tid == 0) s_singular = 0;
+    __syncthreads();
+
+    // ---- LU with partial pivoting (pivot by |re| + |im| like LAPACK izamax)
+    for (int j = 0; j < D; ++j) {
+        if (wave0) {
+            double best = -1.0;
+            int bi = j;
+            if (lane >= j && lane < D) {
+                const cplx v = aug[lane * W3 + j];
+                best = fabs(v.x) + fabs(v.y);
+                bi = lane;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ob = __shfl_xor(best, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (ob > best || (ob == best && oi < bi)) {
+                    best = ob;
+                    bi = oi;
+                }
+            }
+            if (lane == 0) {
+                s_piv = bi;
+                if (!(best > 0.0)) s_singular = 1;   // zero or NaN pivot
+            }
+        }
+        __syncthreads();
+        if (s_singular) break;
+        const int p = s_piv;
+        if (p != j) {
+            for (int col = tid; col < used; col += NT) {
+                const cplx t = aug[j * W3 + col];
+                aug[j * W3 + col] = aug[p * W3 + col];
+                aug[p * W3 + col] = t;
+            }
+        }
+        __syncthreads();
+        const cplx piv = aug[j * W3 + j];
+        const int rows = D - j - 1, cols = used - j - 1;
+        for (int i = tid; i < rows; i += NT) {
+            const int r = j + 1 + i;
+            aug[r * W3 + j] = c_div(aug[r * W3 + j], piv);
+        }
+        __syncthreads();
+        for (int it = tid; it < rows * cols; it += NT) {
+            const int i = it / cols, cidx = it - i * cols;
+            const int r = j + 1 + i, col = j + 1 + cidx;
+            const cplx l = aug[r * W3 + j], u = aug[j * W3 + col];
+            cplx v = aug[r * W3 + col];
+            v.x -= l.x * u.x - l.y * u.y;
+            v.y -= l.x * u.y + l.y * u.x;
+            aug[r * W3 + col] = v;
+        }
+        __syncthreads();
+    }
+    const bool singular = s_singular != 0;
+    if (!singular) {
+        // back substitution, one right-hand side per lane (nrhs <= 58: wave 0)
+        if (tid < nrhs) {
+            const int col = D + tid;
+            for (int j = D - 1; j >= 0; --j) {
+                cplx v = aug[j * W3 + col];
+                for (int k = j + 1; k < D; ++k) {
+                    const cplx u = aug[j * W3 + k], x = aug[k * W3 + col];
+                    v.x -= u.x * x.x - u.y * x.y;
+                    v.y -= u.x * x.y + u.y * x.x;
+                }
+                aug[j * W3 + col] = c_div(v, aug[j * W3 + j]);
+            }
+        }
+        __syncthreads();
+    } else {
+        // np.linalg.lstsq(M, R): minimum-norm solution via the Hermitian eigendecomposition;
+        // singular values below eps * D * max are dropped (mvdr_solve_kernel's branch)
+        fill();
+        __syncthreads();
+        for (int idx = tid; idx < m * m; idx += NT) {
+            const int i = idx / m, jx = idx - i * m;
+            JA[idx] = (i < D && jx < D) ? aug[i * W3 + jx] : c_make(0.0, 0.0);
+        }
+        __syncthreads();
+        if (wave0) {
+            jacobi_eigh_wave(JA, JV, m, lane, 20);
+            double lmax = 0.0;
+            for (int i = lane; i < D; i += 64) lmax = fmax(lmax, fabs(JA[i * m + i].x));
+            lmax = wave_max(lmax);
+            if (lane == 0) s_val[0] = 2.220446049250313e-16 * (double)D * lmax;
+        }
+        __syncthreads();
+        const double cut = s_val[0];
+        // each right-hand side R in turn: tmp = diag(1/l) V^H R -> the left block, V tmp -> R
+        for (int c0 = D; c0 < used; c0 += D) {
+            for (int it = tid; it < D * D; it += NT) {
+                const int j = it / D, col = it - j * D;
+                cplx v = c_make(0.0, 0.0);
+                for (int i = 0; i < D; ++i) c_cfma(v, JV[i * m + j], aug[i * W3 + c0 + col]);
+                const double l = JA[j * m + j].x;
+                const double il = fabs(l) > cut ? 1.0 / l : 0.0;
+                aug[j * W3 + col] = c_scale(v, il);
+            }
+            __syncthreads();
+            for (int it = tid; it < D * D; it += NT) {
+                const int i = it / D, col = it - i * D;
+                cplx v = c_make(0.0, 0.0);
+                for (int j = 0; j < D; ++j) c_fma(v, JV[i * m + j], aug[j * W3 + col]);
+                aug[i * W3 + c0 + col] = v;
+            }
+            __syncthreads();
+        }
+    }
+    cplx *Wf = W + (int64_t)f * D * D;
+    if (fall) {
+        // Psi = aug[:, D:2D].  W = Psi / max(Re tr Psi, eps)
+        if (wave0) {
+            double tr = 0.0;
+            for (int i = lane; i < D; i += 64) tr += aug[i * W3 + D + i].x;
+            tr = wave_sum(tr);
+            if (lane == 0) s_val[0] = fmax(tr, eps);
+        }
+        __syncthreads();
+        const double dentr = s_val[0];
+        for (int it = tid; it < D * D; it += NT) {
+            const int i = it / D, col = it - i * D;
+            const cplx v = aug[i * W3 + D + col];
+            const cplx wv = c_make(v.x / dentr, v.y / dentr);
+            aug[i * W3 + col] = wv;   // W stays in the left block for the SNR terms
+            Wf[it] = wv;
+        }
+    } else {
+        // A = aug[:, D:2D], B = aug[:, 2D:3D]; A B -> JA, spread over the workgroup
+        for (int it = tid; it < D * D; it += NT) {
+            const int i = it / D, col = it - i * D;
+            cplx v = c_make(0.0, 0.0);
+            for (int k = 0; k < D; ++k) c_fma(v, aug[i * W3 + D + k], aug[k * W3 + 2 * D + col]);
+            JA[i * m + col] = v;
+        }
+        __syncthreads();
+        // the traces: lane i holds the i-th diagonal entries, summed over the wave in wave_sum's
+        // fixed order
+        if (wave0) {
+            cplx a = c_make(0.0, 0.0), b = c_make(0.0, 0.0), ab = c_make(0.0, 0.0);
+            if (lane < D) {
+                a = aug[lane * W3 + D + lane];
+                b = aug[lane * W3 + 2 * D + lane];
+                ab = JA[lane * m + lane];
+            }
+            const cplx gi = c_make(wave_sum(a.x), wave_sum(a.y));
+            const cplx gx = c_make(wave_sum(b.x), wave_sum(b.y));
+            const double tab = wave_sum(ab.x);
+            if (lane == 0) {
+                s_val[0] = fmax(c_mul(gi, gx).x - tab, eps);   // max(Re g, eps)
+                s_val[1] = gi.x;
+                s_val[2] = gi.y;
+            }
+        }
+        __syncthreads();
+        const double den = s_val[0];
+        const cplx gi = c_make(s_val[1], s_val[2]);
+        // (reads the two right blocks and JA, writes the left block: disjoint)
+        for (int it = tid; it < D * D; it += NT) {
+            const int i = it / D, col = it - i * D;
+            const cplx v = c_sub(c_mul(gi, aug[i * W3 + 2 * D + col]), JA[i * m + col]);
+            const cplx wv = c_make(v.x / den, v.y / den);
+            aug[i * W3 + col] = wv;
+            Wf[it] = wv;
+        }
+    }
+    __syncthreads();
+    // SNR terms per reference channel r: w_r^H Phi_X w_r and w_r^H Phi_D w_r, as in
+    // mvdr_solve_kernel (T_X -> the block at cx, T_D -> JA)
+    for (int it = tid; it < D * D; it += NT) {
+        const int d = it / D, r = it - d * D;
+        cplx tx = c_make(0.0, 0.0), tn = c_make(0.0, 0.0);
+        for (int e = 0; e < D; ++e) {
+            const cplx we = aug[e * W3 + r];
+            c_fma(tx, PhiX[d * D + e], we);
+            c_fma(tn, PhiD[d * D + e], we);
+        }
+        aug[d * W3 + cx + r] = tx;
+        JA[d * m + r] = tn;
+    }
+    __syncthreads();
+    if (tid < D) {
+        const int r = tid;
+        cplx num = c_make(0.0, 0.0), den = c_make(0.0, 0.0);
+        for (int d = 0; d < D; ++d) {
+            const cplx wd = aug[d * W3 + r];
+            c_cfma(num, wd, aug[d * W3 + cx + r]);
+            c_cfma(den, wd, JA[d * m + r]);
+        }
+        snr[((int64_t)f * D + r) * 2] = num;
+        snr[((int64_t)f * D + r) * 2 + 1] = den;
+    }
+}
+
 int psd_chunks(int F, int64_t T, int *chunk_frames) {
     int64_t tiles = (T + PSD_TILE - 1) / PSD_TILE;
     int64_t want = (2048 + F - 1) / F;
@@ -1096,6 +1503,117 @@ int mvdr_segments_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, cons
     hipLaunchKernelGGL(mvdr_apply_kernel<true>, dim3((unsigned)((T + chunk - 1) / chunk), F), dim3(256), 0,
                        ctx->stream, Y, W, Phi, ref, F, T, D, ban, chunk, Xhat, ref_channel,
                        ctx->status_dev, g.L, (const int32_t *)fallbacks);
+    GSS_LAUNCH_CHECK(ctx, "mvdr_apply_kernel");
+    return GSS_OK;
+}
+
+// ------------------------------------------------------------------ interferer-nulling LCMV
+size_t lcmv_masks_workspace_bytes(int F, int K) {
+    size_t b = 0;
+    b += align_up(sizeof(double) * (size_t)F * K);               // fmass
+    b += align_up(sizeof(int32_t) * 4);                          // pick
+    return b + 4096;
+}
+
+int lcmv_masks_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T, int target,
+                   const gss_bf_lcmv &bf, int drop, int64_t sf, int64_t ef, double *mx, double *mi,
+                   double *mn, int32_t *interferer) {
+    // (masks_from_posteriors_run's range)
+    int64_t lo_end = 0, hi_begin = T;
+    if (drop) {
+        lo_end = sf >= 0 ? (sf < T ? sf : T) : (T + sf > 0 ? T + sf : 0);
+        if (ef > 0) hi_begin = T - ef > 0 ? T - ef : 0;
+    }
+    double *fmass = arena_alloc_t<double>(ctx, (size_t)F * K);
+    int32_t *pick = arena_alloc_t<int32_t>(ctx, 4);
+    GSS_REQUIRE(ctx, fmass && pick, GSS_ERR_NOMEM, "lcmv masks workspace");
+    {
+        GSS_PROF(ctx, "lcmv_pick");
+        if (bf.interferer < 0) {
+            hipLaunchKernelGGL(lcmv_mass_kernel, dim3(F, K), dim3(256), 0, ctx->stream, gamma, K, T,
+                               lo_end, hi_begin, fmass);
+            GSS_LAUNCH_CHECK(ctx, "lcmv_mass_kernel");
+        }
+        hipLaunchKernelGGL(lcmv_pick_kernel, dim3(1), dim3(64), 0, ctx->stream, fmass, F, K, target,
+                           bf.candidates, (int)bf.interferer, pick);
+        GSS_LAUNCH_CHECK(ctx, "lcmv_pick_kernel");
+    }
+    GSS_PROF(ctx, "masks3");
+    const int64_t total = (int64_t)F * T;
+    hipLaunchKernelGGL(masks3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       ctx->stream, gamma, F, K, T, target, pick, lo_end, hi_begin, mx, mi, mn,
+                       interferer, ctx->status_dev);
+    GSS_LAUNCH_CHECK(ctx, "masks3_kernel");
+    return GSS_OK;
+}
+
+size_t lcmv_workspace_bytes(int F, int64_t T, int D) {
+    const size_t NE = tri_count(D);
+    int cf;
+    const int nch = psd_chunks(F, T, &cf);
+    size_t b = 0;
+    b += align_up(sizeof(cplx) * (size_t)F * nch * 3 * NE);      // part
+    b += align_up(sizeof(double) * (size_t)F * 3);               // msum
+    b += align_up(sizeof(double) * (size_t)F * 3 * T);           // W3
+    b += align_up(sizeof(cplx) * (size_t)F * 2 * D * D);         // Phi
+    b += align_up(sizeof(cplx) * (size_t)F * D * D);             // W
+    b += align_up(sizeof(cplx) * (size_t)F * D * 2);             // snr
+    b += align_up(sizeof(int32_t) * 4);                          // ref
+    return b + 4096;
+}
+
+int lcmv_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
+             const double *mi, const double *mn, int ban, int forced_ref, double min_mass,
+             cplx *Xhat, int32_t *ref_channel) {
+    const int NE = tri_count(D);
+    int cf;
+    const int nch = psd_chunks(F, T, &cf);
+    cplx *part = arena_alloc_t<cplx>(ctx, (size_t)F * nch * 3 * NE);
+    double *msum = arena_alloc_t<double>(ctx, (size_t)F * 3);
+    double *W3 = arena_alloc_t<double>(ctx, (size_t)F * 3 * T);
+    cplx *Phi = arena_alloc_t<cplx>(ctx, (size_t)F * 2 * D * D);
+    cplx *W = arena_alloc_t<cplx>(ctx, (size_t)F * D * D);
+    cplx *snr = arena_alloc_t<cplx>(ctx, (size_t)F * D * 2);
+    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);   // [0]: reference channel, [2]: fallback counter
+    GSS_REQUIRE(ctx, part && msum && W3 && Phi && W && snr && ref, GSS_ERR_NOMEM,
+                "lcmv workspace");
+    int32_t *const fallbacks = ref + 2;
+    ctx->last_targets = 0;
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(fallbacks, 0, sizeof(int32_t), ctx->stream));
+    {
+        GSS_PROF(ctx, "psd3");
+        hipLaunchKernelGGL(mask_pack3_kernel, dim3(F), dim3(256), 0, ctx->stream, mx, mi, mn, T, W3,
+                           msum);
+        GSS_LAUNCH_CHECK(ctx, "mask_pack3_kernel");
+        GSS_TRY(psd3_partials_run(ctx, Y, F, T, D, W3, nch, cf, part));
+    }
+    {
+        GSS_PROF(ctx, "lcmv_solve");
+        const int m = D + (D & 1);
+        const size_t lds = (sizeof(cplx) * ((size_t)D * 3 * D + 2 * (size_t)m * m) + 32 + 15) / 16 * 16;
+        if (lds > 64 * 1024)
+            GSS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(lcmv_solve_kernel),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)lds));
+        hipLaunchKernelGGL(lcmv_solve_kernel, dim3(F), dim3(MVDR_NT), lds, ctx->stream, part, msum,
+                           nch, D, 1e-10, min_mass, Phi, W, snr, fallbacks);
+        GSS_LAUNCH_CHECK(ctx, "lcmv_solve_kernel");
+        // the count of this call -> the context's status word
+        GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_LCMV_FALLBACKS, fallbacks,
+                                          sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    {
+        GSS_PROF(ctx, "mvdr_ref");
+        hipLaunchKernelGGL(mvdr_ref_kernel, dim3(1), dim3(MVDR_REF_NT),
+                           sizeof(cplx) * MVDR_REF_CHUNK * (size_t)D * 2, ctx->stream, snr, F, D, 1e-10,
+                           forced_ref, ref);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_ref_kernel");
+    }
+    GSS_PROF(ctx, "mvdr_apply");
+    const int chunk = 256;
+    hipLaunchKernelGGL(mvdr_apply_kernel<false>, dim3((unsigned)((T + chunk - 1) / chunk), F),
+                       dim3(256), 0, ctx->stream, Y, W, Phi, ref, F, T, D, ban, chunk, Xhat,
+                       ref_channel, ctx->status_dev, (int64_t)0, (const int32_t *)nullptr);
     GSS_LAUNCH_CHECK(ctx, "mvdr_apply_kernel");
     return GSS_OK;
 }

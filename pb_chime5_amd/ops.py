@@ -12,6 +12,9 @@ here                        reference call (file:line)
 ``cacgmm_posteriors_guided``  the same from any initialisation / source_activity_mask
 ``mvdr_souden_from_masks``  pb_bss beamformer chain       (beamforming_wrapper.py:51-97)
 ``mvdr_souden_segments_from_masks``  the same with statistics per segment of frames
+``lcmv_souden_from_masks``  beamform_lcmv_souden_from_masks (beamforming_wrapper.py:127-171)
+``lcmv_masks_from_posteriors`` / ``enhance_observation_lcmv``
+                            the interferer-nulling LCMV fed from the posteriors
 ``enhance_observation``     Enhancer.enhance_observation  (core.py:514-571)
 ``channel_scores`` / ``select_channels`` / ``enhance_observation_select``
                             envelope-variance channel selection ahead of WPE (not in the
@@ -25,7 +28,7 @@ import ctypes
 import numpy as np
 
 from . import _capi
-from ._capi import (Context, GssBfSegments, GssCacgmmModel, GssChannelSelect, GssDebugTaps,
+from ._capi import (Context, GssBfLcmv, GssBfSegments, GssCacgmmModel, GssChannelSelect, GssDebugTaps,
                     GssGuidance, GssParams, c_void_p, default_context)
 from .cacgmm import CACGMM
 
@@ -610,6 +613,124 @@ def mvdr_souden_segments_from_masks(Y, X_mask, N_mask, ban=False, *, segment_fra
     return out if len(out) > 1 else out[0]
 
 
+def check_bf_lcmv(num_classes, target_index, interferer=None, candidates=None, min_mass=None,
+                  num_channels=None):
+    """The settings of the interferer-nulling LCMV as a gss_bf_lcmv, or ValueError naming the
+    argument: ``interferer`` a class index other than the target (None: chosen among
+    ``candidates``, an iterable of class indices -- None: every class but the target -- by its
+    mass), ``min_mass`` finite and >= 0.  ``min_mass=None`` is ``2 * num_channels`` (0 while
+    ``num_channels`` is not known, as in `check_bf_segments`)."""
+    K = num_classes
+    if not _is_integer(K) or not 1 <= K <= 19:
+        raise ValueError(f'num_classes={K!r}: an integer in [1, 19]')
+    if not _is_integer(target_index) or not 0 <= target_index < K:
+        raise ValueError(f'target_index={target_index!r} outside [0, {K})')
+    if interferer is not None:
+        if not _is_integer(interferer) or not 0 <= interferer < K:
+            raise ValueError(f'interferer={interferer!r} outside [0, {K})')
+        if interferer == target_index:
+            raise ValueError(f'interferer={interferer!r} is the target')
+    bits = 0
+    if candidates is None:
+        candidates = [k for k in range(K) if k != target_index]
+    elif isinstance(candidates, (str, bytes)) or not hasattr(candidates, '__iter__'):
+        raise ValueError(f'candidates={candidates!r}: an iterable of class indices')
+    for k in candidates:
+        if not _is_integer(k) or not 0 <= k < K:
+            raise ValueError(f'candidates: {k!r} outside [0, {K})')
+        if k != target_index:
+            bits |= 1 << int(k)
+    if min_mass is None:
+        min_mass = 2 * num_channels if num_channels is not None else 0
+    if not _is_real(min_mass) or not np.isfinite(min_mass) or min_mass < 0:
+        raise ValueError(f'min_mass={min_mass!r}: a finite number >= 0')
+    return GssBfLcmv(interferer=-1 if interferer is None else int(interferer), candidates=bits,
+                     min_mass=float(min_mass))
+
+
+def _check_lcmv_channels(D):
+    if D < 2:
+        raise ValueError(f'D={D}: the LCMV needs at least 2 channels')
+    if D >= 30:     # (not an `assert` statement: those vanish under python -O)
+        raise AssertionError(f'assert D < 30 failed: D={D}')
+
+
+def lcmv_souden_from_masks(Y, X_mask, I_mask, N_mask, ban=False, *, min_mass=0.0,
+                           ref_channel=None, return_ref_channel=False, return_fallbacks=False,
+                           ctx=None):
+    """beamform_lcmv_souden_from_masks (gss_lcmv_souden): Souden's LCMV, distortionless for the
+    target and with a null on the interferer, from three masks.  A frequency whose interferer
+    mask sums to less than ``min_mass`` takes the MVDR of ``N_mask + I_mask`` instead;
+    ``min_mass=0`` (the reference's behaviour) never falls back.  ``ref_channel`` names the
+    reference channel; None = the SNR argmax against Phi_I + Phi_N.
+
+    Y (D,T,F), masks (T,F) -> X_hat (T,F); with ``return_ref_channel`` / ``return_fallbacks`` a
+    tuple (X_hat[, ref_channel][, number of frequencies that fell back]).  Argument errors are
+    ValueError before any device work; a non-finite SNR raises AssertionError like the MVDR."""
+    Y = np.asarray(Y)
+    if Y.ndim != 3:
+        raise ValueError(f'Y: shape {Y.shape} is not (D,T,F)')
+    D, T, F = Y.shape
+    _check_lcmv_channels(D)
+    for name, m in (('X_mask', X_mask), ('I_mask', I_mask), ('N_mask', N_mask)):
+        if np.shape(m) != (T, F):
+            raise ValueError(f'{name}: shape {np.shape(m)} is not (T,F) = {(T, F)}')
+    if not _is_real(min_mass) or not np.isfinite(min_mass) or min_mass < 0:
+        raise ValueError(f'min_mass={min_mass!r}: a finite number >= 0')
+    if ref_channel is not None and (not _is_integer(ref_channel) or not 0 <= ref_channel < D):
+        raise ValueError(f'ref_channel={ref_channel!r} outside [0, {D})')
+    ctx = ctx or default_context()
+    Y_d, _ = _obs_to_device_ftd(ctx, Y)
+    mx = _mask_to_device_ft(ctx, X_mask, T, F)
+    mi = _mask_to_device_ft(ctx, I_mask, T, F)
+    mn = _mask_to_device_ft(ctx, N_mask, T, F)
+    X_d = ctx.empty(16 * F * T)
+    ctx._check(ctx.lib.gss_lcmv_souden(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, c_void_p(mx.ptr), c_void_p(mi.ptr),
+        c_void_p(mn.ptr), int(bool(ban)), -1 if ref_channel is None else int(ref_channel),
+        float(min_mass), c_void_p(X_d.ptr), None), 'gss_lcmv_souden')
+    ref = _check_ref_channel(ctx)
+    out = (ctx.to_host(X_d, (T, F), np.complex128),)
+    if return_ref_channel:
+        out += (ref,)
+    if return_fallbacks:
+        out += (ctx.last_lcmv_fallbacks(),)
+    return out if len(out) > 1 else out[0]
+
+
+def lcmv_masks_from_posteriors(posterior, target_index, *, interferer=None, candidates=None,
+                               drop_context=True, start_context_frames=0, end_context_frames=0,
+                               ctx=None):
+    """The three masks of the LCMV from the posteriors (gss_lcmv_masks_from_posteriors):
+    posterior (K,T,F) -> (X_mask, I_mask, N_mask, interferer), masks (T,F).  The interferer is
+    ``interferer``, or the class among ``candidates`` (None: every class but the target) of
+    largest mass over the frames the context zeroing keeps; -1 (an all-zero I_mask) when there
+    is no candidate or no mass.  N_mask is the sum of the remaining classes; the context frames
+    are zeroed by the rule of ``masks[:, :start] = 0; if end > 0: masks[:, -end:] = 0``."""
+    g = np.asarray(posterior, dtype=np.float64)
+    if g.ndim != 3:
+        raise ValueError(f'posterior: shape {g.shape} is not (K,T,F)')
+    K, T, F = g.shape
+    bf = check_bf_lcmv(K, target_index, interferer, candidates, 0)
+    for name, v in (('start_context_frames', start_context_frames),
+                    ('end_context_frames', end_context_frames)):
+        if not _is_integer(v):
+            raise ValueError(f'{name}={v!r} is not an integer')
+    ctx = ctx or default_context()
+    g_d = ctx.to_device(g.transpose(2, 0, 1))                       # (F,K,T)
+    bufs = [ctx.empty(8 * F * T) for _ in range(3)]
+    which = ctx.empty(16)
+    ctx._check(ctx.lib.gss_lcmv_masks_from_posteriors(
+        ctx.handle, c_void_p(g_d.ptr), F, K, T, int(target_index), ctypes.byref(bf),
+        int(bool(drop_context)), int(start_context_frames), int(end_context_frames),
+        *(c_void_p(b.ptr) for b in bufs), c_void_p(which.ptr)),
+        'gss_lcmv_masks_from_posteriors')
+    masks = [np.ascontiguousarray(ctx.to_host(b, (F, T), np.float64).T) for b in bufs]
+    found = int(ctx.to_host(which, (1,), np.int32)[0])
+    assert found == ctx.last_lcmv_interferer(), (found, ctx.last_lcmv_interferer())
+    return (*masks, found)
+
+
 def gev_from_masks(Y, X_mask, N_mask, ban=True, *, ctx=None):
     """beamform_gev_from_masks: Y (D,T,F), 2-D masks (T,F) -> X_hat (T,F).  The phase
     of a generalised eigenvector is arbitrary (upstream too); magnitudes are defined.
@@ -926,12 +1047,24 @@ class ResidentUtterance:
         self.out_d = ctx.empty(8 * max(self.n_out, 1))
 
     def enqueue(self, target_index, start_context, end_context, taps=None, segments=None,
-                channel_select=None):
+                channel_select=None, lcmv=None):
         """``segments``: a gss_bf_segments (`check_bf_segments`) for the segment-wise
         beamformer (gss_enhance_observation_segments; float64 samples only).
         ``channel_select``: a `ChannelSelect` for the envelope-variance selection ahead of WPE
-        (gss_enhance_observation_select / its pcm16 twin; not together with segments)."""
+        (gss_enhance_observation_select / its pcm16 twin; not together with segments).
+        ``lcmv``: a gss_bf_lcmv (`check_bf_lcmv`) for the interferer-nulling beamformer
+        (gss_enhance_observation_lcmv; float64 samples only, on its own)."""
         ctx = self.ctx
+        if lcmv is not None:
+            assert segments is None and channel_select is None, 'the LCMV call stands alone'
+            assert not self.pcm, 'the LCMV call has no pcm16 twin'
+            ctx._check(ctx.lib.gss_enhance_observation_lcmv(
+                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
+                self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
+                int(start_context), int(end_context), ctypes.byref(lcmv),
+                c_void_p(self.out_d.ptr), ctypes.byref(taps) if taps is not None else None),
+                'gss_enhance_observation_lcmv')
+            return
         if channel_select is not None:
             assert segments is None, 'no selection inside the segment-wise call'
             st = channel_select.struct(ctx, self.D)
@@ -1284,6 +1417,59 @@ def enhance_observation_segments(obs, activity, target_index, start_context_samp
     details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
     details['ref_channel'] = int(details['ref_channel'])
     details['segment_fallbacks'] = ctx.last_segment_fallbacks()
+    return x_hat, details
+
+
+def enhance_observation_lcmv(obs, activity, target_index, start_context_samples,
+                             end_context_samples, *, interferer=None, candidates=None,
+                             min_mass=None, params=None, window=None, debug=False, ctx=None,
+                             wpe_arrays=None, **param_kwargs):
+    """`enhance_observation` with the interferer-nulling LCMV of `lcmv_souden_from_masks`
+    (gss_enhance_observation_lcmv) in the place of the MVDR: the interferer is ``interferer`` or
+    the class among ``candidates`` (None: every class but the target) with the most posterior
+    mass; frequencies where its mask sums to less than ``min_mass`` (None: 2 * channels) take
+    the MVDR.  ``debug`` details as there -- ``distortion_mask`` is I + N -- plus
+    ``interferer`` (-1: none), ``interferer_mask`` (T,F) and ``lcmv_fallbacks``.  Only
+    ``bf='mvdrSouden_ban'`` has it (NotImplementedError otherwise); bad settings are
+    ValueError, both before any device work."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    if params.bf != _BF_CODES['mvdrSouden_ban']:
+        names = {v: k for k, v in _BF_CODES.items()}
+        raise NotImplementedError(f"bf={names[params.bf]!r} with null_interferer: only "
+                                  "'mvdrSouden_ban' has an interferer-nulling form")
+    obs = np.asarray(obs)
+    if obs.ndim != 2:
+        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    _check_lcmv_channels(obs.shape[0])
+    K = np.shape(activity)[0]
+    bf = check_bf_lcmv(K, target_index, interferer, candidates, min_mass, obs.shape[0])
+    params = params_for(params, obs.shape[0], wpe_arrays)
+    ctx = ctx or default_context()
+    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
+    utt = ResidentUtterance(ctx, obs, activity, params)
+    bufs, taps = _debug_taps(utt) if debug else ({}, None)
+    utt.enqueue(target_index, start_context_samples, end_context_samples, taps, lcmv=bf)
+    x_hat = utt.result()
+    if not debug:
+        return x_hat
+    details = _debug_details(utt, bufs)
+    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+    details['ref_channel'] = int(details['ref_channel'])
+    found = details['interferer'] = ctx.last_lcmv_interferer()
+    details['lcmv_fallbacks'] = ctx.last_lcmv_fallbacks()
+    # the interferer's posterior with the context frames zeroed: the bits the call used
+    mask = np.zeros_like(details['target_mask'])
+    if found >= 0:
+        mask[...] = details['posterior'][found]
+        if params.bf_drop_context:
+            sf, ef = (samples_to_stft_frames(c, params.stft_size, params.stft_shift,
+                                             fading=params.stft_fading)
+                      for c in (start_context_samples, end_context_samples))
+            mask[:sf] = 0
+            if ef > 0:
+                mask[-ef:] = 0
+    details['interferer_mask'] = mask
     return x_hat, details
 
 

@@ -47,6 +47,10 @@ def main(argv=None):
                          'frames, a multiple of 64 (get_enhancer(bf_segment_frames=...))')
     ap.add_argument('--bf-segment-context', type=int, default=0,
                     help='segments either side in the statistics of a segment')
+    ap.add_argument('--bf-null-interferer', action='store_true',
+                    help='interferer-nulling LCMV in the place of the MVDR: a null on the '
+                         'competing speaker with the most posterior mass '
+                         '(get_enhancer(bf_null_interferer=True))')
     ap.add_argument('--channel-keep', type=_channel_keep, default=None,
                     help='keep the channels the envelope-variance measure ranks best: a count '
                          '(20) or a share (0.8) (get_enhancer(channel_keep=...))')
@@ -71,7 +75,8 @@ def main(argv=None):
         bf_drop_context=not args.no_bf_drop_context, bf=args.bf, postfilter=args.postfilter,
         device_id=parallel.device_index(), wpe_per_array=args.wpe_per_array,
         bf_segment_frames=args.bf_segment_frames, bf_segment_context=args.bf_segment_context,
-        channel_keep=args.channel_keep, channel_bands=args.channel_bands)
+        channel_keep=args.channel_keep, channel_bands=args.channel_bands,
+        bf_null_interferer=args.bf_null_interferer)
     if parallel.is_master():
         Path(args.out).mkdir(parents=True, exist_ok=True)
     parallel.barrier()

@@ -1,5 +1,5 @@
 """Mask-based beamforming front door with the reference's call surface
-(/root/reference/pb_chime5/speech_enhancement/beamforming_wrapper.py:11-124).
+(/root/reference/pb_chime5/speech_enhancement/beamforming_wrapper.py:11-171).
 
 ``beamform_mvdr_souden_from_masks(Y, X_mask, N_mask, ban=False)`` accepts the same
 layouts as the reference -- Y (D,T,F) or (1,D,T,F); masks (T,F), (D,T,F) or
@@ -110,3 +110,36 @@ def beamform_mvdr_souden_from_masks(Y, X_mask, N_mask, ban=False, debug=False, c
     if ban:
         return bf.X_hat_mvdr_souden_ban
     return bf.X_hat_mvdr_souden
+
+
+def beamform_lcmv_souden_from_masks(Y, X_mask, I_mask, N_mask, ban=False, debug=False, *,
+                                    ref_channel=None, ctx=None):
+    """beamforming_wrapper.py:127-171: Souden's LCMV from target, interferer and noise masks,
+    with the reference's layouts -- Y (D,T,F) or (1,D,T,F); masks (T,F), (D,T,F) or (1,D,T,F),
+    median-reduced over the channel axis.  Nothing falls back to the MVDR (``min_mass=0`` of
+    ``ops.lcmv_souden_from_masks``): an empty interferer mask gives NaN under ``ban``, as
+    upstream.  ``ref_channel`` (an addition): the reference channel; None = the SNR argmax."""
+    if np.ndim(Y) == 4:
+        Y = morph('1DTF->FDT', Y)
+    else:
+        Y = morph('DTF->FDT', Y)
+    if np.ndim(X_mask) == 4:
+        pattern = '1DTF->FT'
+    elif np.ndim(X_mask) == 3:
+        pattern = 'DTF->FT'
+    elif np.ndim(X_mask) == 2:
+        pattern = 'TF->FT'
+    else:
+        raise NotImplementedError(np.shape(X_mask))
+    if pattern == 'TF->FT':
+        X_mask, I_mask, N_mask = (morph(pattern, m) for m in (X_mask, I_mask, N_mask))
+    else:
+        X_mask, I_mask, N_mask = (morph(pattern, m, reduce=np.median)
+                                  for m in (X_mask, I_mask, N_mask))
+    assert Y.ndim == 3, Y.shape
+    F, D, T = Y.shape
+    assert D < 30, (D, Y.shape)
+    for m in (X_mask, I_mask, N_mask):
+        assert m.shape == (F, T), (m.shape, F, T)
+    return ops.lcmv_souden_from_masks(Y.transpose(1, 2, 0), X_mask.T, I_mask.T, N_mask.T,
+                                      ban=ban, min_mass=0.0, ref_channel=ref_channel, ctx=ctx)
