@@ -85,7 +85,7 @@ typedef enum {
  * their layouts, revision still 7.  So were gss_cacgmm_fit and gss_cacgmm_predict with the
  * gss_cacgmm_model descriptor.  So were gss_lcmv_souden, gss_lcmv_masks_from_posteriors,
  * gss_enhance_observation_lcmv, gss_last_lcmv_interferer and gss_last_lcmv_fallbacks with the
- * gss_bf_lcmv descriptor. */
+ * gss_bf_lcmv descriptor.  So were gss_posterior_activity and gss_enhance_observation_activity. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -503,6 +503,25 @@ int gss_select_channels(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, i
  * or larger than that call's count (0 before any). */
 int gss_last_selected_channels(gss_ctx *ctx, int32_t *channels_host, int n);
 
+/* Per-speaker frame activity from the posteriors (not in the reference): the power-weighted share
+ * of every frame that the mixture model gives each class.  For Y (F,T,D) -- the signal the EM
+ * saw, i.e. after WPE --, gamma (F,K,T) and frequency weights w (F,), NULL = all ones:
+ *    p[f,t] = sum_d |Y[f,t,d]|^2;   power[t] = sum_f w[f] p[f,t];
+ *    score[k,t] = sum_f w[f] gamma[f,k,t] p[f,t] / power[t],   0 where power[t] is not > 0.
+ * Scores lie in [0, 1] up to rounding, are not clamped, and sum to 1 over k wherever the
+ * posteriors do and the frame is not digital silence.  Y, gamma -> scores (K,T) and, unless
+ * NULL, power (T).  The sums have one fixed order (no floating-point atomics): the same call gives
+ * the same bits.  The library holds no policy: what the scores mean for a speaker's activity is
+ * decided on the host (pb_chime5_amd.posterior_activity).
+ * GSS_ERR_INVALID (the message names the argument), before any launch: Y_dev, gamma_dev or
+ * scores_dev NULL, F < 1, T < 1, K outside [1, GSS_MAX_CLASSES], D outside
+ * [1, GSS_MAX_CHANNELS].  The weight table is NOT inspected: negative or non-finite weights
+ * propagate; the Python layer checks them (pb_chime5_amd.ops.check_freq_weights). */
+int gss_posterior_activity(gss_ctx *ctx, const gss_cplx *Y_dev, const double *gamma_dev,
+                           int F, int K, int64_t T, int D,
+                           const double *freq_weights_dev /* (F,), NULL = ones */,
+                           double *scores_dev /* (K,T) */, double *power_dev /* (T,), may be NULL */);
+
 /* Layout helpers between the canonical device layouts and the reference's. */
 int gss_layout_dtf_to_ftd(gss_ctx *ctx, const gss_cplx *src_dev, int D, int64_t T,
                           int F, gss_cplx *dst_dev);
@@ -613,6 +632,24 @@ int gss_enhance_observation_lcmv(gss_ctx *ctx, const gss_params *params,
                                  int64_t end_context_samples,
                                  const gss_bf_lcmv *lcmv,
                                  double *out_dev, const gss_debug_taps *taps);
+
+/* gss_enhance_observation plus gss_posterior_activity on the pipeline's own post-WPE observation
+ * and its posteriors before context zeroing (what the taps Obs_ftd and gamma show), nothing
+ * copied: scores (K,T) and, unless NULL, power (T) with T = gss_stft_num_frames(N, ...);
+ * freq_weights (stft_size / 2 + 1,) or NULL for ones, not inspected.  `out` and every tap have the
+ * bits of gss_enhance_observation.
+ * GSS_ERR_INVALID (the message names the argument), before any launch: params, obs_dev, act_dev,
+ * out_dev or scores_dev NULL, N < 1, K outside [1, GSS_MAX_CLASSES], D outside
+ * [1, GSS_MAX_CHANNELS]; then the errors of gss_enhance_observation. */
+int gss_enhance_observation_activity(gss_ctx *ctx, const gss_params *params,
+                                     const double *obs_dev, int D, int64_t N,
+                                     const uint8_t *act_dev, int K, int64_t N_act,
+                                     int target_index,
+                                     int64_t start_context_samples,
+                                     int64_t end_context_samples,
+                                     const double *freq_weights_dev,
+                                     double *out_dev, double *scores_dev, double *power_dev,
+                                     const gss_debug_taps *taps);
 
 /* gss_enhance_observation on the sel->keep channels the envelope-variance measure ranks best:
  * the STFT runs on all D channels, then scores, pick and gather, then the unchanged pipeline

@@ -189,6 +189,12 @@ SIGNATURES = {
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
                 ctypes.POINTER(GssChannelSelect), c_void_p, ctypes.POINTER(GssDebugTaps)]),
+    'gss_posterior_activity': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int,
+                                       c_void_p, c_void_p, c_void_p]),
+    'gss_enhance_observation_activity': (
+        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
+                c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                c_void_p, ctypes.POINTER(GssDebugTaps)]),
     'gss_enhance_observation_host': (
         c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
                 c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p]),

@@ -20,6 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from pb_chime5_amd import mapping, ops
+from pb_chime5_amd import posterior_activity as pact
 from pb_chime5_amd.database.chime5 import activity_time_to_frequency
 from pb_chime5_amd.io import dump_audio, load_audio
 from pb_chime5_amd.utils.numpy_utils import morph
@@ -465,11 +466,18 @@ class Enhancer:
             equal_start_context=True)
 
     def enhance_session(self, session_ids, audio_dir, dataset_slice=False,
-                        audio_dir_exist_ok=False):
+                        audio_dir_exist_ok=False, refined_rttm=False):
         """core.py:333-394; examples are sharded over the visible GPUs by
-        pb_chime5_amd.parallel when more than one process is running."""
+        pb_chime5_amd.parallel when more than one process is running.
+        ``refined_rttm=True`` (an addition): every utterance also writes
+        ``<example_id>.rttm`` next to its WAV -- the frames inside the utterance that the
+        posteriors give the target speaker (`enhance_example_activity`), file id = the session
+        id.  One file per utterance and no merge step (`from_rttm` takes a list of files and
+        unites overlapping lines); such a session runs one utterance at a time."""
         from pb_chime5_amd import parallel
         self._no_null('enhance_session')
+        if refined_rttm:
+            self._no_activity_options('enhance_session(refined_rttm=True)')
         audio_dir = Path(audio_dir)
         it = self.get_iterator(session_ids)
 
@@ -497,7 +505,8 @@ class Enhancer:
                     return max((samples(v) for v in tree.values()), default=0)
                 return int(tree)
             costs = [samples(ex['num_samples']) for ex in it]
-        self._enhance_and_write(parallel.split_managed(it, costs=costs), audio_dir)
+        self._enhance_and_write(parallel.split_managed(it, costs=costs), audio_dir,
+                                refined_rttm=refined_rttm)
         # (split_managed ends without a barrier: this rank's pipeline has drained by now)
         parallel.barrier()
 
@@ -515,16 +524,28 @@ class Enhancer:
         else:
             raise NotImplementedError(x_hat.shape)
 
-    def _enhance_and_write(self, examples, audio_dir):
+    def _write_rttm(self, ex, intervals, audio_dir):
+        dataset = mapping.session_to_dataset[ex['session_id']]
+        pact.write_rttm(Path(audio_dir) / f'{dataset}' / f'{ex["example_id"]}.rttm',
+                        ex['session_id'], {ex['speaker_id']: intervals})
+
+    def _enhance_and_write(self, examples, audio_dir, refined_rttm=False):
         """Enhance the examples and write ``audio_dir/<dataset>/<example_id>.wav``.
         With the fused device pipeline ``self.inflight`` (default 2) utterances are kept
         in flight on separate HIP streams: the host loads the next example's audio
         while the GPU works, and one utterance's latency-bound kernels overlap the
         other's compute-bound ones.  Results are identical to the one-at-a-time loop."""
-        # (a segment-wise beamformer has no pipelined pcm16 entry point: one at a time)
-        if self.inflight <= 1 or not self._fusable() or self._bf_segments() is not None:
+        # (a segment-wise beamformer has no pipelined pcm16 entry point: one at a time; neither
+        # has the posterior activity of a refined RTTM)
+        if (self.inflight <= 1 or not self._fusable() or self._bf_segments() is not None
+                or refined_rttm):
             for ex in examples:
                 try:
+                    if refined_rttm:
+                        x_hat, intervals = self.enhance_example_activity(ex)
+                        self._write(ex, x_hat, audio_dir)
+                        self._write_rttm(ex, intervals, audio_dir)
+                        continue
                     self._write(ex, self.enhance_example(ex), audio_dir)
                 except Exception:
                     print('ERROR: Failed example:', ex.get('example_id'))
@@ -841,6 +862,19 @@ class Enhancer:
                 f'{what} with bf_null_interferer: the interferer-nulling beamformer is built '
                 'for enhance_observation only')
 
+    def _no_activity_options(self, what):
+        """The posterior activity is built for the whole-window MVDR on all channels."""
+        self._no_segments(what)
+        self._no_null(what)
+        self._no_channel_keep(what)
+
+    @staticmethod
+    def _no_posterior_activity(what, posterior_activity):
+        if posterior_activity:
+            raise NotImplementedError(
+                f'{what} with posterior_activity: the scores are built for '
+                'enhance_observation_activity (one target) only')
+
     def interferer_candidates(self, ex_array_activity, speaker_id):
         """The classes the interferer of ``speaker_id`` is chosen from, as indices into the
         activity keys: every key but the target and the garbage tracks that
@@ -931,6 +965,77 @@ class Enhancer:
                 masks[:, -end_context_frames:, :] = 0
         self.enhance_observation_locals = locals()
         return x_hat
+
+    def enhance_observation_activity(self, obs, ex_array_activity, speaker_id, ex=None, *,
+                                     freq_weights=None, fused=None, wpe_arrays=None):
+        """`enhance_observation` plus what the separation learned about the annotation: returns
+        (x_hat, `posterior_activity.PosteriorActivity`) -- x_hat with the bits of
+        `enhance_observation`, and for every class of ``ex_array_activity`` the power-weighted
+        share of each STFT frame that the posteriors (before context zeroing) give it
+        (`ops.posterior_activity`; ``freq_weights`` (F,) >= 0 weighs the frequencies).  The fused
+        path is one gss_enhance_observation_activity call, the block path
+        `ops.posterior_activity` on the blocks' Obs and posterior.  Not with
+        ``bf_segment_frames``, ``bf_null_interferer`` or ``channel_keep``
+        (NotImplementedError)."""
+        self._no_activity_options('enhance_observation_activity')
+        freq_weights = ops.check_freq_weights(freq_weights, self.stft_size // 2 + 1)
+        if wpe_arrays is None:
+            wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
+        wpe_arrays = ops.check_wpe_arrays(wpe_arrays, np.shape(obs)[0])
+        keys = tuple(ex_array_activity.keys())
+        target_speaker_index = keys.index(speaker_id)
+        start_ctx = end_ctx = 0
+        if ex is not None and 'start_orig' in ex:
+            start_ctx, end_ctx = start_end_context_samples(ex)
+        context_frames = [ops.samples_to_stft_frames(c, self.stft_size, self.stft_shift,
+                                                     fading=self.stft_fading)
+                          for c in (start_ctx, end_ctx)]
+        if fused is None:
+            fused = self._fusable()
+        if not fused:
+            blocks = self._blocks_posterior(obs, ex_array_activity, False, wpe_arrays)
+            scores, power = ops.posterior_activity(blocks[0], blocks[2], freq_weights,
+                                                   return_power=True, ctx=self._ctx())
+            # (the context frames of the posteriors are zeroed in place from here on)
+            x_hat = self._enhance_observation_blocks(obs, ex_array_activity, speaker_id, ex,
+                                                     False, wpe_arrays, blocks)
+        else:
+            activity = np.array(list(ex_array_activity.values()))
+            if not self.bf_drop_context:
+                start_ctx = end_ctx = 0
+            params = self._params()
+            ctx = self._ctx()
+            ctx.set_utterances_in_flight(1)
+            try:
+                x_hat, scores, power = ops.enhance_observation_activity(
+                    obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
+                    freq_weights=freq_weights, ctx=ctx, wpe_arrays=wpe_arrays)
+            finally:
+                ctx.set_utterances_in_flight(0)
+        return x_hat, pact.PosteriorActivity(scores, power, keys, target_speaker_index,
+                                             *context_frames)
+
+    def enhance_example_activity(self, ex, rule=None, freq_weights=None):
+        """`enhance_example` plus the target speaker's refined activity: returns (x_hat,
+        intervals) -- x_hat trimmed as `enhance_example` trims it, intervals
+        [(start, end), ...] where `posterior_activity.decide` (``rule``: an `ActivityRule`, None:
+        its defaults) finds the speaker active, restricted to the utterance's own span (the
+        context is left out), in samples of the recording on the reference array's clock."""
+        self._no_activity_options('enhance_example_activity')
+        rule = pact.ActivityRule() if rule is None else rule
+        obs, ex_array_activity, speaker_id = self._prepare_example(ex)
+        x_hat, act = self.enhance_observation_activity(
+            obs, ex_array_activity, speaker_id, ex=ex, freq_weights=freq_weights)
+        num_samples = np.shape(obs)[-1]
+        active = pact.decide(act.scores, act.power, rule)[act.target_index]
+        intervals = pact.frames_to_intervals(active, self.stft_size, self.stft_shift,
+                                             self.stft_fading, num_samples)
+        keep = self._keep_range(ex)
+        if keep is not None:
+            intervals = pact.clip_intervals(intervals, *keep)
+        window_start, _ = self._audio_span(ex, self._reference_array(ex))
+        intervals = [(window_start + a, window_start + b) for a, b in intervals]
+        return self._trim_context(x_hat, ex), intervals
 
     def enhance_observation_guided(self, obs, frame_guidance, speaker_id, ex=None, *,
                                    initialization=None, debug=False, fused=None,
@@ -1032,13 +1137,15 @@ class Enhancer:
         return speaker_ids
 
     def enhance_observation_speakers(self, obs, ex_array_activity, speaker_ids=None, ex=None,
-                                     debug=False, fused=None, wpe_arrays=None):
+                                     debug=False, fused=None, wpe_arrays=None, *,
+                                     posterior_activity=False):
         """Several speakers of one window from ONE separation: returns dict speaker_id -> x_hat
         (N',) in the order of ``speaker_ids`` (None: every speaker of the activity, the
         garbage tracks left out), each what `enhance_observation` returns for that speaker.
         STFT, WPE and GSS run once; the fused path runs the target-dependent tail of all
         speakers together (gss_enhance_observation_targets), the block path calls
         ``bf_block`` and the iSTFT once per speaker."""
+        self._no_posterior_activity('enhance_observation_speakers', posterior_activity)
         self._no_segments('enhance_observation_speakers')
         self._no_null('enhance_observation_speakers')
         self._no_channel_keep('enhance_observation_speakers')
@@ -1072,9 +1179,10 @@ class Enhancer:
                                                             speaker_ids=speaker_ids)
         return dict(zip(speaker_ids, x_hat))
 
-    def enhance_example_speakers(self, ex, speaker_ids=None):
+    def enhance_example_speakers(self, ex, speaker_ids=None, *, posterior_activity=False):
         """`enhance_example` for several speakers of the example's window at once: dict
         speaker_id -> x_hat, each trimmed like `enhance_example` trims its output."""
+        self._no_posterior_activity('enhance_example_speakers', posterior_activity)
         self._no_segments('enhance_example_speakers')
         self._no_null('enhance_example_speakers')
         self._no_channel_keep('enhance_example_speakers')
@@ -1110,10 +1218,9 @@ class Enhancer:
             Obs = self.wpe_block(Obs, debug=debug)
         return Obs
 
-    def _blocks_front(self, obs, ex_array_activity, ex, debug, wpe_arrays):
-        """The target-independent blocks of the block path: STFT, WPE (joint or per array),
-        activity, GSS and the zeroed context frames.  Returns Obs, acitivity_freq, masks and
-        (start_context_frames, end_context_frames) or None without bf_drop_context."""
+    def _blocks_posterior(self, obs, ex_array_activity, debug, wpe_arrays):
+        """STFT, WPE (joint or per array), activity and GSS of the block path.  Returns Obs,
+        acitivity_freq and the posteriors (K,T,F) as GSS gives them."""
         Obs = self.stft(obs)
         self._selected_channels = None
         if self.channel_keep is not None:
@@ -1125,7 +1232,14 @@ class Enhancer:
             np.array(list(ex_array_activity.values())),
             stft_window_length=self.stft_size, stft_shift=self.stft_shift,
             stft_fading=self.stft_fading, stft_pad=True)
-        masks = self.gss_block(Obs, acitivity_freq, debug=debug)
+        return Obs, acitivity_freq, self.gss_block(Obs, acitivity_freq, debug=debug)
+
+    def _blocks_front(self, obs, ex_array_activity, ex, debug, wpe_arrays, blocks=None):
+        """The target-independent blocks of the block path: `_blocks_posterior` (or its result,
+        ``blocks``) and the zeroed context frames.  Returns Obs, acitivity_freq, masks and
+        (start_context_frames, end_context_frames) or None without bf_drop_context."""
+        Obs, acitivity_freq, masks = blocks or self._blocks_posterior(
+            obs, ex_array_activity, debug, wpe_arrays)
         if self.bf_drop_context:
             start_context_frames, end_context_frames = start_end_context_frames(
                 ex, stft_size=self.stft_size, stft_shift=self.stft_shift,
@@ -1137,11 +1251,12 @@ class Enhancer:
         return Obs, acitivity_freq, masks, None
 
     def _enhance_observation_blocks(self, obs, ex_array_activity, speaker_id, ex, debug,
-                                    wpe_arrays=1):
+                                    wpe_arrays=1, blocks=None):
         """Block-by-block path with the reference's control flow (one device
-        round trip per block); used when a block was swapped out."""
+        round trip per block); used when a block was swapped out.  ``blocks``: the result of
+        `_blocks_posterior` when the caller has run it already."""
         Obs, acitivity_freq, masks, context_frames = self._blocks_front(
-            obs, ex_array_activity, ex, debug, wpe_arrays)
+            obs, ex_array_activity, ex, debug, wpe_arrays, blocks)
         if self._selected_channels is not None:
             selected_channels = self._selected_channels
         if context_frames is not None:

@@ -55,8 +55,11 @@ class Enhancer(core.Enhancer):
             context_samples=self.context_samples, equal_start_context=False)
 
     def enhance_session(self, session_ids, audio_dir, dataset_slice=False,
-                        audio_dir_exist_ok=False):
+                        audio_dir_exist_ok=False, refined_rttm=False):
+        """``refined_rttm``: see `core.Enhancer.enhance_session`."""
         from pb_chime5_amd import parallel
+        if refined_rttm:
+            self._no_activity_options('enhance_session(refined_rttm=True)')
         audio_dir = Path(audio_dir)
         it = self.get_dataset(session_ids)
         if parallel.is_master():
@@ -77,7 +80,8 @@ class Enhancer(core.Enhancer):
         costs = [ex['num_samples'] for ex in it.examples]
         indices = parallel.split_managed(range(len(it)), costs=costs)
         # the examples travel without audio; _prepare_example reads it (on the loader thread)
-        self._enhance_and_write((dict(it.examples[index]) for index in indices), audio_dir)
+        self._enhance_and_write((dict(it.examples[index]) for index in indices), audio_dir,
+                                refined_rttm=refined_rttm)
         parallel.barrier()      # (split_managed ends without one; the pipeline has drained)
 
     def _prepare_example(self, ex, dtype=np.float64):
@@ -110,6 +114,13 @@ class Enhancer(core.Enhancer):
             return None
         keep_from = ex['start_orig'] - ex['start']
         return keep_from, keep_from + ex['num_samples_orig']
+
+    # one clock and no array level: an RTTM example names no reference array
+    def _reference_array(self, ex):
+        return None
+
+    def _audio_span(self, ex, array=None):
+        return ex['start'], ex['end']
 
 
 def get_database(chime6_dir, rttm, multiarray):

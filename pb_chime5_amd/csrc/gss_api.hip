@@ -1045,6 +1045,31 @@ extern "C" int gss_last_selected_channels(gss_ctx *ctx, int32_t *channels, int n
     return GSS_OK;
 }
 
+// The argument rules of the posterior activity (include/gss_hip.h), shared by both entries.
+static int check_activity_sizes(gss_ctx *ctx, int K, int D, const char *what) {
+    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_MAX_CLASSES, GSS_ERR_INVALID, "%s: K=%d outside [1, %d]",
+                what, K, GSS_MAX_CLASSES);
+    GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_INVALID, "%s: D=%d outside [1, %d]",
+                what, D, GSS_MAX_CHANNELS);
+    return GSS_OK;
+}
+
+extern "C" int gss_posterior_activity(gss_ctx *ctx, const gss_cplx *Y, const double *gamma, int F,
+                                      int K, int64_t T, int D, const double *freq_weights,
+                                      double *scores, double *power) {
+    GSS_ENTER(ctx);
+    const char *what = "gss_posterior_activity";
+    GSS_REQUIRE(ctx, Y, GSS_ERR_INVALID, "%s: Y_dev is NULL", what);
+    GSS_REQUIRE(ctx, gamma, GSS_ERR_INVALID, "%s: gamma_dev is NULL", what);
+    GSS_REQUIRE(ctx, scores, GSS_ERR_INVALID, "%s: scores_dev is NULL", what);
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F=%d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, T >= 1, GSS_ERR_INVALID, "%s: T=%lld is smaller than 1", what, (long long)T);
+    GSS_TRY(check_activity_sizes(ctx, K, D, what));
+    GSS_TRY(arena_reserve(ctx, pact_workspace_bytes(F, T, K)));
+    return pact_run(ctx, reinterpret_cast<const cplx *>(Y), gamma, F, K, T, D, freq_weights,
+                    scores, power);
+}
+
 extern "C" int gss_selftest_mfma(gss_ctx *ctx) {
     GSS_ENTER(ctx);
     return selftest_mfma_run(ctx);
@@ -1136,10 +1161,11 @@ static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, in
 // (segment_frames > 0: the segment-wise beamformer in the place of the whole-window one; lcmv:
 // the interferer-nulling one, with four mask buffers;
 // select_bands > 0: D is the number of channels kept out of select_D, and the selection stage
-// needs its own workspace and, when it gathers, the STFT of all select_D channels)
+// needs its own workspace and, when it gathers, the STFT of all select_D channels;
+// activity: the posterior activity runs between the front and the masks)
 static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
                                  int K, int64_t segment_frames = 0, int select_bands = 0,
-                                 int select_D = 0, bool lcmv = false) {
+                                 int select_D = 0, bool lcmv = false, bool activity = false) {
     size_t b = front_buffer_bytes(F, T, T_act, D, K);
     b += (lcmv ? 4 : 2) * align_up(sizeof(double) * (size_t)F * T);   // masks (LCMV: X, I, N, I + N)
     b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
@@ -1152,6 +1178,7 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
         stage = std::max(stage, std::max(lcmv_workspace_bytes(F, T, D),
                                          lcmv_masks_workspace_bytes(F, K)));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
+    if (activity) stage = std::max(stage, pact_workspace_bytes(F, T, K));   // the partial planes
     if (select_bands > 0)
         stage = std::max(stage, chsel_workspace_bytes(F, T, select_D, select_bands) +
                                     (select_D > D ? align_up(sizeof(cplx) * (size_t)F * T * select_D)
@@ -1297,6 +1324,13 @@ static int copy_front_taps(gss_ctx *ctx, const gss_debug_taps *taps, const Pipel
     return GSS_OK;
 }
 
+// What gss_enhance_observation_activity adds to the call: the posterior activity of the
+// pipeline's own X and gamma (weights (F,) or NULL, scores (K,T), power (T) or NULL).
+struct PipelineActivity {
+    const double *weights;
+    double *scores, *power;
+};
+
 static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const void *obs,
                                     int obs_type, int D, int64_t N, const uint8_t *act, int K,
                                     int64_t N_act, int target, int64_t start_ctx, int64_t end_ctx,
@@ -1306,7 +1340,8 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
                                     const gss_bf_segments *seg = nullptr,
                                     const gss_channel_select *sel = nullptr,
                                     bool select = false,
-                                    const gss_bf_lcmv *lcmv = nullptr) {
+                                    const gss_bf_lcmv *lcmv = nullptr,
+                                    const PipelineActivity *pact = nullptr) {
     GSS_REQUIRE(ctx, !guided || guidance, GSS_ERR_INVALID,
                 "gss_enhance_observation_guided: guidance is NULL");
     GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, guided ? (const void *)guidance : act, out,
@@ -1348,7 +1383,7 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K,
                                                   seg ? seg->segment_frames : 0,
                                                   select ? sel->bands : 0, D_all,
-                                                  lcmv != nullptr)));
+                                                  lcmv != nullptr, pact != nullptr)));
     PipelineFront fr;
     GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
     double *mx = arena_alloc_t<double>(ctx, (size_t)F * T);
@@ -1364,6 +1399,10 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     GSS_TRY(run_front(ctx, p, obs, obs_type, D, N, act, K, N_act, F, T, T_act, fr, mark,
                       guided ? &guide : nullptr, select ? sel : nullptr, D_all));
     cplx *const X = fr.X;
+    if (pact) {     // (reads X and gamma, writes the caller's buffers only)
+        GSS_TRY(pact_run(ctx, X, fr.gamma, F, K, T, D, pact->weights, pact->scores, pact->power));
+        ctx->arena_off = mark;
+    }
 
     int64_t sf = 0, ef = 0;
     if (p->bf_drop_context) {
@@ -1545,6 +1584,28 @@ extern "C" int gss_enhance_observation_lcmv(gss_ctx *ctx, const gss_params *p, c
     return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
                                     out, taps, /*guided=*/false, nullptr, nullptr, nullptr, false,
                                     lcmv);
+}
+
+extern "C" int gss_enhance_observation_activity(gss_ctx *ctx, const gss_params *p,
+                                                const double *obs, int D, int64_t N,
+                                                const uint8_t *act, int K, int64_t N_act,
+                                                int target, int64_t start_ctx, int64_t end_ctx,
+                                                const double *freq_weights, double *out,
+                                                double *scores, double *power,
+                                                const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *what = "gss_enhance_observation_activity";
+    GSS_REQUIRE(ctx, p, GSS_ERR_INVALID, "%s: params is NULL", what);
+    GSS_REQUIRE(ctx, obs, GSS_ERR_INVALID, "%s: obs_dev is NULL", what);
+    GSS_REQUIRE(ctx, act, GSS_ERR_INVALID, "%s: act_dev is NULL", what);
+    GSS_REQUIRE(ctx, out, GSS_ERR_INVALID, "%s: out_dev is NULL", what);
+    GSS_REQUIRE(ctx, scores, GSS_ERR_INVALID, "%s: scores_dev is NULL", what);
+    GSS_REQUIRE(ctx, N >= 1, GSS_ERR_INVALID, "%s: N=%lld is smaller than 1", what, (long long)N);
+    GSS_TRY(check_activity_sizes(ctx, K, D, what));
+    const PipelineActivity pact{freq_weights, scores, power};
+    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, /*guided=*/false, nullptr, nullptr, nullptr, false,
+                                    nullptr, &pact);
 }
 
 extern "C" int gss_enhance_observation_pcm16(gss_ctx *ctx, const gss_params *p,

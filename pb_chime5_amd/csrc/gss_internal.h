@@ -399,6 +399,13 @@ int chsel_scores_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
 int chsel_select_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
                      const gss_channel_select &sel, cplx *Ysel, int32_t *channels);
 
+// Posterior activity (posterior_activity.hip; include/gss_hip.h: gss_posterior_activity): Y (F,T,D)
+// and gamma (F,K,T) -> scores (K,T) and, unless NULL, power (T); W (F,) frequency weights or NULL
+// for ones.  The partial planes come from the arena (pact_workspace_bytes).
+size_t pact_workspace_bytes(int F, int64_t T, int K);
+int pact_run(gss_ctx *ctx, const cplx *Y, const double *gamma, int F, int K, int64_t T, int D,
+             const double *W, double *scores, double *power);
+
 int selftest_mfma_run(gss_ctx *ctx);
 
 // Shared device routine: cyclic-Jacobi eigendecomposition of Hermitian matrices

@@ -19,6 +19,9 @@ here                        reference call (file:line)
 ``channel_scores`` / ``select_channels`` / ``enhance_observation_select``
                             envelope-variance channel selection ahead of WPE (not in the
                             reference, which picks microphones by position)
+``posterior_activity`` / ``enhance_observation_activity``
+                            the power-weighted share of every frame that the posteriors give
+                            each class (not in the reference)
 =========================  ====================================================
 
 All of them raise if libgss_hip.so or a GPU is missing.
@@ -987,6 +990,114 @@ def enhance_observation_select(obs, activity, target_index, start_context_sample
 
 
 # --------------------------------------------------------------------------
+# posterior activity
+# --------------------------------------------------------------------------
+def check_freq_weights(freq_weights, num_frequencies):
+    """The frequency weights of the posterior activity as a float64 (F,) array, or None for all
+    ones.  ValueError for another shape and for negative or non-finite values (the library does
+    not inspect the table)."""
+    if freq_weights is None:
+        return None
+    try:
+        if np.iscomplexobj(freq_weights):
+            raise TypeError
+        w = np.asarray(freq_weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('freq_weights: not an array of real numbers') from None
+    if w.shape != (int(num_frequencies),):
+        raise ValueError(f'freq_weights: shape {w.shape} is not ({int(num_frequencies)},)')
+    if not np.all(np.isfinite(w)):
+        raise ValueError('freq_weights: not finite')
+    if np.any(w < 0):
+        raise ValueError('freq_weights: negative')
+    return np.ascontiguousarray(w)
+
+
+def check_posterior_activity_args(Obs, posterior, freq_weights=None):
+    """Obs (D,T,F) complex, posterior (K,T,F) and the weights of `posterior_activity` as arrays;
+    ValueError for anything else, before any device work."""
+    Obs, posterior = np.asarray(Obs), np.asarray(posterior)
+    if Obs.ndim != 3:
+        raise ValueError(f'Obs: shape {Obs.shape} is not (D,T,F)')
+    if posterior.ndim != 3:
+        raise ValueError(f'posterior: shape {posterior.shape} is not (K,T,F)')
+    if 0 in Obs.shape or 0 in posterior.shape:
+        raise ValueError(f'Obs {Obs.shape}, posterior {posterior.shape}: an empty axis')
+    if Obs.shape[1:] != posterior.shape[1:]:
+        raise ValueError(f'Obs (D,T,F) = {Obs.shape} and posterior (K,T,F) = {posterior.shape} '
+                         'differ in T or F')
+    return Obs, posterior, check_freq_weights(freq_weights, Obs.shape[2])
+
+
+def posterior_activity(Obs, posterior, freq_weights=None, return_power=False, *, ctx=None):
+    """The power-weighted share of every frame that the posteriors give each class
+    (gss_posterior_activity): Obs (D,T,F) complex -- the signal the EM saw, i.e. after WPE --,
+    posterior (K,T,F) -> scores (K,T) float64,
+
+        score[k,t] = sum_f w[f] posterior[k,t,f] p[t,f] / power[t],   p = sum_d |Obs|^2,
+        power[t] = sum_f w[f] p[t,f]          (score 0 where power[t] is 0),
+
+    in [0, 1] up to rounding, not clamped.  ``freq_weights`` (F,) >= 0, None: all ones.  With
+    ``return_power`` also power (T,).  The measure is written down in
+    tests/posterior_activity_reference.py; `pb_chime5_amd.posterior_activity.decide` turns the
+    scores into a decision.  Argument errors are ValueError before any device work."""
+    Obs, posterior, w = check_posterior_activity_args(Obs, posterior, freq_weights)
+    ctx = ctx or default_context()
+    Y_d, (D, T, F) = _obs_to_device_ftd(ctx, Obs)
+    K = posterior.shape[0]
+    g_d = ctx.to_device(np.ascontiguousarray(
+        np.asarray(posterior, dtype=np.float64).transpose(2, 0, 1)))
+    w_d = ctx.to_device(w) if w is not None else None
+    s_d = ctx.empty(8 * K * T)
+    p_d = ctx.empty(8 * T) if return_power else None
+    ctx._check(ctx.lib.gss_posterior_activity(
+        ctx.handle, c_void_p(Y_d.ptr), c_void_p(g_d.ptr), F, K, T, D,
+        c_void_p(w_d.ptr) if w_d is not None else None, c_void_p(s_d.ptr),
+        c_void_p(p_d.ptr) if p_d is not None else None), 'gss_posterior_activity')
+    scores = ctx.to_host(s_d, (K, T), np.float64)
+    if return_power:
+        return scores, ctx.to_host(p_d, (T,), np.float64)
+    return scores
+
+
+def enhance_observation_activity(obs, activity, target_index, start_context_samples,
+                                 end_context_samples, *, freq_weights=None, params=None,
+                                 window=None, debug=False, ctx=None, wpe_arrays=None,
+                                 **param_kwargs):
+    """`enhance_observation` plus `posterior_activity` of the pipeline's own post-WPE observation
+    and its posteriors before context zeroing, in one call and without copying either
+    (gss_enhance_observation_activity).  Returns (x_hat, scores (K,T), power (T,)), or
+    (x_hat, scores, power, details) with ``debug=True``; x_hat and the details have the bits of
+    `enhance_observation`.  ``freq_weights`` (stft_size // 2 + 1,) >= 0, None: all ones; a bad
+    table is ValueError before any device work."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    w = check_freq_weights(freq_weights, params.stft_size // 2 + 1)
+    obs = np.asarray(obs)
+    if obs.ndim != 2:
+        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    params = params_for(params, obs.shape[0], wpe_arrays)
+    ctx = ctx or default_context()
+    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
+    utt = ResidentUtterance(ctx, obs, activity, params)
+    bufs, taps = _debug_taps(utt) if debug else ({}, None)
+    w_d = ctx.to_device(w) if w is not None else None
+    s_d = ctx.empty(8 * utt.K * max(utt.T, 1))
+    p_d = ctx.empty(8 * max(utt.T, 1))
+    utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
+                activity=(w_d, s_d, p_d))
+    x_hat = utt.result()
+    scores = ctx.to_host(s_d, (utt.K, utt.T), np.float64)
+    power = ctx.to_host(p_d, (utt.T,), np.float64)
+    if not debug:
+        return x_hat, scores, power
+    details = _debug_details(utt, bufs)
+    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+    details['ref_channel'] = int(details['ref_channel'])
+    return x_hat, scores, power, details
+
+
+# --------------------------------------------------------------------------
 # fused pipeline
 # --------------------------------------------------------------------------
 def make_params(*, stft_size=1024, stft_shift=256, stft_fading=True, wpe=True, wpe_taps=10,
@@ -1047,14 +1158,31 @@ class ResidentUtterance:
         self.out_d = ctx.empty(8 * max(self.n_out, 1))
 
     def enqueue(self, target_index, start_context, end_context, taps=None, segments=None,
-                channel_select=None, lcmv=None):
+                channel_select=None, lcmv=None, activity=None):
         """``segments``: a gss_bf_segments (`check_bf_segments`) for the segment-wise
         beamformer (gss_enhance_observation_segments; float64 samples only).
         ``channel_select``: a `ChannelSelect` for the envelope-variance selection ahead of WPE
         (gss_enhance_observation_select / its pcm16 twin; not together with segments).
         ``lcmv``: a gss_bf_lcmv (`check_bf_lcmv`) for the interferer-nulling beamformer
-        (gss_enhance_observation_lcmv; float64 samples only, on its own)."""
+        (gss_enhance_observation_lcmv; float64 samples only, on its own).
+        ``activity``: device buffers (weights (F,) or None, scores (K,T), power (T,) or None) for
+        the posterior activity of the call's own observation and posteriors
+        (gss_enhance_observation_activity; float64 samples only, on its own)."""
         ctx = self.ctx
+        if activity is not None:
+            assert segments is None and channel_select is None and lcmv is None, \
+                'the activity call stands alone'
+            assert not self.pcm, 'the activity call has no pcm16 twin'
+            w_d, s_d, p_d = activity
+            ctx._check(ctx.lib.gss_enhance_observation_activity(
+                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D, self.N,
+                c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
+                int(start_context), int(end_context),
+                c_void_p(w_d.ptr) if w_d is not None else None, c_void_p(self.out_d.ptr),
+                c_void_p(s_d.ptr), c_void_p(p_d.ptr) if p_d is not None else None,
+                ctypes.byref(taps) if taps is not None else None),
+                'gss_enhance_observation_activity')
+            return
         if lcmv is not None:
             assert segments is None and channel_select is None, 'the LCMV call stands alone'
             assert not self.pcm, 'the LCMV call has no pcm16 twin'

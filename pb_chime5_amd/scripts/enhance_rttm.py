@@ -56,6 +56,10 @@ def main(argv=None):
                          '(20) or a share (0.8) (get_enhancer(channel_keep=...))')
     ap.add_argument('--channel-bands', type=int, default=40,
                     help='mel filters of the channel selection')
+    ap.add_argument('--refined-rttm', action='store_true',
+                    help='also write <example_id>.rttm next to every WAV: where inside the '
+                         'segment the posteriors give the speaker the power '
+                         '(enhance_session(refined_rttm=True); one utterance at a time)')
     ap.add_argument('--no-bf-drop-context', action='store_true')
     ap.add_argument('--job-id', type=int, default=1)
     ap.add_argument('--number-of-jobs', type=int, default=1)
@@ -86,8 +90,9 @@ def main(argv=None):
         dataset_slice = slice(args.job_id - 1, None, args.number_of_jobs)
     else:
         dataset_slice = False
+    extra = {'refined_rttm': True} if args.refined_rttm else {}
     enhancer.enhance_session(args.session_id, Path(args.out) / 'audio',
-                             dataset_slice=dataset_slice, audio_dir_exist_ok=True)
+                             dataset_slice=dataset_slice, audio_dir_exist_ok=True, **extra)
     if parallel.is_master():
         print(f'Finished: {Path(args.out) / "audio"}')
 
