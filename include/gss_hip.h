@@ -85,7 +85,9 @@ typedef enum {
  * their layouts, revision still 7.  So were gss_cacgmm_fit and gss_cacgmm_predict with the
  * gss_cacgmm_model descriptor.  So were gss_lcmv_souden, gss_lcmv_masks_from_posteriors,
  * gss_enhance_observation_lcmv, gss_last_lcmv_interferer and gss_last_lcmv_fallbacks with the
- * gss_bf_lcmv descriptor.  So were gss_posterior_activity and gss_enhance_observation_activity. */
+ * gss_bf_lcmv descriptor.  So were gss_posterior_activity and gss_enhance_observation_activity.
+ * So were gss_wpe_weighted, gss_wpd_weights, gss_wpd_souden, gss_last_wpd_zero_pivots and
+ * gss_enhance_observation_wpd with the gss_bf_wpd descriptor. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -456,6 +458,78 @@ int gss_last_lcmv_interferer(gss_ctx *ctx, int32_t *interferer_host);
  * any. */
 int gss_last_lcmv_fallbacks(gss_ctx *ctx, int64_t *count_host);
 
+/* One WPE step -- correlation, solve, filter application -- with weights from the caller in
+ * the place of the inverse power of the observation: R = sum_t w_t yt_t yt_t^H,
+ * P = sum_t w_t yt_t y_t^H, X = Y - solve(R, P)^H yt.  Y (F,T,D), weights (F,T) -> X (F,T,D); X
+ * must not alias Y.  The launches are those of one gss_wpe iteration without its power pass:
+ * fed with the output of gss_wpe_inverse_power(psd_context = 0) it gives the bits of
+ * gss_wpe(iterations = 1, psd_context = 0).  The weights are not inspected.  The zeroed pivots
+ * are reported by gss_last_wpe_zero_pivots, as for gss_wpe.
+ * GSS_ERR_INVALID: a NULL pointer, F < 1, T < 1, taps < 1, delay < 0. */
+int gss_wpe_weighted(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D, int taps,
+                     int delay, const double *weights_dev, gss_cplx *X_dev);
+
+/* WPD convolutional beamformer (weighted power minimisation distortionless response: Nakatani &
+ * Kinoshita 2019, "A unified convolutional beamformer for simultaneous denoising and
+ * dereverberation"; Boeddeker, Nakatani, Kinoshita, Haeb-Umbach 2020, "Jointly optimal
+ * dereverberation and beamforming"; not in the reference): ONE filter over the current frame and
+ * the WPE tap window, optimised under the time-varying power of the target, computed in its
+ * exact factorisation into a WPE step and a weighted-power MPDR. */
+typedef struct {
+    int taps, delay, iterations, ban;
+                           /* taps >= 1, delay >= 0: the tap window of the WPE step;            */
+                           /* iterations >= 1; ban: blind analytic normalisation against Phi_a  */
+    double power_floor;    /* in (0, 1], finite: the target power is floored at this fraction   */
+                           /* of its maximum over the frames the gate keeps.  1e-3 in the       */
+                           /* Python layer: a choice, not a measurement                         */
+} gss_bf_wpd;
+
+/* The weights of one WPD iteration on their own (a stage entry point for checking them).  With
+ * the gate g (T) uint8, nonzero = 1, NULL = all ones:
+ *    p_t = mask[f,t] * mean_d |Y[f,t,d]|^2      (Xhat_dev == NULL: the first iteration), or
+ *    p_t = |Xhat[t,f]|^2                        (Xhat_dev != NULL: later ones; Y_dev, mask_dev
+ *                                                are not read and may be NULL);
+ *    p_max = max over the frames with g_t = 1 of p_t (fixed order, no atomics);
+ *    a_t = g_t / max(p_t, power_floor * p_max);  a_t = 0 for every t where p_max = 0.
+ * Y (F,T,D) + mask (F,T), or Xhat (T,F) -> weights (F,T).
+ * GSS_ERR_INVALID (the message names the argument), before any launch: weights_dev NULL, both
+ * sources NULL, F < 1, T < 1, D outside [1, 30), power_floor outside (0, 1] or not finite. */
+int gss_wpd_weights(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                    const double *mask_dev, const gss_cplx *Xhat_dev, const uint8_t *gate_dev,
+                    double power_floor, double *weights_dev);
+
+/* The WPD beamformer from a target mask.  Per frequency and iteration i = 1 .. iterations:
+ *    a = the weights of gss_wpd_weights (i = 1: from Y and the target mask; i > 1: from the
+ *        Xhat of iteration i - 1), with wpd->power_floor and the gate;
+ *    Z = gss_wpe_weighted(Y, taps, delay, a)            (the WPE solve, zero-pivot semantics);
+ *    Xhat = what gss_mvdr_souden computes for the observation Z, the target mask m * g and the
+ *        "distortion mask" a: Phi_X = sum m g z z^H / max(sum m g, 1e-10),
+ *        Phi_a = sum a z z^H / max(sum a, 1e-10), Souden with eps 1e-10, ONE reference channel
+ *        for all frequencies -- the SNR argmax, chosen anew in every iteration, or ref_channel
+ *        >= 0 as named by the caller (-1: choose) --, `ban` against Phi_a.
+ * Phi_X is taken from Z, not from Y: the filter C w on the stacked observation [y; yt] with
+ * C = [I; -G] sees the target covariance C^H Phibar_X C, which is the covariance of z.  A frame
+ * with g_t = 0 (the context frames of the fused call) enters no statistic, so the mask there does
+ * not matter; the filter is still applied to it.  A frequency with p_max = 0 gives what the MVDR
+ * gives for two all-zero masks: Xhat = 0, or NaN under `ban` (0 / 0).
+ * Y (F,T,D), target_mask (F,T), gate (T) uint8 or NULL -> Xhat (T,F); ref_channel_dev (device
+ * int32, may be NULL) receives the status word of gss_last_ref_channel, which works after this
+ * call (-1: non-finite SNR, Xhat filled with NaN).  The pivots the WPE steps zeroed are counted
+ * in a word of their own, gss_last_wpd_zero_pivots; gss_last_wpe_zero_pivots keeps the WPE
+ * stage's count.
+ * GSS_ERR_INVALID (the message names the field), before any launch: a NULL pointer (Y_dev,
+ * target_mask_dev, wpd, Xhat_dev), taps < 1, delay < 0, iterations < 1, power_floor outside
+ * (0, 1] or not finite, D >= 30, ref_channel outside [-1, D). */
+int gss_wpd_souden(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                   const double *target_mask_dev, const uint8_t *gate_dev,
+                   const gss_bf_wpd *wpd, int ref_channel, gss_cplx *Xhat_dev,
+                   int32_t *ref_channel_dev);
+
+/* Number of pivots the WPE steps of the last gss_wpd_souden / gss_enhance_observation_wpd call
+ * on this context zeroed, summed over its iterations and frequencies (synchronises the stream,
+ * like gss_last_wpe_zero_pivots); 0 before any. */
+int gss_last_wpd_zero_pivots(gss_ctx *ctx, int64_t *count_host);
+
 /* beamform_gev_from_masks (beamforming_wrapper.py:77-89,192-208): masked PSD
  * matrices, principal generalised eigenvector of (Phi_X, Phi_N) with
  * w^H Phi_N w = 1 (phase arbitrary, as upstream), optional BAN, apply.
@@ -632,6 +706,24 @@ int gss_enhance_observation_lcmv(gss_ctx *ctx, const gss_params *params,
                                  int64_t end_context_samples,
                                  const gss_bf_lcmv *lcmv,
                                  double *out_dev, const gss_debug_taps *taps);
+
+/* gss_enhance_observation with the WPD beamformer in the place of the MVDR: STFT -> WPE as
+ * configured -> frame activity -> CACGMM -> gss_masks_from_posteriors -> gss_wpd_souden ON THE
+ * STFT BEFORE WPE (kept beside the WPE output, which only feeds the mixture model), with the
+ * gate 0 on the context frames that bf_drop_context zeroes (NULL without it), `ban` and the
+ * other settings from `wpd`, the reference channel chosen -> postfilter -> iSTFT.  The taps
+ * keep their meaning: Obs_ftd is the input of the mixture model (after WPE), distortion_mask
+ * as in gss_enhance_observation (the WPD does not read it).  gss_last_ref_channel and
+ * gss_last_wpd_zero_pivots work afterwards; gss_last_wpe_zero_pivots is the WPE stage's count.
+ * params->bf must be 0: GSS_ERR_UNSUPPORTED otherwise.  Errors of `wpd` as gss_wpd_souden. */
+int gss_enhance_observation_wpd(gss_ctx *ctx, const gss_params *params,
+                                const double *obs_dev, int D, int64_t N,
+                                const uint8_t *act_dev, int K, int64_t N_act,
+                                int target_index,
+                                int64_t start_context_samples,
+                                int64_t end_context_samples,
+                                const gss_bf_wpd *wpd,
+                                double *out_dev, const gss_debug_taps *taps);
 
 /* gss_enhance_observation plus gss_posterior_activity on the pipeline's own post-WPE observation
  * and its posteriors before context zeroing (what the taps Obs_ftd and gamma show), nothing

@@ -63,6 +63,12 @@ class GssBfLcmv(ctypes.Structure):
                 ('min_mass', ctypes.c_double)]
 
 
+class GssBfWpd(ctypes.Structure):
+    """gss_bf_wpd: the tap window, iterations, BAN and power floor of the WPD beamformer."""
+    _fields_ = [('taps', c_int), ('delay', c_int), ('iterations', c_int), ('ban', c_int),
+                ('power_floor', ctypes.c_double)]
+
+
 class GssChannelSelect(ctypes.Structure):
     """gss_channel_select: the band table and the settings of the envelope-variance channel
     selection."""
@@ -137,6 +143,17 @@ SIGNATURES = {
                 c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     'gss_last_lcmv_interferer': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_lcmv_fallbacks': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'gss_wpe_weighted': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int,
+                                 c_void_p, c_void_p]),
+    'gss_wpd_weights': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
+                                c_void_p, ctypes.c_double, c_void_p]),
+    'gss_wpd_souden': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
+                               ctypes.POINTER(GssBfWpd), c_int, c_void_p, c_void_p]),
+    'gss_last_wpd_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'gss_enhance_observation_wpd': (
+        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
+                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
+                ctypes.POINTER(GssBfWpd), c_void_p, ctypes.POINTER(GssDebugTaps)]),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,
@@ -457,6 +474,14 @@ class Context:
         out = ctypes.c_int64()
         self._check(self.lib.gss_last_wpe_zero_pivots(self.handle, ctypes.byref(out)),
                     'gss_last_wpe_zero_pivots')
+        return int(out.value)
+
+    def last_wpd_zero_pivots(self):
+        """Pivots the WPE steps of the last WPD call zeroed (synchronises); the WPE stage's own
+        count stays in `last_wpe_zero_pivots`."""
+        out = ctypes.c_int64()
+        self._check(self.lib.gss_last_wpd_zero_pivots(self.handle, ctypes.byref(out)),
+                    'gss_last_wpd_zero_pivots')
         return int(out.value)
 
     def last_segment_fallbacks(self):

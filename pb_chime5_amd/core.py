@@ -250,8 +250,19 @@ class Beamformer:
     # 'mvdrSouden_ban' has it, and not together with segments.
     null_interferer: bool = False
     null_min_mass: float = None
+    # WPD convolutional beamformer (types 'wpdSouden' / 'wpdSouden_ban'; an addition, see
+    # ops.wpd_souden_from_masks): the tap window, the iterations and the floor of the target
+    # power.  Unread by the other types.  wpd_power_floor = 1e-3 is a choice, not a measurement.
+    wpd_taps: int = 10
+    wpd_delay: int = 2
+    wpd_iterations: int = 1
+    wpd_power_floor: float = ops.WPD_POWER_FLOOR
 
     def __post_init__(self):
+        if self.type in ops.WPD_BF_TYPES:
+            ops.check_bf_wpd(self.wpd_taps, self.wpd_delay, self.wpd_iterations,
+                             self.wpd_power_floor, segment_frames=self.segment_frames,
+                             null_interferer=self.null_interferer)
         if self.null_interferer:
             if self.type != 'mvdrSouden_ban':
                 raise NotImplementedError(
@@ -284,12 +295,33 @@ class Beamformer:
         return dict(segment_frames=self.segment_frames, segment_context=self.segment_context,
                     min_mass=self.segment_min_mass)
 
+    @property
+    def wpd(self):
+        """The keyword arguments of the WPD calls in ``ops`` (types 'wpdSouden' /
+        'wpdSouden_ban'), or None."""
+        if self.type not in ops.WPD_BF_TYPES:
+            return None
+        return dict(taps=self.wpd_taps, delay=self.wpd_delay, iterations=self.wpd_iterations,
+                    power_floor=self.wpd_power_floor, ban=ops.WPD_BF_TYPES[self.type])
+
     def __call__(self, Obs, target_mask, distortion_mask, debug=False, *, interferer_mask=None,
-                 noise_mask=None):
+                 noise_mask=None, raw_obs=None, frame_gate=None):
         """``interferer_mask`` (with ``null_interferer``): the competing talker's mask, a part
-        of ``distortion_mask``; ``noise_mask``: the rest of it (None: their difference)."""
+        of ``distortion_mask``; ``noise_mask``: the rest of it (None: their difference).
+        ``raw_obs`` (the WPD types): the STFT before WPE, which the WPD dereverberates itself
+        (None: ``Obs``); ``frame_gate`` (T,) of 0 / 1: frames outside its statistics."""
         bf = self.type
-        if self.null_interferer:
+        if self.wpd is not None:
+            if interferer_mask is not None or noise_mask is not None:
+                raise ValueError('interferer_mask / noise_mask without null_interferer')
+            from pb_chime5_amd.speech_enhancement.beamforming_wrapper import (
+                beamform_wpd_souden_from_masks)
+            X_hat = beamform_wpd_souden_from_masks(
+                Obs if raw_obs is None else raw_obs, target_mask, frame_gate=frame_gate,
+                **self.wpd)
+        elif raw_obs is not None or frame_gate is not None:
+            raise ValueError(f'raw_obs / frame_gate with bf={bf!r}: only the WPD types read them')
+        elif self.null_interferer:
             if interferer_mask is None:
                 raise ValueError('null_interferer: the beamformer needs interferer_mask')
             if noise_mask is None:
@@ -377,6 +409,8 @@ class Enhancer:
     channel_bands: int = 40
 
     def __post_init__(self):
+        if self._bf_wpd() is not None:      # (the one place that validates; raises for combinations)
+            ops.check_bf_wpd(**self._bf_wpd(), channel_keep=self.channel_keep)
         if self.channel_keep is None:
             return
         ops.check_channel_keep(self.channel_keep)
@@ -537,8 +571,9 @@ class Enhancer:
         other's compute-bound ones.  Results are identical to the one-at-a-time loop."""
         # (a segment-wise beamformer has no pipelined pcm16 entry point: one at a time; neither
         # has the posterior activity of a refined RTTM)
+        # (nor has the WPD: the pipelined path is out of its scope)
         if (self.inflight <= 1 or not self._fusable() or self._bf_segments() is not None
-                or refined_rttm):
+                or refined_rttm or self._bf_wpd() is not None):
             for ex in examples:
                 try:
                     if refined_rttm:
@@ -862,11 +897,22 @@ class Enhancer:
                 f'{what} with bf_null_interferer: the interferer-nulling beamformer is built '
                 'for enhance_observation only')
 
+    def _bf_wpd(self):
+        """The WPD settings of the beamformer (``Beamformer.wpd``) or None."""
+        return getattr(getattr(self, 'bf_block', None), 'wpd', None)
+
+    def _no_wpd(self, what):
+        if self._bf_wpd() is not None:
+            raise NotImplementedError(
+                f'{what} with bf={self.bf_block.type!r}: the WPD beamformer is built for '
+                'enhance_observation, enhance_example and enhance_session only')
+
     def _no_activity_options(self, what):
         """The posterior activity is built for the whole-window MVDR on all channels."""
         self._no_segments(what)
         self._no_null(what)
         self._no_channel_keep(what)
+        self._no_wpd(what)
 
     @staticmethod
     def _no_posterior_activity(what, posterior_activity):
@@ -893,7 +939,9 @@ class Enhancer:
             wpe_psd_context=w.psd_context if w else 0,
             bss_iterations=self.gss_block.iterations,
             bss_iterations_post=self.gss_block.iterations_post,
-            bf_drop_context=self.bf_drop_context, bf=self.bf_block.type,
+            bf_drop_context=self.bf_drop_context,
+            # (the WPD travels in a descriptor of its own; its fused call takes the MVDR's code)
+            bf='mvdrSouden_ban' if self._bf_wpd() is not None else self.bf_block.type,
             postfilter=self.bf_block.postfilter)
 
     def enhance_observation(self, obs, ex_array_activity, speaker_id, ex=None,
@@ -922,7 +970,11 @@ class Enhancer:
         segments = self._bf_segments()
         select = self._channel_select()
         try:
-            if self._bf_null():
+            if self._bf_wpd() is not None:
+                res = ops.enhance_observation_wpd(
+                    obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
+                    debug=debug, ctx=ctx, wpe_arrays=wpe_arrays, **self._bf_wpd())
+            elif self._bf_null():
                 res = ops.enhance_observation_lcmv(
                     obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
                     debug=debug, ctx=ctx, wpe_arrays=wpe_arrays,
@@ -1047,6 +1099,7 @@ class Enhancer:
         ``initialization``: optional dict of the same shape with initial affiliations used as
         given (a neural mask estimator's output).  ``fused=False`` runs the blocks."""
         self._no_segments('enhance_observation_guided')
+        self._no_wpd('enhance_observation_guided')
         self._no_null('enhance_observation_guided')
         self._no_channel_keep('enhance_observation_guided')
         if wpe_arrays is None:
@@ -1147,6 +1200,7 @@ class Enhancer:
         ``bf_block`` and the iSTFT once per speaker."""
         self._no_posterior_activity('enhance_observation_speakers', posterior_activity)
         self._no_segments('enhance_observation_speakers')
+        self._no_wpd('enhance_observation_speakers')
         self._no_null('enhance_observation_speakers')
         self._no_channel_keep('enhance_observation_speakers')
         speaker_ids = self.speaker_ids_of(ex_array_activity, speaker_ids)
@@ -1184,6 +1238,7 @@ class Enhancer:
         speaker_id -> x_hat, each trimmed like `enhance_example` trims its output."""
         self._no_posterior_activity('enhance_example_speakers', posterior_activity)
         self._no_segments('enhance_example_speakers')
+        self._no_wpd('enhance_example_speakers')
         self._no_null('enhance_example_speakers')
         self._no_channel_keep('enhance_example_speakers')
         obs, ex_array_activity, _ = self._prepare_example(ex)
@@ -1194,7 +1249,7 @@ class Enhancer:
                                  wpe_arrays=1):
         """Block path of `enhance_observation_speakers`: one STFT / WPE / GSS, then the masks,
         ``bf_block`` and the iSTFT per speaker (`_enhance_observation_blocks` for each)."""
-        Obs, acitivity_freq, masks, _ = self._blocks_front(obs, ex_array_activity, ex, debug,
+        Obs, acitivity_freq, masks, _, _ = self._blocks_front(obs, ex_array_activity, ex, debug,
                                                            wpe_arrays)
         keys = tuple(ex_array_activity.keys())
         out = {}
@@ -1220,8 +1275,9 @@ class Enhancer:
 
     def _blocks_posterior(self, obs, ex_array_activity, debug, wpe_arrays):
         """STFT, WPE (joint or per array), activity and GSS of the block path.  Returns Obs,
-        acitivity_freq and the posteriors (K,T,F) as GSS gives them."""
-        Obs = self.stft(obs)
+        acitivity_freq, the posteriors (K,T,F) as GSS gives them and the STFT before WPE (what a
+        WPD beamformer block works on)."""
+        Obs = raw_obs = self.stft(obs)
         self._selected_channels = None
         if self.channel_keep is not None:
             select = self._channel_select()
@@ -1232,13 +1288,14 @@ class Enhancer:
             np.array(list(ex_array_activity.values())),
             stft_window_length=self.stft_size, stft_shift=self.stft_shift,
             stft_fading=self.stft_fading, stft_pad=True)
-        return Obs, acitivity_freq, self.gss_block(Obs, acitivity_freq, debug=debug)
+        return Obs, acitivity_freq, self.gss_block(Obs, acitivity_freq, debug=debug), raw_obs
 
     def _blocks_front(self, obs, ex_array_activity, ex, debug, wpe_arrays, blocks=None):
         """The target-independent blocks of the block path: `_blocks_posterior` (or its result,
-        ``blocks``) and the zeroed context frames.  Returns Obs, acitivity_freq, masks and
-        (start_context_frames, end_context_frames) or None without bf_drop_context."""
-        Obs, acitivity_freq, masks = blocks or self._blocks_posterior(
+        ``blocks``) and the zeroed context frames.  Returns Obs, acitivity_freq, masks,
+        (start_context_frames, end_context_frames) or None without bf_drop_context, and the STFT
+        before WPE."""
+        Obs, acitivity_freq, masks, raw_obs = blocks or self._blocks_posterior(
             obs, ex_array_activity, debug, wpe_arrays)
         if self.bf_drop_context:
             start_context_frames, end_context_frames = start_end_context_frames(
@@ -1247,15 +1304,16 @@ class Enhancer:
             masks[:, :start_context_frames, :] = 0
             if end_context_frames > 0:
                 masks[:, -end_context_frames:, :] = 0
-            return Obs, acitivity_freq, masks, (start_context_frames, end_context_frames)
-        return Obs, acitivity_freq, masks, None
+            return (Obs, acitivity_freq, masks, (start_context_frames, end_context_frames),
+                    raw_obs)
+        return Obs, acitivity_freq, masks, None, raw_obs
 
     def _enhance_observation_blocks(self, obs, ex_array_activity, speaker_id, ex, debug,
                                     wpe_arrays=1, blocks=None):
         """Block-by-block path with the reference's control flow (one device
         round trip per block); used when a block was swapped out.  ``blocks``: the result of
         `_blocks_posterior` when the caller has run it already."""
-        Obs, acitivity_freq, masks, context_frames = self._blocks_front(
+        Obs, acitivity_freq, masks, context_frames, raw_obs = self._blocks_front(
             obs, ex_array_activity, ex, debug, wpe_arrays, blocks)
         if self._selected_channels is not None:
             selected_channels = self._selected_channels
@@ -1275,6 +1333,17 @@ class Enhancer:
             X_hat = self.bf_block(Obs, target_mask=target_mask, distortion_mask=distortion_mask,
                                   debug=debug, interferer_mask=interferer_mask,
                                   noise_mask=noise_mask)
+        elif self._bf_wpd() is not None:
+            # the raw STFT goes to the beamformer block, with the context frames gated out of its
+            # statistics as the fused call gates them
+            frame_gate = None
+            if context_frames is not None:
+                frame_gate = np.ones(Obs.shape[1], np.uint8)
+                frame_gate[:start_context_frames] = 0
+                if end_context_frames > 0:
+                    frame_gate[-end_context_frames:] = 0
+            X_hat = self.bf_block(Obs, target_mask=target_mask, distortion_mask=distortion_mask,
+                                  debug=debug, raw_obs=raw_obs, frame_gate=frame_gate)
         else:
             X_hat = self.bf_block(Obs, target_mask=target_mask,
                                   distortion_mask=distortion_mask, debug=debug)
@@ -1282,6 +1351,22 @@ class Enhancer:
         if debug:
             self.enhance_observation_locals = locals()
         return x_hat
+
+
+def bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps=None, bf_wpd_delay=None,
+                    bf_wpd_iterations=1, bf_wpd_power_floor=ops.WPD_POWER_FLOOR):
+    """The ``wpd_*`` fields of `Beamformer` from the ``bf_wpd_*`` keywords of the
+    ``get_enhancer`` functions: taps / delay None mean the WPE block's.  Settings other than the
+    defaults with a ``bf`` that is no WPD type are a combination nobody reads:
+    NotImplementedError."""
+    if bf not in ops.WPD_BF_TYPES:
+        if (bf_wpd_taps is not None or bf_wpd_delay is not None or bf_wpd_iterations != 1
+                or bf_wpd_power_floor != ops.WPD_POWER_FLOOR):
+            ops.check_bf_wpd(bf=bf)
+        return {}
+    return dict(wpd_taps=wpe_tabs if bf_wpd_taps is None else bf_wpd_taps,
+                wpd_delay=wpe_delay if bf_wpd_delay is None else bf_wpd_delay,
+                wpd_iterations=bf_wpd_iterations, wpd_power_floor=bf_wpd_power_floor)
 
 
 def get_enhancer(
@@ -1324,10 +1409,23 @@ def get_enhancer(
     channel_bands=40,
     bf_null_interferer=False,
     bf_null_min_mass=None,
+    bf_wpd_taps=None,
+    bf_wpd_delay=None,
+    bf_wpd_iterations=1,
+    bf_wpd_power_floor=ops.WPD_POWER_FLOOR,
 ):
     """core.py:574-637 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*`` and
-    ``bf_null_*`` are additions).
+    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*``,
+    ``bf_null_*`` and ``bf_wpd_*`` are additions).
+    ``bf='wpdSouden_ban'`` / ``'wpdSouden'``: the WPD convolutional beamformer (see
+    `ops.wpd_souden_from_masks`) on the STFT BEFORE WPE -- WPE as configured still feeds the
+    mixture model (``wpe_per_array`` only shapes that WPE) --, ``bf_wpd_taps`` / ``bf_wpd_delay``
+    (None: the WPE block's) its tap window, ``bf_wpd_iterations`` its iterations and
+    ``bf_wpd_power_floor`` (1e-3: a choice, not a measurement) the floor of the target power.  For
+    `Enhancer.enhance_observation` / `enhance_example` and, one utterance at a time,
+    `enhance_session` (the pipelined pcm16 path is out of scope); not with ``bf_segment_frames``,
+    ``bf_null_interferer``, ``channel_keep``, the multi-speaker methods or the activity methods
+    (NotImplementedError).
     ``bf_null_interferer=True``: 'mvdrSouden_ban' becomes the interferer-nulling LCMV (see
     `Beamformer`): the competing speaker with the most posterior mass in the window -- the
     garbage class is no candidate -- gets a null; where that speaker is next to silent at a
@@ -1363,7 +1461,10 @@ def get_enhancer(
                             segment_context=bf_segment_context,
                             segment_min_mass=bf_segment_min_mass,
                             null_interferer=bool(bf_null_interferer),
-                            null_min_mass=bf_null_min_mass),
+                            null_min_mass=bf_null_min_mass,
+                            **bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps,
+                                              bf_wpd_delay, bf_wpd_iterations,
+                                              bf_wpd_power_floor)),
         stft_size=stft_size,
         stft_shift=stft_shift,
         stft_fading=stft_fading,

@@ -14,8 +14,9 @@ from pathlib import Path
 import numpy as np
 
 from pb_chime5_amd import core
+from pb_chime5_amd import ops
 from pb_chime5_amd.core import (   # noqa: F401
-    WPE, GSS, Beamformer, start_end_context_frames, default_database_path)
+    WPE, GSS, Beamformer, bf_block_kwargs, start_end_context_frames, default_database_path)
 from pb_chime5_amd.io import load_audio
 from pb_chime5_amd.utils.numpy_utils import morph
 
@@ -148,9 +149,14 @@ def get_enhancer(
     channel_bands=40,
     bf_null_interferer=False,
     bf_null_min_mass=None,
+    bf_wpd_taps=None,
+    bf_wpd_delay=None,
+    bf_wpd_iterations=1,
+    bf_wpd_power_floor=ops.WPD_POWER_FLOOR,
 ):
     """core_chime6.py:572-635 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*`` and ``bf_null_*`` are additions,
+    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*`` and
+    ``bf_wpd_*`` are additions,
     see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
@@ -170,7 +176,10 @@ def get_enhancer(
                             segment_context=bf_segment_context,
                             segment_min_mass=bf_segment_min_mass,
                             null_interferer=bool(bf_null_interferer),
-                            null_min_mass=bf_null_min_mass),
+                            null_min_mass=bf_null_min_mass,
+                            **bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps,
+                                              bf_wpd_delay, bf_wpd_iterations,
+                                              bf_wpd_power_floor)),
         stft_size=stft_size,
         stft_shift=stft_shift,
         stft_fading=stft_fading,

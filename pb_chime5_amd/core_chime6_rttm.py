@@ -15,8 +15,9 @@ from dataclasses import dataclass, field
 import numpy as np
 from pathlib import Path
 
-from pb_chime5_amd import core, mapping
-from pb_chime5_amd.core import WPE, GSS, Beamformer, start_end_context_frames  # noqa: F401
+from pb_chime5_amd import core, mapping, ops
+from pb_chime5_amd.core import (  # noqa: F401
+    WPE, GSS, Beamformer, bf_block_kwargs, start_end_context_frames)
 from pb_chime5_amd.database.chime5 import rttm as rttm_module
 from pb_chime5_amd.io import dump_audio
 
@@ -169,9 +170,14 @@ def get_enhancer(
     channel_bands=40,
     bf_null_interferer=False,
     bf_null_min_mass=None,
+    bf_wpd_taps=None,
+    bf_wpd_delay=None,
+    bf_wpd_iterations=1,
+    bf_wpd_power_floor=ops.WPD_POWER_FLOOR,
 ):
     """core_chime6_rttm.py:360-422 (same keyword arguments and defaults; ``device_id``,
-    ``wpe_per_array``, ``bf_segment_*``, ``channel_*`` and ``bf_null_*`` are additions, see core.get_enhancer)."""
+    ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*`` and
+    ``bf_wpd_*`` are additions, see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     db = get_database(chime6_dir, database_rttm, multiarray)
     return Enhancer(
@@ -189,7 +195,10 @@ def get_enhancer(
                             segment_context=bf_segment_context,
                             segment_min_mass=bf_segment_min_mass,
                             null_interferer=bool(bf_null_interferer),
-                            null_min_mass=bf_null_min_mass),
+                            null_min_mass=bf_null_min_mass,
+                            **bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps,
+                                              bf_wpd_delay, bf_wpd_iterations,
+                                              bf_wpd_power_floor)),
         stft_size=stft_size,
         stft_shift=stft_shift,
         stft_fading=stft_fading,

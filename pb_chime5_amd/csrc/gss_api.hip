@@ -185,6 +185,7 @@ extern "C" int gss_create(int device_id, gss_ctx **out) {
     ctx->status_host[GSS_STATUS_SEGMENT_FALLBACKS] = 0;
     ctx->status_host[GSS_STATUS_LCMV_INTERFERER] = -1;
     ctx->status_host[GSS_STATUS_LCMV_FALLBACKS] = 0;
+    ctx->status_host[GSS_STATUS_WPD_ZERO_PIVOTS] = 0;
     *out = ctx;
     return GSS_OK;
 }
@@ -897,6 +898,91 @@ extern "C" int gss_last_segment_fallbacks(gss_ctx *ctx, int64_t *count) {
     return GSS_OK;
 }
 
+extern "C" int gss_wpe_weighted(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D, int taps,
+                                int delay, const double *weights, gss_cplx *X) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, Y && X && weights && F >= 1 && T >= 1, GSS_ERR_INVALID,
+                "gss_wpe_weighted: bad arguments");
+    GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
+                "gss_wpe_weighted: D=%d outside [1, %d]", D, GSS_MAX_CHANNELS);
+    GSS_REQUIRE(ctx, taps >= 1 && delay >= 0, GSS_ERR_INVALID, "gss_wpe_weighted: taps=%d delay=%d",
+                taps, delay);
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(arena_reserve(ctx, wpe_workspace_bytes(F, T, D, taps, delay)));
+    const WpeCallerWeights cw{weights, 2, false};
+    return wpe_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, taps, delay, 1, 0,
+                   reinterpret_cast<cplx *>(X), -1, 0, &cw);
+}
+
+static int check_power_floor(gss_ctx *ctx, double floor, const char *what) {
+    GSS_REQUIRE(ctx, std::isfinite(floor) && floor > 0.0 && floor <= 1.0, GSS_ERR_INVALID,
+                "%s: power_floor = %g outside (0, 1] or not finite", what, floor);
+    return GSS_OK;
+}
+
+// The descriptor's rules (include/gss_hip.h)
+static int check_wpd(gss_ctx *ctx, const gss_bf_wpd *wpd, int D, const char *what) {
+    GSS_REQUIRE(ctx, wpd, GSS_ERR_INVALID, "%s: wpd is NULL", what);
+    GSS_REQUIRE(ctx, wpd->taps >= 1, GSS_ERR_INVALID, "%s: taps = %d is smaller than 1", what,
+                wpd->taps);
+    GSS_REQUIRE(ctx, wpd->delay >= 0, GSS_ERR_INVALID, "%s: delay = %d is negative", what,
+                wpd->delay);
+    GSS_REQUIRE(ctx, wpd->iterations >= 1, GSS_ERR_INVALID, "%s: iterations = %d is smaller than 1",
+                what, wpd->iterations);
+    GSS_TRY(check_power_floor(ctx, wpd->power_floor, what));
+    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    return GSS_OK;
+}
+
+extern "C" int gss_wpd_weights(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                               const double *mask, const gss_cplx *Xhat, const uint8_t *gate,
+                               double power_floor, double *weights) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, weights, GSS_ERR_INVALID, "gss_wpd_weights: weights_dev is NULL");
+    GSS_REQUIRE(ctx, Xhat || (Y && mask), GSS_ERR_INVALID,
+                "gss_wpd_weights: neither Xhat_dev nor Y_dev with mask_dev");
+    GSS_REQUIRE(ctx, F >= 1 && T >= 1, GSS_ERR_INVALID, "gss_wpd_weights: F=%d T=%lld", F,
+                (long long)T);
+    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    GSS_TRY(check_power_floor(ctx, power_floor, "gss_wpd_weights"));
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    return wpd_weights_run(ctx, reinterpret_cast<const cplx *>(Y), mask,
+                           reinterpret_cast<const cplx *>(Xhat), gate, F, T, D, power_floor,
+                           weights, nullptr);
+}
+
+extern "C" int gss_wpd_souden(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                              const double *mask, const uint8_t *gate, const gss_bf_wpd *wpd,
+                              int ref_channel, gss_cplx *Xhat, int32_t *ref) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, Y, GSS_ERR_INVALID, "gss_wpd_souden: Y_dev is NULL");
+    GSS_REQUIRE(ctx, mask, GSS_ERR_INVALID, "gss_wpd_souden: target_mask_dev is NULL");
+    GSS_REQUIRE(ctx, Xhat, GSS_ERR_INVALID, "gss_wpd_souden: Xhat_dev is NULL");
+    GSS_REQUIRE(ctx, F >= 1 && T >= 1, GSS_ERR_INVALID, "gss_wpd_souden: F=%d T=%lld", F,
+                (long long)T);
+    GSS_TRY(check_wpd(ctx, wpd, D, "gss_wpd_souden"));
+    GSS_REQUIRE(ctx, ref_channel >= -1 && ref_channel < D, GSS_ERR_INVALID,
+                "ref_channel %d outside [-1, %d)", ref_channel, D);
+    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(arena_reserve(ctx, wpd_workspace_bytes(F, T, D, wpd->taps, wpd->delay)));
+    return wpd_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mask, gate, *wpd, ref_channel,
+                   reinterpret_cast<cplx *>(Xhat), ref);
+}
+
+extern "C" int gss_last_wpd_zero_pivots(gss_ctx *ctx, int64_t *count) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, count, GSS_ERR_INVALID, "gss_last_wpd_zero_pivots: NULL");
+    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *count = __atomic_load_n(ctx->status_host + GSS_STATUS_WPD_ZERO_PIVOTS, __ATOMIC_ACQUIRE);
+    return GSS_OK;
+}
+
 // The descriptor's rules (include/gss_hip.h); K bounds the class indices.
 static int check_lcmv(gss_ctx *ctx, const gss_bf_lcmv *lcmv, int K, int target, const char *what) {
     GSS_REQUIRE(ctx, lcmv, GSS_ERR_INVALID, "%s: lcmv is NULL", what);
@@ -1165,8 +1251,13 @@ static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, in
 // activity: the posterior activity runs between the front and the masks)
 static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
                                  int K, int64_t segment_frames = 0, int select_bands = 0,
-                                 int select_D = 0, bool lcmv = false, bool activity = false) {
+                                 int select_D = 0, bool lcmv = false, bool activity = false,
+                                 const gss_bf_wpd *wpd = nullptr) {
     size_t b = front_buffer_bytes(F, T, T_act, D, K);
+    // (WPD: the raw STFT beside the WPE output -- the joint WPE leaves it in Y's buffer, the
+    // per-array WPE overwrites that one -- and the frame gate)
+    if (wpd && p->wpe && wpe_arrays_of(p) > 1) b += align_up(sizeof(cplx) * (size_t)F * T * D);
+    if (wpd) b += align_up((size_t)T);
     b += (lcmv ? 4 : 2) * align_up(sizeof(double) * (size_t)F * T);   // masks (LCMV: X, I, N, I + N)
     b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
     b += 4096;
@@ -1177,6 +1268,7 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
     if (lcmv)
         stage = std::max(stage, std::max(lcmv_workspace_bytes(F, T, D),
                                          lcmv_masks_workspace_bytes(F, K)));
+    if (wpd) stage = std::max(stage, wpd_workspace_bytes(F, T, D, wpd->taps, wpd->delay));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
     if (activity) stage = std::max(stage, pact_workspace_bytes(F, T, K));   // the partial planes
     if (select_bands > 0)
@@ -1244,6 +1336,7 @@ static int check_pipeline_rest(gss_ctx *ctx, const gss_params *p, int D, int64_t
 // The pipeline's buffers that outlive the front; allocated first from the reserved arena.
 struct PipelineFront {
     cplx *Y, *X;
+    cplx *Yraw = nullptr;   // WPD over a per-array WPE: a copy of the STFT, which that WPE overwrites
     uint8_t *actf;
     double *gamma;
 };
@@ -1284,6 +1377,9 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const void *obs, int obs
         GSS_TRY(chsel_select_run(ctx, Yall, F, T, D_all, *sel, Y, nullptr));
         ctx->arena_off = mark;
     }
+    if (fr.Yraw)
+        GSS_HIP_CHECK(ctx, hipMemcpyAsync(fr.Yraw, Y, sizeof(cplx) * (size_t)F * T * D,
+                                          hipMemcpyDeviceToDevice, ctx->stream));
     if (!p->wpe)    // no solve in this call: clear the count an earlier utterance left behind
         GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + 2, 0, sizeof(int32_t), ctx->stream));
     const int A = wpe_arrays_of(p);
@@ -1341,7 +1437,8 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
                                     const gss_channel_select *sel = nullptr,
                                     bool select = false,
                                     const gss_bf_lcmv *lcmv = nullptr,
-                                    const PipelineActivity *pact = nullptr) {
+                                    const PipelineActivity *pact = nullptr,
+                                    const gss_bf_wpd *wpd = nullptr) {
     GSS_REQUIRE(ctx, !guided || guidance, GSS_ERR_INVALID,
                 "gss_enhance_observation_guided: guidance is NULL");
     GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, guided ? (const void *)guidance : act, out,
@@ -1383,9 +1480,18 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K,
                                                   seg ? seg->segment_frames : 0,
                                                   select ? sel->bands : 0, D_all,
-                                                  lcmv != nullptr, pact != nullptr)));
+                                                  lcmv != nullptr, pact != nullptr, wpd)));
     PipelineFront fr;
     GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
+    uint8_t *gate = nullptr;
+    if (wpd) {
+        if (p->wpe && wpe_arrays_of(p) > 1) {
+            fr.Yraw = arena_alloc_t<cplx>(ctx, (size_t)F * T * D);
+            GSS_REQUIRE(ctx, fr.Yraw, GSS_ERR_NOMEM, "workspace sizing bug");
+        }
+        gate = arena_alloc_t<uint8_t>(ctx, (size_t)T);
+        GSS_REQUIRE(ctx, gate, GSS_ERR_NOMEM, "workspace sizing bug");
+    }
     double *mx = arena_alloc_t<double>(ctx, (size_t)F * T);
     double *mn = arena_alloc_t<double>(ctx, (size_t)F * T);
     // (LCMV: mi, mnn = the interferer and noise masks, mn = their sum, the distortion mask)
@@ -1414,7 +1520,13 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     if (!lcmv || (taps && taps->distortion_mask))
         GSS_TRY(masks_from_posteriors_run(ctx, fr.gamma, F, K, T, target, p->bf_drop_context, sf,
                                           ef, mx, mn));
-    if (lcmv) {     // (bf == 0, checked by the entry point)
+    if (wpd) {      // (bf == 0, checked by the entry point) on the STFT before WPE
+        const cplx *raw = fr.Yraw ? fr.Yraw : fr.Y;
+        if (p->bf_drop_context) GSS_TRY(wpd_context_gate_run(ctx, T, sf, ef, gate));
+        GSS_TRY(wpd_run(ctx, raw, F, T, D, mx, p->bf_drop_context ? gate : nullptr, *wpd,
+                        /*forced_ref=*/-1, Xhat, ref));
+        ctx->arena_off = mark;
+    } else if (lcmv) {     // (bf == 0, checked by the entry point)
         GSS_TRY(lcmv_masks_run(ctx, fr.gamma, F, K, T, target, *lcmv, p->bf_drop_context, sf, ef,
                                mx, mi, mnn, nullptr));
         ctx->arena_off = mark;
@@ -1564,6 +1676,21 @@ extern "C" int gss_enhance_observation_segments(gss_ctx *ctx, const gss_params *
                 p->bf);
     return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
                                     out, taps, /*guided=*/false, nullptr, seg);
+}
+
+extern "C" int gss_enhance_observation_wpd(gss_ctx *ctx, const gss_params *p, const double *obs,
+                                           int D, int64_t N, const uint8_t *act, int K,
+                                           int64_t N_act, int target, int64_t start_ctx,
+                                           int64_t end_ctx, const gss_bf_wpd *wpd, double *out,
+                                           const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, !p || p->bf == 0, GSS_ERR_UNSUPPORTED,
+                "gss_enhance_observation_wpd: bf=%d, only 0 ('mvdrSouden_ban') has a WPD form",
+                p->bf);
+    GSS_TRY(check_wpd(ctx, wpd, D, "gss_enhance_observation_wpd"));
+    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, false, nullptr, nullptr, nullptr, false, nullptr,
+                                    nullptr, wpd);
 }
 
 extern "C" int gss_enhance_observation_lcmv(gss_ctx *ctx, const gss_params *p, const double *obs,

@@ -168,6 +168,7 @@ struct gss_ctx {
     // [4]: the interferer class of the last LCMV mask call (masks3_kernel), -1 = none.
     // [5]: frequencies of the last LCMV beamformer that fell back to the MVDR of the merged mask
     // (copied from the device counter by lcmv_run).
+    // [6]: pivots zeroed by the WPE steps of the last WPD call (wpe_run with the caller's weights).
     // [GSS_STATUS_TARGETS + s]: target s of the last targets call (mvdr_apply_targets_kernel,
     // which writes target 0's word to [0] as well).
     int32_t *status_host = nullptr;
@@ -192,6 +193,7 @@ struct gss_ctx {
 #define GSS_STATUS_SEGMENT_FALLBACKS 3                           // see gss_ctx::status_host
 #define GSS_STATUS_LCMV_INTERFERER 4
 #define GSS_STATUS_LCMV_FALLBACKS 5
+#define GSS_STATUS_WPD_ZERO_PIVOTS 6                             // pivots zeroed by the last WPD call
 #define GSS_STATUS_TARGETS 16                                    // first per-target word
 #define GSS_STATUS_CHANNELS 40                                   // first selected-channel word
 #define GSS_STATUS_BYTES (4 * (GSS_STATUS_CHANNELS + GSS_MAX_CHANNELS))
@@ -259,8 +261,18 @@ int wpe_inverse_power_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, 
 // host, each has its own correlation work queues.
 // array_bins > 0: the call is (part of) a per-array WPE stage over array_bins virtual bins of
 // one array each (picks the correlation geometry for the whole stage; 0 = joint WPE).
+// cw: ONE iteration whose weights w (F,T) come from the caller instead of wpe_power_kernel
+// (gss_wpe_weighted, the WPD): no power pass, every other launch and argument as without it.  The
+// pivot count goes to status word `status_word`; `accumulate`: it continues the count of the
+// preceding call instead of starting at 0 (the iterations of one WPD call).
+struct WpeCallerWeights {
+    const double *w;
+    int status_word;
+    bool accumulate;
+};
 int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int delay,
-            int iterations, int psd_context, cplx *X, int part = -1, int array_bins = 0);
+            int iterations, int psd_context, cplx *X, int part = -1, int array_bins = 0,
+            const WpeCallerWeights *cw = nullptr);
 // the pivot count of the last wpe_run parts -> the context's status word (after the join)
 int wpe_copy_zero_pivots(gss_ctx *ctx);
 // per-array WPE: (F, T, A C) -> (F A, T, C) (to_arrays) or back; src and dst must not alias
@@ -405,6 +417,21 @@ int chsel_select_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
 size_t pact_workspace_bytes(int F, int64_t T, int K);
 int pact_run(gss_ctx *ctx, const cplx *Y, const double *gamma, int F, int K, int64_t T, int D,
              const double *W, double *scores, double *power);
+
+// WPD convolutional beamformer (wpd.hip; include/gss_hip.h: gss_wpd_souden).  weights_run: the
+// weights a (F,T) of one iteration from Y (F,T,D) and the mask (F,T), or (xhat != NULL) from
+// |xhat (T,F)|^2; gate (T) or NULL; mxg (F,T), may be NULL, receives mask * gate (first form).
+// wpd_run: `bf` has been validated by the entry point, forced_ref as in mvdr_run; the pivots its
+// WPE steps zero go to status word GSS_STATUS_WPD_ZERO_PIVOTS, the WPE stage's word is untouched.
+size_t wpd_workspace_bytes(int F, int64_t T, int D, int taps, int delay);
+int wpd_weights_run(gss_ctx *ctx, const cplx *Y, const double *mask, const cplx *xhat,
+                    const uint8_t *gate, int F, int64_t T, int D, double power_floor, double *a,
+                    double *mxg);
+int wpd_context_gate_run(gss_ctx *ctx, int64_t T, int64_t start_frames, int64_t end_frames,
+                         uint8_t *gate);
+int wpd_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mask,
+            const uint8_t *gate, const gss_bf_wpd &bf, int forced_ref, cplx *Xhat,
+            int32_t *ref_channel);
 
 int selftest_mfma_run(gss_ctx *ctx);
 

@@ -1977,7 +1977,8 @@ int wpe_inverse_power_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, 
 }
 
 int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int delay,
-            int iterations, int psd_context, cplx *X, int part, int array_bins) {
+            int iterations, int psd_context, cplx *X, int part, int array_bins,
+            const WpeCallerWeights *cw) {
     const int n = taps * D;
     const int c = delay + taps - 1;
     if (iterations == 0) {
@@ -1989,7 +1990,11 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
         return GSS_OK;
     }
     GSS_REQUIRE(ctx, X != Y, GSS_ERR_INVALID, "gss_wpe: X must not alias Y");
-    double *w = arena_alloc_t<double>(ctx, (size_t)F * T);
+    GSS_REQUIRE(ctx, !cw || (cw->w && iterations == 1 && part < 0), GSS_ERR_INVALID,
+                "wpe: the caller's weights serve one iteration of a whole call");
+    // (the caller's weights: no power pass and no buffer for one; every launch below is the same)
+    double *w_own = cw ? nullptr : arena_alloc_t<double>(ctx, (size_t)F * T);
+    const double *w = cw ? cw->w : w_own;
     // (NULL without smoothing: the kernel's two __restrict__ outputs must not alias)
     double *raw = psd_context > 0 ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
     cplx *R = arena_alloc_t<cplx>(ctx, (size_t)F * n * n);
@@ -2078,7 +2083,8 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
     // zeroed pivots of this call (all iterations, all frequencies): counted on the device,
     // copied to the context's status words at the end (gss_last_wpe_zero_pivots)
     int32_t *zero_pivots = reinterpret_cast<int32_t *>(tiles_dev + 1024 + 4096);
-    if (part <= 0) GSS_HIP_CHECK(ctx, hipMemsetAsync(zero_pivots, 0, sizeof(int32_t), ctx->stream));
+    if (part <= 0 && !(cw && cw->accumulate))
+        GSS_HIP_CHECK(ctx, hipMemsetAsync(zero_pivots, 0, sizeof(int32_t), ctx->stream));
     if (part == 0) GSS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     // work-queue heads of the persistent correlation kernel: 8 counters, 64 bytes apart (a second
     // set for the second of two parts that run side by side)
@@ -2277,9 +2283,9 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
 
     for (int it = 0; it < iterations; ++it) {
         const cplx *cur = it == 0 ? Y : X;
-        {
+        if (!cw) {
             GSS_PROF(ctx, "wpe_power");
-            GSS_TRY(wpe_power_launch(ctx, cur, F, T, D, psd_context, raw, w));
+            GSS_TRY(wpe_power_launch(ctx, cur, F, T, D, psd_context, raw, w_own));
         }
         if (corr_persist) {
             GSS_HIP_CHECK(ctx, hipMemsetAsync(corr_counters, 0, 8 * 16 * sizeof(int), ctx->stream));
@@ -2359,8 +2365,8 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
     }
     // (two parts: the caller copies the count after both have finished)
     if (part < 0)
-        GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + 2, zero_pivots, sizeof(int32_t),
-                                          hipMemcpyDeviceToHost, ctx->stream));
+        GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + (cw ? cw->status_word : 2), zero_pivots,
+                                          sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     return GSS_OK;
 }
 

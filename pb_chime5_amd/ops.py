@@ -31,8 +31,8 @@ import ctypes
 import numpy as np
 
 from . import _capi
-from ._capi import (Context, GssBfLcmv, GssBfSegments, GssCacgmmModel, GssChannelSelect, GssDebugTaps,
-                    GssGuidance, GssParams, c_void_p, default_context)
+from ._capi import (Context, GssBfLcmv, GssBfSegments, GssBfWpd, GssCacgmmModel, GssChannelSelect,
+                    GssDebugTaps, GssGuidance, GssParams, c_void_p, default_context)
 from .cacgmm import CACGMM
 
 _BF_CODES = {'mvdrSouden_ban': 0, 'ch2': 1, 'sum': 2, 'gev_ban': 3}
@@ -734,6 +734,167 @@ def lcmv_masks_from_posteriors(posterior, target_index, *, interferer=None, cand
     return (*masks, found)
 
 
+WPD_POWER_FLOOR = 1e-3      # a choice, not a measurement
+
+
+def check_bf_wpd(taps=10, delay=2, iterations=1, power_floor=WPD_POWER_FLOOR, ban=False,
+                 num_channels=None, *, bf=None, segment_frames=None, null_interferer=False,
+                 channel_keep=None, multi_target=False, activity=False):
+    """The settings of the WPD beamformer as a gss_bf_wpd -- the one place that validates them.
+    ValueError naming the argument: ``taps`` an integer >= 1, ``delay`` an integer >= 0,
+    ``iterations`` an integer >= 1, ``power_floor`` finite in (0, 1]; AssertionError for
+    ``num_channels`` >= 30 like the MVDR.  NotImplementedError for what the WPD does not combine
+    with: a ``bf`` other than 'wpdSouden' / 'wpdSouden_ban' (None: not checked), the segment-wise
+    and the interferer-nulling beamformer, the channel selection, the multi-target and the
+    activity calls.  All before any device work."""
+    for name, value, low in (('taps', taps, 1), ('delay', delay, 0), ('iterations', iterations, 1)):
+        if not _is_integer(value) or value < low or value >= 2 ** 31:
+            raise ValueError(f'{name}={value!r}: an integer >= {low}')
+    if not _is_real(power_floor) or not np.isfinite(power_floor) \
+            or not 0 < power_floor <= 1:
+        raise ValueError(f'power_floor={power_floor!r}: a finite number in (0, 1]')
+    if num_channels is not None:
+        if not _is_integer(num_channels) or num_channels < 1:
+            raise ValueError(f'num_channels={num_channels!r}: a positive integer')
+        if num_channels >= 30:     # (not an `assert` statement: those vanish under python -O)
+            raise AssertionError(f'assert D < 30 failed: D={num_channels}')
+    if bf is not None and bf not in WPD_BF_TYPES:
+        raise NotImplementedError(f'bf={bf!r} with WPD settings: only {sorted(WPD_BF_TYPES)}')
+    for name, on in (('bf_segment_frames', segment_frames is not None),
+                     ('bf_null_interferer', bool(null_interferer)),
+                     ('channel_keep', channel_keep is not None),
+                     ('several targets from one separation', bool(multi_target)),
+                     ('the posterior activity', bool(activity))):
+        if on:
+            raise NotImplementedError(f'the WPD beamformer does not combine with {name}')
+    return GssBfWpd(taps=int(taps), delay=int(delay), iterations=int(iterations),
+                    ban=int(bool(ban)), power_floor=float(power_floor))
+
+
+WPD_BF_TYPES = {'wpdSouden': False, 'wpdSouden_ban': True}      # type -> ban
+
+
+def _gate_to_device(ctx, frame_gate, T):
+    """frame_gate (T,) of 0 / 1 (bool or numbers; None: every frame counts) -> device uint8."""
+    if frame_gate is None:
+        return None
+    g = np.asarray(frame_gate)
+    if g.shape != (T,):
+        raise ValueError(f'frame_gate: shape {g.shape} is not (T,) = {(T,)}')
+    return ctx.to_device((g != 0).astype(np.uint8))
+
+
+def wpe_weighted(Obs, weights, taps=10, delay=2, *, ctx=None):
+    """One WPE step with the caller's weights (gss_wpe_weighted): Obs (D,T,F), weights (F,T) ->
+    (D,T,F).  With ``get_power_inverse`` of the observation it is ``wpe_dtf(iterations=1)`` bit
+    for bit."""
+    Obs = np.asarray(Obs)
+    if Obs.ndim != 3:
+        raise ValueError(f'Obs: shape {Obs.shape} is not (D,T,F)')
+    D, T, F = Obs.shape
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (F, T):
+        raise ValueError(f'weights: shape {w.shape} is not (F,T) = {(F, T)}')
+    check_bf_wpd(taps, delay)
+    ctx = ctx or default_context()
+    Y_d, _ = _obs_to_device_ftd(ctx, Obs)
+    w_d = ctx.to_device(w)
+    X_d = ctx.empty(16 * F * T * D)
+    ctx._check(ctx.lib.gss_wpe_weighted(ctx.handle, c_void_p(Y_d.ptr), F, T, D, int(taps),
+                                        int(delay), c_void_p(w_d.ptr), c_void_p(X_d.ptr)),
+               'gss_wpe_weighted')
+    return _ftd_to_host_dtf(ctx, X_d, D, T, F)
+
+
+def wpd_weights(Y=None, X_mask=None, *, X_hat=None, frame_gate=None,
+                power_floor=WPD_POWER_FLOOR, ctx=None):
+    """The weights of one WPD iteration (gss_wpd_weights), (F,T): from Y (D,T,F) and the target
+    mask X_mask (T,F) -- ``a = gate / max(mask * mean_d |Y|^2, power_floor * its gated maximum)``
+    -- or from a beamformed signal ``X_hat`` (T,F) -- its power in the place of the masked
+    one.  All zero at a frequency whose gated maximum is 0."""
+    check_bf_wpd(power_floor=power_floor)
+    if X_hat is not None:
+        if Y is not None or X_mask is not None:
+            raise ValueError('wpd_weights: either Y with X_mask, or X_hat')
+        xh = np.ascontiguousarray(X_hat, dtype=np.complex128)
+        if xh.ndim != 2:
+            raise ValueError(f'X_hat: shape {xh.shape} is not (T,F)')
+        T, F = xh.shape
+        ctx = ctx or default_context()
+        g_d = _gate_to_device(ctx, frame_gate, T)
+        x_d = ctx.to_device(xh)
+        a_d = ctx.empty(8 * F * T)
+        ctx._check(ctx.lib.gss_wpd_weights(
+            ctx.handle, None, F, T, 1, None, c_void_p(x_d.ptr),
+            c_void_p(g_d.ptr) if g_d is not None else None, float(power_floor),
+            c_void_p(a_d.ptr)), 'gss_wpd_weights')
+        return ctx.to_host(a_d, (F, T), np.float64)
+    if Y is None or X_mask is None:
+        raise ValueError('wpd_weights: either Y with X_mask, or X_hat')
+    Y = np.asarray(Y)
+    if Y.ndim != 3:
+        raise ValueError(f'Y: shape {Y.shape} is not (D,T,F)')
+    D, T, F = Y.shape
+    check_bf_wpd(power_floor=power_floor, num_channels=D)
+    if np.shape(X_mask) != (T, F):
+        raise ValueError(f'X_mask: shape {np.shape(X_mask)} is not (T,F) = {(T, F)}')
+    ctx = ctx or default_context()
+    g_d = _gate_to_device(ctx, frame_gate, T)
+    Y_d, _ = _obs_to_device_ftd(ctx, Y)
+    m_d = _mask_to_device_ft(ctx, X_mask, T, F)
+    a_d = ctx.empty(8 * F * T)
+    ctx._check(ctx.lib.gss_wpd_weights(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, c_void_p(m_d.ptr), None,
+        c_void_p(g_d.ptr) if g_d is not None else None, float(power_floor),
+        c_void_p(a_d.ptr)), 'gss_wpd_weights')
+    return ctx.to_host(a_d, (F, T), np.float64)
+
+
+def wpd_souden_from_masks(Y, X_mask, ban=False, *, taps=10, delay=2, iterations=1,
+                          power_floor=WPD_POWER_FLOOR, frame_gate=None, ref_channel=None,
+                          return_ref_channel=False, return_zero_pivots=False, ctx=None):
+    """The WPD convolutional beamformer from a target mask (gss_wpd_souden): per iteration one
+    WPE step on Y whose weights are 1 / target power (the masked observation power first, the
+    power of the previous iteration's output afterwards; floored at ``power_floor`` times its
+    maximum over the frames ``frame_gate`` keeps), then the Souden MVDR of the result with the
+    target mask and those weights as the distortion mask.  ``frame_gate`` (T,) of 0 / 1 takes
+    frames out of every statistic (None: none); ``ref_channel`` names the reference channel
+    (None: the SNR argmax, chosen anew in every iteration).
+
+    Y (D,T,F) -- the observation BEFORE any dereverberation --, X_mask (T,F) -> X_hat (T,F); with
+    ``return_ref_channel`` / ``return_zero_pivots`` a tuple (X_hat[, ref_channel][, pivots the
+    WPE solves zeroed]).  Argument errors are ValueError before any device work; a non-finite
+    SNR raises AssertionError like the MVDR."""
+    Y = np.asarray(Y)
+    if Y.ndim != 3:
+        raise ValueError(f'Y: shape {Y.shape} is not (D,T,F)')
+    D, T, F = Y.shape
+    bf = check_bf_wpd(taps, delay, iterations, power_floor, ban, D)
+    if np.shape(X_mask) != (T, F):
+        raise ValueError(f'X_mask: shape {np.shape(X_mask)} is not (T,F) = {(T, F)}')
+    if ref_channel is not None and (not _is_integer(ref_channel) or not 0 <= ref_channel < D):
+        raise ValueError(f'ref_channel={ref_channel!r} outside [0, {D})')
+    if frame_gate is not None and np.shape(frame_gate) != (T,):
+        raise ValueError(f'frame_gate: shape {np.shape(frame_gate)} is not (T,) = {(T,)}')
+    ctx = ctx or default_context()
+    g_d = _gate_to_device(ctx, frame_gate, T)
+    Y_d, _ = _obs_to_device_ftd(ctx, Y)
+    mx = _mask_to_device_ft(ctx, X_mask, T, F)
+    X_d = ctx.empty(16 * F * T)
+    ctx._check(ctx.lib.gss_wpd_souden(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, c_void_p(mx.ptr),
+        c_void_p(g_d.ptr) if g_d is not None else None, ctypes.byref(bf),
+        -1 if ref_channel is None else int(ref_channel), c_void_p(X_d.ptr), None),
+        'gss_wpd_souden')
+    ref = _check_ref_channel(ctx)
+    out = (ctx.to_host(X_d, (T, F), np.complex128),)
+    if return_ref_channel:
+        out += (ref,)
+    if return_zero_pivots:
+        out += (ctx.last_wpd_zero_pivots(),)
+    return out if len(out) > 1 else out[0]
+
+
 def gev_from_masks(Y, X_mask, N_mask, ban=True, *, ctx=None):
     """beamform_gev_from_masks: Y (D,T,F), 2-D masks (T,F) -> X_hat (T,F).  The phase
     of a generalised eigenvector is arbitrary (upstream too); magnitudes are defined.
@@ -1158,8 +1319,10 @@ class ResidentUtterance:
         self.out_d = ctx.empty(8 * max(self.n_out, 1))
 
     def enqueue(self, target_index, start_context, end_context, taps=None, segments=None,
-                channel_select=None, lcmv=None, activity=None):
-        """``segments``: a gss_bf_segments (`check_bf_segments`) for the segment-wise
+                channel_select=None, lcmv=None, activity=None, wpd=None):
+        """``wpd``: a gss_bf_wpd (`check_bf_wpd`) for the WPD beamformer on the STFT before WPE
+        (gss_enhance_observation_wpd; float64 samples only, on its own).
+        ``segments``: a gss_bf_segments (`check_bf_segments`) for the segment-wise
         beamformer (gss_enhance_observation_segments; float64 samples only).
         ``channel_select``: a `ChannelSelect` for the envelope-variance selection ahead of WPE
         (gss_enhance_observation_select / its pcm16 twin; not together with segments).
@@ -1169,6 +1332,17 @@ class ResidentUtterance:
         the posterior activity of the call's own observation and posteriors
         (gss_enhance_observation_activity; float64 samples only, on its own)."""
         ctx = self.ctx
+        if wpd is not None:
+            assert segments is None and channel_select is None and lcmv is None \
+                and activity is None, 'the WPD call stands alone'
+            assert not self.pcm, 'the WPD call has no pcm16 twin'
+            ctx._check(ctx.lib.gss_enhance_observation_wpd(
+                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
+                self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
+                int(start_context), int(end_context), ctypes.byref(wpd),
+                c_void_p(self.out_d.ptr), ctypes.byref(taps) if taps is not None else None),
+                'gss_enhance_observation_wpd')
+            return
         if activity is not None:
             assert segments is None and channel_select is None and lcmv is None, \
                 'the activity call stands alone'
@@ -1598,6 +1772,46 @@ def enhance_observation_lcmv(obs, activity, target_index, start_context_samples,
             if ef > 0:
                 mask[-ef:] = 0
     details['interferer_mask'] = mask
+    return x_hat, details
+
+
+def enhance_observation_wpd(obs, activity, target_index, start_context_samples,
+                            end_context_samples, *, taps=None, delay=None, iterations=1,
+                            power_floor=WPD_POWER_FLOOR, ban=True, params=None, window=None,
+                            debug=False, ctx=None, wpe_arrays=None, **param_kwargs):
+    """`enhance_observation` with the WPD beamformer of `wpd_souden_from_masks`
+    (gss_enhance_observation_wpd) in the place of the MVDR: the beamformer works on the STFT
+    BEFORE WPE with the target mask of the mixture model, which still sees the WPE output; the
+    context frames that ``bf_drop_context`` zeroes are gated out of its statistics.  ``taps`` /
+    ``delay`` None: those of the WPE block.  ``debug`` details as there (``Obs`` is the input of
+    the mixture model) plus ``wpd_zero_pivots``.  ``params.bf`` must be 'mvdrSouden_ban' (its
+    code selects the Souden solve; ``ban`` decides the normalisation): NotImplementedError
+    otherwise; bad settings are ValueError, both before any device work."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    if params.bf != _BF_CODES['mvdrSouden_ban']:
+        names = {v: k for k, v in _BF_CODES.items()}
+        raise NotImplementedError(f"bf={names[params.bf]!r} with the WPD beamformer: only "
+                                  "'mvdrSouden_ban' has a WPD form")
+    obs = np.asarray(obs)
+    if obs.ndim != 2:
+        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    bf = check_bf_wpd(params.wpe_taps if taps is None else taps,
+                      params.wpe_delay if delay is None else delay, iterations, power_floor, ban,
+                      obs.shape[0])
+    params = params_for(params, obs.shape[0], wpe_arrays)
+    ctx = ctx or default_context()
+    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
+    utt = ResidentUtterance(ctx, obs, activity, params)
+    bufs, dbg = _debug_taps(utt) if debug else ({}, None)
+    utt.enqueue(target_index, start_context_samples, end_context_samples, dbg, wpd=bf)
+    x_hat = utt.result()
+    if not debug:
+        return x_hat
+    details = _debug_details(utt, bufs)
+    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+    details['ref_channel'] = int(details['ref_channel'])
+    details['wpd_zero_pivots'] = ctx.last_wpd_zero_pivots()
     return x_hat, details
 
 

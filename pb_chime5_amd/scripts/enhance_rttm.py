@@ -51,6 +51,17 @@ def main(argv=None):
                     help='interferer-nulling LCMV in the place of the MVDR: a null on the '
                          'competing speaker with the most posterior mass '
                          '(get_enhancer(bf_null_interferer=True))')
+    ap.add_argument('--bf-wpd-taps', type=int, default=None,
+                    help="with --bf wpdSouden_ban / wpdSouden, the WPD convolutional beamformer on "
+                         "the STFT before WPE: its taps (default: --wpe-tabs) "
+                         "(get_enhancer(bf_wpd_taps=...))")
+    ap.add_argument('--bf-wpd-delay', type=int, default=None,
+                    help='delay of the WPD tap window (default: --wpe-delay)')
+    ap.add_argument('--bf-wpd-iterations', type=int, default=1,
+                    help='WPD iterations: the target power of iteration i > 1 is the power of '
+                         'the output of iteration i - 1')
+    ap.add_argument('--bf-wpd-power-floor', type=float, default=1e-3,
+                    help='floor of the target power as a share of its maximum, in (0, 1]')
     ap.add_argument('--channel-keep', type=_channel_keep, default=None,
                     help='keep the channels the envelope-variance measure ranks best: a count '
                          '(20) or a share (0.8) (get_enhancer(channel_keep=...))')
@@ -80,7 +91,9 @@ def main(argv=None):
         device_id=parallel.device_index(), wpe_per_array=args.wpe_per_array,
         bf_segment_frames=args.bf_segment_frames, bf_segment_context=args.bf_segment_context,
         channel_keep=args.channel_keep, channel_bands=args.channel_bands,
-        bf_null_interferer=args.bf_null_interferer)
+        bf_null_interferer=args.bf_null_interferer, bf_wpd_taps=args.bf_wpd_taps,
+        bf_wpd_delay=args.bf_wpd_delay, bf_wpd_iterations=args.bf_wpd_iterations,
+        bf_wpd_power_floor=args.bf_wpd_power_floor)
     if parallel.is_master():
         Path(args.out).mkdir(parents=True, exist_ok=True)
     parallel.barrier()

@@ -143,3 +143,32 @@ def beamform_lcmv_souden_from_masks(Y, X_mask, I_mask, N_mask, ban=False, debug=
         assert m.shape == (F, T), (m.shape, F, T)
     return ops.lcmv_souden_from_masks(Y.transpose(1, 2, 0), X_mask.T, I_mask.T, N_mask.T,
                                       ban=ban, min_mass=0.0, ref_channel=ref_channel, ctx=ctx)
+
+
+def beamform_wpd_souden_from_masks(Y, X_mask, ban=False, *, taps=10, delay=2, iterations=1,
+                                   power_floor=ops.WPD_POWER_FLOOR, frame_gate=None,
+                                   ref_channel=None, ctx=None):
+    """The WPD convolutional beamformer (an addition; ``ops.wpd_souden_from_masks``) with the
+    layouts of its siblings -- Y (D,T,F) or (1,D,T,F), the observation BEFORE dereverberation;
+    X_mask (T,F), (D,T,F) or (1,D,T,F), median-reduced over the channel axis -- and X_hat (T,F)
+    out.  ``frame_gate`` (T,) of 0 / 1: frames that enter no statistic (None: none).
+    ``power_floor`` = 1e-3 is a choice, not a measurement."""
+    if np.ndim(Y) == 4:
+        Y = morph('1DTF->FDT', Y)
+    else:
+        Y = morph('DTF->FDT', Y)
+    if np.ndim(X_mask) == 4:
+        X_mask = morph('1DTF->FT', X_mask, reduce=np.median)
+    elif np.ndim(X_mask) == 3:
+        X_mask = morph('DTF->FT', X_mask, reduce=np.median)
+    elif np.ndim(X_mask) == 2:
+        X_mask = morph('TF->FT', X_mask)
+    else:
+        raise NotImplementedError(np.shape(X_mask))
+    assert Y.ndim == 3, Y.shape
+    F, D, T = Y.shape
+    assert D < 30, (D, Y.shape)
+    assert X_mask.shape == (F, T), (X_mask.shape, F, T)
+    return ops.wpd_souden_from_masks(Y.transpose(1, 2, 0), X_mask.T, ban=ban, taps=taps,
+                                     delay=delay, iterations=iterations, power_floor=power_floor,
+                                     frame_gate=frame_gate, ref_channel=ref_channel, ctx=ctx)
