@@ -76,6 +76,23 @@ class GssChannelSelect(ctypes.Structure):
                 ('floor', ctypes.c_double)]
 
 
+_TAPS = ctypes.POINTER(GssDebugTaps)
+# what the fused entries start with: ctx, params, obs_dev, D, N, act_dev, K, N_act, and of one
+# target its index and the two contexts
+_FUSED_HEAD = [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64, c_void_p, c_int,
+               c_int64]
+_FUSED_TARGET = [c_int, c_int64, c_int64]
+
+
+def _fused(*inserted, after_out=()):
+    """A fused one-target entry: the head, what the entry inserts, out_dev, what it adds behind
+    out_dev, the debug taps."""
+    return c_int, _FUSED_HEAD + _FUSED_TARGET + list(inserted) + [c_void_p, *after_out, _TAPS]
+
+
+# (S, target_index, start and end contexts of S targets)
+_FUSED_TARGETS = (c_int, _FUSED_HEAD + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, _TAPS])
+
 # name -> (restype, argtypes); every symbol include/gss_hip.h declares
 SIGNATURES = {
     'gss_device_count': (c_int, []),
@@ -150,10 +167,7 @@ SIGNATURES = {
     'gss_wpd_souden': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
                                ctypes.POINTER(GssBfWpd), c_int, c_void_p, c_void_p]),
     'gss_last_wpd_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
-    'gss_enhance_observation_wpd': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
-                ctypes.POINTER(GssBfWpd), c_void_p, ctypes.POINTER(GssDebugTaps)]),
+    'gss_enhance_observation_wpd': _fused(ctypes.POINTER(GssBfWpd)),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,
@@ -164,57 +178,28 @@ SIGNATURES = {
                                       c_void_p]),
     'gss_layout_permute_f64': (c_int, [c_void_p, c_void_p, c_int64, c_int64,
                                        c_int64, c_int, c_void_p]),
-    'gss_enhance_observation': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p,
-                ctypes.POINTER(GssDebugTaps)]),
+    'gss_enhance_observation': _fused(),
+    # (the guidance in the place of act_dev, no N_act)
     'gss_enhance_observation_guided': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                ctypes.POINTER(GssGuidance), c_int, c_int, c_int64, c_int64, c_void_p,
-                ctypes.POINTER(GssDebugTaps)]),
-    'gss_enhance_observation_segments': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
-                ctypes.POINTER(GssBfSegments), c_void_p, ctypes.POINTER(GssDebugTaps)]),
-    'gss_enhance_observation_lcmv': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
-                ctypes.POINTER(GssBfLcmv), c_void_p, ctypes.POINTER(GssDebugTaps)]),
-    'gss_enhance_observation_pcm16': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p,
-                ctypes.POINTER(GssDebugTaps)]),
-    'gss_enhance_observation_targets': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                ctypes.POINTER(GssDebugTaps)]),
-    'gss_enhance_observation_targets_pcm16': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                ctypes.POINTER(GssDebugTaps)]),
+        c_int, _FUSED_HEAD[:5] + [ctypes.POINTER(GssGuidance), c_int] + _FUSED_TARGET
+        + [c_void_p, _TAPS]),
+    'gss_enhance_observation_segments': _fused(ctypes.POINTER(GssBfSegments)),
+    'gss_enhance_observation_lcmv': _fused(ctypes.POINTER(GssBfLcmv)),
+    'gss_enhance_observation_pcm16': _fused(),
+    'gss_enhance_observation_targets': _FUSED_TARGETS,
+    'gss_enhance_observation_targets_pcm16': _FUSED_TARGETS,
     'gss_last_ref_channels': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), c_int]),
     'gss_channel_scores': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
                                    ctypes.POINTER(GssChannelSelect), c_void_p, c_void_p]),
     'gss_select_channels': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
                                     ctypes.POINTER(GssChannelSelect), c_void_p, c_void_p]),
     'gss_last_selected_channels': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), c_int]),
-    'gss_enhance_observation_select': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
-                ctypes.POINTER(GssChannelSelect), c_void_p, ctypes.POINTER(GssDebugTaps)]),
-    'gss_enhance_observation_select_pcm16': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_int64, c_int64,
-                ctypes.POINTER(GssChannelSelect), c_void_p, ctypes.POINTER(GssDebugTaps)]),
+    'gss_enhance_observation_select': _fused(ctypes.POINTER(GssChannelSelect)),
+    'gss_enhance_observation_select_pcm16': _fused(ctypes.POINTER(GssChannelSelect)),
     'gss_posterior_activity': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int,
                                        c_void_p, c_void_p, c_void_p]),
-    'gss_enhance_observation_activity': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
-                c_void_p, ctypes.POINTER(GssDebugTaps)]),
-    'gss_enhance_observation_host': (
-        c_int, [c_void_p, ctypes.POINTER(GssParams), c_void_p, c_int, c_int64,
-                c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_void_p]),
+    'gss_enhance_observation_activity': _fused(c_void_p, after_out=(c_void_p, c_void_p)),
+    'gss_enhance_observation_host': (c_int, _FUSED_HEAD + _FUSED_TARGET + [c_void_p]),
     'gss_workspace_bytes': (c_size_t, [c_void_p]),
     'gss_selftest_mfma': (c_int, [c_void_p]),
 }
@@ -442,12 +427,15 @@ class Context:
                     'profile_report')
         return json.loads(buf.value.decode())
 
+    def _last(self, symbol, ctype):
+        """One status word of the last call through its gss_last_* reader (synchronises)."""
+        out = ctype()
+        self._check(getattr(self.lib, symbol)(self.handle, ctypes.byref(out)), symbol)
+        return int(out.value)
+
     def last_ref_channel(self):
         """Reference channel of the last MVDR run (synchronises); -1 = non-finite SNR."""
-        out = ctypes.c_int32()
-        self._check(self.lib.gss_last_ref_channel(self.handle, ctypes.byref(out)),
-                    'gss_last_ref_channel')
-        return int(out.value)
+        return self._last('gss_last_ref_channel', ctypes.c_int32)
 
     def last_ref_channels(self, S):
         """Status words of the S targets of the last targets call (synchronises): the reference
@@ -471,42 +459,27 @@ class Context:
     def last_wpe_zero_pivots(self):
         """Pivots the WPE solve of the last call zeroed (synchronises); > 0 on live channels
         means rank-deficient normal equations (T <= taps * D), see include/gss_hip.h."""
-        out = ctypes.c_int64()
-        self._check(self.lib.gss_last_wpe_zero_pivots(self.handle, ctypes.byref(out)),
-                    'gss_last_wpe_zero_pivots')
-        return int(out.value)
+        return self._last('gss_last_wpe_zero_pivots', ctypes.c_int64)
 
     def last_wpd_zero_pivots(self):
         """Pivots the WPE steps of the last WPD call zeroed (synchronises); the WPE stage's own
         count stays in `last_wpe_zero_pivots`."""
-        out = ctypes.c_int64()
-        self._check(self.lib.gss_last_wpd_zero_pivots(self.handle, ctypes.byref(out)),
-                    'gss_last_wpd_zero_pivots')
-        return int(out.value)
+        return self._last('gss_last_wpd_zero_pivots', ctypes.c_int64)
 
     def last_segment_fallbacks(self):
         """(segment, frequency) pairs of the last segment-wise MVDR on this context that fell
         back to the whole-window statistics (synchronises)."""
-        out = ctypes.c_int64()
-        self._check(self.lib.gss_last_segment_fallbacks(self.handle, ctypes.byref(out)),
-                    'gss_last_segment_fallbacks')
-        return int(out.value)
+        return self._last('gss_last_segment_fallbacks', ctypes.c_int64)
 
     def last_lcmv_interferer(self):
         """The interferer class of the last LCMV mask / fused call on this context, -1 when it
         had none (synchronises)."""
-        out = ctypes.c_int32()
-        self._check(self.lib.gss_last_lcmv_interferer(self.handle, ctypes.byref(out)),
-                    'gss_last_lcmv_interferer')
-        return int(out.value)
+        return self._last('gss_last_lcmv_interferer', ctypes.c_int32)
 
     def last_lcmv_fallbacks(self):
         """Frequencies of the last LCMV beamformer on this context that fell back to the MVDR of
         the merged mask (synchronises)."""
-        out = ctypes.c_int64()
-        self._check(self.lib.gss_last_lcmv_fallbacks(self.handle, ctypes.byref(out)),
-                    'gss_last_lcmv_fallbacks')
-        return int(out.value)
+        return self._last('gss_last_lcmv_fallbacks', ctypes.c_int64)
 
     def workspace_bytes(self):
         return int(self.lib.gss_workspace_bytes(self.handle))

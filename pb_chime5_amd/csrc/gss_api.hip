@@ -19,6 +19,10 @@
     GSS_TRY(variant_refresh(ctx))
 static int variant_refresh(gss_ctx *ctx);
 
+// status words [0] and [2] (gss_ctx::status_host; the other words: GSS_STATUS_* in gss_internal.h)
+#define GSS_STATUS_REF_CHANNEL 0
+#define GSS_STATUS_WPE_ZERO_PIVOTS 2
+
 // ------------------------------------------------------------------ errors
 // (gss_host_malloc / gss_host_free are documented as callable from any thread -- the session
 // driver's loader threads grow their staging blocks on the first context while its owner
@@ -180,8 +184,8 @@ extern "C" int gss_create(int device_id, gss_ctx **out) {
         delete ctx;
         return GSS_ERR_HIP;
     }
-    ctx->status_host[0] = INT32_MIN;
-    ctx->status_host[2] = 0;
+    ctx->status_host[GSS_STATUS_REF_CHANNEL] = INT32_MIN;
+    ctx->status_host[GSS_STATUS_WPE_ZERO_PIVOTS] = 0;
     ctx->status_host[GSS_STATUS_SEGMENT_FALLBACKS] = 0;
     ctx->status_host[GSS_STATUS_LCMV_INTERFERER] = -1;
     ctx->status_host[GSS_STATUS_LCMV_FALLBACKS] = 0;
@@ -516,6 +520,44 @@ static int check_windows(gss_ctx *ctx) {
     return GSS_OK;
 }
 
+static int check_stft_bins(gss_ctx *ctx, int F, int64_t T, int D) {
+    const int64_t bins = (int64_t)F * T * D;
+    GSS_REQUIRE(ctx, bins < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
+                "the tensor with 32 bits)", (long long)bins);
+    return GSS_OK;
+}
+
+// beamforming_wrapper.py:44: assert D < 30
+static int check_bf_channels(gss_ctx *ctx, int D) {
+    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    return GSS_OK;
+}
+
+// pb_bss CACGMMTrainer.fit: assert K < 20 (-> AssertionError in the reference too)
+static int check_class_count(gss_ctx *ctx, int K) {
+    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_MAX_CLASSES, GSS_ERR_INVALID,
+                "cacgmm: assert 1 <= K < 20 failed: K=%d", K);
+    return GSS_OK;
+}
+
+static int check_target_index(gss_ctx *ctx, int target, int K) {
+    GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
+                "target_index %d outside [0, %d)", target, K);
+    return GSS_OK;
+}
+
+// The WPE argument rule.  `fixed_schedule` (gss_wpe_weighted, one iteration without a PSD
+// context): the message names only what the caller gave.
+static int check_wpe_args(gss_ctx *ctx, const char *what, int taps, int delay, int iterations,
+                          int psd_context, bool fixed_schedule = false) {
+    if (taps >= 1 && delay >= 0 && iterations >= 0 && psd_context >= 0) return GSS_OK;
+    if (fixed_schedule)
+        return gss_fail(ctx, GSS_ERR_INVALID, "%s: taps=%d delay=%d", what, taps, delay);
+    return gss_fail(ctx, GSS_ERR_INVALID, "%s: taps=%d delay=%d iterations=%d psd_context=%d", what,
+                    taps, delay, iterations, psd_context);
+}
+
 extern "C" int gss_stft(gss_ctx *ctx, const double *x, int D, int64_t N, int fading,
                         gss_cplx *Y) {
     GSS_ENTER(ctx);
@@ -547,12 +589,8 @@ extern "C" int gss_wpe(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
     GSS_REQUIRE(ctx, Y && X && F >= 1 && T >= 1, GSS_ERR_INVALID, "gss_wpe: bad arguments");
     GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
                 "gss_wpe: D=%d outside [1, %d]", D, GSS_MAX_CHANNELS);
-    GSS_REQUIRE(ctx, taps >= 1 && delay >= 0 && iterations >= 0 && psd_context >= 0,
-                GSS_ERR_INVALID, "gss_wpe: taps=%d delay=%d iterations=%d psd_context=%d", taps,
-                delay, iterations, psd_context);
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_wpe_args(ctx, "gss_wpe", taps, delay, iterations, psd_context));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, wpe_workspace_bytes(F, T, D, taps, delay)));
     return wpe_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, taps, delay, iterations,
                    psd_context, reinterpret_cast<cplx *>(X));
@@ -566,12 +604,8 @@ extern "C" int gss_wpe_arrays(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T,
     const int D = A * C;
     GSS_REQUIRE(ctx, D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
                 "gss_wpe_arrays: A * C = %d outside [1, %d]", D, GSS_MAX_CHANNELS);
-    GSS_REQUIRE(ctx, taps >= 1 && delay >= 0 && iterations >= 0 && psd_context >= 0,
-                GSS_ERR_INVALID, "gss_wpe_arrays: taps=%d delay=%d iterations=%d psd_context=%d",
-                taps, delay, iterations, psd_context);
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_wpe_args(ctx, "gss_wpe_arrays", taps, delay, iterations, psd_context));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     if (A == 1) {       // one array: gss_wpe itself
         GSS_REQUIRE(ctx, X != Y || iterations == 0, GSS_ERR_INVALID,
                     "gss_wpe_arrays: X must not alias Y");
@@ -597,9 +631,7 @@ extern "C" int gss_wpe_inverse_power(gss_ctx *ctx, const gss_cplx *Y, int F, int
                 "gss_wpe_inverse_power: bad arguments");
     GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
                 "gss_wpe_inverse_power: D=%d outside [1, %d]", D, GSS_MAX_CHANNELS);
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported",
-                (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, sizeof(double) * (size_t)F * T + 8192));
     return wpe_inverse_power_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, psd_context,
                                  inverse_power);
@@ -608,9 +640,7 @@ extern "C" int gss_wpe_inverse_power(gss_ctx *ctx, const gss_cplx *Y, int F, int
 static int check_cacgmm_args(gss_ctx *ctx, int D, int K, int iterations, int post) {
     GSS_REQUIRE(ctx, D >= 2 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
                 "cacgmm: D=%d outside [2, %d]", D, GSS_MAX_CHANNELS);
-    // pb_bss CACGMMTrainer.fit: assert K < 20 (-> AssertionError in the reference too)
-    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_MAX_CLASSES, GSS_ERR_INVALID,
-                "cacgmm: assert 1 <= K < 20 failed: K=%d", K);
+    GSS_TRY(check_class_count(ctx, K));
     GSS_REQUIRE(ctx, iterations >= 1 && post >= 0, GSS_ERR_INVALID,
                 "cacgmm: iterations=%d iterations_post=%d", iterations, post);
     return GSS_OK;
@@ -623,12 +653,21 @@ extern "C" int gss_cacgmm(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int
     GSS_REQUIRE(ctx, Y && act && gamma && F >= 1 && T >= 1, GSS_ERR_INVALID,
                 "gss_cacgmm: bad arguments");
     GSS_TRY(check_cacgmm_args(ctx, D, K, iterations, post));
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, cacgmm_workspace_bytes(F, T, D, K)));
     return cacgmm_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D,
                       em_guide_from_activity(act, T), K, iterations, post, gamma);
+}
+
+static int check_mask_strides(gss_ctx *ctx, const gss_guidance *g, int K, int64_t T) {
+    GSS_REQUIRE(ctx, g->mask_k_stride >= T, GSS_ERR_INVALID,
+                "guidance: mask_k_stride %lld is smaller than T = %lld",
+                (long long)g->mask_k_stride, (long long)T);
+    GSS_REQUIRE(ctx, g->mask_f_stride == 0 || g->mask_f_stride >= K * g->mask_k_stride,
+                GSS_ERR_INVALID, "guidance: mask_f_stride %lld is smaller than K * "
+                "mask_k_stride = %lld", (long long)g->mask_f_stride,
+                (long long)(K * g->mask_k_stride));
+    return GSS_OK;
 }
 
 // The descriptor's rules (include/gss_hip.h) -> the EM's view of it.  The values behind the
@@ -646,15 +685,7 @@ static int check_guidance(gss_ctx *ctx, const gss_guidance *g, int K, int64_t T,
                     "init_k_stride = %lld", (long long)g->init_f_stride,
                     (long long)(K * g->init_k_stride));
     }
-    if (g->mask_dev) {
-        GSS_REQUIRE(ctx, g->mask_k_stride >= T, GSS_ERR_INVALID,
-                    "guidance: mask_k_stride %lld is smaller than T = %lld",
-                    (long long)g->mask_k_stride, (long long)T);
-        GSS_REQUIRE(ctx, g->mask_f_stride == 0 || g->mask_f_stride >= K * g->mask_k_stride,
-                    GSS_ERR_INVALID, "guidance: mask_f_stride %lld is smaller than K * "
-                    "mask_k_stride = %lld", (long long)g->mask_f_stride,
-                    (long long)(K * g->mask_k_stride));
-    }
+    if (g->mask_dev) GSS_TRY(check_mask_strides(ctx, g, K, T));
     *out = EmGuide{g->init_dev, g->mask_dev, g->init_dev ? g->init_f_stride : 0,
                    g->init_dev ? g->init_k_stride : 0, g->mask_dev ? g->mask_f_stride : 0,
                    g->mask_dev ? g->mask_k_stride : 0};
@@ -670,9 +701,7 @@ extern "C" int gss_cacgmm_guided(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t
     GSS_TRY(check_cacgmm_args(ctx, D, K, iterations, post));
     EmGuide guide;
     GSS_TRY(check_guidance(ctx, g, K, T, &guide));
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, cacgmm_workspace_bytes(F, T, D, K)));
     return cacgmm_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, guide, K, iterations, post,
                       gamma);
@@ -684,13 +713,7 @@ extern "C" int gss_cacgmm_guided(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t
 static int check_mask_guidance(gss_ctx *ctx, const gss_guidance *g, int K, int64_t T, EmGuide *out) {
     *out = EmGuide{};
     if (!g || !g->mask_dev) return GSS_OK;
-    GSS_REQUIRE(ctx, g->mask_k_stride >= T, GSS_ERR_INVALID,
-                "guidance: mask_k_stride %lld is smaller than T = %lld",
-                (long long)g->mask_k_stride, (long long)T);
-    GSS_REQUIRE(ctx, g->mask_f_stride == 0 || g->mask_f_stride >= K * g->mask_k_stride,
-                GSS_ERR_INVALID, "guidance: mask_f_stride %lld is smaller than K * "
-                "mask_k_stride = %lld", (long long)g->mask_f_stride,
-                (long long)(K * g->mask_k_stride));
+    GSS_TRY(check_mask_strides(ctx, g, K, T));
     out->mask = g->mask_dev;
     out->mask_f_stride = g->mask_f_stride;
     out->mask_k_stride = g->mask_k_stride;
@@ -727,9 +750,7 @@ extern "C" int gss_cacgmm_fit(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T,
     } else {
         GSS_TRY(check_guidance(ctx, g, K, T, &guide));
     }
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     if (iterations == 0) {
         // fit(initialization=model, iterations=0) is the model
         const size_t fk = (size_t)F * K;
@@ -772,9 +793,7 @@ extern "C" int gss_cacgmm_predict(gss_ctx *ctx, const gss_cplx *Y, int F, int64_
                 "gss_cacgmm_predict: gamma_dev and loglik_dev are both NULL");
     EmGuide guide;
     GSS_TRY(check_mask_guidance(ctx, g, K, T, &guide));
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     // the workspace of THIS call's (F, T, D, K): a predict may see more frames than any fit did
     GSS_TRY(arena_reserve(ctx, cacgmm_workspace_bytes(F, T, D, K)));
     const EmModel in = em_model(model);
@@ -792,8 +811,7 @@ extern "C" int gss_masks_from_posteriors(gss_ctx *ctx, const double *gamma, int 
     GSS_ENTER(ctx);
     GSS_REQUIRE(ctx, gamma && mx && mn && F >= 1 && T >= 1 && K >= 1, GSS_ERR_INVALID,
                 "gss_masks_from_posteriors: bad arguments");
-    GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
-                "target_index %d outside [0, %d)", target, K);
+    GSS_TRY(check_target_index(ctx, target, K));
     return masks_from_posteriors_run(ctx, gamma, F, K, T, target, drop, sf, ef, mx, mn);
 }
 
@@ -803,11 +821,8 @@ extern "C" int gss_mvdr_souden(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T
     GSS_ENTER(ctx);
     GSS_REQUIRE(ctx, Y && mx && mn && Xhat && F >= 1 && T >= 1, GSS_ERR_INVALID,
                 "gss_mvdr_souden: bad arguments");
-    // beamforming_wrapper.py:44: assert D < 30
-    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_bf_channels(ctx, D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, mvdr_workspace_bytes(F, T, D)));
     return mvdr_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mx, mn, ban,
                     reinterpret_cast<cplx *>(Xhat), ref);
@@ -819,23 +834,27 @@ extern "C" int gss_mvdr_souden_ref(gss_ctx *ctx, const gss_cplx *Y, int F, int64
     GSS_ENTER(ctx);
     GSS_REQUIRE(ctx, Y && mx && mn && Xhat && F >= 1 && T >= 1, GSS_ERR_INVALID,
                 "gss_mvdr_souden_ref: bad arguments");
-    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    GSS_TRY(check_bf_channels(ctx, D));
     GSS_REQUIRE(ctx, ref_channel >= 0 && ref_channel < D, GSS_ERR_INVALID,
                 "ref_channel %d outside [0, %d)", ref_channel, D);
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, mvdr_workspace_bytes(F, T, D)));
     return mvdr_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mx, mn, ban,
                     reinterpret_cast<cplx *>(Xhat), nullptr, /*gev=*/0, ref_channel);
 }
 
-extern "C" int gss_last_ref_channel(gss_ctx *ctx, int32_t *ref_channel) {
+// One status word of the last call (gss_ctx::status_host), after the context's stream has drained.
+template <typename Out>
+static int read_status_word(gss_ctx *ctx, int word, Out *out, const char *entry) {
     GSS_ENTER(ctx);
-    GSS_REQUIRE(ctx, ref_channel, GSS_ERR_INVALID, "gss_last_ref_channel: NULL");
+    GSS_REQUIRE(ctx, out, GSS_ERR_INVALID, "%s: NULL", entry);
     GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    *ref_channel = __atomic_load_n(ctx->status_host, __ATOMIC_ACQUIRE);
+    *out = __atomic_load_n(ctx->status_host + word, __ATOMIC_ACQUIRE);
     return GSS_OK;
+}
+
+extern "C" int gss_last_ref_channel(gss_ctx *ctx, int32_t *ref_channel) {
+    return read_status_word(ctx, GSS_STATUS_REF_CHANNEL, ref_channel, "gss_last_ref_channel");
 }
 
 extern "C" int gss_last_ref_channels(gss_ctx *ctx, int32_t *ref_channels, int S) {
@@ -852,11 +871,7 @@ extern "C" int gss_last_ref_channels(gss_ctx *ctx, int32_t *ref_channels, int S)
 }
 
 extern "C" int gss_last_wpe_zero_pivots(gss_ctx *ctx, int64_t *count) {
-    GSS_ENTER(ctx);
-    GSS_REQUIRE(ctx, count, GSS_ERR_INVALID, "gss_last_wpe_zero_pivots: NULL");
-    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    *count = __atomic_load_n(ctx->status_host + 2, __ATOMIC_ACQUIRE);
-    return GSS_OK;
+    return read_status_word(ctx, GSS_STATUS_WPE_ZERO_PIVOTS, count, "gss_last_wpe_zero_pivots");
 }
 
 static int check_segments(gss_ctx *ctx, const gss_bf_segments *seg, const char *what) {
@@ -878,24 +893,18 @@ extern "C" int gss_mvdr_souden_segments(gss_ctx *ctx, const gss_cplx *Y, int F, 
     GSS_ENTER(ctx);
     GSS_REQUIRE(ctx, Y && mx && mn && Xhat && F >= 1 && T >= 1, GSS_ERR_INVALID,
                 "gss_mvdr_souden_segments: bad arguments");
-    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    GSS_TRY(check_bf_channels(ctx, D));
     GSS_REQUIRE(ctx, ref_channel >= -1 && ref_channel < D, GSS_ERR_INVALID,
                 "ref_channel %d outside [-1, %d)", ref_channel, D);
     GSS_TRY(check_segments(ctx, seg, "gss_mvdr_souden_segments"));
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, mvdr_segments_workspace_bytes(F, T, D, seg->segment_frames)));
     return mvdr_segments_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mx, mn, ban, *seg,
                              reinterpret_cast<cplx *>(Xhat), ref, ref_channel);
 }
 
 extern "C" int gss_last_segment_fallbacks(gss_ctx *ctx, int64_t *count) {
-    GSS_ENTER(ctx);
-    GSS_REQUIRE(ctx, count, GSS_ERR_INVALID, "gss_last_segment_fallbacks: NULL");
-    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    *count = __atomic_load_n(ctx->status_host + GSS_STATUS_SEGMENT_FALLBACKS, __ATOMIC_ACQUIRE);
-    return GSS_OK;
+    return read_status_word(ctx, GSS_STATUS_SEGMENT_FALLBACKS, count, "gss_last_segment_fallbacks");
 }
 
 extern "C" int gss_wpe_weighted(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D, int taps,
@@ -905,11 +914,8 @@ extern "C" int gss_wpe_weighted(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t 
                 "gss_wpe_weighted: bad arguments");
     GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
                 "gss_wpe_weighted: D=%d outside [1, %d]", D, GSS_MAX_CHANNELS);
-    GSS_REQUIRE(ctx, taps >= 1 && delay >= 0, GSS_ERR_INVALID, "gss_wpe_weighted: taps=%d delay=%d",
-                taps, delay);
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_wpe_args(ctx, "gss_wpe_weighted", taps, delay, 1, 0, /*fixed_schedule=*/true));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, wpe_workspace_bytes(F, T, D, taps, delay)));
     const WpeCallerWeights cw{weights, 2, false};
     return wpe_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, taps, delay, 1, 0,
@@ -932,7 +938,7 @@ static int check_wpd(gss_ctx *ctx, const gss_bf_wpd *wpd, int D, const char *wha
     GSS_REQUIRE(ctx, wpd->iterations >= 1, GSS_ERR_INVALID, "%s: iterations = %d is smaller than 1",
                 what, wpd->iterations);
     GSS_TRY(check_power_floor(ctx, wpd->power_floor, what));
-    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    GSS_TRY(check_bf_channels(ctx, D));
     return GSS_OK;
 }
 
@@ -945,11 +951,9 @@ extern "C" int gss_wpd_weights(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T
                 "gss_wpd_weights: neither Xhat_dev nor Y_dev with mask_dev");
     GSS_REQUIRE(ctx, F >= 1 && T >= 1, GSS_ERR_INVALID, "gss_wpd_weights: F=%d T=%lld", F,
                 (long long)T);
-    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    GSS_TRY(check_bf_channels(ctx, D));
     GSS_TRY(check_power_floor(ctx, power_floor, "gss_wpd_weights"));
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     return wpd_weights_run(ctx, reinterpret_cast<const cplx *>(Y), mask,
                            reinterpret_cast<const cplx *>(Xhat), gate, F, T, D, power_floor,
                            weights, nullptr);
@@ -967,20 +971,14 @@ extern "C" int gss_wpd_souden(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T,
     GSS_TRY(check_wpd(ctx, wpd, D, "gss_wpd_souden"));
     GSS_REQUIRE(ctx, ref_channel >= -1 && ref_channel < D, GSS_ERR_INVALID,
                 "ref_channel %d outside [-1, %d)", ref_channel, D);
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, wpd_workspace_bytes(F, T, D, wpd->taps, wpd->delay)));
     return wpd_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mask, gate, *wpd, ref_channel,
                    reinterpret_cast<cplx *>(Xhat), ref);
 }
 
 extern "C" int gss_last_wpd_zero_pivots(gss_ctx *ctx, int64_t *count) {
-    GSS_ENTER(ctx);
-    GSS_REQUIRE(ctx, count, GSS_ERR_INVALID, "gss_last_wpd_zero_pivots: NULL");
-    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    *count = __atomic_load_n(ctx->status_host + GSS_STATUS_WPD_ZERO_PIVOTS, __ATOMIC_ACQUIRE);
-    return GSS_OK;
+    return read_status_word(ctx, GSS_STATUS_WPD_ZERO_PIVOTS, count, "gss_last_wpd_zero_pivots");
 }
 
 // The descriptor's rules (include/gss_hip.h); K bounds the class indices.
@@ -999,8 +997,7 @@ static int check_lcmv(gss_ctx *ctx, const gss_bf_lcmv *lcmv, int K, int target, 
 static int check_lcmv_channels(gss_ctx *ctx, int D, const char *what) {
     GSS_REQUIRE(ctx, D >= 2, GSS_ERR_INVALID, "%s: D = %d, the LCMV needs at least 2 channels",
                 what, D);
-    GSS_REQUIRE(ctx, D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
-    return GSS_OK;
+    return check_bf_channels(ctx, D);
 }
 
 extern "C" int gss_lcmv_souden(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
@@ -1014,9 +1011,7 @@ extern "C" int gss_lcmv_souden(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T
                 "gss_lcmv_souden: min_mass = %g is negative or not finite", min_mass);
     GSS_REQUIRE(ctx, ref_channel >= -1 && ref_channel < D, GSS_ERR_INVALID,
                 "ref_channel %d outside [-1, %d)", ref_channel, D);
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, lcmv_workspace_bytes(F, T, D)));
     return lcmv_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mx, mi, mn, ban, ref_channel,
                     min_mass, reinterpret_cast<cplx *>(Xhat), ref);
@@ -1029,10 +1024,8 @@ extern "C" int gss_lcmv_masks_from_posteriors(gss_ctx *ctx, const double *gamma,
     GSS_ENTER(ctx);
     GSS_REQUIRE(ctx, gamma && mx && mi && mn && F >= 1 && T >= 1, GSS_ERR_INVALID,
                 "gss_lcmv_masks_from_posteriors: bad arguments");
-    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_MAX_CLASSES, GSS_ERR_INVALID,
-                "cacgmm: assert 1 <= K < 20 failed: K=%d", K);
-    GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
-                "target_index %d outside [0, %d)", target, K);
+    GSS_TRY(check_class_count(ctx, K));
+    GSS_TRY(check_target_index(ctx, target, K));
     GSS_TRY(check_lcmv(ctx, lcmv, K, target, "gss_lcmv_masks_from_posteriors"));
     GSS_TRY(arena_reserve(ctx, lcmv_masks_workspace_bytes(F, K)));
     return lcmv_masks_run(ctx, gamma, F, K, T, target, *lcmv, drop, sf, ef, mx, mi, mn,
@@ -1040,19 +1033,11 @@ extern "C" int gss_lcmv_masks_from_posteriors(gss_ctx *ctx, const double *gamma,
 }
 
 extern "C" int gss_last_lcmv_interferer(gss_ctx *ctx, int32_t *interferer) {
-    GSS_ENTER(ctx);
-    GSS_REQUIRE(ctx, interferer, GSS_ERR_INVALID, "gss_last_lcmv_interferer: NULL");
-    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    *interferer = __atomic_load_n(ctx->status_host + GSS_STATUS_LCMV_INTERFERER, __ATOMIC_ACQUIRE);
-    return GSS_OK;
+    return read_status_word(ctx, GSS_STATUS_LCMV_INTERFERER, interferer, "gss_last_lcmv_interferer");
 }
 
 extern "C" int gss_last_lcmv_fallbacks(gss_ctx *ctx, int64_t *count) {
-    GSS_ENTER(ctx);
-    GSS_REQUIRE(ctx, count, GSS_ERR_INVALID, "gss_last_lcmv_fallbacks: NULL");
-    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    *count = __atomic_load_n(ctx->status_host + GSS_STATUS_LCMV_FALLBACKS, __ATOMIC_ACQUIRE);
-    return GSS_OK;
+    return read_status_word(ctx, GSS_STATUS_LCMV_FALLBACKS, count, "gss_last_lcmv_fallbacks");
 }
 
 extern "C" int gss_gev(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D, const double *mx,
@@ -1060,10 +1045,8 @@ extern "C" int gss_gev(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
     GSS_ENTER(ctx);
     GSS_REQUIRE(ctx, Y && mx && mn && Xhat && F >= 1 && T >= 1, GSS_ERR_INVALID,
                 "gss_gev: bad arguments");
-    GSS_REQUIRE(ctx, D >= 1 && D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_bf_channels(ctx, D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, mvdr_workspace_bytes(F, T, D)));
     return mvdr_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mx, mn, ban,
                     reinterpret_cast<cplx *>(Xhat), nullptr, /*gev=*/1);
@@ -1094,9 +1077,7 @@ extern "C" int gss_channel_scores(gss_ctx *ctx, const gss_cplx *Y, int F, int64_
     GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
                 "gss_channel_scores: D=%d outside [1, %d]", D, GSS_MAX_CHANNELS);
     GSS_TRY(check_channel_select(ctx, sel, D, false, "gss_channel_scores"));
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported",
-                (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, chsel_workspace_bytes(F, T, D, sel->bands)));
     return chsel_scores_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, *sel, scores,
                             band_var);
@@ -1111,9 +1092,7 @@ extern "C" int gss_select_channels(gss_ctx *ctx, const gss_cplx *Y, int F, int64
     GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
                 "gss_select_channels: D=%d outside [1, %d]", D, GSS_MAX_CHANNELS);
     GSS_TRY(check_channel_select(ctx, sel, D, true, "gss_select_channels"));
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported",
-                (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     GSS_TRY(arena_reserve(ctx, chsel_workspace_bytes(F, T, D, sel->bands)));
     return chsel_select_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, *sel,
                             reinterpret_cast<cplx *>(Ysel), channels);
@@ -1244,15 +1223,39 @@ static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, in
     return stage;
 }
 
-// (segment_frames > 0: the segment-wise beamformer in the place of the whole-window one; lcmv:
-// the interferer-nulling one, with four mask buffers;
-// select_bands > 0: D is the number of channels kept out of select_D, and the selection stage
-// needs its own workspace and, when it gathers, the STFT of all select_D channels;
+// What gss_enhance_observation_activity adds to the call: the posterior activity of the
+// pipeline's own X and gamma (weights (F,) or NULL, scores (K,T), power (T) or NULL).
+struct PipelineActivity {
+    const double *weights = nullptr;
+    double *scores = nullptr, *power = nullptr;     // scores == NULL: no posterior activity
+};
+
+// What an entry point adds to the plain one-target call on float64 samples
+// (gss_enhance_observation); each entry fills its own field.  `guided` / `select` say what kind
+// of call it is, apart from the descriptor, so that a NULL descriptor is reported and not taken
+// for a plain call.
+struct PipelineCall {
+    const char *entry = "gss_enhance_observation";   // the name in the messages
+    int obs_type = 0;                                // samples of obs: 0 = float64, 1 = int16 PCM
+    bool guided = false;
+    const gss_guidance *guidance = nullptr;
+    bool select = false;
+    const gss_channel_select *sel = nullptr;
+    const gss_bf_segments *seg = nullptr;            // the segment-wise beamformer
+    const gss_bf_lcmv *lcmv = nullptr;               // the interferer-nulling beamformer
+    const gss_bf_wpd *wpd = nullptr;                 // the WPD beamformer
+    PipelineActivity activity;
+};
+
+// (seg: the segment-wise beamformer in the place of the whole-window one; lcmv: the
+// interferer-nulling one, with four mask buffers;
+// select: D is the number of channels kept out of D_all, and the selection stage needs its own
+// workspace and, when it gathers, the STFT of all D_all channels;
 // activity: the posterior activity runs between the front and the masks)
 static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
-                                 int K, int64_t segment_frames = 0, int select_bands = 0,
-                                 int select_D = 0, bool lcmv = false, bool activity = false,
-                                 const gss_bf_wpd *wpd = nullptr) {
+                                 int K, int D_all, const PipelineCall &call) {
+    const gss_bf_wpd *const wpd = call.wpd;
+    const bool lcmv = call.lcmv != nullptr;
     size_t b = front_buffer_bytes(F, T, T_act, D, K);
     // (WPD: the raw STFT beside the WPE output -- the joint WPE leaves it in Y's buffer, the
     // per-array WPE overwrites that one -- and the frame gate)
@@ -1262,19 +1265,20 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
     b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
     b += 4096;
     size_t stage = front_stage_bytes(p, F, T, D, K);
-    stage = std::max(stage, segment_frames > 0
-                                ? mvdr_segments_workspace_bytes(F, T, D, segment_frames)
+    stage = std::max(stage, call.seg
+                                ? mvdr_segments_workspace_bytes(F, T, D, call.seg->segment_frames)
                                 : mvdr_workspace_bytes(F, T, D));
     if (lcmv)
         stage = std::max(stage, std::max(lcmv_workspace_bytes(F, T, D),
                                          lcmv_masks_workspace_bytes(F, K)));
     if (wpd) stage = std::max(stage, wpd_workspace_bytes(F, T, D, wpd->taps, wpd->delay));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
-    if (activity) stage = std::max(stage, pact_workspace_bytes(F, T, K));   // the partial planes
-    if (select_bands > 0)
-        stage = std::max(stage, chsel_workspace_bytes(F, T, select_D, select_bands) +
-                                    (select_D > D ? align_up(sizeof(cplx) * (size_t)F * T * select_D)
-                                                  : 0) + 4096);
+    if (call.activity.scores)
+        stage = std::max(stage, pact_workspace_bytes(F, T, K));   // the partial planes
+    if (call.select)
+        stage = std::max(stage, chsel_workspace_bytes(F, T, D_all, call.sel->bands) +
+                                    (D_all > D ? align_up(sizeof(cplx) * (size_t)F * T * D_all)
+                                               : 0) + 4096);
     return b + stage + (1 << 16);
 }
 
@@ -1310,8 +1314,7 @@ static int check_pipeline_rest(gss_ctx *ctx, const gss_params *p, int D, int64_t
                                int64_t N_act, int64_t *T_out, int64_t *T_act_out) {
     GSS_TRY(check_cacgmm_args(ctx, D, K, p->bss_iterations, p->bss_iterations_post));
     if (p->wpe) GSS_TRY(check_wpe_arrays(ctx, p, D));   // (no WPE: the field is not read)
-    if (p->bf == 0 || p->bf == 3)
-        GSS_REQUIRE(ctx, D < 30, GSS_ERR_INVALID, "assert D < 30 failed: D=%d", D);
+    if (p->bf == 0 || p->bf == 3) GSS_TRY(check_bf_channels(ctx, D));
     if (p->bf == 1)
         GSS_REQUIRE(ctx, D > 2, GSS_ERR_INVALID, "bf='ch2' needs more than 2 channels");
 
@@ -1325,9 +1328,7 @@ static int check_pipeline_rest(gss_ctx *ctx, const gss_params *p, int D, int64_t
                 "activity covers %lld frames but the observation has %lld",
                 (long long)T_act, (long long)T);
 
-    GSS_REQUIRE(ctx, (int64_t)F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
-                "F * T * D = %lld STFT bins: 2^31 or more are not supported (some kernels index "
-                "the tensor with 32 bits)", (long long)((int64_t)F * T * D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
     *T_out = T;
     *T_act_out = T_act;
     return GSS_OK;
@@ -1354,19 +1355,20 @@ static int alloc_front(gss_ctx *ctx, const gss_params *p, int F, int64_t T, int6
 // STFT, WPE (joint or per array), frame activity and the guided CACGMM of one window: obs ->
 // X (F,T,D) and gamma (F,K,T), nothing of it depending on a target.  Stage workspace above
 // `mark` is released after each stage.  `guide` (a guided call): the model's guidance per STFT
-// frame as the caller gives it, instead of the frame activity made from `act`.
-static int run_front(gss_ctx *ctx, const gss_params *p, const void *obs, int obs_type, int D,
-                     int64_t N, const uint8_t *act, int K, int64_t N_act, int F, int64_t T,
-                     int64_t T_act, const PipelineFront &fr, size_t mark,
-                     const EmGuide *guide = nullptr, const gss_channel_select *sel = nullptr,
-                     int D_all = 0) {
+// frame as the caller gives it, instead of the frame activity made from `act`.  `D_all` (a
+// selection): the channels of `obs`, of which D are kept.
+static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call, const void *obs,
+                     int D_all, int D, int64_t N, const uint8_t *act, int K, int64_t N_act, int F,
+                     int64_t T, int64_t T_act, const PipelineFront &fr, size_t mark,
+                     const EmGuide &guide) {
+    const int obs_type = call.obs_type;
     cplx *const Y = fr.Y, *const X = fr.X;
-    if (!sel) {
+    if (!call.select) {
         GSS_TRY(stft_run(ctx, obs, obs_type, D, N, p->stft_fading, Y));
     } else if (D == D_all) {
         // every channel is kept: ranked (the status words name them), nothing moves
         GSS_TRY(stft_run(ctx, obs, obs_type, D, N, p->stft_fading, Y));
-        GSS_TRY(chsel_select_run(ctx, Y, F, T, D, *sel, nullptr, nullptr));
+        GSS_TRY(chsel_select_run(ctx, Y, F, T, D, *call.sel, nullptr, nullptr));
         ctx->arena_off = mark;
     } else {
         // the STFT of all D_all channels lives above `mark` until the kept D = sel->keep of
@@ -1374,14 +1376,15 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const void *obs, int obs
         cplx *Yall = arena_alloc_t<cplx>(ctx, (size_t)F * T * D_all);
         GSS_REQUIRE(ctx, Yall, GSS_ERR_NOMEM, "workspace sizing bug");
         GSS_TRY(stft_run(ctx, obs, obs_type, D_all, N, p->stft_fading, Yall));
-        GSS_TRY(chsel_select_run(ctx, Yall, F, T, D_all, *sel, Y, nullptr));
+        GSS_TRY(chsel_select_run(ctx, Yall, F, T, D_all, *call.sel, Y, nullptr));
         ctx->arena_off = mark;
     }
     if (fr.Yraw)
         GSS_HIP_CHECK(ctx, hipMemcpyAsync(fr.Yraw, Y, sizeof(cplx) * (size_t)F * T * D,
                                           hipMemcpyDeviceToDevice, ctx->stream));
     if (!p->wpe)    // no solve in this call: clear the count an earlier utterance left behind
-        GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + 2, 0, sizeof(int32_t), ctx->stream));
+        GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + GSS_STATUS_WPE_ZERO_PIVOTS, 0,
+                                          sizeof(int32_t), ctx->stream));
     const int A = wpe_arrays_of(p);
     if (p->wpe && A == 1) {
         GSS_TRY(pipeline_wpe(ctx, p, Y, F, T, D, X));
@@ -1395,9 +1398,9 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const void *obs, int obs
         GSS_TRY(wpe_arrays_regroup_run(ctx, Y, F, T, A, D / A, false, X));
         ctx->arena_off = mark;
     }
-    if (!guide) GSS_TRY(activity_run(ctx, act, K, N_act, p->stft_fading, fr.actf));
-    GSS_TRY(cacgmm_run(ctx, X, F, T, D, guide ? *guide : em_guide_from_activity(fr.actf, T_act), K,
-                       p->bss_iterations, p->bss_iterations_post, fr.gamma));
+    if (!call.guided) GSS_TRY(activity_run(ctx, act, K, N_act, p->stft_fading, fr.actf));
+    GSS_TRY(cacgmm_run(ctx, X, F, T, D, call.guided ? guide : em_guide_from_activity(fr.actf, T_act),
+                       K, p->bss_iterations, p->bss_iterations_post, fr.gamma));
     ctx->arena_off = mark;
     return GSS_OK;
 }
@@ -1420,52 +1423,31 @@ static int copy_front_taps(gss_ctx *ctx, const gss_debug_taps *taps, const Pipel
     return GSS_OK;
 }
 
-// What gss_enhance_observation_activity adds to the call: the posterior activity of the
-// pipeline's own X and gamma (weights (F,) or NULL, scores (K,T), power (T) or NULL).
-struct PipelineActivity {
-    const double *weights;
-    double *scores, *power;
-};
-
-static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const void *obs,
-                                    int obs_type, int D, int64_t N, const uint8_t *act, int K,
-                                    int64_t N_act, int target, int64_t start_ctx, int64_t end_ctx,
-                                    double *out, const gss_debug_taps *taps,
-                                    bool guided = false,
-                                    const gss_guidance *guidance = nullptr,
-                                    const gss_bf_segments *seg = nullptr,
-                                    const gss_channel_select *sel = nullptr,
-                                    bool select = false,
-                                    const gss_bf_lcmv *lcmv = nullptr,
-                                    const PipelineActivity *pact = nullptr,
-                                    const gss_bf_wpd *wpd = nullptr) {
-    GSS_REQUIRE(ctx, !guided || guidance, GSS_ERR_INVALID,
+static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const void *obs, int D,
+                                    int64_t N, const uint8_t *act, int K, int64_t N_act,
+                                    int target, int64_t start_ctx, int64_t end_ctx, double *out,
+                                    const gss_debug_taps *taps, const PipelineCall &call) {
+    GSS_REQUIRE(ctx, !call.guided || call.guidance, GSS_ERR_INVALID,
                 "gss_enhance_observation_guided: guidance is NULL");
-    GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, guided ? (const void *)guidance : act, out,
-                                 guided ? "gss_enhance_observation_guided"
-                                 : select ? "gss_enhance_observation_select"
-                                          : "gss_enhance_observation"));
+    GSS_TRY(check_pipeline_front(ctx, p, obs, D, N,
+                                 call.guided ? (const void *)call.guidance : act, out, call.entry));
     // a selection: D_all channels come in, the pipeline below runs on the D = sel->keep kept
     const int D_all = D;
-    if (select) {
-        GSS_TRY(check_channel_select(ctx, sel, D, true, "gss_enhance_observation_select"));
+    if (call.select) {
+        GSS_TRY(check_channel_select(ctx, call.sel, D, true, "gss_enhance_observation_select"));
         GSS_REQUIRE(ctx, !(p->wpe && p->wpe_arrays > 1), GSS_ERR_UNSUPPORTED,
                     "gss_enhance_observation_select: wpe_arrays=%d, a selection breaks the equal "
                     "arrays of the per-array WPE", p->wpe_arrays);
         GSS_REQUIRE(ctx, p->bf != 1, GSS_ERR_UNSUPPORTED,
                     "gss_enhance_observation_select: bf=1 ('ch2') names a physical channel");
         const int64_t T_all = gss_stft_num_frames(N, p->stft_size, p->stft_shift, p->stft_fading);
-        GSS_REQUIRE(ctx, (int64_t)(p->stft_size / 2 + 1) * T_all * D_all < (1LL << 31),
-                    GSS_ERR_UNSUPPORTED,
-                    "F * T * D = %lld STFT bins: 2^31 or more are not supported",
-                    (long long)((int64_t)(p->stft_size / 2 + 1) * T_all * D_all));
-        D = sel->keep;
+        GSS_TRY(check_stft_bins(ctx, p->stft_size / 2 + 1, T_all, D_all));
+        D = call.sel->keep;
     }
-    GSS_REQUIRE(ctx, !guided || !taps || !taps->act_frames, GSS_ERR_INVALID,
+    GSS_REQUIRE(ctx, !call.guided || !taps || !taps->act_frames, GSS_ERR_INVALID,
                 "gss_enhance_observation_guided: taps->act_frames must be NULL (a guided call "
                 "has no frame activity)");
-    GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
-                "target_index %d outside [0, %d)", target, K);
+    GSS_TRY(check_target_index(ctx, target, K));
     // core.py:221-222
     GSS_REQUIRE(ctx, start_ctx >= 0 && end_ctx >= 0, GSS_ERR_INVALID,
                 "assert context samples >= 0 failed: %lld %lld", (long long)start_ctx,
@@ -1475,16 +1457,13 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     const int size = p->stft_size, shift = p->stft_shift, fading = p->stft_fading;
     const int F = size / 2 + 1;
     EmGuide guide{};
-    if (guided) GSS_TRY(check_guidance(ctx, guidance, K, T, &guide));
+    if (call.guided) GSS_TRY(check_guidance(ctx, call.guidance, K, T, &guide));
 
-    GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K,
-                                                  seg ? seg->segment_frames : 0,
-                                                  select ? sel->bands : 0, D_all,
-                                                  lcmv != nullptr, pact != nullptr, wpd)));
+    GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K, D_all, call)));
     PipelineFront fr;
     GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
     uint8_t *gate = nullptr;
-    if (wpd) {
+    if (call.wpd) {
         if (p->wpe && wpe_arrays_of(p) > 1) {
             fr.Yraw = arena_alloc_t<cplx>(ctx, (size_t)F * T * D);
             GSS_REQUIRE(ctx, fr.Yraw, GSS_ERR_NOMEM, "workspace sizing bug");
@@ -1495,18 +1474,18 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     double *mx = arena_alloc_t<double>(ctx, (size_t)F * T);
     double *mn = arena_alloc_t<double>(ctx, (size_t)F * T);
     // (LCMV: mi, mnn = the interferer and noise masks, mn = their sum, the distortion mask)
-    double *mi = lcmv ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
-    double *mnn = lcmv ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
+    double *mi = call.lcmv ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
+    double *mnn = call.lcmv ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
     cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)F * T);
     int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);
-    GSS_REQUIRE(ctx, mx && mn && Xhat && ref && (!lcmv || (mi && mnn)), GSS_ERR_NOMEM,
+    GSS_REQUIRE(ctx, mx && mn && Xhat && ref && (!call.lcmv || (mi && mnn)), GSS_ERR_NOMEM,
                 "workspace sizing bug");
     const size_t mark = ctx->arena_off;
-    GSS_TRY(run_front(ctx, p, obs, obs_type, D, N, act, K, N_act, F, T, T_act, fr, mark,
-                      guided ? &guide : nullptr, select ? sel : nullptr, D_all));
+    GSS_TRY(run_front(ctx, p, call, obs, D_all, D, N, act, K, N_act, F, T, T_act, fr, mark, guide));
     cplx *const X = fr.X;
-    if (pact) {     // (reads X and gamma, writes the caller's buffers only)
-        GSS_TRY(pact_run(ctx, X, fr.gamma, F, K, T, D, pact->weights, pact->scores, pact->power));
+    if (call.activity.scores) {      // (reads X and gamma, writes the caller's buffers only)
+        GSS_TRY(pact_run(ctx, X, fr.gamma, F, K, T, D, call.activity.weights,
+                         call.activity.scores, call.activity.power));
         ctx->arena_off = mark;
     }
 
@@ -1517,24 +1496,24 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     }
     // (the LCMV takes its three masks below; mx, mn are the taps' masks there: the target and
     // I + N, the sum over the other classes)
-    if (!lcmv || (taps && taps->distortion_mask))
+    if (!call.lcmv || (taps && taps->distortion_mask))
         GSS_TRY(masks_from_posteriors_run(ctx, fr.gamma, F, K, T, target, p->bf_drop_context, sf,
                                           ef, mx, mn));
-    if (wpd) {      // (bf == 0, checked by the entry point) on the STFT before WPE
+    if (call.wpd) {     // (bf == 0, checked by the entry point) on the STFT before WPE
         const cplx *raw = fr.Yraw ? fr.Yraw : fr.Y;
         if (p->bf_drop_context) GSS_TRY(wpd_context_gate_run(ctx, T, sf, ef, gate));
-        GSS_TRY(wpd_run(ctx, raw, F, T, D, mx, p->bf_drop_context ? gate : nullptr, *wpd,
+        GSS_TRY(wpd_run(ctx, raw, F, T, D, mx, p->bf_drop_context ? gate : nullptr, *call.wpd,
                         /*forced_ref=*/-1, Xhat, ref));
         ctx->arena_off = mark;
-    } else if (lcmv) {     // (bf == 0, checked by the entry point)
-        GSS_TRY(lcmv_masks_run(ctx, fr.gamma, F, K, T, target, *lcmv, p->bf_drop_context, sf, ef,
+    } else if (call.lcmv) {   // (bf == 0, checked by the entry point)
+        GSS_TRY(lcmv_masks_run(ctx, fr.gamma, F, K, T, target, *call.lcmv, p->bf_drop_context, sf, ef,
                                mx, mi, mnn, nullptr));
         ctx->arena_off = mark;
         GSS_TRY(lcmv_run(ctx, X, F, T, D, mx, mi, mnn, /*ban=*/1, /*forced_ref=*/-1,
-                         lcmv->min_mass, Xhat, ref));
+                         call.lcmv->min_mass, Xhat, ref));
         ctx->arena_off = mark;
-    } else if (seg) {      // (bf == 0, checked by the entry point)
-        GSS_TRY(mvdr_segments_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, *seg, Xhat, ref));
+    } else if (call.seg) {   // (bf == 0, checked by the entry point)
+        GSS_TRY(mvdr_segments_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, *call.seg, Xhat, ref));
         ctx->arena_off = mark;
     } else if (p->bf == 0 || p->bf == 3) {
         GSS_TRY(mvdr_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, Xhat, ref, /*gev=*/p->bf == 3));
@@ -1571,8 +1550,7 @@ static int enhance_observation_targets_impl(gss_ctx *ctx, const gss_params *p, c
     GSS_REQUIRE(ctx, targets && start_ctx && end_ctx, GSS_ERR_INVALID,
                 "gss_enhance_observation_targets: NULL target or context array");
     // (K bounded before the indices are used as bit positions below)
-    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_MAX_CLASSES, GSS_ERR_INVALID,
-                "cacgmm: assert 1 <= K < 20 failed: K=%d", K);
+    GSS_TRY(check_class_count(ctx, K));
     GSS_REQUIRE(ctx, S >= 1 && S <= K, GSS_ERR_INVALID,
                 "%d targets of %d classes: need 1 <= S <= K", S, K);
     uint32_t seen = 0;
@@ -1600,7 +1578,9 @@ static int enhance_observation_targets_impl(gss_ctx *ctx, const gss_params *p, c
     int32_t *ref = arena_alloc_t<int32_t>(ctx, 4 * (size_t)S);
     GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
     const size_t mark = ctx->arena_off;
-    GSS_TRY(run_front(ctx, p, obs, obs_type, D, N, act, K, N_act, F, T, T_act, fr, mark));
+    PipelineCall call;
+    call.obs_type = obs_type;
+    GSS_TRY(run_front(ctx, p, call, obs, D, D, N, act, K, N_act, F, T, T_act, fr, mark, EmGuide{}));
     cplx *const X = fr.X;
 
     int64_t sf[GSS_MAX_CLASSES] = {}, ef[GSS_MAX_CLASSES] = {};
@@ -1648,8 +1628,8 @@ extern "C" int gss_enhance_observation(gss_ctx *ctx, const gss_params *p, const 
                                        int64_t end_ctx, double *out,
                                        const gss_debug_taps *taps) {
     GSS_ENTER_VARIANTS(ctx);
-    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
-                                    out, taps);
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, PipelineCall{});
 }
 
 extern "C" int gss_enhance_observation_guided(gss_ctx *ctx, const gss_params *p,
@@ -1659,8 +1639,12 @@ extern "C" int gss_enhance_observation_guided(gss_ctx *ctx, const gss_params *p,
                                               const gss_debug_taps *taps) {
     GSS_ENTER_VARIANTS(ctx);
     // (the frame counts of observation and guidance are one: N_act = N)
-    return enhance_observation_impl(ctx, p, obs, 0, D, N, nullptr, K, N, target, start_ctx,
-                                    end_ctx, out, taps, /*guided=*/true, guidance);
+    PipelineCall call;
+    call.entry = "gss_enhance_observation_guided";
+    call.guided = true;
+    call.guidance = guidance;
+    return enhance_observation_impl(ctx, p, obs, D, N, nullptr, K, N, target, start_ctx, end_ctx,
+                                    out, taps, call);
 }
 
 extern "C" int gss_enhance_observation_segments(gss_ctx *ctx, const gss_params *p,
@@ -1674,8 +1658,10 @@ extern "C" int gss_enhance_observation_segments(gss_ctx *ctx, const gss_params *
     GSS_REQUIRE(ctx, !p || p->bf == 0, GSS_ERR_UNSUPPORTED,
                 "gss_enhance_observation_segments: bf=%d, only 0 ('mvdrSouden_ban') has segments",
                 p->bf);
-    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
-                                    out, taps, /*guided=*/false, nullptr, seg);
+    PipelineCall call;
+    call.seg = seg;
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
 }
 
 extern "C" int gss_enhance_observation_wpd(gss_ctx *ctx, const gss_params *p, const double *obs,
@@ -1688,9 +1674,10 @@ extern "C" int gss_enhance_observation_wpd(gss_ctx *ctx, const gss_params *p, co
                 "gss_enhance_observation_wpd: bf=%d, only 0 ('mvdrSouden_ban') has a WPD form",
                 p->bf);
     GSS_TRY(check_wpd(ctx, wpd, D, "gss_enhance_observation_wpd"));
-    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
-                                    out, taps, false, nullptr, nullptr, nullptr, false, nullptr,
-                                    nullptr, wpd);
+    PipelineCall call;
+    call.wpd = wpd;
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
 }
 
 extern "C" int gss_enhance_observation_lcmv(gss_ctx *ctx, const gss_params *p, const double *obs,
@@ -1702,15 +1689,14 @@ extern "C" int gss_enhance_observation_lcmv(gss_ctx *ctx, const gss_params *p, c
     GSS_REQUIRE(ctx, !p || p->bf == 0, GSS_ERR_UNSUPPORTED,
                 "gss_enhance_observation_lcmv: bf=%d, only 0 ('mvdrSouden_ban') has an "
                 "interferer-nulling form", p->bf);
-    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_MAX_CLASSES, GSS_ERR_INVALID,
-                "cacgmm: assert 1 <= K < 20 failed: K=%d", K);
-    GSS_REQUIRE(ctx, target >= 0 && target < K, GSS_ERR_INVALID,
-                "target_index %d outside [0, %d)", target, K);
+    GSS_TRY(check_class_count(ctx, K));
+    GSS_TRY(check_target_index(ctx, target, K));
     GSS_TRY(check_lcmv(ctx, lcmv, K, target, "gss_enhance_observation_lcmv"));
     GSS_TRY(check_lcmv_channels(ctx, D, "gss_enhance_observation_lcmv"));
-    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
-                                    out, taps, /*guided=*/false, nullptr, nullptr, nullptr, false,
-                                    lcmv);
+    PipelineCall call;
+    call.lcmv = lcmv;
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
 }
 
 extern "C" int gss_enhance_observation_activity(gss_ctx *ctx, const gss_params *p,
@@ -1729,10 +1715,12 @@ extern "C" int gss_enhance_observation_activity(gss_ctx *ctx, const gss_params *
     GSS_REQUIRE(ctx, scores, GSS_ERR_INVALID, "%s: scores_dev is NULL", what);
     GSS_REQUIRE(ctx, N >= 1, GSS_ERR_INVALID, "%s: N=%lld is smaller than 1", what, (long long)N);
     GSS_TRY(check_activity_sizes(ctx, K, D, what));
-    const PipelineActivity pact{freq_weights, scores, power};
-    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
-                                    out, taps, /*guided=*/false, nullptr, nullptr, nullptr, false,
-                                    nullptr, &pact);
+    PipelineCall call;
+    call.activity.weights = freq_weights;
+    call.activity.scores = scores;
+    call.activity.power = power;
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
 }
 
 extern "C" int gss_enhance_observation_pcm16(gss_ctx *ctx, const gss_params *p,
@@ -1741,8 +1729,10 @@ extern "C" int gss_enhance_observation_pcm16(gss_ctx *ctx, const gss_params *p,
                                              int64_t start_ctx, int64_t end_ctx, double *out,
                                              const gss_debug_taps *taps) {
     GSS_ENTER_VARIANTS(ctx);
-    return enhance_observation_impl(ctx, p, obs, 1, D, N, act, K, N_act, target, start_ctx, end_ctx,
-                                    out, taps);
+    PipelineCall call;
+    call.obs_type = 1;
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
 }
 
 extern "C" int gss_enhance_observation_select(gss_ctx *ctx, const gss_params *p,
@@ -1752,8 +1742,12 @@ extern "C" int gss_enhance_observation_select(gss_ctx *ctx, const gss_params *p,
                                               const gss_channel_select *sel, double *out,
                                               const gss_debug_taps *taps) {
     GSS_ENTER_VARIANTS(ctx);
-    return enhance_observation_impl(ctx, p, obs, 0, D, N, act, K, N_act, target, start_ctx, end_ctx,
-                                    out, taps, /*guided=*/false, nullptr, nullptr, sel, true);
+    PipelineCall call;
+    call.entry = "gss_enhance_observation_select";
+    call.select = true;
+    call.sel = sel;
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
 }
 
 extern "C" int gss_enhance_observation_select_pcm16(gss_ctx *ctx, const gss_params *p,
@@ -1764,8 +1758,13 @@ extern "C" int gss_enhance_observation_select_pcm16(gss_ctx *ctx, const gss_para
                                                     const gss_channel_select *sel, double *out,
                                                     const gss_debug_taps *taps) {
     GSS_ENTER_VARIANTS(ctx);
-    return enhance_observation_impl(ctx, p, obs, 1, D, N, act, K, N_act, target, start_ctx, end_ctx,
-                                    out, taps, /*guided=*/false, nullptr, nullptr, sel, true);
+    PipelineCall call;
+    call.entry = "gss_enhance_observation_select";
+    call.obs_type = 1;
+    call.select = true;
+    call.sel = sel;
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
 }
 
 extern "C" int gss_enhance_observation_targets(gss_ctx *ctx, const gss_params *p,

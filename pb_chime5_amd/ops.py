@@ -27,6 +27,7 @@ here                        reference call (file:line)
 All of them raise if libgss_hip.so or a GPU is missing.
 """
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -1140,12 +1141,9 @@ def enhance_observation_select(obs, activity, target_index, start_context_sample
     bufs, taps = _debug_taps(utt, D=n) if debug else ({}, None)
     utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
                 channel_select=sel)
-    x_hat = utt.result()
+    x_hat, details = _one_target_result(utt, bufs, debug, D=n)
     if not debug:
         return x_hat
-    details = _debug_details(utt, bufs, D=n)
-    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
-    details['ref_channel'] = int(details['ref_channel'])
     details['selected_channels'] = np.array(ctx.last_selected_channels(n), dtype=int)
     return x_hat, details
 
@@ -1237,25 +1235,16 @@ def enhance_observation_activity(obs, activity, target_index, start_context_samp
     obs = np.asarray(obs)
     if obs.ndim != 2:
         raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
-    params = params_for(params, obs.shape[0], wpe_arrays)
-    ctx = ctx or default_context()
-    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
-    utt = ResidentUtterance(ctx, obs, activity, params)
-    bufs, taps = _debug_taps(utt) if debug else ({}, None)
+    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
     w_d = ctx.to_device(w) if w is not None else None
     s_d = ctx.empty(8 * utt.K * max(utt.T, 1))
     p_d = ctx.empty(8 * max(utt.T, 1))
     utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
                 activity=(w_d, s_d, p_d))
-    x_hat = utt.result()
+    x_hat, details = _one_target_result(utt, bufs, debug)
     scores = ctx.to_host(s_d, (utt.K, utt.T), np.float64)
     power = ctx.to_host(p_d, (utt.T,), np.float64)
-    if not debug:
-        return x_hat, scores, power
-    details = _debug_details(utt, bufs)
-    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
-    details['ref_channel'] = int(details['ref_channel'])
-    return x_hat, scores, power, details
+    return (x_hat, scores, power, details) if debug else (x_hat, scores, power)
 
 
 # --------------------------------------------------------------------------
@@ -1296,6 +1285,44 @@ def params_for(params, num_channels, wpe_arrays=None):
     return p
 
 
+# The fused one-target entries by the option a call adds to the plain one (None): option ->
+# (entry, its _pcm16 twin or None, what the assertions call it).  Every entry but 'activity'
+# inserts one descriptor before out_dev.
+_FUSED_ENTRIES = {
+    None: ('gss_enhance_observation', 'gss_enhance_observation_pcm16', 'plain'),
+    'wpd': ('gss_enhance_observation_wpd', None, 'WPD'),
+    'activity': ('gss_enhance_observation_activity', None, 'activity'),
+    'lcmv': ('gss_enhance_observation_lcmv', None, 'LCMV'),
+    'channel_select': ('gss_enhance_observation_select', 'gss_enhance_observation_select_pcm16',
+                       'selection'),
+    'segments': ('gss_enhance_observation_segments', None, 'segment-wise'),
+}
+
+
+def _enqueue_fused(ctx, params, obs_d, D, N, act_d, K, N_act, target_index, start_context,
+                   end_context, out_d, taps=None, pcm=False, option=None, value=None):
+    """The one place that issues a fused one-target call on inputs in HBM.  ``option``: a key of
+    `_FUSED_ENTRIES`; ``value``: the struct that entry takes (gss_bf_wpd, gss_bf_lcmv,
+    gss_bf_segments, gss_channel_select), for 'activity' the device buffers (weights or None,
+    scores, power or None).  ``pcm``: int16 samples, the entry's _pcm16 twin."""
+    name, twin, label = _FUSED_ENTRIES[option]
+    assert twin is not None or not pcm, f'the {label} call has no pcm16 twin'
+
+    def ptr(buf):
+        return c_void_p(buf.ptr) if buf is not None else None
+    before, after = (), ()
+    if option == 'activity':    # the weights before out_dev, the scores and the power after it
+        before, after = (ptr(value[0]),), (ptr(value[1]), ptr(value[2]))
+    elif option is not None:
+        before = (ctypes.byref(value),)
+    ctx._check(getattr(ctx.lib, twin if pcm else name)(
+        ctx.handle, ctypes.byref(params), ptr(obs_d), D, N, ptr(act_d), K, N_act,
+        int(target_index), int(start_context), int(end_context), *before, ptr(out_d), *after,
+        ctypes.byref(taps) if taps is not None else None), name)
+    if option == 'channel_select':
+        ctx.selected_count = value.keep
+
+
 class ResidentUtterance:
     """An utterance whose inputs already sit in HBM (what bench.py times).  ``pcm=True``: the
     samples are int16 PCM, scaled by 2^-15 on the device (the _pcm16 entries); otherwise they
@@ -1331,71 +1358,18 @@ class ResidentUtterance:
         ``activity``: device buffers (weights (F,) or None, scores (K,T), power (T,) or None) for
         the posterior activity of the call's own observation and posteriors
         (gss_enhance_observation_activity; float64 samples only, on its own)."""
-        ctx = self.ctx
-        if wpd is not None:
-            assert segments is None and channel_select is None and lcmv is None \
-                and activity is None, 'the WPD call stands alone'
-            assert not self.pcm, 'the WPD call has no pcm16 twin'
-            ctx._check(ctx.lib.gss_enhance_observation_wpd(
-                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
-                self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
-                int(start_context), int(end_context), ctypes.byref(wpd),
-                c_void_p(self.out_d.ptr), ctypes.byref(taps) if taps is not None else None),
-                'gss_enhance_observation_wpd')
-            return
-        if activity is not None:
-            assert segments is None and channel_select is None and lcmv is None, \
-                'the activity call stands alone'
-            assert not self.pcm, 'the activity call has no pcm16 twin'
-            w_d, s_d, p_d = activity
-            ctx._check(ctx.lib.gss_enhance_observation_activity(
-                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D, self.N,
-                c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
-                int(start_context), int(end_context),
-                c_void_p(w_d.ptr) if w_d is not None else None, c_void_p(self.out_d.ptr),
-                c_void_p(s_d.ptr), c_void_p(p_d.ptr) if p_d is not None else None,
-                ctypes.byref(taps) if taps is not None else None),
-                'gss_enhance_observation_activity')
-            return
-        if lcmv is not None:
-            assert segments is None and channel_select is None, 'the LCMV call stands alone'
-            assert not self.pcm, 'the LCMV call has no pcm16 twin'
-            ctx._check(ctx.lib.gss_enhance_observation_lcmv(
-                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
-                self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
-                int(start_context), int(end_context), ctypes.byref(lcmv),
-                c_void_p(self.out_d.ptr), ctypes.byref(taps) if taps is not None else None),
-                'gss_enhance_observation_lcmv')
-            return
-        if channel_select is not None:
-            assert segments is None, 'no selection inside the segment-wise call'
-            st = channel_select.struct(ctx, self.D)
-            entry = (ctx.lib.gss_enhance_observation_select_pcm16 if self.pcm
-                     else ctx.lib.gss_enhance_observation_select)
-            ctx._check(entry(
-                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
-                self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
-                int(start_context), int(end_context), ctypes.byref(st),
-                c_void_p(self.out_d.ptr), ctypes.byref(taps) if taps is not None else None),
-                'gss_enhance_observation_select')
-            ctx.selected_count = st.keep
-            return
-        if segments is not None:
-            assert not self.pcm, 'the segment-wise call has no pcm16 twin'
-            ctx._check(ctx.lib.gss_enhance_observation_segments(
-                ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
-                self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
-                int(start_context), int(end_context), ctypes.byref(segments),
-                c_void_p(self.out_d.ptr), ctypes.byref(taps) if taps is not None else None),
-                'gss_enhance_observation_segments')
-            return
-        entry = ctx.lib.gss_enhance_observation_pcm16 if self.pcm else ctx.lib.gss_enhance_observation
-        ctx._check(entry(
-            ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D,
-            self.N, c_void_p(self.act_d.ptr), self.K, self.N_act, int(target_index),
-            int(start_context), int(end_context), c_void_p(self.out_d.ptr),
-            ctypes.byref(taps) if taps is not None else None),
-            'gss_enhance_observation')
+        given = [(name, v) for name, v in (('wpd', wpd), ('activity', activity), ('lcmv', lcmv),
+                                           ('channel_select', channel_select),
+                                           ('segments', segments)) if v is not None]
+        option, value = given[0] if given else (None, None)
+        assert len(given) <= 1, ('no selection inside the segment-wise call'
+                                 if option == 'channel_select'
+                                 else f'the {_FUSED_ENTRIES[option][2]} call stands alone')
+        if option == 'channel_select':
+            value = value.struct(self.ctx, self.D)
+        _enqueue_fused(self.ctx, self.params, self.obs_d, self.D, self.N, self.act_d, self.K,
+                       self.N_act, target_index, start_context, end_context, self.out_d, taps,
+                       self.pcm, option, value)
 
     def enqueue_targets(self, target_indices, start_contexts, end_contexts, out_d, taps=None):
         """gss_enhance_observation_targets: len(target_indices) rows of n_out samples into
@@ -1511,6 +1485,24 @@ class UtterancePipeline:
             buf = self._bufs[slot][name] = self.slots[slot].empty(max(int(nbytes * 1.25), 16))
         return buf
 
+    def _next_slot(self, obs, act, wpe_arrays, select=False):
+        """The set-up both enqueue calls share, for inputs ``obs`` (D,N) and ``act`` (K,N_act):
+        the utterance's params (checked against a selection with ``select``), the next slot and
+        its context, the length of the result and the slot's grow-only device buffers."""
+        p = params_for(self.params, obs.shape[0], wpe_arrays)
+        if select:
+            _check_select_params(p, 'channel selection')
+        slot = self._next
+        self._next = (self._next + 1) % len(self.slots)
+        ctx = self.slots[slot]
+        T = stft_frames(obs.shape[1], p.stft_size, p.stft_shift, p.stft_fading)
+        n_out = int(ctx.lib.gss_istft_num_samples(T, p.stft_size, p.stft_shift, p.stft_fading))
+        return SimpleNamespace(
+            slot=slot, ctx=ctx, params=p, n_out=n_out,
+            obs_d=self._buffer(slot, 'obs', obs.nbytes),
+            act_d=self._buffer(slot, 'act', act.nbytes),
+            out_d=self._buffer(slot, 'out', 8 * max(n_out, 1)))
+
     def enqueue(self, tag, obs, activity, target_index, start_context, end_context,
                 wpe_arrays=None):
         """``wpe_arrays``: microphone arrays of this utterance for a per-array WPE (None: as
@@ -1520,25 +1512,12 @@ class UtterancePipeline:
         pcm = np.asarray(obs).dtype == np.int16
         obs = np.ascontiguousarray(obs, dtype=np.int16 if pcm else np.float64)
         act = np.ascontiguousarray((np.asarray(activity) != 0).astype(np.uint8))
-        p = params_for(self.params, obs.shape[0], wpe_arrays)
-        slot = self._next
-        self._next = (self._next + 1) % len(self.slots)
-        ctx = self.slots[slot]
-        D, N = obs.shape
-        K, N_act = act.shape
-        T = stft_frames(N, p.stft_size, p.stft_shift, p.stft_fading)
-        n_out = int(ctx.lib.gss_istft_num_samples(T, p.stft_size, p.stft_shift, p.stft_fading))
-        obs_d = self._buffer(slot, 'obs', obs.nbytes)
-        act_d = self._buffer(slot, 'act', act.nbytes)
-        out_d = self._buffer(slot, 'out', 8 * max(n_out, 1))
-        ctx.upload(obs_d, obs)
-        ctx.upload(act_d, act)
-        entry = ctx.lib.gss_enhance_observation_pcm16 if pcm else ctx.lib.gss_enhance_observation
-        ctx._check(entry(
-            ctx.handle, ctypes.byref(p), c_void_p(obs_d.ptr), D, N, c_void_p(act_d.ptr), K,
-            N_act, int(target_index), int(start_context), int(end_context),
-            c_void_p(out_d.ptr), None), 'gss_enhance_observation')
-        self._pending.append((tag, slot, n_out))
+        s = self._next_slot(obs, act, wpe_arrays)
+        s.ctx.upload(s.obs_d, obs)
+        s.ctx.upload(s.act_d, act)
+        _enqueue_fused(s.ctx, s.params, s.obs_d, *obs.shape, s.act_d, *act.shape, target_index,
+                       start_context, end_context, s.out_d, pcm=pcm)
+        self._pending.append((tag, s.slot, s.n_out))
 
     # ---- page-locked staging (the session driver's path) ----------------------------
     def acquire_staging(self, timeout=None):
@@ -1557,23 +1536,12 @@ class UtterancePipeline:
         ``channel_select``: a `ChannelSelect`; the utterance takes
         gss_enhance_observation_select_pcm16, still without any wait."""
         assert not self.full(), 'pop() the oldest utterance first'
-        p = params_for(self.params, staging.obs.shape[0], wpe_arrays)
-        if channel_select is not None:
-            _check_select_params(p, 'channel selection')
-        slot = self._next
-        self._next = (self._next + 1) % len(self.slots)
-        ctx = self.slots[slot]
         obs, act = staging.obs, staging.act
-        D, N = obs.shape
-        K, N_act = act.shape
-        T = stft_frames(N, p.stft_size, p.stft_shift, p.stft_fading)
-        n_out = int(ctx.lib.gss_istft_num_samples(T, p.stft_size, p.stft_shift, p.stft_fading))
+        s = self._next_slot(obs, act, wpe_arrays, select=channel_select is not None)
+        slot, ctx, n_out = s.slot, s.ctx, s.n_out
         a, b = (0, n_out) if keep is None else (min(max(int(keep[0]), 0), n_out),
                                                  min(max(int(keep[1]), 0), n_out))
         b = max(a, b)
-        obs_d = self._buffer(slot, 'obs', obs.nbytes)
-        act_d = self._buffer(slot, 'act', act.nbytes)
-        out_d = self._buffer(slot, 'out', 8 * max(n_out, 1))
         out_h = self._out_host[slot]
         if out_h is None or out_h.nbytes < 8 * (b - a):
             have = 0
@@ -1584,22 +1552,14 @@ class UtterancePipeline:
                 max(int(8 * (b - a) * 1.25) + 4096, 2 * have))
         out_view = out_h.view((b - a,), np.float64)
         # (the band table of a selection is copied to the slot's GPU once, on its first use)
-        st = channel_select.struct(ctx, D) if channel_select is not None else None
-        ctx.upload_async(obs_d, obs)
-        ctx.upload_async(act_d, act)
-        if st is not None:
-            ctx._check(ctx.lib.gss_enhance_observation_select_pcm16(
-                ctx.handle, ctypes.byref(p), c_void_p(obs_d.ptr), D, N, c_void_p(act_d.ptr), K,
-                N_act, int(target_index), int(start_context), int(end_context),
-                ctypes.byref(st), c_void_p(out_d.ptr), None), 'gss_enhance_observation_select')
-            ctx.selected_count = st.keep
-        else:
-            ctx._check(ctx.lib.gss_enhance_observation_pcm16(
-                ctx.handle, ctypes.byref(p), c_void_p(obs_d.ptr), D, N, c_void_p(act_d.ptr), K,
-                N_act, int(target_index), int(start_context), int(end_context),
-                c_void_p(out_d.ptr), None), 'gss_enhance_observation')
+        st = channel_select.struct(ctx, obs.shape[0]) if channel_select is not None else None
+        ctx.upload_async(s.obs_d, obs)
+        ctx.upload_async(s.act_d, act)
+        _enqueue_fused(ctx, s.params, s.obs_d, *obs.shape, s.act_d, *act.shape, target_index,
+                       start_context, end_context, s.out_d, pcm=True,
+                       option='channel_select' if st is not None else None, value=st)
         if b > a:
-            ctx.download_async(out_view, out_d, offset=8 * a)
+            ctx.download_async(out_view, s.out_d, offset=8 * a)
         self._pending.append((tag, slot, n_out, staging, out_view))
 
     def pop(self):
@@ -1660,6 +1620,26 @@ class UtterancePipeline:
                 pass
 
 
+def _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx):
+    """The head that the one-target wrappers on a time-domain activity share once their own
+    arguments are checked: (context, the utterance in HBM, tap buffers, taps); the last two
+    empty without ``debug``."""
+    params = params_for(params, np.shape(obs)[0], wpe_arrays)
+    ctx = ctx or default_context()
+    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
+    utt = ResidentUtterance(ctx, obs, activity, params)
+    bufs, taps = _debug_taps(utt) if debug else ({}, None)
+    return ctx, utt, bufs, taps
+
+
+def _require_souden(params, setting, form):
+    """What only bf='mvdrSouden_ban' combines with, before any device work."""
+    if params.bf != _BF_CODES['mvdrSouden_ban']:
+        names = {v: k for k, v in _BF_CODES.items()}
+        raise NotImplementedError(f"bf={names[params.bf]!r} with {setting}: only "
+                                  f"'mvdrSouden_ban' has {form}")
+
+
 def enhance_observation(obs, activity, target_index, start_context_samples,
                         end_context_samples, *, params=None, window=None, debug=False,
                         ctx=None, wpe_arrays=None, **param_kwargs):
@@ -1671,18 +1651,11 @@ def enhance_observation(obs, activity, target_index, start_context_samples,
     array (A arrays of D / A channels, array-major) instead of one joint WPE."""
     if params is None:
         params = make_params(**param_kwargs)
-    params = params_for(params, np.shape(obs)[0], wpe_arrays)
-    ctx = ctx or default_context()
-    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
-    utt = ResidentUtterance(ctx, obs, activity, params)
-    bufs, taps = _debug_taps(utt) if debug else ({}, None)
+    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
     utt.enqueue(target_index, start_context_samples, end_context_samples, taps)
-    x_hat = utt.result()
+    x_hat, details = _one_target_result(utt, bufs, debug)
     if not debug:
         return x_hat
-    details = _debug_details(utt, bufs)
-    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
-    details['ref_channel'] = int(details['ref_channel'])
     return x_hat, details
 
 
@@ -1698,26 +1671,16 @@ def enhance_observation_segments(obs, activity, target_index, start_context_samp
     device work."""
     if params is None:
         params = make_params(**param_kwargs)
-    if params.bf != _BF_CODES['mvdrSouden_ban']:
-        names = {v: k for k, v in _BF_CODES.items()}
-        raise NotImplementedError(f"bf={names[params.bf]!r} with segment_frames: only "
-                                  "'mvdrSouden_ban' has a segment-wise form")
+    _require_souden(params, 'segment_frames', 'a segment-wise form')
     obs = np.asarray(obs)
     if obs.ndim != 2:
         raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
     seg = check_bf_segments(segment_frames, segment_context, min_mass, obs.shape[0])
-    params = params_for(params, obs.shape[0], wpe_arrays)
-    ctx = ctx or default_context()
-    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
-    utt = ResidentUtterance(ctx, obs, activity, params)
-    bufs, taps = _debug_taps(utt) if debug else ({}, None)
+    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
     utt.enqueue(target_index, start_context_samples, end_context_samples, taps, segments=seg)
-    x_hat = utt.result()
+    x_hat, details = _one_target_result(utt, bufs, debug)
     if not debug:
         return x_hat
-    details = _debug_details(utt, bufs)
-    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
-    details['ref_channel'] = int(details['ref_channel'])
     details['segment_fallbacks'] = ctx.last_segment_fallbacks()
     return x_hat, details
 
@@ -1736,28 +1699,18 @@ def enhance_observation_lcmv(obs, activity, target_index, start_context_samples,
     ValueError, both before any device work."""
     if params is None:
         params = make_params(**param_kwargs)
-    if params.bf != _BF_CODES['mvdrSouden_ban']:
-        names = {v: k for k, v in _BF_CODES.items()}
-        raise NotImplementedError(f"bf={names[params.bf]!r} with null_interferer: only "
-                                  "'mvdrSouden_ban' has an interferer-nulling form")
+    _require_souden(params, 'null_interferer', 'an interferer-nulling form')
     obs = np.asarray(obs)
     if obs.ndim != 2:
         raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
     _check_lcmv_channels(obs.shape[0])
     K = np.shape(activity)[0]
     bf = check_bf_lcmv(K, target_index, interferer, candidates, min_mass, obs.shape[0])
-    params = params_for(params, obs.shape[0], wpe_arrays)
-    ctx = ctx or default_context()
-    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
-    utt = ResidentUtterance(ctx, obs, activity, params)
-    bufs, taps = _debug_taps(utt) if debug else ({}, None)
+    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
     utt.enqueue(target_index, start_context_samples, end_context_samples, taps, lcmv=bf)
-    x_hat = utt.result()
+    x_hat, details = _one_target_result(utt, bufs, debug)
     if not debug:
         return x_hat
-    details = _debug_details(utt, bufs)
-    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
-    details['ref_channel'] = int(details['ref_channel'])
     found = details['interferer'] = ctx.last_lcmv_interferer()
     details['lcmv_fallbacks'] = ctx.last_lcmv_fallbacks()
     # the interferer's posterior with the context frames zeroed: the bits the call used
@@ -1789,28 +1742,18 @@ def enhance_observation_wpd(obs, activity, target_index, start_context_samples,
     otherwise; bad settings are ValueError, both before any device work."""
     if params is None:
         params = make_params(**param_kwargs)
-    if params.bf != _BF_CODES['mvdrSouden_ban']:
-        names = {v: k for k, v in _BF_CODES.items()}
-        raise NotImplementedError(f"bf={names[params.bf]!r} with the WPD beamformer: only "
-                                  "'mvdrSouden_ban' has a WPD form")
+    _require_souden(params, 'the WPD beamformer', 'a WPD form')
     obs = np.asarray(obs)
     if obs.ndim != 2:
         raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
     bf = check_bf_wpd(params.wpe_taps if taps is None else taps,
                       params.wpe_delay if delay is None else delay, iterations, power_floor, ban,
                       obs.shape[0])
-    params = params_for(params, obs.shape[0], wpe_arrays)
-    ctx = ctx or default_context()
-    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
-    utt = ResidentUtterance(ctx, obs, activity, params)
-    bufs, dbg = _debug_taps(utt) if debug else ({}, None)
+    ctx, utt, bufs, dbg = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
     utt.enqueue(target_index, start_context_samples, end_context_samples, dbg, wpd=bf)
-    x_hat = utt.result()
+    x_hat, details = _one_target_result(utt, bufs, debug)
     if not debug:
         return x_hat
-    details = _debug_details(utt, bufs)
-    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
-    details['ref_channel'] = int(details['ref_channel'])
     details['wpd_zero_pivots'] = ctx.last_wpd_zero_pivots()
     return x_hat, details
 
@@ -1866,16 +1809,25 @@ def enhance_observation_guided(obs, initialization, source_activity_mask, target
         del bufs['act_frames']
         taps.act_frames = None
     utt.enqueue(target_index, start_context_samples, end_context_samples, taps)
-    x_hat = utt.result()
+    x_hat, details = _one_target_result(utt, bufs, debug)
     if not debug:
         return x_hat
-    details = _debug_details(utt, bufs)
-    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
-    details['ref_channel'] = int(details['ref_channel'])
     return x_hat, details
 
 
 _PER_TARGET = ('target_mask', 'distortion_mask', 'X_hat', 'ref_channel')
+
+
+def _one_target_result(utt, bufs, debug, D=None):
+    """The tail the one-target wrappers share: (x_hat, None), or with ``debug`` (x_hat, details)
+    with the per-target entries of `_debug_details` squeezed and ``ref_channel`` an int."""
+    x_hat = utt.result()
+    if not debug:
+        return x_hat, None
+    details = _debug_details(utt, bufs, D=D)
+    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+    details['ref_channel'] = int(details['ref_channel'])
+    return x_hat, details
 
 
 def _debug_taps(utt, S=1, D=None):

@@ -26,6 +26,19 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert b'gfx950' in lib.gss_version()
 
 
+def test_every_fused_entry_has_a_caller_in_the_binding():
+    """Each gss_enhance_observation* prototype is an entry of the binding's call table (or its
+    pcm16 twin), or one of the entries with a head of their own; the table names no other."""
+    from pb_chime5_amd import _capi, ops
+    table = {name for entry, twin, _ in ops._FUSED_ENTRIES.values() for name in (entry, twin)
+             if name is not None}
+    assert table <= set(_capi.SIGNATURES), sorted(table - set(_capi.SIGNATURES))
+    own_head = {'gss_enhance_observation_guided', 'gss_enhance_observation_targets',
+                'gss_enhance_observation_targets_pcm16', 'gss_enhance_observation_host'}
+    fused = {name for name in _capi.SIGNATURES if name.startswith('gss_enhance_observation')}
+    assert fused - own_head == table, sorted((fused - own_head) ^ table)
+
+
 def test_geometry_helpers_match_oracle():
     import gss_oracle as oracle
     from pb_chime5_amd import ops

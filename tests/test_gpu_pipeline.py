@@ -1192,3 +1192,59 @@ def test_adopted_stream_and_profiling_with_the_second_stream(gpu_ctx):
         gpu_ctx.set_stream(None)
         hip.hipStreamDestroy(stream)
     assert np.array_equal(run(), want)
+
+
+def test_first_failing_check_of_the_fused_entries(gpu_ctx):
+    """Every fused entry with two faults in one call: the status and the message are those of the
+    check that comes first.  Nothing is launched."""
+    import ctypes
+    from pb_chime5_amd import _capi, ops
+    ctx = gpu_ctx
+    ops._prepare_windows(ctx, 1024, 256)
+    buf = ctx.empty(8 * 4 * 4096)
+    q = _capi.c_void_p(buf.ptr)
+    INVALID, UNSUPPORTED = _capi.GSS_ERR_INVALID, _capi.GSS_ERR_UNSUPPORTED
+    N = 4096
+
+    def ref(struct):
+        return ctypes.byref(struct) if struct is not None else None
+
+    def head(bf='mvdrSouden_ban', D=4, K=2, target=0, start=0):
+        return (ctx.handle, ref(ops.make_params(bf=bf)), q, D, N, q, K, N, target, start, 0)
+    lib = ctx.lib
+    sel = _capi.GssChannelSelect(bank_dev=buf.ptr, bands=4, keep=3, floor=1e-10)
+    cases = [
+        ('plain D', lambda: lib.gss_enhance_observation(*head(D=0, target=2), q, None),
+         UNSUPPORTED, 'D=0'),
+        ('plain target', lambda: lib.gss_enhance_observation(*head(target=2, start=-1), q, None),
+         INVALID, 'target_index'),
+        ('guided', lambda: lib.gss_enhance_observation_guided(ctx.handle, None, q, 4, N, None, 2, 0,
+                                                              0, 0, q, None),
+         INVALID, 'guidance is NULL'),
+        ('select NULL', lambda: lib.gss_enhance_observation_select(*head(target=-1), None, q, None),
+         INVALID, 'sel is NULL'),
+        ('select ch2', lambda: lib.gss_enhance_observation_select(*head(bf='ch2', target=-1),
+                                                                  ref(sel), q, None),
+         UNSUPPORTED, "'ch2'"),
+        ('segments', lambda: lib.gss_enhance_observation_segments(
+            *head(bf='gev_ban'), ref(_capi.GssBfSegments(0, 0, 1.0)), q, None),
+         INVALID, 'segment_frames'),
+        ('wpd', lambda: lib.gss_enhance_observation_wpd(
+            *head(bf='gev_ban'), ref(_capi.GssBfWpd(0, 2, 1, 1, 1e-3)), q, None),
+         UNSUPPORTED, 'WPD form'),
+        ('lcmv bf', lambda: lib.gss_enhance_observation_lcmv(
+            *head(bf='gev_ban', K=25), ref(_capi.GssBfLcmv(-1, 0b10, 1.0)), q, None),
+         UNSUPPORTED, 'interferer-nulling'),
+        ('lcmv target', lambda: lib.gss_enhance_observation_lcmv(*head(target=2), None, q, None),
+         INVALID, 'target_index'),
+        ('activity', lambda: lib.gss_enhance_observation_activity(*head(K=0), None, q, None, None,
+                                                                  None),
+         INVALID, 'scores_dev is NULL'),
+        ('targets', lambda: lib.gss_enhance_observation_targets(*head(K=25)[:8], 0, q, q, q, q,
+                                                                None),
+         INVALID, 'K=25'),
+    ]
+    for name, call, status, word in cases:
+        got, message = call(), lib.gss_last_error(ctx.handle).decode()
+        print(name, got, message)
+        assert got == status and word in message, (name, got, message)
