@@ -87,7 +87,8 @@ typedef enum {
  * gss_enhance_observation_lcmv, gss_last_lcmv_interferer and gss_last_lcmv_fallbacks with the
  * gss_bf_lcmv descriptor.  So were gss_posterior_activity and gss_enhance_observation_activity.
  * So were gss_wpe_weighted, gss_wpd_weights, gss_wpd_souden, gss_last_wpd_zero_pivots and
- * gss_enhance_observation_wpd with the gss_bf_wpd descriptor. */
+ * gss_enhance_observation_wpd with the gss_bf_wpd descriptor.  So was gss_cacgmm_shared_prior
+ * (it takes the gss_guidance descriptor as it is). */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -239,6 +240,27 @@ typedef struct {
 int gss_cacgmm_guided(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
                       const gss_guidance *guidance, int K, int iterations,
                       int iterations_post, double *gamma_dev);
+
+/* gss_cacgmm_guided with ONE mixture weight per class and FRAME for all frequencies in place of
+ * one per class and frequency: pb_bss's CACGMMTrainer with weight_constant_axis=-3 (Ito et al.,
+ * frequency-independent source-presence priors), which the reference never calls.  Wherever an
+ * E-step of gss_cacgmm_guided multiplies by pi[f, k] this one multiplies by prior[k, t], and
+ * wherever an M-step forms pi[f, k] = mean_t gamma it forms prior[k, t] = (1/F) sum_f gamma[f, k, t]
+ * from the clipped affiliations that go into the covariance.  The first M-step takes its prior
+ * from the initialisation: the table itself when it is (K,T), its mean over f when it is (F,K,T),
+ * the derived where(mask, 1, 1e-10) / sum_k table when only a mask is given.  Everything else --
+ * observation, descriptor, mask rules, clip 1e-10 during the fit and none in the predict step,
+ * eigenvalue floor, the iterations / iterations_post schedule -- is gss_cacgmm_guided's.  The
+ * prior ties the frequencies together (class k is the same source in every bin), so the EM can
+ * start from a (K,T) table that is no annotation at all; with a mask it is weak guidance (who
+ * may speak, not who does).
+ * gamma_dev (F,K,T); prior_dev (K,T) or NULL: the prior of the last M-step, i.e. the one the
+ * predict step used (not the mean of the returned posteriors).  Always the multi-launch path, one
+ * block of frequencies on one stream.  No atomics: the same call gives the same bits.
+ * Errors: those of gss_cacgmm_guided.  (Entry point only: revision still 7.) */
+int gss_cacgmm_shared_prior(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                            const gss_guidance *guidance, int K, int iterations,
+                            int iterations_post, double *gamma_dev, double *prior_dev);
 
 /* ---- the mixture model as an object ---------------------------------------
  * A fitted CACGMM in caller-owned device buffers: exactly what predict needs, no eigenvector

@@ -136,6 +136,9 @@ SIGNATURES = {
                            c_int, c_int, c_int, c_void_p]),
     'gss_cacgmm_guided': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
                                   ctypes.POINTER(GssGuidance), c_int, c_int, c_int, c_void_p]),
+    'gss_cacgmm_shared_prior': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
+                                        ctypes.POINTER(GssGuidance), c_int, c_int, c_int,
+                                        c_void_p, c_void_p]),
     'gss_cacgmm_fit': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
                                ctypes.POINTER(GssGuidance), c_int, c_int,
                                ctypes.POINTER(GssCacgmmModel), ctypes.POINTER(GssCacgmmModel)]),

@@ -165,11 +165,24 @@ class _DebugLocals(dict):
 
 
 @dataclass
+class BlindSeparation:
+    """What `Enhancer.enhance_observation_blind` returns.  Classes carry indices, not names."""
+    x_hat: np.ndarray          # (K, N) enhanced signal of every class
+    prior: np.ndarray          # (K, T) the frequency-shared prior: a per-frame activity estimate
+    active: np.ndarray         # (K, T) bool: `posterior_activity.decide(prior, power, rule)`
+    intervals: list            # per class [(start, end), ...] in samples
+
+
+@dataclass
 class GSS:
     """core.py:144-214 -> CACGMMTrainer.fit / predict for every frequency."""
     iterations: int
     iterations_post: int
     verbose: bool = True
+    # One prior per class and frame for all frequencies in place of a mixture weight per class and
+    # frequency (`ops.cacgmm_posteriors_shared_prior`; pb_bss weight_constant_axis=-3, which the
+    # reference never calls).  Off: the reference's model, every call as before.
+    shared_prior: bool = False
 
     def __call__(self, Obs, acitivity_freq, debug=False, *, initialization=None):
         """``acitivity_freq`` (K,T), or (K,T,F) for guidance that differs by frequency: zero =
@@ -178,6 +191,8 @@ class GSS:
         (K,T,F): initial affiliations used as given instead of the ones derived from the
         activity (a neural mask, the posteriors of an earlier pass).  A 0/1 activity without
         ``initialization`` takes the unweighted call; everything else the guided one."""
+        if self.shared_prior:
+            return self._call_shared_prior(Obs, acitivity_freq, debug, initialization)
         binary = ops.activity_is_binary(acitivity_freq, initialization)
         if binary:
             posterior = ops.cacgmm_posteriors(
@@ -202,6 +217,23 @@ class GSS:
                 if self.iterations_post > 1:
                     model = ops.cacgmm_fit(Obs, iterations=self.iterations_post - 1, model=model)
                 return model
+            self.locals = _DebugLocals(locals(), learned)
+        return posterior
+
+    def _call_shared_prior(self, Obs, acitivity_freq, debug, initialization):
+        """Every kind of activity through `ops.cacgmm_posteriors_shared_prior`: the activity is
+        the mask (weak guidance: who may speak), its weights or ``initialization`` the start."""
+        derived, source_active_mask = ops.guidance_from_activity(acitivity_freq)
+        if initialization is None:
+            initialization = derived
+        posterior, prior = ops.cacgmm_posteriors_shared_prior(
+            Obs, initialization, source_active_mask, iterations=self.iterations,
+            iterations_post=self.iterations_post, return_prior=True)
+        if debug:
+            def learned():
+                raise NotImplementedError(
+                    "GSS(shared_prior=True) has no 'learned' model: a model whose weight is "
+                    '(K,T) cannot predict other frames')
             self.locals = _DebugLocals(locals(), learned)
         return posterior
 
@@ -816,20 +848,23 @@ class Enhancer:
                     'projection of the human annotations.') from None
         return reference_array
 
-    def _prepare_example(self, ex, dtype=np.float64):
+    def _prepare_example(self, ex, dtype=np.float64, with_activity=True):
         """Host side of enhance_example (core.py:396-490): activity slices of the
         reference array, channel selection, arrays cut to the shortest.  ``dtype=np.int16``
-        keeps the PCM samples as stored (the session driver converts on the device)."""
-        session_id = ex['session_id']
+        keeps the PCM samples as stored (the session driver converts on the device).
+        ``with_activity=False`` (the annotation-free methods): only the audio is loaded -- no
+        annotation and no target speaker is looked up -- and (obs, None, None) returned."""
         reference_array = self._reference_array(ex)
-        speaker_id = ex['speaker_id']
-
-        array_start = ex['start']['observation'][reference_array]
-        array_end = ex['end']['observation'][reference_array]
-        ex_array_activity = {
-            k: arr[array_start:min(array_end, len(arr))]
-            for k, arr in self.activity[session_id][reference_array].items()
-        }
+        ex_array_activity = speaker_id = None
+        if with_activity:
+            session_id = ex['session_id']
+            speaker_id = ex['speaker_id']
+            array_start = ex['start']['observation'][reference_array]
+            array_end = ex['end']['observation'][reference_array]
+            ex_array_activity = {
+                k: arr[array_start:min(array_end, len(arr))]
+                for k, arr in self.activity[session_id][reference_array].items()
+            }
 
         def load_arrays(select):
             arrays = [
@@ -906,6 +941,17 @@ class Enhancer:
             raise NotImplementedError(
                 f'{what} with bf={self.bf_block.type!r}: the WPD beamformer is built for '
                 'enhance_observation, enhance_example and enhance_session only')
+
+    def _no_blind_options(self, what):
+        """The annotation-free path is built for the whole-window beamformers on all channels
+        after one joint WPE."""
+        self._no_segments(what)
+        self._no_null(what)
+        self._no_channel_keep(what)
+        self._no_wpd(what)
+        if self.wpe_per_array:
+            raise NotImplementedError(
+                f'{what} with wpe_per_array: the annotation-free path runs one joint WPE')
 
     def _no_activity_options(self, what):
         """The posterior activity is built for the whole-window MVDR on all channels."""
@@ -1088,6 +1134,75 @@ class Enhancer:
         window_start, _ = self._audio_span(ex, self._reference_array(ex))
         intervals = [(window_start + a, window_start + b) for a, b in intervals]
         return self._trim_context(x_hat, ex), intervals
+
+    def enhance_observation_blind(self, obs, num_speakers, ex=None, *, seed=0, rule=None,
+                                  debug=False):
+        """Separation without an annotation, on the stage operators: stft -> WPE -> the CACGMM
+        with a frequency-shared prior from `ops.blind_initialization` with K = num_speakers + 1
+        classes (`ops.cacgmm_posteriors_blind`, ``gss_block.iterations`` iterations) -> for every
+        class k the masks (target k, distortion = the rest; the context frames of ``ex`` dropped
+        as ``bf_drop_context`` says) -> the configured beamformer -> istft.  Returns a
+        `BlindSeparation`: x_hat (K,N), the prior (K,T) -- a per-frame activity estimate of every
+        class --, what `posterior_activity.decide` (``rule``: an `ActivityRule`, None: its
+        defaults) makes of it, and the sample intervals of every class.  Classes carry indices,
+        not speaker names, and which of them is the noise class is not decided here (the class
+        with the flattest prior is a usable guess).  Not with ``bf_segment_frames``,
+        ``bf_null_interferer``, ``channel_keep``, the WPD beamformers or ``wpe_per_array``
+        (NotImplementedError)."""
+        what = 'enhance_observation_blind'
+        self._no_blind_options(what)
+        if (isinstance(num_speakers, bool) or not isinstance(num_speakers, (int, np.integer))
+                or not 1 <= num_speakers <= 18):
+            raise ValueError(f'num_speakers: {num_speakers!r} is not an integer in [1, 18]')
+        rule = pact.ActivityRule() if rule is None else rule
+        obs = np.asarray(obs)
+        if obs.ndim != 2:
+            raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+        K = int(num_speakers) + 1
+        iterations = self.gss_block.iterations
+        ops.blind_initialization(K, 1, seed)        # (argument errors before any device work)
+        ctx = self._ctx()
+        Obs = self._blocks_wpe(self.stft(obs), debug, 1)
+        posterior, prior = ops.cacgmm_posteriors_blind(Obs, K, iterations, seed=seed,
+                                                       return_prior=True, ctx=ctx)
+        _, power = ops.posterior_activity(Obs, posterior, None, return_power=True, ctx=ctx)
+        active = pact.decide(prior, power, rule)
+        masks = posterior.copy()
+        if self.bf_drop_context and ex is not None and 'start_orig' in ex:
+            start_context_frames, end_context_frames = start_end_context_frames(
+                ex, stft_size=self.stft_size, stft_shift=self.stft_shift,
+                stft_fading=self.stft_fading)
+            masks[:, :start_context_frames, :] = 0
+            if end_context_frames > 0:
+                masks[:, -end_context_frames:, :] = 0
+        X_hat = [self.bf_block(Obs, target_mask=masks[k],
+                               distortion_mask=np.sum(np.delete(masks, k, axis=0), axis=0))
+                 for k in range(K)]
+        x_hat = np.stack([self.istft(X) for X in X_hat])
+        num_samples = obs.shape[-1]
+        intervals = [pact.frames_to_intervals(active[k], self.stft_size, self.stft_shift,
+                                              self.stft_fading, num_samples) for k in range(K)]
+        if debug:
+            self.enhance_observation_locals = locals()
+        return BlindSeparation(x_hat, prior, active, intervals)
+
+    def enhance_example_blind(self, ex, num_speakers, **kw):
+        """`enhance_observation_blind` from an example: channels, context and trimming as
+        `enhance_example`; the example's activity and target speaker are not looked up (a session
+        without an annotation works).  The intervals are clipped to the
+        utterance's own span and count samples of the recording on the reference array's
+        clock."""
+        self._no_blind_options('enhance_example_blind')
+        obs, _, _ = self._prepare_example(ex, with_activity=False)
+        out = self.enhance_observation_blind(obs, num_speakers, ex=ex, **kw)
+        keep = self._keep_range(ex)
+        window_start, _ = self._audio_span(ex, self._reference_array(ex))
+        intervals = []
+        for row in out.intervals:
+            if keep is not None:
+                row = pact.clip_intervals(row, *keep)
+            intervals.append([(window_start + a, window_start + b) for a, b in row])
+        return BlindSeparation(self._trim_context(out.x_hat, ex), out.prior, out.active, intervals)
 
     def enhance_observation_guided(self, obs, frame_guidance, speaker_id, ex=None, *,
                                    initialization=None, debug=False, fused=None,

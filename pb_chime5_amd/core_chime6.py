@@ -57,15 +57,18 @@ class Enhancer(core.Enhancer):
             drop_unknown_target_speaker=True, context_samples=self.context_samples,
             equal_start_context=False)
 
-    def _prepare_example(self, ex, dtype=np.float64):
-        """Host side of core_chime6.py:396-487: one clock for activity and all arrays."""
-        session_id = ex['session_id']
-        speaker_id = ex['speaker_id']
+    def _prepare_example(self, ex, dtype=np.float64, with_activity=True):
+        """Host side of core_chime6.py:396-487: one clock for activity and all arrays.
+        ``with_activity=False``: the audio only, (obs, None, None)."""
         array_start, array_end = ex['start'], ex['end']
-        ex_array_activity = {
-            k: arr[array_start:min(array_end, len(arr))]
-            for k, arr in self.activity[session_id].items()
-        }
+        ex_array_activity = speaker_id = None
+        if with_activity:
+            session_id = ex['session_id']
+            speaker_id = ex['speaker_id']
+            ex_array_activity = {
+                k: arr[array_start:min(array_end, len(arr))]
+                for k, arr in self.activity[session_id].items()
+            }
 
         def load_arrays(select):
             arrays = [load_audio(ex['audio_path']['observation'][array], start=array_start,

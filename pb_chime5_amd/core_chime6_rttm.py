@@ -85,19 +85,24 @@ class Enhancer(core.Enhancer):
                                 refined_rttm=refined_rttm)
         parallel.barrier()      # (split_managed ends without one; the pipeline has drained)
 
-    def _prepare_example(self, ex, dtype=np.float64):
+    def _prepare_example(self, ex, dtype=np.float64, with_activity=True):
         """core_chime6_rttm.py:228-258.  Examples of ``get_dataset`` carry their audio;
-        inside ``enhance_session`` it is read here (``dtype=np.int16``: PCM as stored)."""
+        inside ``enhance_session`` it is read here (``dtype=np.int16``: PCM as stored).
+        ``with_activity=False``: the audio only, (obs, None, None)."""
         array_start, array_end = ex['start'], ex['end']
-        ex_array_activity = {
-            k: arr[array_start:array_end] for k, arr in self.activity[ex['session_id']].items()
-        }
+        if not with_activity:
+            ex_array_activity = None
+        else:
+            ex_array_activity = {
+                k: arr[array_start:array_end]
+                for k, arr in self.activity[ex['session_id']].items()
+            }
         obs = ex.get('audio_data')
         if obs is None:
             obs = rttm_module.recursive_load_audio(
                 ex['audio_path'], start=array_start, stop=array_end,
                 min_num_samples=ex.get('end_orig', array_end) - array_start, dtype=dtype)
-        return obs, ex_array_activity, ex['speaker_id']
+        return obs, ex_array_activity, ex['speaker_id'] if with_activity else None
 
     def _trim_context(self, x_hat, ex):
         if self.context_samples > 0:

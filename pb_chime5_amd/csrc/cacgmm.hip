@@ -2210,9 +2210,10 @@ int psd3_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, cons
     return GSS_OK;
 }
 
-size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K) {
+size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K, bool one_block) {
     const size_t NE = tri_count(D);
-    const EmBlockPlan bp = em_block_plan(F, T, D, K);
+    // (one_block: the plan of the shared-prior schedule, whatever the block settings say)
+    const EmBlockPlan bp = one_block ? EmBlockPlan{F, 1, 1} : em_block_plan(F, T, D, K);
     const EmStrides st = em_strides(bp, F, T, D);
     size_t b = 0;
     b += align_up(sizeof(cplx) * (size_t)F * NE * K);            // Mq
@@ -2270,8 +2271,10 @@ int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, co
     const bool reg = estep_reg_supported(D, K) && !gss_variant_set("estep_lds");
     // one array: the whole EM (all iterations + predict) in one launch (em_onchip4_kernel)
     const bool onchip = s.onchip_allowed && D == 4 && K >= 2 && K <= 6 && reg && iterations > 0 &&
-                        !gss_variant_set("em_unfused");
-    const EmBlockPlan bplan = onchip ? EmBlockPlan{F, 1, 1} : em_block_plan(F, T, D, K);
+                        !gss_variant_set("em_unfused") && !s.shared_prior;
+    // (a prior shared by the frequencies: blocks that advance on their own cannot form it)
+    const EmBlockPlan bplan =
+        onchip || s.shared_prior ? EmBlockPlan{F, 1, 1} : em_block_plan(F, T, D, K);
     const EmStrides st = em_strides(bplan, F, T, D);
 
     cplx *Mq = arena_alloc_t<cplx>(ctx, (size_t)F * NE * K);
@@ -2293,6 +2296,12 @@ int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, co
     GSS_REQUIRE(ctx, Mq && logdet && pi && W && Bp && Sg_lds && Yn && Sg_reg && need_eigh && tri_tab &&
                          zero_tiles,
                 GSS_ERR_NOMEM, "cacgmm workspace");
+    EmPriorWork pw{};
+    if (s.shared_prior) {
+        GSS_REQUIRE(ctx, !s.import_model && !s.export_model && !s.loglik, GSS_ERR_INVALID,
+                    "cacgmm: a model with a shared prior cannot leave the call");
+        GSS_TRY(cacgmm_prior_alloc(ctx, F, T, K, s.prior, &pw));
+    }
     GSS_REQUIRE(ctx, em_estep_lds(D, K) <= 160 * 1024 &&
                          wcov_lds_layout(D, std::min(K, 8)).total <= 160 * 1024,
                 GSS_ERR_UNSUPPORTED, "cacgmm: D=%d K=%d LDS", D, K);
@@ -2368,6 +2377,15 @@ int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, co
     };
     auto estep = [&](EmBlock &b, int mode) -> int {
         EmArgs &a = b.a;
+        if (s.shared_prior) {
+            a.Sg = pw.Sg;
+            const EmPriorArgs p{b.Yn, b.Mq, a.logdet, pw.prior, a.act, a.act_stride, a.act_fstride,
+                                a.init, a.init_stride, a.init_fstride, a.W, pw.G, pw.Sg, a.gamma,
+                                T, b.F, D, a.masked, a.aff_eps};
+            return cacgmm_prior_estep_run(ctx, p, K, mode == MODE_FIRST ? EM_PRIOR_FIRST
+                                                     : mode == MODE_EM  ? EM_PRIOR_FIT
+                                                                        : EM_PRIOR_PREDICT);
+        }
         if (reg && mode != MODE_FIRST) {
             a.Sg = b.Sg_reg;
             switch (D) {
@@ -2442,7 +2460,13 @@ int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, co
     // CACGMMTrainer.fit(initialization=array, iterations=I, source_activity_mask)
     auto em_iteration = [&](EmBlock &b, bool first) -> int {
         GSS_TRY(estep(b, first ? MODE_FIRST : MODE_EM));
-        b.sg_nch = (reg && !first) ? b.reg_nch : b.nch_lds;
+        b.sg_nch = s.shared_prior ? ntile : (reg && !first) ? b.reg_nch : b.nch_lds;
+        if (s.shared_prior) {
+            // prior[k, t] = mean over f of the affiliations the covariance is formed from; one
+            // table for every frequency is its own mean (copied, not summed F times)
+            const bool one_table = guide.init ? guide.init_f_stride == 0 : guide.mask_f_stride == 0;
+            GSS_TRY(cacgmm_prior_update_run(ctx, pw, first && one_table ? 1 : F, K, T));
+        }
         GSS_TRY(launch_mstep_k(ctx, K, b.a, b.Yn, b.F));
         return eig(b);
     };

@@ -707,6 +707,30 @@ extern "C" int gss_cacgmm_guided(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t
                       gamma);
 }
 
+// pb_bss weight_constant_axis=-3: one prior[k, t] for all frequencies in place of pi[f, k]
+extern "C" int gss_cacgmm_shared_prior(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                                       const gss_guidance *g, int K, int iterations, int post,
+                                       double *gamma, double *prior) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, Y && gamma && F >= 1 && T >= 1, GSS_ERR_INVALID,
+                "gss_cacgmm_shared_prior: bad arguments");
+    GSS_TRY(check_cacgmm_args(ctx, D, K, iterations, post));
+    EmGuide guide;
+    GSS_TRY(check_guidance(ctx, g, K, T, &guide));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
+    GSS_TRY(arena_reserve(ctx, cacgmm_workspace_bytes(F, T, D, K, /*one_block=*/true) +
+                                   cacgmm_prior_workspace_bytes(F, T, K)));
+    // the schedule of cacgmm_run: fit, post - 1 unmasked iterations, predict (masked for post 0)
+    EmSchedule s;
+    s.iterations = iterations;
+    s.model_iterations = std::max(post - 1, 0);
+    s.predict_masked = post == 0;
+    s.gamma = gamma;
+    s.shared_prior = true;
+    s.prior = prior;
+    return cacgmm_schedule_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, guide, K, s);
+}
+
 // ------------------------------------------------------------------ the model as an object
 // The mask of a guidance that may be absent (fit(initialization=model), predict): NULL or no
 // mask = unmasked; the initialisation's fields are not read.

@@ -281,7 +281,7 @@ int wpe_arrays_regroup_run(gss_ctx *ctx, const cplx *src, int F, int64_t T, int 
 // second stream + fork / join events of a context, created on first use
 int aux_stream_ready(gss_ctx *ctx);
 
-size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K);
+size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K, bool one_block = false);
 // What guides the mixture model (gss_guidance on the device side): initial affiliations and
 // source activity mask, element (f, k, t) at [f * f_stride + k * k_stride + t]; f stride 0 =
 // one (K, T) table for every frequency.  init NULL: the initialisation is derived from the mask
@@ -320,6 +320,12 @@ struct EmSchedule {
     double *loglik = nullptr;        // (F,T), NULL = none
     const EmModel *import_model = nullptr, *export_model = nullptr;
     bool onchip_allowed = false;
+    // One prior[k, t] for all frequencies in place of pi[f, k] (gss_cacgmm_shared_prior; pb_bss
+    // weight_constant_axis=-3): the multi-launch path as ONE block of frequencies on one stream,
+    // E-steps from cacgmm_prior.hip; no model import / export and no log-likelihood.  `prior`
+    // (K,T) receives the prior of the last M-step -- the one the predict step used -- or is NULL.
+    bool shared_prior = false;
+    double *prior = nullptr;
 };
 int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGuide &guide,
                         int K, const EmSchedule &s);
@@ -333,6 +339,37 @@ int cacgmm_loglik_run(gss_ctx *ctx, const cplx *Yn, const cplx *Mq, const double
                       const double *pi, const uint8_t *act, int64_t act_stride,
                       int64_t act_fstride, int masked, int F, int64_t T, int D, int K,
                       double *loglik);
+
+// cacgmm_prior.hip: the E-step with a per-frame prior shared by the frequencies and the prior
+// update.  The workspace the mode adds to cacgmm_workspace_bytes has its own term.
+enum { EM_PRIOR_FIRST = 0, EM_PRIOR_FIT = 1, EM_PRIOR_PREDICT = 2 };
+struct EmPriorWork {
+    double *G;       // (F,K,T) clipped affiliations of the last fit E-step
+    double *prior;   // (K,T)
+    double *part;    // (slices,K,T) of the column sum
+    double *Sg;      // (F, ceil(T / 64), K) sums of gamma per 64-frame tile
+};
+struct EmPriorArgs {
+    const cplx *Yn;             // (F,D,T) unit-normalised observation
+    const cplx *Mq;             // (F,NE,K)
+    const double *logdet;       // (F,K)
+    const double *prior;        // (K,T)
+    const uint8_t *act;         // mask, element (f, k, t) at [f * act_fstride + k * act_stride + t];
+    int64_t act_stride, act_fstride;    // always readable, used when `masked` (or init == NULL)
+    const double *init;         // EM_PRIOR_FIRST: initial affiliations, NULL = derived from the mask
+    int64_t init_stride, init_fstride;
+    double *W, *G, *Sg;         // EM_PRIOR_FIRST / FIT: (F,K,T), (F,K,T), (F, ceil(T / 64), K)
+    double *gamma;              // EM_PRIOR_PREDICT: (F,K,T)
+    int64_t T;
+    int F, D;
+    int masked;
+    double aff_eps;             // clip, 0 = none
+};
+size_t cacgmm_prior_workspace_bytes(int F, int64_t T, int K);
+int cacgmm_prior_alloc(gss_ctx *ctx, int F, int64_t T, int K, double *prior_out, EmPriorWork *w);
+int cacgmm_prior_estep_run(gss_ctx *ctx, const EmPriorArgs &a, int K, int mode);
+// prior = mean over the first nf frequencies of w.G (nf = 1: a frequency-independent table, copied)
+int cacgmm_prior_update_run(gss_ctx *ctx, const EmPriorWork &w, int nf, int K, int64_t T);
 
 // S > 1: S targets' weights (S, F, 2, T) -> partials (S, F, nch, 2, NE), one launch
 int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,

@@ -10,6 +10,10 @@ here                        reference call (file:line)
 ``wpe_v8``                  nara_wpe.wpe.wpe_v8           (core.py:52-58)
 ``cacgmm_posteriors``       CACGMMTrainer.fit + predict   (core.py:165-208)
 ``cacgmm_posteriors_guided``  the same from any initialisation / source_activity_mask
+``cacgmm_posteriors_shared_prior`` / ``cacgmm_posteriors_blind`` / ``blind_initialization``
+                            the same with one prior per class and frame for all frequencies
+                            (pb_bss ``weight_constant_axis=-3``, which the reference never
+                            calls): separation without an annotation
 ``mvdr_souden_from_masks``  pb_bss beamformer chain       (beamforming_wrapper.py:51-97)
 ``mvdr_souden_segments_from_masks``  the same with statistics per segment of frames
 ``lcmv_souden_from_masks``  beamform_lcmv_souden_from_masks (beamforming_wrapper.py:127-171)
@@ -38,6 +42,7 @@ from .cacgmm import CACGMM
 
 _BF_CODES = {'mvdrSouden_ban': 0, 'ch2': 1, 'sum': 2, 'gev_ban': 3}
 _POSTFILTER_CODES = {None: 0, 'mask_mul': 1}
+_MAX_CHANNELS, _MAX_CLASSES = 32, 19      # include/gss_hip.h: GSS_MAX_CHANNELS, GSS_MAX_CLASSES
 
 
 # --------------------------------------------------------------------------
@@ -373,6 +378,90 @@ def cacgmm_posteriors_guided(Obs, initialization=None, source_activity_mask=None
     ctx._check(ctx.lib.gss_layout_permute_f64(ctx.handle, c_void_p(g_d.ptr), F, K * T, 1, 2,
                                               c_void_p(o_d.ptr)), 'gss_layout_permute_f64')
     return ctx.to_host(o_d, (K, T, F), np.float64)
+
+
+def _check_em_iterations(iterations, iterations_post):
+    for name, value, least in (('iterations', iterations, 1),
+                               ('iterations_post', iterations_post, 0)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least:
+            raise ValueError(f'{name}: {value!r} is not an integer >= {least}')
+
+
+def _check_em_obs(Obs):
+    Obs = np.asarray(Obs)
+    if Obs.ndim != 3:
+        raise ValueError(f'Obs: shape {Obs.shape} is not (D,T,F)')
+    if not np.iscomplexobj(Obs):
+        raise ValueError(f'Obs: dtype {Obs.dtype} is not complex')
+    D, T, F = Obs.shape
+    if not 2 <= D <= _MAX_CHANNELS:
+        raise ValueError(f'Obs: {D} channels outside [2, {_MAX_CHANNELS}]')
+    if T < 1 or F < 1:
+        raise ValueError(f'Obs: shape {Obs.shape} has no frames or no frequencies')
+    return Obs
+
+
+def cacgmm_posteriors_shared_prior(Obs, initialization=None, source_activity_mask=None,
+                                   iterations=20, iterations_post=1, *, return_prior=False,
+                                   ctx=None):
+    """`cacgmm_posteriors_guided` with one prior ``prior[k, t]`` per class and frame, shared by
+    all frequencies, in place of the mixture weight ``pi[f, k]``: pb_bss's
+    ``CACGMMTrainer(...).fit(..., weight_constant_axis=-3)``.  The M-step forms the prior as the
+    mean over f of the (clipped) affiliations; the first one takes it from the initialisation.
+    Obs (D,T,F) complex; tables as in `cacgmm_posteriors_guided` -> posterior (K,T,F) float64,
+    with ``return_prior`` also the prior (K,T) of the last M-step, the one the final predict
+    used.  Every argument error is a ValueError before any device work."""
+    Obs = _check_em_obs(Obs)
+    _check_em_iterations(iterations, iterations_post)
+    init, mask, K = guidance_tables(initialization, source_activity_mask, *Obs.shape[1:])
+    if not 1 <= K <= _MAX_CLASSES:
+        raise ValueError(f'{K} classes outside [1, {_MAX_CLASSES}]')
+    ctx = ctx or default_context()
+    Y_d, (D, T, F) = _obs_to_device_ftd(ctx, Obs)
+    guide = DeviceGuidance(ctx, init, mask, T)
+    g_d = ctx.empty(8 * F * K * T)
+    o_d = ctx.empty(8 * F * K * T)
+    p_d = ctx.empty(8 * K * T) if return_prior else None
+    ctx._check(ctx.lib.gss_cacgmm_shared_prior(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, D, ctypes.byref(guide.struct), K, int(iterations),
+        int(iterations_post), c_void_p(g_d.ptr), c_void_p(p_d.ptr if p_d else None)),
+        'gss_cacgmm_shared_prior')
+    # (F, K*T) -> (K*T, F)
+    ctx._check(ctx.lib.gss_layout_permute_f64(ctx.handle, c_void_p(g_d.ptr), F, K * T, 1, 2,
+                                              c_void_p(o_d.ptr)), 'gss_layout_permute_f64')
+    posterior = ctx.to_host(o_d, (K, T, F), np.float64)
+    if return_prior:
+        return posterior, ctx.to_host(p_d, (K, T), np.float64)
+    return posterior
+
+
+def blind_initialization(num_classes, num_frames, seed=0):
+    """The start of the annotation-free EM: ``np.random.default_rng(seed).uniform(size=(K, T))``
+    divided by its sum over k -- one (K,T) table for every frequency, which is what lets the
+    shared prior keep class k the same source in every bin.  The definition is exact (the same
+    seed gives the same bits)."""
+    for name, value in (('num_classes', num_classes), ('num_frames', num_frames), ('seed', seed)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise ValueError(f'{name}: {value!r} is not an integer')
+    if not 1 <= num_classes <= _MAX_CLASSES:
+        raise ValueError(f'num_classes: {num_classes} outside [1, {_MAX_CLASSES}]')
+    if num_frames < 1:
+        raise ValueError(f'num_frames: {num_frames} < 1')
+    if seed < 0:
+        raise ValueError(f'seed: {seed} is negative')
+    table = np.random.default_rng(int(seed)).uniform(size=(int(num_classes), int(num_frames)))
+    return table / np.sum(table, axis=0, keepdims=True)
+
+
+def cacgmm_posteriors_blind(Obs, num_classes, iterations=20, *, seed=0, return_prior=False,
+                            ctx=None):
+    """Separation without an annotation: `cacgmm_posteriors_shared_prior` from
+    `blind_initialization`, no mask, ``iterations_post=1``.  Obs (D,T,F) -> posterior (K,T,F)
+    (and the prior (K,T)).  Classes carry indices, not names."""
+    Obs = _check_em_obs(Obs)
+    init = blind_initialization(num_classes, Obs.shape[1], seed)
+    return cacgmm_posteriors_shared_prior(Obs, init, None, iterations, 1,
+                                          return_prior=return_prior, ctx=ctx)
 
 
 class DeviceModel:
