@@ -88,7 +88,9 @@ typedef enum {
  * gss_bf_lcmv descriptor.  So were gss_posterior_activity and gss_enhance_observation_activity.
  * So were gss_wpe_weighted, gss_wpd_weights, gss_wpd_souden, gss_last_wpd_zero_pivots and
  * gss_enhance_observation_wpd with the gss_bf_wpd descriptor.  So was gss_cacgmm_shared_prior
- * (it takes the gss_guidance descriptor as it is). */
+ * (it takes the gss_guidance descriptor as it is).  So were gss_wpe_online_init, gss_wpe_online and
+ * gss_enhance_observation_wpe_online with the gss_wpe_online_state and gss_wpe_online_cfg
+ * descriptors. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -552,6 +554,47 @@ int gss_wpd_souden(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
  * like gss_last_wpe_zero_pivots); 0 before any. */
 int gss_last_wpd_zero_pivots(gss_ctx *ctx, int64_t *count_host);
 
+/* ---- online WPE -------------------------------------------------------------
+ * Frame-recursive dereverberation with a carried state: nara_wpe's online form (a recursive
+ * least-squares filter that is updated at every frame and forgets at the rate alpha), which the
+ * reference never calls.  (Entry points only, looked up by the binding: revision still 7.)
+ * A problem is one frequency f, or one (frequency, array) pair under per-array WPE, with C
+ * channels, n = taps * C and L = taps + delay.  For each frame t, in order:
+ *    buf   = [hist; y_t]                        (L+1, C): frames t-L .. t (zeros before the stream)
+ *    sigma = sum |buf|^2 / ((L+1) C)
+ *    w[tau C + c] = frame t - delay - tau, channel c,   tau = 0 .. taps-1
+ *    x_t   = y_t - G^H w                        the OUTPUT: the filter before its update
+ *    nom   = P w;  den = alpha sigma + Re(w^H nom)
+ *    den > 0:  P <- (P - nom nom^H / den) / alpha,  G <- G + (nom / den) x_t^H
+ *    else:     P, G unchanged -- the whole buffer is digital silence (w = 0, y_t = 0, x_t = 0),
+ *              where the literal recursion divides 0 by 0
+ *    hist  <- buf[1:]
+ * A fresh state is P = I, G = 0, hist = 0. */
+typedef struct {
+    gss_cplx *inv_cov_dev;  /* (F, A, n, n) row-major; a reader takes the upper triangle and the real
+                               part of the diagonal; on return both triangles are stored, the lower
+                               the exact conjugate of the upper, diagonal imaginary parts 0 */
+    gss_cplx *filter_dev;   /* (F, A, n, C) */
+    gss_cplx *history_dev;  /* (F, A, taps + delay, C), oldest frame first */
+} gss_wpe_online_state;    /* caller-owned, like gss_cacgmm_model */
+
+/* P = I, G = 0, hist = 0 in the caller's buffers.  Errors as gss_wpe_online. */
+int gss_wpe_online_init(gss_ctx *ctx, int F, int A, int C, int taps, int delay,
+                        const gss_wpe_online_state *state);
+
+/* Y (F,T,A*C) -> X (F,T,A*C), channels array-major as in gss_wpe_arrays; A = 1 is the joint WPE.
+ * `state` is read, advanced by T frames and written back; NULL: a fresh state that is thrown
+ * away after the call.  T = 0 is a no-op.  One persistent workgroup per problem walks the
+ * frames; n <= 64 keeps the state on the chip for the whole call, larger n (or GSS_VARIANT
+ * wpe_online_mem) leaves it in its buffers -- the form depends on n alone, so a recording fed in
+ * blocks through one state gives the bits of the single call.  No atomics: the same call gives
+ * the same bits.
+ * GSS_ERR_INVALID (the message names the argument), before any launch: a NULL pointer, a NULL
+ * state field, F < 1, T < 0, A < 1, C < 1, taps < 1, delay < 0 or >= 2^20, alpha outside (0, 1]
+ * or not finite, X_dev == Y_dev.  GSS_ERR_UNSUPPORTED: taps * C > 512, A * C > GSS_MAX_CHANNELS. */
+int gss_wpe_online(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int A, int C, int taps,
+                   int delay, double alpha, const gss_wpe_online_state *state, gss_cplx *X_dev);
+
 /* beamform_gev_from_masks (beamforming_wrapper.py:77-89,192-208): masked PSD
  * matrices, principal generalised eigenvector of (Phi_X, Phi_N) with
  * w^H Phi_N w = 1 (phase arbitrary, as upstream), optional BAN, apply.
@@ -746,6 +789,23 @@ int gss_enhance_observation_wpd(gss_ctx *ctx, const gss_params *params,
                                 int64_t end_context_samples,
                                 const gss_bf_wpd *wpd,
                                 double *out_dev, const gss_debug_taps *taps);
+
+/* gss_enhance_observation with gss_wpe_online from a fresh state in the place of the offline WPE:
+ * an exponentially forgetting, time-varying dereverberation filter in front of the mixture model
+ * and the beamformer.  wpe_taps, wpe_delay and wpe_arrays come from `params`; wpe_iterations is
+ * not read.  Everything else, the taps included (Obs_ftd: after the online WPE), is
+ * gss_enhance_observation's; gss_last_wpe_zero_pivots reads 0 afterwards (there is no solve).
+ * GSS_ERR_INVALID: cfg NULL, alpha outside (0, 1] or not finite, params->wpe == 0,
+ * params->wpe_psd_context != 0.  GSS_ERR_UNSUPPORTED: wpe_taps * channels per array > 512. */
+typedef struct { double alpha; } gss_wpe_online_cfg;
+int gss_enhance_observation_wpe_online(gss_ctx *ctx, const gss_params *params,
+                                       const double *obs_dev, int D, int64_t N,
+                                       const uint8_t *act_dev, int K, int64_t N_act,
+                                       int target_index,
+                                       int64_t start_context_samples,
+                                       int64_t end_context_samples,
+                                       const gss_wpe_online_cfg *cfg,
+                                       double *out_dev, const gss_debug_taps *taps);
 
 /* gss_enhance_observation plus gss_posterior_activity on the pipeline's own post-WPE observation
  * and its posteriors before context zeroing (what the taps Obs_ftd and gamma show), nothing

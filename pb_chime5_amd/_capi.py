@@ -69,6 +69,17 @@ class GssBfWpd(ctypes.Structure):
                 ('power_floor', ctypes.c_double)]
 
 
+class GssWpeOnlineState(ctypes.Structure):
+    """gss_wpe_online_state: P (F,A,n,n), G (F,A,n,C) and the last taps + delay frames (F,A,L,C)
+    of the online WPE, complex, in HBM."""
+    _fields_ = [('inv_cov_dev', c_void_p), ('filter_dev', c_void_p), ('history_dev', c_void_p)]
+
+
+class GssWpeOnlineCfg(ctypes.Structure):
+    """gss_wpe_online_cfg: the forgetting factor of the online WPE in the fused call."""
+    _fields_ = [('alpha', ctypes.c_double)]
+
+
 class GssChannelSelect(ctypes.Structure):
     """gss_channel_select: the band table and the settings of the envelope-variance channel
     selection."""
@@ -171,6 +182,11 @@ SIGNATURES = {
                                ctypes.POINTER(GssBfWpd), c_int, c_void_p, c_void_p]),
     'gss_last_wpd_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_enhance_observation_wpd': _fused(ctypes.POINTER(GssBfWpd)),
+    'gss_wpe_online_init': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                    ctypes.POINTER(GssWpeOnlineState)]),
+    'gss_wpe_online': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int,
+                               ctypes.c_double, ctypes.POINTER(GssWpeOnlineState), c_void_p]),
+    'gss_enhance_observation_wpe_online': _fused(ctypes.POINTER(GssWpeOnlineCfg)),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,

@@ -28,13 +28,47 @@ from pb_chime5_amd.utils.numpy_utils import morph
 
 @dataclass
 class WPE:
-    """core.py:41-88 -> nara_wpe.wpe.wpe_v8."""
+    """core.py:41-88 -> nara_wpe.wpe.wpe_v8.
+    ``online=True`` (an addition): nara_wpe's online form instead -- a frame-recursive filter that
+    forgets at the rate ``alpha``, from a fresh state (`ops.wpe_online_dtf`); ``iterations`` is
+    not read, ``stack=False`` means one filter per array, a ``psd_context`` other than 0 is
+    NotImplementedError.  alpha = 0.9999 is a choice, not a measurement."""
     taps: int
     delay: int
     iterations: int
     psd_context: int
+    online: bool = False
+    alpha: float = ops.WPE_ONLINE_ALPHA
+
+    def __post_init__(self):
+        if self.online:
+            ops.check_wpe_online(self.taps, self.delay, self.alpha)
+
+    def _call_online(self, Obs, stack, debug):
+        if self.psd_context != 0:
+            raise NotImplementedError(
+                f'online=True with psd_context={self.psd_context!r}: the online WPE has no PSD '
+                'context')
+        kw = dict(taps=self.taps, delay=self.delay, alpha=self.alpha)
+        if Obs.ndim == 3:
+            assert stack is None, stack
+            Obs = ops.wpe_online_dtf(Obs, **kw)
+        elif Obs.ndim == 4:
+            if stack is not True and stack is not False:
+                raise NotImplementedError(stack)
+            _A = Obs.shape[0]
+            Obs = morph('ACTF->A*CTF', Obs)
+            Obs = ops.wpe_online_dtf(Obs, arrays=1 if stack else _A, **kw)
+            Obs = morph('A*CTF->ACTF', Obs, A=_A)
+        else:
+            raise NotImplementedError(Obs.shape)
+        if debug:
+            self.locals = locals()
+        return Obs
 
     def __call__(self, Obs, stack=None, debug=False):
+        if self.online:
+            return self._call_online(Obs, stack, debug)
         kw = dict(taps=self.taps, delay=self.delay, iterations=self.iterations,
                   psd_context=self.psd_context)
         if Obs.ndim == 3:
@@ -443,6 +477,10 @@ class Enhancer:
     def __post_init__(self):
         if self._bf_wpd() is not None:      # (the one place that validates; raises for combinations)
             ops.check_bf_wpd(**self._bf_wpd(), channel_keep=self.channel_keep)
+            if self._wpe_online() is not None:
+                raise NotImplementedError(
+                    f'wpe_online with bf={self.bf_block.type!r}: the WPD beamformer dereverberates '
+                    'with an offline WPE step of its own')
         if self.channel_keep is None:
             return
         ops.check_channel_keep(self.channel_keep)
@@ -604,8 +642,10 @@ class Enhancer:
         # (a segment-wise beamformer has no pipelined pcm16 entry point: one at a time; neither
         # has the posterior activity of a refined RTTM)
         # (nor has the WPD: the pipelined path is out of its scope)
+        # (nor has the online WPE)
         if (self.inflight <= 1 or not self._fusable() or self._bf_segments() is not None
-                or refined_rttm or self._bf_wpd() is not None):
+                or refined_rttm or self._bf_wpd() is not None
+                or self._wpe_online() is not None):
             for ex in examples:
                 try:
                     if refined_rttm:
@@ -942,6 +982,17 @@ class Enhancer:
                 f'{what} with bf={self.bf_block.type!r}: the WPD beamformer is built for '
                 'enhance_observation, enhance_example and enhance_session only')
 
+    def _wpe_online(self):
+        """The forgetting factor of an online WPE block (``WPE.online``) or None."""
+        block = getattr(self, 'wpe_block', None)
+        return block.alpha if getattr(block, 'online', False) else None
+
+    def _no_wpe_online(self, what):
+        if self._wpe_online() is not None:
+            raise NotImplementedError(
+                f'{what} with wpe_online: the online WPE is built for enhance_observation, '
+                'enhance_example, enhance_session and the annotation-free methods only')
+
     def _no_blind_options(self, what):
         """The annotation-free path is built for the whole-window beamformers on all channels
         after one joint WPE."""
@@ -959,6 +1010,7 @@ class Enhancer:
         self._no_null(what)
         self._no_channel_keep(what)
         self._no_wpd(what)
+        self._no_wpe_online(what)
 
     @staticmethod
     def _no_posterior_activity(what, posterior_activity):
@@ -1015,8 +1067,22 @@ class Enhancer:
         ctx.set_utterances_in_flight(1)
         segments = self._bf_segments()
         select = self._channel_select()
+        online = self._wpe_online()
+        if online is not None:
+            # (the fused online call takes no second descriptor; the stage path combines)
+            for name, on in (('bf_segment_frames', segments is not None),
+                             ('bf_null_interferer', self._bf_null()),
+                             ('channel_keep', select is not None)):
+                if on:
+                    raise NotImplementedError(
+                        f'wpe_online with {name} in the fused call: pass fused=False for the '
+                        'stage path')
         try:
-            if self._bf_wpd() is not None:
+            if online is not None:
+                res = ops.enhance_observation_wpe_online(
+                    obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
+                    debug=debug, ctx=ctx, wpe_arrays=wpe_arrays, alpha=online)
+            elif self._bf_wpd() is not None:
                 res = ops.enhance_observation_wpd(
                     obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
                     debug=debug, ctx=ctx, wpe_arrays=wpe_arrays, **self._bf_wpd())
@@ -1215,6 +1281,7 @@ class Enhancer:
         given (a neural mask estimator's output).  ``fused=False`` runs the blocks."""
         self._no_segments('enhance_observation_guided')
         self._no_wpd('enhance_observation_guided')
+        self._no_wpe_online('enhance_observation_guided')
         self._no_null('enhance_observation_guided')
         self._no_channel_keep('enhance_observation_guided')
         if wpe_arrays is None:
@@ -1316,6 +1383,7 @@ class Enhancer:
         self._no_posterior_activity('enhance_observation_speakers', posterior_activity)
         self._no_segments('enhance_observation_speakers')
         self._no_wpd('enhance_observation_speakers')
+        self._no_wpe_online('enhance_observation_speakers')
         self._no_null('enhance_observation_speakers')
         self._no_channel_keep('enhance_observation_speakers')
         speaker_ids = self.speaker_ids_of(ex_array_activity, speaker_ids)
@@ -1354,6 +1422,7 @@ class Enhancer:
         self._no_posterior_activity('enhance_example_speakers', posterior_activity)
         self._no_segments('enhance_example_speakers')
         self._no_wpd('enhance_example_speakers')
+        self._no_wpe_online('enhance_example_speakers')
         self._no_null('enhance_example_speakers')
         self._no_channel_keep('enhance_example_speakers')
         obs, ex_array_activity, _ = self._prepare_example(ex)
@@ -1484,6 +1553,26 @@ def bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps=None, bf_wpd_delay=None
                 wpd_iterations=bf_wpd_iterations, wpd_power_floor=bf_wpd_power_floor)
 
 
+def wpe_block_from(wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context, wpe_online=False,
+                   wpe_alpha=ops.WPE_ONLINE_ALPHA):
+    """The WPE block of the ``get_enhancer`` functions from their ``wpe*`` keywords (None
+    without WPE).  NotImplementedError for the combinations nobody reads: ``wpe_online`` without
+    WPE or with a PSD context, a ``wpe_alpha`` other than the default without ``wpe_online``."""
+    assert wpe_online is True or wpe_online is False, wpe_online
+    if wpe_online and not wpe:
+        raise NotImplementedError('wpe_online with wpe=False: there is no WPE block to replace')
+    if wpe_online and wpe_psd_context != 0:
+        raise NotImplementedError(
+            f'wpe_online with wpe_psd_context={wpe_psd_context!r}: the online WPE has no PSD '
+            'context')
+    if not wpe_online and wpe_alpha != ops.WPE_ONLINE_ALPHA:
+        raise NotImplementedError(f'wpe_alpha={wpe_alpha!r} without wpe_online: nobody reads it')
+    if not wpe:
+        return None
+    return WPE(taps=wpe_tabs, delay=wpe_delay, iterations=wpe_iterations,
+               psd_context=wpe_psd_context, online=wpe_online, alpha=wpe_alpha)
+
+
 def get_enhancer(
     multiarray=False,
     reference_array=None,
@@ -1528,10 +1617,21 @@ def get_enhancer(
     bf_wpd_delay=None,
     bf_wpd_iterations=1,
     bf_wpd_power_floor=ops.WPD_POWER_FLOOR,
+    wpe_online=False,
+    wpe_alpha=ops.WPE_ONLINE_ALPHA,
 ):
     """core.py:574-637 (same keyword arguments and defaults; ``activity_store``,
     ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*``,
-    ``bf_null_*`` and ``bf_wpd_*`` are additions).
+    ``bf_null_*``, ``bf_wpd_*``, ``wpe_online`` and ``wpe_alpha`` are additions).
+    ``wpe_online=True``: the WPE block is nara_wpe's online form (see `ops.wpe_online_dtf`) -- a
+    frame-recursive filter from a fresh state per utterance that forgets at the rate
+    ``wpe_alpha`` (0.9999: a choice, not a measurement), the time-varying front for long windows
+    with movement; ``wpe_iterations`` is not read, ``wpe_per_array`` is honoured, a
+    ``wpe_psd_context`` other than 0 is NotImplementedError.  For `Enhancer.enhance_observation` /
+    `enhance_example`, one utterance at a time `enhance_session`, and the annotation-free
+    methods; not with the WPD types, the guided, multi-speaker or activity methods or
+    ``refined_rttm``, and with ``bf_segment_frames``, ``bf_null_interferer`` or ``channel_keep``
+    only on the stage path (``fused=False``) (NotImplementedError).
     ``bf='wpdSouden_ban'`` / ``'wpdSouden'``: the WPD convolutional beamformer (see
     `ops.wpd_souden_from_masks`) on the STFT BEFORE WPE -- WPE as configured still feeds the
     mixture model (``wpe_per_array`` only shapes that WPE) --, ``bf_wpd_taps`` / ``bf_wpd_delay``
@@ -1564,8 +1664,8 @@ def get_enhancer(
         multiarray=multiarray,
         reference_array=reference_array,
         context_samples=context_samples,
-        wpe_block=WPE(taps=wpe_tabs, delay=wpe_delay, iterations=wpe_iterations,
-                      psd_context=wpe_psd_context) if wpe else None,
+        wpe_block=wpe_block_from(wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context,
+                                 wpe_online, wpe_alpha),
         activity=Activity(type=activity_type, garbage_class=activity_garbage_class,
                           path=activity_path, database_path=database_path,
                           store=activity_store),

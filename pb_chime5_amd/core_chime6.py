@@ -156,10 +156,12 @@ def get_enhancer(
     bf_wpd_delay=None,
     bf_wpd_iterations=1,
     bf_wpd_power_floor=ops.WPD_POWER_FLOOR,
+    wpe_online=False,
+    wpe_alpha=ops.WPE_ONLINE_ALPHA,
 ):
     """core_chime6.py:572-635 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*`` and
-    ``bf_wpd_*`` are additions,
+    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*``,
+    ``bf_wpd_*``, ``wpe_online`` and ``wpe_alpha`` are additions,
     see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
@@ -167,8 +169,8 @@ def get_enhancer(
         multiarray=multiarray,
         reference_array=reference_array,
         context_samples=context_samples,
-        wpe_block=WPE(taps=wpe_tabs, delay=wpe_delay, iterations=wpe_iterations,
-                      psd_context=wpe_psd_context) if wpe else None,
+        wpe_block=core.wpe_block_from(wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context,
+                                      wpe_online, wpe_alpha),
         activity=Activity(type=activity_type, garbage_class=activity_garbage_class,
                           path=activity_path, database_path=database_path,
                           store=activity_store),

@@ -179,10 +179,12 @@ def get_enhancer(
     bf_wpd_delay=None,
     bf_wpd_iterations=1,
     bf_wpd_power_floor=ops.WPD_POWER_FLOOR,
+    wpe_online=False,
+    wpe_alpha=ops.WPE_ONLINE_ALPHA,
 ):
     """core_chime6_rttm.py:360-422 (same keyword arguments and defaults; ``device_id``,
-    ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*`` and
-    ``bf_wpd_*`` are additions, see core.get_enhancer)."""
+    ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*``,
+    ``bf_wpd_*``, ``wpe_online`` and ``wpe_alpha`` are additions, see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     db = get_database(chime6_dir, database_rttm, multiarray)
     return Enhancer(
@@ -190,8 +192,8 @@ def get_enhancer(
         context_samples=context_samples,
         multiarray=multiarray,
         reference_array=None,
-        wpe_block=WPE(taps=wpe_tabs, delay=wpe_delay, iterations=wpe_iterations,
-                      psd_context=wpe_psd_context) if wpe else None,
+        wpe_block=core.wpe_block_from(wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context,
+                                      wpe_online, wpe_alpha),
         activity=Activity(garbage_class=activity_garbage_class, rttm=activity_rttm),
         gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
                       verbose=False),

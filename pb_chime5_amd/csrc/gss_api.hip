@@ -54,7 +54,9 @@ const char *const kVariantKeys[] = {
     // cacgmm.hip
     "em_wgs", "estep_wpb", "estep_lds", "mstep_prefetch_d", "mstep_tiled", "mstep_plan_min_d",
     "mstep_chunked", "mstep_slots", "force_eigh", "em_unfused", "em_l3_mb", "em_l3_fit_mb",
-    "em_streams", "mstep_maxseg", "em4_cold_eigh", "mstep_generic"};
+    "em_streams", "mstep_maxseg", "em4_cold_eigh", "mstep_generic",
+    // wpe_online.hip (read by the entry points below)
+    "wpe_online_mem"};
 struct VariantTable {
     std::mutex lock;
     std::string text;
@@ -622,6 +624,64 @@ extern "C" int gss_wpe_arrays(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T,
     GSS_TRY(wpe_arrays_regroup_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, A, C, true, Yg));
     GSS_TRY(wpe_run(ctx, Yg, F * A, T, C, taps, delay, iterations, psd_context, Xg, -1, F * A));
     return wpe_arrays_regroup_run(ctx, Xg, F, T, A, C, false, reinterpret_cast<cplx *>(X));
+}
+
+// The online WPE argument rule, before any launch; fills n = taps * C.
+static int check_wpe_online(gss_ctx *ctx, const char *what, int F, int A, int C, int taps, int delay,
+                            double alpha) {
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F = %d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, A >= 1, GSS_ERR_INVALID, "%s: A = %d is smaller than 1", what, A);
+    GSS_REQUIRE(ctx, C >= 1, GSS_ERR_INVALID, "%s: C = %d is smaller than 1", what, C);
+    GSS_REQUIRE(ctx, taps >= 1, GSS_ERR_INVALID, "%s: taps = %d is smaller than 1", what, taps);
+    GSS_REQUIRE(ctx, delay >= 0, GSS_ERR_INVALID, "%s: delay = %d is negative", what, delay);
+    GSS_REQUIRE(ctx, delay < (1 << 20), GSS_ERR_INVALID, "%s: delay = %d is not below 2^20", what,
+                delay);
+    GSS_REQUIRE(ctx, std::isfinite(alpha) && alpha > 0.0 && alpha <= 1.0, GSS_ERR_INVALID,
+                "%s: alpha = %g outside (0, 1]", what, alpha);
+    GSS_REQUIRE(ctx, (int64_t)A * C <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
+                "%s: A * C = %lld outside [1, %d]", what, (long long)A * C, GSS_MAX_CHANNELS);
+    GSS_REQUIRE(ctx, (int64_t)taps * C <= 512, GSS_ERR_UNSUPPORTED,
+                "%s: n = taps * C = %lld is larger than 512", what, (long long)taps * C);
+    return GSS_OK;
+}
+
+static int check_wpe_online_state(gss_ctx *ctx, const char *what, const gss_wpe_online_state *s) {
+    GSS_REQUIRE(ctx, s->inv_cov_dev, GSS_ERR_INVALID, "%s: state->inv_cov_dev is NULL", what);
+    GSS_REQUIRE(ctx, s->filter_dev, GSS_ERR_INVALID, "%s: state->filter_dev is NULL", what);
+    GSS_REQUIRE(ctx, s->history_dev, GSS_ERR_INVALID, "%s: state->history_dev is NULL", what);
+    return GSS_OK;
+}
+
+extern "C" int gss_wpe_online_init(gss_ctx *ctx, int F, int A, int C, int taps, int delay,
+                                   const gss_wpe_online_state *state) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, state, GSS_ERR_INVALID, "gss_wpe_online_init: state is NULL");
+    GSS_TRY(check_wpe_online_state(ctx, "gss_wpe_online_init", state));
+    GSS_TRY(check_wpe_online(ctx, "gss_wpe_online_init", F, A, C, taps, delay, 1.0));
+    return wpe_online_init_run(ctx, F, A, C, taps, delay, reinterpret_cast<cplx *>(state->inv_cov_dev),
+                               reinterpret_cast<cplx *>(state->filter_dev),
+                               reinterpret_cast<cplx *>(state->history_dev));
+}
+
+extern "C" int gss_wpe_online(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int A, int C,
+                              int taps, int delay, double alpha, const gss_wpe_online_state *state,
+                              gss_cplx *X) {
+    GSS_ENTER_VARIANTS(ctx);
+    GSS_REQUIRE(ctx, Y, GSS_ERR_INVALID, "gss_wpe_online: Y_dev is NULL");
+    GSS_REQUIRE(ctx, X, GSS_ERR_INVALID, "gss_wpe_online: X_dev is NULL");
+    GSS_REQUIRE(ctx, X != Y, GSS_ERR_INVALID, "gss_wpe_online: X_dev must not alias Y_dev");
+    GSS_REQUIRE(ctx, T >= 0, GSS_ERR_INVALID, "gss_wpe_online: T = %lld is negative", (long long)T);
+    if (state) GSS_TRY(check_wpe_online_state(ctx, "gss_wpe_online", state));
+    GSS_TRY(check_wpe_online(ctx, "gss_wpe_online", F, A, C, taps, delay, alpha));
+    GSS_TRY(check_stft_bins(ctx, F, T, A * C));
+    const bool force_mem = gss_variant_set("wpe_online_mem");
+    if (T == 0) return GSS_OK;
+    GSS_TRY(arena_reserve(ctx, wpe_online_workspace_bytes(F, T, A, C, taps, delay, state == nullptr)));
+    return wpe_online_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, A, C, taps, delay, alpha,
+                          state ? reinterpret_cast<cplx *>(state->inv_cov_dev) : nullptr,
+                          state ? reinterpret_cast<cplx *>(state->filter_dev) : nullptr,
+                          state ? reinterpret_cast<cplx *>(state->history_dev) : nullptr,
+                          reinterpret_cast<cplx *>(X), force_mem);
 }
 
 extern "C" int gss_wpe_inverse_power(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
@@ -1268,6 +1328,7 @@ struct PipelineCall {
     const gss_bf_segments *seg = nullptr;            // the segment-wise beamformer
     const gss_bf_lcmv *lcmv = nullptr;               // the interferer-nulling beamformer
     const gss_bf_wpd *wpd = nullptr;                 // the WPD beamformer
+    const gss_wpe_online_cfg *wpe_online = nullptr;  // the online WPE in the place of the offline one
     PipelineActivity activity;
 };
 
@@ -1296,6 +1357,11 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
         stage = std::max(stage, std::max(lcmv_workspace_bytes(F, T, D),
                                          lcmv_masks_workspace_bytes(F, K)));
     if (wpd) stage = std::max(stage, wpd_workspace_bytes(F, T, D, wpd->taps, wpd->delay));
+    // (online WPE from a fresh state: F A (n^2 + n C + L C) complex values of state -- the joint
+    // 24-channel case, n = 240, is the large one -- and sigma)
+    if (call.wpe_online && p->wpe)
+        stage = std::max(stage, wpe_online_workspace_bytes(F, T, wpe_arrays_of(p), D / wpe_arrays_of(p),
+                                                           p->wpe_taps, p->wpe_delay, true));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
     if (call.activity.scores)
         stage = std::max(stage, pact_workspace_bytes(F, T, K));   // the partial planes
@@ -1410,7 +1476,16 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call
         GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + GSS_STATUS_WPE_ZERO_PIVOTS, 0,
                                           sizeof(int32_t), ctx->stream));
     const int A = wpe_arrays_of(p);
-    if (p->wpe && A == 1) {
+    if (p->wpe && call.wpe_online) {
+        // the online WPE reads the array-major channels where they are: no regrouping; no solve,
+        // so the pivot count an earlier utterance left behind is cleared
+        GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + GSS_STATUS_WPE_ZERO_PIVOTS, 0,
+                                          sizeof(int32_t), ctx->stream));
+        GSS_TRY(wpe_online_run(ctx, Y, F, T, A, D / A, p->wpe_taps, p->wpe_delay,
+                               call.wpe_online->alpha, nullptr, nullptr, nullptr, X,
+                               gss_variant_set("wpe_online_mem")));
+        ctx->arena_off = mark;
+    } else if (p->wpe && A == 1) {
         GSS_TRY(pipeline_wpe(ctx, p, Y, F, T, D, X));
         ctx->arena_off = mark;
     } else if (p->wpe) {
@@ -1700,6 +1775,31 @@ extern "C" int gss_enhance_observation_wpd(gss_ctx *ctx, const gss_params *p, co
     GSS_TRY(check_wpd(ctx, wpd, D, "gss_enhance_observation_wpd"));
     PipelineCall call;
     call.wpd = wpd;
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
+}
+
+extern "C" int gss_enhance_observation_wpe_online(gss_ctx *ctx, const gss_params *p,
+                                                  const double *obs, int D, int64_t N,
+                                                  const uint8_t *act, int K, int64_t N_act,
+                                                  int target, int64_t start_ctx, int64_t end_ctx,
+                                                  const gss_wpe_online_cfg *cfg, double *out,
+                                                  const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *const what = "gss_enhance_observation_wpe_online";
+    GSS_REQUIRE(ctx, cfg, GSS_ERR_INVALID, "%s: cfg is NULL", what);
+    GSS_REQUIRE(ctx, p, GSS_ERR_INVALID, "%s: params is NULL", what);
+    GSS_REQUIRE(ctx, p->wpe, GSS_ERR_INVALID, "%s: wpe = 0, there is no WPE stage to replace", what);
+    GSS_REQUIRE(ctx, p->wpe_psd_context == 0, GSS_ERR_INVALID,
+                "%s: wpe_psd_context = %d, the online WPE has no PSD context", what,
+                p->wpe_psd_context);
+    GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED, "D=%d", D);
+    GSS_TRY(check_wpe_arrays(ctx, p, D));
+    GSS_TRY(check_wpe_online(ctx, what, 1, wpe_arrays_of(p), D / wpe_arrays_of(p), p->wpe_taps,
+                             p->wpe_delay, cfg->alpha));
+    PipelineCall call;
+    call.entry = what;
+    call.wpe_online = cfg;
     return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
                                     out, taps, call);
 }

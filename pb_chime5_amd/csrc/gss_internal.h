@@ -470,6 +470,17 @@ int wpd_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *
             const uint8_t *gate, const gss_bf_wpd &bf, int forced_ref, cplx *Xhat,
             int32_t *ref_channel);
 
+// Online WPE (wpe_online.hip; include/gss_hip.h: gss_wpe_online).  Y (F,T,A C) -> X (F,T,A C), the
+// state (P (F A,n,n), G (F A,n,C), hist (F A,L,C)) advanced in place; P == G == hist == NULL: a
+// fresh state from the arena, thrown away.  force_mem: the memory form at any n (GSS_VARIANT
+// wpe_online_mem, read by the entry points).  Arguments validated by the entry point, T >= 1.
+size_t wpe_online_workspace_bytes(int F, int64_t T, int A, int C, int taps, int delay, bool fresh);
+bool wpe_online_uses_memory_form(int n, bool force_mem);
+int wpe_online_init_run(gss_ctx *ctx, int F, int A, int C, int taps, int delay, cplx *P, cplx *G,
+                        cplx *hist);
+int wpe_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int A, int C, int taps, int delay,
+                   double alpha, cplx *P, cplx *G, cplx *hist, cplx *X, bool force_mem);
+
 int selftest_mfma_run(gss_ctx *ctx);
 
 // Shared device routine: cyclic-Jacobi eigendecomposition of Hermitian matrices

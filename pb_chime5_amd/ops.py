@@ -8,6 +8,9 @@ here                        reference call (file:line)
 =========================  ====================================================
 ``stft`` / ``istft``        nara_wpe.utils.stft / istft   (core.py:305-321)
 ``wpe_v8``                  nara_wpe.wpe.wpe_v8           (core.py:52-58)
+``wpe_online_dtf`` / ``OnlineWPEState`` / ``enhance_observation_wpe_online``
+                            nara_wpe's online (frame-recursive) WPE with a carried state, which
+                            the reference never calls
 ``cacgmm_posteriors``       CACGMMTrainer.fit + predict   (core.py:165-208)
 ``cacgmm_posteriors_guided``  the same from any initialisation / source_activity_mask
 ``cacgmm_posteriors_shared_prior`` / ``cacgmm_posteriors_blind`` / ``blind_initialization``
@@ -37,7 +40,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import (Context, GssBfLcmv, GssBfSegments, GssBfWpd, GssCacgmmModel, GssChannelSelect,
-                    GssDebugTaps, GssGuidance, GssParams, c_void_p, default_context)
+                    GssDebugTaps, GssGuidance, GssParams, GssWpeOnlineCfg, GssWpeOnlineState,
+                    c_void_p, default_context)
 from .cacgmm import CACGMM
 
 _BF_CODES = {'mvdrSouden_ban': 0, 'ch2': 1, 'sum': 2, 'gev_ban': 3}
@@ -256,6 +260,145 @@ def wpe_v8(Y, taps=10, delay=3, iterations=3, psd_context=0, *, ctx=None):
     Yf = Y.reshape((-1, D, T))
     out = wpe_dtf(Yf.transpose(1, 2, 0), taps, delay, iterations, psd_context, ctx=ctx)
     return out.transpose(2, 0, 1).reshape(lead + (D, T))
+
+
+# --------------------------------------------------------------------------
+# online WPE (gss_wpe_online): frame-recursive, exponentially forgetting, with a carried state
+# --------------------------------------------------------------------------
+WPE_ONLINE_ALPHA = 0.9999   # the forgetting factor: a choice, not a measurement
+WPE_ONLINE_MAX_N = 512      # include/gss_hip.h: taps * channels per array
+
+
+def check_wpe_online(taps=10, delay=2, alpha=WPE_ONLINE_ALPHA, num_channels=None, arrays=1):
+    """The settings of the online WPE -- the one place that validates them, before any device
+    work.  ValueError naming the argument: ``taps`` an integer >= 1, ``delay`` an integer >= 0,
+    ``alpha`` a finite number in (0, 1], ``arrays`` as `check_wpe_arrays` (it must divide
+    ``num_channels``), ``num_channels`` a positive integer.  NotImplementedError for what the
+    kernels are not built for: more than 32 channels, taps * channels per array > 512.
+    Returns (A, C) -- C None without ``num_channels``."""
+    for name, value, low in (('taps', taps, 1), ('delay', delay, 0)):
+        if not _is_integer(value) or value < low or value >= 2 ** 20:
+            raise ValueError(f'{name}={value!r}: an integer >= {low} (and below 2^20)')
+    if not _is_real(alpha) or not np.isfinite(alpha) or not 0 < alpha <= 1:
+        raise ValueError(f'alpha={alpha!r}: a finite number in (0, 1]')
+    if num_channels is not None and (not _is_integer(num_channels) or num_channels < 1):
+        raise ValueError(f'num_channels={num_channels!r}: a positive integer')
+    A = check_wpe_arrays(arrays, num_channels)
+    if num_channels is None:
+        return A, None
+    C = int(num_channels) // A
+    if num_channels > _MAX_CHANNELS:
+        raise NotImplementedError(f'num_channels={num_channels}: at most {_MAX_CHANNELS}')
+    if taps * C > WPE_ONLINE_MAX_N:
+        raise NotImplementedError(f'taps={taps} on {C} channels per array: taps * channels = '
+                                  f'{taps * C} is larger than {WPE_ONLINE_MAX_N}')
+    return A, C
+
+
+class OnlineWPEState:
+    """The state of the online WPE in HBM (gss_wpe_online_state), caller-owned like a
+    `DeviceModel`: inv_cov P (F,A,n,n), filter G (F,A,n,C) and history (F,A,taps + delay,C) -- the
+    last frames, oldest first --, complex128, n = taps * C."""
+
+    def __init__(self, ctx, F, A, C, taps, delay):
+        self.ctx = ctx
+        self.F, self.A, self.C, self.taps, self.delay = (int(v) for v in (F, A, C, taps, delay))
+        self.n, self.L = self.taps * self.C, self.taps + self.delay
+        self.shapes = {'inv_cov': (self.F, self.A, self.n, self.n),
+                       'filter': (self.F, self.A, self.n, self.C),
+                       'history': (self.F, self.A, self.L, self.C)}
+        self.bufs = {k: ctx.empty(16 * int(np.prod(v, dtype=np.int64)))
+                     for k, v in self.shapes.items()}
+
+    @property
+    def key(self):
+        return self.F, self.A, self.C, self.taps, self.delay
+
+    def struct(self):
+        return GssWpeOnlineState(inv_cov_dev=self.bufs['inv_cov'].ptr,
+                                 filter_dev=self.bufs['filter'].ptr,
+                                 history_dev=self.bufs['history'].ptr)
+
+    @classmethod
+    def fresh(cls, F, A, C, taps, delay, *, ctx=None):
+        """P = I, G = 0, history = 0 (gss_wpe_online_init)."""
+        if not _is_integer(F) or F < 1:
+            raise ValueError(f'F={F!r}: a positive integer')
+        if not _is_integer(C) or C < 1:
+            raise ValueError(f'C={C!r}: a positive integer')
+        A = check_wpe_arrays(A)
+        check_wpe_online(taps, delay, num_channels=A * C, arrays=A)
+        ctx = ctx or default_context()
+        state = cls(ctx, F, A, C, taps, delay)
+        ctx._check(ctx.lib.gss_wpe_online_init(ctx.handle, state.F, state.A, state.C, state.taps,
+                                               state.delay, ctypes.byref(state.struct())),
+                   'gss_wpe_online_init')
+        return state
+
+    def to_host(self):
+        """{'inv_cov', 'filter', 'history'} as NumPy arrays plus 'taps' and 'delay': everything
+        `from_host` needs (synchronises)."""
+        out = {k: self.ctx.to_host(self.bufs[k], shape, np.complex128)
+               for k, shape in self.shapes.items()}
+        out.update(taps=self.taps, delay=self.delay)
+        return out
+
+    @classmethod
+    def from_host(cls, host, *, ctx=None):
+        """A device state from the dict of `to_host` (in any context: a state saved in one
+        process continues in another).  ValueError for shapes that do not fit each other."""
+        G = np.ascontiguousarray(host['filter'], dtype=np.complex128)
+        if G.ndim != 4:
+            raise ValueError(f'filter: shape {G.shape} is not (F,A,n,C)')
+        F, A, n, C = G.shape
+        taps, delay = int(host['taps']), int(host['delay'])
+        check_wpe_online(taps, delay, num_channels=A * C, arrays=A)
+        ctx = ctx or default_context()
+        state = cls(ctx, F, A, C, taps, delay)
+        for k, shape in state.shapes.items():
+            a = np.ascontiguousarray(host[k], dtype=np.complex128)
+            if a.shape != shape:
+                raise ValueError(f'{k}: shape {a.shape} is not {shape} (taps={taps}, delay={delay})')
+            ctx.upload(state.bufs[k], a)
+        return state
+
+    def copy(self):
+        """An independent state with the same bits, in the same context."""
+        return OnlineWPEState.from_host(self.to_host(), ctx=self.ctx)
+
+
+def wpe_online_dtf(Obs, taps=10, delay=2, alpha=WPE_ONLINE_ALPHA, *, arrays=1, state=None,
+                   ctx=None):
+    """The online WPE on the reference's (D,T,F) layout (gss_wpe_online): every frame is filtered
+    with the filter as it stands BEFORE that frame updates it, and the filter forgets at the rate
+    ``alpha``.  ``arrays`` = A > 1: per array, A groups of D / A consecutive channels.  ``state``:
+    an `OnlineWPEState` to continue from, advanced IN PLACE by the T frames (feeding a recording in
+    blocks through one state gives the bits of one call); None: a fresh state, thrown away.
+    Returns (D,T,F)."""
+    Obs = np.asarray(Obs)
+    if Obs.ndim != 3:
+        raise ValueError(f'Obs: shape {Obs.shape} is not (D,T,F)')
+    D, T, F = Obs.shape
+    A, C = check_wpe_online(taps, delay, alpha, D, arrays)
+    if state is not None:
+        if not isinstance(state, OnlineWPEState):
+            raise ValueError(f'state: {type(state).__name__} is not an OnlineWPEState')
+        if state.key != (F, A, C, int(taps), int(delay)):
+            raise ValueError(f'state: built for (F, A, C, taps, delay) = {state.key}, the call has '
+                             f'{(F, A, C, int(taps), int(delay))}')
+        if ctx is not None and ctx is not state.ctx:
+            raise ValueError('state: it lives in another context than ctx')
+        ctx = state.ctx
+    ctx = ctx or default_context()
+    if T == 0 or F == 0:
+        return np.zeros((D, T, F), np.complex128)
+    Y_d, _ = _obs_to_device_ftd(ctx, Obs)
+    X_d = ctx.empty(16 * F * T * D)
+    ctx._check(ctx.lib.gss_wpe_online(
+        ctx.handle, c_void_p(Y_d.ptr), F, T, A, C, int(taps), int(delay), float(alpha),
+        ctypes.byref(state.struct()) if state is not None else None, c_void_p(X_d.ptr)),
+        'gss_wpe_online')
+    return _ftd_to_host_dtf(ctx, X_d, D, T, F)
 
 
 def cacgmm_posteriors(Obs, activity_freq, iterations=20, iterations_post=1, *, ctx=None):
@@ -1380,6 +1523,7 @@ def params_for(params, num_channels, wpe_arrays=None):
 _FUSED_ENTRIES = {
     None: ('gss_enhance_observation', 'gss_enhance_observation_pcm16', 'plain'),
     'wpd': ('gss_enhance_observation_wpd', None, 'WPD'),
+    'wpe_online': ('gss_enhance_observation_wpe_online', None, 'online WPE'),
     'activity': ('gss_enhance_observation_activity', None, 'activity'),
     'lcmv': ('gss_enhance_observation_lcmv', None, 'LCMV'),
     'channel_select': ('gss_enhance_observation_select', 'gss_enhance_observation_select_pcm16',
@@ -1391,8 +1535,8 @@ _FUSED_ENTRIES = {
 def _enqueue_fused(ctx, params, obs_d, D, N, act_d, K, N_act, target_index, start_context,
                    end_context, out_d, taps=None, pcm=False, option=None, value=None):
     """The one place that issues a fused one-target call on inputs in HBM.  ``option``: a key of
-    `_FUSED_ENTRIES`; ``value``: the struct that entry takes (gss_bf_wpd, gss_bf_lcmv,
-    gss_bf_segments, gss_channel_select), for 'activity' the device buffers (weights or None,
+    `_FUSED_ENTRIES`; ``value``: the struct that entry takes (gss_bf_wpd, gss_wpe_online_cfg,
+    gss_bf_lcmv, gss_bf_segments, gss_channel_select), for 'activity' the device buffers (weights or None,
     scores, power or None).  ``pcm``: int16 samples, the entry's _pcm16 twin."""
     name, twin, label = _FUSED_ENTRIES[option]
     assert twin is not None or not pcm, f'the {label} call has no pcm16 twin'
@@ -1435,8 +1579,10 @@ class ResidentUtterance:
         self.out_d = ctx.empty(8 * max(self.n_out, 1))
 
     def enqueue(self, target_index, start_context, end_context, taps=None, segments=None,
-                channel_select=None, lcmv=None, activity=None, wpd=None):
-        """``wpd``: a gss_bf_wpd (`check_bf_wpd`) for the WPD beamformer on the STFT before WPE
+                channel_select=None, lcmv=None, activity=None, wpd=None, wpe_online=None):
+        """``wpe_online``: a gss_wpe_online_cfg for the online WPE in the place of the offline one
+        (gss_enhance_observation_wpe_online; float64 samples only, on its own).
+        ``wpd``: a gss_bf_wpd (`check_bf_wpd`) for the WPD beamformer on the STFT before WPE
         (gss_enhance_observation_wpd; float64 samples only, on its own).
         ``segments``: a gss_bf_segments (`check_bf_segments`) for the segment-wise
         beamformer (gss_enhance_observation_segments; float64 samples only).
@@ -1447,7 +1593,8 @@ class ResidentUtterance:
         ``activity``: device buffers (weights (F,) or None, scores (K,T), power (T,) or None) for
         the posterior activity of the call's own observation and posteriors
         (gss_enhance_observation_activity; float64 samples only, on its own)."""
-        given = [(name, v) for name, v in (('wpd', wpd), ('activity', activity), ('lcmv', lcmv),
+        given = [(name, v) for name, v in (('wpe_online', wpe_online), ('wpd', wpd),
+                                           ('activity', activity), ('lcmv', lcmv),
                                            ('channel_select', channel_select),
                                            ('segments', segments)) if v is not None]
         option, value = given[0] if given else (None, None)
@@ -1844,6 +1991,36 @@ def enhance_observation_wpd(obs, activity, target_index, start_context_samples,
     if not debug:
         return x_hat
     details['wpd_zero_pivots'] = ctx.last_wpd_zero_pivots()
+    return x_hat, details
+
+
+def enhance_observation_wpe_online(obs, activity, target_index, start_context_samples,
+                                   end_context_samples, *, alpha=WPE_ONLINE_ALPHA, params=None,
+                                   window=None, debug=False, ctx=None, wpe_arrays=None,
+                                   **param_kwargs):
+    """`enhance_observation` with the online WPE of `wpe_online_dtf` from a fresh state
+    (gss_enhance_observation_wpe_online) in the place of the offline one: taps, delay and the
+    arrays are those of ``params``, its ``wpe_iterations`` is not read.  ``debug`` details as
+    there (``Obs`` is the output of the online WPE).  ValueError for bad settings, ``wpe=False``
+    or a PSD context, before any device work."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    obs = np.asarray(obs)
+    if obs.ndim != 2:
+        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    if not params.wpe:
+        raise ValueError('wpe_online with wpe=False: there is no WPE stage to replace')
+    if params.wpe_psd_context != 0:
+        raise ValueError(f'wpe_online with wpe_psd_context={params.wpe_psd_context}: the online '
+                         'WPE has no PSD context')
+    check_wpe_online(params.wpe_taps, params.wpe_delay, alpha, obs.shape[0],
+                     params.wpe_arrays if wpe_arrays is None else wpe_arrays)
+    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
+    utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
+                wpe_online=GssWpeOnlineCfg(alpha=float(alpha)))
+    x_hat, details = _one_target_result(utt, bufs, debug)
+    if not debug:
+        return x_hat
     return x_hat, details
 
 

@@ -38,6 +38,13 @@ def main(argv=None):
     ap.add_argument('--wpe-iterations', type=int, default=3)
     ap.add_argument('--wpe-per-array', action='store_true',
                     help='WPE on each microphone array on its own (get_enhancer(wpe_per_array=True))')
+    ap.add_argument('--wpe-online', action='store_true',
+                    help="nara_wpe's online WPE in the place of the offline one: a frame-recursive "
+                         'filter that forgets, the time-varying front for long windows with '
+                         'movement; --wpe-iterations is not read (get_enhancer(wpe_online=True))')
+    ap.add_argument('--wpe-alpha', type=float, default=0.9999,
+                    help='forgetting factor of --wpe-online, in (0, 1] (a choice, not a '
+                         'measurement)')
     ap.add_argument('--bss-iterations', type=int, default=20)
     ap.add_argument('--bss-iterations-post', type=int, default=1)
     ap.add_argument('--bf', default='mvdrSouden_ban')
@@ -93,7 +100,8 @@ def main(argv=None):
         channel_keep=args.channel_keep, channel_bands=args.channel_bands,
         bf_null_interferer=args.bf_null_interferer, bf_wpd_taps=args.bf_wpd_taps,
         bf_wpd_delay=args.bf_wpd_delay, bf_wpd_iterations=args.bf_wpd_iterations,
-        bf_wpd_power_floor=args.bf_wpd_power_floor)
+        bf_wpd_power_floor=args.bf_wpd_power_floor, wpe_online=args.wpe_online,
+        wpe_alpha=args.wpe_alpha)
     if parallel.is_master():
         Path(args.out).mkdir(parents=True, exist_ok=True)
     parallel.barrier()
