@@ -906,6 +906,29 @@ int gss_enhance_observation_host(gss_ctx *ctx, const gss_params *params,
 /* Bytes of context workspace the last call needed (diagnostics / sizing). */
 size_t gss_workspace_bytes(gss_ctx *ctx);
 
+/* Workspace debug mode, for tests (off for a new context; it synchronises, never use it in a
+ * product run).  pattern 0..255 switches it on, -1 off.  While it is on
+ *  - the context's workspace is filled with the byte `pattern` at the start of every call and
+ *    again whenever a fused call hands the workspace of one stage to the next,
+ *  - every block gss_dev_malloc returns is filled with it,
+ *  - every workspace block is followed by a guard of at least 256 bytes of it, compared with the
+ *    pattern when the block is released, at the start of the next call and by the report below.
+ * A kernel that reads workspace or output memory before writing it sees the pattern (0xFF: NaN as
+ * a double, -1 as an integer) instead of whatever the previous call left there; one that writes
+ * behind its block breaks a guard.  Results, launches and gss_workspace_bytes() of a context with
+ * the mode off are those of a library without it.  Switching (in either direction) clears the
+ * record of violations. */
+int gss_debug_workspace(gss_ctx *ctx, int pattern);
+
+/* Checks the guards that are still live (synchronises) and returns the number of violated guards
+ * since the mode was switched on, and in buf (len bytes, may be NULL) a text naming the first:
+ * block index, tag, offset and size of the block.  guard_dev (may be NULL) receives the device
+ * address of live guard `guard_index` (0 = behind the first block of the last call), NULL when
+ * there is none; the address lies inside the workspace allocation.  GSS_ERR_INVALID when the mode
+ * is off. */
+int gss_debug_workspace_report(gss_ctx *ctx, int64_t *violations, char *buf, int len,
+                               int guard_index, void **guard_dev);
+
 /* Device self-test of the f64 MFMA fragment layout the WPE kernel relies on;
  * returns 0 when the layout matches. */
 int gss_selftest_mfma(gss_ctx *ctx);

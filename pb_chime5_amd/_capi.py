@@ -220,6 +220,9 @@ SIGNATURES = {
     'gss_enhance_observation_activity': _fused(c_void_p, after_out=(c_void_p, c_void_p)),
     'gss_enhance_observation_host': (c_int, _FUSED_HEAD + _FUSED_TARGET + [c_void_p]),
     'gss_workspace_bytes': (c_size_t, [c_void_p]),
+    'gss_debug_workspace': (c_int, [c_void_p, c_int]),
+    'gss_debug_workspace_report': (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.c_char_p,
+                                           c_int, c_int, ctypes.POINTER(c_void_p)]),
     'gss_selftest_mfma': (c_int, [c_void_p]),
 }
 
@@ -502,6 +505,23 @@ class Context:
 
     def workspace_bytes(self):
         return int(self.lib.gss_workspace_bytes(self.handle))
+
+    def debug_workspace(self, pattern=None):
+        """The workspace debug mode (tests only; it synchronises): fill byte 0..255 = on, None = off.
+        While on, workspace and `empty()` blocks start as that byte and every workspace block has
+        a guard behind it (include/gss_hip.h: gss_debug_workspace)."""
+        self._check(self.lib.gss_debug_workspace(self.handle, -1 if pattern is None else int(pattern)),
+                    'gss_debug_workspace')
+
+    def debug_workspace_report(self, guard_index=-1):
+        """(violated guards since the mode was switched on, text naming the first, device address
+        of live guard `guard_index` or None); checks the live guards (synchronises)."""
+        count, addr = c_int64(), c_void_p()
+        buf = ctypes.create_string_buffer(1024)
+        self._check(self.lib.gss_debug_workspace_report(
+            self.handle, ctypes.byref(count), buf, len(buf), int(guard_index), ctypes.byref(addr)),
+            'gss_debug_workspace_report')
+        return int(count.value), buf.value.decode(), addr.value
 
     # -- STFT tables -------------------------------------------------------
     def set_windows(self, size, shift, analysis, synthesis):

@@ -267,6 +267,8 @@ extern "C" int gss_dev_malloc(gss_ctx *ctx, size_t bytes, void **dev_ptr) {
     if (e != hipSuccess)
         return gss_fail(ctx, GSS_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes,
                         hipGetErrorString(e));
+    if (ctx->debug_pattern >= 0)    // workspace debug mode: outputs and states start poisoned too
+        GSS_HIP_CHECK(ctx, hipMemsetAsync(*dev_ptr, ctx->debug_pattern, bytes, ctx->stream));
     return GSS_OK;
 }
 
@@ -347,30 +349,176 @@ extern "C" int gss_memset(gss_ctx *ctx, void *dst, int value, size_t bytes) {
 // ------------------------------------------------------------------ arena
 void arena_reset(gss_ctx *ctx) { ctx->arena_off = 0; }
 
-int arena_reserve(gss_ctx *ctx, size_t bytes) {
-    bytes = align_up(bytes + 4096, 1 << 20);
-    ctx->arena_off = 0;
-    if (bytes <= ctx->arena_size) return GSS_OK;
+// ---- workspace debug mode (gss_debug_workspace): plain host code around the arena, off by default
+namespace {
+constexpr size_t kDebugGuard = 256;             // bytes of pattern behind every block (plus its alignment slack)
+constexpr size_t kDebugHeadroom = 1 << 20;      // room for the guards of 2048 blocks per reserve
+
+// the debug mode owns the streams while it looks at memory: the internal second stream is
+// forked from and joined to ctx->stream by events, which a host-side check does not see
+int debug_sync(gss_ctx *ctx) {
     GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->arena) {
-        GSS_HIP_CHECK(ctx, hipFree(ctx->arena));
-        ctx->arena = nullptr;
-        ctx->arena_size = 0;
-    }
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctx->arena), bytes);
-    if (e != hipSuccess)
-        return gss_fail(ctx, GSS_ERR_NOMEM, "workspace hipMalloc(%zu) failed: %s", bytes,
-                        hipGetErrorString(e));
-    ctx->arena_size = bytes;
+    if (ctx->aux_stream) GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->aux_stream));
+    if (ctx->stream != ctx->own_stream) GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->own_stream));
     return GSS_OK;
 }
 
-void *arena_alloc(gss_ctx *ctx, size_t bytes) {
+// compares one guard with the pattern (the streams are idle); a violated guard counts once
+int debug_check_guard(gss_ctx *ctx, gss_ctx::DebugGuard &g) {
+    if (g.reported) return GSS_OK;
+    unsigned char host[2 * kDebugGuard];
+    GSS_HIP_CHECK(ctx, hipMemcpy(host, ctx->arena + g.guard_off, g.guard_bytes, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < g.guard_bytes; ++i) {
+        if (host[i] == (unsigned char)ctx->debug_pattern) continue;
+        g.reported = true;
+        if (ctx->debug_violations++ == 0) {
+            char text[512];
+            snprintf(text, sizeof(text),
+                     "workspace block %d%s%s (logical offset %zu, %zu bytes): byte %zu behind its "
+                     "end holds 0x%02x, the guard pattern is 0x%02x",
+                     g.block, g.tag ? " " : "", g.tag ? g.tag : "", g.logical_off, g.bytes, i,
+                     (unsigned)host[i], (unsigned)ctx->debug_pattern);
+            ctx->debug_first = text;
+        }
+        break;
+    }
+    return GSS_OK;
+}
+
+int debug_check_live_guards(gss_ctx *ctx) {
+    if (ctx->debug_guards.empty()) return GSS_OK;
+    GSS_TRY(debug_sync(ctx));
+    for (auto &g : ctx->debug_guards) GSS_TRY(debug_check_guard(ctx, g));
+    return GSS_OK;
+}
+}   // namespace
+
+int arena_reserve(gss_ctx *ctx, size_t bytes) {
+    bytes = align_up(bytes + 4096, 1 << 20);
+    const bool debug = ctx->debug_pattern >= 0;
+    if (debug) {
+        // the guards of the previous call are looked at one last time; the blocks of this call
+        // get room for theirs beyond what the sizing formulas ask for
+        GSS_TRY(debug_check_live_guards(ctx));
+        ctx->debug_guards.clear();
+        ctx->debug_blocks = 0;
+        ctx->debug_phys = 0;
+        ctx->debug_logical_size = bytes;
+        bytes += kDebugHeadroom;
+    }
+    ctx->arena_off = 0;
+    if (bytes > ctx->arena_size) {
+        GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->arena) {
+            GSS_HIP_CHECK(ctx, hipFree(ctx->arena));
+            ctx->arena = nullptr;
+            ctx->arena_size = 0;
+        }
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctx->arena), bytes);
+        if (e != hipSuccess)
+            return gss_fail(ctx, GSS_ERR_NOMEM, "workspace hipMalloc(%zu) failed: %s", bytes,
+                            hipGetErrorString(e));
+        ctx->arena_size = bytes;
+    }
+    // (nothing that lived before a reserve survives it: poisoning all of it is always legal)
+    if (debug) {
+        GSS_TRY(debug_sync(ctx));
+        GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->arena, ctx->debug_pattern, ctx->arena_size, ctx->stream));
+    }
+    return GSS_OK;
+}
+
+void *arena_alloc(gss_ctx *ctx, size_t bytes, const char *tag) {
     size_t off = align_up(ctx->arena_off, 256);
+    if (ctx->debug_pattern >= 0) {
+        // the same logical bump (and the same "too small" answer) as the plain arena; the block
+        // itself goes behind the guard of its predecessor
+        // (bounded by what THIS reserve asked for, where the plain arena is bounded by the size
+        // it has grown to: a sizing formula that is too small fails here on a warm context too)
+        if (off + bytes > ctx->debug_logical_size) return nullptr;
+        const size_t phys = align_up(ctx->debug_phys, 256);
+        const size_t guard_end = align_up(phys + bytes, 256) + kDebugGuard;
+        if (guard_end > ctx->arena_size) {
+            // the headroom holds the guards of 2048 live blocks, fifty times what a call has: this
+            // is the mode running out, not the call's formula, and the report says so
+            if (ctx->debug_violations++ == 0) {
+                char text[256];
+                snprintf(text, sizeof(text),
+                         "the guard headroom of the workspace debug mode (%zu bytes) is used up at "
+                         "block %d%s%s: no sizing bug of the call",
+                         kDebugHeadroom, ctx->debug_blocks, tag ? " " : "", tag ? tag : "");
+                ctx->debug_first = text;
+            }
+            return nullptr;
+        }
+        ctx->debug_guards.push_back({ctx->debug_blocks++, off, bytes, phys + bytes,
+                                     guard_end - (phys + bytes), tag, false});
+        ctx->debug_phys = guard_end;
+        ctx->arena_off = off + bytes;
+        if (ctx->arena_off > ctx->arena_peak) ctx->arena_peak = ctx->arena_off;
+        return ctx->arena + phys;
+    }
     if (off + bytes > ctx->arena_size) return nullptr;  // reserve() was too small: bug
     ctx->arena_off = off + bytes;
     if (ctx->arena_off > ctx->arena_peak) ctx->arena_peak = ctx->arena_off;
     return ctx->arena + off;
+}
+
+// arena_release with the debug mode on: the guards of the released blocks are checked, then
+// everything above the mark is poisoned again -- the next stage starts in the pattern, not in
+// its predecessor's numbers.  Synchronises both streams first: the second stream may still own
+// blocks above the mark, whatever the events say to the first.
+int arena_release_debug(gss_ctx *ctx, size_t mark) {
+    GSS_TRY(debug_sync(ctx));
+    // released: the blocks that end above the mark.  (An empty block that sits exactly on the
+    // mark could have been allocated on either side of it; it stays, nothing lives in it.)
+    while (!ctx->debug_guards.empty() &&
+           ctx->debug_guards.back().logical_off + ctx->debug_guards.back().bytes > mark) {
+        GSS_TRY(debug_check_guard(ctx, ctx->debug_guards.back()));
+        ctx->debug_guards.pop_back();
+    }
+    ctx->arena_off = mark;
+    ctx->debug_phys = ctx->debug_guards.empty()
+                          ? 0
+                          : ctx->debug_guards.back().guard_off + ctx->debug_guards.back().guard_bytes;
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->arena + ctx->debug_phys, ctx->debug_pattern,
+                                      ctx->arena_size - ctx->debug_phys, ctx->stream));
+    return GSS_OK;
+}
+
+extern "C" int gss_debug_workspace(gss_ctx *ctx, int pattern) {
+    GSS_ENTER(ctx);
+    GSS_REQUIRE(ctx, pattern >= -1 && pattern <= 255, GSS_ERR_INVALID,
+                "gss_debug_workspace: pattern=%d (a byte, or -1 for off)", pattern);
+    GSS_TRY(debug_sync(ctx));
+    // a switch starts a new record; the arena keeps its size (a plain reserve never shrinks it)
+    ctx->debug_pattern = pattern;
+    ctx->debug_guards.clear();
+    ctx->debug_blocks = 0;
+    ctx->debug_phys = 0;
+    ctx->debug_logical_size = 0;
+    ctx->debug_violations = 0;
+    ctx->debug_first.clear();
+    ctx->arena_off = 0;
+    // (the WPE tile tables are rebuilt, into a poisoned block, by the next WPE call)
+    ctx->wpe_tiles_key[0] = ctx->wpe_tiles_key[1] = ctx->wpe_tiles_key[2] = ctx->wpe_tiles_key[3] = -1;
+    return GSS_OK;
+}
+
+extern "C" int gss_debug_workspace_report(gss_ctx *ctx, int64_t *violations, char *buf, int len,
+                                          int guard_index, void **guard_dev) {
+    GSS_ENTER(ctx);
+    if (guard_dev) *guard_dev = nullptr;
+    if (violations) *violations = 0;
+    if (buf && len > 0) buf[0] = 0;
+    GSS_REQUIRE(ctx, ctx->debug_pattern >= 0, GSS_ERR_INVALID,
+                "gss_debug_workspace_report: the workspace debug mode is off");
+    GSS_TRY(debug_check_live_guards(ctx));
+    if (violations) *violations = ctx->debug_violations;
+    if (buf && len > 0) snprintf(buf, (size_t)len, "%s", ctx->debug_first.c_str());
+    if (guard_dev && guard_index >= 0 && (size_t)guard_index < ctx->debug_guards.size())
+        *guard_dev = ctx->arena + ctx->debug_guards[guard_index].guard_off;
+    return GSS_OK;
 }
 
 extern "C" size_t gss_workspace_bytes(gss_ctx *ctx) { return ctx ? ctx->arena_peak : 0; }
@@ -1434,10 +1582,11 @@ struct PipelineFront {
 
 static int alloc_front(gss_ctx *ctx, const gss_params *p, int F, int64_t T, int64_t T_act, int D,
                        int K, PipelineFront *fr) {
-    fr->Y = arena_alloc_t<cplx>(ctx, (size_t)F * T * D);
-    fr->X = p->wpe ? arena_alloc_t<cplx>(ctx, (size_t)F * T * D) : fr->Y;
-    fr->actf = arena_alloc_t<uint8_t>(ctx, (size_t)K * T_act);
-    fr->gamma = arena_alloc_t<double>(ctx, (size_t)F * K * T);
+    // (the names show up in the guard report of the workspace debug mode)
+    fr->Y = arena_alloc_t<cplx>(ctx, (size_t)F * T * D, "pipeline Y");
+    fr->X = p->wpe ? arena_alloc_t<cplx>(ctx, (size_t)F * T * D, "pipeline X") : fr->Y;
+    fr->actf = arena_alloc_t<uint8_t>(ctx, (size_t)K * T_act, "pipeline frame activity");
+    fr->gamma = arena_alloc_t<double>(ctx, (size_t)F * K * T, "pipeline gamma");
     GSS_REQUIRE(ctx, fr->Y && fr->X && fr->actf && fr->gamma, GSS_ERR_NOMEM, "workspace sizing bug");
     return GSS_OK;
 }
@@ -1459,7 +1608,7 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call
         // every channel is kept: ranked (the status words name them), nothing moves
         GSS_TRY(stft_run(ctx, obs, obs_type, D, N, p->stft_fading, Y));
         GSS_TRY(chsel_select_run(ctx, Y, F, T, D, *call.sel, nullptr, nullptr));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     } else {
         // the STFT of all D_all channels lives above `mark` until the kept D = sel->keep of
         // them are gathered into Y
@@ -1467,7 +1616,7 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call
         GSS_REQUIRE(ctx, Yall, GSS_ERR_NOMEM, "workspace sizing bug");
         GSS_TRY(stft_run(ctx, obs, obs_type, D_all, N, p->stft_fading, Yall));
         GSS_TRY(chsel_select_run(ctx, Yall, F, T, D_all, *call.sel, Y, nullptr));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     }
     if (fr.Yraw)
         GSS_HIP_CHECK(ctx, hipMemcpyAsync(fr.Yraw, Y, sizeof(cplx) * (size_t)F * T * D,
@@ -1484,10 +1633,10 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call
         GSS_TRY(wpe_online_run(ctx, Y, F, T, A, D / A, p->wpe_taps, p->wpe_delay,
                                call.wpe_online->alpha, nullptr, nullptr, nullptr, X,
                                gss_variant_set("wpe_online_mem")));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     } else if (p->wpe && A == 1) {
         GSS_TRY(pipeline_wpe(ctx, p, Y, F, T, D, X));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     } else if (p->wpe) {
         // per-array WPE: Y (F, T, A C) is regrouped into X's buffer as (F A, T, C), WPE writes
         // (F A, T, C) into Y's buffer (Y is not read after this stage), and that is scattered
@@ -1495,12 +1644,12 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call
         GSS_TRY(wpe_arrays_regroup_run(ctx, Y, F, T, A, D / A, true, X));
         GSS_TRY(pipeline_wpe(ctx, p, X, F * A, T, D / A, Y));
         GSS_TRY(wpe_arrays_regroup_run(ctx, Y, F, T, A, D / A, false, X));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     }
     if (!call.guided) GSS_TRY(activity_run(ctx, act, K, N_act, p->stft_fading, fr.actf));
     GSS_TRY(cacgmm_run(ctx, X, F, T, D, call.guided ? guide : em_guide_from_activity(fr.actf, T_act),
                        K, p->bss_iterations, p->bss_iterations_post, fr.gamma));
-    ctx->arena_off = mark;
+    GSS_TRY(arena_release(ctx, mark));
     return GSS_OK;
 }
 
@@ -1585,7 +1734,7 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     if (call.activity.scores) {      // (reads X and gamma, writes the caller's buffers only)
         GSS_TRY(pact_run(ctx, X, fr.gamma, F, K, T, D, call.activity.weights,
                          call.activity.scores, call.activity.power));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     }
 
     int64_t sf = 0, ef = 0;
@@ -1603,20 +1752,20 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
         if (p->bf_drop_context) GSS_TRY(wpd_context_gate_run(ctx, T, sf, ef, gate));
         GSS_TRY(wpd_run(ctx, raw, F, T, D, mx, p->bf_drop_context ? gate : nullptr, *call.wpd,
                         /*forced_ref=*/-1, Xhat, ref));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     } else if (call.lcmv) {   // (bf == 0, checked by the entry point)
         GSS_TRY(lcmv_masks_run(ctx, fr.gamma, F, K, T, target, *call.lcmv, p->bf_drop_context, sf, ef,
                                mx, mi, mnn, nullptr));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
         GSS_TRY(lcmv_run(ctx, X, F, T, D, mx, mi, mnn, /*ban=*/1, /*forced_ref=*/-1,
                          call.lcmv->min_mass, Xhat, ref));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     } else if (call.seg) {   // (bf == 0, checked by the entry point)
         GSS_TRY(mvdr_segments_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, *call.seg, Xhat, ref));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     } else if (p->bf == 0 || p->bf == 3) {
         GSS_TRY(mvdr_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, Xhat, ref, /*gev=*/p->bf == 3));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     } else {
         GSS_TRY(channel_pick_run(ctx, X, F, T, D, p->bf, Xhat));
     }
@@ -1695,7 +1844,7 @@ static int enhance_observation_targets_impl(gss_ctx *ctx, const gss_params *p, c
     if (beamformer) {
         GSS_TRY(mvdr_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, Xhat, ref, /*gev=*/p->bf == 3,
                          /*forced_ref=*/-1, S, /*targets=*/true));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
         if (p->postfilter == 1)
             GSS_TRY(mask_mul_targets_run(ctx, Xhat, (int64_t)F * T, Xhat, mx, F, T, S, 1));
     } else {
@@ -1705,7 +1854,7 @@ static int enhance_observation_targets_impl(gss_ctx *ctx, const gss_params *p, c
         GSS_REQUIRE(ctx, X1, GSS_ERR_NOMEM, "workspace sizing bug");
         GSS_TRY(channel_pick_run(ctx, X, F, T, D, p->bf, X1));
         GSS_TRY(mask_mul_targets_run(ctx, X1, 0, Xhat, mx, F, T, S, p->postfilter == 1));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     }
     GSS_TRY(istft_run(ctx, Xhat, T, fading, out, S));
 

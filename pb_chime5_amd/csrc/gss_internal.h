@@ -154,6 +154,28 @@ struct gss_ctx {
     size_t arena_off = 0;
     size_t arena_peak = 0;
 
+    // Workspace debug mode (gss_debug_workspace; tests only, synchronises).  Off (-1): none of
+    // the fields below is read.  On: arena and gss_dev_malloc blocks are filled with the byte
+    // `debug_pattern` before use, and every arena block is followed by a guard of that byte
+    // which release / reserve / report compare with the pattern.  arena_off and arena_peak stay
+    // the LOGICAL offsets of the plain arena (what gss_workspace_bytes reports and the
+    // *_workspace_bytes formulas bound); the blocks themselves sit at debug_phys, which also
+    // counts the guards, inside the headroom arena_reserve adds for them.
+    struct DebugGuard {
+        int block;                      // index of the block since the last reserve
+        size_t logical_off, bytes;      // the block as the plain arena would place it
+        size_t guard_off, guard_bytes;  // physical: alignment slack + 256 bytes behind the block
+        const char *tag;                // arena_alloc's optional name, a string literal or NULL
+        bool reported;                  // a violated guard counts once
+    };
+    int debug_pattern = -1;
+    size_t debug_phys = 0;
+    size_t debug_logical_size = 0;      // what the last reserve asked for, without the headroom
+    int debug_blocks = 0;
+    std::vector<DebugGuard> debug_guards;
+    int64_t debug_violations = 0;
+    std::string debug_first;            // text naming the first violation
+
     // STFT tables
     int stft_size = 0, stft_shift = 0;
     double *win_analysis = nullptr;   // device, stft_size
@@ -222,12 +244,21 @@ int gss_fail(gss_ctx *ctx, int code, const char *fmt, ...);
 
 // Arena: reserve() makes sure `bytes` are available for the coming top-level call
 // (may synchronise + reallocate); alloc() bumps.  reset() starts a new call.
+// release() rewinds to a mark taken from ctx->arena_off: everything allocated after the mark is
+// given back (the stages of a fused call work in each other's bytes).  Nothing that lived before
+// a reserve() survives it, nothing above a mark survives its release().
 int arena_reserve(gss_ctx *ctx, size_t bytes);
 void arena_reset(gss_ctx *ctx);
-void *arena_alloc(gss_ctx *ctx, size_t bytes);
+void *arena_alloc(gss_ctx *ctx, size_t bytes, const char *tag = nullptr);
+int arena_release_debug(gss_ctx *ctx, size_t mark);
+static inline int arena_release(gss_ctx *ctx, size_t mark) {
+    if (ctx->debug_pattern >= 0) return arena_release_debug(ctx, mark);
+    ctx->arena_off = mark;
+    return GSS_OK;
+}
 template <typename T>
-static inline T *arena_alloc_t(gss_ctx *ctx, size_t count) {
-    return reinterpret_cast<T *>(arena_alloc(ctx, count * sizeof(T)));
+static inline T *arena_alloc_t(gss_ctx *ctx, size_t count, const char *tag = nullptr) {
+    return reinterpret_cast<T *>(arena_alloc(ctx, count * sizeof(T), tag));
 }
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 

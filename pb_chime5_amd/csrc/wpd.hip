@@ -183,10 +183,10 @@ int wpd_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *
                                     nullptr));
         const WpeCallerWeights cw{a, GSS_STATUS_WPD_ZERO_PIVOTS, it > 0};
         GSS_TRY(wpe_run(ctx, Y, F, T, D, bf.taps, bf.delay, 1, 0, Z, -1, 0, &cw));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
         // (the reference channel is chosen anew in every iteration; the last one's stays)
         GSS_TRY(mvdr_run(ctx, Z, F, T, D, mxg, a, bf.ban, Xhat, ref_channel, /*gev=*/0, forced_ref));
-        ctx->arena_off = mark;
+        GSS_TRY(arena_release(ctx, mark));
     }
     return GSS_OK;
 }

@@ -2067,6 +2067,9 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
         GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         if (!ctx->wpe_tiles)
             GSS_HIP_CHECK(ctx, hipMalloc(&ctx->wpe_tiles, sizeof(CorrTile) * (1024 + 4096 + 1 + 64)));
+        if (ctx->debug_pattern >= 0)    // workspace debug mode: tables, counters and pivot word start poisoned
+            GSS_HIP_CHECK(ctx, hipMemset(ctx->wpe_tiles, ctx->debug_pattern,
+                                         sizeof(CorrTile) * (1024 + 4096 + 1 + 64)));
         GSS_HIP_CHECK(ctx, hipMemcpy(ctx->wpe_tiles, tiles.data(), sizeof(CorrTile) * ntiles,
                                      hipMemcpyHostToDevice));
         if (!upd.empty())
