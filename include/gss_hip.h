@@ -90,7 +90,8 @@ typedef enum {
  * gss_enhance_observation_wpd with the gss_bf_wpd descriptor.  So was gss_cacgmm_shared_prior
  * (it takes the gss_guidance descriptor as it is).  So were gss_wpe_online_init, gss_wpe_online and
  * gss_enhance_observation_wpe_online with the gss_wpe_online_state and gss_wpe_online_cfg
- * descriptors. */
+ * descriptors.  So were gss_cacgmm_align, gss_cacgmm_model_permute and gss_last_align_moved with
+ * the gss_align_plan descriptor. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -325,6 +326,58 @@ int gss_cacgmm_fit(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
 int gss_cacgmm_predict(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
                        const gss_cacgmm_model *model, int K, const gss_guidance *guidance,
                        double *gamma_dev, double *loglik_dev);
+
+/* ---- permutation alignment of per-frequency posteriors ---------------------
+ * A per-frequency CACGMM started without an annotation numbers its classes independently in
+ * every bin.  The aligner finds per frequency the permutation of the classes under which the
+ * rows gamma[f, k, :] of all bins look alike (pb_bss users know it as the permutation aligner;
+ * the definition here is this library's own, tests/align_reference.py is its NumPy form).
+ * (Entry points only, looked up by the binding: revision still 7.)
+ *
+ * Features: feat[f, j, :] = gamma[f, j, :] / sqrt(sum_t gamma[f, j, t]^2), all zero for a zero row
+ * (cosine similarity; the mean is not removed).  The mapping starts as the identity.  A plan
+ * entry (iterations, start, end) runs up to `iterations` passes over the frequencies [start, end):
+ *   1. c[k, :] = sum_{f in [start, end)} feat[f, mapping[f, k], :], every row scaled to unit norm
+ *      (a zero row stays zero);
+ *   2. for every f of the range, all from the same c: S[k, j] = <c[k, :], feat[f, j, :]> and
+ *      mapping[f, :] = the permutation p that maximises sum_k S[k, p[k]] over all K!, the
+ *      lexicographically smallest among exact maxima;
+ *   3. a pass that changes no mapping ends the entry.
+ * Frequencies outside the range are untouched.  The library holds no plan policy: the host builds
+ * the plan (pb_chime5_amd.ops.alignment_plan is the customary one).
+ * The exhaustive search limits K to GSS_ALIGN_MAX_CLASSES; K = 1 gives the identity.  Values are
+ * not inspected: with non-finite posteriors the mapping is unspecified but every row is a
+ * permutation, every loop is bounded and every index stays in range. */
+#define GSS_ALIGN_MAX_CLASSES 8
+typedef struct {
+    const int32_t *iterations, *start, *end;   /* HOST arrays of `entries` values, read during the call */
+    int32_t entries;
+} gss_align_plan;
+
+/* gamma_dev (F,K,T) -> mapping_dev (F,K) int32, every row a permutation of 0..K-1;
+ * aligned_dev (F,K,T) or NULL: aligned[f, k, :] = gamma[f, mapping[f, k], :], must not be
+ * gamma_dev; activity_dev (K,T) or NULL: (1/F) sum_f aligned[f, k, t], the quantity
+ * gss_cacgmm_shared_prior calls its prior.  Asynchronous on the context's stream; float64, no
+ * floating-point atomics: the same call gives the same bits.
+ * GSS_ERR_INVALID, before any launch: a NULL gamma_dev, mapping_dev, plan or plan array;
+ * entries < 1; an entry with iterations < 1 or not 0 <= start < end <= F; F, T or K < 1;
+ * aligned_dev == gamma_dev.  GSS_ERR_UNSUPPORTED: K > GSS_ALIGN_MAX_CLASSES. */
+int gss_cacgmm_align(gss_ctx *ctx, const double *gamma_dev, int F, int K, int64_t T,
+                     const gss_align_plan *plan, int32_t *mapping_dev, double *aligned_dev,
+                     double *activity_dev);
+
+/* The model with its classes renumbered: row (f, k) of precision (F,K,D,D), log_det (F,K) and
+ * weight (F,K) of model_out is row (f, mapping[f, k]) of model, so that predict(model_out)[f, k]
+ * = predict(model)[f, mapping[f, k]].  mapping_dev (F,K) int32; an entry outside [0, K) writes
+ * NaN for that class and reads nothing.  Asynchronous; not in place.
+ * GSS_ERR_INVALID: a NULL model, field or mapping_dev, F, K or D < 1, a buffer of model_out that
+ * is one of model's.  GSS_ERR_UNSUPPORTED: K > GSS_MAX_CLASSES or D > GSS_MAX_CHANNELS. */
+int gss_cacgmm_model_permute(gss_ctx *ctx, const gss_cacgmm_model *model, int F, int K, int D,
+                             const int32_t *mapping_dev, const gss_cacgmm_model *model_out);
+
+/* Frequencies whose row of the mapping the last alignment on this context left different from
+ * the identity (synchronises the stream, like gss_last_wpe_zero_pivots); 0 before any. */
+int gss_last_align_moved(gss_ctx *ctx, int64_t *count_host);
 
 /* A0  mask post-processing of enhance_observation (core.py:537-554): zero the
  * context frames, pick the target class, sum the others.

@@ -44,6 +44,12 @@ class GssCacgmmModel(ctypes.Structure):
     _fields_ = [('precision_dev', c_void_p), ('log_det_dev', c_void_p), ('weight_dev', c_void_p)]
 
 
+class GssAlignPlan(ctypes.Structure):
+    """gss_align_plan: host arrays of `entries` int32 values each."""
+    _fields_ = [('iterations', c_void_p), ('start', c_void_p), ('end', c_void_p),
+                ('entries', ctypes.c_int32)]
+
+
 class GssGuidance(ctypes.Structure):
     """gss_guidance: element (f, k, t) of a table at [f * f_stride + k * k_stride + t]."""
     _fields_ = [('init_dev', c_void_p), ('mask_dev', c_void_p),
@@ -156,6 +162,11 @@ SIGNATURES = {
     'gss_cacgmm_predict': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
                                    ctypes.POINTER(GssCacgmmModel), c_int,
                                    ctypes.POINTER(GssGuidance), c_void_p, c_void_p]),
+    'gss_cacgmm_align': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64,
+                                 ctypes.POINTER(GssAlignPlan), c_void_p, c_void_p, c_void_p]),
+    'gss_cacgmm_model_permute': (c_int, [c_void_p, ctypes.POINTER(GssCacgmmModel), c_int, c_int,
+                                         c_int, c_void_p, ctypes.POINTER(GssCacgmmModel)]),
+    'gss_last_align_moved': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_masks_from_posteriors': (
         c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_int64,
                 c_int64, c_void_p, c_void_p]),
@@ -487,6 +498,11 @@ class Context:
         """Pivots the WPE steps of the last WPD call zeroed (synchronises); the WPE stage's own
         count stays in `last_wpe_zero_pivots`."""
         return self._last('gss_last_wpd_zero_pivots', ctypes.c_int64)
+
+    def last_align_moved(self):
+        """Frequencies whose row the last alignment on this context left off the identity
+        (synchronises)."""
+        return self._last('gss_last_align_moved', ctypes.c_int64)
 
     def last_segment_fallbacks(self):
         """(segment, frequency) pairs of the last segment-wise MVDR on this context that fell

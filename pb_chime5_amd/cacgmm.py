@@ -74,6 +74,19 @@ class CACGMM:
         return CACGMM(self.precision * c[..., None, None], self.log_determinant - D * np.log(c),
                       self.weight)
 
+    def permuted(self, mapping):
+        """The model with its classes renumbered per frequency, on the host: class k of frequency
+        f of the result is class ``mapping[f, k]`` of this one, so that its ``predict`` gives
+        this model's posteriors gathered the same way.  ``mapping`` (F,K) integers, every row a
+        permutation of 0..K-1 (`ops.align_posteriors` returns one); ValueError otherwise.
+        `ops.cacgmm_model_permute` is the device version."""
+        from . import ops
+        F, K, _ = self.shape
+        mapping = ops.check_mapping(mapping, F, K)
+        rows = np.arange(F)[:, None]
+        return CACGMM(self.precision[rows, mapping], self.log_determinant[rows, mapping],
+                      self.weight[rows, mapping])
+
     def save(self, path):
         """np.savez of the three arrays (no pickle)."""
         np.savez(path, precision=self.precision, log_determinant=self.log_determinant,

@@ -1202,7 +1202,7 @@ class Enhancer:
         return self._trim_context(x_hat, ex), intervals
 
     def enhance_observation_blind(self, obs, num_speakers, ex=None, *, seed=0, rule=None,
-                                  debug=False):
+                                  debug=False, method='shared_prior'):
         """Separation without an annotation, on the stage operators: stft -> WPE -> the CACGMM
         with a frequency-shared prior from `ops.blind_initialization` with K = num_speakers + 1
         classes (`ops.cacgmm_posteriors_blind`, ``gss_block.iterations`` iterations) -> for every
@@ -1214,9 +1214,14 @@ class Enhancer:
         not speaker names, and which of them is the noise class is not decided here (the class
         with the flattest prior is a usable guess).  Not with ``bf_segment_frames``,
         ``bf_null_interferer``, ``channel_keep``, the WPD beamformers or ``wpe_per_array``
-        (NotImplementedError)."""
+        (NotImplementedError).
+        ``method='aligned'``: the per-frequency CACGMM from the same start followed by the
+        permutation alignment (`ops.align_posteriors` with its default plan) in place of the
+        shared prior; ``prior`` is then the aligned posteriors' mean over f, and
+        ``num_speakers`` is at most 7."""
         what = 'enhance_observation_blind'
         self._no_blind_options(what)
+        ops.check_blind_method(method)
         if (isinstance(num_speakers, bool) or not isinstance(num_speakers, (int, np.integer))
                 or not 1 <= num_speakers <= 18):
             raise ValueError(f'num_speakers: {num_speakers!r} is not an integer in [1, 18]')
@@ -1227,10 +1232,13 @@ class Enhancer:
         K = int(num_speakers) + 1
         iterations = self.gss_block.iterations
         ops.blind_initialization(K, 1, seed)        # (argument errors before any device work)
+        if method == 'aligned' and K > 8:
+            raise ValueError(f'num_speakers: {num_speakers} with method=\'aligned\': the alignment '
+                             'searches all K! permutations of at most 8 classes')
         ctx = self._ctx()
         Obs = self._blocks_wpe(self.stft(obs), debug, 1)
         posterior, prior = ops.cacgmm_posteriors_blind(Obs, K, iterations, seed=seed,
-                                                       return_prior=True, ctx=ctx)
+                                                       return_prior=True, method=method, ctx=ctx)
         _, power = ops.posterior_activity(Obs, posterior, None, return_power=True, ctx=ctx)
         active = pact.decide(prior, power, rule)
         masks = posterior.copy()

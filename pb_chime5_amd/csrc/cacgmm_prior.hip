@@ -360,7 +360,7 @@ int launch_estep_prior(gss_ctx *ctx, const EmPriorArgs &a, int mode) {
 // thread per (k, t) and slice of frequencies, ascending f (consecutive threads read consecutive
 // addresses); the slices are the second grid dimension, so that K T = 4705 columns do not leave
 // the chip empty.  A second short kernel adds the slices in order and divides.  No atomics.
-constexpr int PRIOR_MAX_SLICES = 32;
+// (At most PRIOR_MAX_SLICES slices, gss_internal.h: the aligner's activity shares the kernels.)
 
 __global__ __launch_bounds__(256) void prior_partial_kernel(const double *__restrict__ G, int nf,
                                                             int per_slice, int64_t KT,

@@ -192,6 +192,7 @@ extern "C" int gss_create(int device_id, gss_ctx **out) {
     ctx->status_host[GSS_STATUS_LCMV_INTERFERER] = -1;
     ctx->status_host[GSS_STATUS_LCMV_FALLBACKS] = 0;
     ctx->status_host[GSS_STATUS_WPD_ZERO_PIVOTS] = 0;
+    ctx->status_host[GSS_STATUS_ALIGN_MOVED] = 0;
     *out = ctx;
     return GSS_OK;
 }
@@ -1037,6 +1038,62 @@ extern "C" int gss_cacgmm_predict(gss_ctx *ctx, const gss_cplx *Y, int F, int64_
     return cacgmm_schedule_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, guide, K, s);
 }
 
+// ------------------------------------------------------------------ permutation alignment
+extern "C" int gss_cacgmm_align(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
+                                const gss_align_plan *plan, int32_t *mapping, double *aligned,
+                                double *activity) {
+    GSS_ENTER(ctx);
+    const char *what = "gss_cacgmm_align";
+    GSS_REQUIRE(ctx, gamma, GSS_ERR_INVALID, "%s: gamma_dev is NULL", what);
+    GSS_REQUIRE(ctx, mapping, GSS_ERR_INVALID, "%s: mapping_dev is NULL", what);
+    GSS_REQUIRE(ctx, plan, GSS_ERR_INVALID, "%s: plan is NULL", what);
+    GSS_REQUIRE(ctx, plan->iterations && plan->start && plan->end, GSS_ERR_INVALID,
+                "%s: plan: an array (iterations, start or end) is NULL", what);
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F=%d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, T >= 1, GSS_ERR_INVALID, "%s: T=%lld is smaller than 1", what, (long long)T);
+    GSS_REQUIRE(ctx, K >= 1, GSS_ERR_INVALID, "%s: K=%d is smaller than 1", what, K);
+    GSS_REQUIRE(ctx, K <= GSS_ALIGN_MAX_CLASSES, GSS_ERR_UNSUPPORTED,
+                "%s: K=%d is larger than %d (the search is exhaustive)", what, K,
+                GSS_ALIGN_MAX_CLASSES);
+    GSS_REQUIRE(ctx, plan->entries >= 1, GSS_ERR_INVALID, "%s: plan: entries=%d is smaller than 1",
+                what, (int)plan->entries);
+    for (int e = 0; e < plan->entries; ++e) {
+        GSS_REQUIRE(ctx, plan->iterations[e] >= 1, GSS_ERR_INVALID,
+                    "%s: plan entry %d: iterations=%d is smaller than 1", what, e,
+                    (int)plan->iterations[e]);
+        GSS_REQUIRE(ctx, 0 <= plan->start[e] && plan->start[e] < plan->end[e] && plan->end[e] <= F,
+                    GSS_ERR_INVALID, "%s: plan entry %d: not 0 <= start=%d < end=%d <= F=%d", what,
+                    e, (int)plan->start[e], (int)plan->end[e], F);
+    }
+    GSS_REQUIRE(ctx, aligned != gamma, GSS_ERR_INVALID, "%s: aligned_dev is gamma_dev", what);
+    GSS_TRY(arena_reserve(ctx, cacgmm_align_workspace_bytes(F, K, T, plan, activity && !aligned)));
+    return cacgmm_align_run(ctx, gamma, F, K, T, plan, mapping, aligned, activity);
+}
+
+extern "C" int gss_cacgmm_model_permute(gss_ctx *ctx, const gss_cacgmm_model *model, int F, int K,
+                                        int D, const int32_t *mapping,
+                                        const gss_cacgmm_model *model_out) {
+    GSS_ENTER(ctx);
+    const char *what = "gss_cacgmm_model_permute";
+    GSS_TRY(check_model(ctx, model, "model"));
+    GSS_TRY(check_model(ctx, model_out, "model_out"));
+    GSS_REQUIRE(ctx, mapping, GSS_ERR_INVALID, "%s: mapping_dev is NULL", what);
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F=%d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, K >= 1, GSS_ERR_INVALID, "%s: K=%d is smaller than 1", what, K);
+    GSS_REQUIRE(ctx, D >= 1, GSS_ERR_INVALID, "%s: D=%d is smaller than 1", what, D);
+    GSS_REQUIRE(ctx, K <= GSS_MAX_CLASSES, GSS_ERR_UNSUPPORTED, "%s: K=%d is larger than %d", what,
+                K, GSS_MAX_CLASSES);
+    GSS_REQUIRE(ctx, D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED, "%s: D=%d is larger than %d", what,
+                D, GSS_MAX_CHANNELS);
+    const void *in[3] = {model->precision_dev, model->log_det_dev, model->weight_dev};
+    const void *out[3] = {model_out->precision_dev, model_out->log_det_dev, model_out->weight_dev};
+    for (const void *o : out)
+        for (const void *i : in)
+            GSS_REQUIRE(ctx, o != i, GSS_ERR_INVALID,
+                        "%s: model_out shares a buffer with model (the gather is not in place)", what);
+    return cacgmm_model_permute_run(ctx, em_model(model), F, K, D, mapping, em_model(model_out));
+}
+
 extern "C" int gss_masks_from_posteriors(gss_ctx *ctx, const double *gamma, int F, int K,
                                          int64_t T, int target, int drop, int64_t sf,
                                          int64_t ef, double *mx, double *mn) {
@@ -1104,6 +1161,10 @@ extern "C" int gss_last_ref_channels(gss_ctx *ctx, int32_t *ref_channels, int S)
 
 extern "C" int gss_last_wpe_zero_pivots(gss_ctx *ctx, int64_t *count) {
     return read_status_word(ctx, GSS_STATUS_WPE_ZERO_PIVOTS, count, "gss_last_wpe_zero_pivots");
+}
+
+extern "C" int gss_last_align_moved(gss_ctx *ctx, int64_t *count) {
+    return read_status_word(ctx, GSS_STATUS_ALIGN_MOVED, count, "gss_last_align_moved");
 }
 
 static int check_segments(gss_ctx *ctx, const gss_bf_segments *seg, const char *what) {

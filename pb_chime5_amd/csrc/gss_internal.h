@@ -191,6 +191,7 @@ struct gss_ctx {
     // [5]: frequencies of the last LCMV beamformer that fell back to the MVDR of the merged mask
     // (copied from the device counter by lcmv_run).
     // [6]: pivots zeroed by the WPE steps of the last WPD call (wpe_run with the caller's weights).
+    // [7]: frequencies whose row the last gss_cacgmm_align left off the identity (align_moved_kernel).
     // [GSS_STATUS_TARGETS + s]: target s of the last targets call (mvdr_apply_targets_kernel,
     // which writes target 0's word to [0] as well).
     int32_t *status_host = nullptr;
@@ -216,7 +217,8 @@ struct gss_ctx {
 #define GSS_STATUS_LCMV_INTERFERER 4
 #define GSS_STATUS_LCMV_FALLBACKS 5
 #define GSS_STATUS_WPD_ZERO_PIVOTS 6                             // pivots zeroed by the last WPD call
-#define GSS_STATUS_TARGETS 16                                    // first per-target word
+#define GSS_STATUS_ALIGN_MOVED 7                                 // rows the last alignment left off the identity
+#define GSS_STATUS_TARGETS 16                                   // first per-target word
 #define GSS_STATUS_CHANNELS 40                                   // first selected-channel word
 #define GSS_STATUS_BYTES (4 * (GSS_STATUS_CHANNELS + GSS_MAX_CHANNELS))
 static_assert(GSS_STATUS_TARGETS + GSS_MAX_CLASSES + 1 <= GSS_STATUS_CHANNELS, "status words overlap");
@@ -396,11 +398,25 @@ struct EmPriorArgs {
     int masked;
     double aff_eps;             // clip, 0 = none
 };
+constexpr int PRIOR_MAX_SLICES = 32;    // slices of the column sum: `part` holds this many (K,T) planes
 size_t cacgmm_prior_workspace_bytes(int F, int64_t T, int K);
 int cacgmm_prior_alloc(gss_ctx *ctx, int F, int64_t T, int K, double *prior_out, EmPriorWork *w);
 int cacgmm_prior_estep_run(gss_ctx *ctx, const EmPriorArgs &a, int K, int mode);
 // prior = mean over the first nf frequencies of w.G (nf = 1: a frequency-independent table, copied)
 int cacgmm_prior_update_run(gss_ctx *ctx, const EmPriorWork &w, int nf, int K, int64_t T);
+
+// cacgmm_align.hip: permutation alignment of per-frequency posteriors (include/gss_hip.h:
+// gss_cacgmm_align, gss_cacgmm_model_permute).  The plan has been validated by the entry point
+// and is read during the call; the workspace has its own term (own_aligned: the activity is
+// wanted but the caller takes no aligned table, so one comes from the arena).  The count of
+// moved rows goes to status word GSS_STATUS_ALIGN_MOVED.
+size_t cacgmm_align_workspace_bytes(int F, int K, int64_t T, const gss_align_plan *plan,
+                                    bool own_aligned);
+int cacgmm_align_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
+                     const gss_align_plan *plan, int32_t *mapping, double *aligned,
+                     double *activity);
+int cacgmm_model_permute_run(gss_ctx *ctx, const EmModel &in, int F, int K, int D,
+                             const int32_t *mapping, const EmModel &out);
 
 // S > 1: S targets' weights (S, F, 2, T) -> partials (S, F, nch, 2, NE), one launch
 int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,

@@ -17,6 +17,10 @@ here                        reference call (file:line)
                             the same with one prior per class and frame for all frequencies
                             (pb_bss ``weight_constant_axis=-3``, which the reference never
                             calls): separation without an annotation
+``align_posteriors`` / ``alignment_plan`` / ``cacgmm_model_permute`` / ``cacgmm_fit_blind``
+                            the classes of a per-frequency model aligned across frequencies
+                            (what pb_bss users run after a blind fit; the reference never does):
+                            an annotation-free model object
 ``mvdr_souden_from_masks``  pb_bss beamformer chain       (beamforming_wrapper.py:51-97)
 ``mvdr_souden_segments_from_masks``  the same with statistics per segment of frames
 ``lcmv_souden_from_masks``  beamform_lcmv_souden_from_masks (beamforming_wrapper.py:127-171)
@@ -596,15 +600,228 @@ def blind_initialization(num_classes, num_frames, seed=0):
     return table / np.sum(table, axis=0, keepdims=True)
 
 
+BLIND_METHODS = ('shared_prior', 'aligned')
+
+
+def check_blind_method(method):
+    if method not in BLIND_METHODS:
+        raise ValueError(f'method: {method!r} is not one of {BLIND_METHODS}')
+    return method
+
+
 def cacgmm_posteriors_blind(Obs, num_classes, iterations=20, *, seed=0, return_prior=False,
-                            ctx=None):
-    """Separation without an annotation: `cacgmm_posteriors_shared_prior` from
-    `blind_initialization`, no mask, ``iterations_post=1``.  Obs (D,T,F) -> posterior (K,T,F)
-    (and the prior (K,T)).  Classes carry indices, not names."""
+                            method='shared_prior', plan=None, ctx=None):
+    """Separation without an annotation.  Obs (D,T,F) -> posterior (K,T,F) (and a (K,T) per-frame
+    activity of every class).  Classes carry indices, not names.
+    ``method='shared_prior'``: `cacgmm_posteriors_shared_prior` from `blind_initialization`, no
+    mask, ``iterations_post=1``; ``return_prior`` gives the prior.
+    ``method='aligned'``: the per-frequency model (`cacgmm_posteriors_guided`) from the same
+    start, then `align_posteriors` with ``plan`` (None: `alignment_plan`); ``return_prior`` gives
+    the aligned posteriors' mean over f.  At most 8 classes."""
     Obs = _check_em_obs(Obs)
+    check_blind_method(method)
     init = blind_initialization(num_classes, Obs.shape[1], seed)
-    return cacgmm_posteriors_shared_prior(Obs, init, None, iterations, 1,
-                                          return_prior=return_prior, ctx=ctx)
+    if method == 'shared_prior':
+        if plan is not None:
+            raise ValueError("plan: only method='aligned' takes an alignment plan")
+        return cacgmm_posteriors_shared_prior(Obs, init, None, iterations, 1,
+                                              return_prior=return_prior, ctx=ctx)
+    _check_em_iterations(iterations, 1)
+    _check_align_classes(num_classes)
+    plan = check_alignment_plan(alignment_plan(Obs.shape[2]) if plan is None else plan,
+                                Obs.shape[2])
+    ctx = ctx or default_context()
+    posterior = cacgmm_posteriors_guided(Obs, init, None, iterations, 1, ctx=ctx)
+    return align_posteriors(posterior, plan, return_activity=return_prior, ctx=ctx)
+
+
+# --------------------------------------------------------------------------
+# permutation alignment (include/gss_hip.h: gss_cacgmm_align; not in the reference)
+# --------------------------------------------------------------------------
+_ALIGN_MAX_CLASSES = 8                      # include/gss_hip.h: GSS_ALIGN_MAX_CLASSES
+
+
+def _check_align_classes(K):
+    if not 1 <= K <= _ALIGN_MAX_CLASSES:
+        raise ValueError(f'{K} classes outside [1, {_ALIGN_MAX_CLASSES}]: the alignment searches '
+                         'all K! permutations')
+
+
+def alignment_plan(num_frequencies, *, segment_start=None, segment_width=None, segment_shift=None,
+                   main_iterations=20, sub_iterations=2):
+    """The customary plan of `align_posteriors`: ``main_iterations`` passes over a band of
+    ``segment_width`` frequencies from ``segment_start``, then ``sub_iterations`` passes over the
+    band widened by ``segment_shift`` on either side, again and again until it is [0, F).  The
+    defaults scale the usual setting of a 512-point STFT (70, 100, 20 of 257 bins) to F; they
+    are choices, not measurements.  Returns [(iterations, start, end), ...]."""
+    values = dict(num_frequencies=num_frequencies, main_iterations=main_iterations,
+                  sub_iterations=sub_iterations)
+    for name, value in (('segment_start', segment_start), ('segment_width', segment_width),
+                        ('segment_shift', segment_shift)):
+        if value is not None:
+            values[name] = value
+    for name, value in values.items():
+        if not _is_integer(value):
+            raise ValueError(f'{name}: {value!r} is not an integer')
+    F = int(num_frequencies)
+    if F < 1:
+        raise ValueError(f'num_frequencies: {F} < 1')
+    for name in ('main_iterations', 'sub_iterations'):
+        if values[name] < 1:
+            raise ValueError(f'{name}: {values[name]} < 1')
+    segment_start = F * 70 // 257 if segment_start is None else int(segment_start)
+    segment_width = F * 100 // 257 if segment_width is None else int(segment_width)
+    segment_shift = max(F * 20 // 257, 1) if segment_shift is None else int(segment_shift)
+    if segment_start < 0:
+        raise ValueError(f'segment_start: {segment_start} is negative')
+    if segment_width < 0:
+        raise ValueError(f'segment_width: {segment_width} is negative')
+    if segment_shift < 1:
+        raise ValueError(f'segment_shift: {segment_shift} < 1')
+    start = max(min(segment_start, F - 1), 0)
+    end = min(start + max(segment_width, 1), F)
+    plan = [(int(main_iterations), start, end)]
+    while (start, end) != (0, F):
+        start = max(start - segment_shift, 0)
+        end = min(end + segment_shift, F)
+        plan.append((int(sub_iterations), start, end))
+    return plan
+
+
+def check_alignment_plan(plan, num_frequencies):
+    """The one place a plan is validated: a non-empty sequence of (iterations, start, end)
+    integers with iterations >= 1 and 0 <= start < end <= F.  Returns it as a list of int
+    tuples; ValueError otherwise."""
+    if isinstance(plan, (str, bytes)) or not hasattr(plan, '__iter__'):
+        raise ValueError(f'plan: {plan!r} is not a sequence of (iterations, start, end)')
+    plan = list(plan)
+    if not plan:
+        raise ValueError('plan: no entries')
+    out = []
+    for index, entry in enumerate(plan):
+        try:
+            entry = tuple(entry)
+        except TypeError:
+            entry = None
+        if entry is None or len(entry) != 3 or not all(_is_integer(v) for v in entry):
+            raise ValueError(f'plan entry {index}: {plan[index]!r} is not (iterations, start, end) '
+                             'of three integers')
+        iterations, start, end = (int(v) for v in entry)
+        if not 1 <= iterations <= 2 ** 31 - 1:
+            raise ValueError(f'plan entry {index}: iterations = {iterations} < 1 (or not an int32)')
+        if not 0 <= start < end <= num_frequencies:
+            raise ValueError(f'plan entry {index}: not 0 <= start = {start} < end = {end} <= '
+                             f'F = {num_frequencies}')
+        out.append((iterations, start, end))
+    return out
+
+
+def check_mapping(mapping, num_frequencies, num_classes):
+    """mapping (F,K) integers, every row a permutation of 0..K-1 -> int32 array; ValueError."""
+    m = np.asarray(mapping)
+    if m.shape != (num_frequencies, num_classes):
+        raise ValueError(f'mapping: shape {m.shape} is not (F,K) = '
+                         f'{(num_frequencies, num_classes)}')
+    if m.dtype.kind not in 'iu':
+        raise ValueError(f'mapping: dtype {m.dtype} is not an integer type')
+    if not np.array_equal(np.sort(m, axis=1),
+                          np.broadcast_to(np.arange(num_classes), m.shape)):
+        bad = int(np.argmax(np.any(np.sort(m, axis=1) != np.arange(num_classes), axis=1)))
+        raise ValueError(f'mapping: row {bad} = {m[bad].tolist()} is not a permutation of '
+                         f'0..{num_classes - 1}')
+    return np.ascontiguousarray(m, dtype=np.int32)
+
+
+class DeviceAlignPlan:
+    """A validated plan as the host arrays of a gss_align_plan (read during the call)."""
+
+    def __init__(self, plan):
+        self.arrays = [np.ascontiguousarray([entry[i] for entry in plan], dtype=np.int32)
+                       for i in range(3)]
+        self.struct = _capi.GssAlignPlan(*(a.ctypes.data for a in self.arrays), len(plan))
+
+
+def _check_posterior_ktf(posterior):
+    posterior = np.asarray(posterior)
+    if posterior.ndim != 3:
+        raise ValueError(f'posterior: shape {posterior.shape} is not (K,T,F)')
+    if posterior.dtype.kind not in 'fiu':
+        raise ValueError(f'posterior: dtype {posterior.dtype} is not real')
+    K, T, F = posterior.shape
+    if T < 1 or F < 1:
+        raise ValueError(f'posterior: shape {posterior.shape} has no frames or no frequencies')
+    _check_align_classes(K)
+    return posterior
+
+
+def align_posteriors(posterior, plan=None, *, return_mapping=False, return_activity=False,
+                     ctx=None):
+    """Align the classes of per-frequency posteriors across frequencies (`gss_cacgmm_align`):
+    posterior (K,T,F), plan as `alignment_plan` returns it (None: its defaults for F) -> the
+    aligned posterior (K,T,F), ``aligned[k, :, f] = posterior[mapping[f, k], :, f]``; with
+    ``return_mapping`` also the mapping (F,K) int32, every row a permutation; with
+    ``return_activity`` also the aligned posteriors' mean over f, (K,T) -- what the shared
+    prior calls its prior.  Every argument error is a ValueError before any device work."""
+    posterior = _check_posterior_ktf(posterior)
+    K, T, F = posterior.shape
+    plan = check_alignment_plan(alignment_plan(F) if plan is None else plan, F)
+    ctx = ctx or default_context()
+    dplan = DeviceAlignPlan(plan)
+    g_d = ctx.to_device(np.ascontiguousarray(posterior.transpose(2, 0, 1), dtype=np.float64))
+    m_d = ctx.empty(4 * F * K)
+    a_d = ctx.empty(8 * F * K * T)
+    o_d = ctx.empty(8 * F * K * T)
+    act_d = ctx.empty(8 * K * T) if return_activity else None
+    ctx._check(ctx.lib.gss_cacgmm_align(
+        ctx.handle, c_void_p(g_d.ptr), F, K, T, ctypes.byref(dplan.struct), c_void_p(m_d.ptr),
+        c_void_p(a_d.ptr), c_void_p(act_d.ptr if act_d else None)), 'gss_cacgmm_align')
+    # (F, K*T) -> (K*T, F)
+    ctx._check(ctx.lib.gss_layout_permute_f64(ctx.handle, c_void_p(a_d.ptr), F, K * T, 1, 2,
+                                              c_void_p(o_d.ptr)), 'gss_layout_permute_f64')
+    out = [ctx.to_host(o_d, (K, T, F), np.float64)]
+    if return_mapping:
+        out.append(ctx.to_host(m_d, (F, K), np.int32))
+    if return_activity:
+        out.append(ctx.to_host(act_d, (K, T), np.float64))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def cacgmm_model_permute(model, mapping, *, ctx=None):
+    """`cacgmm.CACGMM.permuted` on the device (`gss_cacgmm_model_permute`): class k of frequency
+    f of the result is class ``mapping[f, k]`` of ``model``."""
+    if not isinstance(model, CACGMM):
+        raise ValueError(f'model: a CACGMM, not {type(model).__name__}')
+    F, K, D = model.shape
+    mapping = check_mapping(mapping, F, K)
+    ctx = ctx or default_context()
+    src = DeviceModel(ctx, F, K, D, model)
+    dst = DeviceModel(ctx, F, K, D)
+    m_d = ctx.to_device(mapping)
+    ctx._check(ctx.lib.gss_cacgmm_model_permute(
+        ctx.handle, ctypes.byref(src.struct), F, K, D, c_void_p(m_d.ptr),
+        ctypes.byref(dst.struct)), 'gss_cacgmm_model_permute')
+    return dst.to_host(ctx)
+
+
+def cacgmm_fit_blind(Obs, num_classes, iterations=20, *, seed=0, plan=None,
+                     return_posterior=False, ctx=None):
+    """The annotation-free model object: `cacgmm_fit` from `blind_initialization` with no mask,
+    `cacgmm_predict` on the fitted frames, `align_posteriors` and `cacgmm_model_permute` -> a
+    `cacgmm.CACGMM` whose class k is the same source in every frequency; its ``predict`` on the
+    fitted frames gives the aligned posteriors (``return_posterior``: returned as well, (K,T,F)).
+    At most 8 classes."""
+    Obs = _check_em_obs(Obs)
+    _check_em_iterations(iterations, 1)
+    init = blind_initialization(num_classes, Obs.shape[1], seed)
+    _check_align_classes(num_classes)
+    F = Obs.shape[2]
+    plan = check_alignment_plan(alignment_plan(F) if plan is None else plan, F)
+    ctx = ctx or default_context()
+    model = cacgmm_fit(Obs, init, None, int(iterations), ctx=ctx)
+    posterior = cacgmm_predict(model, Obs, ctx=ctx)
+    aligned, mapping = align_posteriors(posterior, plan, return_mapping=True, ctx=ctx)
+    model = cacgmm_model_permute(model, mapping, ctx=ctx)
+    return (model, aligned) if return_posterior else model
 
 
 class DeviceModel:
