@@ -379,6 +379,37 @@ int gss_cacgmm_model_permute(gss_ctx *ctx, const gss_cacgmm_model *model, int F,
  * the identity (synchronises the stream, like gss_last_wpe_zero_pivots); 0 before any. */
 int gss_last_align_moved(gss_ctx *ctx, int64_t *count_host);
 
+/* ---- cross-window class linking ---------------------------------------------
+ * Two overlapping windows of a recording, separated independently, number their classes
+ * independently.  On the L frames they share, the link finds the permutation of the current
+ * window's classes under which its posteriors agree with the previous window's
+ * (tests/link_reference.py is the NumPy form).  prev_dev (F,K,T_prev) and cur_dev (F,K,T_cur) are
+ * posteriors in the device layout; frame prev_begin + t of prev is compared with frame
+ * cur_begin + t of cur, t in [0, L):
+ *   num[a, b] = sum_f sum_t prev[f, a, t] cur[f, b, t]
+ *   S[a, b]   = num[a, b] / sqrt(sum_f sum_t prev[f, a, t]^2 * sum_f sum_t cur[f, b, t]^2),
+ *               0 where a norm is zero
+ *   mapping   = the permutation p that maximises sum_a S[a, p[a]] over all K!, the
+ *               lexicographically smallest among exact maxima
+ * so that linked[a] = cur[mapping[a]] (the aligner's convention).  mapping_dev (K,) int32,
+ * scores_dev (K,K) = S.  Asynchronous on the context's stream; float64, no floating-point atomics:
+ * the same call gives the same bits.  Values are not inspected (non-finite posteriors: some
+ * permutation).  (Entry points only, looked up by the binding: revision still 7.)
+ * GSS_ERR_INVALID, before any launch: a NULL pointer; F, K or L < 1; a negative begin or a frame
+ * range that ends behind its table.  GSS_ERR_UNSUPPORTED: K > GSS_ALIGN_MAX_CLASSES. */
+int gss_cacgmm_link(gss_ctx *ctx, const double *prev_dev, int64_t T_prev, int64_t prev_begin,
+                    const double *cur_dev, int64_t T_cur, int64_t cur_begin, int64_t L,
+                    int F, int K, int32_t *mapping_dev, double *scores_dev);
+
+/* A table with its classes renumbered by ONE mapping for all frequencies (what a link returns):
+ * out[f, a, :] = gamma[f, mapping[a], :].  gamma_dev, out_dev (F,K,T), mapping_dev (K,) int32 on
+ * the device (no host round trip after gss_cacgmm_link); an entry outside [0, K) writes NaN for
+ * that class and reads nothing.  Asynchronous; not in place.
+ * GSS_ERR_INVALID: a NULL pointer, F, K or T < 1, out_dev == gamma_dev.
+ * GSS_ERR_UNSUPPORTED: K > GSS_MAX_CLASSES. */
+int gss_cacgmm_link_gather(gss_ctx *ctx, const double *gamma_dev, int F, int K, int64_t T,
+                           const int32_t *mapping_dev, double *out_dev);
+
 /* A0  mask post-processing of enhance_observation (core.py:537-554): zero the
  * context frames, pick the target class, sum the others.
  * gamma (F,K,T) -> target (F,T), distortion (F,T).  drop_context = 0 skips the
@@ -946,6 +977,25 @@ int gss_enhance_observation_targets_pcm16(gss_ctx *ctx, const gss_params *params
                                           const int64_t *start_context_samples,
                                           const int64_t *end_context_samples, double *out_dev,
                                           const gss_debug_taps *taps);
+
+/* Annotation-free separation of one window in one call: STFT, the joint offline WPE of
+ * `params`, the CACGMM with a frequency-shared prior from init_dev (K,T) -- no mask,
+ * params->bss_iterations iterations and one post iteration, what gss_cacgmm_shared_prior runs
+ * for (iterations, 1) --, the frame power of gss_posterior_activity, then the target-dependent
+ * tail of gss_enhance_observation_targets with S = K (target s = class s, no context frames,
+ * the beamformer of `params`) and K iSTFTs.  obs_dev (D,N) float64; out_dev
+ * (K, gss_istft_num_samples(T, ...)); prior_dev (K,T) the prior of the last M-step; power_dev (T,)
+ * or NULL; gamma_dev (F,K,T) or NULL the posteriors.  taps as in the targets call (act_frames
+ * must be NULL: there is no frame activity).  The name does not begin with
+ * gss_enhance_observation: the call has no activity, no target index and K outputs.
+ * GSS_ERR_INVALID: a NULL params, obs_dev, init_dev, out_dev or prior_dev, N < 1, and what the
+ * stages reject.  GSS_ERR_UNSUPPORTED: params->wpe_arrays > 1 with WPE on (the per-array WPE).
+ * The online WPE, the channel selection, the segment-wise, LCMV and WPD beamformers are options
+ * of entries of their own and have no form here. */
+int gss_separate_observation(gss_ctx *ctx, const gss_params *params, const double *obs_dev,
+                             int D, int64_t N, const double *init_dev, int K, double *out_dev,
+                             double *prior_dev, double *power_dev, double *gamma_dev,
+                             const gss_debug_taps *taps);
 
 /* Same, with host buffers: copies in, runs, copies out, synchronises. */
 int gss_enhance_observation_host(gss_ctx *ctx, const gss_params *params,

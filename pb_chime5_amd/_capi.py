@@ -167,6 +167,10 @@ SIGNATURES = {
     'gss_cacgmm_model_permute': (c_int, [c_void_p, ctypes.POINTER(GssCacgmmModel), c_int, c_int,
                                          c_int, c_void_p, ctypes.POINTER(GssCacgmmModel)]),
     'gss_last_align_moved': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'gss_cacgmm_link': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                c_int64, c_int, c_int, c_void_p, c_void_p]),
+    'gss_cacgmm_link_gather': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p,
+                                       c_void_p]),
     'gss_masks_from_posteriors': (
         c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_int64,
                 c_int64, c_void_p, c_void_p]),
@@ -229,6 +233,9 @@ SIGNATURES = {
     'gss_posterior_activity': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int,
                                        c_void_p, c_void_p, c_void_p]),
     'gss_enhance_observation_activity': _fused(c_void_p, after_out=(c_void_p, c_void_p)),
+    # (ctx, params, obs_dev, D, N, init_dev, K, out_dev, prior_dev, power_dev, gamma_dev, taps)
+    'gss_separate_observation': (c_int, _FUSED_HEAD[:5] + [c_void_p, c_int, c_void_p, c_void_p,
+                                                           c_void_p, c_void_p, _TAPS]),
     'gss_enhance_observation_host': (c_int, _FUSED_HEAD + _FUSED_TARGET + [c_void_p]),
     'gss_workspace_bytes': (c_size_t, [c_void_p]),
     'gss_debug_workspace': (c_int, [c_void_p, c_int]),

@@ -208,6 +208,20 @@ class BlindSeparation:
 
 
 @dataclass
+class BlindRecording:
+    """What `Enhancer.enhance_recording_blind` returns.  Classes carry indices, not names; one
+    index is one source through the whole recording as far as the links hold."""
+    x_hat: np.ndarray          # (K, N) the windows' enhanced signals, linked and cross-faded
+    prior: np.ndarray          # (K, T) the windows' priors, linked and cross-faded over frames
+    active: np.ndarray         # (K, T) bool: `posterior_activity.decide(prior, power, rule)`
+    intervals: list            # per class [(start, end), ...] in samples
+    windows: list              # [(start, end), ...] in samples
+    mappings: np.ndarray       # (n, K) int: class k of the recording is class mappings[w, k] of
+    #                            window w's own numbering; row 0 is the identity
+    link_scores: np.ndarray    # (n, K): S[k, mappings[w, k]] of window w's link; NaN in row 0
+
+
+@dataclass
 class GSS:
     """core.py:144-214 -> CACGMMTrainer.fit / predict for every frequency."""
     iterations: int
@@ -1202,7 +1216,7 @@ class Enhancer:
         return self._trim_context(x_hat, ex), intervals
 
     def enhance_observation_blind(self, obs, num_speakers, ex=None, *, seed=0, rule=None,
-                                  debug=False, method='shared_prior'):
+                                  debug=False, method='shared_prior', fused=False):
         """Separation without an annotation, on the stage operators: stft -> WPE -> the CACGMM
         with a frequency-shared prior from `ops.blind_initialization` with K = num_speakers + 1
         classes (`ops.cacgmm_posteriors_blind`, ``gss_block.iterations`` iterations) -> for every
@@ -1218,10 +1232,27 @@ class Enhancer:
         ``method='aligned'``: the per-frequency CACGMM from the same start followed by the
         permutation alignment (`ops.align_posteriors` with its default plan) in place of the
         shared prior; ``prior`` is then the aligned posteriors' mean over f, and
-        ``num_speakers`` is at most 7."""
+        ``num_speakers`` is at most 7.
+        ``fused=True``: the whole window in one library call (`ops.separate_observation`,
+        gss_separate_observation) instead of the stage operators -- no host round trip between
+        the stages, the beamformer and the iSTFT once for all classes.  Only with
+        ``method='shared_prior'`` and the offline WPE (NotImplementedError otherwise), and it
+        has no context frames: with ``ex`` and ``bf_drop_context`` it raises
+        NotImplementedError.  The default keeps the stage path and its bits."""
         what = 'enhance_observation_blind'
         self._no_blind_options(what)
         ops.check_blind_method(method)
+        if fused:
+            if method != 'shared_prior':
+                raise NotImplementedError(f"{what}(fused=True) with method={method!r}: the fused "
+                                          "call runs the shared prior only")
+            self._no_wpe_online(f'{what}(fused=True)')
+            if not self._fusable():
+                raise NotImplementedError(f'{what}(fused=True) with custom blocks')
+            if self.bf_drop_context and ex is not None and 'start_orig' in ex:
+                raise NotImplementedError(
+                    f'{what}(fused=True) with ex and bf_drop_context: the fused call has no '
+                    'context frames (fused=False drops them)')
         if (isinstance(num_speakers, bool) or not isinstance(num_speakers, (int, np.integer))
                 or not 1 <= num_speakers <= 18):
             raise ValueError(f'num_speakers: {num_speakers!r} is not an integer in [1, 18]')
@@ -1236,6 +1267,8 @@ class Enhancer:
             raise ValueError(f'num_speakers: {num_speakers} with method=\'aligned\': the alignment '
                              'searches all K! permutations of at most 8 classes')
         ctx = self._ctx()
+        if fused:
+            return self._separate_fused(obs, K, seed, rule, debug, ctx)
         Obs = self._blocks_wpe(self.stft(obs), debug, 1)
         posterior, prior = ops.cacgmm_posteriors_blind(Obs, K, iterations, seed=seed,
                                                        return_prior=True, method=method, ctx=ctx)
@@ -1259,6 +1292,128 @@ class Enhancer:
         if debug:
             self.enhance_observation_locals = locals()
         return BlindSeparation(x_hat, prior, active, intervals)
+
+    def _blind_params(self):
+        """`_params` of the annotation-free calls: one post iteration, whatever the GSS block
+        says (what `ops.cacgmm_posteriors_blind` runs)."""
+        params = self._params()
+        params.bss_iterations_post = 1
+        return params
+
+    def _separate_fused(self, obs, K, seed, rule, debug, ctx):
+        """`enhance_observation_blind(fused=True)` after its checks."""
+        params = self._blind_params()
+        T = ops.stft_frames(obs.shape[-1], self.stft_size, self.stft_shift, self.stft_fading)
+        init = ops.blind_initialization(K, T, seed)
+        ctx.set_utterances_in_flight(1)
+        try:
+            res = ops.separate_observation(obs, init, params=params, debug=debug, ctx=ctx)
+        finally:
+            ctx.set_utterances_in_flight(0)
+        x_hat, prior, power = res[:3]
+        active = pact.decide(prior, power, rule)
+        num_samples = obs.shape[-1]
+        intervals = [pact.frames_to_intervals(active[k], self.stft_size, self.stft_shift,
+                                              self.stft_fading, num_samples) for k in range(K)]
+        if debug:
+            details = res[3]
+            self.enhance_observation_locals = locals()
+        return BlindSeparation(x_hat, prior, active, intervals)
+
+    def enhance_recording_blind(self, obs, num_speakers, *, window_samples, hop_samples, seed=0,
+                                start='carry', rule=None):
+        """Annotation-free separation of a whole recording in linked windows: obs (D,N) ->
+        `BlindRecording`.  The recording is cut into windows of ``window_samples`` every
+        ``hop_samples`` (both multiples of ``stft_shift``, ``hop < window <= 2 hop``; the last
+        window runs to N; `recording.window_plan`).  Every window is one fused call
+        (`enhance_observation_blind(fused=True)`, K = num_speakers + 1 <= 8 classes) whose
+        posteriors stay in HBM; for every window but the first one link call
+        (`ops.link_posteriors`, gss_cacgmm_link) compares them with the previous window's -- in
+        that window's linked numbering -- on the frames the two share, ``stft_size / stft_shift
+        - 1`` frames left out on either side (a window's zero padding stands there where its
+        neighbour has samples), and the window's signals, prior and posteriors take the mapping.
+        ``start='fresh'``: window w starts from ``ops.blind_initialization(K, T_w, seed + w)``;
+        ``'carry'``: the first columns of that table are the previous window's linked prior on
+        the shared frames (`recording.start_table`), which mostly keeps the numbering by itself.
+        The windows are cross-faded on the host (`recording.stitch`: the later window's weight
+        rises as ``(i + 0.5) / overlap``), the prior and the frame power the same way over
+        frames, and `posterior_activity.decide` (``rule``) and `frames_to_intervals` follow as
+        in the window call.
+
+        ``mappings[w, k]`` is the class of window w's own numbering that class k of the
+        recording is, ``link_scores[w, k]`` the cosine similarity that link found for it.  A
+        class that is silent in an overlap cannot be linked there: its score is near 0 and its
+        place in the mapping is whatever the other classes leave -- read the scores before
+        trusting a class across such a window.  Nothing here decides which class is the noise or
+        names a speaker.  Options as `enhance_observation_blind(fused=True)`; every argument
+        error is a ValueError before any device work."""
+        from pb_chime5_amd import recording
+        what = 'enhance_recording_blind'
+        self._no_blind_options(what)
+        self._no_wpe_online(what)
+        if not self._fusable():
+            raise NotImplementedError(f'{what} with custom blocks')
+        obs = np.asarray(obs)
+        if obs.ndim != 2:
+            raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+        D, N = obs.shape
+        plan = recording.check_recording(N, num_speakers, window_samples, hop_samples,
+                                         self.stft_size, self.stft_shift, start, seed,
+                                         self.stft_fading)
+        rule = pact.ActivityRule() if rule is None else rule
+        K = int(num_speakers) + 1
+        params = self._blind_params()
+        frames = [ops.stft_frames(e - s, self.stft_size, self.stft_shift, True)
+                  for s, e in plan.windows]
+        s, e = plan.windows[0]                            # (argument errors before device work)
+        ops.check_separate_args(obs[:, s:e], np.empty((K, frames[0])), params)
+        ctx = self._ctx()
+        ops._prepare_windows(ctx, params.stft_size, params.stft_shift, None)
+        F = self.stft_size // 2 + 1
+        H, L = plan.hop_frames, plan.shared_frames
+        # the posteriors in HBM: the window's own numbering and the linked one, reused by turns
+        own_d = ctx.empty(8 * F * K * max(frames))
+        linked_d = ctx.empty(8 * F * K * max(frames))
+        mapping_d, scores_d = ctx.empty(max(4 * K, 16)), ctx.empty(max(8 * K * K, 16))
+        n = len(plan.windows)
+        mappings = np.tile(np.arange(K), (n, 1))
+        link_scores = np.full((n, K), np.nan)
+        x_hats, priors, powers = [], [], []
+        ctx.set_utterances_in_flight(1)
+        try:
+            for w, ((s, e), T_w) in enumerate(zip(plan.windows, frames)):
+                init = recording.start_table(K, T_w, int(seed), w, start,
+                                             priors[-1] if priors else None, H, L)
+                win = ops.ResidentSeparation(ctx, obs[:, s:e], init, params,
+                                             gamma_d=own_d if w else linked_d)
+                win.enqueue()
+                if w:
+                    (pb, pe), (cb, _) = plan.link_frames
+                    ops.link_posteriors_device(ctx, linked_d, frames[w - 1], pb, own_d, T_w, cb,
+                                               pe - pb, F, K, mapping_d, scores_d)
+                    # (the previous window's table has been read: the linked one takes its place)
+                    ops.link_gather_device(ctx, own_d, F, K, T_w, mapping_d, linked_d)
+                x_hat, prior, power = win.result()
+                if w:
+                    mappings[w] = ctx.to_host(mapping_d, (K,), np.int32)
+                    S = ctx.to_host(scores_d, (K, K), np.float64)
+                    link_scores[w] = S[np.arange(K), mappings[w]]
+                x_hats.append(x_hat[mappings[w], :e - s])
+                priors.append(prior[mappings[w]])
+                powers.append(power)
+        finally:
+            ctx.set_utterances_in_flight(0)
+        starts = [s for s, _ in plan.windows]
+        frame_offsets = [w * H for w in range(n)]
+        T = frame_offsets[-1] + frames[-1]
+        x_hat = recording.stitch(x_hats, starts, N)
+        prior = recording.stitch(priors, frame_offsets, T)
+        power = recording.stitch(powers, frame_offsets, T)
+        active = pact.decide(prior, power, rule)
+        intervals = [pact.frames_to_intervals(active[k], self.stft_size, self.stft_shift,
+                                              self.stft_fading, N) for k in range(K)]
+        return BlindRecording(x_hat, prior, active, intervals, list(plan.windows), mappings,
+                              link_scores)
 
     def enhance_example_blind(self, ex, num_speakers, **kw):
         """`enhance_observation_blind` from an example: channels, context and trimming as

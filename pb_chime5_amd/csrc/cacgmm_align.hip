@@ -28,21 +28,10 @@
 // a pass is a function of the mappings in its range, so it would change nothing either.  No sync.
 #include <algorithm>
 
+#include "cacgmm_perm.h"
 #include "gss_internal.h"
 
 namespace {
-
-constexpr int ALIGN_WG = 256;
-
-// sum over the workgroup's 256 threads in one fixed order (DPP inside a wave, waves ascending);
-// the total is returned to every thread.  `red` holds 4 doubles.
-__device__ __forceinline__ double block_sum_256(double v, double *red) {
-    const double w = wave_sum(v);
-    __syncthreads();                         // (red may still be read from a previous use)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // ------------------------------------------------------------------ 1 / row norms
 __global__ __launch_bounds__(ALIGN_WG) void align_norms_kernel(const double *__restrict__ gamma,
@@ -106,45 +95,13 @@ __global__ __launch_bounds__(ALIGN_WG) void align_centroid_finish_kernel(
 }
 
 // ------------------------------------------------------------------ score and assign
-__host__ __device__ constexpr int align_factorial(int n) { return n <= 1 ? 1 : n * align_factorial(n - 1); }
-
-// total of candidate `index` (lexicographic rank among the K! permutations, decoded with the
-// factorial number system: digit k picks among the classes not taken yet, ascending), and the
-// permutation itself when `perm` is given
-template <int K>
-__device__ __forceinline__ double align_candidate(int index, const double *S, int32_t *perm) {
-    int rem = index;
-    unsigned used = 0;
-    double total = 0.0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int fact = align_factorial(K - 1 - k);
-        int digit = rem / fact;
-        rem -= digit * fact;
-        int j = 0;
-#pragma unroll
-        for (int e = 0; e < K; ++e) {
-            const bool is_free = ((used >> e) & 1u) == 0;
-            if (is_free && digit == 0) j = e;
-            if (is_free) --digit;
-        }
-        used |= 1u << j;
-        total += S[k * K + j];
-        if (perm) perm[k] = j;
-    }
-    return total;
-}
-
-__device__ __forceinline__ bool align_better(double ta, int ia, double tb, int ib) {
-    return ta > tb || (ta == tb && ia < ib);
-}
-
+// (the candidates, their decoder and the tie rule: cacgmm_perm.h)
 template <int K>
 __global__ __launch_bounds__(ALIGN_WG) void align_assign_kernel(
     const double *__restrict__ gamma, const double *__restrict__ c, const double *__restrict__ sq,
     int nblk, const double *__restrict__ inv_n, int32_t *__restrict__ mapping, int f_begin,
     int64_t T, const int32_t *__restrict__ prev_changed, int32_t *__restrict__ changed) {
-    constexpr int KK = K * K, NF = align_factorial(K);
+    constexpr int KK = K * K;
     __shared__ double red[4][KK];
     __shared__ double S[KK];
     __shared__ double best_total[4];
@@ -190,38 +147,9 @@ __global__ __launch_bounds__(ALIGN_WG) void align_assign_kernel(
     }
     __syncthreads();
 
-    // the K! candidates, thread tid takes ranks tid, tid + 256, ...: ascending, so `>` keeps the
-    // smallest rank among equal totals
-    double bt = -INFINITY;
-    int bi = 0;
-    for (int i = tid; i < NF; i += ALIGN_WG) {
-        const double tot = align_candidate<K>(i, S, nullptr);
-        if (align_better(tot, i, bt, bi)) {
-            bt = tot;
-            bi = i;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ot = __shfl_xor(bt, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (align_better(ot, oi, bt, bi)) {
-            bt = ot;
-            bi = oi;
-        }
-    }
-    if (lane == 0) {
-        best_total[wave] = bt;
-        best_index[wave] = bi;
-    }
-    __syncthreads();
+    // the K! candidates, the smallest rank among equal totals (cacgmm_perm.h)
+    const int bi = align_search<K>(S, best_total, best_index);
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (align_better(best_total[w], best_index[w], bt, bi)) {
-                bt = best_total[w];
-                bi = best_index[w];
-            }
-        bi = min(max(bi, 0), NF - 1);        // (non-finite scores: any permutation, but a permutation)
         int32_t perm[K];
         align_candidate<K>(bi, S, perm);
         bool moved = false;

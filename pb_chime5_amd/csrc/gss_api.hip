@@ -1094,6 +1094,51 @@ extern "C" int gss_cacgmm_model_permute(gss_ctx *ctx, const gss_cacgmm_model *mo
     return cacgmm_model_permute_run(ctx, em_model(model), F, K, D, mapping, em_model(model_out));
 }
 
+// ------------------------------------------------------------------ cross-window linking
+extern "C" int gss_cacgmm_link(gss_ctx *ctx, const double *prev, int64_t T_prev,
+                               int64_t prev_begin, const double *cur, int64_t T_cur,
+                               int64_t cur_begin, int64_t L, int F, int K, int32_t *mapping,
+                               double *scores) {
+    GSS_ENTER(ctx);
+    const char *what = "gss_cacgmm_link";
+    GSS_REQUIRE(ctx, prev, GSS_ERR_INVALID, "%s: prev_dev is NULL", what);
+    GSS_REQUIRE(ctx, cur, GSS_ERR_INVALID, "%s: cur_dev is NULL", what);
+    GSS_REQUIRE(ctx, mapping, GSS_ERR_INVALID, "%s: mapping_dev is NULL", what);
+    GSS_REQUIRE(ctx, scores, GSS_ERR_INVALID, "%s: scores_dev is NULL", what);
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F=%d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, K >= 1, GSS_ERR_INVALID, "%s: K=%d is smaller than 1", what, K);
+    GSS_REQUIRE(ctx, L >= 1, GSS_ERR_INVALID, "%s: L=%lld is smaller than 1", what, (long long)L);
+    GSS_REQUIRE(ctx, K <= GSS_ALIGN_MAX_CLASSES, GSS_ERR_UNSUPPORTED,
+                "%s: K=%d is larger than %d (the search is exhaustive)", what, K,
+                GSS_ALIGN_MAX_CLASSES);
+    // (begin <= T - L, not begin + L <= T: no overflow for any int64 argument)
+    GSS_REQUIRE(ctx, prev_begin >= 0 && L <= T_prev && prev_begin <= T_prev - L, GSS_ERR_INVALID,
+                "%s: prev frames [%lld, %lld + %lld) outside [0, T_prev=%lld)", what,
+                (long long)prev_begin, (long long)prev_begin, (long long)L, (long long)T_prev);
+    GSS_REQUIRE(ctx, cur_begin >= 0 && L <= T_cur && cur_begin <= T_cur - L, GSS_ERR_INVALID,
+                "%s: cur frames [%lld, %lld + %lld) outside [0, T_cur=%lld)", what,
+                (long long)cur_begin, (long long)cur_begin, (long long)L, (long long)T_cur);
+    GSS_TRY(arena_reserve(ctx, cacgmm_link_workspace_bytes(F, K)));
+    return cacgmm_link_run(ctx, prev, T_prev, prev_begin, cur, T_cur, cur_begin, L, F, K, mapping,
+                           scores);
+}
+
+extern "C" int gss_cacgmm_link_gather(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
+                                      const int32_t *mapping, double *out) {
+    GSS_ENTER(ctx);
+    const char *what = "gss_cacgmm_link_gather";
+    GSS_REQUIRE(ctx, gamma, GSS_ERR_INVALID, "%s: gamma_dev is NULL", what);
+    GSS_REQUIRE(ctx, mapping, GSS_ERR_INVALID, "%s: mapping_dev is NULL", what);
+    GSS_REQUIRE(ctx, out, GSS_ERR_INVALID, "%s: out_dev is NULL", what);
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F=%d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, K >= 1, GSS_ERR_INVALID, "%s: K=%d is smaller than 1", what, K);
+    GSS_REQUIRE(ctx, T >= 1, GSS_ERR_INVALID, "%s: T=%lld is smaller than 1", what, (long long)T);
+    GSS_REQUIRE(ctx, out != gamma, GSS_ERR_INVALID, "%s: out_dev is gamma_dev", what);
+    GSS_REQUIRE(ctx, K <= GSS_MAX_CLASSES, GSS_ERR_UNSUPPORTED, "%s: K=%d is larger than %d", what,
+                K, GSS_MAX_CLASSES);
+    return cacgmm_link_gather_run(ctx, gamma, F, K, T, mapping, out);
+}
+
 extern "C" int gss_masks_from_posteriors(gss_ctx *ctx, const double *gamma, int F, int K,
                                          int64_t T, int target, int drop, int64_t sf,
                                          int64_t ef, double *mx, double *mn) {
@@ -1506,13 +1551,17 @@ static size_t front_buffer_bytes(int F, int64_t T, int64_t T_act, int D, int K) 
     return b;
 }
 
-static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, int K) {
+static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, int K,
+                                bool shared_prior = false) {
     const int A = wpe_arrays_of(p);
     size_t stage = 0;
     // (per-array WPE: R is F A (C taps)^2, C = D / A)
     if (p->wpe)
         stage = std::max(stage, wpe_workspace_bytes(F * A, T, D / A, p->wpe_taps, p->wpe_delay) + (1 << 16));
-    stage = std::max(stage, cacgmm_workspace_bytes(F, T, D, K));
+    // (the shared prior: the reserve of gss_cacgmm_shared_prior)
+    stage = std::max(stage, shared_prior ? cacgmm_workspace_bytes(F, T, D, K, /*one_block=*/true) +
+                                               cacgmm_prior_workspace_bytes(F, T, K)
+                                         : cacgmm_workspace_bytes(F, T, D, K));
     return stage;
 }
 
@@ -1539,6 +1588,10 @@ struct PipelineCall {
     const gss_bf_wpd *wpd = nullptr;                 // the WPD beamformer
     const gss_wpe_online_cfg *wpe_online = nullptr;  // the online WPE in the place of the offline one
     PipelineActivity activity;
+    // gss_separate_observation: the EM is the one with a frequency-shared prior, started from
+    // this (K,T) table with no mask, in the place of the activity-guided one
+    const double *blind_init = nullptr;
+    double *blind_prior = nullptr;                   // (K,T), receives the prior of the last M-step
 };
 
 // (seg: the segment-wise beamformer in the place of the whole-window one; lcmv: the
@@ -1591,6 +1644,24 @@ static size_t targets_workspace(const gss_params *p, int F, int64_t T, int64_t T
     b += align_up(sizeof(int32_t) * 4 * (size_t)S);          // ref
     b += 4096;
     size_t stage = front_stage_bytes(p, F, T, D, K);
+    stage = std::max(stage, mvdr_workspace_bytes(F, T, D, S));
+    stage = std::max(stage, align_up(sizeof(cplx) * (size_t)F * T) + 4096);
+    stage = std::max(stage, stft_workspace_bytes((int64_t)S * T, p->stft_size));
+    return b + stage + (1 << 16);
+}
+
+// gss_separate_observation: the targets call with S = K, the EM with the shared prior in the
+// place of the guided one, and the posterior activity's partial planes and scores.
+static size_t separate_workspace(const gss_params *p, int F, int64_t T, int D, int K) {
+    const int S = K;
+    size_t b = front_buffer_bytes(F, T, T, D, K);
+    b += 2 * align_up(sizeof(double) * (size_t)S * F * T);   // masks
+    b += align_up(sizeof(cplx) * (size_t)S * F * T);         // Xhat
+    b += align_up(sizeof(int32_t) * 4 * (size_t)S);          // ref
+    b += 4096;
+    size_t stage = front_stage_bytes(p, F, T, D, K, /*shared_prior=*/true);
+    stage = std::max(stage, pact_workspace_bytes(F, T, K) +
+                                align_up(sizeof(double) * (size_t)K * T) + 4096);   // planes, scores
     stage = std::max(stage, mvdr_workspace_bytes(F, T, D, S));
     stage = std::max(stage, align_up(sizeof(cplx) * (size_t)F * T) + 4096);
     stage = std::max(stage, stft_workspace_bytes((int64_t)S * T, p->stft_size));
@@ -1706,6 +1777,18 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call
         GSS_TRY(pipeline_wpe(ctx, p, X, F * A, T, D / A, Y));
         GSS_TRY(wpe_arrays_regroup_run(ctx, Y, F, T, A, D / A, false, X));
         GSS_TRY(arena_release(ctx, mark));
+    }
+    if (call.blind_init) {
+        // gss_cacgmm_shared_prior(init, no mask, bss_iterations, post = 1): fit, then predict
+        EmSchedule s;
+        s.iterations = p->bss_iterations;
+        s.gamma = fr.gamma;
+        s.shared_prior = true;
+        s.prior = call.blind_prior;
+        GSS_TRY(cacgmm_schedule_run(ctx, X, F, T, D, EmGuide{call.blind_init, nullptr, 0, T, 0, 0},
+                                    K, s));
+        GSS_TRY(arena_release(ctx, mark));
+        return GSS_OK;
     }
     if (!call.guided) GSS_TRY(activity_run(ctx, act, K, N_act, p->stft_fading, fr.actf));
     GSS_TRY(cacgmm_run(ctx, X, F, T, D, call.guided ? guide : em_guide_from_activity(fr.actf, T_act),
@@ -1843,57 +1926,18 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     return GSS_OK;
 }
 
-// S targets of one window: the front once, then the target-dependent tail for all S targets
-// together -- masks, PSD, solve, reference channel, apply, postfilter and iSTFT each one launch
-// over S per-target blocks.  Row s of `out` and of every per-target tap is what
-// enhance_observation_impl gives for target_index[s] with that target's contexts.
-static int enhance_observation_targets_impl(gss_ctx *ctx, const gss_params *p, const void *obs,
-                                            int obs_type, int D, int64_t N, const uint8_t *act,
-                                            int K, int64_t N_act, int S, const int32_t *targets,
-                                            const int64_t *start_ctx, const int64_t *end_ctx,
-                                            double *out, const gss_debug_taps *taps) {
-    // (the status words of this call: none until its beamformer runs -- a call that fails before
-    // it, or a 'ch2' / 'sum' call, leaves no per-target words behind)
-    ctx->last_targets = 0;
-    GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, act, out, "gss_enhance_observation_targets"));
-    GSS_REQUIRE(ctx, targets && start_ctx && end_ctx, GSS_ERR_INVALID,
-                "gss_enhance_observation_targets: NULL target or context array");
-    // (K bounded before the indices are used as bit positions below)
-    GSS_TRY(check_class_count(ctx, K));
-    GSS_REQUIRE(ctx, S >= 1 && S <= K, GSS_ERR_INVALID,
-                "%d targets of %d classes: need 1 <= S <= K", S, K);
-    uint32_t seen = 0;
-    for (int s = 0; s < S; ++s) {
-        GSS_REQUIRE(ctx, targets[s] >= 0 && targets[s] < K, GSS_ERR_INVALID,
-                    "target_index[%d] = %d outside [0, %d)", s, targets[s], K);
-        GSS_REQUIRE(ctx, !(seen >> targets[s] & 1u), GSS_ERR_INVALID,
-                    "target_index[%d] = %d is given twice", s, targets[s]);
-        seen |= 1u << targets[s];
-        GSS_REQUIRE(ctx, start_ctx[s] >= 0 && end_ctx[s] >= 0, GSS_ERR_INVALID,
-                    "assert context samples >= 0 failed: %lld %lld (target %d)",
-                    (long long)start_ctx[s], (long long)end_ctx[s], s);
-    }
-    int64_t T, T_act;
-    GSS_TRY(check_pipeline_rest(ctx, p, D, N, K, N_act, &T, &T_act));
+// The target-dependent tail for S targets together (masks, beamformer or channel pick,
+// postfilter, iSTFT, the taps) on the front's X and gamma; start_ctx / end_ctx NULL: no context
+// frames.  mx, mn (S,F,T), Xhat (S,T,F), ref (4 S) and everything below `mark` stay allocated.
+static int run_targets_tail(gss_ctx *ctx, const gss_params *p, const PipelineFront &fr, int F,
+                            int64_t T, int64_t T_act, int D, int K, int S, const int32_t *targets,
+                            const int64_t *start_ctx, const int64_t *end_ctx, double *mx,
+                            double *mn, cplx *Xhat, int32_t *ref, size_t mark, double *out,
+                            const gss_debug_taps *taps) {
     const int size = p->stft_size, shift = p->stft_shift, fading = p->stft_fading;
-    const int F = size / 2 + 1;
-
-    GSS_TRY(arena_reserve(ctx, targets_workspace(p, F, T, T_act, D, K, S)));
-    PipelineFront fr;
-    GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
-    double *mx = arena_alloc_t<double>(ctx, (size_t)S * F * T);
-    double *mn = arena_alloc_t<double>(ctx, (size_t)S * F * T);
-    cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)S * F * T);
-    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4 * (size_t)S);
-    GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
-    const size_t mark = ctx->arena_off;
-    PipelineCall call;
-    call.obs_type = obs_type;
-    GSS_TRY(run_front(ctx, p, call, obs, D, D, N, act, K, N_act, F, T, T_act, fr, mark, EmGuide{}));
     cplx *const X = fr.X;
-
     int64_t sf[GSS_MAX_CLASSES] = {}, ef[GSS_MAX_CLASSES] = {};
-    if (p->bf_drop_context) {
+    if (p->bf_drop_context && start_ctx && end_ctx) {
         for (int s = 0; s < S; ++s) {
             sf[s] = gss_samples_to_stft_frames(start_ctx[s], size, shift, fading);
             ef[s] = gss_samples_to_stft_frames(end_ctx[s], size, shift, fading);
@@ -1929,6 +1973,56 @@ static int enhance_observation_targets_impl(gss_ctx *ctx, const gss_params *p, c
                                               hipMemcpyDeviceToDevice, ctx->stream));
     }
     return GSS_OK;
+}
+
+// S targets of one window: the front once, then the target-dependent tail for all S targets
+// together -- masks, PSD, solve, reference channel, apply, postfilter and iSTFT each one launch
+// over S per-target blocks.  Row s of `out` and of every per-target tap is what
+// enhance_observation_impl gives for target_index[s] with that target's contexts.
+static int enhance_observation_targets_impl(gss_ctx *ctx, const gss_params *p, const void *obs,
+                                            int obs_type, int D, int64_t N, const uint8_t *act,
+                                            int K, int64_t N_act, int S, const int32_t *targets,
+                                            const int64_t *start_ctx, const int64_t *end_ctx,
+                                            double *out, const gss_debug_taps *taps) {
+    // (the status words of this call: none until its beamformer runs -- a call that fails before
+    // it, or a 'ch2' / 'sum' call, leaves no per-target words behind)
+    ctx->last_targets = 0;
+    GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, act, out, "gss_enhance_observation_targets"));
+    GSS_REQUIRE(ctx, targets && start_ctx && end_ctx, GSS_ERR_INVALID,
+                "gss_enhance_observation_targets: NULL target or context array");
+    // (K bounded before the indices are used as bit positions below)
+    GSS_TRY(check_class_count(ctx, K));
+    GSS_REQUIRE(ctx, S >= 1 && S <= K, GSS_ERR_INVALID,
+                "%d targets of %d classes: need 1 <= S <= K", S, K);
+    uint32_t seen = 0;
+    for (int s = 0; s < S; ++s) {
+        GSS_REQUIRE(ctx, targets[s] >= 0 && targets[s] < K, GSS_ERR_INVALID,
+                    "target_index[%d] = %d outside [0, %d)", s, targets[s], K);
+        GSS_REQUIRE(ctx, !(seen >> targets[s] & 1u), GSS_ERR_INVALID,
+                    "target_index[%d] = %d is given twice", s, targets[s]);
+        seen |= 1u << targets[s];
+        GSS_REQUIRE(ctx, start_ctx[s] >= 0 && end_ctx[s] >= 0, GSS_ERR_INVALID,
+                    "assert context samples >= 0 failed: %lld %lld (target %d)",
+                    (long long)start_ctx[s], (long long)end_ctx[s], s);
+    }
+    int64_t T, T_act;
+    GSS_TRY(check_pipeline_rest(ctx, p, D, N, K, N_act, &T, &T_act));
+    const int F = p->stft_size / 2 + 1;
+
+    GSS_TRY(arena_reserve(ctx, targets_workspace(p, F, T, T_act, D, K, S)));
+    PipelineFront fr;
+    GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
+    double *mx = arena_alloc_t<double>(ctx, (size_t)S * F * T);
+    double *mn = arena_alloc_t<double>(ctx, (size_t)S * F * T);
+    cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)S * F * T);
+    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4 * (size_t)S);
+    GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
+    const size_t mark = ctx->arena_off;
+    PipelineCall call;
+    call.obs_type = obs_type;
+    GSS_TRY(run_front(ctx, p, call, obs, D, D, N, act, K, N_act, F, T, T_act, fr, mark, EmGuide{}));
+    return run_targets_tail(ctx, p, fr, F, T, T_act, D, K, S, targets, start_ctx, end_ctx, mx, mn,
+                            Xhat, ref, mark, out, taps);
 }
 
 extern "C" int gss_enhance_observation(gss_ctx *ctx, const gss_params *p, const double *obs,
@@ -2122,6 +2216,53 @@ extern "C" int gss_enhance_observation_targets_pcm16(gss_ctx *ctx, const gss_par
     GSS_ENTER_VARIANTS(ctx);
     return enhance_observation_targets_impl(ctx, p, obs, 1, D, N, act, K, N_act, S, targets,
                                             start_ctx, end_ctx, out, taps);
+}
+
+extern "C" int gss_separate_observation(gss_ctx *ctx, const gss_params *p, const double *obs,
+                                        int D, int64_t N, const double *init, int K, double *out,
+                                        double *prior, double *power, double *gamma,
+                                        const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *what = "gss_separate_observation";
+    ctx->last_targets = 0;
+    GSS_REQUIRE(ctx, p, GSS_ERR_INVALID, "%s: params is NULL", what);
+    GSS_REQUIRE(ctx, prior, GSS_ERR_INVALID, "%s: prior_dev is NULL", what);
+    GSS_TRY(check_pipeline_front(ctx, p, obs, D, N, init, out, what));
+    GSS_REQUIRE(ctx, !(p->wpe && p->wpe_arrays > 1), GSS_ERR_UNSUPPORTED,
+                "%s: wpe_arrays=%d, the per-array WPE has no annotation-free form", what,
+                p->wpe_arrays);
+    GSS_REQUIRE(ctx, !taps || !taps->act_frames, GSS_ERR_INVALID,
+                "%s: taps->act_frames must be NULL (there is no frame activity)", what);
+    GSS_TRY(check_class_count(ctx, K));
+    int64_t T, T_act;
+    GSS_TRY(check_pipeline_rest(ctx, p, D, N, K, N, &T, &T_act));
+    const int F = p->stft_size / 2 + 1, S = K;
+
+    GSS_TRY(arena_reserve(ctx, separate_workspace(p, F, T, D, K)));
+    PipelineFront fr;
+    GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
+    double *mx = arena_alloc_t<double>(ctx, (size_t)S * F * T);
+    double *mn = arena_alloc_t<double>(ctx, (size_t)S * F * T);
+    cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)S * F * T);
+    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4 * (size_t)S);
+    GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
+    const size_t mark = ctx->arena_off;
+    PipelineCall call;
+    call.entry = what;
+    call.blind_init = init;
+    call.blind_prior = prior;
+    GSS_TRY(run_front(ctx, p, call, obs, D, D, N, nullptr, K, N, F, T, T_act, fr, mark, EmGuide{}));
+    if (power) {     // (reads X and gamma; the scores are not asked for)
+        double *scores = arena_alloc_t<double>(ctx, (size_t)K * T, "separate scores");
+        GSS_REQUIRE(ctx, scores, GSS_ERR_NOMEM, "workspace sizing bug");
+        GSS_TRY(pact_run(ctx, fr.X, fr.gamma, F, K, T, D, nullptr, scores, power));
+        GSS_TRY(arena_release(ctx, mark));
+    }
+    GSS_TRY(copy_tap(ctx, gamma, fr.gamma, sizeof(double) * (size_t)F * K * T));
+    int32_t targets[GSS_MAX_CLASSES];
+    for (int s = 0; s < S; ++s) targets[s] = s;
+    return run_targets_tail(ctx, p, fr, F, T, T_act, D, K, S, targets, nullptr, nullptr, mx, mn,
+                            Xhat, ref, mark, out, taps);
 }
 
 extern "C" int gss_enhance_observation_host(gss_ctx *ctx, const gss_params *p,

@@ -418,6 +418,16 @@ int cacgmm_align_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
 int cacgmm_model_permute_run(gss_ctx *ctx, const EmModel &in, int F, int K, int D,
                              const int32_t *mapping, const EmModel &out);
 
+// cacgmm_link.hip: cross-window class linking (include/gss_hip.h: gss_cacgmm_link,
+// gss_cacgmm_link_gather).  The frame ranges have been validated by the entry point; the partial
+// rows come from the arena (cacgmm_link_workspace_bytes).
+size_t cacgmm_link_workspace_bytes(int F, int K);
+int cacgmm_link_run(gss_ctx *ctx, const double *prev, int64_t T_prev, int64_t prev_begin,
+                    const double *cur, int64_t T_cur, int64_t cur_begin, int64_t L, int F, int K,
+                    int32_t *mapping, double *scores);
+int cacgmm_link_gather_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
+                           const int32_t *mapping, double *out);
+
 // S > 1: S targets' weights (S, F, 2, T) -> partials (S, F, nch, 2, NE), one launch
 int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,
                      int nch, int chunk_frames, cplx *part, int S = 1);

@@ -21,6 +21,10 @@ here                        reference call (file:line)
                             the classes of a per-frequency model aligned across frequencies
                             (what pb_bss users run after a blind fit; the reference never does):
                             an annotation-free model object
+``link_posteriors`` / ``separate_observation``
+                            the classes of two overlapping windows linked on the frames they
+                            share, and the annotation-free window as one fused call (what
+                            `Enhancer.enhance_recording_blind` is built of; not in the reference)
 ``mvdr_souden_from_masks``  pb_bss beamformer chain       (beamforming_wrapper.py:51-97)
 ``mvdr_souden_segments_from_masks``  the same with statistics per segment of frames
 ``lcmv_souden_from_masks``  beamform_lcmv_souden_from_masks (beamforming_wrapper.py:127-171)
@@ -801,6 +805,73 @@ def cacgmm_model_permute(model, mapping, *, ctx=None):
         ctx.handle, ctypes.byref(src.struct), F, K, D, c_void_p(m_d.ptr),
         ctypes.byref(dst.struct)), 'gss_cacgmm_model_permute')
     return dst.to_host(ctx)
+
+
+# --------------------------------------------------------------------------
+# cross-window class linking (include/gss_hip.h: gss_cacgmm_link; not in the reference)
+# --------------------------------------------------------------------------
+def check_link_frames(frames, num_frames, name):
+    """A ``(begin, end)`` pair of integers with 0 <= begin < end <= num_frames (None: all
+    frames) -> (begin, end) as ints; ValueError."""
+    if frames is None:
+        return 0, int(num_frames)
+    try:
+        frames = tuple(frames)
+    except TypeError:
+        frames = None
+    if frames is None or len(frames) != 2 or not all(_is_integer(v) for v in frames):
+        raise ValueError(f'{name}: {frames!r} is not a (begin, end) pair of integers')
+    begin, end = (int(v) for v in frames)
+    if not 0 <= begin < end <= num_frames:
+        raise ValueError(f'{name}: not 0 <= begin = {begin} < end = {end} <= T = {num_frames}')
+    return begin, end
+
+
+def link_posteriors_device(ctx, prev_d, T_prev, prev_begin, cur_d, T_cur, cur_begin, L, F, K,
+                           mapping_d, scores_d):
+    """`gss_cacgmm_link` on tables that sit in HBM in the device layout (F,K,T): enqueues, copies
+    nothing.  ``mapping_d`` (K,) int32 and ``scores_d`` (K,K) float64 are device buffers."""
+    ctx._check(ctx.lib.gss_cacgmm_link(
+        ctx.handle, c_void_p(prev_d.ptr), int(T_prev), int(prev_begin), c_void_p(cur_d.ptr),
+        int(T_cur), int(cur_begin), int(L), int(F), int(K), c_void_p(mapping_d.ptr),
+        c_void_p(scores_d.ptr)), 'gss_cacgmm_link')
+
+
+def link_gather_device(ctx, gamma_d, F, K, T, mapping_d, out_d):
+    """`gss_cacgmm_link_gather`: ``out[f, a, :] = gamma[f, mapping[a], :]`` in HBM, the mapping
+    read on the device (no host round trip after the link).  Not in place."""
+    ctx._check(ctx.lib.gss_cacgmm_link_gather(
+        ctx.handle, c_void_p(gamma_d.ptr), int(F), int(K), int(T), c_void_p(mapping_d.ptr),
+        c_void_p(out_d.ptr)), 'gss_cacgmm_link_gather')
+
+
+def link_posteriors(prev, cur, *, prev_frames=None, cur_frames=None, ctx=None):
+    """Link the classes of two windows' posteriors on the frames they share
+    (`gss_cacgmm_link`): prev (K,T_prev,F), cur (K,T_cur,F); ``prev_frames`` / ``cur_frames``
+    ``(begin, end)`` pairs of equally many frames (None: the whole table) -> mapping (K,) int32
+    and scores (K,K): ``scores[a, b]`` is the cosine similarity, over the frames and all
+    frequencies, of class a of ``prev`` and class b of ``cur``; the mapping is the permutation
+    that maximises ``sum_a scores[a, mapping[a]]`` (the lexicographically smallest among exact
+    maxima), so that ``cur[mapping]`` continues ``prev``.  At most 8 classes.  Every argument
+    error is a ValueError before any device work."""
+    prev = _check_posterior_ktf(prev)
+    cur = _check_posterior_ktf(cur)
+    K, T_prev, F = prev.shape
+    if cur.shape[0] != K or cur.shape[2] != F:
+        raise ValueError(f'cur: shape {cur.shape} does not have the {K} classes and {F} '
+                         f'frequencies of prev {prev.shape}')
+    T_cur = cur.shape[1]
+    pb, pe = check_link_frames(prev_frames, T_prev, 'prev_frames')
+    cb, ce = check_link_frames(cur_frames, T_cur, 'cur_frames')
+    if pe - pb != ce - cb:
+        raise ValueError(f'prev_frames covers {pe - pb} frames, cur_frames {ce - cb}')
+    ctx = ctx or default_context()
+    p_d = ctx.to_device(np.ascontiguousarray(prev.transpose(2, 0, 1), dtype=np.float64))
+    c_d = ctx.to_device(np.ascontiguousarray(cur.transpose(2, 0, 1), dtype=np.float64))
+    m_d = ctx.empty(max(4 * K, 16))
+    s_d = ctx.empty(max(8 * K * K, 16))
+    link_posteriors_device(ctx, p_d, T_prev, pb, c_d, T_cur, cb, pe - pb, F, K, m_d, s_d)
+    return ctx.to_host(m_d, (K,), np.int32), ctx.to_host(s_d, (K, K), np.float64)
 
 
 def cacgmm_fit_blind(Obs, num_classes, iterations=20, *, seed=0, plan=None,
@@ -2396,3 +2467,109 @@ def enhance_observation_targets(obs, activity, target_indices, start_context_sam
     if not debug:
         return x_hat
     return x_hat, _debug_details(utt, bufs, S)
+
+
+# --------------------------------------------------------------------------
+# annotation-free separation of one window in one call (gss_separate_observation)
+# --------------------------------------------------------------------------
+def check_separate_args(obs, initialization, params):
+    """obs (D,N) real, initialization (K,T) with T the STFT frames of N samples -> (obs float64,
+    initialization float64, D, N, K, T); ValueError before any device work."""
+    obs = np.asarray(obs)
+    if obs.ndim != 2 or obs.dtype.kind not in 'fiu':
+        raise ValueError(f'obs: shape {obs.shape}, dtype {obs.dtype} is not a real (D,N) array')
+    D, N = obs.shape
+    if not 2 <= D <= _MAX_CHANNELS:
+        raise ValueError(f'obs: {D} channels outside [2, {_MAX_CHANNELS}]')
+    if N < 1:
+        raise ValueError('obs: no samples')
+    init = np.asarray(initialization)
+    if init.ndim != 2 or init.dtype.kind not in 'fiu':
+        raise ValueError(f'initialization: shape {init.shape}, dtype {init.dtype} is not a real '
+                         '(K,T) table')
+    K = init.shape[0]
+    if not 1 <= K <= _MAX_CLASSES:
+        raise ValueError(f'{K} classes outside [1, {_MAX_CLASSES}]')
+    T = stft_frames(N, params.stft_size, params.stft_shift, params.stft_fading)
+    if init.shape[1] != T:
+        raise ValueError(f'initialization: {init.shape[1]} frames, the observation has {T}')
+    return (np.ascontiguousarray(obs, dtype=np.float64),
+            np.ascontiguousarray(init, dtype=np.float64), D, N, K, T)
+
+
+class ResidentSeparation:
+    """One window of `gss_separate_observation` whose inputs sit in HBM: obs (D,N),
+    initialization (K,T).  ``gamma_d``: a device buffer of at least 8 F K T bytes that receives
+    the posteriors in the device layout (F,K,T) (None: one of the call's own)."""
+
+    def __init__(self, ctx, obs, initialization, params, gamma_d=None):
+        obs, init, self.D, self.N, self.K, self.T = check_separate_args(obs, initialization,
+                                                                        params)
+        self.ctx, self.params = ctx, params
+        self.F = params.stft_size // 2 + 1
+        self.n_out = int(ctx.lib.gss_istft_num_samples(
+            self.T, params.stft_size, params.stft_shift, params.stft_fading))
+        self.obs_d = ctx.to_device(obs)
+        self.init_d = ctx.to_device(init)
+        self.out_d = ctx.empty(8 * max(self.K * self.n_out, 1))
+        self.prior_d = ctx.empty(8 * self.K * self.T)
+        self.power_d = ctx.empty(max(8 * self.T, 16))
+        self.gamma_d = gamma_d if gamma_d is not None else ctx.empty(8 * self.F * self.K * self.T)
+        assert self.gamma_d.nbytes >= 8 * self.F * self.K * self.T
+
+    def enqueue(self, taps=None):
+        ctx = self.ctx
+        ctx._check(ctx.lib.gss_separate_observation(
+            ctx.handle, ctypes.byref(self.params), c_void_p(self.obs_d.ptr), self.D, self.N,
+            c_void_p(self.init_d.ptr), self.K, c_void_p(self.out_d.ptr),
+            c_void_p(self.prior_d.ptr), c_void_p(self.power_d.ptr), c_void_p(self.gamma_d.ptr),
+            ctypes.byref(taps) if taps is not None else None), 'gss_separate_observation')
+
+    def result(self):
+        """(x_hat (K,N'), prior (K,T), power (T,)) on the host; a class whose beamformer failed
+        raises what `enhance_observation` raises, naming the class."""
+        ctx = self.ctx
+        x_hat = ctx.to_host(self.out_d, (self.K, self.n_out), np.float64)
+        prior = ctx.to_host(self.prior_d, (self.K, self.T), np.float64)
+        power = ctx.to_host(self.power_d, (self.T,), np.float64)
+        if self.params.bf in (_BF_CODES['mvdrSouden_ban'], _BF_CODES['gev_ban']):
+            for k, ref in enumerate(ctx.last_ref_channels(self.K)):
+                _raise_for_ref_channel(ref, f'class {k}')
+        return x_hat, prior, power
+
+    def posterior(self):
+        """The posteriors as the host has them elsewhere: (K,T,F)."""
+        g = self.ctx.to_host(self.gamma_d, (self.F, self.K, self.T), np.float64)
+        return np.ascontiguousarray(g.transpose(1, 2, 0))
+
+
+def separate_observation(obs, initialization, *, params=None, window=None, debug=False,
+                         return_posterior=False, ctx=None, **param_kwargs):
+    """Annotation-free separation of one window in ONE call (`gss_separate_observation`): STFT,
+    the joint WPE, the CACGMM with a frequency-shared prior from ``initialization`` (K,T) -- no
+    mask, ``bss_iterations`` iterations, one post iteration: `cacgmm_posteriors_blind` with
+    ``method='shared_prior'`` from that table --, the frame power of `posterior_activity`, the
+    beamformer for every class (target k = class k, no context frames) and K iSTFTs.
+
+    obs (D,N) float64.  Returns (x_hat (K,N'), prior (K,T), power (T,)); with
+    ``return_posterior`` also the posteriors (K,T,F); with ``debug=True`` also the details of
+    `enhance_observation_targets` (no ``acitivity_freq``: there is no activity).  The per-array
+    WPE is NotImplementedError; every argument error is a ValueError before any device work."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    check_separate_args(obs, initialization, params)
+    ctx = ctx or default_context()
+    _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
+    win = ResidentSeparation(ctx, obs, initialization, params)
+    bufs, taps = ({}, None)
+    if debug:
+        bufs, taps = _debug_taps(win, win.K)
+        del bufs['act_frames']
+        taps.act_frames = None
+    win.enqueue(taps)
+    out = list(win.result())
+    if return_posterior:
+        out.append(win.posterior())
+    if debug:
+        out.append(_debug_details(win, bufs, win.K))
+    return tuple(out)
