@@ -91,7 +91,9 @@ typedef enum {
  * (it takes the gss_guidance descriptor as it is).  So were gss_wpe_online_init, gss_wpe_online and
  * gss_enhance_observation_wpe_online with the gss_wpe_online_state and gss_wpe_online_cfg
  * descriptors.  So were gss_cacgmm_align, gss_cacgmm_model_permute and gss_last_align_moved with
- * the gss_align_plan descriptor. */
+ * the gss_align_plan descriptor.  So were gss_mvdr_online_init, gss_mvdr_online,
+ * gss_last_mvdr_online_fallbacks and gss_enhance_observation_bf_online with the
+ * gss_mvdr_online_state and gss_bf_online descriptors. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -679,6 +681,66 @@ int gss_wpe_online_init(gss_ctx *ctx, int F, int A, int C, int taps, int delay,
 int gss_wpe_online(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int A, int C, int taps,
                    int delay, double alpha, const gss_wpe_online_state *state, gss_cplx *X_dev);
 
+/* ---- online MVDR ------------------------------------------------------------
+ * Souden's mask-based MVDR (optionally with blind analytic normalisation) in a causal form: the
+ * two PSD matrices are exponentially forgetting running sums, the filter is recomputed at every
+ * frame, and the state is carried between calls.  (Entry points only, looked up by the binding:
+ * revision still 7.)  One problem per frequency f with D channels.  For each frame t, in order,
+ * with y = Y[f,t,:], a = mask_x[f,t], b = mask_n[f,t] and beta = cfg->forget:
+ *    Phi_X <- beta Phi_X + a y y^H,   Phi_N <- beta Phi_N + b y y^H
+ *    Cholesky Phi_N = L L^H; a pivot that is not > 0 or not finite makes t a FALLBACK frame:
+ *                     w = 0, Xhat[f,t] = 0, the frame is counted, the update above stays
+ *    Psi = Phi_N^-1 Phi_X;  w = Psi[:, ref] / max(Re trace(Psi), 1e-10)
+ *    ban:  v = Phi_N w;  w <- w sqrt(v^H v) / |w^H v|       (eps = 0 as upstream, except that
+ *                     |w^H v| = 0 -- a zero filter: no target mass yet, as in the context frames
+ *                     of every window -- leaves w = 0 where upstream divides 0 by 0)
+ *    Xhat[f,t] = w^H y          the sums INCLUDE frame t: causal, zero look-ahead
+ * A fresh state is Phi_X = 0, Phi_N = loading * p_f * I, where p_f is the mean of |Y[f,t,d]|^2
+ * over the frames and channels handed to the initialisation (1 when there are none, or when
+ * that mean is exactly 0). */
+typedef struct {
+    gss_cplx *phi_x, *phi_n;   /* (F, D, D) row-major; a reader takes the upper triangle and the real
+                                  part of the diagonal; on return both triangles are stored, the lower
+                                  the exact conjugate of the upper, diagonal imaginary parts 0 */
+    int32_t F, D;
+} gss_mvdr_online_state;       /* caller-owned, like gss_wpe_online_state */
+
+typedef struct {
+    double forget;             /* beta, in (0, 1] */
+    double loading;            /* of a fresh state; read only when `state` is NULL */
+    int32_t ref_channel;       /* -1: chosen as by gss_mvdr_souden over the call's frames -- NOT
+                                  causal: the whole-window statistics of the call pick it */
+    int32_t wpe_online;        /* the last two are read by the fused entry only */
+    double wpe_alpha;
+} gss_bf_online;
+
+/* Phi_X = 0, Phi_N = loading * p_f * I in the caller's buffers, p_f from Y_dev (F,T,D); Y_dev
+ * NULL or T = 0: p_f = 1.  The sum for p_f has one fixed order.  GSS_ERR_INVALID before any
+ * launch: a NULL state or state field, state->F / state->D other than F / D, F < 1, T < 0,
+ * loading not finite or <= 0.  GSS_ERR_UNSUPPORTED: D outside [1, GSS_MAX_CHANNELS]. */
+int gss_mvdr_online_init(gss_ctx *ctx, int F, int D, const gss_cplx *Y_dev, int64_t T,
+                         double loading, gss_mvdr_online_state *state);
+
+/* Y (F,T,D), masks (F,T) -> Xhat (F,T) and, when W_dev is not NULL, the filters (F,T,D).
+ * `state` is read, advanced by T frames and written back; NULL: a fresh state from the workspace,
+ * initialised from Y_dev with cfg->loading and thrown away.  T = 0 is a no-op.  One persistent
+ * wave per frequency walks the frames with both matrices on the chip; the kernel form and every
+ * order of summation depend on D alone, so a recording fed in blocks through one state gives the
+ * bits of the single call, and the same call gives the same bits.  gss_last_ref_channel reports
+ * the reference channel used (-1: ref_channel = -1 found no finite SNR; Xhat and W are NaN and
+ * the state is untouched), gss_last_mvdr_online_fallbacks the fallback frames.
+ * GSS_ERR_INVALID (the message names the argument), before any launch: a NULL pointer other than
+ * state / W_dev, a NULL state field, state->F / state->D other than F / D, F < 1, T < 0, forget
+ * outside (0, 1] or not finite, loading not finite or <= 0, ref_channel outside [-1, D).
+ * GSS_ERR_UNSUPPORTED: D outside [1, GSS_MAX_CHANNELS]. */
+int gss_mvdr_online(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                    const double *mask_x_dev, const double *mask_n_dev, int ban,
+                    const gss_bf_online *cfg, gss_mvdr_online_state *state, gss_cplx *Xhat_dev,
+                    gss_cplx *W_dev);
+
+/* (frequency, frame) pairs of the last online MVDR on this context that fell back (synchronises). */
+int gss_last_mvdr_online_fallbacks(gss_ctx *ctx, int64_t *count_host);
+
 /* beamform_gev_from_masks (beamforming_wrapper.py:77-89,192-208): masked PSD
  * matrices, principal generalised eigenvector of (Phi_X, Phi_N) with
  * w^H Phi_N w = 1 (phase arbitrary, as upstream), optional BAN, apply.
@@ -890,6 +952,22 @@ int gss_enhance_observation_wpe_online(gss_ctx *ctx, const gss_params *params,
                                        int64_t end_context_samples,
                                        const gss_wpe_online_cfg *cfg,
                                        double *out_dev, const gss_debug_taps *taps);
+
+/* gss_enhance_observation with gss_mvdr_online (BAN on, a fresh state initialised from the window
+ * with cfg->loading) in the place of the whole-window beamformer.  cfg->ref_channel is usually -1,
+ * the window's.  cfg->wpe_online != 0: gss_wpe_online with cfg->wpe_alpha in the place of the
+ * offline WPE as well, as gss_enhance_observation_wpe_online -- the two online stages in one
+ * call.  params->bf must be 0.  gss_last_mvdr_online_fallbacks works afterwards.
+ * GSS_ERR_INVALID: cfg NULL, the errors of gss_mvdr_online's cfg, params->bf != 0, and with
+ * wpe_online those of gss_enhance_observation_wpe_online. */
+int gss_enhance_observation_bf_online(gss_ctx *ctx, const gss_params *params,
+                                      const double *obs_dev, int D, int64_t N,
+                                      const uint8_t *act_dev, int K, int64_t N_act,
+                                      int target_index,
+                                      int64_t start_context_samples,
+                                      int64_t end_context_samples,
+                                      const gss_bf_online *cfg,
+                                      double *out_dev, const gss_debug_taps *taps);
 
 /* gss_enhance_observation plus gss_posterior_activity on the pipeline's own post-WPE observation
  * and its posteriors before context zeroing (what the taps Obs_ftd and gamma show), nothing

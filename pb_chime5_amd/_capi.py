@@ -81,6 +81,21 @@ class GssWpeOnlineState(ctypes.Structure):
     _fields_ = [('inv_cov_dev', c_void_p), ('filter_dev', c_void_p), ('history_dev', c_void_p)]
 
 
+class GssMvdrOnlineState(ctypes.Structure):
+    """gss_mvdr_online_state: the running sums Phi_X and Phi_N (F,D,D) of the online MVDR,
+    complex, in HBM."""
+    _fields_ = [('phi_x', c_void_p), ('phi_n', c_void_p), ('F', ctypes.c_int32),
+                ('D', ctypes.c_int32)]
+
+
+class GssBfOnline(ctypes.Structure):
+    """gss_bf_online: the online MVDR's forgetting factor, the loading of a fresh state and the
+    reference channel (-1: the window's); wpe_online / wpe_alpha are read by the fused entry."""
+    _fields_ = [('forget', ctypes.c_double), ('loading', ctypes.c_double),
+                ('ref_channel', ctypes.c_int32), ('wpe_online', ctypes.c_int32),
+                ('wpe_alpha', ctypes.c_double)]
+
+
 class GssWpeOnlineCfg(ctypes.Structure):
     """gss_wpe_online_cfg: the forgetting factor of the online WPE in the fused call."""
     _fields_ = [('alpha', ctypes.c_double)]
@@ -202,6 +217,13 @@ SIGNATURES = {
     'gss_wpe_online': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int,
                                ctypes.c_double, ctypes.POINTER(GssWpeOnlineState), c_void_p]),
     'gss_enhance_observation_wpe_online': _fused(ctypes.POINTER(GssWpeOnlineCfg)),
+    'gss_mvdr_online_init': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, ctypes.c_double,
+                                     ctypes.POINTER(GssMvdrOnlineState)]),
+    'gss_mvdr_online': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
+                                c_int, ctypes.POINTER(GssBfOnline),
+                                ctypes.POINTER(GssMvdrOnlineState), c_void_p, c_void_p]),
+    'gss_last_mvdr_online_fallbacks': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'gss_enhance_observation_bf_online': _fused(ctypes.POINTER(GssBfOnline)),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,
@@ -525,6 +547,11 @@ class Context:
         """Frequencies of the last LCMV beamformer on this context that fell back to the MVDR of
         the merged mask (synchronises)."""
         return self._last('gss_last_lcmv_fallbacks', ctypes.c_int64)
+
+    def last_mvdr_online_fallbacks(self):
+        """(frequency, frame) pairs of the last online MVDR on this context whose noise matrix had
+        no Cholesky factor (synchronises)."""
+        return self._last('gss_last_mvdr_online_fallbacks', ctypes.c_int64)
 
     def workspace_bytes(self):
         return int(self.lib.gss_workspace_bytes(self.handle))

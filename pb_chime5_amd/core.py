@@ -337,8 +337,32 @@ class Beamformer:
     wpd_delay: int = 2
     wpd_iterations: int = 1
     wpd_power_floor: float = ops.WPD_POWER_FLOOR
+    # Online MVDR (an addition, see ops.mvdr_souden_online_from_masks): 'mvdrSouden_ban' on
+    # running sums that forget at the rate ``forget``, a filter per frame, from a fresh state per
+    # utterance with the relative diagonal ``loading``; the reference channel is the window's.
+    # forget = 0.99 and loading = 1e-2 are choices, not measurements.  Unread without ``online``.
+    online: bool = False
+    forget: float = ops.BF_ONLINE_FORGET
+    loading: float = ops.BF_ONLINE_LOADING
 
     def __post_init__(self):
+        assert self.online is True or self.online is False, self.online
+        if self.online:
+            if self.type != 'mvdrSouden_ban':
+                raise NotImplementedError(
+                    f"bf={self.type!r} with bf_online: only 'mvdrSouden_ban' has an online form")
+            for name, on in (('bf_segment_frames', self.segment_frames is not None),
+                             ('bf_null_interferer', self.null_interferer)):
+                if on:
+                    raise NotImplementedError(
+                        f'bf_online with {name}: the online beamformer has a filter per frame '
+                        'from two masks')
+            ops.check_bf_online(self.forget, self.loading)
+        else:
+            for name, value, default in (('bf_forget', self.forget, ops.BF_ONLINE_FORGET),
+                                         ('bf_loading', self.loading, ops.BF_ONLINE_LOADING)):
+                if value != default:
+                    raise NotImplementedError(f'{name}={value!r} without bf_online: nobody reads it')
         if self.type in ops.WPD_BF_TYPES:
             ops.check_bf_wpd(self.wpd_taps, self.wpd_delay, self.wpd_iterations,
                              self.wpd_power_floor, segment_frames=self.segment_frames,
@@ -384,6 +408,13 @@ class Beamformer:
         return dict(taps=self.wpd_taps, delay=self.wpd_delay, iterations=self.wpd_iterations,
                     power_floor=self.wpd_power_floor, ban=ops.WPD_BF_TYPES[self.type])
 
+    @property
+    def online_settings(self):
+        """The keyword arguments of the online calls in ``ops``, or None."""
+        if not self.online:
+            return None
+        return dict(forget=self.forget, loading=self.loading)
+
     def __call__(self, Obs, target_mask, distortion_mask, debug=False, *, interferer_mask=None,
                  noise_mask=None, raw_obs=None, frame_gate=None):
         """``interferer_mask`` (with ``null_interferer``): the competing talker's mask, a part
@@ -413,6 +444,10 @@ class Beamformer:
                 Obs, target_mask, interferer_mask, noise_mask, ban=True, min_mass=min_mass)
         elif interferer_mask is not None or noise_mask is not None:
             raise ValueError('interferer_mask / noise_mask without null_interferer')
+        elif self.online:       # ('mvdrSouden_ban', checked above; the window's reference channel)
+            X_hat = ops.mvdr_souden_online_from_masks(
+                Obs, target_mask, distortion_mask, ban=True, ref_channel=-1,
+                **self.online_settings)
         elif bf == 'mvdrSouden_ban':
             from pb_chime5_amd.speech_enhancement.beamforming_wrapper import (
                 beamform_mvdr_souden_from_masks)
@@ -495,6 +530,9 @@ class Enhancer:
                 raise NotImplementedError(
                     f'wpe_online with bf={self.bf_block.type!r}: the WPD beamformer dereverberates '
                     'with an offline WPE step of its own')
+        if self._bf_online() is not None and self.channel_keep is not None:
+            raise NotImplementedError(
+                'bf_online with channel_keep: the online beamformer has no selection')
         if self.channel_keep is None:
             return
         ops.check_channel_keep(self.channel_keep)
@@ -656,10 +694,10 @@ class Enhancer:
         # (a segment-wise beamformer has no pipelined pcm16 entry point: one at a time; neither
         # has the posterior activity of a refined RTTM)
         # (nor has the WPD: the pipelined path is out of its scope)
-        # (nor has the online WPE)
+        # (nor has the online WPE, nor the online beamformer)
         if (self.inflight <= 1 or not self._fusable() or self._bf_segments() is not None
                 or refined_rttm or self._bf_wpd() is not None
-                or self._wpe_online() is not None):
+                or self._wpe_online() is not None or self._bf_online() is not None):
             for ex in examples:
                 try:
                     if refined_rttm:
@@ -996,6 +1034,16 @@ class Enhancer:
                 f'{what} with bf={self.bf_block.type!r}: the WPD beamformer is built for '
                 'enhance_observation, enhance_example and enhance_session only')
 
+    def _bf_online(self):
+        """The online settings of the beamformer (``Beamformer.online_settings``) or None."""
+        return getattr(getattr(self, 'bf_block', None), 'online_settings', None)
+
+    def _no_bf_online(self, what):
+        if self._bf_online() is not None:
+            raise NotImplementedError(
+                f'{what} with bf_online: the online beamformer is built for enhance_observation, '
+                'enhance_example and enhance_session only')
+
     def _wpe_online(self):
         """The forgetting factor of an online WPE block (``WPE.online``) or None."""
         block = getattr(self, 'wpe_block', None)
@@ -1014,6 +1062,7 @@ class Enhancer:
         self._no_null(what)
         self._no_channel_keep(what)
         self._no_wpd(what)
+        self._no_bf_online(what)
         if self.wpe_per_array:
             raise NotImplementedError(
                 f'{what} with wpe_per_array: the annotation-free path runs one joint WPE')
@@ -1024,6 +1073,7 @@ class Enhancer:
         self._no_null(what)
         self._no_channel_keep(what)
         self._no_wpd(what)
+        self._no_bf_online(what)
         self._no_wpe_online(what)
 
     @staticmethod
@@ -1082,7 +1132,8 @@ class Enhancer:
         segments = self._bf_segments()
         select = self._channel_select()
         online = self._wpe_online()
-        if online is not None:
+        bf_online = self._bf_online()
+        if online is not None and bf_online is None:
             # (the fused online call takes no second descriptor; the stage path combines)
             for name, on in (('bf_segment_frames', segments is not None),
                              ('bf_null_interferer', self._bf_null()),
@@ -1092,7 +1143,14 @@ class Enhancer:
                         f'wpe_online with {name} in the fused call: pass fused=False for the '
                         'stage path')
         try:
-            if online is not None:
+            if bf_online is not None:
+                # (both online stages in one call: the descriptor carries the WPE's alpha)
+                res = ops.enhance_observation_bf_online(
+                    obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
+                    debug=debug, ctx=ctx, wpe_arrays=wpe_arrays, ref_channel=-1,
+                    wpe_online=online is not None,
+                    wpe_alpha=ops.WPE_ONLINE_ALPHA if online is None else online, **bf_online)
+            elif online is not None:
                 res = ops.enhance_observation_wpe_online(
                     obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
                     debug=debug, ctx=ctx, wpe_arrays=wpe_arrays, alpha=online)
@@ -1444,6 +1502,7 @@ class Enhancer:
         given (a neural mask estimator's output).  ``fused=False`` runs the blocks."""
         self._no_segments('enhance_observation_guided')
         self._no_wpd('enhance_observation_guided')
+        self._no_bf_online('enhance_observation_guided')
         self._no_wpe_online('enhance_observation_guided')
         self._no_null('enhance_observation_guided')
         self._no_channel_keep('enhance_observation_guided')
@@ -1546,6 +1605,7 @@ class Enhancer:
         self._no_posterior_activity('enhance_observation_speakers', posterior_activity)
         self._no_segments('enhance_observation_speakers')
         self._no_wpd('enhance_observation_speakers')
+        self._no_bf_online('enhance_observation_speakers')
         self._no_wpe_online('enhance_observation_speakers')
         self._no_null('enhance_observation_speakers')
         self._no_channel_keep('enhance_observation_speakers')
@@ -1585,6 +1645,7 @@ class Enhancer:
         self._no_posterior_activity('enhance_example_speakers', posterior_activity)
         self._no_segments('enhance_example_speakers')
         self._no_wpd('enhance_example_speakers')
+        self._no_bf_online('enhance_example_speakers')
         self._no_wpe_online('enhance_example_speakers')
         self._no_null('enhance_example_speakers')
         self._no_channel_keep('enhance_example_speakers')
@@ -1782,10 +1843,25 @@ def get_enhancer(
     bf_wpd_power_floor=ops.WPD_POWER_FLOOR,
     wpe_online=False,
     wpe_alpha=ops.WPE_ONLINE_ALPHA,
+    bf_online=False,
+    bf_forget=ops.BF_ONLINE_FORGET,
+    bf_loading=ops.BF_ONLINE_LOADING,
 ):
     """core.py:574-637 (same keyword arguments and defaults; ``activity_store``,
     ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*``,
-    ``bf_null_*``, ``bf_wpd_*``, ``wpe_online`` and ``wpe_alpha`` are additions).
+    ``bf_null_*``, ``bf_wpd_*``, ``wpe_online``, ``wpe_alpha``, ``bf_online``, ``bf_forget`` and
+    ``bf_loading`` are additions).
+    ``bf_online=True``: 'mvdrSouden_ban' becomes the online MVDR (see
+    `ops.mvdr_souden_online_from_masks`) -- running sums that forget at the rate ``bf_forget``
+    (0.99, a memory of 1.6 s at the 16 ms frame shift: a choice, not a measurement), a filter per
+    frame with no look-ahead, from a fresh state per utterance with the relative diagonal loading
+    ``bf_loading`` (1e-2: a choice, not a measurement); the reference channel is the window's.
+    For `Enhancer.enhance_observation` / `enhance_example` (one fused call, or the stage path
+    with ``fused=False``) and, one utterance at a time, `enhance_session`; it combines with
+    ``wpe_online=True`` and ``wpe_per_array``.  Not with another ``bf``, ``bf_segment_frames``,
+    ``bf_null_interferer``, ``channel_keep``, ``refined_rttm``, the guided, multi-speaker,
+    activity or annotation-free methods, and a ``bf_forget`` / ``bf_loading`` other than the
+    default without it is a setting nobody reads (NotImplementedError).
     ``wpe_online=True``: the WPE block is nara_wpe's online form (see `ops.wpe_online_dtf`) -- a
     frame-recursive filter from a fresh state per utterance that forgets at the rate
     ``wpe_alpha`` (0.9999: a choice, not a measurement), the time-varying front for long windows
@@ -1840,6 +1916,7 @@ def get_enhancer(
                             segment_min_mass=bf_segment_min_mass,
                             null_interferer=bool(bf_null_interferer),
                             null_min_mass=bf_null_min_mass,
+                            online=bf_online, forget=bf_forget, loading=bf_loading,
                             **bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps,
                                               bf_wpd_delay, bf_wpd_iterations,
                                               bf_wpd_power_floor)),

@@ -181,10 +181,13 @@ def get_enhancer(
     bf_wpd_power_floor=ops.WPD_POWER_FLOOR,
     wpe_online=False,
     wpe_alpha=ops.WPE_ONLINE_ALPHA,
+    bf_online=False,
+    bf_forget=ops.BF_ONLINE_FORGET,
+    bf_loading=ops.BF_ONLINE_LOADING,
 ):
     """core_chime6_rttm.py:360-422 (same keyword arguments and defaults; ``device_id``,
     ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*``,
-    ``bf_wpd_*``, ``wpe_online`` and ``wpe_alpha`` are additions, see core.get_enhancer)."""
+    ``bf_wpd_*``, ``wpe_online``, ``wpe_alpha``, ``bf_online``, ``bf_forget`` and ``bf_loading`` are additions, see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     db = get_database(chime6_dir, database_rttm, multiarray)
     return Enhancer(
@@ -203,6 +206,7 @@ def get_enhancer(
                             segment_min_mass=bf_segment_min_mass,
                             null_interferer=bool(bf_null_interferer),
                             null_min_mass=bf_null_min_mass,
+                            online=bf_online, forget=bf_forget, loading=bf_loading,
                             **bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps,
                                               bf_wpd_delay, bf_wpd_iterations,
                                               bf_wpd_power_floor)),

@@ -1245,6 +1245,81 @@ extern "C" int gss_last_segment_fallbacks(gss_ctx *ctx, int64_t *count) {
     return read_status_word(ctx, GSS_STATUS_SEGMENT_FALLBACKS, count, "gss_last_segment_fallbacks");
 }
 
+// The online MVDR argument rule, before any launch.
+static int check_bf_online(gss_ctx *ctx, const char *what, const gss_bf_online *cfg, int D) {
+    GSS_REQUIRE(ctx, cfg, GSS_ERR_INVALID, "%s: cfg is NULL", what);
+    GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED, "%s: D = %d outside [1, %d]",
+                what, D, GSS_MAX_CHANNELS);
+    GSS_REQUIRE(ctx, std::isfinite(cfg->forget) && cfg->forget > 0.0 && cfg->forget <= 1.0,
+                GSS_ERR_INVALID, "%s: forget = %g outside (0, 1]", what, cfg->forget);
+    GSS_REQUIRE(ctx, std::isfinite(cfg->loading) && cfg->loading > 0.0, GSS_ERR_INVALID,
+                "%s: loading = %g is not finite and > 0", what, cfg->loading);
+    GSS_REQUIRE(ctx, cfg->ref_channel >= -1 && cfg->ref_channel < D, GSS_ERR_INVALID,
+                "%s: ref_channel = %d outside [-1, %d)", what, (int)cfg->ref_channel, D);
+    // (the whole-window pass that picks the channel is the reference's beamformer)
+    if (cfg->ref_channel < 0) GSS_TRY(check_bf_channels(ctx, D));
+    return GSS_OK;
+}
+
+static int check_mvdr_online_state(gss_ctx *ctx, const char *what, const gss_mvdr_online_state *s,
+                                   int F, int D) {
+    GSS_REQUIRE(ctx, s->phi_x, GSS_ERR_INVALID, "%s: state->phi_x is NULL", what);
+    GSS_REQUIRE(ctx, s->phi_n, GSS_ERR_INVALID, "%s: state->phi_n is NULL", what);
+    GSS_REQUIRE(ctx, s->phi_x != s->phi_n, GSS_ERR_INVALID, "%s: state->phi_x and state->phi_n alias",
+                what);
+    GSS_REQUIRE(ctx, s->F == F && s->D == D, GSS_ERR_INVALID,
+                "%s: state of F = %d, D = %d in a call of F = %d, D = %d", what, (int)s->F, (int)s->D,
+                F, D);
+    return GSS_OK;
+}
+
+extern "C" int gss_mvdr_online_init(gss_ctx *ctx, int F, int D, const gss_cplx *Y, int64_t T,
+                                    double loading, gss_mvdr_online_state *state) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_mvdr_online_init";
+    GSS_REQUIRE(ctx, state, GSS_ERR_INVALID, "%s: state is NULL", what);
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F = %d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED, "%s: D = %d outside [1, %d]",
+                what, D, GSS_MAX_CHANNELS);
+    GSS_REQUIRE(ctx, T >= 0, GSS_ERR_INVALID, "%s: T = %lld is negative", what, (long long)T);
+    GSS_REQUIRE(ctx, std::isfinite(loading) && loading > 0.0, GSS_ERR_INVALID,
+                "%s: loading = %g is not finite and > 0", what, loading);
+    GSS_TRY(check_mvdr_online_state(ctx, what, state, F, D));
+    if (Y && T > 0) GSS_TRY(check_stft_bins(ctx, F, T, D));
+    return mvdr_online_init_run(ctx, F, D, reinterpret_cast<const cplx *>(Y), Y ? T : 0, loading,
+                                reinterpret_cast<cplx *>(state->phi_x),
+                                reinterpret_cast<cplx *>(state->phi_n));
+}
+
+extern "C" int gss_mvdr_online(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                               const double *mx, const double *mn, int ban, const gss_bf_online *cfg,
+                               gss_mvdr_online_state *state, gss_cplx *Xhat, gss_cplx *W) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_mvdr_online";
+    GSS_REQUIRE(ctx, Y, GSS_ERR_INVALID, "%s: Y_dev is NULL", what);
+    GSS_REQUIRE(ctx, mx, GSS_ERR_INVALID, "%s: mask_x_dev is NULL", what);
+    GSS_REQUIRE(ctx, mn, GSS_ERR_INVALID, "%s: mask_n_dev is NULL", what);
+    GSS_REQUIRE(ctx, Xhat, GSS_ERR_INVALID, "%s: Xhat_dev is NULL", what);
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F = %d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, T >= 0, GSS_ERR_INVALID, "%s: T = %lld is negative", what, (long long)T);
+    GSS_TRY(check_bf_online(ctx, what, cfg, D));
+    if (state) GSS_TRY(check_mvdr_online_state(ctx, what, state, F, D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
+    if (T == 0) return GSS_OK;
+    GSS_TRY(arena_reserve(ctx, mvdr_online_workspace_bytes(F, T, D, state == nullptr,
+                                                           cfg->ref_channel < 0)));
+    return mvdr_online_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mx, mn, ban != 0,
+                           cfg->forget, cfg->loading, cfg->ref_channel,
+                           state ? reinterpret_cast<cplx *>(state->phi_x) : nullptr,
+                           state ? reinterpret_cast<cplx *>(state->phi_n) : nullptr,
+                           reinterpret_cast<cplx *>(Xhat), T, 1, reinterpret_cast<cplx *>(W));
+}
+
+extern "C" int gss_last_mvdr_online_fallbacks(gss_ctx *ctx, int64_t *count) {
+    return read_status_word(ctx, GSS_STATUS_MVDR_ONLINE_FALLBACKS, count,
+                            "gss_last_mvdr_online_fallbacks");
+}
+
 extern "C" int gss_wpe_weighted(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D, int taps,
                                 int delay, const double *weights, gss_cplx *X) {
     GSS_ENTER_VARIANTS(ctx);
@@ -1587,6 +1662,7 @@ struct PipelineCall {
     const gss_bf_lcmv *lcmv = nullptr;               // the interferer-nulling beamformer
     const gss_bf_wpd *wpd = nullptr;                 // the WPD beamformer
     const gss_wpe_online_cfg *wpe_online = nullptr;  // the online WPE in the place of the offline one
+    const gss_bf_online *bf_online = nullptr;        // the online MVDR in the place of the whole-window one
     PipelineActivity activity;
     // gss_separate_observation: the EM is the one with a frequency-shared prior, started from
     // this (K,T) table with no mask, in the place of the activity-guided one
@@ -1624,6 +1700,9 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
     if (call.wpe_online && p->wpe)
         stage = std::max(stage, wpe_online_workspace_bytes(F, T, wpe_arrays_of(p), D / wpe_arrays_of(p),
                                                            p->wpe_taps, p->wpe_delay, true));
+    // (online MVDR: the state of a fresh call, and the whole-window pass that picks the channel)
+    if (call.bf_online)
+        stage = std::max(stage, mvdr_online_workspace_bytes(F, T, D, true, call.bf_online->ref_channel < 0));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
     if (call.activity.scores)
         stage = std::max(stage, pact_workspace_bytes(F, T, K));   // the partial planes
@@ -1904,6 +1983,11 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
         GSS_TRY(lcmv_run(ctx, X, F, T, D, mx, mi, mnn, /*ban=*/1, /*forced_ref=*/-1,
                          call.lcmv->min_mass, Xhat, ref));
         GSS_TRY(arena_release(ctx, mark));
+    } else if (call.bf_online) {   // (bf == 0, checked by the entry point); Xhat is (T,F)
+        GSS_TRY(mvdr_online_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, call.bf_online->forget,
+                                call.bf_online->loading, call.bf_online->ref_channel, nullptr, nullptr,
+                                Xhat, 1, F, nullptr, ref));
+        GSS_TRY(arena_release(ctx, mark));
     } else if (call.seg) {   // (bf == 0, checked by the entry point)
         GSS_TRY(mvdr_segments_run(ctx, X, F, T, D, mx, mn, /*ban=*/1, *call.seg, Xhat, ref));
         GSS_TRY(arena_release(ctx, mark));
@@ -2104,6 +2188,37 @@ extern "C" int gss_enhance_observation_wpe_online(gss_ctx *ctx, const gss_params
     PipelineCall call;
     call.entry = what;
     call.wpe_online = cfg;
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
+}
+
+extern "C" int gss_enhance_observation_bf_online(gss_ctx *ctx, const gss_params *p,
+                                                 const double *obs, int D, int64_t N,
+                                                 const uint8_t *act, int K, int64_t N_act,
+                                                 int target, int64_t start_ctx, int64_t end_ctx,
+                                                 const gss_bf_online *cfg, double *out,
+                                                 const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *const what = "gss_enhance_observation_bf_online";
+    GSS_REQUIRE(ctx, p, GSS_ERR_INVALID, "%s: params is NULL", what);
+    GSS_TRY(check_bf_online(ctx, what, cfg, D));
+    GSS_REQUIRE(ctx, p->bf == 0, GSS_ERR_UNSUPPORTED,
+                "%s: bf=%d, only 0 ('mvdrSouden_ban') has an online form", what, p->bf);
+    PipelineCall call;
+    call.entry = what;
+    call.bf_online = cfg;
+    gss_wpe_online_cfg wpe_cfg{cfg->wpe_alpha};
+    if (cfg->wpe_online) {
+        GSS_REQUIRE(ctx, p->wpe, GSS_ERR_INVALID, "%s: wpe = 0, there is no WPE stage to replace",
+                    what);
+        GSS_REQUIRE(ctx, p->wpe_psd_context == 0, GSS_ERR_INVALID,
+                    "%s: wpe_psd_context = %d, the online WPE has no PSD context", what,
+                    p->wpe_psd_context);
+        GSS_TRY(check_wpe_arrays(ctx, p, D));
+        GSS_TRY(check_wpe_online(ctx, what, 1, wpe_arrays_of(p), D / wpe_arrays_of(p), p->wpe_taps,
+                                 p->wpe_delay, cfg->wpe_alpha));
+        call.wpe_online = &wpe_cfg;
+    }
     return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
                                     out, taps, call);
 }

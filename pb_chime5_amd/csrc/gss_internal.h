@@ -68,6 +68,13 @@ __device__ __forceinline__ void c_cfma(cplx &acc, cplx a, cplx b) {
     acc.y = fma(a.x, b.y, acc.y);
     acc.y = fma(-a.y, b.x, acc.y);
 }
+// a conj(b) with every product rounded on its own: c_outer(b, a) is its exact conjugate, and
+// c_outer(a, a) is exactly real (the Hermitian running sums of the online WPE and MVDR).
+__device__ __forceinline__ cplx c_outer(cplx a, cplx b) {
+#pragma clang fp contract(off)
+    const double xx = a.x * b.x, yy = a.y * b.y, yx = a.y * b.x, xy = a.x * b.y;
+    return c_make(xx + yy, yx - xy);
+}
 
 // Barrier for code that is run by ONE wavefront on data in LDS (the lanes of a wave issue
 // their LDS operations in order, so only the compiler has to be kept from reordering).
@@ -192,6 +199,8 @@ struct gss_ctx {
     // (copied from the device counter by lcmv_run).
     // [6]: pivots zeroed by the WPE steps of the last WPD call (wpe_run with the caller's weights).
     // [7]: frequencies whose row the last gss_cacgmm_align left off the identity (align_moved_kernel).
+    // [8]: (frequency, frame) pairs of the last online MVDR call whose Phi_N had no Cholesky factor
+    // (copied from the device counter by mvdr_online_run).
     // [GSS_STATUS_TARGETS + s]: target s of the last targets call (mvdr_apply_targets_kernel,
     // which writes target 0's word to [0] as well).
     int32_t *status_host = nullptr;
@@ -218,6 +227,7 @@ struct gss_ctx {
 #define GSS_STATUS_LCMV_FALLBACKS 5
 #define GSS_STATUS_WPD_ZERO_PIVOTS 6                             // pivots zeroed by the last WPD call
 #define GSS_STATUS_ALIGN_MOVED 7                                 // rows the last alignment left off the identity
+#define GSS_STATUS_MVDR_ONLINE_FALLBACKS 8                        // fallback frames of the last online MVDR call
 #define GSS_STATUS_TARGETS 16                                   // first per-target word
 #define GSS_STATUS_CHANNELS 40                                   // first selected-channel word
 #define GSS_STATUS_BYTES (4 * (GSS_STATUS_CHANNELS + GSS_MAX_CHANNELS))
@@ -537,6 +547,21 @@ int wpe_online_init_run(gss_ctx *ctx, int F, int A, int C, int taps, int delay, 
                         cplx *hist);
 int wpe_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int A, int C, int taps, int delay,
                    double alpha, cplx *P, cplx *G, cplx *hist, cplx *X, bool force_mem);
+
+// Online MVDR (mvdr_online.hip; include/gss_hip.h: gss_mvdr_online).  Y (F,T,D), masks (F,T) ->
+// X, element (f, t) at [f xs_f + t xs_t], and the filters W (F,T,D) or NULL; phi_x, phi_n (F,D,D)
+// the caller's state, advanced in place, both NULL: a fresh one from the arena, initialised from Y
+// with `loading` and thrown away.  ref < 0: the reference channel of mvdr_run over the call's
+// frames (window_ref in the workspace formula).  The fallback frames go to status word
+// GSS_STATUS_MVDR_ONLINE_FALLBACKS, the reference channel to word 0.  Arguments validated by the
+// entry point, T >= 1.
+size_t mvdr_online_workspace_bytes(int F, int64_t T, int D, bool fresh, bool window_ref);
+int mvdr_online_init_run(gss_ctx *ctx, int F, int D, const cplx *Y, int64_t T, double loading,
+                         cplx *phi_x, cplx *phi_n);
+int mvdr_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
+                    const double *mn, int ban, double beta, double loading, int ref, cplx *phi_x,
+                    cplx *phi_n, cplx *X, int64_t xs_f, int64_t xs_t, cplx *W,
+                    int32_t *ref_out = nullptr);
 
 int selftest_mfma_run(gss_ctx *ctx);
 

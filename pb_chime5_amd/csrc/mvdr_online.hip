@@ -1,0 +1,317 @@
+// Online MVDR: Souden's mask-based MVDR (optionally with blind analytic normalisation) whose
+// statistics are exponentially forgetting running sums and whose filter is recomputed at every
+// frame (include/gss_hip.h: gss_mvdr_online).  Per frequency, for every
+// frame t in order, with y = Y[f,t,:], a = mask_x[f,t], b = mask_n[f,t]:
+//   Phi_X <- beta Phi_X + a y y^H,   Phi_N <- beta Phi_N + b y y^H
+//   Phi_N = U^H U (a pivot that is not > 0 or not finite: a FALLBACK frame -- w = 0, X = 0, the
+//   frame is counted, the update above stays)
+//   w = (Phi_N^-1 Phi_X)[:, ref] / max(Re trace(Phi_N^-1 Phi_X), 1e-10)
+//   ban:  v = Phi_N w,  w <- w sqrt(v^H v) / |w^H v|   (w^H v = 0, a zero filter: w stays 0)
+//   X[f,t] = w^H y                       (the sums include frame t: causal, no look-ahead)
+// Only the two running sums are a recurrence in time, but the factorisation of frame t needs the
+// sums of frame t, so one persistent wave per frequency walks the frames of the call with both
+// matrices in LDS.  Per frame: the rank-one update on the 8 x 8 lane grid, chol_inverse_sweep
+// (dense_wave.h; U and W = U^-H = L^-1 in one register-resident pass of D steps), then with
+// Phi_N^-1 = W^H W
+//   B  = W Phi_X (lower triangle and column ref only),  tr = sum_{i >= k} Re(B_ik conj(W_ik)),
+//   w  = W^H B[:, ref] / max(tr, 1e-10)
+// -- no explicit Psi and no triangular substitutions.  The form (the template argument NR =
+// ceil(D / 8), the leading dimension 8 NR + 1) and every order of summation depend on D alone,
+// never on T, F or where a call begins: a recording fed in blocks gives the bits of one call.
+// Both sums keep the FULL Hermitian matrix; (i, j) and (j, i) are updated with operations that
+// commute with conjugation (c_outer, real scalings), so the lower triangle stays the exact
+// conjugate of the upper one and the diagonal exactly real.  No floating-point atomics.
+#include "dense_wave.h"
+
+namespace {
+
+struct MolArgs {
+    const cplx *Y;           // (F, T, D)
+    const double *mx, *mn;   // (F, T)
+    cplx *phi_x, *phi_n;     // (F, D, D)
+    cplx *X;                 // element (f, t) at [f xs_f + t xs_t]
+    int64_t xs_f, xs_t;
+    cplx *W;                 // (F, T, D) or NULL
+    const int32_t *ref_dev;  // the reference channel of a whole-window pass, NULL: `ref`
+    int32_t *fallbacks;      // the call's device counter
+    int32_t *status;         // status word of the reference channel
+    int32_t *ref_out;        // the reference channel used, or NULL
+    int64_t T;
+    int D, ref, ban;
+    double beta;
+};
+
+// p_f = mean |Y[f]|^2 over the T D values handed in (1 when there are none or the mean is 0),
+// Phi_X = 0, Phi_N = loading p_f I.  Thread j sums the values j, j + 256, ... in ascending
+// order, the 256 partial sums are added by a fixed tree.
+__global__ __launch_bounds__(256) void mvdr_online_init_kernel(const cplx *__restrict__ Y, int64_t T,
+                                                               int D, double loading,
+                                                               cplx *__restrict__ phi_x,
+                                                               cplx *__restrict__ phi_n) {
+    __shared__ double part[256];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int64_t total = Y ? T * D : 0;
+    double acc = 0.0;
+    for (int64_t i = tid; i < total; i += 256) {
+        const cplx v = Y[(int64_t)f * total + i];
+        acc = fma(v.x, v.x, acc);
+        acc = fma(v.y, v.y, acc);
+    }
+    part[tid] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) part[tid] += part[tid + s];
+        __syncthreads();
+    }
+    double p = total > 0 ? part[0] / (double)total : 1.0;
+    if (p == 0.0) p = 1.0;
+    const double delta = loading * p;
+    for (int idx = tid; idx < D * D; idx += 256) {
+        const int r = idx / D, c = idx - r * D;
+        phi_x[(int64_t)f * D * D + idx] = c_make(0.0, 0.0);
+        phi_n[(int64_t)f * D * D + idx] = c_make(r == c ? delta : 0.0, 0.0);
+    }
+}
+
+// A state handed in is read from its upper triangle and the real part of its diagonal.
+__device__ __forceinline__ void mol_load(const cplx *__restrict__ g, cplx *m, int D, int ld, int lane) {
+    for (int idx = lane; idx < D * D; idx += 64) {
+        const int r = idx / D, c = idx - r * D;
+        cplx v = r <= c ? g[idx] : c_conj(g[c * D + r]);
+        if (r == c) v.y = 0.0;
+        m[r * ld + c] = v;
+    }
+}
+
+// One wave per frequency; lane (ty, tx) = (lane >> 3, lane & 7) owns the entries (ty + 8 a,
+// tx + 8 b) of both sums and of the sweep's register tile.  LDS: Phi_X, Phi_N and the sweep's
+// rows M, each D rows of ld = 8 NR + 1 complex values (odd: the lanes that walk a column fall on
+// different 16-byte slots), y, B[:, ref], w and the sweep's 1 / U_jj.  y and the two mask values
+// of frame t + 1 are fetched while frame t's dependent chain runs.
+template <int NR>
+__global__ __launch_bounds__(64) void mvdr_online_kernel(MolArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int ld = 8 * NR + 1;
+    const int D = a.D;
+    cplx *PX = reinterpret_cast<cplx *>(smem);
+    cplx *PN = PX + D * ld;
+    cplx *M = PN + D * ld;
+    cplx *yb = M + D * ld;      // 8 NR each
+    cplx *cb = yb + 8 * NR;
+    cplx *wb = cb + 8 * NR;
+    double *dinv = reinterpret_cast<double *>(wb + 8 * NR);
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int tx = lane & 7, ty = lane >> 3;
+    const bool row = lane < D;
+    const int64_t T = a.T;
+    const cplx zero = c_make(0.0, 0.0);
+    const cplx *Yf = a.Y + (int64_t)f * T * D;
+    const double *mxf = a.mx + (int64_t)f * T, *mnf = a.mn + (int64_t)f * T;
+    cplx *Xf = a.X + (int64_t)f * a.xs_f;
+    cplx *Wf = a.W ? a.W + (int64_t)f * T * D : nullptr;
+    cplx *gx = a.phi_x + (int64_t)f * D * D, *gn = a.phi_n + (int64_t)f * D * D;
+
+    const int ref = a.ref_dev ? a.ref_dev[0] : a.ref;
+    if (f == 0 && lane == 0) {
+        __hip_atomic_store(a.status, ref < 0 ? -1 : ref, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (a.ref_out) a.ref_out[0] = ref < 0 ? -1 : ref;
+    }
+    if (ref < 0) {   // the whole-window pass found no finite SNR: as mvdr_apply_kernel, state untouched
+        const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+        for (int64_t t = lane; t < T; t += 64) Xf[t * a.xs_t] = c_make(qnan, qnan);
+        if (Wf)
+            for (int64_t i = lane; i < T * D; i += 64) Wf[i] = c_make(qnan, qnan);
+        return;
+    }
+    mol_load(gx, PX, D, ld, lane);
+    mol_load(gn, PN, D, ld, lane);
+    wave_sync();
+
+    const double beta = a.beta;
+    cplx y_next = row ? Yf[lane] : zero;
+    double ma_next = mxf[0], mb_next = mnf[0];
+    int nfall = 0;
+    for (int64_t t = 0; t < T; ++t) {
+        const cplx y = y_next;
+        const double ma = ma_next, mb = mb_next;
+        if (row) yb[lane] = y;
+        if (t + 1 < T) {
+            if (row) y_next = Yf[(t + 1) * D + lane];
+            ma_next = mxf[t + 1];
+            mb_next = mnf[t + 1];
+        }
+        wave_sync();
+        // the two running sums; the sweep's tile is the upper triangle of the new Phi_N
+        cplx reg[NR][NR];
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai)
+#pragma unroll
+            for (int bi = 0; bi < NR; ++bi) {
+                const int i = ty + 8 * ai, k = tx + 8 * bi;
+                reg[ai][bi] = zero;
+                if (i < D && k < D) {
+                    const cplx o = c_outer(yb[i], yb[k]);
+                    const cplx px = PX[i * ld + k], pn = PN[i * ld + k];
+                    PX[i * ld + k] = c_make(fma(beta, px.x, ma * o.x), fma(beta, px.y, ma * o.y));
+                    const cplx nn = c_make(fma(beta, pn.x, mb * o.x), fma(beta, pn.y, mb * o.y));
+                    PN[i * ld + k] = nn;
+                    if (k >= i) reg[ai][bi] = nn;
+                }
+            }
+        wave_sync();
+        const bool ok = chol_inverse_sweep<8, NR, true>(reg, D, M, ld, dinv, tx, ty);
+        cplx w = zero, x = zero;
+        if (!ok) {   // decided by the pivots alone, the same in every lane
+            ++nfall;
+        } else {
+            // M: row i holds W[i][k] / dinv[i] for k < i; W[i][i] = dinv[i].
+            // B[i][k] = dinv[i] (sum_{j<i} M[i][j] Phi_X[j][k] + Phi_X[i][k])
+            double trp = 0.0;
+#pragma unroll
+            for (int ai = 0; ai < NR; ++ai) {
+                const int i = ty + 8 * ai;
+                if (i < D) {
+                    cplx acc[NR];
+#pragma unroll
+                    for (int bi = 0; bi <= ai; ++bi) acc[bi] = zero;
+                    for (int j = 0; j < i; ++j) {
+                        const cplx m = M[i * ld + j];
+#pragma unroll
+                        for (int bi = 0; bi <= ai; ++bi) c_fma(acc[bi], m, PX[j * ld + min(tx + 8 * bi, D - 1)]);
+                    }
+                    const double d2 = dinv[i] * dinv[i];
+#pragma unroll
+                    for (int bi = 0; bi <= ai; ++bi) {
+                        const int k = tx + 8 * bi;
+                        if (k <= i) {
+                            const cplx bu = c_add(acc[bi], PX[i * ld + k]);
+                            const cplx m = k < i ? M[i * ld + k] : c_make(1.0, 0.0);
+                            trp = fma(d2, fma(bu.x, m.x, bu.y * m.y), trp);
+                        }
+                    }
+                }
+            }
+            // cb[i] = dinv[i] B[i][ref]
+            if (row) {
+                cplx acc = zero;
+                for (int j = 0; j < lane; ++j) c_fma(acc, M[lane * ld + j], PX[j * ld + ref]);
+                acc = c_add(acc, PX[lane * ld + ref]);
+                cb[lane] = c_scale(acc, dinv[lane] * dinv[lane]);
+            }
+            const double tr = wave_sum(trp);
+            wave_sync();
+            // w[k] = sum_{i >= k} conj(W[i][k]) B[i][ref] / max(tr, eps)
+            if (row) {
+                cplx acc = cb[lane];
+                for (int i = lane + 1; i < D; ++i) c_cfma(acc, M[i * ld + lane], cb[i]);
+                w = c_scale(acc, 1.0 / fmax(tr, 1e-10));
+            }
+            if (a.ban) {
+                if (row) wb[lane] = w;
+                wave_sync();
+                cplx v = zero;     // (Phi_N w)[i], from column i of the Hermitian matrix
+                if (row)
+                    for (int k = 0; k < D; ++k) c_cfma(v, PN[k * ld + lane], wb[k]);
+                const double vv = wave_sum(fma(v.x, v.x, v.y * v.y));
+                cplx wv = zero;
+                c_cfma(wv, w, v);
+                const double wr = wave_sum(wv.x), wi = wave_sum(wv.y);
+                // eps = 0 as upstream, but a filter that is exactly zero (no target mass yet: the
+                // context frames of every window) stays zero where upstream divides 0 by 0
+                const double den = hypot(wr, wi);
+                w = c_scale(w, den == 0.0 ? 0.0 : sqrt(vv) / den);
+            }
+            cplx p = zero;
+            c_cfma(p, w, y);
+            x = c_make(wave_sum(p.x), wave_sum(p.y));
+        }
+        if (lane == 0) Xf[t * a.xs_t] = x;
+        if (Wf && row) Wf[t * D + lane] = w;
+    }
+    wave_sync();
+    for (int idx = lane; idx < D * D; idx += 64) {
+        const int r = idx / D, c = idx - r * D;
+        gx[idx] = PX[r * ld + c];
+        gn[idx] = PN[r * ld + c];
+    }
+    if (lane == 0 && nfall) atomicAdd(a.fallbacks, nfall);
+}
+
+size_t mol_lds_bytes(int D) {
+    const size_t nr = (size_t)(D + 7) / 8, ld = 8 * nr + 1;
+    return sizeof(cplx) * (3 * (size_t)D * ld + 3 * 8 * nr) + sizeof(double) * 8 * nr;
+}
+
+}  // namespace
+
+// for a thrown-away state its two matrices, the counter, and for ref_channel = -1 the
+// whole-window pass with the output it is not asked for
+size_t mvdr_online_workspace_bytes(int F, int64_t T, int D, bool fresh, bool window_ref) {
+    size_t b = align_up(sizeof(int32_t) * 4);
+    if (fresh) b += 2 * align_up(sizeof(cplx) * (size_t)F * D * D);
+    if (window_ref) b += mvdr_workspace_bytes(F, T, D) + align_up(sizeof(cplx) * (size_t)F * T);
+    return b + 4096;
+}
+
+int mvdr_online_init_run(gss_ctx *ctx, int F, int D, const cplx *Y, int64_t T, double loading,
+                         cplx *phi_x, cplx *phi_n) {
+    GSS_PROF(ctx, "mvdr_online_init");
+    hipLaunchKernelGGL(mvdr_online_init_kernel, dim3(F), dim3(256), 0, ctx->stream,
+                       T > 0 ? Y : nullptr, T, D, loading, phi_x, phi_n);
+    GSS_LAUNCH_CHECK(ctx, "mvdr_online_init_kernel");
+    return GSS_OK;
+}
+
+// phi_x, phi_n: the caller's state, advanced in place; both NULL: a fresh state from the arena,
+// initialised from Y with `loading`, thrown away.  X: element (f, t) at [f xs_f + t xs_t].
+// ref < 0: the reference channel of the whole-window beamformer over the call's frames;
+// ref_out: receives the channel used.  The
+// arguments have been validated by the entry point (T >= 1).
+int mvdr_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
+                    const double *mn, int ban, double beta, double loading, int ref, cplx *phi_x,
+                    cplx *phi_n, cplx *X, int64_t xs_f, int64_t xs_t, cplx *W,
+                    int32_t *ref_out) {
+    int32_t *words = arena_alloc_t<int32_t>(ctx, 4);   // [0]: fallback counter, [1]: the window's ref
+    GSS_REQUIRE(ctx, words, GSS_ERR_NOMEM, "online MVDR workspace");
+    if (!phi_x) {
+        phi_x = arena_alloc_t<cplx>(ctx, (size_t)F * D * D);
+        phi_n = arena_alloc_t<cplx>(ctx, (size_t)F * D * D);
+        GSS_REQUIRE(ctx, phi_x && phi_n, GSS_ERR_NOMEM, "online MVDR workspace");
+        GSS_TRY(mvdr_online_init_run(ctx, F, D, Y, T, loading, phi_x, phi_n));
+    }
+    ctx->last_targets = 0;
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(words, 0, sizeof(int32_t) * 4, ctx->stream));
+    const int32_t *ref_dev = nullptr;
+    if (ref < 0) {
+        const size_t mark = ctx->arena_off;
+        cplx *Xw = arena_alloc_t<cplx>(ctx, (size_t)F * T);
+        GSS_REQUIRE(ctx, Xw, GSS_ERR_NOMEM, "online MVDR workspace");
+        GSS_TRY(mvdr_run(ctx, Y, F, T, D, mx, mn, ban, Xw, words + 1));
+        GSS_TRY(arena_release(ctx, mark));
+        ref_dev = words + 1;
+    }
+    MolArgs a{Y, mx, mn, phi_x, phi_n, X, xs_f, xs_t, W, ref_dev, words, ctx->status_dev, ref_out,
+              T, D, ref, ban, beta};
+    {
+        GSS_PROF(ctx, "mvdr_online");
+        const size_t lds = mol_lds_bytes(D);
+#define GSS_MOL_LAUNCH(NR)                                                                         \
+    do {                                                                                           \
+        if (lds > 48 * 1024)                                                                       \
+            GSS_HIP_CHECK(ctx, hipFuncSetAttribute(                                                \
+                                   reinterpret_cast<const void *>(mvdr_online_kernel<NR>),         \
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));         \
+        hipLaunchKernelGGL(mvdr_online_kernel<NR>, dim3(F), dim3(64), lds, ctx->stream, a);        \
+    } while (0)
+        if (D <= 8) GSS_MOL_LAUNCH(1);
+        else if (D <= 16) GSS_MOL_LAUNCH(2);
+        else if (D <= 24) GSS_MOL_LAUNCH(3);
+        else GSS_MOL_LAUNCH(4);
+#undef GSS_MOL_LAUNCH
+        GSS_LAUNCH_CHECK(ctx, "mvdr_online_kernel");
+    }
+    // the count of this call -> the context's status word
+    GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_MVDR_ONLINE_FALLBACKS, words,
+                                      sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return GSS_OK;
+}

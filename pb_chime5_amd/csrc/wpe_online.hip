@@ -15,7 +15,7 @@
 //   memory  (n <= 512): four waves per problem, P, G stay in their HBM buffers; the update of P
 //     by frame t and the product P_{t+1} w_{t+1} share one pass over the matrix.
 // Both keep the FULL Hermitian matrix and update (i, j) and (j, i) with operations that commute
-// with conjugation (wol_outer: no fused multiply-add in the product nom_i conj(nom_j)), so the
+// with conjugation (c_outer: no fused multiply-add in the product nom_i conj(nom_j)), so the
 // lower triangle stays the exact conjugate of the upper one and the diagonal exactly real -- a
 // state written back is the state held, and a call continued from it continues bit for bit.
 // No atomics, every sum in one fixed order: the same call gives the same bits.
@@ -50,17 +50,9 @@ __device__ __forceinline__ cplx wol_frame(const WolArgs &a, int f, int arr, int6
     return a.hist[((int64_t)(f * a.A + arr) * a.L + (a.L + s)) * a.C + c];
 }
 
-// a conj(b) with every product rounded on its own: wol_outer(b, a) is its exact conjugate, and
-// wol_outer(a, a) is exactly real.
-__device__ __forceinline__ cplx wol_outer(cplx a, cplx b) {
-#pragma clang fp contract(off)
-    const double xx = a.x * b.x, yy = a.y * b.y, yx = a.y * b.x, xy = a.x * b.y;
-    return c_make(xx + yy, yx - xy);
-}
-
 // (p - nom_i conj(nom_j) / den) / alpha; commutes with conjugation
 __device__ __forceinline__ cplx wol_downdate(cplx p, cplx ni, cplx nj, double rden, double inv_alpha) {
-    const cplx o = wol_outer(ni, nj);
+    const cplx o = c_outer(ni, nj);
     return c_make(fma(-o.x, rden, p.x) * inv_alpha, fma(-o.y, rden, p.y) * inv_alpha);
 }
 

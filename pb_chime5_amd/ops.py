@@ -27,6 +27,9 @@ here                        reference call (file:line)
                             `Enhancer.enhance_recording_blind` is built of; not in the reference)
 ``mvdr_souden_from_masks``  pb_bss beamformer chain       (beamforming_wrapper.py:51-97)
 ``mvdr_souden_segments_from_masks``  the same with statistics per segment of frames
+``mvdr_souden_online_from_masks`` / ``OnlineMVDRState`` / ``enhance_observation_bf_online``
+                            the same with exponentially forgetting running sums, a filter per
+                            frame and a carried state (not in the reference)
 ``lcmv_souden_from_masks``  beamform_lcmv_souden_from_masks (beamforming_wrapper.py:127-171)
 ``lcmv_masks_from_posteriors`` / ``enhance_observation_lcmv``
                             the interferer-nulling LCMV fed from the posteriors
@@ -48,8 +51,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import (Context, GssBfLcmv, GssBfSegments, GssBfWpd, GssCacgmmModel, GssChannelSelect,
-                    GssDebugTaps, GssGuidance, GssParams, GssWpeOnlineCfg, GssWpeOnlineState,
-                    c_void_p, default_context)
+                    GssBfOnline, GssDebugTaps, GssGuidance, GssMvdrOnlineState, GssParams,
+                    GssWpeOnlineCfg, GssWpeOnlineState, c_void_p, default_context)
 from .cacgmm import CACGMM
 
 _BF_CODES = {'mvdrSouden_ban': 0, 'ch2': 1, 'sum': 2, 'gev_ban': 3}
@@ -1137,6 +1140,177 @@ def mvdr_souden_segments_from_masks(Y, X_mask, N_mask, ban=False, *, segment_fra
     return out if len(out) > 1 else out[0]
 
 
+# --------------------------------------------------------------------------
+# online MVDR (gss_mvdr_online): frame-recursive Souden MVDR with a carried state
+# --------------------------------------------------------------------------
+# Both defaults are choices, not measurements: 0.99 is a memory of
+# 1 / (1 - 0.99) = 100 frames, 1.6 s at the 16 ms frame shift; the loading is relative to the mean
+# power of the frames the state is initialised from.
+BF_ONLINE_FORGET = 0.99
+BF_ONLINE_LOADING = 1e-2
+
+
+def check_bf_online(forget=BF_ONLINE_FORGET, loading=BF_ONLINE_LOADING, ref_channel=0,
+                    num_channels=None):
+    """The settings of the online MVDR -- the one place that validates them, before any device
+    work.  ValueError naming the argument: ``forget`` a finite number in (0, 1], ``loading`` a
+    finite number > 0, ``num_channels`` an integer in [1, 32], ``ref_channel`` an integer in
+    [-1, num_channels) (-1: the whole-window beamformer's choice over the call's frames, which
+    needs fewer than 30 channels like that beamformer).  Returns (forget, loading, ref_channel)."""
+    if not _is_real(forget) or not np.isfinite(forget) or not 0 < forget <= 1:
+        raise ValueError(f'forget={forget!r}: a finite number in (0, 1]')
+    if not _is_real(loading) or not np.isfinite(loading) or not loading > 0:
+        raise ValueError(f'loading={loading!r}: a finite number > 0')
+    if num_channels is not None and (not _is_integer(num_channels)
+                                     or not 1 <= num_channels <= _MAX_CHANNELS):
+        raise ValueError(f'num_channels={num_channels!r}: an integer in [1, {_MAX_CHANNELS}]')
+    if not _is_integer(ref_channel) or ref_channel < -1 or (
+            num_channels is not None and ref_channel >= num_channels):
+        raise ValueError(f'ref_channel={ref_channel!r}: an integer in [-1, '
+                         f'{"num_channels" if num_channels is None else num_channels})')
+    if ref_channel == -1 and num_channels is not None and num_channels >= 30:
+        raise ValueError(f'ref_channel=-1 on num_channels={num_channels}: the whole-window '
+                         'beamformer that picks the channel asserts D < 30')
+    return float(forget), float(loading), int(ref_channel)
+
+
+def _bf_online_cfg(forget, loading, ref_channel, wpe_online=False, wpe_alpha=WPE_ONLINE_ALPHA):
+    return GssBfOnline(forget=forget, loading=loading, ref_channel=ref_channel,
+                       wpe_online=int(bool(wpe_online)), wpe_alpha=float(wpe_alpha))
+
+
+class OnlineMVDRState:
+    """The state of the online MVDR in HBM (gss_mvdr_online_state), caller-owned like an
+    `OnlineWPEState`: the running sums phi_x and phi_n (F,D,D), complex128, Hermitian."""
+
+    def __init__(self, ctx, F, D):
+        self.ctx = ctx
+        self.F, self.D = int(F), int(D)
+        self.shapes = {'phi_x': (self.F, self.D, self.D), 'phi_n': (self.F, self.D, self.D)}
+        self.bufs = {k: ctx.empty(16 * self.F * self.D * self.D) for k in self.shapes}
+
+    @property
+    def key(self):
+        return self.F, self.D
+
+    def struct(self):
+        return GssMvdrOnlineState(phi_x=self.bufs['phi_x'].ptr, phi_n=self.bufs['phi_n'].ptr,
+                                  F=self.F, D=self.D)
+
+    @classmethod
+    def fresh(cls, F, D, loading=BF_ONLINE_LOADING, Y=None, *, ctx=None):
+        """phi_x = 0, phi_n = loading * p_f * I (gss_mvdr_online_init); p_f is the mean power of
+        frequency f of ``Y`` (D,T,F), 1 without ``Y`` or where that mean is exactly 0."""
+        if not _is_integer(F) or F < 1:
+            raise ValueError(f'F={F!r}: a positive integer')
+        check_bf_online(loading=loading, num_channels=D)
+        T = 0
+        if Y is not None:
+            Y = np.asarray(Y)
+            if Y.ndim != 3 or Y.shape[0] != D or Y.shape[2] != F:
+                raise ValueError(f'Y: shape {Y.shape} is not (D,T,F) = ({D},T,{F})')
+            T = Y.shape[1]
+        ctx = ctx or default_context()
+        state = cls(ctx, F, D)
+        Y_d = _obs_to_device_ftd(ctx, Y)[0] if T > 0 else None
+        ctx._check(ctx.lib.gss_mvdr_online_init(
+            ctx.handle, state.F, state.D, c_void_p(Y_d.ptr) if Y_d is not None else None, T,
+            float(loading), ctypes.byref(state.struct())), 'gss_mvdr_online_init')
+        return state
+
+    def to_host(self):
+        """{'phi_x', 'phi_n'} as NumPy arrays: everything `from_host` needs (synchronises)."""
+        return {k: self.ctx.to_host(self.bufs[k], shape, np.complex128)
+                for k, shape in self.shapes.items()}
+
+    @classmethod
+    def from_host(cls, host, *, ctx=None):
+        """A device state from the dict of `to_host` (in any context: a state saved in one
+        process continues in another).  ValueError for shapes that do not fit each other."""
+        px = np.ascontiguousarray(host['phi_x'], dtype=np.complex128)
+        if px.ndim != 3 or px.shape[1] != px.shape[2]:
+            raise ValueError(f'phi_x: shape {px.shape} is not (F,D,D)')
+        F, D, _ = px.shape
+        if F < 1:
+            raise ValueError(f'phi_x: shape {px.shape} has no frequency')
+        check_bf_online(num_channels=D)
+        pn = np.ascontiguousarray(host['phi_n'], dtype=np.complex128)
+        if pn.shape != px.shape:
+            raise ValueError(f'phi_n: shape {pn.shape} is not {px.shape}')
+        ctx = ctx or default_context()
+        state = cls(ctx, F, D)
+        ctx.upload(state.bufs['phi_x'], px)
+        ctx.upload(state.bufs['phi_n'], pn)
+        return state
+
+    def copy(self):
+        """An independent state with the same bits, in the same context."""
+        return OnlineMVDRState.from_host(self.to_host(), ctx=self.ctx)
+
+
+def _check_online_mask(mask, name, T, F):
+    mask = np.asarray(mask, dtype=np.float64)
+    if mask.shape != (T, F):
+        raise ValueError(f'{name}: shape {mask.shape} is not (T,F) = ({T},{F})')
+    if not np.all(np.isfinite(mask)) or np.any(mask < 0):
+        raise ValueError(f'{name}: a mask value is negative or not finite')
+    return mask
+
+
+def mvdr_souden_online_from_masks(Y, X_mask, N_mask, ban=False, *, forget=BF_ONLINE_FORGET,
+                                  loading=BF_ONLINE_LOADING, ref_channel=0, state=None,
+                                  return_filters=False, return_fallbacks=False, ctx=None):
+    """The online MVDR (gss_mvdr_online): Y (D,T,F), 2-D masks (T,F) -> X_hat (T,F) complex128.
+    Both PSD matrices are running sums that forget at the rate ``forget``; the filter of frame t
+    is solved from the sums INCLUDING frame t (causal, no look-ahead).  ``state``: an
+    `OnlineMVDRState` to continue from, advanced IN PLACE by the T frames (feeding a recording in
+    blocks through one state gives the bits of one call); None: a fresh state initialised from
+    ``Y`` with ``loading``, thrown away.  ``ref_channel`` = -1: the whole-window beamformer's
+    choice over the call's frames (not causal; AssertionError when an SNR is not finite, like
+    there).  Returns X_hat, then with ``return_filters`` the filters (T,F,D), then with
+    ``return_fallbacks`` the number of (frequency, frame) pairs whose noise matrix had no Cholesky
+    factor (their X_hat and filter are 0)."""
+    Y = np.asarray(Y)
+    if Y.ndim != 3:
+        raise ValueError(f'Y: shape {Y.shape} is not (D,T,F)')
+    D, T, F = Y.shape
+    forget, loading, ref_channel = check_bf_online(forget, loading, ref_channel, D)
+    X_mask = _check_online_mask(X_mask, 'X_mask', T, F)
+    N_mask = _check_online_mask(N_mask, 'N_mask', T, F)
+    if state is not None:
+        if not isinstance(state, OnlineMVDRState):
+            raise ValueError(f'state: {type(state).__name__} is not an OnlineMVDRState')
+        if state.key != (F, D):
+            raise ValueError(f'state: built for (F, D) = {state.key}, the call has {(F, D)}')
+        if ctx is not None and ctx is not state.ctx:
+            raise ValueError('state: it lives in another context than ctx')
+        ctx = state.ctx
+    ctx = ctx or default_context()
+    fallbacks = 0
+    if T == 0 or F == 0:
+        X_hat, W = np.zeros((T, F), np.complex128), np.zeros((T, F, D), np.complex128)
+    else:
+        Y_d, _ = _obs_to_device_ftd(ctx, Y)
+        mx = _mask_to_device_ft(ctx, X_mask, T, F)
+        mn = _mask_to_device_ft(ctx, N_mask, T, F)
+        X_d = ctx.empty(16 * F * T)
+        W_d = ctx.empty(16 * F * T * D) if return_filters else None
+        cfg = _bf_online_cfg(forget, loading, ref_channel)
+        ctx._check(ctx.lib.gss_mvdr_online(
+            ctx.handle, c_void_p(Y_d.ptr), F, T, D, c_void_p(mx.ptr), c_void_p(mn.ptr),
+            int(bool(ban)), ctypes.byref(cfg),
+            ctypes.byref(state.struct()) if state is not None else None, c_void_p(X_d.ptr),
+            c_void_p(W_d.ptr) if W_d is not None else None), 'gss_mvdr_online')
+        _check_ref_channel(ctx)
+        X_hat = np.ascontiguousarray(ctx.to_host(X_d, (F, T), np.complex128).T)
+        W = (np.ascontiguousarray(ctx.to_host(W_d, (F, T, D), np.complex128).transpose(1, 0, 2))
+             if return_filters else None)
+        if return_fallbacks:
+            fallbacks = ctx.last_mvdr_online_fallbacks()
+    out = (X_hat,) + ((W,) if return_filters else ()) + ((fallbacks,) if return_fallbacks else ())
+    return out if len(out) > 1 else X_hat
+
+
 def check_bf_lcmv(num_classes, target_index, interferer=None, candidates=None, min_mass=None,
                   num_channels=None):
     """The settings of the interferer-nulling LCMV as a gss_bf_lcmv, or ValueError naming the
@@ -1812,6 +1986,7 @@ _FUSED_ENTRIES = {
     None: ('gss_enhance_observation', 'gss_enhance_observation_pcm16', 'plain'),
     'wpd': ('gss_enhance_observation_wpd', None, 'WPD'),
     'wpe_online': ('gss_enhance_observation_wpe_online', None, 'online WPE'),
+    'bf_online': ('gss_enhance_observation_bf_online', None, 'online MVDR'),
     'activity': ('gss_enhance_observation_activity', None, 'activity'),
     'lcmv': ('gss_enhance_observation_lcmv', None, 'LCMV'),
     'channel_select': ('gss_enhance_observation_select', 'gss_enhance_observation_select_pcm16',
@@ -1823,7 +1998,7 @@ _FUSED_ENTRIES = {
 def _enqueue_fused(ctx, params, obs_d, D, N, act_d, K, N_act, target_index, start_context,
                    end_context, out_d, taps=None, pcm=False, option=None, value=None):
     """The one place that issues a fused one-target call on inputs in HBM.  ``option``: a key of
-    `_FUSED_ENTRIES`; ``value``: the struct that entry takes (gss_bf_wpd, gss_wpe_online_cfg,
+    `_FUSED_ENTRIES`; ``value``: the struct that entry takes (gss_bf_wpd, gss_wpe_online_cfg, gss_bf_online,
     gss_bf_lcmv, gss_bf_segments, gss_channel_select), for 'activity' the device buffers (weights or None,
     scores, power or None).  ``pcm``: int16 samples, the entry's _pcm16 twin."""
     name, twin, label = _FUSED_ENTRIES[option]
@@ -1867,8 +2042,12 @@ class ResidentUtterance:
         self.out_d = ctx.empty(8 * max(self.n_out, 1))
 
     def enqueue(self, target_index, start_context, end_context, taps=None, segments=None,
-                channel_select=None, lcmv=None, activity=None, wpd=None, wpe_online=None):
-        """``wpe_online``: a gss_wpe_online_cfg for the online WPE in the place of the offline one
+                channel_select=None, lcmv=None, activity=None, wpd=None, wpe_online=None,
+                bf_online=None):
+        """``bf_online``: a gss_bf_online for the online MVDR in the place of the whole-window one,
+        with its ``wpe_online`` field the online WPE as well (gss_enhance_observation_bf_online;
+        float64 samples only, on its own).
+        ``wpe_online``: a gss_wpe_online_cfg for the online WPE in the place of the offline one
         (gss_enhance_observation_wpe_online; float64 samples only, on its own).
         ``wpd``: a gss_bf_wpd (`check_bf_wpd`) for the WPD beamformer on the STFT before WPE
         (gss_enhance_observation_wpd; float64 samples only, on its own).
@@ -1881,7 +2060,8 @@ class ResidentUtterance:
         ``activity``: device buffers (weights (F,) or None, scores (K,T), power (T,) or None) for
         the posterior activity of the call's own observation and posteriors
         (gss_enhance_observation_activity; float64 samples only, on its own)."""
-        given = [(name, v) for name, v in (('wpe_online', wpe_online), ('wpd', wpd),
+        given = [(name, v) for name, v in (('bf_online', bf_online), ('wpe_online', wpe_online),
+                                           ('wpd', wpd),
                                            ('activity', activity), ('lcmv', lcmv),
                                            ('channel_select', channel_select),
                                            ('segments', segments)) if v is not None]
@@ -2309,6 +2489,45 @@ def enhance_observation_wpe_online(obs, activity, target_index, start_context_sa
     x_hat, details = _one_target_result(utt, bufs, debug)
     if not debug:
         return x_hat
+    return x_hat, details
+
+
+def enhance_observation_bf_online(obs, activity, target_index, start_context_samples,
+                                  end_context_samples, *, forget=BF_ONLINE_FORGET,
+                                  loading=BF_ONLINE_LOADING, ref_channel=-1, wpe_online=False,
+                                  wpe_alpha=WPE_ONLINE_ALPHA, params=None, window=None,
+                                  debug=False, ctx=None, wpe_arrays=None, **param_kwargs):
+    """`enhance_observation` with the online MVDR of `mvdr_souden_online_from_masks` (BAN on, a
+    fresh state initialised from the window; gss_enhance_observation_bf_online) in the place of
+    the whole-window one.  ``ref_channel`` = -1: the window's.  ``wpe_online``: the online WPE
+    with ``wpe_alpha`` in the place of the offline one as well, as
+    `enhance_observation_wpe_online`.  ``debug`` details as there plus ``bf_online_fallbacks``.
+    Only ``bf='mvdrSouden_ban'`` has it (NotImplementedError otherwise); bad settings are
+    ValueError, both before any device work."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    _require_souden(params, 'bf_online', 'an online form')
+    obs = np.asarray(obs)
+    if obs.ndim != 2:
+        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    forget, loading, ref_channel = check_bf_online(forget, loading, ref_channel, obs.shape[0])
+    if wpe_online:
+        if not params.wpe:
+            raise ValueError('wpe_online with wpe=False: there is no WPE stage to replace')
+        if params.wpe_psd_context != 0:
+            raise ValueError(f'wpe_online with wpe_psd_context={params.wpe_psd_context}: the '
+                             'online WPE has no PSD context')
+        check_wpe_online(params.wpe_taps, params.wpe_delay, wpe_alpha, obs.shape[0],
+                         params.wpe_arrays if wpe_arrays is None else wpe_arrays)
+    elif wpe_alpha != WPE_ONLINE_ALPHA:
+        raise ValueError(f'wpe_alpha={wpe_alpha!r} without wpe_online: nobody reads it')
+    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
+    utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
+                bf_online=_bf_online_cfg(forget, loading, ref_channel, wpe_online, wpe_alpha))
+    x_hat, details = _one_target_result(utt, bufs, debug)
+    if not debug:
+        return x_hat
+    details['bf_online_fallbacks'] = ctx.last_mvdr_online_fallbacks()
     return x_hat, details
 
 

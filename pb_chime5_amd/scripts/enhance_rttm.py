@@ -45,6 +45,15 @@ def main(argv=None):
     ap.add_argument('--wpe-alpha', type=float, default=0.9999,
                     help='forgetting factor of --wpe-online, in (0, 1] (a choice, not a '
                          'measurement)')
+    ap.add_argument('--bf-online', action='store_true',
+                    help="the online MVDR in the place of the whole-window 'mvdrSouden_ban': running "
+                         'sums that forget, a filter per frame, no look-ahead '
+                         '(get_enhancer(bf_online=True))')
+    ap.add_argument('--bf-forget', type=float, default=0.99,
+                    help='forgetting factor of --bf-online, in (0, 1] (a choice, not a measurement)')
+    ap.add_argument('--bf-loading', type=float, default=1e-2,
+                    help='relative diagonal loading of the fresh state of --bf-online, > 0 (a '
+                         'choice, not a measurement)')
     ap.add_argument('--bss-iterations', type=int, default=20)
     ap.add_argument('--bss-iterations-post', type=int, default=1)
     ap.add_argument('--bf', default='mvdrSouden_ban')
@@ -101,7 +110,8 @@ def main(argv=None):
         bf_null_interferer=args.bf_null_interferer, bf_wpd_taps=args.bf_wpd_taps,
         bf_wpd_delay=args.bf_wpd_delay, bf_wpd_iterations=args.bf_wpd_iterations,
         bf_wpd_power_floor=args.bf_wpd_power_floor, wpe_online=args.wpe_online,
-        wpe_alpha=args.wpe_alpha)
+        wpe_alpha=args.wpe_alpha, bf_online=args.bf_online, bf_forget=args.bf_forget,
+        bf_loading=args.bf_loading)
     if parallel.is_master():
         Path(args.out).mkdir(parents=True, exist_ok=True)
     parallel.barrier()
