@@ -2210,24 +2210,48 @@ int psd3_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, cons
     return GSS_OK;
 }
 
-size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K, bool one_block) {
+// The blocks of cacgmm_schedule_run, with the strides of its block plan.
+struct EmWork {
+    cplx *Mq;                   // (F,NE,K)
+    double *logdet, *pi, *W;    // (F,K), (F,K), (F,K,T)
+    cplx *Bp;                   // partial sums per chunk, or segment, of the M-step
+    double *Sg_lds;
+    // the unit-normalised (F, D, T) copy feeds the register-form E-step and the M-step of every
+    // channel count; the register-form E-step has its own (finer) partial sums of gamma
+    cplx *Yn;
+    double *Sg_reg;
+    int *need_eigh;
+    // per (frequency, 64-frame tile): holds a frame whose normalised observation is zero
+    int *zero_tiles;
+    // (d1, d2) of the packed triangle, row-major and column-major order (em_chol / em_eigh)
+    int *tri_tab;
+    cplx *basis;                // em_onchip4: warm-start eigenvectors (D = 4)
+};
+static EmWork em_blocks(Workspace &ws, int F, int64_t T, int D, int K, const EmStrides &st,
+                        bool onchip) {
     const size_t NE = tri_count(D);
+    EmWork k;
+    k.Mq = ws.take<cplx>((size_t)F * NE * K, "cacgmm Mq");
+    k.logdet = ws.take<double>((size_t)F * K, "cacgmm logdet");
+    k.pi = ws.take<double>((size_t)F * K, "cacgmm pi");
+    k.W = ws.take<double>((size_t)F * K * T, "cacgmm W");
+    k.Bp = ws.take<cplx>((size_t)F * st.bp_nch * K * NE, "cacgmm Bp");
+    k.Sg_lds = ws.take<double>((size_t)F * st.nch * K, "cacgmm Sg");
+    k.Yn = ws.take<cplx>((size_t)F * D * T, "cacgmm Yn");
+    k.Sg_reg = ws.take<double>((size_t)F * st.reg_nch * K, "cacgmm Sg (register form)");
+    k.need_eigh = ws.take<int>((size_t)F * K, "cacgmm need_eigh");
+    k.zero_tiles = ws.take<int>((size_t)F * ((T + EM_TILE - 1) / EM_TILE), "cacgmm zero_tiles");
+    k.tri_tab = ws.take<int>(2 * NE, "cacgmm tri_tab");
+    k.basis = onchip ? ws.take<cplx>((size_t)F * K * 16, "cacgmm basis") : nullptr;
+    return k;
+}
+
+size_t cacgmm_workspace_bytes(int F, int64_t T, int D, int K, bool one_block) {
     // (one_block: the plan of the shared-prior schedule, whatever the block settings say)
     const EmBlockPlan bp = one_block ? EmBlockPlan{F, 1, 1} : em_block_plan(F, T, D, K);
-    const EmStrides st = em_strides(bp, F, T, D);
-    size_t b = 0;
-    b += align_up(sizeof(cplx) * (size_t)F * NE * K);            // Mq
-    b += 2 * align_up(sizeof(double) * (size_t)F * K);           // logdet, pi
-    b += align_up(sizeof(double) * (size_t)F * K * T);           // W
-    b += align_up(sizeof(cplx) * (size_t)F * st.bp_nch * K * NE);   // Bp (chunks, or segments)
-    b += align_up(sizeof(double) * (size_t)F * st.nch * K);      // Sg
-    b += align_up(sizeof(int) * (size_t)F * K);                  // need_eigh
-    b += align_up(sizeof(int) * 2 * NE);                         // tri_tab
-    b += align_up(sizeof(cplx) * (size_t)F * D * T);             // Yn (register-form E-step)
-    b += align_up(sizeof(double) * (size_t)F * st.reg_nch * K);  // Sg of the register-form E-step
-    b += align_up(sizeof(cplx) * (size_t)F * K * 16);            // em_onchip4: warm-start eigenvectors (D = 4)
-    b += align_up(sizeof(int) * (size_t)F * ((T + EM_TILE - 1) / EM_TILE));   // zero_tiles
-    return b + 4096;
+    Workspace ws;
+    em_blocks(ws, F, T, D, K, em_strides(bp, F, T, D), true);
+    return ws.bytes + 4096;
 }
 
 namespace {
@@ -2277,31 +2301,21 @@ int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, co
         onchip || s.shared_prior ? EmBlockPlan{F, 1, 1} : em_block_plan(F, T, D, K);
     const EmStrides st = em_strides(bplan, F, T, D);
 
-    cplx *Mq = arena_alloc_t<cplx>(ctx, (size_t)F * NE * K);
-    double *logdet = arena_alloc_t<double>(ctx, (size_t)F * K);
-    double *pi = arena_alloc_t<double>(ctx, (size_t)F * K);
-    double *W = arena_alloc_t<double>(ctx, (size_t)F * K * T);
-    cplx *Bp = arena_alloc_t<cplx>(ctx, (size_t)F * st.bp_nch * K * NE);
-    double *Sg_lds = arena_alloc_t<double>(ctx, (size_t)F * st.nch * K);
-    // the unit-normalised (F, D, T) copy feeds the register-form E-step and the M-step of every
-    // channel count; the register-form E-step has its own (finer) partial sums of gamma
-    cplx *Yn = arena_alloc_t<cplx>(ctx, (size_t)F * D * T);
-    double *Sg_reg = arena_alloc_t<double>(ctx, (size_t)F * st.reg_nch * K);
-    int *need_eigh = arena_alloc_t<int>(ctx, (size_t)F * K);
-    // per (frequency, 64-frame tile): holds a frame whose normalised observation is zero
-    const int ntile = (int)((T + EM_TILE - 1) / EM_TILE);
-    int *zero_tiles = arena_alloc_t<int>(ctx, (size_t)F * ntile);
-    // (d1, d2) of the packed triangle, row-major and column-major order (em_chol / em_eigh)
-    int *tri_tab = arena_alloc_t<int>(ctx, 2 * (size_t)NE);
-    GSS_REQUIRE(ctx, Mq && logdet && pi && W && Bp && Sg_lds && Yn && Sg_reg && need_eigh && tri_tab &&
-                         zero_tiles,
-                GSS_ERR_NOMEM, "cacgmm workspace");
+    GSS_REQUIRE(ctx, !s.shared_prior || (!s.import_model && !s.export_model && !s.loglik),
+                GSS_ERR_INVALID, "cacgmm: a model with a shared prior cannot leave the call");
+    Workspace ws(ctx);
+    const EmWork k = em_blocks(ws, F, T, D, K, st, onchip);
     EmPriorWork pw{};
     if (s.shared_prior) {
-        GSS_REQUIRE(ctx, !s.import_model && !s.export_model && !s.loglik, GSS_ERR_INVALID,
-                    "cacgmm: a model with a shared prior cannot leave the call");
-        GSS_TRY(cacgmm_prior_alloc(ctx, F, T, K, s.prior, &pw));
+        pw = cacgmm_prior_alloc(ws, F, T, K, !s.prior);
+        if (s.prior) pw.prior = s.prior;
     }
+    GSS_TRY(ws.status("cacgmm"));
+    cplx *const Mq = k.Mq, *const Bp = k.Bp, *const Yn = k.Yn;
+    double *const logdet = k.logdet, *const pi = k.pi, *const W = k.W;
+    double *const Sg_lds = k.Sg_lds, *const Sg_reg = k.Sg_reg;
+    int *const need_eigh = k.need_eigh, *const zero_tiles = k.zero_tiles, *const tri_tab = k.tri_tab;
+    const int ntile = (int)((T + EM_TILE - 1) / EM_TILE);
     GSS_REQUIRE(ctx, em_estep_lds(D, K) <= 160 * 1024 &&
                          wcov_lds_layout(D, std::min(K, 8)).total <= 160 * 1024,
                 GSS_ERR_UNSUPPORTED, "cacgmm: D=%d K=%d LDS", D, K);
@@ -2428,8 +2442,7 @@ int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, co
         GSS_TRY(make_block(0, F, ctx->stream, &b));
         GSS_TRY(prepare(b));
         OnchipArgs o{};
-        o.basis = arena_alloc_t<cplx>(ctx, (size_t)F * K * 16);
-        GSS_REQUIRE(ctx, o.basis, GSS_ERR_NOMEM, "cacgmm workspace");
+        o.basis = k.basis;
         o.Yn = Yn;
         o.act = act;
         o.act_stride = act_stride;

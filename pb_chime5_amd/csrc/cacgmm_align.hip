@@ -243,17 +243,32 @@ int64_t plan_passes(const gss_align_plan *plan) {
 
 }  // namespace
 
+struct AlignWork {
+    double *inv_n;      // (F,K) 1 / row norms
+    double *c;          // (K,T) centroid
+    double *part;       // slices of a column sum
+    double *sq;         // squares of the centroid per block of frames
+    int32_t *changed;   // one word per pass
+    double *aligned;    // own_aligned: the aligned table the activity is formed from
+};
+static AlignWork align_blocks(Workspace &ws, int F, int K, int64_t T, const gss_align_plan *plan,
+                              bool own_aligned) {
+    const size_t KT = (size_t)K * T, nblk = (size_t)((T + ALIGN_WG - 1) / ALIGN_WG);
+    AlignWork k;
+    k.inv_n = ws.take<double>((size_t)F * K, "align inv_n");
+    k.c = ws.take<double>(KT, "align centroid");
+    k.part = ws.take<double>((size_t)PRIOR_MAX_SLICES * KT, "align slices");
+    k.sq = ws.take<double>((size_t)K * nblk, "align squares");
+    k.changed = ws.take<int32_t>((size_t)plan_passes(plan), "align changed");
+    k.aligned = own_aligned ? ws.take<double>((size_t)F * KT, "align aligned") : nullptr;
+    return k;
+}
+
 size_t cacgmm_align_workspace_bytes(int F, int K, int64_t T, const gss_align_plan *plan,
                                     bool own_aligned) {
-    const size_t nblk = (size_t)((T + ALIGN_WG - 1) / ALIGN_WG);
-    size_t b = 0;
-    b += align_up(sizeof(double) * (size_t)F * K);                      // 1 / row norms
-    b += align_up(sizeof(double) * (size_t)K * T);                      // centroid
-    b += align_up(sizeof(double) * (size_t)PRIOR_MAX_SLICES * K * T);   // slices of a column sum
-    b += align_up(sizeof(double) * (size_t)K * nblk);                   // squares of the centroid
-    b += align_up(sizeof(int32_t) * (size_t)plan_passes(plan));         // "changed" word per pass
-    if (own_aligned) b += align_up(sizeof(double) * (size_t)F * K * T); // aligned table for the activity
-    return b + 4096;
+    Workspace ws;
+    align_blocks(ws, F, K, T, plan, own_aligned);
+    return ws.bytes + 4096;
 }
 
 int cacgmm_align_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
@@ -262,14 +277,12 @@ int cacgmm_align_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
     const int64_t KT = (int64_t)K * T;
     const int nblk = (int)((T + ALIGN_WG - 1) / ALIGN_WG);
     const int64_t passes = plan_passes(plan);
-    double *inv_n = arena_alloc_t<double>(ctx, (size_t)F * K, "align inv_n");
-    double *c = arena_alloc_t<double>(ctx, (size_t)KT, "align centroid");
-    double *part = arena_alloc_t<double>(ctx, (size_t)PRIOR_MAX_SLICES * KT, "align slices");
-    double *sq = arena_alloc_t<double>(ctx, (size_t)K * nblk, "align squares");
-    int32_t *changed = arena_alloc_t<int32_t>(ctx, (size_t)passes, "align changed");
-    if (activity && !aligned) aligned = arena_alloc_t<double>(ctx, (size_t)F * KT, "align aligned");
-    GSS_REQUIRE(ctx, inv_n && c && part && sq && changed && (aligned || !activity), GSS_ERR_NOMEM,
-                "cacgmm workspace (align)");
+    Workspace ws(ctx);
+    const AlignWork k = align_blocks(ws, F, K, T, plan, activity && !aligned);
+    GSS_TRY(ws.status("cacgmm align"));
+    double *inv_n = k.inv_n, *c = k.c, *part = k.part, *sq = k.sq;
+    int32_t *changed = k.changed;
+    if (k.aligned) aligned = k.aligned;
 
     {
         GSS_PROF(ctx, "align_norms");

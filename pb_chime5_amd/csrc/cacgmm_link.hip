@@ -165,15 +165,22 @@ int launch_link(gss_ctx *ctx, const double *prev, int64_t T_prev, int64_t prev_b
 
 }  // namespace
 
+static double *link_blocks(Workspace &ws, int F, int K) {
+    return ws.take<double>((size_t)F * link_entries(K), "link partial rows");
+}
+
 size_t cacgmm_link_workspace_bytes(int F, int K) {
-    return align_up(sizeof(double) * (size_t)F * link_entries(K)) + 4096;      // the partial rows
+    Workspace ws;
+    link_blocks(ws, F, K);
+    return ws.bytes + 4096;
 }
 
 int cacgmm_link_run(gss_ctx *ctx, const double *prev, int64_t T_prev, int64_t prev_begin,
                     const double *cur, int64_t T_cur, int64_t cur_begin, int64_t L, int F, int K,
                     int32_t *mapping, double *scores) {
-    double *part = arena_alloc_t<double>(ctx, (size_t)F * link_entries(K), "link partial rows");
-    GSS_REQUIRE(ctx, part, GSS_ERR_NOMEM, "cacgmm workspace (link)");
+    Workspace ws(ctx);
+    double *part = link_blocks(ws, F, K);
+    GSS_TRY(ws.status("cacgmm link"));
 #define GSS_LINK_CASE(N)                                                                          \
     case N:                                                                                       \
         return launch_link<N>(ctx, prev, T_prev, prev_begin, cur, T_cur, cur_begin, L, F, part,   \

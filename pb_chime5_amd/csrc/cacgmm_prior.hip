@@ -395,23 +395,19 @@ static int prior_per_slice(int nf, int K, int64_t T) {
     return (int)((nf + want - 1) / want);
 }
 
-size_t cacgmm_prior_workspace_bytes(int F, int64_t T, int K) {
-    size_t b = 0;
-    b += align_up(sizeof(double) * (size_t)F * K * T);                  // gamma of the fit iterations
-    b += align_up(sizeof(double) * (size_t)K * T);                      // the prior
-    b += align_up(sizeof(double) * (size_t)PRIOR_MAX_SLICES * K * T);   // slices of the column sum
-    b += align_up(sizeof(double) * (size_t)F * ((T + 63) / 64) * K);    // sums of gamma per tile
-    return b + 4096;
+EmPriorWork cacgmm_prior_alloc(Workspace &ws, int F, int64_t T, int K, bool own_prior) {
+    EmPriorWork w;
+    w.G = ws.take<double>((size_t)F * K * T, "shared prior G");
+    w.prior = own_prior ? ws.take<double>((size_t)K * T, "shared prior") : nullptr;
+    w.part = ws.take<double>((size_t)PRIOR_MAX_SLICES * K * T, "shared prior slices");
+    w.Sg = ws.take<double>((size_t)F * ((T + 63) / 64) * K, "shared prior Sg");
+    return w;
 }
 
-int cacgmm_prior_alloc(gss_ctx *ctx, int F, int64_t T, int K, double *prior_out, EmPriorWork *w) {
-    w->G = arena_alloc_t<double>(ctx, (size_t)F * K * T);
-    w->prior = prior_out ? prior_out : arena_alloc_t<double>(ctx, (size_t)K * T);
-    w->part = arena_alloc_t<double>(ctx, (size_t)PRIOR_MAX_SLICES * K * T);
-    w->Sg = arena_alloc_t<double>(ctx, (size_t)F * ((T + 63) / 64) * K);
-    GSS_REQUIRE(ctx, w->G && w->prior && w->part && w->Sg, GSS_ERR_NOMEM,
-                "cacgmm workspace (shared prior)");
-    return GSS_OK;
+size_t cacgmm_prior_workspace_bytes(int F, int64_t T, int K) {
+    Workspace ws;
+    cacgmm_prior_alloc(ws, F, T, K, true);
+    return ws.bytes + 4096;
 }
 
 int cacgmm_prior_estep_run(gss_ctx *ctx, const EmPriorArgs &a, int K, int mode) {

@@ -281,14 +281,35 @@ void bands_launch(gss_ctx *ctx, const cplx *Y, const double *W, int F, int64_t M
 
 }  // namespace
 
-// E planes, V, scores, channel indices
-size_t chsel_workspace_bytes(int F, int64_t T, int D, int B) {
+// chsel_select_run: scores and channel indices, then the blocks of the chsel_scores_run it
+// calls: the E planes and, unless the caller takes the band variances, V
+struct ChselPickWork {
+    double *scores;
+    int32_t *idx;
+};
+static ChselPickWork chsel_select_blocks(Workspace &ws) {
+    ChselPickWork k;
+    k.scores = ws.take<double>(GSS_MAX_CHANNELS, "channel selection scores");
+    k.idx = ws.take<int32_t>(GSS_MAX_CHANNELS, "channel selection indices");
+    return k;
+}
+struct ChselScoreWork {
+    double *E, *band_var;
+};
+static ChselScoreWork chsel_scores_blocks(Workspace &ws, int F, int64_t T, int D, int B,
+                                          bool own_band_var) {
     const int64_t M = T * D;
-    size_t b = align_up(sizeof(double) * (size_t)bands_shares(F, M) * B * M);
-    b += align_up(sizeof(double) * (size_t)B * D);
-    b += align_up(sizeof(double) * GSS_MAX_CHANNELS);
-    b += align_up(sizeof(int32_t) * GSS_MAX_CHANNELS);
-    return b + 4096;
+    ChselScoreWork k;
+    k.E = ws.take<double>((size_t)bands_shares(F, M) * B * M, "channel selection E");
+    k.band_var = own_band_var ? ws.take<double>((size_t)B * D, "channel selection V") : nullptr;
+    return k;
+}
+
+size_t chsel_workspace_bytes(int F, int64_t T, int D, int B) {
+    Workspace ws;
+    chsel_select_blocks(ws);
+    chsel_scores_blocks(ws, F, T, D, B, true);
+    return ws.bytes + 4096;
 }
 
 int chsel_scores_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
@@ -296,9 +317,11 @@ int chsel_scores_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
     const int B = sel.bands;
     const int64_t M = T * D;
     const int FS = bands_shares(F, M);
-    double *E = arena_alloc_t<double>(ctx, (size_t)FS * B * M);
-    if (!band_var) band_var = arena_alloc_t<double>(ctx, (size_t)B * D);
-    GSS_REQUIRE(ctx, E && band_var, GSS_ERR_NOMEM, "channel selection: workspace sizing bug");
+    Workspace ws(ctx);
+    const ChselScoreWork k = chsel_scores_blocks(ws, F, T, D, B, !band_var);
+    GSS_TRY(ws.status("channel selection scores"));
+    double *E = k.E;
+    if (!band_var) band_var = k.band_var;
     {
         GSS_PROF(ctx, "chsel_bands");
         if (B <= 8) bands_launch<8>(ctx, Y, sel.bank_dev, F, M, B, FS, E);
@@ -324,14 +347,14 @@ int chsel_scores_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
 int chsel_select_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
                      const gss_channel_select &sel, cplx *Ysel, int32_t *channels) {
     const int n = sel.keep;
-    double *scores = arena_alloc_t<double>(ctx, GSS_MAX_CHANNELS);
-    int32_t *idx = arena_alloc_t<int32_t>(ctx, GSS_MAX_CHANNELS);
-    GSS_REQUIRE(ctx, scores && idx, GSS_ERR_NOMEM, "channel selection: workspace sizing bug");
-    GSS_TRY(chsel_scores_run(ctx, Y, F, T, D, sel, scores, nullptr));
+    Workspace ws(ctx);
+    const ChselPickWork k = chsel_select_blocks(ws);
+    GSS_TRY(ws.status("channel selection"));
+    GSS_TRY(chsel_scores_run(ctx, Y, F, T, D, sel, k.scores, nullptr));
     {
         GSS_PROF(ctx, "chsel_pick");
         hipLaunchKernelGGL(chsel_pick_kernel, dim3(1), dim3(64), 0, ctx->stream,
-                           (const double *)scores, D, n, idx, channels,
+                           (const double *)k.scores, D, n, k.idx, channels,
                            ctx->status_dev + GSS_STATUS_CHANNELS);
         GSS_LAUNCH_CHECK(ctx, "chsel_pick_kernel");
     }
@@ -341,7 +364,7 @@ int chsel_select_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
         const unsigned total = (unsigned)((int64_t)F * T * n);
         const unsigned per_block = 256u * GATHER_PER;
         hipLaunchKernelGGL(chsel_gather_kernel, dim3((total + per_block - 1) / per_block),
-                           dim3(256), 0, ctx->stream, Y, total, D, n, (const int32_t *)idx, Ysel);
+                           dim3(256), 0, ctx->stream, Y, total, D, n, (const int32_t *)k.idx, Ysel);
         GSS_LAUNCH_CHECK(ctx, "chsel_gather_kernel");
     }
     return GSS_OK;

@@ -747,6 +747,17 @@ extern "C" int gss_wpe(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
                    psd_context, reinterpret_cast<cplx *>(X));
 }
 
+// gss_wpe_arrays with more than one array: input and output regrouped by array, (F A, T, C)
+struct WpeArraysWork {
+    cplx *Yg, *Xg;
+};
+static WpeArraysWork wpe_arrays_blocks(Workspace &ws, int F, int64_t T, int D) {
+    WpeArraysWork k;
+    k.Yg = ws.take<cplx>((size_t)F * T * D, "wpe arrays Y by array");
+    k.Xg = ws.take<cplx>((size_t)F * T * D, "wpe arrays X by array");
+    return k;
+}
+
 extern "C" int gss_wpe_arrays(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int A, int C,
                               int taps, int delay, int iterations, int psd_context, gss_cplx *X) {
     GSS_ENTER_VARIANTS(ctx);
@@ -764,15 +775,16 @@ extern "C" int gss_wpe_arrays(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T,
         return wpe_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, taps, delay, iterations,
                        psd_context, reinterpret_cast<cplx *>(X));
     }
-    const size_t ftd = (size_t)F * T * D;
-    GSS_TRY(arena_reserve(ctx, 2 * align_up(sizeof(cplx) * ftd) +
-                                   wpe_workspace_bytes(F * A, T, C, taps, delay) + (1 << 16)));
-    cplx *Yg = arena_alloc_t<cplx>(ctx, ftd);
-    cplx *Xg = arena_alloc_t<cplx>(ctx, ftd);
-    GSS_REQUIRE(ctx, Yg && Xg, GSS_ERR_NOMEM, "gss_wpe_arrays workspace");
-    GSS_TRY(wpe_arrays_regroup_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, A, C, true, Yg));
-    GSS_TRY(wpe_run(ctx, Yg, F * A, T, C, taps, delay, iterations, psd_context, Xg, -1, F * A));
-    return wpe_arrays_regroup_run(ctx, Xg, F, T, A, C, false, reinterpret_cast<cplx *>(X));
+    Workspace sizing;
+    wpe_arrays_blocks(sizing, F, T, D);
+    GSS_TRY(arena_reserve(ctx, sizing.bytes + wpe_workspace_bytes(F * A, T, C, taps, delay) +
+                                   (1 << 16)));
+    Workspace ws(ctx);
+    const WpeArraysWork k = wpe_arrays_blocks(ws, F, T, D);
+    GSS_TRY(ws.status("gss_wpe_arrays"));
+    GSS_TRY(wpe_arrays_regroup_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, A, C, true, k.Yg));
+    GSS_TRY(wpe_run(ctx, k.Yg, F * A, T, C, taps, delay, iterations, psd_context, k.Xg, -1, F * A));
+    return wpe_arrays_regroup_run(ctx, k.Xg, F, T, A, C, false, reinterpret_cast<cplx *>(X));
 }
 
 // The online WPE argument rule, before any launch; fills n = taps * C.
@@ -841,7 +853,7 @@ extern "C" int gss_wpe_inverse_power(gss_ctx *ctx, const gss_cplx *Y, int F, int
     GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
                 "gss_wpe_inverse_power: D=%d outside [1, %d]", D, GSS_MAX_CHANNELS);
     GSS_TRY(check_stft_bins(ctx, F, T, D));
-    GSS_TRY(arena_reserve(ctx, sizeof(double) * (size_t)F * T + 8192));
+    GSS_TRY(arena_reserve(ctx, wpe_inverse_power_workspace_bytes(F, T)));
     return wpe_inverse_power_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, psd_context,
                                  inverse_power);
 }
@@ -1615,17 +1627,8 @@ static int pipeline_wpe(gss_ctx *ctx, const gss_params *p, const cplx *Y, int Fv
     return wpe_copy_zero_pivots(ctx);
 }
 
-// Workspace of the pipeline's front (STFT, WPE, activity, EM): its buffers (Y, X, frame
-// activity, gamma) and the largest stage workspace it needs on top of them.
-static size_t front_buffer_bytes(int F, int64_t T, int64_t T_act, int D, int K) {
-    size_t b = 0;
-    size_t ftd = align_up(sizeof(cplx) * (size_t)F * T * D);
-    b += 2 * ftd;                                            // Y, X
-    b += align_up((size_t)K * T_act);                        // frame activity
-    b += align_up(sizeof(double) * (size_t)F * K * T);       // gamma
-    return b;
-}
-
+// The largest stage workspace the pipeline's front (STFT, WPE, activity, EM) needs on top of
+// the pipeline's buffers.
 static size_t front_stage_bytes(const gss_params *p, int F, int64_t T, int D, int K,
                                 bool shared_prior = false) {
     const int A = wpe_arrays_of(p);
@@ -1670,8 +1673,56 @@ struct PipelineCall {
     double *blind_prior = nullptr;                   // (K,T), receives the prior of the last M-step
 };
 
-// (seg: the segment-wise beamformer in the place of the whole-window one; lcmv: the
-// interferer-nulling one, with four mask buffers;
+// The pipeline's buffers that outlive the front, taken first from the reserved arena; every
+// stage runs above them and is released after it.  S > 1 (the targets and the separate calls):
+// masks, Xhat and ref in S consecutive per-target blocks.
+struct PipelineBuffers {
+    cplx *Y, *X;        // the STFT and the WPE output; no WPE: X is Y
+    uint8_t *actf;
+    double *gamma;
+    // WPD: the raw STFT beside the WPE output -- the joint WPE leaves it in Y's buffer, the
+    // per-array WPE overwrites that one, hence a copy -- and the frame gate
+    cplx *Yraw;
+    uint8_t *gate;
+    double *mx, *mn;    // (S,F,T) target and distortion masks
+    double *mi, *mnn;   // LCMV: the interferer and noise masks (mn = their sum)
+    cplx *Xhat;         // (S,T,F)
+    int32_t *ref;       // (4 S)
+};
+static PipelineBuffers pipeline_blocks(Workspace &ws, const gss_params *p, int F, int64_t T,
+                                       int64_t T_act, int D, int K, int S, const PipelineCall &call) {
+    const size_t ft = (size_t)F * T;
+    PipelineBuffers b;
+    b.Y = ws.take<cplx>(ft * D, "pipeline Y");
+    b.X = p->wpe ? ws.take<cplx>(ft * D, "pipeline X") : b.Y;
+    b.actf = ws.take<uint8_t>((size_t)K * T_act, "pipeline frame activity");
+    b.gamma = ws.take<double>(ft * K, "pipeline gamma");
+    const bool raw_copy = call.wpd && p->wpe && wpe_arrays_of(p) > 1;
+    b.Yraw = raw_copy ? ws.take<cplx>(ft * D, "pipeline raw Y") : nullptr;
+    b.gate = call.wpd ? ws.take<uint8_t>((size_t)T, "pipeline frame gate") : nullptr;
+    b.mx = ws.take<double>(S * ft, "pipeline target mask");
+    b.mn = ws.take<double>(S * ft, "pipeline distortion mask");
+    b.mi = call.lcmv ? ws.take<double>(ft, "pipeline interferer mask") : nullptr;
+    b.mnn = call.lcmv ? ws.take<double>(ft, "pipeline noise mask") : nullptr;
+    b.Xhat = ws.take<cplx>(S * ft, "pipeline Xhat");
+    b.ref = ws.take<int32_t>(4 * (size_t)S, "pipeline ref");
+    return b;
+}
+// Single blocks above the pipeline's buffers: the STFT of all D_all channels until the kept ones
+// are gathered (a selection), the one channel-picked X_hat of a targets call ('ch2' / 'sum'), the
+// scores of the separate call's posterior activity, which nobody asked for
+static cplx *select_all_blocks(Workspace &ws, int F, int64_t T, int D_all) {
+    return ws.take<cplx>((size_t)F * T * D_all, "pipeline Y of all channels");
+}
+static cplx *channel_pick_blocks(Workspace &ws, int F, int64_t T) {
+    return ws.take<cplx>((size_t)F * T, "pipeline picked channel");
+}
+static double *separate_scores_blocks(Workspace &ws, int K, int64_t T) {
+    return ws.take<double>((size_t)K * T, "separate scores");
+}
+
+// The reserve of the one-target call: its buffers and the largest stage above them.
+// (seg: the segment-wise beamformer in the place of the whole-window one;
 // select: D is the number of channels kept out of D_all, and the selection stage needs its own
 // workspace and, when it gathers, the STFT of all D_all channels;
 // activity: the posterior activity runs between the front and the masks)
@@ -1679,14 +1730,9 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
                                  int K, int D_all, const PipelineCall &call) {
     const gss_bf_wpd *const wpd = call.wpd;
     const bool lcmv = call.lcmv != nullptr;
-    size_t b = front_buffer_bytes(F, T, T_act, D, K);
-    // (WPD: the raw STFT beside the WPE output -- the joint WPE leaves it in Y's buffer, the
-    // per-array WPE overwrites that one -- and the frame gate)
-    if (wpd && p->wpe && wpe_arrays_of(p) > 1) b += align_up(sizeof(cplx) * (size_t)F * T * D);
-    if (wpd) b += align_up((size_t)T);
-    b += (lcmv ? 4 : 2) * align_up(sizeof(double) * (size_t)F * T);   // masks (LCMV: X, I, N, I + N)
-    b += align_up(sizeof(cplx) * (size_t)F * T);             // Xhat
-    b += 4096;
+    Workspace ws, all;
+    pipeline_blocks(ws, p, F, T, T_act, D, K, 1, call);
+    if (D_all > D) select_all_blocks(all, F, T, D_all);
     size_t stage = front_stage_bytes(p, F, T, D, K);
     stage = std::max(stage, call.seg
                                 ? mvdr_segments_workspace_bytes(F, T, D, call.seg->segment_frames)
@@ -1707,44 +1753,26 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
     if (call.activity.scores)
         stage = std::max(stage, pact_workspace_bytes(F, T, K));   // the partial planes
     if (call.select)
-        stage = std::max(stage, chsel_workspace_bytes(F, T, D_all, call.sel->bands) +
-                                    (D_all > D ? align_up(sizeof(cplx) * (size_t)F * T * D_all)
-                                               : 0) + 4096);
-    return b + stage + (1 << 16);
+        stage = std::max(stage, chsel_workspace_bytes(F, T, D_all, call.sel->bands) + all.bytes + 4096);
+    return ws.bytes + 4096 + stage + (1 << 16);
 }
 
 // The same with the tail of S targets: masks, Xhat and the beamformer's intermediates S times,
-// S iSTFT frame buffers, one channel-picked X_hat ('ch2' / 'sum').
+// S iSTFT frame buffers, one channel-picked X_hat ('ch2' / 'sum').  blind
+// (gss_separate_observation, S = K): the EM with the shared prior in the place of the guided
+// one, and the posterior activity's partial planes and scores.
 static size_t targets_workspace(const gss_params *p, int F, int64_t T, int64_t T_act, int D,
-                                int K, int S) {
-    size_t b = front_buffer_bytes(F, T, T_act, D, K);
-    b += 2 * align_up(sizeof(double) * (size_t)S * F * T);   // masks
-    b += align_up(sizeof(cplx) * (size_t)S * F * T);         // Xhat
-    b += align_up(sizeof(int32_t) * 4 * (size_t)S);          // ref
-    b += 4096;
-    size_t stage = front_stage_bytes(p, F, T, D, K);
+                                int K, int S, bool blind) {
+    Workspace ws, scores, picked;
+    pipeline_blocks(ws, p, F, T, T_act, D, K, S, PipelineCall{});
+    separate_scores_blocks(scores, K, T);
+    channel_pick_blocks(picked, F, T);
+    size_t stage = front_stage_bytes(p, F, T, D, K, /*shared_prior=*/blind);
+    if (blind) stage = std::max(stage, pact_workspace_bytes(F, T, K) + scores.bytes + 4096);
     stage = std::max(stage, mvdr_workspace_bytes(F, T, D, S));
-    stage = std::max(stage, align_up(sizeof(cplx) * (size_t)F * T) + 4096);
+    stage = std::max(stage, picked.bytes + 4096);
     stage = std::max(stage, stft_workspace_bytes((int64_t)S * T, p->stft_size));
-    return b + stage + (1 << 16);
-}
-
-// gss_separate_observation: the targets call with S = K, the EM with the shared prior in the
-// place of the guided one, and the posterior activity's partial planes and scores.
-static size_t separate_workspace(const gss_params *p, int F, int64_t T, int D, int K) {
-    const int S = K;
-    size_t b = front_buffer_bytes(F, T, T, D, K);
-    b += 2 * align_up(sizeof(double) * (size_t)S * F * T);   // masks
-    b += align_up(sizeof(cplx) * (size_t)S * F * T);         // Xhat
-    b += align_up(sizeof(int32_t) * 4 * (size_t)S);          // ref
-    b += 4096;
-    size_t stage = front_stage_bytes(p, F, T, D, K, /*shared_prior=*/true);
-    stage = std::max(stage, pact_workspace_bytes(F, T, K) +
-                                align_up(sizeof(double) * (size_t)K * T) + 4096);   // planes, scores
-    stage = std::max(stage, mvdr_workspace_bytes(F, T, D, S));
-    stage = std::max(stage, align_up(sizeof(cplx) * (size_t)F * T) + 4096);
-    stage = std::max(stage, stft_workspace_bytes((int64_t)S * T, p->stft_size));
-    return b + stage + (1 << 16);
+    return ws.bytes + 4096 + stage + (1 << 16);
 }
 
 // Checks of the fused pipeline that do not depend on the target(s): before ...
@@ -1783,25 +1811,6 @@ static int check_pipeline_rest(gss_ctx *ctx, const gss_params *p, int D, int64_t
     return GSS_OK;
 }
 
-// The pipeline's buffers that outlive the front; allocated first from the reserved arena.
-struct PipelineFront {
-    cplx *Y, *X;
-    cplx *Yraw = nullptr;   // WPD over a per-array WPE: a copy of the STFT, which that WPE overwrites
-    uint8_t *actf;
-    double *gamma;
-};
-
-static int alloc_front(gss_ctx *ctx, const gss_params *p, int F, int64_t T, int64_t T_act, int D,
-                       int K, PipelineFront *fr) {
-    // (the names show up in the guard report of the workspace debug mode)
-    fr->Y = arena_alloc_t<cplx>(ctx, (size_t)F * T * D, "pipeline Y");
-    fr->X = p->wpe ? arena_alloc_t<cplx>(ctx, (size_t)F * T * D, "pipeline X") : fr->Y;
-    fr->actf = arena_alloc_t<uint8_t>(ctx, (size_t)K * T_act, "pipeline frame activity");
-    fr->gamma = arena_alloc_t<double>(ctx, (size_t)F * K * T, "pipeline gamma");
-    GSS_REQUIRE(ctx, fr->Y && fr->X && fr->actf && fr->gamma, GSS_ERR_NOMEM, "workspace sizing bug");
-    return GSS_OK;
-}
-
 // STFT, WPE (joint or per array), frame activity and the guided CACGMM of one window: obs ->
 // X (F,T,D) and gamma (F,K,T), nothing of it depending on a target.  Stage workspace above
 // `mark` is released after each stage.  `guide` (a guided call): the model's guidance per STFT
@@ -1809,7 +1818,7 @@ static int alloc_front(gss_ctx *ctx, const gss_params *p, int F, int64_t T, int6
 // selection): the channels of `obs`, of which D are kept.
 static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call, const void *obs,
                      int D_all, int D, int64_t N, const uint8_t *act, int K, int64_t N_act, int F,
-                     int64_t T, int64_t T_act, const PipelineFront &fr, size_t mark,
+                     int64_t T, int64_t T_act, const PipelineBuffers &fr, size_t mark,
                      const EmGuide &guide) {
     const int obs_type = call.obs_type;
     cplx *const Y = fr.Y, *const X = fr.X;
@@ -1823,8 +1832,9 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call
     } else {
         // the STFT of all D_all channels lives above `mark` until the kept D = sel->keep of
         // them are gathered into Y
-        cplx *Yall = arena_alloc_t<cplx>(ctx, (size_t)F * T * D_all);
-        GSS_REQUIRE(ctx, Yall, GSS_ERR_NOMEM, "workspace sizing bug");
+        Workspace ws(ctx);
+        cplx *Yall = select_all_blocks(ws, F, T, D_all);
+        GSS_TRY(ws.status(call.entry));
         GSS_TRY(stft_run(ctx, obs, obs_type, D_all, N, p->stft_fading, Yall));
         GSS_TRY(chsel_select_run(ctx, Yall, F, T, D_all, *call.sel, Y, nullptr));
         GSS_TRY(arena_release(ctx, mark));
@@ -1883,7 +1893,7 @@ static int copy_tap(gss_ctx *ctx, void *dst, const void *src, size_t bytes) {
 }
 
 // The front's debug taps: Obs_ftd, act_frames, gamma
-static int copy_front_taps(gss_ctx *ctx, const gss_debug_taps *taps, const PipelineFront &fr,
+static int copy_front_taps(gss_ctx *ctx, const gss_debug_taps *taps, const PipelineBuffers &fr,
                            int F, int64_t T, int64_t T_act, int D, int K) {
     GSS_TRY(copy_tap(ctx, taps->Obs_ftd, fr.X, sizeof(cplx) * (size_t)F * T * D));
     if (taps->act_frames)
@@ -1931,26 +1941,13 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
     if (call.guided) GSS_TRY(check_guidance(ctx, call.guidance, K, T, &guide));
 
     GSS_TRY(arena_reserve(ctx, pipeline_workspace(p, F, T, T_act, D, K, D_all, call)));
-    PipelineFront fr;
-    GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
-    uint8_t *gate = nullptr;
-    if (call.wpd) {
-        if (p->wpe && wpe_arrays_of(p) > 1) {
-            fr.Yraw = arena_alloc_t<cplx>(ctx, (size_t)F * T * D);
-            GSS_REQUIRE(ctx, fr.Yraw, GSS_ERR_NOMEM, "workspace sizing bug");
-        }
-        gate = arena_alloc_t<uint8_t>(ctx, (size_t)T);
-        GSS_REQUIRE(ctx, gate, GSS_ERR_NOMEM, "workspace sizing bug");
-    }
-    double *mx = arena_alloc_t<double>(ctx, (size_t)F * T);
-    double *mn = arena_alloc_t<double>(ctx, (size_t)F * T);
-    // (LCMV: mi, mnn = the interferer and noise masks, mn = their sum, the distortion mask)
-    double *mi = call.lcmv ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
-    double *mnn = call.lcmv ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
-    cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)F * T);
-    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);
-    GSS_REQUIRE(ctx, mx && mn && Xhat && ref && (!call.lcmv || (mi && mnn)), GSS_ERR_NOMEM,
-                "workspace sizing bug");
+    Workspace ws(ctx);
+    const PipelineBuffers fr = pipeline_blocks(ws, p, F, T, T_act, D, K, 1, call);
+    GSS_TRY(ws.status(call.entry));
+    uint8_t *const gate = fr.gate;
+    double *const mx = fr.mx, *const mn = fr.mn, *const mi = fr.mi, *const mnn = fr.mnn;
+    cplx *const Xhat = fr.Xhat;
+    int32_t *const ref = fr.ref;
     const size_t mark = ctx->arena_off;
     GSS_TRY(run_front(ctx, p, call, obs, D_all, D, N, act, K, N_act, F, T, T_act, fr, mark, guide));
     cplx *const X = fr.X;
@@ -2012,14 +2009,15 @@ static int enhance_observation_impl(gss_ctx *ctx, const gss_params *p, const voi
 
 // The target-dependent tail for S targets together (masks, beamformer or channel pick,
 // postfilter, iSTFT, the taps) on the front's X and gamma; start_ctx / end_ctx NULL: no context
-// frames.  mx, mn (S,F,T), Xhat (S,T,F), ref (4 S) and everything below `mark` stay allocated.
-static int run_targets_tail(gss_ctx *ctx, const gss_params *p, const PipelineFront &fr, int F,
+// frames.  The buffers of `fr`, everything below `mark`, stay allocated.
+static int run_targets_tail(gss_ctx *ctx, const gss_params *p, const PipelineBuffers &fr, int F,
                             int64_t T, int64_t T_act, int D, int K, int S, const int32_t *targets,
-                            const int64_t *start_ctx, const int64_t *end_ctx, double *mx,
-                            double *mn, cplx *Xhat, int32_t *ref, size_t mark, double *out,
-                            const gss_debug_taps *taps) {
+                            const int64_t *start_ctx, const int64_t *end_ctx, size_t mark,
+                            double *out, const gss_debug_taps *taps) {
     const int size = p->stft_size, shift = p->stft_shift, fading = p->stft_fading;
-    cplx *const X = fr.X;
+    cplx *const X = fr.X, *const Xhat = fr.Xhat;
+    double *const mx = fr.mx, *const mn = fr.mn;
+    int32_t *const ref = fr.ref;
     int64_t sf[GSS_MAX_CLASSES] = {}, ef[GSS_MAX_CLASSES] = {};
     if (p->bf_drop_context && start_ctx && end_ctx) {
         for (int s = 0; s < S; ++s) {
@@ -2039,8 +2037,9 @@ static int run_targets_tail(gss_ctx *ctx, const gss_params *p, const PipelineFro
     } else {
         // 'ch2' / 'sum' do not depend on the target: one X_hat, then each target's copy of it
         // (times its mask with the postfilter)
-        cplx *X1 = arena_alloc_t<cplx>(ctx, (size_t)F * T);
-        GSS_REQUIRE(ctx, X1, GSS_ERR_NOMEM, "workspace sizing bug");
+        Workspace ws(ctx);
+        cplx *X1 = channel_pick_blocks(ws, F, T);
+        GSS_TRY(ws.status("channel pick of a targets call"));
         GSS_TRY(channel_pick_run(ctx, X, F, T, D, p->bf, X1));
         GSS_TRY(mask_mul_targets_run(ctx, X1, 0, Xhat, mx, F, T, S, p->postfilter == 1));
         GSS_TRY(arena_release(ctx, mark));
@@ -2093,20 +2092,16 @@ static int enhance_observation_targets_impl(gss_ctx *ctx, const gss_params *p, c
     GSS_TRY(check_pipeline_rest(ctx, p, D, N, K, N_act, &T, &T_act));
     const int F = p->stft_size / 2 + 1;
 
-    GSS_TRY(arena_reserve(ctx, targets_workspace(p, F, T, T_act, D, K, S)));
-    PipelineFront fr;
-    GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
-    double *mx = arena_alloc_t<double>(ctx, (size_t)S * F * T);
-    double *mn = arena_alloc_t<double>(ctx, (size_t)S * F * T);
-    cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)S * F * T);
-    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4 * (size_t)S);
-    GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
-    const size_t mark = ctx->arena_off;
     PipelineCall call;
     call.obs_type = obs_type;
+    GSS_TRY(arena_reserve(ctx, targets_workspace(p, F, T, T_act, D, K, S, /*blind=*/false)));
+    Workspace ws(ctx);
+    const PipelineBuffers fr = pipeline_blocks(ws, p, F, T, T_act, D, K, S, call);
+    GSS_TRY(ws.status("gss_enhance_observation_targets"));
+    const size_t mark = ctx->arena_off;
     GSS_TRY(run_front(ctx, p, call, obs, D, D, N, act, K, N_act, F, T, T_act, fr, mark, EmGuide{}));
-    return run_targets_tail(ctx, p, fr, F, T, T_act, D, K, S, targets, start_ctx, end_ctx, mx, mn,
-                            Xhat, ref, mark, out, taps);
+    return run_targets_tail(ctx, p, fr, F, T, T_act, D, K, S, targets, start_ctx, end_ctx, mark, out,
+                            taps);
 }
 
 extern "C" int gss_enhance_observation(gss_ctx *ctx, const gss_params *p, const double *obs,
@@ -2353,31 +2348,27 @@ extern "C" int gss_separate_observation(gss_ctx *ctx, const gss_params *p, const
     GSS_TRY(check_pipeline_rest(ctx, p, D, N, K, N, &T, &T_act));
     const int F = p->stft_size / 2 + 1, S = K;
 
-    GSS_TRY(arena_reserve(ctx, separate_workspace(p, F, T, D, K)));
-    PipelineFront fr;
-    GSS_TRY(alloc_front(ctx, p, F, T, T_act, D, K, &fr));
-    double *mx = arena_alloc_t<double>(ctx, (size_t)S * F * T);
-    double *mn = arena_alloc_t<double>(ctx, (size_t)S * F * T);
-    cplx *Xhat = arena_alloc_t<cplx>(ctx, (size_t)S * F * T);
-    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4 * (size_t)S);
-    GSS_REQUIRE(ctx, mx && mn && Xhat && ref, GSS_ERR_NOMEM, "workspace sizing bug");
-    const size_t mark = ctx->arena_off;
     PipelineCall call;
     call.entry = what;
     call.blind_init = init;
     call.blind_prior = prior;
+    GSS_TRY(arena_reserve(ctx, targets_workspace(p, F, T, T_act, D, K, S, /*blind=*/true)));
+    Workspace ws(ctx);
+    const PipelineBuffers fr = pipeline_blocks(ws, p, F, T, T_act, D, K, S, call);
+    GSS_TRY(ws.status(what));
+    const size_t mark = ctx->arena_off;
     GSS_TRY(run_front(ctx, p, call, obs, D, D, N, nullptr, K, N, F, T, T_act, fr, mark, EmGuide{}));
     if (power) {     // (reads X and gamma; the scores are not asked for)
-        double *scores = arena_alloc_t<double>(ctx, (size_t)K * T, "separate scores");
-        GSS_REQUIRE(ctx, scores, GSS_ERR_NOMEM, "workspace sizing bug");
+        double *scores = separate_scores_blocks(ws, K, T);
+        GSS_TRY(ws.status(what));
         GSS_TRY(pact_run(ctx, fr.X, fr.gamma, F, K, T, D, nullptr, scores, power));
         GSS_TRY(arena_release(ctx, mark));
     }
     GSS_TRY(copy_tap(ctx, gamma, fr.gamma, sizeof(double) * (size_t)F * K * T));
     int32_t targets[GSS_MAX_CLASSES];
     for (int s = 0; s < S; ++s) targets[s] = s;
-    return run_targets_tail(ctx, p, fr, F, T, T_act, D, K, S, targets, nullptr, nullptr, mx, mn,
-                            Xhat, ref, mark, out, taps);
+    return run_targets_tail(ctx, p, fr, F, T, T_act, D, K, S, targets, nullptr, nullptr, mark, out,
+                            taps);
 }
 
 extern "C" int gss_enhance_observation_host(gss_ctx *ctx, const gss_params *p,

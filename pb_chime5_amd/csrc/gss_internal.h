@@ -172,7 +172,7 @@ struct gss_ctx {
         int block;                      // index of the block since the last reserve
         size_t logical_off, bytes;      // the block as the plain arena would place it
         size_t guard_off, guard_bytes;  // physical: alignment slack + 256 bytes behind the block
-        const char *tag;                // arena_alloc's optional name, a string literal or NULL
+        const char *tag;                // the name Workspace::take gave it, a string literal
         bool reported;                  // a violated guard counts once
     };
     int debug_pattern = -1;
@@ -261,18 +261,43 @@ int gss_fail(gss_ctx *ctx, int code, const char *fmt, ...);
 // a reserve() survives it, nothing above a mark survives its release().
 int arena_reserve(gss_ctx *ctx, size_t bytes);
 void arena_reset(gss_ctx *ctx);
-void *arena_alloc(gss_ctx *ctx, size_t bytes, const char *tag = nullptr);
+void *arena_alloc(gss_ctx *ctx, size_t bytes, const char *tag);   // through a Workspace only
 int arena_release_debug(gss_ctx *ctx, size_t mark);
 static inline int arena_release(gss_ctx *ctx, size_t mark) {
     if (ctx->debug_pattern >= 0) return arena_release_debug(ctx, mark);
     ctx->arena_off = mark;
     return GSS_OK;
 }
-template <typename T>
-static inline T *arena_alloc_t(gss_ctx *ctx, size_t count, const char *tag = nullptr) {
-    return reinterpret_cast<T *>(arena_alloc(ctx, count * sizeof(T), tag));
-}
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
+// The blocks of a stage, written once: a stage's list function take()s them from a Workspace,
+// and the same list serves the run (Workspace(ctx): every take is an arena_alloc, in order) and
+// the stage's *_workspace_bytes() (Workspace(): take returns NULL and adds the block's aligned
+// size to `bytes`).  The measured sum bounds what the list bumps the arena by at whatever offset
+// the stage starts above a mark, up to the alignment of its first block (the pad every sizing
+// function adds).  A list takes an optional block by an option of its own; a sizing function
+// that is not told the option measures with the block taken.
+struct Workspace {
+    gss_ctx *ctx = nullptr;   // NULL: measuring
+    size_t bytes = 0;         // measuring: sum of the aligned block sizes
+    bool failed = false;      // allocating: a block came back NULL
+    Workspace() = default;
+    explicit Workspace(gss_ctx *c) : ctx(c) {}
+    template <typename T>
+    T *take(size_t count, const char *tag) {
+        if (!ctx) {
+            bytes += align_up(count * sizeof(T));
+            return nullptr;
+        }
+        T *p = reinterpret_cast<T *>(arena_alloc(ctx, count * sizeof(T), tag));
+        failed |= !p;
+        return p;
+    }
+    // allocating mode, after the list: the reserve of the entry point was too small for `stage`
+    int status(const char *stage) const {
+        return failed ? gss_fail(ctx, GSS_ERR_NOMEM, "%s: workspace sizing bug", stage) : GSS_OK;
+    }
+};
 
 // Profiling scope: records HIP events around a launch when enabled.
 struct ProfScope {
@@ -296,6 +321,7 @@ struct ProfScope {
 // ---------------------------------------------------------------- stage launchers
 // (device pointers, workspace from the arena, asynchronous on ctx->stream)
 size_t wpe_workspace_bytes(int F, int64_t T, int D, int taps, int delay);
+size_t wpe_inverse_power_workspace_bytes(int F, int64_t T);
 int wpe_inverse_power_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int psd_context,
                           double *w);
 // part: -1 = the whole call; 0 / 1 = one of two sets of frequencies that run side by side on
@@ -410,7 +436,8 @@ struct EmPriorArgs {
 };
 constexpr int PRIOR_MAX_SLICES = 32;    // slices of the column sum: `part` holds this many (K,T) planes
 size_t cacgmm_prior_workspace_bytes(int F, int64_t T, int K);
-int cacgmm_prior_alloc(gss_ctx *ctx, int F, int64_t T, int K, double *prior_out, EmPriorWork *w);
+// the block list of the mode (own_prior false: the caller's table, w.prior is left NULL for it)
+EmPriorWork cacgmm_prior_alloc(Workspace &ws, int F, int64_t T, int K, bool own_prior);
 int cacgmm_prior_estep_run(gss_ctx *ctx, const EmPriorArgs &a, int K, int mode);
 // prior = mean over the first nf frequencies of w.G (nf = 1: a frequency-independent table, copied)
 int cacgmm_prior_update_run(gss_ctx *ctx, const EmPriorWork &w, int nf, int K, int64_t T);

@@ -1277,19 +1277,33 @@ int masks_targets_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T
     return GSS_OK;
 }
 
+// The blocks of mvdr_run (rows = 2 weight rows, S targets) and of lcmv_run (rows = 3, S = 1):
+// every intermediate in S consecutive per-target blocks of the one-target layout.
+struct BfWork {
+    cplx *part;         // (S, F, nch, rows, NE) PSD partials
+    double *msum, *Wr;  // (S, F, rows) mask sums, (S, F, rows, T) packed weight rows
+    cplx *Phi, *W, *snr;
+    int32_t *ref;       // per target [0]: reference channel, [2]: fallback counter (LCMV)
+    int nch, cf;        // the chunks of the PSD pass
+};
+static BfWork bf_blocks(Workspace &ws, int F, int64_t T, int D, int S, int rows) {
+    const size_t NE = tri_count(D), SF = (size_t)S * F;
+    BfWork k;
+    k.nch = psd_chunks(F, T, &k.cf);
+    k.part = ws.take<cplx>(SF * k.nch * rows * NE, "beamformer psd partials");
+    k.msum = ws.take<double>(SF * rows, "beamformer mask sums");
+    k.Wr = ws.take<double>(SF * rows * T, "beamformer weight rows");
+    k.Phi = ws.take<cplx>(SF * 2 * D * D, "beamformer Phi");
+    k.W = ws.take<cplx>(SF * D * D, "beamformer W");
+    k.snr = ws.take<cplx>(SF * D * 2, "beamformer snr");
+    k.ref = ws.take<int32_t>(4 * (size_t)S, "beamformer ref");
+    return k;
+}
+
 size_t mvdr_workspace_bytes(int F, int64_t T, int D, int S) {
-    const size_t NE = tri_count(D);
-    int cf;
-    const int nch = psd_chunks(F, T, &cf);
-    size_t b = 0;
-    b += align_up(sizeof(cplx) * (size_t)S * F * nch * 2 * NE);
-    b += align_up(sizeof(double) * (size_t)S * F * 2);
-    b += align_up(sizeof(double) * (size_t)S * F * 2 * T);
-    b += align_up(sizeof(cplx) * (size_t)S * F * 2 * D * D);
-    b += align_up(sizeof(cplx) * (size_t)S * F * D * D);
-    b += align_up(sizeof(cplx) * (size_t)S * F * D * 2);
-    b += align_up(sizeof(int32_t) * 4 * (size_t)S);
-    return b + 4096;
+    Workspace ws;
+    bf_blocks(ws, F, T, D, S, 2);
+    return ws.bytes + 4096;
 }
 
 int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
@@ -1297,18 +1311,13 @@ int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double 
              int forced_ref, int S, bool targets) {
     // S targets (gss_enhance_observation_targets): masks (S,F,T), Xhat (S,T,F), ref_channel (S),
     // every intermediate in S consecutive per-target blocks of the one-target layout
-    const int NE = tri_count(D);
-    int cf;
-    const int nch = psd_chunks(F, T, &cf);
-    cplx *part = arena_alloc_t<cplx>(ctx, (size_t)S * F * nch * 2 * NE);
-    double *msum = arena_alloc_t<double>(ctx, (size_t)S * F * 2);
-    double *W2 = arena_alloc_t<double>(ctx, (size_t)S * F * 2 * T);
-    cplx *Phi = arena_alloc_t<cplx>(ctx, (size_t)S * F * 2 * D * D);
-    cplx *W = arena_alloc_t<cplx>(ctx, (size_t)S * F * D * D);
-    cplx *snr = arena_alloc_t<cplx>(ctx, (size_t)S * F * D * 2);
-    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4 * (size_t)S);
-    GSS_REQUIRE(ctx, part && msum && W2 && Phi && W && snr && ref, GSS_ERR_NOMEM,
-                "mvdr workspace");
+    Workspace ws(ctx);
+    const BfWork k = bf_blocks(ws, F, T, D, S, 2);
+    GSS_TRY(ws.status("mvdr"));
+    const int nch = k.nch, cf = k.cf;
+    cplx *part = k.part, *Phi = k.Phi, *W = k.W, *snr = k.snr;
+    double *msum = k.msum, *W2 = k.Wr;
+    int32_t *ref = k.ref;
     ctx->last_targets = targets ? S : 0;
     {
         GSS_PROF(ctx, targets ? "psd_targets" : "psd");
@@ -1409,24 +1418,39 @@ SegmentGeometry segment_geometry(int F, int64_t T, int64_t L) {
 }
 }  // namespace
 
+// The blocks of mvdr_segments_run for the geometry g (B segments).
+struct SegWork {
+    cplx *part;                     // (F, nch, 2, NE) PSD partials of the one pass over Y
+    double *msum, *W2;              // (F, B, 2) mask sums, (F, 2, T) packed weights
+    cplx *whole_part;               // the whole-window sums a segment falls back to
+    double *whole_msum;
+    cplx *wpart;                    // (B, F, 2, NE) every segment's window
+    double *wmsum;
+    cplx *Phi, *W, *snr, *snr_part;
+    int32_t *ref;                   // [0]: reference channel, [2]: fallback counter
+};
+static SegWork segments_blocks(Workspace &ws, int F, int64_t T, int D, const SegmentGeometry &g) {
+    const size_t NE = tri_count(D), B = g.B;
+    SegWork k;
+    k.part = ws.take<cplx>((size_t)F * g.nch * 2 * NE, "segments psd partials");
+    k.msum = ws.take<double>((size_t)F * B * 2, "segments mask sums");
+    k.W2 = ws.take<double>((size_t)F * 2 * T, "segments weight rows");
+    k.whole_part = ws.take<cplx>((size_t)F * 2 * NE, "segments whole-window partials");
+    k.whole_msum = ws.take<double>((size_t)F * 2, "segments whole-window mask sums");
+    k.wpart = ws.take<cplx>(B * F * 2 * NE, "segments window partials");
+    k.wmsum = ws.take<double>(B * F * 2, "segments window mask sums");
+    k.Phi = ws.take<cplx>(B * F * 2 * D * D, "segments Phi");
+    k.W = ws.take<cplx>(B * F * D * D, "segments W");
+    k.snr = ws.take<cplx>(B * F * D * 2, "segments snr");
+    k.snr_part = ws.take<cplx>(B * D * 2, "segments snr sums");
+    k.ref = ws.take<int32_t>(4, "segments ref");
+    return k;
+}
+
 size_t mvdr_segments_workspace_bytes(int F, int64_t T, int D, int64_t segment_frames) {
-    const size_t NE = tri_count(D);
-    const SegmentGeometry g = segment_geometry(F, T, segment_frames);
-    const size_t B = g.B;
-    size_t b = 0;
-    b += align_up(sizeof(cplx) * (size_t)F * g.nch * 2 * NE);    // part
-    b += align_up(sizeof(double) * (size_t)F * B * 2);           // msum
-    b += align_up(sizeof(double) * (size_t)F * 2 * T);           // W2
-    b += align_up(sizeof(cplx) * (size_t)F * 2 * NE);            // whole_part
-    b += align_up(sizeof(double) * (size_t)F * 2);               // whole_msum
-    b += align_up(sizeof(cplx) * B * F * 2 * NE);                // wpart
-    b += align_up(sizeof(double) * B * F * 2);                   // wmsum
-    b += align_up(sizeof(cplx) * B * F * 2 * D * D);             // Phi
-    b += align_up(sizeof(cplx) * B * F * D * D);                 // W
-    b += align_up(sizeof(cplx) * B * F * D * 2);                 // snr
-    b += align_up(sizeof(cplx) * B * D * 2);                     // snr_part
-    b += align_up(sizeof(int32_t) * 4);                          // ref
-    return b + 4096;
+    Workspace ws;
+    segments_blocks(ws, F, T, D, segment_geometry(F, T, segment_frames));
+    return ws.bytes + 4096;
 }
 
 int mvdr_segments_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
@@ -1434,22 +1458,13 @@ int mvdr_segments_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, cons
                       int32_t *ref_channel, int forced_ref) {
     const int NE = tri_count(D);
     const SegmentGeometry g = segment_geometry(F, T, seg.segment_frames);
-    const size_t B = g.B;
-    cplx *part = arena_alloc_t<cplx>(ctx, (size_t)F * g.nch * 2 * NE);
-    double *msum = arena_alloc_t<double>(ctx, (size_t)F * B * 2);
-    double *W2 = arena_alloc_t<double>(ctx, (size_t)F * 2 * T);
-    cplx *whole_part = arena_alloc_t<cplx>(ctx, (size_t)F * 2 * NE);
-    double *whole_msum = arena_alloc_t<double>(ctx, (size_t)F * 2);
-    cplx *wpart = arena_alloc_t<cplx>(ctx, B * F * 2 * NE);
-    double *wmsum = arena_alloc_t<double>(ctx, B * F * 2);
-    cplx *Phi = arena_alloc_t<cplx>(ctx, B * F * 2 * D * D);
-    cplx *W = arena_alloc_t<cplx>(ctx, B * F * D * D);
-    cplx *snr = arena_alloc_t<cplx>(ctx, B * F * D * 2);
-    cplx *snr_part = arena_alloc_t<cplx>(ctx, B * D * 2);
-    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);   // [0]: reference channel, [2]: fallback counter
-    GSS_REQUIRE(ctx, part && msum && W2 && whole_part && whole_msum && wpart && wmsum && Phi && W &&
-                         snr && snr_part && ref, GSS_ERR_NOMEM, "mvdr segments workspace");
-    int32_t *const fallbacks = ref + 2;
+    Workspace ws(ctx);
+    const SegWork k = segments_blocks(ws, F, T, D, g);
+    GSS_TRY(ws.status("mvdr segments"));
+    cplx *part = k.part, *whole_part = k.whole_part, *wpart = k.wpart;
+    double *msum = k.msum, *W2 = k.W2, *whole_msum = k.whole_msum, *wmsum = k.wmsum;
+    cplx *Phi = k.Phi, *W = k.W, *snr = k.snr, *snr_part = k.snr_part;
+    int32_t *ref = k.ref, *const fallbacks = ref + 2;
     ctx->last_targets = 0;
     GSS_HIP_CHECK(ctx, hipMemsetAsync(fallbacks, 0, sizeof(int32_t), ctx->stream));
     {
@@ -1508,11 +1523,21 @@ int mvdr_segments_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, cons
 }
 
 // ------------------------------------------------------------------ interferer-nulling LCMV
+struct LcmvMaskWork {
+    double *fmass;      // (F,K) mass of every class
+    int32_t *pick;      // the interferer
+};
+static LcmvMaskWork lcmv_masks_blocks(Workspace &ws, int F, int K) {
+    LcmvMaskWork k;
+    k.fmass = ws.take<double>((size_t)F * K, "lcmv masks fmass");
+    k.pick = ws.take<int32_t>(4, "lcmv masks pick");
+    return k;
+}
+
 size_t lcmv_masks_workspace_bytes(int F, int K) {
-    size_t b = 0;
-    b += align_up(sizeof(double) * (size_t)F * K);               // fmass
-    b += align_up(sizeof(int32_t) * 4);                          // pick
-    return b + 4096;
+    Workspace ws;
+    lcmv_masks_blocks(ws, F, K);
+    return ws.bytes + 4096;
 }
 
 int lcmv_masks_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T, int target,
@@ -1524,60 +1549,45 @@ int lcmv_masks_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T, i
         lo_end = sf >= 0 ? (sf < T ? sf : T) : (T + sf > 0 ? T + sf : 0);
         if (ef > 0) hi_begin = T - ef > 0 ? T - ef : 0;
     }
-    double *fmass = arena_alloc_t<double>(ctx, (size_t)F * K);
-    int32_t *pick = arena_alloc_t<int32_t>(ctx, 4);
-    GSS_REQUIRE(ctx, fmass && pick, GSS_ERR_NOMEM, "lcmv masks workspace");
+    Workspace ws(ctx);
+    const LcmvMaskWork k = lcmv_masks_blocks(ws, F, K);
+    GSS_TRY(ws.status("lcmv masks"));
     {
         GSS_PROF(ctx, "lcmv_pick");
         if (bf.interferer < 0) {
             hipLaunchKernelGGL(lcmv_mass_kernel, dim3(F, K), dim3(256), 0, ctx->stream, gamma, K, T,
-                               lo_end, hi_begin, fmass);
+                               lo_end, hi_begin, k.fmass);
             GSS_LAUNCH_CHECK(ctx, "lcmv_mass_kernel");
         }
-        hipLaunchKernelGGL(lcmv_pick_kernel, dim3(1), dim3(64), 0, ctx->stream, fmass, F, K, target,
-                           bf.candidates, (int)bf.interferer, pick);
+        hipLaunchKernelGGL(lcmv_pick_kernel, dim3(1), dim3(64), 0, ctx->stream, k.fmass, F, K, target,
+                           bf.candidates, (int)bf.interferer, k.pick);
         GSS_LAUNCH_CHECK(ctx, "lcmv_pick_kernel");
     }
     GSS_PROF(ctx, "masks3");
     const int64_t total = (int64_t)F * T;
     hipLaunchKernelGGL(masks3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       ctx->stream, gamma, F, K, T, target, pick, lo_end, hi_begin, mx, mi, mn,
+                       ctx->stream, gamma, F, K, T, target, k.pick, lo_end, hi_begin, mx, mi, mn,
                        interferer, ctx->status_dev);
     GSS_LAUNCH_CHECK(ctx, "masks3_kernel");
     return GSS_OK;
 }
 
 size_t lcmv_workspace_bytes(int F, int64_t T, int D) {
-    const size_t NE = tri_count(D);
-    int cf;
-    const int nch = psd_chunks(F, T, &cf);
-    size_t b = 0;
-    b += align_up(sizeof(cplx) * (size_t)F * nch * 3 * NE);      // part
-    b += align_up(sizeof(double) * (size_t)F * 3);               // msum
-    b += align_up(sizeof(double) * (size_t)F * 3 * T);           // W3
-    b += align_up(sizeof(cplx) * (size_t)F * 2 * D * D);         // Phi
-    b += align_up(sizeof(cplx) * (size_t)F * D * D);             // W
-    b += align_up(sizeof(cplx) * (size_t)F * D * 2);             // snr
-    b += align_up(sizeof(int32_t) * 4);                          // ref
-    return b + 4096;
+    Workspace ws;
+    bf_blocks(ws, F, T, D, 1, 3);
+    return ws.bytes + 4096;
 }
 
 int lcmv_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
              const double *mi, const double *mn, int ban, int forced_ref, double min_mass,
              cplx *Xhat, int32_t *ref_channel) {
-    const int NE = tri_count(D);
-    int cf;
-    const int nch = psd_chunks(F, T, &cf);
-    cplx *part = arena_alloc_t<cplx>(ctx, (size_t)F * nch * 3 * NE);
-    double *msum = arena_alloc_t<double>(ctx, (size_t)F * 3);
-    double *W3 = arena_alloc_t<double>(ctx, (size_t)F * 3 * T);
-    cplx *Phi = arena_alloc_t<cplx>(ctx, (size_t)F * 2 * D * D);
-    cplx *W = arena_alloc_t<cplx>(ctx, (size_t)F * D * D);
-    cplx *snr = arena_alloc_t<cplx>(ctx, (size_t)F * D * 2);
-    int32_t *ref = arena_alloc_t<int32_t>(ctx, 4);   // [0]: reference channel, [2]: fallback counter
-    GSS_REQUIRE(ctx, part && msum && W3 && Phi && W && snr && ref, GSS_ERR_NOMEM,
-                "lcmv workspace");
-    int32_t *const fallbacks = ref + 2;
+    Workspace ws(ctx);
+    const BfWork k = bf_blocks(ws, F, T, D, 1, 3);
+    GSS_TRY(ws.status("lcmv"));
+    const int nch = k.nch, cf = k.cf;
+    cplx *part = k.part, *Phi = k.Phi, *W = k.W, *snr = k.snr;
+    double *msum = k.msum, *W3 = k.Wr;
+    int32_t *ref = k.ref, *const fallbacks = ref + 2;
     ctx->last_targets = 0;
     GSS_HIP_CHECK(ctx, hipMemsetAsync(fallbacks, 0, sizeof(int32_t), ctx->stream));
     {

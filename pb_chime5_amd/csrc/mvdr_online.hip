@@ -244,13 +244,28 @@ size_t mol_lds_bytes(int D) {
 
 }  // namespace
 
-// for a thrown-away state its two matrices, the counter, and for ref_channel = -1 the
-// whole-window pass with the output it is not asked for
+// the counter and, for a thrown-away state, its two matrices
+struct MolWork {
+    int32_t *words;         // [0]: fallback counter, [1]: the window's ref
+    cplx *phi_x, *phi_n;
+};
+static MolWork mol_blocks(Workspace &ws, int F, int D, bool fresh) {
+    MolWork k;
+    k.words = ws.take<int32_t>(4, "online mvdr words");
+    k.phi_x = fresh ? ws.take<cplx>((size_t)F * D * D, "online mvdr phi_x") : nullptr;
+    k.phi_n = fresh ? ws.take<cplx>((size_t)F * D * D, "online mvdr phi_n") : nullptr;
+    return k;
+}
+// ref_channel = -1, above a mark: the output of the whole-window pass, which nobody asked for
+static cplx *mol_window_blocks(Workspace &ws, int F, int64_t T) {
+    return ws.take<cplx>((size_t)F * T, "online mvdr window X");
+}
+
 size_t mvdr_online_workspace_bytes(int F, int64_t T, int D, bool fresh, bool window_ref) {
-    size_t b = align_up(sizeof(int32_t) * 4);
-    if (fresh) b += 2 * align_up(sizeof(cplx) * (size_t)F * D * D);
-    if (window_ref) b += mvdr_workspace_bytes(F, T, D) + align_up(sizeof(cplx) * (size_t)F * T);
-    return b + 4096;
+    Workspace ws;
+    mol_blocks(ws, F, D, fresh);
+    if (window_ref) mol_window_blocks(ws, F, T);
+    return ws.bytes + (window_ref ? mvdr_workspace_bytes(F, T, D) : 0) + 4096;
 }
 
 int mvdr_online_init_run(gss_ctx *ctx, int F, int D, const cplx *Y, int64_t T, double loading,
@@ -271,12 +286,12 @@ int mvdr_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const 
                     const double *mn, int ban, double beta, double loading, int ref, cplx *phi_x,
                     cplx *phi_n, cplx *X, int64_t xs_f, int64_t xs_t, cplx *W,
                     int32_t *ref_out) {
-    int32_t *words = arena_alloc_t<int32_t>(ctx, 4);   // [0]: fallback counter, [1]: the window's ref
-    GSS_REQUIRE(ctx, words, GSS_ERR_NOMEM, "online MVDR workspace");
+    Workspace ws(ctx);
+    const MolWork k = mol_blocks(ws, F, D, !phi_x);
+    GSS_TRY(ws.status("online mvdr"));
+    int32_t *words = k.words;
     if (!phi_x) {
-        phi_x = arena_alloc_t<cplx>(ctx, (size_t)F * D * D);
-        phi_n = arena_alloc_t<cplx>(ctx, (size_t)F * D * D);
-        GSS_REQUIRE(ctx, phi_x && phi_n, GSS_ERR_NOMEM, "online MVDR workspace");
+        phi_x = k.phi_x, phi_n = k.phi_n;
         GSS_TRY(mvdr_online_init_run(ctx, F, D, Y, T, loading, phi_x, phi_n));
     }
     ctx->last_targets = 0;
@@ -284,8 +299,8 @@ int mvdr_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const 
     const int32_t *ref_dev = nullptr;
     if (ref < 0) {
         const size_t mark = ctx->arena_off;
-        cplx *Xw = arena_alloc_t<cplx>(ctx, (size_t)F * T);
-        GSS_REQUIRE(ctx, Xw, GSS_ERR_NOMEM, "online MVDR workspace");
+        cplx *Xw = mol_window_blocks(ws, F, T);
+        GSS_TRY(ws.status("online mvdr window"));
         GSS_TRY(mvdr_run(ctx, Y, F, T, D, mx, mn, ban, Xw, words + 1));
         GSS_TRY(arena_release(ctx, mark));
         ref_dev = words + 1;

@@ -166,15 +166,22 @@ void sums_launch(gss_ctx *ctx, const cplx *Y, const double *gamma, const double 
 }  // namespace
 
 // the partial planes (FS, K + 1, T)
+static double *pact_blocks(Workspace &ws, int F, int64_t T, int K) {
+    return ws.take<double>((size_t)sums_shares(F, T) * (K + 1) * T, "posterior activity partial planes");
+}
+
 size_t pact_workspace_bytes(int F, int64_t T, int K) {
-    return align_up(sizeof(double) * (size_t)sums_shares(F, T) * (K + 1) * T) + 4096;
+    Workspace ws;
+    pact_blocks(ws, F, T, K);
+    return ws.bytes + 4096;
 }
 
 int pact_run(gss_ctx *ctx, const cplx *Y, const double *gamma, int F, int K, int64_t T, int D,
              const double *W, double *scores, double *power) {
     const int FS = sums_shares(F, T);
-    double *part = arena_alloc_t<double>(ctx, (size_t)FS * (K + 1) * T);
-    GSS_REQUIRE(ctx, part, GSS_ERR_NOMEM, "posterior activity: workspace sizing bug");
+    Workspace ws(ctx);
+    double *part = pact_blocks(ws, F, T, K);
+    GSS_TRY(ws.status("posterior activity"));
     {
         GSS_PROF(ctx, "pact_sums");
         if (K <= 5) sums_launch<5>(ctx, Y, gamma, W, F, T, D, K, part);

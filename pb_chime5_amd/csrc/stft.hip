@@ -442,8 +442,15 @@ int ilog2(int n) {
 
 }  // namespace
 
+// the iSTFT's only block: the windowed frames of `frames` spectra before the overlap-add
+static double *istft_blocks(Workspace &ws, int64_t frames, int size) {
+    return ws.take<double>((size_t)frames * size, "istft frames");
+}
+
 size_t stft_workspace_bytes(int64_t T, int size) {
-    return align_up(sizeof(double) * (size_t)(T + 1) * size) + 4096;
+    Workspace ws;
+    istft_blocks(ws, T + 1, size);   // (one frame of slack)
+    return ws.bytes + 4096;
 }
 
 template <int PAIRS, typename TIn>
@@ -497,8 +504,9 @@ int istft_run(gss_ctx *ctx, const cplx *X, int64_t T, int fading, double *x, int
     const int size = ctx->stft_size, shift = ctx->stft_shift;
     const int pad = fading ? size - shift : 0;
     const int64_t n_out = gss_istft_num_samples(T, size, shift, fading);
-    double *frm = arena_alloc_t<double>(ctx, (size_t)S * T * size);
-    GSS_REQUIRE(ctx, frm, GSS_ERR_NOMEM, "istft workspace");
+    Workspace ws(ctx);
+    double *frm = istft_blocks(ws, (int64_t)S * T, size);
+    GSS_TRY(ws.status("istft"));
     if ((size & (size - 1)) != 0) {
         GSS_PROF(ctx, S > 1 ? "istft_frames_targets" : "istft_frames");
         const size_t lds = sizeof(cplx) * (size / 2 + size / 2 + 1);

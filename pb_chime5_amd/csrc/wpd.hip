@@ -159,33 +159,45 @@ int wpd_context_gate_run(gss_ctx *ctx, int64_t T, int64_t start_frames, int64_t 
     return GSS_OK;
 }
 
+// the blocks that live through the iterations; the WPE and the MVDR run above them
+struct WpdWork {
+    double *a, *mxg;    // (F,T) weights of the iteration, mask * gate
+    cplx *Z;            // (F,T,D) dereverberated observation
+};
+static WpdWork wpd_blocks(Workspace &ws, int F, int64_t T, int D) {
+    WpdWork k;
+    k.a = ws.take<double>((size_t)F * T, "wpd a");
+    k.mxg = ws.take<double>((size_t)F * T, "wpd mask gate");
+    k.Z = ws.take<cplx>((size_t)F * T * D, "wpd Z");
+    return k;
+}
+
 size_t wpd_workspace_bytes(int F, int64_t T, int D, int taps, int delay) {
-    size_t b = 0;
-    b += 2 * align_up(sizeof(double) * (size_t)F * T);       // a, m g
-    b += align_up(sizeof(cplx) * (size_t)F * T * D);         // Z
-    b += std::max(wpe_workspace_bytes(F, T, D, taps, delay), mvdr_workspace_bytes(F, T, D));
-    return b + 4096;
+    Workspace ws;
+    wpd_blocks(ws, F, T, D);
+    return ws.bytes + 4096 +
+           std::max(wpe_workspace_bytes(F, T, D, taps, delay), mvdr_workspace_bytes(F, T, D));
 }
 
 int wpd_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mask,
             const uint8_t *gate, const gss_bf_wpd &bf, int forced_ref, cplx *Xhat,
             int32_t *ref_channel) {
-    double *a = arena_alloc_t<double>(ctx, (size_t)F * T);
-    double *mxg = arena_alloc_t<double>(ctx, (size_t)F * T);
-    cplx *Z = arena_alloc_t<cplx>(ctx, (size_t)F * T * D);
-    GSS_REQUIRE(ctx, a && mxg && Z, GSS_ERR_NOMEM, "wpd workspace");
+    Workspace ws(ctx);
+    const WpdWork k = wpd_blocks(ws, F, T, D);
+    GSS_TRY(ws.status("wpd"));
     const size_t mark = ctx->arena_off;
     for (int it = 0; it < bf.iterations; ++it) {
         if (it == 0)
-            GSS_TRY(wpd_weights_run(ctx, Y, mask, nullptr, gate, F, T, D, bf.power_floor, a, mxg));
+            GSS_TRY(wpd_weights_run(ctx, Y, mask, nullptr, gate, F, T, D, bf.power_floor, k.a, k.mxg));
         else
-            GSS_TRY(wpd_weights_run(ctx, nullptr, nullptr, Xhat, gate, F, T, D, bf.power_floor, a,
+            GSS_TRY(wpd_weights_run(ctx, nullptr, nullptr, Xhat, gate, F, T, D, bf.power_floor, k.a,
                                     nullptr));
-        const WpeCallerWeights cw{a, GSS_STATUS_WPD_ZERO_PIVOTS, it > 0};
-        GSS_TRY(wpe_run(ctx, Y, F, T, D, bf.taps, bf.delay, 1, 0, Z, -1, 0, &cw));
+        const WpeCallerWeights cw{k.a, GSS_STATUS_WPD_ZERO_PIVOTS, it > 0};
+        GSS_TRY(wpe_run(ctx, Y, F, T, D, bf.taps, bf.delay, 1, 0, k.Z, -1, 0, &cw));
         GSS_TRY(arena_release(ctx, mark));
         // (the reference channel is chosen anew in every iteration; the last one's stays)
-        GSS_TRY(mvdr_run(ctx, Z, F, T, D, mxg, a, bf.ban, Xhat, ref_channel, /*gev=*/0, forced_ref));
+        GSS_TRY(mvdr_run(ctx, k.Z, F, T, D, k.mxg, k.a, bf.ban, Xhat, ref_channel, /*gev=*/0,
+                         forced_ref));
         GSS_TRY(arena_release(ctx, mark));
     }
     return GSS_OK;

@@ -1946,13 +1946,36 @@ static int corr_tiles_pairs(int n, int D, int c, std::vector<CorrTile> &tiles) {
 
 static int corr_padf(int D, int ct) { return (ct + D - 1) / D + 1; }
 
-size_t wpe_workspace_bytes(int F, int64_t T, int D, int taps, int delay) {
+// The blocks of wpe_run.  own_w: the weights of the power pass (not with the caller's weights);
+// smoothed: the raw power (psd_context > 0; NULL without smoothing: the power kernel's two
+// __restrict__ outputs must not alias).
+struct WpeWork {
+    double *w, *raw;
+    cplx *R, *P;     // (F,n,n) correlation matrix, (F,n,D) correlation vector / filter
+};
+static WpeWork wpe_blocks(Workspace &ws, int F, int64_t T, int D, int taps, bool own_w,
+                          bool smoothed) {
     const size_t n = (size_t)taps * D;
-    size_t b = 0;
-    b += 2 * align_up(sizeof(double) * (size_t)F * T);   // w, raw power (psd_context > 0)
-    b += align_up(sizeof(cplx) * (size_t)F * n * n);     // R
-    b += align_up(sizeof(cplx) * (size_t)F * n * D);     // P / G
-    return b + 4096;
+    WpeWork k;
+    k.w = own_w ? ws.take<double>((size_t)F * T, "wpe w") : nullptr;
+    k.raw = smoothed ? ws.take<double>((size_t)F * T, "wpe raw power") : nullptr;
+    k.R = ws.take<cplx>((size_t)F * n * n, "wpe R");
+    k.P = ws.take<cplx>((size_t)F * n * D, "wpe P");
+    return k;
+}
+static double *wpe_inverse_power_blocks(Workspace &ws, int F, int64_t T, bool smoothed) {
+    return smoothed ? ws.take<double>((size_t)F * T, "wpe raw power") : nullptr;
+}
+
+size_t wpe_workspace_bytes(int F, int64_t T, int D, int taps, int delay) {
+    Workspace ws;
+    wpe_blocks(ws, F, T, D, taps, true, true);
+    return ws.bytes + 4096;
+}
+size_t wpe_inverse_power_workspace_bytes(int F, int64_t T) {
+    Workspace ws;
+    wpe_inverse_power_blocks(ws, F, T, true);
+    return ws.bytes + 4096;
 }
 
 static int wpe_power_launch(gss_ctx *ctx, const cplx *cur, int F, int64_t T, int D,
@@ -1971,8 +1994,9 @@ static int wpe_power_launch(gss_ctx *ctx, const cplx *cur, int F, int64_t T, int
 // gss_wpe_inverse_power: the weights of one WPE iteration on their own
 int wpe_inverse_power_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int psd_context,
                           double *w) {
-    double *raw = psd_context > 0 ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
-    GSS_REQUIRE(ctx, raw || psd_context == 0, GSS_ERR_NOMEM, "wpe power workspace");
+    Workspace ws(ctx);
+    double *raw = wpe_inverse_power_blocks(ws, F, T, psd_context > 0);
+    GSS_TRY(ws.status("wpe inverse power"));
     return wpe_power_launch(ctx, Y, F, T, D, psd_context, raw, w);
 }
 
@@ -1993,13 +2017,12 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
     GSS_REQUIRE(ctx, !cw || (cw->w && iterations == 1 && part < 0), GSS_ERR_INVALID,
                 "wpe: the caller's weights serve one iteration of a whole call");
     // (the caller's weights: no power pass and no buffer for one; every launch below is the same)
-    double *w_own = cw ? nullptr : arena_alloc_t<double>(ctx, (size_t)F * T);
+    Workspace ws(ctx);
+    const WpeWork k = wpe_blocks(ws, F, T, D, taps, !cw, psd_context > 0);
+    GSS_TRY(ws.status("wpe"));
+    double *w_own = k.w, *raw = k.raw;
     const double *w = cw ? cw->w : w_own;
-    // (NULL without smoothing: the kernel's two __restrict__ outputs must not alias)
-    double *raw = psd_context > 0 ? arena_alloc_t<double>(ctx, (size_t)F * T) : nullptr;
-    cplx *R = arena_alloc_t<cplx>(ctx, (size_t)F * n * n);
-    cplx *P = arena_alloc_t<cplx>(ctx, (size_t)F * n * D);
-    GSS_REQUIRE(ctx, w && (raw || psd_context == 0) && R && P, GSS_ERR_NOMEM, "wpe workspace");
+    cplx *R = k.R, *P = k.P;
 
     // tile lists: correlation tiles, then one trailing-update list per block column
     std::vector<CorrTile> tiles;

@@ -292,13 +292,27 @@ __global__ __launch_bounds__(WOL_MEM_THREADS) void wpe_online_mem_kernel(WolArgs
 
 bool wpe_online_uses_memory_form(int n, bool force_mem) { return force_mem || n > WOL_ONCHIP_MAX_N; }
 
-// sigma, then for a fresh state its buffers, then the new history
-size_t wpe_online_workspace_bytes(int F, int64_t T, int A, int C, int taps, int delay, bool fresh) {
+// sigma, then for a fresh state its buffers.  hist: the fresh state's history, or, with the
+// caller's state, the new history (one element more than L C: never an empty block).
+struct WolWork {
+    double *sigma;
+    cplx *P, *G, *hist;
+};
+static WolWork wol_blocks(Workspace &ws, int F, int64_t T, int A, int C, int taps, int delay,
+                          bool fresh) {
     const size_t probs = (size_t)F * A, n = (size_t)taps * C, L = (size_t)taps + delay;
-    size_t b = align_up(sizeof(double) * probs * (size_t)std::max<int64_t>(T, 1));
-    if (fresh) b += align_up(sizeof(cplx) * probs * n * n) + align_up(sizeof(cplx) * probs * n * C);
-    b += 2 * align_up(sizeof(cplx) * probs * L * C + 16);
-    return b + 4096;
+    WolWork k;
+    k.sigma = ws.take<double>(probs * (size_t)T, "online wpe sigma");
+    k.P = fresh ? ws.take<cplx>(probs * n * n, "online wpe P") : nullptr;
+    k.G = fresh ? ws.take<cplx>(probs * n * C, "online wpe G") : nullptr;
+    k.hist = ws.take<cplx>(probs * L * C + 1, fresh ? "online wpe history" : "online wpe new history");
+    return k;
+}
+
+size_t wpe_online_workspace_bytes(int F, int64_t T, int A, int C, int taps, int delay, bool fresh) {
+    Workspace ws;
+    wol_blocks(ws, F, std::max<int64_t>(T, 1), A, C, taps, delay, fresh);
+    return ws.bytes + 4096;
 }
 
 int wpe_online_init_run(gss_ctx *ctx, int F, int A, int C, int taps, int delay, cplx *P, cplx *G,
@@ -321,19 +335,15 @@ int wpe_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int A, int C, 
     const int n = taps * C, L = taps + delay;
     const size_t probs = (size_t)F * A;
     const bool fresh = P == nullptr;
-    double *sigma = arena_alloc_t<double>(ctx, probs * (size_t)T);
-    cplx *hist_new = nullptr;
+    Workspace ws(ctx);
+    const WolWork k = wol_blocks(ws, F, T, A, C, taps, delay, fresh);
+    GSS_TRY(ws.status("online wpe"));
+    double *sigma = k.sigma;
+    cplx *hist_new = fresh ? nullptr : k.hist;
     if (fresh) {
-        P = arena_alloc_t<cplx>(ctx, probs * n * n);
-        G = arena_alloc_t<cplx>(ctx, probs * n * C);
-        hist = arena_alloc_t<cplx>(ctx, probs * L * C + 1);
-        GSS_REQUIRE(ctx, P && G && hist, GSS_ERR_NOMEM, "online WPE workspace");
+        P = k.P, G = k.G, hist = k.hist;
         GSS_TRY(wpe_online_init_run(ctx, F, A, C, taps, delay, P, G, hist));
-    } else {
-        hist_new = arena_alloc_t<cplx>(ctx, probs * L * C + 1);
-        GSS_REQUIRE(ctx, hist_new, GSS_ERR_NOMEM, "online WPE workspace");
     }
-    GSS_REQUIRE(ctx, sigma, GSS_ERR_NOMEM, "online WPE workspace");
     WolArgs a{Y, X, P, G, hist, sigma, T, A, C, taps, delay, n, L, alpha, 1.0 / alpha};
     {
         GSS_PROF(ctx, "wpe_online_sigma");
