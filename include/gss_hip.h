@@ -93,7 +93,10 @@ typedef enum {
  * descriptors.  So were gss_cacgmm_align, gss_cacgmm_model_permute and gss_last_align_moved with
  * the gss_align_plan descriptor.  So were gss_mvdr_online_init, gss_mvdr_online,
  * gss_last_mvdr_online_fallbacks and gss_enhance_observation_bf_online with the
- * gss_mvdr_online_state and gss_bf_online descriptors. */
+ * gss_mvdr_online_state and gss_bf_online descriptors.  So were gss_cacgmm_online_init,
+ * gss_cacgmm_online, gss_cacgmm_online_model, gss_last_cacgmm_online_fallbacks and
+ * gss_enhance_observation_gss_online with the gss_cacgmm_online_state and gss_em_online
+ * descriptors. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -741,6 +744,82 @@ int gss_mvdr_online(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D
 /* (frequency, frame) pairs of the last online MVDR on this context that fell back (synchronises). */
 int gss_last_mvdr_online_fallbacks(gss_ctx *ctx, int64_t *count_host);
 
+/* ---- online CACGMM ----------------------------------------------------------
+ * The recursive (online) EM of the complex angular central Gaussian mixture: the class statistics
+ * are running sums that forget, frame t is classified by the model of the frames before it and
+ * then enters the sums, and the state is carried between calls.  (Entry points only, looked up by
+ * the binding: revision still 7.)  One problem per frequency f with D channels and K classes.  The
+ * state is, per class, a Hermitian S_k (D,D) and a mass n_k > 0; the model they stand for is
+ * B_k = S_k / n_k, pi_k = n_k / sum_j n_j.  For each frame t, in order, with y = Y[f,t,:], m_kt
+ * the mask (1 without one) and beta = cfg->forget:
+ *    z       = y / max(||y||, tiny)
+ *    q_k     = max(|z^H B_k^-1 z|, tiny),  l_k = ln det B_k    from a Cholesky factor of S_k; a
+ *              pivot that is not > 0 or not finite makes k a FALLBACK class for this frame:
+ *              B_k = I (q_k = max(||z||^2, tiny), l_k = 0), counted
+ *    gamma_k = exp(lp_k - max_j lp_j) pi_k m_kt / max(sum, tiny),  lp_k = -D ln q_k - l_k
+ *              (CACGMM.predict, affiliation_eps = 0; every class masked off: zeros)
+ *    gamma[f,k,t] = gamma_k          the model of the frames BEFORE t: causal, zero look-ahead
+ *    ||y|| == 0 exactly: the state is left alone (no decay, no update); else with
+ *    g_k = clip(gamma_k, 1e-10, 1 - 1e-10):
+ *    S_k <- beta S_k + g_k D z z^H / max(q_k, 10 tiny),    n_k <- beta n_k + g_k
+ * There is no eigenvalue normalisation and no eigenvalue floor: the density does not depend on the
+ * scale of B_k, and the decaying start term plus the clip keep every S_k of full rank.
+ * K is limited to GSS_CACGMM_ONLINE_MAX_CLASSES (one wave per class in one workgroup). */
+#define GSS_CACGMM_ONLINE_MAX_CLASSES 8
+typedef struct {
+    gss_cplx *s;               /* (F, K, D, D) row-major; a reader takes the upper triangle and the real
+                                  part of the diagonal; on return both triangles are stored, the lower
+                                  the exact conjugate of the upper, diagonal imaginary parts 0 */
+    double *n;                 /* (F, K) */
+    int32_t F, K, D;
+} gss_cacgmm_online_state;     /* caller-owned, like gss_mvdr_online_state */
+
+typedef struct {
+    double forget;             /* beta, in (0, 1] */
+    double prior_mass;         /* of a fresh state; read only when `state` is NULL */
+} gss_em_online;
+
+/* model == NULL: the fresh state S_k = prior_mass I, n_k = prior_mass (all classes identical: only
+ * a mask tells them apart, and without one every posterior stays exactly 1 / K).  model != NULL:
+ * n_k = model_mass * weight_k, S_k = n_k * precision_k^-1, inverted on the device from a Cholesky
+ * factor of the precision; prior_mass is not read.  A precision without a factor is
+ * GSS_ERR_INVALID AFTER the launch (this call synchronises), the message gives the count and the
+ * state holds n_k I for those classes.
+ * GSS_ERR_INVALID before any launch: a NULL state or state field, state->F / K / D other than
+ * F / K / D, F < 1, the mass that is read not finite or <= 0, a NULL field of model.
+ * GSS_ERR_UNSUPPORTED: D outside [1, GSS_MAX_CHANNELS], K outside
+ * [1, GSS_CACGMM_ONLINE_MAX_CLASSES]. */
+int gss_cacgmm_online_init(gss_ctx *ctx, int F, int K, int D, double prior_mass,
+                           const gss_cacgmm_model *model, double model_mass,
+                           gss_cacgmm_online_state *state);
+
+/* Y (F,T,D) -> gamma (F,K,T).  guidance: only the mask fields are read; NULL or no mask: m = 1.
+ * `state` is read, advanced by T frames and written back; NULL: a fresh state of cfg->prior_mass
+ * from the workspace, thrown away.  T = 0 is a no-op.  One persistent workgroup per frequency
+ * walks the frames, one wave per class with S_k in registers; the kernel form and every order of
+ * summation depend on D and K alone, so a recording fed in blocks through one state gives the
+ * bits of the single call, and the same call gives the same bits.
+ * GSS_ERR_INVALID (the message names the argument), before any launch: a NULL pointer other than
+ * guidance / state, a NULL state field, state->F / K / D other than F / K / D, F < 1, T < 0,
+ * forget outside (0, 1] or not finite, prior_mass not finite or <= 0, the stride errors of the
+ * mask as gss_cacgmm_guided.  GSS_ERR_UNSUPPORTED: D or K out of range as above. */
+int gss_cacgmm_online(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                      const gss_guidance *guidance, int K, const gss_em_online *cfg,
+                      gss_cacgmm_online_state *state, double *gamma_dev);
+
+/* The model a state stands for: precision = B_k^-1 (both triangles), log_det = ln det B_k,
+ * weight = pi_k.  gss_cacgmm_predict with it on a frame gives, to rounding, the posteriors
+ * gss_cacgmm_online gives that frame when fed next.  A class whose S_k has no Cholesky factor
+ * comes out as the identity (log_det 0) the recursion falls back to, counted where
+ * gss_last_cacgmm_online_fallbacks reads.  model_out must not share buffers with the state.
+ * GSS_ERR_INVALID: a NULL state, model_out or field, F / K < 1; GSS_ERR_UNSUPPORTED as above. */
+int gss_cacgmm_online_model(gss_ctx *ctx, const gss_cacgmm_online_state *state,
+                            const gss_cacgmm_model *model_out);
+
+/* (frequency, frame, class) triples of the last online CACGMM on this context that fell back
+ * (synchronises). */
+int gss_last_cacgmm_online_fallbacks(gss_ctx *ctx, int64_t *count_host);
+
 /* beamform_gev_from_masks (beamforming_wrapper.py:77-89,192-208): masked PSD
  * matrices, principal generalised eigenvector of (Phi_X, Phi_N) with
  * w^H Phi_N w = 1 (phase arbitrary, as upstream), optional BAN, apply.
@@ -968,6 +1047,24 @@ int gss_enhance_observation_bf_online(gss_ctx *ctx, const gss_params *params,
                                       int64_t end_context_samples,
                                       const gss_bf_online *cfg,
                                       double *out_dev, const gss_debug_taps *taps);
+
+/* gss_enhance_observation with gss_cacgmm_online (a fresh state of em->prior_mass per call, the
+ * mask the call's frame activity) in the place of the guided EM; bss_iterations and
+ * bss_iterations_post are not read.  bf == NULL: the whole-window beamformer of params follows.
+ * bf != NULL: gss_mvdr_online follows as in gss_enhance_observation_bf_online, and with
+ * bf->wpe_online the online WPE precedes -- all three online stages in one call.  The masks and
+ * everything downstream are unchanged.
+ * GSS_ERR_INVALID: em NULL, forget outside (0, 1] or not finite, prior_mass not finite or <= 0,
+ * and with bf the errors of gss_enhance_observation_bf_online.  GSS_ERR_UNSUPPORTED:
+ * K > GSS_CACGMM_ONLINE_MAX_CLASSES. */
+int gss_enhance_observation_gss_online(gss_ctx *ctx, const gss_params *params,
+                                       const double *obs_dev, int D, int64_t N,
+                                       const uint8_t *act_dev, int K, int64_t N_act,
+                                       int target_index,
+                                       int64_t start_context_samples,
+                                       int64_t end_context_samples,
+                                       const gss_em_online *em, const gss_bf_online *bf,
+                                       double *out_dev, const gss_debug_taps *taps);
 
 /* gss_enhance_observation plus gss_posterior_activity on the pipeline's own post-WPE observation
  * and its posteriors before context zeroing (what the taps Obs_ftd and gamma show), nothing

@@ -96,6 +96,18 @@ class GssBfOnline(ctypes.Structure):
                 ('wpe_alpha', ctypes.c_double)]
 
 
+class GssCacgmmOnlineState(ctypes.Structure):
+    """gss_cacgmm_online_state: the running sums S (F,K,D,D), complex, and the masses n (F,K) of
+    the online CACGMM, in HBM."""
+    _fields_ = [('s', c_void_p), ('n', c_void_p), ('F', ctypes.c_int32), ('K', ctypes.c_int32),
+                ('D', ctypes.c_int32)]
+
+
+class GssEmOnline(ctypes.Structure):
+    """gss_em_online: the online CACGMM's forgetting factor and the mass of a fresh state."""
+    _fields_ = [('forget', ctypes.c_double), ('prior_mass', ctypes.c_double)]
+
+
 class GssWpeOnlineCfg(ctypes.Structure):
     """gss_wpe_online_cfg: the forgetting factor of the online WPE in the fused call."""
     _fields_ = [('alpha', ctypes.c_double)]
@@ -224,6 +236,17 @@ SIGNATURES = {
                                 ctypes.POINTER(GssMvdrOnlineState), c_void_p, c_void_p]),
     'gss_last_mvdr_online_fallbacks': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_enhance_observation_bf_online': _fused(ctypes.POINTER(GssBfOnline)),
+    'gss_cacgmm_online_init': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double,
+                                       ctypes.POINTER(GssCacgmmModel), ctypes.c_double,
+                                       ctypes.POINTER(GssCacgmmOnlineState)]),
+    'gss_cacgmm_online': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
+                                  ctypes.POINTER(GssGuidance), c_int, ctypes.POINTER(GssEmOnline),
+                                  ctypes.POINTER(GssCacgmmOnlineState), c_void_p]),
+    'gss_cacgmm_online_model': (c_int, [c_void_p, ctypes.POINTER(GssCacgmmOnlineState),
+                                        ctypes.POINTER(GssCacgmmModel)]),
+    'gss_last_cacgmm_online_fallbacks': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'gss_enhance_observation_gss_online': _fused(ctypes.POINTER(GssEmOnline),
+                                                 ctypes.POINTER(GssBfOnline)),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,
@@ -552,6 +575,11 @@ class Context:
         """(frequency, frame) pairs of the last online MVDR on this context whose noise matrix had
         no Cholesky factor (synchronises)."""
         return self._last('gss_last_mvdr_online_fallbacks', ctypes.c_int64)
+
+    def last_cacgmm_online_fallbacks(self):
+        """(frequency, frame, class) triples of the last online CACGMM on this context whose S_k had
+        no Cholesky factor (synchronises)."""
+        return self._last('gss_last_cacgmm_online_fallbacks', ctypes.c_int64)
 
     def workspace_bytes(self):
         return int(self.lib.gss_workspace_bytes(self.handle))

@@ -231,6 +231,55 @@ class GSS:
     # frequency (`ops.cacgmm_posteriors_shared_prior`; pb_bss weight_constant_axis=-3, which the
     # reference never calls).  Off: the reference's model, every call as before.
     shared_prior: bool = False
+    # Online CACGMM (an addition, see ops.cacgmm_posteriors_online): the recursive EM in the place
+    # of the iterated one -- running sums that forget at the rate ``forget``, frame t classified
+    # by the model of the frames before it, from a fresh state of ``prior_mass`` per utterance,
+    # masked by the activity; ``iterations`` / ``iterations_post`` are not read.  forget = 0.99
+    # and prior_mass = 1.0 are choices, not measurements.  Unread without ``online``.
+    online: bool = False
+    forget: float = ops.GSS_ONLINE_FORGET
+    prior_mass: float = ops.GSS_ONLINE_PRIOR_MASS
+
+    def __post_init__(self):
+        assert self.online is True or self.online is False, self.online
+        if self.online:
+            if self.shared_prior:
+                raise NotImplementedError(
+                    'gss_online with shared_prior: the online mixture model has a weight per '
+                    'class and frequency')
+            ops.check_gss_online(self.forget, self.prior_mass)
+        else:
+            for name, value, default in (('gss_forget', self.forget, ops.GSS_ONLINE_FORGET),
+                                         ('gss_prior_mass', self.prior_mass,
+                                          ops.GSS_ONLINE_PRIOR_MASS)):
+                if value != default:
+                    raise NotImplementedError(f'{name}={value!r} without gss_online: nobody reads it')
+
+    @property
+    def online_settings(self):
+        """The keyword arguments of the online calls in ``ops``, or None."""
+        if not self.online:
+            return None
+        return dict(forget=self.forget, prior_mass=self.prior_mass)
+
+    def _call_online(self, Obs, acitivity_freq, debug, initialization):
+        """The activity is the mask; its weights have nowhere to go (there is no initialisation:
+        the start is the fresh state)."""
+        if initialization is not None:
+            raise NotImplementedError(
+                'gss_online with an initialization: the online mixture model starts from its '
+                'fresh state, guided by the mask alone')
+        source_active_mask = np.asarray(acitivity_freq) != 0
+        posterior, fallbacks = ops.cacgmm_posteriors_online(
+            Obs, source_active_mask, forget=self.forget, prior_mass=self.prior_mass,
+            return_fallbacks=True)
+        if debug:
+            def learned():
+                raise NotImplementedError(
+                    "GSS(online=True) keeps no 'learned' model: run ops.cacgmm_posteriors_online "
+                    'with a state and ask it to_model()')
+            self.locals = _DebugLocals(locals(), learned)
+        return posterior
 
     def __call__(self, Obs, acitivity_freq, debug=False, *, initialization=None):
         """``acitivity_freq`` (K,T), or (K,T,F) for guidance that differs by frequency: zero =
@@ -239,6 +288,8 @@ class GSS:
         (K,T,F): initial affiliations used as given instead of the ones derived from the
         activity (a neural mask, the posteriors of an earlier pass).  A 0/1 activity without
         ``initialization`` takes the unweighted call; everything else the guided one."""
+        if self.online:
+            return self._call_online(Obs, acitivity_freq, debug, initialization)
         if self.shared_prior:
             return self._call_shared_prior(Obs, acitivity_freq, debug, initialization)
         binary = ops.activity_is_binary(acitivity_freq, initialization)
@@ -533,6 +584,16 @@ class Enhancer:
         if self._bf_online() is not None and self.channel_keep is not None:
             raise NotImplementedError(
                 'bf_online with channel_keep: the online beamformer has no selection')
+        if self._gss_online() is not None:
+            for name, on in (('bf_segment_frames', self._bf_segments() is not None),
+                             ('bf_null_interferer', self._bf_null()),
+                             ('channel_keep', self.channel_keep is not None),
+                             (f'bf={getattr(self.bf_block, "type", None)!r}',
+                              self._bf_wpd() is not None)):
+                if on:
+                    raise NotImplementedError(
+                        f'gss_online with {name}: the online mixture model feeds the whole-window '
+                        'and the online MVDR on all channels only')
         if self.channel_keep is None:
             return
         ops.check_channel_keep(self.channel_keep)
@@ -694,10 +755,11 @@ class Enhancer:
         # (a segment-wise beamformer has no pipelined pcm16 entry point: one at a time; neither
         # has the posterior activity of a refined RTTM)
         # (nor has the WPD: the pipelined path is out of its scope)
-        # (nor has the online WPE, nor the online beamformer)
+        # (nor has the online WPE, nor the online beamformer, nor the online mixture model)
         if (self.inflight <= 1 or not self._fusable() or self._bf_segments() is not None
                 or refined_rttm or self._bf_wpd() is not None
-                or self._wpe_online() is not None or self._bf_online() is not None):
+                or self._wpe_online() is not None or self._bf_online() is not None
+                or self._gss_online() is not None):
             for ex in examples:
                 try:
                     if refined_rttm:
@@ -1044,6 +1106,16 @@ class Enhancer:
                 f'{what} with bf_online: the online beamformer is built for enhance_observation, '
                 'enhance_example and enhance_session only')
 
+    def _gss_online(self):
+        """The online settings of the mixture model (``GSS.online_settings``) or None."""
+        return getattr(getattr(self, 'gss_block', None), 'online_settings', None)
+
+    def _no_gss_online(self, what):
+        if self._gss_online() is not None:
+            raise NotImplementedError(
+                f'{what} with gss_online: the online mixture model is built for '
+                'enhance_observation, enhance_example and enhance_session only')
+
     def _wpe_online(self):
         """The forgetting factor of an online WPE block (``WPE.online``) or None."""
         block = getattr(self, 'wpe_block', None)
@@ -1063,6 +1135,7 @@ class Enhancer:
         self._no_channel_keep(what)
         self._no_wpd(what)
         self._no_bf_online(what)
+        self._no_gss_online(what)
         if self.wpe_per_array:
             raise NotImplementedError(
                 f'{what} with wpe_per_array: the annotation-free path runs one joint WPE')
@@ -1074,6 +1147,7 @@ class Enhancer:
         self._no_channel_keep(what)
         self._no_wpd(what)
         self._no_bf_online(what)
+        self._no_gss_online(what)
         self._no_wpe_online(what)
 
     @staticmethod
@@ -1133,6 +1207,12 @@ class Enhancer:
         select = self._channel_select()
         online = self._wpe_online()
         bf_online = self._bf_online()
+        gss_online = self._gss_online()
+        if gss_online is not None and online is not None and bf_online is None:
+            raise NotImplementedError(
+                'gss_online with wpe_online but without bf_online in the fused call (the online '
+                "WPE rides on the online MVDR's descriptor there): pass fused=False for the stage "
+                'path')
         if online is not None and bf_online is None:
             # (the fused online call takes no second descriptor; the stage path combines)
             for name, on in (('bf_segment_frames', segments is not None),
@@ -1143,7 +1223,16 @@ class Enhancer:
                         f'wpe_online with {name} in the fused call: pass fused=False for the '
                         'stage path')
         try:
-            if bf_online is not None:
+            if gss_online is not None:
+                # (every online stage in one call: the MVDR's descriptor carries the WPE's alpha)
+                bf_kw = {} if bf_online is None else dict(
+                    bf_online=True, bf_forget=bf_online['forget'], bf_loading=bf_online['loading'],
+                    ref_channel=-1, wpe_online=online is not None,
+                    wpe_alpha=ops.WPE_ONLINE_ALPHA if online is None else online)
+                res = ops.enhance_observation_gss_online(
+                    obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
+                    debug=debug, ctx=ctx, wpe_arrays=wpe_arrays, **gss_online, **bf_kw)
+            elif bf_online is not None:
                 # (both online stages in one call: the descriptor carries the WPE's alpha)
                 res = ops.enhance_observation_bf_online(
                     obs, activity, target_speaker_index, start_ctx, end_ctx, params=params,
@@ -1503,6 +1592,7 @@ class Enhancer:
         self._no_segments('enhance_observation_guided')
         self._no_wpd('enhance_observation_guided')
         self._no_bf_online('enhance_observation_guided')
+        self._no_gss_online('enhance_observation_guided')
         self._no_wpe_online('enhance_observation_guided')
         self._no_null('enhance_observation_guided')
         self._no_channel_keep('enhance_observation_guided')
@@ -1606,6 +1696,7 @@ class Enhancer:
         self._no_segments('enhance_observation_speakers')
         self._no_wpd('enhance_observation_speakers')
         self._no_bf_online('enhance_observation_speakers')
+        self._no_gss_online('enhance_observation_speakers')
         self._no_wpe_online('enhance_observation_speakers')
         self._no_null('enhance_observation_speakers')
         self._no_channel_keep('enhance_observation_speakers')
@@ -1646,6 +1737,7 @@ class Enhancer:
         self._no_segments('enhance_example_speakers')
         self._no_wpd('enhance_example_speakers')
         self._no_bf_online('enhance_example_speakers')
+        self._no_gss_online('enhance_example_speakers')
         self._no_wpe_online('enhance_example_speakers')
         self._no_null('enhance_example_speakers')
         self._no_channel_keep('enhance_example_speakers')
@@ -1846,11 +1938,28 @@ def get_enhancer(
     bf_online=False,
     bf_forget=ops.BF_ONLINE_FORGET,
     bf_loading=ops.BF_ONLINE_LOADING,
+    gss_online=False,
+    gss_forget=ops.GSS_ONLINE_FORGET,
+    gss_prior_mass=ops.GSS_ONLINE_PRIOR_MASS,
 ):
     """core.py:574-637 (same keyword arguments and defaults; ``activity_store``,
     ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*``,
-    ``bf_null_*``, ``bf_wpd_*``, ``wpe_online``, ``wpe_alpha``, ``bf_online``, ``bf_forget`` and
-    ``bf_loading`` are additions).
+    ``bf_null_*``, ``bf_wpd_*``, ``wpe_online``, ``wpe_alpha``, ``bf_online``, ``bf_forget``,
+    ``bf_loading``, ``gss_online``, ``gss_forget`` and ``gss_prior_mass`` are additions).
+    ``gss_online=True``: the mixture model becomes the online CACGMM (see
+    `ops.cacgmm_posteriors_online`) -- the recursive EM on running sums that forget at the rate
+    ``gss_forget`` (0.99: a choice, not a measurement; on the moving-speaker scene of DESIGN
+    section 25 0.95 follows the movement and 0.99 shows no gain), frame t classified by the model
+    of the frames before it, from a fresh state of mass ``gss_prior_mass`` (1.0: a choice, not a
+    measurement) per utterance, masked by the annotation; ``bss_iterations`` and
+    ``bss_iterations_post`` are not read.  With ``wpe_online=True`` and ``bf_online=True`` it
+    completes the zero-look-ahead chain.  For `Enhancer.enhance_observation` / `enhance_example`
+    (one fused call, or the stage path with ``fused=False``) and, one utterance at a time,
+    `enhance_session`.  Not with ``bf_segment_frames``, ``bf_null_interferer``, ``channel_keep``,
+    ``refined_rttm``, the WPD types, the guided, multi-speaker, activity or annotation-free
+    methods, and a ``gss_forget`` / ``gss_prior_mass`` other than the default without it is a
+    setting nobody reads (NotImplementedError).  Nothing here is tuned against recognition
+    accuracy.
     ``bf_online=True``: 'mvdrSouden_ban' becomes the online MVDR (see
     `ops.mvdr_souden_online_from_masks`) -- running sums that forget at the rate ``bf_forget``
     (0.99, a memory of 1.6 s at the 16 ms frame shift: a choice, not a measurement), a filter per
@@ -1909,7 +2018,8 @@ def get_enhancer(
                           path=activity_path, database_path=database_path,
                           store=activity_store),
         gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
-                      verbose=False),
+                      verbose=False, online=gss_online, forget=gss_forget,
+                      prior_mass=gss_prior_mass),
         bf_drop_context=bf_drop_context,
         bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
                             segment_context=bf_segment_context,

@@ -161,10 +161,13 @@ def get_enhancer(
     bf_online=False,
     bf_forget=ops.BF_ONLINE_FORGET,
     bf_loading=ops.BF_ONLINE_LOADING,
+    gss_online=False,
+    gss_forget=ops.GSS_ONLINE_FORGET,
+    gss_prior_mass=ops.GSS_ONLINE_PRIOR_MASS,
 ):
     """core_chime6.py:572-635 (same keyword arguments and defaults; ``activity_store``,
     ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*``,
-    ``bf_wpd_*``, ``wpe_online``, ``wpe_alpha``, ``bf_online``, ``bf_forget`` and ``bf_loading`` are additions,
+    ``bf_wpd_*``, ``wpe_online``, ``wpe_alpha``, ``bf_online``, ``bf_forget``, ``bf_loading``, ``gss_online``, ``gss_forget`` and ``gss_prior_mass`` are additions,
     see core.get_enhancer)."""
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
@@ -178,7 +181,8 @@ def get_enhancer(
                           path=activity_path, database_path=database_path,
                           store=activity_store),
         gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
-                      verbose=False),
+                      verbose=False, online=gss_online, forget=gss_forget,
+                      prior_mass=gss_prior_mass),
         bf_drop_context=bf_drop_context,
         bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
                             segment_context=bf_segment_context,

@@ -1332,6 +1332,104 @@ extern "C" int gss_last_mvdr_online_fallbacks(gss_ctx *ctx, int64_t *count) {
                             "gss_last_mvdr_online_fallbacks");
 }
 
+// The online CACGMM argument rules, before any launch.
+static int check_em_online_shape(gss_ctx *ctx, const char *what, int F, int K, int D) {
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F = %d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, D >= 1 && D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED, "%s: D = %d outside [1, %d]",
+                what, D, GSS_MAX_CHANNELS);
+    GSS_REQUIRE(ctx, K >= 1 && K <= GSS_CACGMM_ONLINE_MAX_CLASSES, GSS_ERR_UNSUPPORTED,
+                "%s: K = %d outside [1, %d]", what, K, GSS_CACGMM_ONLINE_MAX_CLASSES);
+    return GSS_OK;
+}
+
+static int check_em_online(gss_ctx *ctx, const char *what, const gss_em_online *cfg) {
+    GSS_REQUIRE(ctx, cfg, GSS_ERR_INVALID, "%s: cfg is NULL", what);
+    GSS_REQUIRE(ctx, std::isfinite(cfg->forget) && cfg->forget > 0.0 && cfg->forget <= 1.0,
+                GSS_ERR_INVALID, "%s: forget = %g outside (0, 1]", what, cfg->forget);
+    GSS_REQUIRE(ctx, std::isfinite(cfg->prior_mass) && cfg->prior_mass > 0.0, GSS_ERR_INVALID,
+                "%s: prior_mass = %g is not finite and > 0", what, cfg->prior_mass);
+    return GSS_OK;
+}
+
+static int check_cacgmm_online_state(gss_ctx *ctx, const char *what,
+                                     const gss_cacgmm_online_state *s, int F, int K, int D) {
+    GSS_REQUIRE(ctx, s->s, GSS_ERR_INVALID, "%s: state->s is NULL", what);
+    GSS_REQUIRE(ctx, s->n, GSS_ERR_INVALID, "%s: state->n is NULL", what);
+    GSS_REQUIRE(ctx, s->F == F && s->K == K && s->D == D, GSS_ERR_INVALID,
+                "%s: state of F = %d, K = %d, D = %d in a call of F = %d, K = %d, D = %d", what,
+                (int)s->F, (int)s->K, (int)s->D, F, K, D);
+    return GSS_OK;
+}
+
+extern "C" int gss_cacgmm_online_init(gss_ctx *ctx, int F, int K, int D, double prior_mass,
+                                      const gss_cacgmm_model *model, double model_mass,
+                                      gss_cacgmm_online_state *state) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_cacgmm_online_init";
+    GSS_REQUIRE(ctx, state, GSS_ERR_INVALID, "%s: state is NULL", what);
+    GSS_TRY(check_em_online_shape(ctx, what, F, K, D));
+    GSS_TRY(check_cacgmm_online_state(ctx, what, state, F, K, D));
+    cplx *S = reinterpret_cast<cplx *>(state->s);
+    if (!model) {
+        GSS_REQUIRE(ctx, std::isfinite(prior_mass) && prior_mass > 0.0, GSS_ERR_INVALID,
+                    "%s: prior_mass = %g is not finite and > 0", what, prior_mass);
+        return cacgmm_online_fresh_run(ctx, F, K, D, prior_mass, S, state->n);
+    }
+    GSS_TRY(check_model(ctx, model, "model"));
+    GSS_REQUIRE(ctx, std::isfinite(model_mass) && model_mass > 0.0, GSS_ERR_INVALID,
+                "%s: model_mass = %g is not finite and > 0", what, model_mass);
+    GSS_TRY(arena_reserve(ctx, cacgmm_online_workspace_bytes(F, K, D, false)));
+    GSS_TRY(cacgmm_online_from_model_run(ctx, em_model(model), F, K, D, model_mass, S, state->n));
+    int32_t bad = 0;
+    GSS_TRY(read_status_word(ctx, GSS_STATUS_CACGMM_ONLINE_BAD_MODEL, &bad, what));
+    GSS_REQUIRE(ctx, bad == 0, GSS_ERR_INVALID,
+                "%s: model: the precision of %d (frequency, class) pairs has no Cholesky factor", what,
+                (int)bad);
+    return GSS_OK;
+}
+
+extern "C" int gss_cacgmm_online(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                                 const gss_guidance *g, int K, const gss_em_online *cfg,
+                                 gss_cacgmm_online_state *state, double *gamma) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_cacgmm_online";
+    GSS_REQUIRE(ctx, Y, GSS_ERR_INVALID, "%s: Y_dev is NULL", what);
+    GSS_REQUIRE(ctx, gamma, GSS_ERR_INVALID, "%s: gamma_dev is NULL", what);
+    GSS_REQUIRE(ctx, T >= 0, GSS_ERR_INVALID, "%s: T = %lld is negative", what, (long long)T);
+    GSS_TRY(check_em_online_shape(ctx, what, F, K, D));
+    GSS_TRY(check_em_online(ctx, what, cfg));
+    if (state) GSS_TRY(check_cacgmm_online_state(ctx, what, state, F, K, D));
+    EmGuide guide;
+    GSS_TRY(check_mask_guidance(ctx, g, K, T, &guide));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
+    if (T == 0) return GSS_OK;
+    GSS_TRY(arena_reserve(ctx, cacgmm_online_workspace_bytes(F, K, D, state == nullptr)));
+    return cacgmm_online_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, guide, K, cfg->forget,
+                             cfg->prior_mass, state ? reinterpret_cast<cplx *>(state->s) : nullptr,
+                             state ? state->n : nullptr, gamma);
+}
+
+extern "C" int gss_cacgmm_online_model(gss_ctx *ctx, const gss_cacgmm_online_state *state,
+                                       const gss_cacgmm_model *model_out) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_cacgmm_online_model";
+    GSS_REQUIRE(ctx, state, GSS_ERR_INVALID, "%s: state is NULL", what);
+    GSS_TRY(check_em_online_shape(ctx, what, state->F, state->K, state->D));
+    GSS_TRY(check_cacgmm_online_state(ctx, what, state, state->F, state->K, state->D));
+    GSS_TRY(check_model(ctx, model_out, "model_out"));
+    GSS_REQUIRE(ctx, (void *)model_out->precision_dev != (void *)state->s &&
+                         model_out->log_det_dev != state->n && model_out->weight_dev != state->n,
+                GSS_ERR_INVALID, "%s: model_out shares a buffer with the state", what);
+    GSS_TRY(arena_reserve(ctx, cacgmm_online_workspace_bytes(state->F, state->K, state->D, false)));
+    return cacgmm_online_to_model_run(ctx, reinterpret_cast<const cplx *>(state->s), state->n,
+                                      state->F, state->K, state->D, em_model(model_out));
+}
+
+extern "C" int gss_last_cacgmm_online_fallbacks(gss_ctx *ctx, int64_t *count) {
+    return read_status_word(ctx, GSS_STATUS_CACGMM_ONLINE_FALLBACKS, count,
+                            "gss_last_cacgmm_online_fallbacks");
+}
+
 extern "C" int gss_wpe_weighted(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D, int taps,
                                 int delay, const double *weights, gss_cplx *X) {
     GSS_ENTER_VARIANTS(ctx);
@@ -1666,6 +1764,7 @@ struct PipelineCall {
     const gss_bf_wpd *wpd = nullptr;                 // the WPD beamformer
     const gss_wpe_online_cfg *wpe_online = nullptr;  // the online WPE in the place of the offline one
     const gss_bf_online *bf_online = nullptr;        // the online MVDR in the place of the whole-window one
+    const gss_em_online *em_online = nullptr;        // the online CACGMM in the place of the guided EM
     PipelineActivity activity;
     // gss_separate_observation: the EM is the one with a frequency-shared prior, started from
     // this (K,T) table with no mask, in the place of the activity-guided one
@@ -1749,6 +1848,7 @@ static size_t pipeline_workspace(const gss_params *p, int F, int64_t T, int64_t 
     // (online MVDR: the state of a fresh call, and the whole-window pass that picks the channel)
     if (call.bf_online)
         stage = std::max(stage, mvdr_online_workspace_bytes(F, T, D, true, call.bf_online->ref_channel < 0));
+    if (call.em_online) stage = std::max(stage, cacgmm_online_workspace_bytes(F, K, D, true));
     stage = std::max(stage, stft_workspace_bytes(T, p->stft_size));
     if (call.activity.scores)
         stage = std::max(stage, pact_workspace_bytes(F, T, K));   // the partial planes
@@ -1880,6 +1980,13 @@ static int run_front(gss_ctx *ctx, const gss_params *p, const PipelineCall &call
         return GSS_OK;
     }
     if (!call.guided) GSS_TRY(activity_run(ctx, act, K, N_act, p->stft_fading, fr.actf));
+    if (call.em_online) {   // (never guided, checked by the entry point)
+        GSS_TRY(cacgmm_online_run(ctx, X, F, T, D, em_guide_from_activity(fr.actf, T_act), K,
+                                  call.em_online->forget, call.em_online->prior_mass, nullptr, nullptr,
+                                  fr.gamma));
+        GSS_TRY(arena_release(ctx, mark));
+        return GSS_OK;
+    }
     GSS_TRY(cacgmm_run(ctx, X, F, T, D, call.guided ? guide : em_guide_from_activity(fr.actf, T_act),
                        K, p->bss_iterations, p->bss_iterations_post, fr.gamma));
     GSS_TRY(arena_release(ctx, mark));
@@ -2187,22 +2294,16 @@ extern "C" int gss_enhance_observation_wpe_online(gss_ctx *ctx, const gss_params
                                     out, taps, call);
 }
 
-extern "C" int gss_enhance_observation_bf_online(gss_ctx *ctx, const gss_params *p,
-                                                 const double *obs, int D, int64_t N,
-                                                 const uint8_t *act, int K, int64_t N_act,
-                                                 int target, int64_t start_ctx, int64_t end_ctx,
-                                                 const gss_bf_online *cfg, double *out,
-                                                 const gss_debug_taps *taps) {
-    GSS_ENTER_VARIANTS(ctx);
-    const char *const what = "gss_enhance_observation_bf_online";
-    GSS_REQUIRE(ctx, p, GSS_ERR_INVALID, "%s: params is NULL", what);
+// The checks of an online MVDR in a fused call and its fields of the call description
+// (wpe_cfg: storage for the online WPE's settings, which must outlive the call).
+static int fill_bf_online(gss_ctx *ctx, const char *what, const gss_params *p,
+                          const gss_bf_online *cfg, int D, PipelineCall *call,
+                          gss_wpe_online_cfg *wpe_cfg) {
     GSS_TRY(check_bf_online(ctx, what, cfg, D));
     GSS_REQUIRE(ctx, p->bf == 0, GSS_ERR_UNSUPPORTED,
                 "%s: bf=%d, only 0 ('mvdrSouden_ban') has an online form", what, p->bf);
-    PipelineCall call;
-    call.entry = what;
-    call.bf_online = cfg;
-    gss_wpe_online_cfg wpe_cfg{cfg->wpe_alpha};
+    call->bf_online = cfg;
+    wpe_cfg->alpha = cfg->wpe_alpha;
     if (cfg->wpe_online) {
         GSS_REQUIRE(ctx, p->wpe, GSS_ERR_INVALID, "%s: wpe = 0, there is no WPE stage to replace",
                     what);
@@ -2212,8 +2313,45 @@ extern "C" int gss_enhance_observation_bf_online(gss_ctx *ctx, const gss_params 
         GSS_TRY(check_wpe_arrays(ctx, p, D));
         GSS_TRY(check_wpe_online(ctx, what, 1, wpe_arrays_of(p), D / wpe_arrays_of(p), p->wpe_taps,
                                  p->wpe_delay, cfg->wpe_alpha));
-        call.wpe_online = &wpe_cfg;
+        call->wpe_online = wpe_cfg;
     }
+    return GSS_OK;
+}
+
+extern "C" int gss_enhance_observation_bf_online(gss_ctx *ctx, const gss_params *p,
+                                                 const double *obs, int D, int64_t N,
+                                                 const uint8_t *act, int K, int64_t N_act,
+                                                 int target, int64_t start_ctx, int64_t end_ctx,
+                                                 const gss_bf_online *cfg, double *out,
+                                                 const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *const what = "gss_enhance_observation_bf_online";
+    GSS_REQUIRE(ctx, p, GSS_ERR_INVALID, "%s: params is NULL", what);
+    PipelineCall call;
+    call.entry = what;
+    gss_wpe_online_cfg wpe_cfg{};
+    GSS_TRY(fill_bf_online(ctx, what, p, cfg, D, &call, &wpe_cfg));
+    return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
+                                    out, taps, call);
+}
+
+extern "C" int gss_enhance_observation_gss_online(gss_ctx *ctx, const gss_params *p,
+                                                  const double *obs, int D, int64_t N,
+                                                  const uint8_t *act, int K, int64_t N_act,
+                                                  int target, int64_t start_ctx, int64_t end_ctx,
+                                                  const gss_em_online *em, const gss_bf_online *bf,
+                                                  double *out, const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *const what = "gss_enhance_observation_gss_online";
+    GSS_REQUIRE(ctx, p, GSS_ERR_INVALID, "%s: params is NULL", what);
+    GSS_TRY(check_em_online(ctx, what, em));
+    GSS_REQUIRE(ctx, K <= GSS_CACGMM_ONLINE_MAX_CLASSES, GSS_ERR_UNSUPPORTED,
+                "%s: K = %d is larger than %d", what, K, GSS_CACGMM_ONLINE_MAX_CLASSES);
+    PipelineCall call;
+    call.entry = what;
+    call.em_online = em;
+    gss_wpe_online_cfg wpe_cfg{};
+    if (bf) GSS_TRY(fill_bf_online(ctx, what, p, bf, D, &call, &wpe_cfg));
     return enhance_observation_impl(ctx, p, obs, D, N, act, K, N_act, target, start_ctx, end_ctx,
                                     out, taps, call);
 }

@@ -201,6 +201,10 @@ struct gss_ctx {
     // [7]: frequencies whose row the last gss_cacgmm_align left off the identity (align_moved_kernel).
     // [8]: (frequency, frame) pairs of the last online MVDR call whose Phi_N had no Cholesky factor
     // (copied from the device counter by mvdr_online_run).
+    // [9]: (frequency, frame, class) triples of the last online CACGMM call whose S_k had no Cholesky
+    // factor (copied from the device counter by cacgmm_online_run; cacgmm_online_to_model_run counts
+    // its identity classes there).  [10]: classes whose precision had none in the last
+    // cacgmm_online_from_model_run.
     // [GSS_STATUS_TARGETS + s]: target s of the last targets call (mvdr_apply_targets_kernel,
     // which writes target 0's word to [0] as well).
     int32_t *status_host = nullptr;
@@ -228,6 +232,8 @@ struct gss_ctx {
 #define GSS_STATUS_WPD_ZERO_PIVOTS 6                             // pivots zeroed by the last WPD call
 #define GSS_STATUS_ALIGN_MOVED 7                                 // rows the last alignment left off the identity
 #define GSS_STATUS_MVDR_ONLINE_FALLBACKS 8                        // fallback frames of the last online MVDR call
+#define GSS_STATUS_CACGMM_ONLINE_FALLBACKS 9                      // fallback (frequency, frame, class) triples of the last online CACGMM call
+#define GSS_STATUS_CACGMM_ONLINE_BAD_MODEL 10                     // classes of the last model -> state conversion without a Cholesky factor
 #define GSS_STATUS_TARGETS 16                                   // first per-target word
 #define GSS_STATUS_CHANNELS 40                                   // first selected-channel word
 #define GSS_STATUS_BYTES (4 * (GSS_STATUS_CHANNELS + GSS_MAX_CHANNELS))
@@ -589,6 +595,20 @@ int mvdr_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const 
                     const double *mn, int ban, double beta, double loading, int ref, cplx *phi_x,
                     cplx *phi_n, cplx *X, int64_t xs_f, int64_t xs_t, cplx *W,
                     int32_t *ref_out = nullptr);
+
+// Online CACGMM (cacgmm_online.hip; include/gss_hip.h: gss_cacgmm_online).  Y (F,T,D), the mask of
+// `guide` (its initialisation is not read) -> gamma (F,K,T); S (F,K,D,D), n (F,K) the caller's
+// state, advanced in place, both NULL: a fresh one of mass prior_mass from the arena, thrown away.
+// The fallback count goes to status word GSS_STATUS_CACGMM_ONLINE_FALLBACKS.  Arguments validated
+// by the entry point, T >= 1, K <= GSS_CACGMM_ONLINE_MAX_CLASSES.
+size_t cacgmm_online_workspace_bytes(int F, int K, int D, bool fresh);
+int cacgmm_online_fresh_run(gss_ctx *ctx, int F, int K, int D, double mass, cplx *S, double *n);
+int cacgmm_online_from_model_run(gss_ctx *ctx, const EmModel &m, int F, int K, int D, double mass,
+                                 cplx *S, double *n);
+int cacgmm_online_to_model_run(gss_ctx *ctx, const cplx *S, const double *n, int F, int K, int D,
+                               const EmModel &m);
+int cacgmm_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGuide &guide,
+                      int K, double beta, double prior_mass, cplx *S, double *n, double *gamma);
 
 int selftest_mfma_run(gss_ctx *ctx);
 

@@ -30,6 +30,9 @@ here                        reference call (file:line)
 ``mvdr_souden_online_from_masks`` / ``OnlineMVDRState`` / ``enhance_observation_bf_online``
                             the same with exponentially forgetting running sums, a filter per
                             frame and a carried state (not in the reference)
+``cacgmm_posteriors_online`` / ``OnlineCACGMMState`` / ``enhance_observation_gss_online``
+                            the recursive (online) EM of the mixture model: running sums that
+                            forget, causal posteriors and a carried state (not in the reference)
 ``lcmv_souden_from_masks``  beamform_lcmv_souden_from_masks (beamforming_wrapper.py:127-171)
 ``lcmv_masks_from_posteriors`` / ``enhance_observation_lcmv``
                             the interferer-nulling LCMV fed from the posteriors
@@ -50,7 +53,8 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _capi
-from ._capi import (Context, GssBfLcmv, GssBfSegments, GssBfWpd, GssCacgmmModel, GssChannelSelect,
+from ._capi import (Context, GssBfLcmv, GssBfSegments, GssBfWpd, GssCacgmmModel,
+                    GssCacgmmOnlineState, GssChannelSelect, GssEmOnline,
                     GssBfOnline, GssDebugTaps, GssGuidance, GssMvdrOnlineState, GssParams,
                     GssWpeOnlineCfg, GssWpeOnlineState, c_void_p, default_context)
 from .cacgmm import CACGMM
@@ -1311,6 +1315,184 @@ def mvdr_souden_online_from_masks(Y, X_mask, N_mask, ban=False, *, forget=BF_ONL
     return out if len(out) > 1 else X_hat
 
 
+GSS_ONLINE_FORGET = 0.99       # choices, not measurements
+GSS_ONLINE_PRIOR_MASS = 1.0
+_ONLINE_MAX_CLASSES = 8        # include/gss_hip.h: GSS_CACGMM_ONLINE_MAX_CLASSES
+
+
+def check_gss_online(forget=GSS_ONLINE_FORGET, prior_mass=GSS_ONLINE_PRIOR_MASS, num_classes=None,
+                     num_channels=None):
+    """The settings of the online CACGMM -- the one place that validates them, before any device
+    work.  ValueError naming the argument: ``forget`` a finite number in (0, 1], ``prior_mass``
+    (the mass of a fresh state, or the mass a model is given) a finite number > 0,
+    ``num_classes`` an integer in [1, 8], ``num_channels`` an integer in [1, 32].  Returns
+    (forget, prior_mass)."""
+    if not _is_real(forget) or not np.isfinite(forget) or not 0 < forget <= 1:
+        raise ValueError(f'forget={forget!r}: a finite number in (0, 1]')
+    if not _is_real(prior_mass) or not np.isfinite(prior_mass) or not prior_mass > 0:
+        raise ValueError(f'prior_mass={prior_mass!r}: a finite number > 0')
+    if num_classes is not None and (not _is_integer(num_classes)
+                                    or not 1 <= num_classes <= _ONLINE_MAX_CLASSES):
+        raise ValueError(f'num_classes={num_classes!r}: an integer in [1, {_ONLINE_MAX_CLASSES}]')
+    if num_channels is not None and (not _is_integer(num_channels)
+                                     or not 1 <= num_channels <= _MAX_CHANNELS):
+        raise ValueError(f'num_channels={num_channels!r}: an integer in [1, {_MAX_CHANNELS}]')
+    return float(forget), float(prior_mass)
+
+
+class OnlineCACGMMState:
+    """The state of the online CACGMM in HBM (gss_cacgmm_online_state), caller-owned like an
+    `OnlineMVDRState`: the running sums ``s`` (F,K,D,D), complex128, Hermitian, and the masses
+    ``n`` (F,K).  The model they stand for is B_k = s_k / n_k, pi_k = n_k / sum_j n_j."""
+
+    def __init__(self, ctx, F, K, D):
+        self.ctx = ctx
+        self.F, self.K, self.D = int(F), int(K), int(D)
+        self.shapes = {'s': (self.F, self.K, self.D, self.D), 'n': (self.F, self.K)}
+        self.dtypes = {'s': np.complex128, 'n': np.float64}
+        self.bufs = {'s': ctx.empty(16 * self.F * self.K * self.D * self.D),
+                     'n': ctx.empty(8 * self.F * self.K)}
+
+    @property
+    def key(self):
+        return self.F, self.K, self.D
+
+    def struct(self):
+        return GssCacgmmOnlineState(s=self.bufs['s'].ptr, n=self.bufs['n'].ptr, F=self.F, K=self.K,
+                                    D=self.D)
+
+    @classmethod
+    def fresh(cls, F, K, D, prior_mass=GSS_ONLINE_PRIOR_MASS, *, ctx=None):
+        """s_k = prior_mass * I, n_k = prior_mass (gss_cacgmm_online_init): all classes are the
+        same, so only a mask tells them apart."""
+        if not _is_integer(F) or F < 1:
+            raise ValueError(f'F={F!r}: a positive integer')
+        check_gss_online(prior_mass=prior_mass, num_classes=K, num_channels=D)
+        ctx = ctx or default_context()
+        state = cls(ctx, F, K, D)
+        ctx._check(ctx.lib.gss_cacgmm_online_init(
+            ctx.handle, state.F, state.K, state.D, float(prior_mass), None, 0.0,
+            ctypes.byref(state.struct())), 'gss_cacgmm_online_init')
+        return state
+
+    @classmethod
+    def from_model(cls, model, mass=GSS_ONLINE_PRIOR_MASS, *, ctx=None):
+        """Continue a fitted `cacgmm.CACGMM`: n_k = mass * weight_k, s_k = n_k * precision_k^-1,
+        inverted on the device.  ``mass`` is how many frames the model counts for against the
+        new ones.  ValueError when a precision has no Cholesky factor."""
+        if not isinstance(model, CACGMM):
+            raise ValueError(f'model: a CACGMM, not {type(model).__name__}')
+        F, K, D = model.shape
+        check_gss_online(prior_mass=mass, num_classes=K, num_channels=D)
+        ctx = ctx or default_context()
+        state = cls(ctx, F, K, D)
+        dev = DeviceModel(ctx, F, K, D, model)
+        ctx._check(ctx.lib.gss_cacgmm_online_init(
+            ctx.handle, F, K, D, 0.0, ctypes.byref(dev.struct), float(mass),
+            ctypes.byref(state.struct())), 'gss_cacgmm_online_init')
+        return state
+
+    def to_model(self):
+        """The `cacgmm.CACGMM` the state stands for (gss_cacgmm_online_model): precision B_k^-1,
+        ln det B_k and pi_k; `cacgmm_predict`, `cacgmm_fit`, ``save`` and `cacgmm_model_permute`
+        work on it."""
+        dev = DeviceModel(self.ctx, self.F, self.K, self.D)
+        self.ctx._check(self.ctx.lib.gss_cacgmm_online_model(
+            self.ctx.handle, ctypes.byref(self.struct()), ctypes.byref(dev.struct)),
+            'gss_cacgmm_online_model')
+        return dev.to_host(self.ctx)
+
+    def to_host(self):
+        """{'s', 'n'} as NumPy arrays: everything `from_host` needs (synchronises)."""
+        return {k: self.ctx.to_host(self.bufs[k], shape, self.dtypes[k])
+                for k, shape in self.shapes.items()}
+
+    @classmethod
+    def from_host(cls, host, *, ctx=None):
+        """A device state from the dict of `to_host` (in any context: a state saved in one
+        process continues in another).  ValueError for shapes that do not fit each other."""
+        s = np.ascontiguousarray(host['s'], dtype=np.complex128)
+        if s.ndim != 4 or s.shape[2] != s.shape[3]:
+            raise ValueError(f's: shape {s.shape} is not (F,K,D,D)')
+        F, K, D, _ = s.shape
+        if F < 1:
+            raise ValueError(f's: shape {s.shape} has no frequency')
+        check_gss_online(num_classes=K, num_channels=D)
+        n = np.ascontiguousarray(host['n'], dtype=np.float64)
+        if n.shape != (F, K):
+            raise ValueError(f'n: shape {n.shape} is not (F,K) = {(F, K)}')
+        ctx = ctx or default_context()
+        state = cls(ctx, F, K, D)
+        ctx.upload(state.bufs['s'], s)
+        ctx.upload(state.bufs['n'], n)
+        return state
+
+    def copy(self):
+        """An independent state with the same bits, in the same context."""
+        return OnlineCACGMMState.from_host(self.to_host(), ctx=self.ctx)
+
+
+def cacgmm_posteriors_online(Obs, source_activity_mask=None, *, num_classes=None,
+                             forget=GSS_ONLINE_FORGET, prior_mass=GSS_ONLINE_PRIOR_MASS,
+                             state=None, return_fallbacks=False, ctx=None):
+    """The online CACGMM (gss_cacgmm_online): Obs (D,T,F) complex -> posterior (K,T,F) float64.
+    Frame t is classified by the model of the frames before it (causal, no look-ahead) and then
+    enters the running sums, which forget at the rate ``forget``.  ``source_activity_mask``
+    (K,T) or (K,T,F), non-zero = active, or None.  ``state``: an `OnlineCACGMMState` to continue
+    from, advanced IN PLACE by the T frames (feeding a recording in blocks through one state
+    gives the bits of one call); None: a fresh state of ``prior_mass``, thrown away.  A fresh
+    state has identical classes, so without a mask every posterior would stay 1 / K: no mask
+    together with no state is a ValueError -- start from a model
+    (`OnlineCACGMMState.from_model`).  ``num_classes``: K, needed only when neither a mask nor a
+    state gives it.  With ``return_fallbacks`` also the number of (frequency, frame, class)
+    triples whose s_k had no Cholesky factor (the class was taken as B_k = I for that frame)."""
+    Obs = np.asarray(Obs)
+    if Obs.ndim != 3:
+        raise ValueError(f'Obs: shape {Obs.shape} is not (D,T,F)')
+    D, T, F = Obs.shape
+    if source_activity_mask is None and state is None:
+        raise ValueError('source_activity_mask and state are both None: a fresh state has '
+                         'identical classes and every posterior would be 1 / K; start from a '
+                         'model (OnlineCACGMMState.from_model)')
+    mask, K = None, None
+    if source_activity_mask is not None:
+        _, mask, K = guidance_tables(None, source_activity_mask, T, F)
+    if state is not None:
+        if not isinstance(state, OnlineCACGMMState):
+            raise ValueError(f'state: {type(state).__name__} is not an OnlineCACGMMState')
+        if K is None:
+            K = state.K
+        if state.key != (F, K, D):
+            raise ValueError(f'state: built for (F, K, D) = {state.key}, the call has {(F, K, D)}')
+        if ctx is not None and ctx is not state.ctx:
+            raise ValueError('state: it lives in another context than ctx')
+        ctx = state.ctx
+    if num_classes is not None and num_classes != K:
+        raise ValueError(f'num_classes={num_classes!r} but the mask / state has {K} classes')
+    forget, prior_mass = check_gss_online(forget, prior_mass, K, D)
+    ctx = ctx or default_context()
+    fallbacks = 0
+    if T == 0 or F == 0:
+        posterior = np.zeros((K, T, F), np.float64)
+    else:
+        Y_d, _ = _obs_to_device_ftd(ctx, Obs)
+        guide = DeviceGuidance(ctx, None, mask, T) if mask is not None else None
+        g_d = ctx.empty(8 * F * K * T)
+        o_d = ctx.empty(8 * F * K * T)
+        cfg = GssEmOnline(forget=forget, prior_mass=prior_mass)
+        ctx._check(ctx.lib.gss_cacgmm_online(
+            ctx.handle, c_void_p(Y_d.ptr), F, T, D, ctypes.byref(guide.struct) if guide else None,
+            K, ctypes.byref(cfg), ctypes.byref(state.struct()) if state is not None else None,
+            c_void_p(g_d.ptr)), 'gss_cacgmm_online')
+        # (F, K*T) -> (K*T, F)
+        ctx._check(ctx.lib.gss_layout_permute_f64(ctx.handle, c_void_p(g_d.ptr), F, K * T, 1, 2,
+                                                  c_void_p(o_d.ptr)), 'gss_layout_permute_f64')
+        posterior = ctx.to_host(o_d, (K, T, F), np.float64)
+        if return_fallbacks:
+            fallbacks = ctx.last_cacgmm_online_fallbacks()
+    return (posterior, fallbacks) if return_fallbacks else posterior
+
+
 def check_bf_lcmv(num_classes, target_index, interferer=None, candidates=None, min_mass=None,
                   num_channels=None):
     """The settings of the interferer-nulling LCMV as a gss_bf_lcmv, or ValueError naming the
@@ -1987,6 +2169,7 @@ _FUSED_ENTRIES = {
     'wpd': ('gss_enhance_observation_wpd', None, 'WPD'),
     'wpe_online': ('gss_enhance_observation_wpe_online', None, 'online WPE'),
     'bf_online': ('gss_enhance_observation_bf_online', None, 'online MVDR'),
+    'gss_online': ('gss_enhance_observation_gss_online', None, 'online CACGMM'),
     'activity': ('gss_enhance_observation_activity', None, 'activity'),
     'lcmv': ('gss_enhance_observation_lcmv', None, 'LCMV'),
     'channel_select': ('gss_enhance_observation_select', 'gss_enhance_observation_select_pcm16',
@@ -2000,7 +2183,7 @@ def _enqueue_fused(ctx, params, obs_d, D, N, act_d, K, N_act, target_index, star
     """The one place that issues a fused one-target call on inputs in HBM.  ``option``: a key of
     `_FUSED_ENTRIES`; ``value``: the struct that entry takes (gss_bf_wpd, gss_wpe_online_cfg, gss_bf_online,
     gss_bf_lcmv, gss_bf_segments, gss_channel_select), for 'activity' the device buffers (weights or None,
-    scores, power or None).  ``pcm``: int16 samples, the entry's _pcm16 twin."""
+    scores, power or None), for 'gss_online' the pair (gss_em_online, gss_bf_online or None).  ``pcm``: int16 samples, the entry's _pcm16 twin."""
     name, twin, label = _FUSED_ENTRIES[option]
     assert twin is not None or not pcm, f'the {label} call has no pcm16 twin'
 
@@ -2009,6 +2192,8 @@ def _enqueue_fused(ctx, params, obs_d, D, N, act_d, K, N_act, target_index, star
     before, after = (), ()
     if option == 'activity':    # the weights before out_dev, the scores and the power after it
         before, after = (ptr(value[0]),), (ptr(value[1]), ptr(value[2]))
+    elif option == 'gss_online':
+        before = (ctypes.byref(value[0]), ctypes.byref(value[1]) if value[1] is not None else None)
     elif option is not None:
         before = (ctypes.byref(value),)
     ctx._check(getattr(ctx.lib, twin if pcm else name)(
@@ -2043,8 +2228,12 @@ class ResidentUtterance:
 
     def enqueue(self, target_index, start_context, end_context, taps=None, segments=None,
                 channel_select=None, lcmv=None, activity=None, wpd=None, wpe_online=None,
-                bf_online=None):
-        """``bf_online``: a gss_bf_online for the online MVDR in the place of the whole-window one,
+                bf_online=None, gss_online=None):
+        """``gss_online``: a pair (gss_em_online, gss_bf_online or None) for the online CACGMM in
+        the place of the guided EM, with the second member the online MVDR (and through its
+        ``wpe_online`` field the online WPE) as well (gss_enhance_observation_gss_online; float64
+        samples only, on its own).
+        ``bf_online``: a gss_bf_online for the online MVDR in the place of the whole-window one,
         with its ``wpe_online`` field the online WPE as well (gss_enhance_observation_bf_online;
         float64 samples only, on its own).
         ``wpe_online``: a gss_wpe_online_cfg for the online WPE in the place of the offline one
@@ -2060,7 +2249,8 @@ class ResidentUtterance:
         ``activity``: device buffers (weights (F,) or None, scores (K,T), power (T,) or None) for
         the posterior activity of the call's own observation and posteriors
         (gss_enhance_observation_activity; float64 samples only, on its own)."""
-        given = [(name, v) for name, v in (('bf_online', bf_online), ('wpe_online', wpe_online),
+        given = [(name, v) for name, v in (('gss_online', gss_online),
+                                           ('bf_online', bf_online), ('wpe_online', wpe_online),
                                            ('wpd', wpd),
                                            ('activity', activity), ('lcmv', lcmv),
                                            ('channel_select', channel_select),
@@ -2528,6 +2718,57 @@ def enhance_observation_bf_online(obs, activity, target_index, start_context_sam
     if not debug:
         return x_hat
     details['bf_online_fallbacks'] = ctx.last_mvdr_online_fallbacks()
+    return x_hat, details
+
+
+def enhance_observation_gss_online(obs, activity, target_index, start_context_samples,
+                                   end_context_samples, *, forget=GSS_ONLINE_FORGET,
+                                   prior_mass=GSS_ONLINE_PRIOR_MASS, bf_online=False,
+                                   bf_forget=BF_ONLINE_FORGET, bf_loading=BF_ONLINE_LOADING,
+                                   ref_channel=-1, wpe_online=False, wpe_alpha=WPE_ONLINE_ALPHA,
+                                   params=None, window=None, debug=False, ctx=None,
+                                   wpe_arrays=None, **param_kwargs):
+    """`enhance_observation` with the online CACGMM of `cacgmm_posteriors_online` (a fresh state
+    of ``prior_mass`` per call, masked by the call's frame activity;
+    gss_enhance_observation_gss_online) in the place of the guided EM; ``bss_iterations`` and
+    ``bss_iterations_post`` are not read.  ``bf_online``: the online MVDR follows as in
+    `enhance_observation_bf_online` (``bf_forget``, ``bf_loading``, ``ref_channel``), and with
+    ``wpe_online`` the online WPE precedes: the whole zero-look-ahead chain in one call.
+    ``debug`` details as there plus ``gss_online_fallbacks`` (and ``bf_online_fallbacks``).
+    Bad settings are ValueError before any device work."""
+    if params is None:
+        params = make_params(**param_kwargs)
+    obs = np.asarray(obs)
+    if obs.ndim != 2:
+        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    forget, prior_mass = check_gss_online(forget, prior_mass, np.shape(activity)[0], obs.shape[0])
+    em = GssEmOnline(forget=forget, prior_mass=prior_mass)
+    bf = None
+    if bf_online:
+        _require_souden(params, 'bf_online', 'an online form')
+        bf_forget, bf_loading, ref_channel = check_bf_online(bf_forget, bf_loading, ref_channel,
+                                                             obs.shape[0])
+        if wpe_online:
+            if not params.wpe:
+                raise ValueError('wpe_online with wpe=False: there is no WPE stage to replace')
+            if params.wpe_psd_context != 0:
+                raise ValueError(f'wpe_online with wpe_psd_context={params.wpe_psd_context}: the '
+                                 'online WPE has no PSD context')
+            check_wpe_online(params.wpe_taps, params.wpe_delay, wpe_alpha, obs.shape[0],
+                             params.wpe_arrays if wpe_arrays is None else wpe_arrays)
+        bf = _bf_online_cfg(bf_forget, bf_loading, ref_channel, wpe_online, wpe_alpha)
+    elif wpe_online:
+        raise ValueError('wpe_online without bf_online inside the gss_online call: the online WPE '
+                         'rides on the online MVDR\'s descriptor')
+    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
+    utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
+                gss_online=(em, bf))
+    x_hat, details = _one_target_result(utt, bufs, debug)
+    if not debug:
+        return x_hat
+    if bf is not None:
+        details['bf_online_fallbacks'] = ctx.last_mvdr_online_fallbacks()
+    details['gss_online_fallbacks'] = ctx.last_cacgmm_online_fallbacks()
     return x_hat, details
 
 

@@ -54,6 +54,14 @@ def main(argv=None):
     ap.add_argument('--bf-loading', type=float, default=1e-2,
                     help='relative diagonal loading of the fresh state of --bf-online, > 0 (a '
                          'choice, not a measurement)')
+    ap.add_argument('--gss-online', action='store_true',
+                    help='the online CACGMM in the place of the iterated mixture model: the '
+                         'recursive EM on running sums that forget, causal posteriors; '
+                         '--bss-iterations is not read (get_enhancer(gss_online=True))')
+    ap.add_argument('--gss-forget', type=float, default=0.99,
+                    help='forgetting factor of --gss-online, in (0, 1] (a choice, not a measurement)')
+    ap.add_argument('--gss-prior-mass', type=float, default=1.0,
+                    help='mass of the fresh state of --gss-online, > 0 (a choice, not a measurement)')
     ap.add_argument('--bss-iterations', type=int, default=20)
     ap.add_argument('--bss-iterations-post', type=int, default=1)
     ap.add_argument('--bf', default='mvdrSouden_ban')
@@ -111,7 +119,8 @@ def main(argv=None):
         bf_wpd_delay=args.bf_wpd_delay, bf_wpd_iterations=args.bf_wpd_iterations,
         bf_wpd_power_floor=args.bf_wpd_power_floor, wpe_online=args.wpe_online,
         wpe_alpha=args.wpe_alpha, bf_online=args.bf_online, bf_forget=args.bf_forget,
-        bf_loading=args.bf_loading)
+        bf_loading=args.bf_loading, gss_online=args.gss_online, gss_forget=args.gss_forget,
+        gss_prior_mass=args.gss_prior_mass)
     if parallel.is_master():
         Path(args.out).mkdir(parents=True, exist_ok=True)
     parallel.barrier()
