@@ -626,12 +626,6 @@ class Enhancer:
                 self.channel_keep, self.stft_size // 2 + 1, bands=self.channel_bands))
         return sel[1]
 
-    def _no_channel_keep(self, what):
-        if self.channel_keep is not None:
-            raise NotImplementedError(
-                f'{what} with channel_keep: the channel selection is built for '
-                'enhance_observation and enhance_session only')
-
     # channels per array that each multiarray mode loads (core.py:428-441)
     _ARRAY_CHANNELS = {True: 4, 'outer_array_mics': 2, 'first_array_mics': 1}
 
@@ -692,9 +686,9 @@ class Enhancer:
         id.  One file per utterance and no merge step (`from_rttm` takes a list of files and
         unites overlapping lines); such a session runs one utterance at a time."""
         from pb_chime5_amd import parallel
-        self._no_null('enhance_session')
+        self._refuse('enhance_session', ('bf_null_interferer',))
         if refined_rttm:
-            self._no_activity_options('enhance_session(refined_rttm=True)')
+            self._refuse('enhance_session(refined_rttm=True)', self._NOT_WITH_ACTIVITY)
         audio_dir = Path(audio_dir)
         it = self.get_iterator(session_ids)
 
@@ -1070,85 +1064,69 @@ class Enhancer:
         """The beamformer's segment settings (``Beamformer.segments``) or None."""
         return getattr(getattr(self, 'bf_block', None), 'segments', None)
 
-    def _no_segments(self, what):
-        if self._bf_segments() is not None:
-            raise NotImplementedError(
-                f'{what} with bf_segment_frames: the segment-wise beamformer is built for '
-                'enhance_observation only')
-
     def _bf_null(self):
         """Whether the beamformer nulls an interferer (``Beamformer.null_interferer``)."""
         return bool(getattr(getattr(self, 'bf_block', None), 'null_interferer', False))
-
-    def _no_null(self, what):
-        if self._bf_null():
-            raise NotImplementedError(
-                f'{what} with bf_null_interferer: the interferer-nulling beamformer is built '
-                'for enhance_observation only')
 
     def _bf_wpd(self):
         """The WPD settings of the beamformer (``Beamformer.wpd``) or None."""
         return getattr(getattr(self, 'bf_block', None), 'wpd', None)
 
-    def _no_wpd(self, what):
-        if self._bf_wpd() is not None:
-            raise NotImplementedError(
-                f'{what} with bf={self.bf_block.type!r}: the WPD beamformer is built for '
-                'enhance_observation, enhance_example and enhance_session only')
-
     def _bf_online(self):
         """The online settings of the beamformer (``Beamformer.online_settings``) or None."""
         return getattr(getattr(self, 'bf_block', None), 'online_settings', None)
 
-    def _no_bf_online(self, what):
-        if self._bf_online() is not None:
-            raise NotImplementedError(
-                f'{what} with bf_online: the online beamformer is built for enhance_observation, '
-                'enhance_example and enhance_session only')
-
     def _gss_online(self):
         """The online settings of the mixture model (``GSS.online_settings``) or None."""
         return getattr(getattr(self, 'gss_block', None), 'online_settings', None)
-
-    def _no_gss_online(self, what):
-        if self._gss_online() is not None:
-            raise NotImplementedError(
-                f'{what} with gss_online: the online mixture model is built for '
-                'enhance_observation, enhance_example and enhance_session only')
 
     def _wpe_online(self):
         """The forgetting factor of an online WPE block (``WPE.online``) or None."""
         block = getattr(self, 'wpe_block', None)
         return block.alpha if getattr(block, 'online', False) else None
 
-    def _no_wpe_online(self, what):
-        if self._wpe_online() is not None:
-            raise NotImplementedError(
-                f'{what} with wpe_online: the online WPE is built for enhance_observation, '
-                'enhance_example, enhance_session and the annotation-free methods only')
+    # What a method that is not built for an option says: option -> (the probe or field that is
+    # neither None nor False when the option is on, the sentence after "<method> with <option>: ").
+    # A method names the options it refuses as a tuple of these keys, in the order in which they
+    # are looked at: the first one that is on speaks.
+    _REFUSALS = {
+        'bf_segment_frames': ('_bf_segments',
+                              'the segment-wise beamformer is built for enhance_observation only'),
+        'bf_null_interferer': ('_bf_null', 'the interferer-nulling beamformer is built for '
+                                           'enhance_observation only'),
+        'channel_keep': ('channel_keep', 'the channel selection is built for enhance_observation '
+                                         'and enhance_session only'),
+        'bf=wpd': ('_bf_wpd', 'the WPD beamformer is built for enhance_observation, '
+                              'enhance_example and enhance_session only'),
+        'bf_online': ('_bf_online', 'the online beamformer is built for enhance_observation, '
+                                    'enhance_example and enhance_session only'),
+        'gss_online': ('_gss_online', 'the online mixture model is built for enhance_observation, '
+                                      'enhance_example and enhance_session only'),
+        'wpe_online': ('_wpe_online', 'the online WPE is built for enhance_observation, '
+                       'enhance_example, enhance_session and the annotation-free methods only'),
+        'wpe_per_array': ('wpe_per_array', 'the annotation-free path runs one joint WPE'),
+    }
+    # the posterior activity is built for the whole-window MVDR on all channels
+    _NOT_WITH_ACTIVITY = ('bf_segment_frames', 'bf_null_interferer', 'channel_keep', 'bf=wpd',
+                          'bf_online', 'gss_online', 'wpe_online')
+    # the annotation-free path for the whole-window beamformers on all channels after one joint WPE
+    _NOT_WITH_BLIND = ('bf_segment_frames', 'bf_null_interferer', 'channel_keep', 'bf=wpd',
+                       'bf_online', 'gss_online', 'wpe_per_array')
+    # the guided and the multi-speaker calls for the whole-window MVDR on all channels
+    _NOT_WITH_GUIDED = _NOT_WITH_SPEAKERS = (
+        'bf_segment_frames', 'bf=wpd', 'bf_online', 'gss_online', 'wpe_online',
+        'bf_null_interferer', 'channel_keep')
 
-    def _no_blind_options(self, what):
-        """The annotation-free path is built for the whole-window beamformers on all channels
-        after one joint WPE."""
-        self._no_segments(what)
-        self._no_null(what)
-        self._no_channel_keep(what)
-        self._no_wpd(what)
-        self._no_bf_online(what)
-        self._no_gss_online(what)
-        if self.wpe_per_array:
-            raise NotImplementedError(
-                f'{what} with wpe_per_array: the annotation-free path runs one joint WPE')
-
-    def _no_activity_options(self, what):
-        """The posterior activity is built for the whole-window MVDR on all channels."""
-        self._no_segments(what)
-        self._no_null(what)
-        self._no_channel_keep(what)
-        self._no_wpd(what)
-        self._no_bf_online(what)
-        self._no_gss_online(what)
-        self._no_wpe_online(what)
+    def _refuse(self, what, options):
+        """NotImplementedError in the name of the method ``what`` for the first of ``options``
+        (keys of `_REFUSALS`) that is on."""
+        for option in options:
+            probe, sentence = self._REFUSALS[option]
+            on = getattr(self, probe)
+            if (on() if callable(on) else on) not in (None, False):
+                if option == 'bf=wpd':
+                    option = f'bf={self.bf_block.type!r}'
+                raise NotImplementedError(f'{what} with {option}: {sentence}')
 
     @staticmethod
     def _no_posterior_activity(what, posterior_activity):
@@ -1302,7 +1280,7 @@ class Enhancer:
         `ops.posterior_activity` on the blocks' Obs and posterior.  Not with
         ``bf_segment_frames``, ``bf_null_interferer`` or ``channel_keep``
         (NotImplementedError)."""
-        self._no_activity_options('enhance_observation_activity')
+        self._refuse('enhance_observation_activity', self._NOT_WITH_ACTIVITY)
         freq_weights = ops.check_freq_weights(freq_weights, self.stft_size // 2 + 1)
         if wpe_arrays is None:
             wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
@@ -1346,7 +1324,7 @@ class Enhancer:
         [(start, end), ...] where `posterior_activity.decide` (``rule``: an `ActivityRule`, None:
         its defaults) finds the speaker active, restricted to the utterance's own span (the
         context is left out), in samples of the recording on the reference array's clock."""
-        self._no_activity_options('enhance_example_activity')
+        self._refuse('enhance_example_activity', self._NOT_WITH_ACTIVITY)
         rule = pact.ActivityRule() if rule is None else rule
         obs, ex_array_activity, speaker_id = self._prepare_example(ex)
         x_hat, act = self.enhance_observation_activity(
@@ -1387,13 +1365,13 @@ class Enhancer:
         has no context frames: with ``ex`` and ``bf_drop_context`` it raises
         NotImplementedError.  The default keeps the stage path and its bits."""
         what = 'enhance_observation_blind'
-        self._no_blind_options(what)
+        self._refuse(what, self._NOT_WITH_BLIND)
         ops.check_blind_method(method)
         if fused:
             if method != 'shared_prior':
                 raise NotImplementedError(f"{what}(fused=True) with method={method!r}: the fused "
                                           "call runs the shared prior only")
-            self._no_wpe_online(f'{what}(fused=True)')
+            self._refuse(f'{what}(fused=True)', ('wpe_online',))
             if not self._fusable():
                 raise NotImplementedError(f'{what}(fused=True) with custom blocks')
             if self.bf_drop_context and ex is not None and 'start_orig' in ex:
@@ -1496,8 +1474,7 @@ class Enhancer:
         error is a ValueError before any device work."""
         from pb_chime5_amd import recording
         what = 'enhance_recording_blind'
-        self._no_blind_options(what)
-        self._no_wpe_online(what)
+        self._refuse(what, self._NOT_WITH_BLIND + ('wpe_online',))
         if not self._fusable():
             raise NotImplementedError(f'{what} with custom blocks')
         obs = np.asarray(obs)
@@ -1568,7 +1545,7 @@ class Enhancer:
         without an annotation works).  The intervals are clipped to the
         utterance's own span and count samples of the recording on the reference array's
         clock."""
-        self._no_blind_options('enhance_example_blind')
+        self._refuse('enhance_example_blind', self._NOT_WITH_BLIND)
         obs, _, _ = self._prepare_example(ex, with_activity=False)
         out = self.enhance_observation_blind(obs, num_speakers, ex=ex, **kw)
         keep = self._keep_range(ex)
@@ -1589,13 +1566,7 @@ class Enhancer:
         speaker in the initial affiliations (diarisation posteriors, annotation confidence).
         ``initialization``: optional dict of the same shape with initial affiliations used as
         given (a neural mask estimator's output).  ``fused=False`` runs the blocks."""
-        self._no_segments('enhance_observation_guided')
-        self._no_wpd('enhance_observation_guided')
-        self._no_bf_online('enhance_observation_guided')
-        self._no_gss_online('enhance_observation_guided')
-        self._no_wpe_online('enhance_observation_guided')
-        self._no_null('enhance_observation_guided')
-        self._no_channel_keep('enhance_observation_guided')
+        self._refuse('enhance_observation_guided', self._NOT_WITH_GUIDED)
         if wpe_arrays is None:
             wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
         wpe_arrays = ops.check_wpe_arrays(wpe_arrays, np.shape(obs)[0])
@@ -1693,13 +1664,7 @@ class Enhancer:
         speakers together (gss_enhance_observation_targets), the block path calls
         ``bf_block`` and the iSTFT once per speaker."""
         self._no_posterior_activity('enhance_observation_speakers', posterior_activity)
-        self._no_segments('enhance_observation_speakers')
-        self._no_wpd('enhance_observation_speakers')
-        self._no_bf_online('enhance_observation_speakers')
-        self._no_gss_online('enhance_observation_speakers')
-        self._no_wpe_online('enhance_observation_speakers')
-        self._no_null('enhance_observation_speakers')
-        self._no_channel_keep('enhance_observation_speakers')
+        self._refuse('enhance_observation_speakers', self._NOT_WITH_SPEAKERS)
         speaker_ids = self.speaker_ids_of(ex_array_activity, speaker_ids)
         if wpe_arrays is None:
             wpe_arrays = self.wpe_arrays(ex, np.shape(obs)[0])
@@ -1734,13 +1699,7 @@ class Enhancer:
         """`enhance_example` for several speakers of the example's window at once: dict
         speaker_id -> x_hat, each trimmed like `enhance_example` trims its output."""
         self._no_posterior_activity('enhance_example_speakers', posterior_activity)
-        self._no_segments('enhance_example_speakers')
-        self._no_wpd('enhance_example_speakers')
-        self._no_bf_online('enhance_example_speakers')
-        self._no_gss_online('enhance_example_speakers')
-        self._no_wpe_online('enhance_example_speakers')
-        self._no_null('enhance_example_speakers')
-        self._no_channel_keep('enhance_example_speakers')
+        self._refuse('enhance_example_speakers', self._NOT_WITH_SPEAKERS)
         obs, ex_array_activity, _ = self._prepare_example(ex)
         out = self.enhance_observation_speakers(obs, ex_array_activity, speaker_ids, ex=ex)
         return {k: self._trim_context(v, ex) for k, v in out.items()}
@@ -1889,6 +1848,46 @@ def wpe_block_from(wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context, wp
                psd_context=wpe_psd_context, online=wpe_online, alpha=wpe_alpha)
 
 
+def _enhancer_fields(
+        *, multiarray, context_samples, wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context,
+        activity_garbage_class, stft_size, stft_shift, stft_fading, bss_iterations,
+        bss_iterations_post, bf_drop_context, bf, postfilter, device_id, wpe_per_array,
+        bf_segment_frames, bf_segment_context, bf_segment_min_mass, channel_keep, channel_bands,
+        bf_null_interferer, bf_null_min_mass, bf_wpd_taps, bf_wpd_delay, bf_wpd_iterations,
+        bf_wpd_power_floor, wpe_online, wpe_alpha, bf_online, bf_forget, bf_loading, gss_online,
+        gss_forget, gss_prior_mass):
+    """What the three ``get_enhancer`` functions build alike from the keywords they share (see
+    `get_enhancer` for each): the ``wpe_block``, ``gss_block``, ``bf_block`` and plain fields of
+    an `Enhancer`, as the keyword arguments of its constructor.  The front door adds its own
+    ``activity`` and whatever else only it has.  (``activity_garbage_class`` is shared but
+    belongs to that activity: not read here.)"""
+    return dict(
+        multiarray=multiarray, context_samples=context_samples, bf_drop_context=bf_drop_context,
+        stft_size=stft_size, stft_shift=stft_shift, stft_fading=stft_fading, device_id=device_id,
+        wpe_per_array=bool(wpe_per_array), channel_keep=channel_keep, channel_bands=channel_bands,
+        wpe_block=wpe_block_from(wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context,
+                                 wpe_online, wpe_alpha),
+        gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
+                      verbose=False, online=gss_online, forget=gss_forget,
+                      prior_mass=gss_prior_mass),
+        bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
+                            segment_context=bf_segment_context,
+                            segment_min_mass=bf_segment_min_mass,
+                            null_interferer=bool(bf_null_interferer),
+                            null_min_mass=bf_null_min_mass,
+                            online=bf_online, forget=bf_forget, loading=bf_loading,
+                            **bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps,
+                                              bf_wpd_delay, bf_wpd_iterations,
+                                              bf_wpd_power_floor)))
+
+
+def _shared_keywords(given):
+    """The keywords of `_enhancer_fields` out of ``given``, the ``locals()`` at the head of a
+    ``get_enhancer``."""
+    import inspect
+    return {k: given[k] for k in inspect.signature(_enhancer_fields).parameters}
+
+
 def get_enhancer(
     multiarray=False,
     reference_array=None,
@@ -2005,37 +2004,13 @@ def get_enhancer(
     no effect with ``multiarray=False`` or ``wpe=False``.
     ``bf_segment_frames=L``: a time-varying 'mvdrSouden_ban' with statistics per segment of L
     STFT frames (see `Beamformer`); None: one filter per utterance."""
+    given = locals()
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
-
     return Enhancer(
-        multiarray=multiarray,
         reference_array=reference_array,
-        context_samples=context_samples,
-        wpe_block=wpe_block_from(wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context,
-                                 wpe_online, wpe_alpha),
+        iterator_factory=iterator_factory,
         activity=Activity(type=activity_type, garbage_class=activity_garbage_class,
                           path=activity_path, database_path=database_path,
                           store=activity_store),
-        gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
-                      verbose=False, online=gss_online, forget=gss_forget,
-                      prior_mass=gss_prior_mass),
-        bf_drop_context=bf_drop_context,
-        bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
-                            segment_context=bf_segment_context,
-                            segment_min_mass=bf_segment_min_mass,
-                            null_interferer=bool(bf_null_interferer),
-                            null_min_mass=bf_null_min_mass,
-                            online=bf_online, forget=bf_forget, loading=bf_loading,
-                            **bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps,
-                                              bf_wpd_delay, bf_wpd_iterations,
-                                              bf_wpd_power_floor)),
-        stft_size=stft_size,
-        stft_shift=stft_shift,
-        stft_fading=stft_fading,
-        device_id=device_id,
-        iterator_factory=iterator_factory,
-        wpe_per_array=bool(wpe_per_array),
-        channel_keep=channel_keep,
-        channel_bands=channel_bands,
-    )
+        **_enhancer_fields(**_shared_keywords(given)))

@@ -165,40 +165,15 @@ def get_enhancer(
     gss_forget=ops.GSS_ONLINE_FORGET,
     gss_prior_mass=ops.GSS_ONLINE_PRIOR_MASS,
 ):
-    """core_chime6.py:572-635 (same keyword arguments and defaults; ``activity_store``,
-    ``iterator_factory``, ``device_id``, ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*``,
-    ``bf_wpd_*``, ``wpe_online``, ``wpe_alpha``, ``bf_online``, ``bf_forget``, ``bf_loading``, ``gss_online``, ``gss_forget`` and ``gss_prior_mass`` are additions,
-    see core.get_enhancer)."""
+    """core_chime6.py:572-635 (same keyword arguments and defaults, and the additions of
+    `core.get_enhancer`, which describes every keyword)."""
+    given = locals()
     assert wpe is True or wpe is False, wpe
     assert activity_path is None or activity_type == 'path', (activity_path, activity_type)
     return Enhancer(
-        multiarray=multiarray,
         reference_array=reference_array,
-        context_samples=context_samples,
-        wpe_block=core.wpe_block_from(wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context,
-                                      wpe_online, wpe_alpha),
+        iterator_factory=iterator_factory,
         activity=Activity(type=activity_type, garbage_class=activity_garbage_class,
                           path=activity_path, database_path=database_path,
                           store=activity_store),
-        gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
-                      verbose=False, online=gss_online, forget=gss_forget,
-                      prior_mass=gss_prior_mass),
-        bf_drop_context=bf_drop_context,
-        bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
-                            segment_context=bf_segment_context,
-                            segment_min_mass=bf_segment_min_mass,
-                            null_interferer=bool(bf_null_interferer),
-                            null_min_mass=bf_null_min_mass,
-                            online=bf_online, forget=bf_forget, loading=bf_loading,
-                            **bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps,
-                                              bf_wpd_delay, bf_wpd_iterations,
-                                              bf_wpd_power_floor)),
-        stft_size=stft_size,
-        stft_shift=stft_shift,
-        stft_fading=stft_fading,
-        device_id=device_id,
-        iterator_factory=iterator_factory,
-        wpe_per_array=bool(wpe_per_array),
-        channel_keep=channel_keep,
-        channel_bands=channel_bands,
-    )
+        **core._enhancer_fields(**core._shared_keywords(given)))

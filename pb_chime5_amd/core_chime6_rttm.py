@@ -60,7 +60,7 @@ class Enhancer(core.Enhancer):
         """``refined_rttm``: see `core.Enhancer.enhance_session`."""
         from pb_chime5_amd import parallel
         if refined_rttm:
-            self._no_activity_options('enhance_session(refined_rttm=True)')
+            self._refuse('enhance_session(refined_rttm=True)', self._NOT_WITH_ACTIVITY)
         audio_dir = Path(audio_dir)
         it = self.get_dataset(session_ids)
         if parallel.is_master():
@@ -188,37 +188,12 @@ def get_enhancer(
     gss_forget=ops.GSS_ONLINE_FORGET,
     gss_prior_mass=ops.GSS_ONLINE_PRIOR_MASS,
 ):
-    """core_chime6_rttm.py:360-422 (same keyword arguments and defaults; ``device_id``,
-    ``wpe_per_array``, ``bf_segment_*``, ``channel_*``, ``bf_null_*``,
-    ``bf_wpd_*``, ``wpe_online``, ``wpe_alpha``, ``bf_online``, ``bf_forget``, ``bf_loading``, ``gss_online``, ``gss_forget`` and ``gss_prior_mass`` are additions, see core.get_enhancer)."""
+    """core_chime6_rttm.py:360-422 (same keyword arguments and defaults, and those additions
+    of `core.get_enhancer` that are no matter of the database; it describes every keyword)."""
+    given = locals()
     assert wpe is True or wpe is False, wpe
-    db = get_database(chime6_dir, database_rttm, multiarray)
     return Enhancer(
-        db=db,
-        context_samples=context_samples,
-        multiarray=multiarray,
+        db=get_database(chime6_dir, database_rttm, multiarray),
         reference_array=None,
-        wpe_block=core.wpe_block_from(wpe, wpe_tabs, wpe_delay, wpe_iterations, wpe_psd_context,
-                                      wpe_online, wpe_alpha),
         activity=Activity(garbage_class=activity_garbage_class, rttm=activity_rttm),
-        gss_block=GSS(iterations=bss_iterations, iterations_post=bss_iterations_post,
-                      verbose=False, online=gss_online, forget=gss_forget,
-                      prior_mass=gss_prior_mass),
-        bf_drop_context=bf_drop_context,
-        bf_block=Beamformer(type=bf, postfilter=postfilter, segment_frames=bf_segment_frames,
-                            segment_context=bf_segment_context,
-                            segment_min_mass=bf_segment_min_mass,
-                            null_interferer=bool(bf_null_interferer),
-                            null_min_mass=bf_null_min_mass,
-                            online=bf_online, forget=bf_forget, loading=bf_loading,
-                            **bf_block_kwargs(bf, wpe_tabs, wpe_delay, bf_wpd_taps,
-                                              bf_wpd_delay, bf_wpd_iterations,
-                                              bf_wpd_power_floor)),
-        stft_size=stft_size,
-        stft_shift=stft_shift,
-        stft_fading=stft_fading,
-        device_id=device_id,
-        wpe_per_array=bool(wpe_per_array),
-        channel_keep=channel_keep,
-        channel_bands=channel_bands,
-    )
+        **core._enhancer_fields(**core._shared_keywords(given)))

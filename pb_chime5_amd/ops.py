@@ -310,24 +310,77 @@ def check_wpe_online(taps=10, delay=2, alpha=WPE_ONLINE_ALPHA, num_channels=None
     return A, C
 
 
-class OnlineWPEState:
+class _OnlineState:
+    """What the states of the online stages share: named buffers in HBM whose shapes follow from
+    the sizes the state is built for (``key``), and their way to the host and back.  A subclass
+    says how the shapes follow from the sizes (`_shapes`), names the sizes (``_sizes``, for the
+    messages) and the buffers that are not complex128 (``dtypes``), and has its own ``struct``,
+    ``fresh`` and the shape inference at the head of ``from_host``."""
+    dtypes = {}
+
+    def __init__(self, ctx, *sizes):
+        self.ctx = ctx
+        self.key = tuple(int(v) for v in sizes)
+        self.shapes = self._shapes(*self.key)
+        self.bufs = {k: ctx.empty(np.dtype(self.dtypes.get(k, np.complex128)).itemsize
+                                  * int(np.prod(shape, dtype=np.int64)))
+                     for k, shape in self.shapes.items()}
+
+    def to_host(self):
+        """The buffers as NumPy arrays by name: everything `from_host` needs (synchronises)."""
+        return {k: self.ctx.to_host(self.bufs[k], shape, self.dtypes.get(k, np.complex128))
+                for k, shape in self.shapes.items()}
+
+    @classmethod
+    def _from_host(cls, host, sizes, ctx, expected=str):
+        """The tail of ``from_host``: every array of ``host`` against the shapes of ``sizes``
+        (ValueError; ``expected(shape)`` words the shape it should have had), then the upload."""
+        arrays = {}
+        for k, shape in cls._shapes(*sizes).items():
+            arrays[k] = a = np.ascontiguousarray(host[k], dtype=cls.dtypes.get(k, np.complex128))
+            if a.shape != shape:
+                raise ValueError(f'{k}: shape {a.shape} is not {expected(shape)}')
+        ctx = ctx or default_context()
+        state = cls(ctx, *sizes)
+        for k, a in arrays.items():
+            ctx.upload(state.bufs[k], a)
+        return state
+
+    def copy(self):
+        """An independent state with the same bits, in the same context."""
+        return type(self).from_host(self.to_host(), ctx=self.ctx)
+
+
+def _state_context(state, cls, key, ctx):
+    """A caller's ``state=`` against this call: of the class ``cls``, built for the call's sizes
+    ``key``, living in ``ctx`` where one is given.  Returns the context to use (``ctx`` without
+    a state)."""
+    if state is None:
+        return ctx
+    if not isinstance(state, cls):
+        raise ValueError(f'state: {type(state).__name__} is not an {cls.__name__}')
+    if state.key != key:
+        raise ValueError(f'state: built for ({cls._sizes}) = {state.key}, the call has {key}')
+    if ctx is not None and ctx is not state.ctx:
+        raise ValueError('state: it lives in another context than ctx')
+    return state.ctx
+
+
+class OnlineWPEState(_OnlineState):
     """The state of the online WPE in HBM (gss_wpe_online_state), caller-owned like a
     `DeviceModel`: inv_cov P (F,A,n,n), filter G (F,A,n,C) and history (F,A,taps + delay,C) -- the
     last frames, oldest first --, complex128, n = taps * C."""
+    _sizes = 'F, A, C, taps, delay'
 
     def __init__(self, ctx, F, A, C, taps, delay):
-        self.ctx = ctx
-        self.F, self.A, self.C, self.taps, self.delay = (int(v) for v in (F, A, C, taps, delay))
+        super().__init__(ctx, F, A, C, taps, delay)
+        self.F, self.A, self.C, self.taps, self.delay = self.key
         self.n, self.L = self.taps * self.C, self.taps + self.delay
-        self.shapes = {'inv_cov': (self.F, self.A, self.n, self.n),
-                       'filter': (self.F, self.A, self.n, self.C),
-                       'history': (self.F, self.A, self.L, self.C)}
-        self.bufs = {k: ctx.empty(16 * int(np.prod(v, dtype=np.int64)))
-                     for k, v in self.shapes.items()}
 
-    @property
-    def key(self):
-        return self.F, self.A, self.C, self.taps, self.delay
+    @staticmethod
+    def _shapes(F, A, C, taps, delay):
+        n = taps * C
+        return {'inv_cov': (F, A, n, n), 'filter': (F, A, n, C), 'history': (F, A, taps + delay, C)}
 
     def struct(self):
         return GssWpeOnlineState(inv_cov_dev=self.bufs['inv_cov'].ptr,
@@ -353,33 +406,20 @@ class OnlineWPEState:
     def to_host(self):
         """{'inv_cov', 'filter', 'history'} as NumPy arrays plus 'taps' and 'delay': everything
         `from_host` needs (synchronises)."""
-        out = {k: self.ctx.to_host(self.bufs[k], shape, np.complex128)
-               for k, shape in self.shapes.items()}
-        out.update(taps=self.taps, delay=self.delay)
-        return out
+        return dict(super().to_host(), taps=self.taps, delay=self.delay)
 
     @classmethod
     def from_host(cls, host, *, ctx=None):
         """A device state from the dict of `to_host` (in any context: a state saved in one
         process continues in another).  ValueError for shapes that do not fit each other."""
-        G = np.ascontiguousarray(host['filter'], dtype=np.complex128)
+        G = np.asarray(host['filter'])
         if G.ndim != 4:
             raise ValueError(f'filter: shape {G.shape} is not (F,A,n,C)')
         F, A, n, C = G.shape
         taps, delay = int(host['taps']), int(host['delay'])
         check_wpe_online(taps, delay, num_channels=A * C, arrays=A)
-        ctx = ctx or default_context()
-        state = cls(ctx, F, A, C, taps, delay)
-        for k, shape in state.shapes.items():
-            a = np.ascontiguousarray(host[k], dtype=np.complex128)
-            if a.shape != shape:
-                raise ValueError(f'{k}: shape {a.shape} is not {shape} (taps={taps}, delay={delay})')
-            ctx.upload(state.bufs[k], a)
-        return state
-
-    def copy(self):
-        """An independent state with the same bits, in the same context."""
-        return OnlineWPEState.from_host(self.to_host(), ctx=self.ctx)
+        return cls._from_host(host, (F, A, C, taps, delay), ctx,
+                              lambda shape: f'{shape} (taps={taps}, delay={delay})')
 
 
 def wpe_online_dtf(Obs, taps=10, delay=2, alpha=WPE_ONLINE_ALPHA, *, arrays=1, state=None,
@@ -395,15 +435,7 @@ def wpe_online_dtf(Obs, taps=10, delay=2, alpha=WPE_ONLINE_ALPHA, *, arrays=1, s
         raise ValueError(f'Obs: shape {Obs.shape} is not (D,T,F)')
     D, T, F = Obs.shape
     A, C = check_wpe_online(taps, delay, alpha, D, arrays)
-    if state is not None:
-        if not isinstance(state, OnlineWPEState):
-            raise ValueError(f'state: {type(state).__name__} is not an OnlineWPEState')
-        if state.key != (F, A, C, int(taps), int(delay)):
-            raise ValueError(f'state: built for (F, A, C, taps, delay) = {state.key}, the call has '
-                             f'{(F, A, C, int(taps), int(delay))}')
-        if ctx is not None and ctx is not state.ctx:
-            raise ValueError('state: it lives in another context than ctx')
-        ctx = state.ctx
+    ctx = _state_context(state, OnlineWPEState, (F, A, C, int(taps), int(delay)), ctx)
     ctx = ctx or default_context()
     if T == 0 or F == 0:
         return np.zeros((D, T, F), np.complex128)
@@ -1183,19 +1215,18 @@ def _bf_online_cfg(forget, loading, ref_channel, wpe_online=False, wpe_alpha=WPE
                        wpe_online=int(bool(wpe_online)), wpe_alpha=float(wpe_alpha))
 
 
-class OnlineMVDRState:
+class OnlineMVDRState(_OnlineState):
     """The state of the online MVDR in HBM (gss_mvdr_online_state), caller-owned like an
     `OnlineWPEState`: the running sums phi_x and phi_n (F,D,D), complex128, Hermitian."""
+    _sizes = 'F, D'
 
     def __init__(self, ctx, F, D):
-        self.ctx = ctx
-        self.F, self.D = int(F), int(D)
-        self.shapes = {'phi_x': (self.F, self.D, self.D), 'phi_n': (self.F, self.D, self.D)}
-        self.bufs = {k: ctx.empty(16 * self.F * self.D * self.D) for k in self.shapes}
+        super().__init__(ctx, F, D)
+        self.F, self.D = self.key
 
-    @property
-    def key(self):
-        return self.F, self.D
+    @staticmethod
+    def _shapes(F, D):
+        return {'phi_x': (F, D, D), 'phi_n': (F, D, D)}
 
     def struct(self):
         return GssMvdrOnlineState(phi_x=self.bufs['phi_x'].ptr, phi_n=self.bufs['phi_n'].ptr,
@@ -1222,34 +1253,19 @@ class OnlineMVDRState:
             float(loading), ctypes.byref(state.struct())), 'gss_mvdr_online_init')
         return state
 
-    def to_host(self):
-        """{'phi_x', 'phi_n'} as NumPy arrays: everything `from_host` needs (synchronises)."""
-        return {k: self.ctx.to_host(self.bufs[k], shape, np.complex128)
-                for k, shape in self.shapes.items()}
-
     @classmethod
     def from_host(cls, host, *, ctx=None):
-        """A device state from the dict of `to_host` (in any context: a state saved in one
-        process continues in another).  ValueError for shapes that do not fit each other."""
-        px = np.ascontiguousarray(host['phi_x'], dtype=np.complex128)
+        """A device state from the dict of `to_host` ({'phi_x', 'phi_n'}; in any context: a state
+        saved in one process continues in another).  ValueError for shapes that do not fit each
+        other."""
+        px = np.asarray(host['phi_x'])
         if px.ndim != 3 or px.shape[1] != px.shape[2]:
             raise ValueError(f'phi_x: shape {px.shape} is not (F,D,D)')
         F, D, _ = px.shape
         if F < 1:
             raise ValueError(f'phi_x: shape {px.shape} has no frequency')
         check_bf_online(num_channels=D)
-        pn = np.ascontiguousarray(host['phi_n'], dtype=np.complex128)
-        if pn.shape != px.shape:
-            raise ValueError(f'phi_n: shape {pn.shape} is not {px.shape}')
-        ctx = ctx or default_context()
-        state = cls(ctx, F, D)
-        ctx.upload(state.bufs['phi_x'], px)
-        ctx.upload(state.bufs['phi_n'], pn)
-        return state
-
-    def copy(self):
-        """An independent state with the same bits, in the same context."""
-        return OnlineMVDRState.from_host(self.to_host(), ctx=self.ctx)
+        return cls._from_host(host, (F, D), ctx)
 
 
 def _check_online_mask(mask, name, T, F):
@@ -1281,15 +1297,7 @@ def mvdr_souden_online_from_masks(Y, X_mask, N_mask, ban=False, *, forget=BF_ONL
     forget, loading, ref_channel = check_bf_online(forget, loading, ref_channel, D)
     X_mask = _check_online_mask(X_mask, 'X_mask', T, F)
     N_mask = _check_online_mask(N_mask, 'N_mask', T, F)
-    if state is not None:
-        if not isinstance(state, OnlineMVDRState):
-            raise ValueError(f'state: {type(state).__name__} is not an OnlineMVDRState')
-        if state.key != (F, D):
-            raise ValueError(f'state: built for (F, D) = {state.key}, the call has {(F, D)}')
-        if ctx is not None and ctx is not state.ctx:
-            raise ValueError('state: it lives in another context than ctx')
-        ctx = state.ctx
-    ctx = ctx or default_context()
+    ctx = _state_context(state, OnlineMVDRState, (F, D), ctx) or default_context()
     fallbacks = 0
     if T == 0 or F == 0:
         X_hat, W = np.zeros((T, F), np.complex128), np.zeros((T, F, D), np.complex128)
@@ -1340,22 +1348,20 @@ def check_gss_online(forget=GSS_ONLINE_FORGET, prior_mass=GSS_ONLINE_PRIOR_MASS,
     return float(forget), float(prior_mass)
 
 
-class OnlineCACGMMState:
+class OnlineCACGMMState(_OnlineState):
     """The state of the online CACGMM in HBM (gss_cacgmm_online_state), caller-owned like an
     `OnlineMVDRState`: the running sums ``s`` (F,K,D,D), complex128, Hermitian, and the masses
     ``n`` (F,K).  The model they stand for is B_k = s_k / n_k, pi_k = n_k / sum_j n_j."""
+    _sizes = 'F, K, D'
+    dtypes = {'s': np.complex128, 'n': np.float64}
 
     def __init__(self, ctx, F, K, D):
-        self.ctx = ctx
-        self.F, self.K, self.D = int(F), int(K), int(D)
-        self.shapes = {'s': (self.F, self.K, self.D, self.D), 'n': (self.F, self.K)}
-        self.dtypes = {'s': np.complex128, 'n': np.float64}
-        self.bufs = {'s': ctx.empty(16 * self.F * self.K * self.D * self.D),
-                     'n': ctx.empty(8 * self.F * self.K)}
+        super().__init__(ctx, F, K, D)
+        self.F, self.K, self.D = self.key
 
-    @property
-    def key(self):
-        return self.F, self.K, self.D
+    @staticmethod
+    def _shapes(F, K, D):
+        return {'s': (F, K, D, D), 'n': (F, K)}
 
     def struct(self):
         return GssCacgmmOnlineState(s=self.bufs['s'].ptr, n=self.bufs['n'].ptr, F=self.F, K=self.K,
@@ -1402,34 +1408,18 @@ class OnlineCACGMMState:
             'gss_cacgmm_online_model')
         return dev.to_host(self.ctx)
 
-    def to_host(self):
-        """{'s', 'n'} as NumPy arrays: everything `from_host` needs (synchronises)."""
-        return {k: self.ctx.to_host(self.bufs[k], shape, self.dtypes[k])
-                for k, shape in self.shapes.items()}
-
     @classmethod
     def from_host(cls, host, *, ctx=None):
-        """A device state from the dict of `to_host` (in any context: a state saved in one
-        process continues in another).  ValueError for shapes that do not fit each other."""
-        s = np.ascontiguousarray(host['s'], dtype=np.complex128)
+        """A device state from the dict of `to_host` ({'s', 'n'}; in any context: a state saved
+        in one process continues in another).  ValueError for shapes that do not fit each other."""
+        s = np.asarray(host['s'])
         if s.ndim != 4 or s.shape[2] != s.shape[3]:
             raise ValueError(f's: shape {s.shape} is not (F,K,D,D)')
         F, K, D, _ = s.shape
         if F < 1:
             raise ValueError(f's: shape {s.shape} has no frequency')
         check_gss_online(num_classes=K, num_channels=D)
-        n = np.ascontiguousarray(host['n'], dtype=np.float64)
-        if n.shape != (F, K):
-            raise ValueError(f'n: shape {n.shape} is not (F,K) = {(F, K)}')
-        ctx = ctx or default_context()
-        state = cls(ctx, F, K, D)
-        ctx.upload(state.bufs['s'], s)
-        ctx.upload(state.bufs['n'], n)
-        return state
-
-    def copy(self):
-        """An independent state with the same bits, in the same context."""
-        return OnlineCACGMMState.from_host(self.to_host(), ctx=self.ctx)
+        return cls._from_host(host, (F, K, D), ctx, lambda shape: f'(F,K) = {shape}')
 
 
 def cacgmm_posteriors_online(Obs, source_activity_mask=None, *, num_classes=None,
@@ -1457,16 +1447,9 @@ def cacgmm_posteriors_online(Obs, source_activity_mask=None, *, num_classes=None
     mask, K = None, None
     if source_activity_mask is not None:
         _, mask, K = guidance_tables(None, source_activity_mask, T, F)
-    if state is not None:
-        if not isinstance(state, OnlineCACGMMState):
-            raise ValueError(f'state: {type(state).__name__} is not an OnlineCACGMMState')
-        if K is None:
-            K = state.K
-        if state.key != (F, K, D):
-            raise ValueError(f'state: built for (F, K, D) = {state.key}, the call has {(F, K, D)}')
-        if ctx is not None and ctx is not state.ctx:
-            raise ValueError('state: it lives in another context than ctx')
-        ctx = state.ctx
+    if K is None:       # (no mask: the state's, once `_state_context` has seen what it is)
+        K = getattr(state, 'K', None)
+    ctx = _state_context(state, OnlineCACGMMState, (F, K, D), ctx)
     if num_classes is not None and num_classes != K:
         raise ValueError(f'num_classes={num_classes!r} but the mask / state has {K} classes')
     forget, prior_mass = check_gss_online(forget, prior_mass, K, D)
@@ -2003,12 +1986,9 @@ def enhance_observation_select(obs, activity, target_index, start_context_sample
     ``selected_channels`` (n,), which maps it back.  The limits of the beamformers (fewer than
     30 channels) apply to n, not D.  bf='ch2' and a per-array WPE are NotImplementedError, bad
     settings ValueError, both before any device work."""
-    if params is None:
-        params = make_params(**param_kwargs)
+    params = _fused_params(params, param_kwargs)
     _check_select_params(params, 'channel selection')
-    obs = np.asarray(obs)
-    if obs.ndim != 2:
-        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    obs = _obs_dn(obs)
     sel = ChannelSelect(keep, params.stft_size // 2 + 1, bank, bands, floor, sample_rate)
     n = sel.count(obs.shape[0])
     ctx = ctx or default_context()
@@ -2105,12 +2085,9 @@ def enhance_observation_activity(obs, activity, target_index, start_context_samp
     (x_hat, scores, power, details) with ``debug=True``; x_hat and the details have the bits of
     `enhance_observation`.  ``freq_weights`` (stft_size // 2 + 1,) >= 0, None: all ones; a bad
     table is ValueError before any device work."""
-    if params is None:
-        params = make_params(**param_kwargs)
+    params = _fused_params(params, param_kwargs)
     w = check_freq_weights(freq_weights, params.stft_size // 2 + 1)
-    obs = np.asarray(obs)
-    if obs.ndim != 2:
-        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    obs = _obs_dn(obs)
     ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
     w_d = ctx.to_device(w) if w is not None else None
     s_d = ctx.empty(8 * utt.K * max(utt.T, 1))
@@ -2181,9 +2158,10 @@ _FUSED_ENTRIES = {
 def _enqueue_fused(ctx, params, obs_d, D, N, act_d, K, N_act, target_index, start_context,
                    end_context, out_d, taps=None, pcm=False, option=None, value=None):
     """The one place that issues a fused one-target call on inputs in HBM.  ``option``: a key of
-    `_FUSED_ENTRIES`; ``value``: the struct that entry takes (gss_bf_wpd, gss_wpe_online_cfg, gss_bf_online,
-    gss_bf_lcmv, gss_bf_segments, gss_channel_select), for 'activity' the device buffers (weights or None,
-    scores, power or None), for 'gss_online' the pair (gss_em_online, gss_bf_online or None).  ``pcm``: int16 samples, the entry's _pcm16 twin."""
+    `_FUSED_ENTRIES`; ``value``: the struct that entry takes (gss_bf_wpd, gss_wpe_online_cfg,
+    gss_bf_online, gss_bf_lcmv, gss_bf_segments, gss_channel_select), for 'activity' the device
+    buffers (weights or None, scores, power or None), for 'gss_online' the pair (gss_em_online,
+    gss_bf_online or None).  ``pcm``: int16 samples, the entry's _pcm16 twin."""
     name, twin, label = _FUSED_ENTRIES[option]
     assert twin is not None or not pcm, f'the {label} call has no pcm16 twin'
 
@@ -2526,6 +2504,46 @@ def _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx):
     return ctx, utt, bufs, taps
 
 
+def _fused_params(params, param_kwargs):
+    """``params`` of a fused wrapper: as given, or (None) made from its loose keywords."""
+    return make_params(**param_kwargs) if params is None else params
+
+
+def _obs_dn(obs):
+    obs = np.asarray(obs)
+    if obs.ndim != 2:
+        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    return obs
+
+
+def _check_fused_wpe_online(params, alpha, num_channels, wpe_arrays):
+    """An online WPE inside a fused call, before any device work: it replaces a WPE stage that
+    runs, has no PSD context, and its settings are `check_wpe_online`'s."""
+    if not params.wpe:
+        raise ValueError('wpe_online with wpe=False: there is no WPE stage to replace')
+    if params.wpe_psd_context != 0:
+        raise ValueError(f'wpe_online with wpe_psd_context={params.wpe_psd_context}: the online '
+                         'WPE has no PSD context')
+    check_wpe_online(params.wpe_taps, params.wpe_delay, alpha, num_channels,
+                     params.wpe_arrays if wpe_arrays is None else wpe_arrays)
+
+
+def _fused_one_target(call, params, wpe_arrays, window, debug, ctx, option=None, extras=None):
+    """The tail that the one-target wrappers on a time-domain activity share once their own
+    arguments are checked.  ``call``: (obs, activity, target_index, start_context_samples,
+    end_context_samples); ``option``: the one keyword of `ResidentUtterance.enqueue` the wrapper
+    adds (None: the plain call); ``extras(ctx, details)``: what it adds to the ``debug`` details."""
+    obs, activity, *target_and_contexts = call
+    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
+    utt.enqueue(*target_and_contexts, taps, **(option or {}))
+    x_hat, details = _one_target_result(utt, bufs, debug)
+    if not debug:
+        return x_hat
+    if extras is not None:
+        extras(ctx, details)
+    return x_hat, details
+
+
 def _require_souden(params, setting, form):
     """What only bf='mvdrSouden_ban' combines with, before any device work."""
     if params.bf != _BF_CODES['mvdrSouden_ban']:
@@ -2543,14 +2561,10 @@ def enhance_observation(obs, activity, target_index, start_context_samples,
     (x_hat, details) with ``debug=True`` where details holds the reference's
     debug locals in the reference's layouts.  ``wpe_arrays`` = A > 1: WPE per microphone
     array (A arrays of D / A channels, array-major) instead of one joint WPE."""
-    if params is None:
-        params = make_params(**param_kwargs)
-    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
-    utt.enqueue(target_index, start_context_samples, end_context_samples, taps)
-    x_hat, details = _one_target_result(utt, bufs, debug)
-    if not debug:
-        return x_hat
-    return x_hat, details
+    params = _fused_params(params, param_kwargs)
+    return _fused_one_target(
+        (obs, activity, target_index, start_context_samples, end_context_samples), params,
+        wpe_arrays, window, debug, ctx)
 
 
 def enhance_observation_segments(obs, activity, target_index, start_context_samples,
@@ -2563,20 +2577,14 @@ def enhance_observation_segments(obs, activity, target_index, start_context_samp
     ``details['segment_fallbacks']``.  Only ``bf='mvdrSouden_ban'`` has segments
     (NotImplementedError otherwise); bad segment settings are ValueError, both before any
     device work."""
-    if params is None:
-        params = make_params(**param_kwargs)
+    params = _fused_params(params, param_kwargs)
     _require_souden(params, 'segment_frames', 'a segment-wise form')
-    obs = np.asarray(obs)
-    if obs.ndim != 2:
-        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    obs = _obs_dn(obs)
     seg = check_bf_segments(segment_frames, segment_context, min_mass, obs.shape[0])
-    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
-    utt.enqueue(target_index, start_context_samples, end_context_samples, taps, segments=seg)
-    x_hat, details = _one_target_result(utt, bufs, debug)
-    if not debug:
-        return x_hat
-    details['segment_fallbacks'] = ctx.last_segment_fallbacks()
-    return x_hat, details
+    return _fused_one_target(
+        (obs, activity, target_index, start_context_samples, end_context_samples), params,
+        wpe_arrays, window, debug, ctx, dict(segments=seg),
+        lambda ctx, details: details.update(segment_fallbacks=ctx.last_segment_fallbacks()))
 
 
 def enhance_observation_lcmv(obs, activity, target_index, start_context_samples,
@@ -2591,35 +2599,31 @@ def enhance_observation_lcmv(obs, activity, target_index, start_context_samples,
     ``interferer`` (-1: none), ``interferer_mask`` (T,F) and ``lcmv_fallbacks``.  Only
     ``bf='mvdrSouden_ban'`` has it (NotImplementedError otherwise); bad settings are
     ValueError, both before any device work."""
-    if params is None:
-        params = make_params(**param_kwargs)
+    params = _fused_params(params, param_kwargs)
     _require_souden(params, 'null_interferer', 'an interferer-nulling form')
-    obs = np.asarray(obs)
-    if obs.ndim != 2:
-        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    obs = _obs_dn(obs)
     _check_lcmv_channels(obs.shape[0])
     K = np.shape(activity)[0]
     bf = check_bf_lcmv(K, target_index, interferer, candidates, min_mass, obs.shape[0])
-    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
-    utt.enqueue(target_index, start_context_samples, end_context_samples, taps, lcmv=bf)
-    x_hat, details = _one_target_result(utt, bufs, debug)
-    if not debug:
-        return x_hat
-    found = details['interferer'] = ctx.last_lcmv_interferer()
-    details['lcmv_fallbacks'] = ctx.last_lcmv_fallbacks()
-    # the interferer's posterior with the context frames zeroed: the bits the call used
-    mask = np.zeros_like(details['target_mask'])
-    if found >= 0:
-        mask[...] = details['posterior'][found]
-        if params.bf_drop_context:
-            sf, ef = (samples_to_stft_frames(c, params.stft_size, params.stft_shift,
-                                             fading=params.stft_fading)
-                      for c in (start_context_samples, end_context_samples))
-            mask[:sf] = 0
-            if ef > 0:
-                mask[-ef:] = 0
-    details['interferer_mask'] = mask
-    return x_hat, details
+
+    def extras(ctx, details):
+        found = details['interferer'] = ctx.last_lcmv_interferer()
+        details['lcmv_fallbacks'] = ctx.last_lcmv_fallbacks()
+        # the interferer's posterior with the context frames zeroed: the bits the call used
+        mask = np.zeros_like(details['target_mask'])
+        if found >= 0:
+            mask[...] = details['posterior'][found]
+            if params.bf_drop_context:
+                sf, ef = (samples_to_stft_frames(c, params.stft_size, params.stft_shift,
+                                                 fading=params.stft_fading)
+                          for c in (start_context_samples, end_context_samples))
+                mask[:sf] = 0
+                if ef > 0:
+                    mask[-ef:] = 0
+        details['interferer_mask'] = mask
+    return _fused_one_target(
+        (obs, activity, target_index, start_context_samples, end_context_samples), params,
+        wpe_arrays, window, debug, ctx, dict(lcmv=bf), extras)
 
 
 def enhance_observation_wpd(obs, activity, target_index, start_context_samples,
@@ -2634,22 +2638,16 @@ def enhance_observation_wpd(obs, activity, target_index, start_context_samples,
     the mixture model) plus ``wpd_zero_pivots``.  ``params.bf`` must be 'mvdrSouden_ban' (its
     code selects the Souden solve; ``ban`` decides the normalisation): NotImplementedError
     otherwise; bad settings are ValueError, both before any device work."""
-    if params is None:
-        params = make_params(**param_kwargs)
+    params = _fused_params(params, param_kwargs)
     _require_souden(params, 'the WPD beamformer', 'a WPD form')
-    obs = np.asarray(obs)
-    if obs.ndim != 2:
-        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    obs = _obs_dn(obs)
     bf = check_bf_wpd(params.wpe_taps if taps is None else taps,
                       params.wpe_delay if delay is None else delay, iterations, power_floor, ban,
                       obs.shape[0])
-    ctx, utt, bufs, dbg = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
-    utt.enqueue(target_index, start_context_samples, end_context_samples, dbg, wpd=bf)
-    x_hat, details = _one_target_result(utt, bufs, debug)
-    if not debug:
-        return x_hat
-    details['wpd_zero_pivots'] = ctx.last_wpd_zero_pivots()
-    return x_hat, details
+    return _fused_one_target(
+        (obs, activity, target_index, start_context_samples, end_context_samples), params,
+        wpe_arrays, window, debug, ctx, dict(wpd=bf),
+        lambda ctx, details: details.update(wpd_zero_pivots=ctx.last_wpd_zero_pivots()))
 
 
 def enhance_observation_wpe_online(obs, activity, target_index, start_context_samples,
@@ -2661,25 +2659,12 @@ def enhance_observation_wpe_online(obs, activity, target_index, start_context_sa
     arrays are those of ``params``, its ``wpe_iterations`` is not read.  ``debug`` details as
     there (``Obs`` is the output of the online WPE).  ValueError for bad settings, ``wpe=False``
     or a PSD context, before any device work."""
-    if params is None:
-        params = make_params(**param_kwargs)
-    obs = np.asarray(obs)
-    if obs.ndim != 2:
-        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
-    if not params.wpe:
-        raise ValueError('wpe_online with wpe=False: there is no WPE stage to replace')
-    if params.wpe_psd_context != 0:
-        raise ValueError(f'wpe_online with wpe_psd_context={params.wpe_psd_context}: the online '
-                         'WPE has no PSD context')
-    check_wpe_online(params.wpe_taps, params.wpe_delay, alpha, obs.shape[0],
-                     params.wpe_arrays if wpe_arrays is None else wpe_arrays)
-    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
-    utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
-                wpe_online=GssWpeOnlineCfg(alpha=float(alpha)))
-    x_hat, details = _one_target_result(utt, bufs, debug)
-    if not debug:
-        return x_hat
-    return x_hat, details
+    params = _fused_params(params, param_kwargs)
+    obs = _obs_dn(obs)
+    _check_fused_wpe_online(params, alpha, obs.shape[0], wpe_arrays)
+    return _fused_one_target(
+        (obs, activity, target_index, start_context_samples, end_context_samples), params,
+        wpe_arrays, window, debug, ctx, dict(wpe_online=GssWpeOnlineCfg(alpha=float(alpha))))
 
 
 def enhance_observation_bf_online(obs, activity, target_index, start_context_samples,
@@ -2694,31 +2679,19 @@ def enhance_observation_bf_online(obs, activity, target_index, start_context_sam
     `enhance_observation_wpe_online`.  ``debug`` details as there plus ``bf_online_fallbacks``.
     Only ``bf='mvdrSouden_ban'`` has it (NotImplementedError otherwise); bad settings are
     ValueError, both before any device work."""
-    if params is None:
-        params = make_params(**param_kwargs)
+    params = _fused_params(params, param_kwargs)
     _require_souden(params, 'bf_online', 'an online form')
-    obs = np.asarray(obs)
-    if obs.ndim != 2:
-        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    obs = _obs_dn(obs)
     forget, loading, ref_channel = check_bf_online(forget, loading, ref_channel, obs.shape[0])
     if wpe_online:
-        if not params.wpe:
-            raise ValueError('wpe_online with wpe=False: there is no WPE stage to replace')
-        if params.wpe_psd_context != 0:
-            raise ValueError(f'wpe_online with wpe_psd_context={params.wpe_psd_context}: the '
-                             'online WPE has no PSD context')
-        check_wpe_online(params.wpe_taps, params.wpe_delay, wpe_alpha, obs.shape[0],
-                         params.wpe_arrays if wpe_arrays is None else wpe_arrays)
+        _check_fused_wpe_online(params, wpe_alpha, obs.shape[0], wpe_arrays)
     elif wpe_alpha != WPE_ONLINE_ALPHA:
         raise ValueError(f'wpe_alpha={wpe_alpha!r} without wpe_online: nobody reads it')
-    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
-    utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
-                bf_online=_bf_online_cfg(forget, loading, ref_channel, wpe_online, wpe_alpha))
-    x_hat, details = _one_target_result(utt, bufs, debug)
-    if not debug:
-        return x_hat
-    details['bf_online_fallbacks'] = ctx.last_mvdr_online_fallbacks()
-    return x_hat, details
+    bf = _bf_online_cfg(forget, loading, ref_channel, wpe_online, wpe_alpha)
+    return _fused_one_target(
+        (obs, activity, target_index, start_context_samples, end_context_samples), params,
+        wpe_arrays, window, debug, ctx, dict(bf_online=bf),
+        lambda ctx, details: details.update(bf_online_fallbacks=ctx.last_mvdr_online_fallbacks()))
 
 
 def enhance_observation_gss_online(obs, activity, target_index, start_context_samples,
@@ -2736,11 +2709,8 @@ def enhance_observation_gss_online(obs, activity, target_index, start_context_sa
     ``wpe_online`` the online WPE precedes: the whole zero-look-ahead chain in one call.
     ``debug`` details as there plus ``gss_online_fallbacks`` (and ``bf_online_fallbacks``).
     Bad settings are ValueError before any device work."""
-    if params is None:
-        params = make_params(**param_kwargs)
-    obs = np.asarray(obs)
-    if obs.ndim != 2:
-        raise ValueError(f'obs: shape {obs.shape} is not (D,N)')
+    params = _fused_params(params, param_kwargs)
+    obs = _obs_dn(obs)
     forget, prior_mass = check_gss_online(forget, prior_mass, np.shape(activity)[0], obs.shape[0])
     em = GssEmOnline(forget=forget, prior_mass=prior_mass)
     bf = None
@@ -2749,27 +2719,19 @@ def enhance_observation_gss_online(obs, activity, target_index, start_context_sa
         bf_forget, bf_loading, ref_channel = check_bf_online(bf_forget, bf_loading, ref_channel,
                                                              obs.shape[0])
         if wpe_online:
-            if not params.wpe:
-                raise ValueError('wpe_online with wpe=False: there is no WPE stage to replace')
-            if params.wpe_psd_context != 0:
-                raise ValueError(f'wpe_online with wpe_psd_context={params.wpe_psd_context}: the '
-                                 'online WPE has no PSD context')
-            check_wpe_online(params.wpe_taps, params.wpe_delay, wpe_alpha, obs.shape[0],
-                             params.wpe_arrays if wpe_arrays is None else wpe_arrays)
+            _check_fused_wpe_online(params, wpe_alpha, obs.shape[0], wpe_arrays)
         bf = _bf_online_cfg(bf_forget, bf_loading, ref_channel, wpe_online, wpe_alpha)
     elif wpe_online:
         raise ValueError('wpe_online without bf_online inside the gss_online call: the online WPE '
                          'rides on the online MVDR\'s descriptor')
-    ctx, utt, bufs, taps = _resident_call(obs, activity, params, wpe_arrays, window, debug, ctx)
-    utt.enqueue(target_index, start_context_samples, end_context_samples, taps,
-                gss_online=(em, bf))
-    x_hat, details = _one_target_result(utt, bufs, debug)
-    if not debug:
-        return x_hat
-    if bf is not None:
-        details['bf_online_fallbacks'] = ctx.last_mvdr_online_fallbacks()
-    details['gss_online_fallbacks'] = ctx.last_cacgmm_online_fallbacks()
-    return x_hat, details
+
+    def extras(ctx, details):
+        if bf is not None:
+            details['bf_online_fallbacks'] = ctx.last_mvdr_online_fallbacks()
+        details['gss_online_fallbacks'] = ctx.last_cacgmm_online_fallbacks()
+    return _fused_one_target(
+        (obs, activity, target_index, start_context_samples, end_context_samples), params,
+        wpe_arrays, window, debug, ctx, dict(gss_online=(em, bf)), extras)
 
 
 class GuidedUtterance:
@@ -2812,8 +2774,7 @@ def enhance_observation_guided(obs, initialization, source_activity_mask, target
     STFT, take the place of the time-domain activity.  Everything else -- STFT, WPE,
     beamformer, postfilter, iSTFT, ``debug`` details (without ``acitivity_freq``) -- as
     there."""
-    if params is None:
-        params = make_params(**param_kwargs)
+    params = _fused_params(params, param_kwargs)
     params = params_for(params, np.shape(obs)[0], wpe_arrays)
     ctx = ctx or default_context()
     _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
@@ -2905,8 +2866,7 @@ def enhance_observation_targets(obs, activity, target_indices, start_context_sam
     ``distortion_mask`` / ``X_hat`` (S,T,F), ``ref_channel`` (S,).  A failing target raises
     what the one-target call raises, for the first such target in target order
     (``target_names[s]`` names it in the message)."""
-    if params is None:
-        params = make_params(**param_kwargs)
+    params = _fused_params(params, param_kwargs)
     params = params_for(params, np.shape(obs)[0], wpe_arrays)
     targets = [int(t) for t in target_indices]
     S = len(targets)
@@ -3015,8 +2975,7 @@ def separate_observation(obs, initialization, *, params=None, window=None, debug
     ``return_posterior`` also the posteriors (K,T,F); with ``debug=True`` also the details of
     `enhance_observation_targets` (no ``acitivity_freq``: there is no activity).  The per-array
     WPE is NotImplementedError; every argument error is a ValueError before any device work."""
-    if params is None:
-        params = make_params(**param_kwargs)
+    params = _fused_params(params, param_kwargs)
     check_separate_args(obs, initialization, params)
     ctx = ctx or default_context()
     _prepare_windows(ctx, params.stft_size, params.stft_shift, window)
