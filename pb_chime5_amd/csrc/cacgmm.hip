@@ -1892,15 +1892,6 @@ int em_chunks(int F, int64_t T, int D, int *chunk_frames) {
     return (int)((tiles + tiles_per_chunk - 1) / tiles_per_chunk);
 }
 
-template <typename Kern>
-int raise_lds_limit(gss_ctx *ctx, Kern kern, size_t lds) {
-    if (lds > 64 * 1024)
-        GSS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds));
-    return GSS_OK;
-}
-
 template <int K>
 int launch_estep(gss_ctx *ctx, int mode, const EmArgs &a, const cplx *Mq, int F) {
     const size_t lds = em_estep_lds(a.D, K);
@@ -2177,35 +2168,26 @@ EmStrides em_strides(const EmBlockPlan &p, int F, int64_t T, int D) {
 
 }  // namespace
 
-// PSD accumulation of the beamformer: same kernel, raw observations, two masks.
-// W = (F, 2, T) [target, distortion]; part = (F, nch, 2, NE).  S targets: S such blocks of
-// each, a second grid dimension over them (the two-row pass of one target, unchanged).
-int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,
-                     int nch, int chunk_frames, cplx *part, int S) {
-    const size_t lds = wcov_lds_layout(D, 2).total;
-    // (the tile pass of the (F, T, D) layout with exactly as many slots as the channel count needs)
-    const wcov_fn_t fn = D <= 4 ? wcov_kernel<2, false, false, false, 1>
-                         : D <= 12 ? wcov_kernel<2, false, false, false, 3>
-                         : D <= 24 ? wcov_kernel<2, false, false, false, 6> : wcov_kernel<2, false, false>;
+// PSD accumulation of the beamformers: same kernel, raw observations, `rows` masks: 2 [target,
+// distortion] or 3 [target, interferer, noise] (the LCMV).  W = (F, rows, T); part = (F, nch,
+// rows, NE).  S targets: S such blocks of each, a second grid dimension over them.
+namespace {
+// (the tile pass of the (F, T, D) layout with exactly as many slots as the channel count needs)
+template <int ROWS>
+wcov_fn_t psd_kernel(int D) {
+    return D <= 4 ? wcov_kernel<ROWS, false, false, false, 1>
+           : D <= 12 ? wcov_kernel<ROWS, false, false, false, 3>
+           : D <= 24 ? wcov_kernel<ROWS, false, false, false, 6> : wcov_kernel<ROWS, false, false>;
+}
+}  // namespace
+int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *Wr,
+                     int rows, int nch, int chunk_frames, cplx *part, int S) {
+    const size_t lds = wcov_lds_layout(D, rows).total;
+    const wcov_fn_t fn = rows == 3 ? psd_kernel<3>(D) : psd_kernel<2>(D);
     GSS_TRY(raise_lds_limit(ctx, fn, lds));
     hipLaunchKernelGGL(fn, dim3(xcd_grid(nch, F), S), dim3(256), lds,
-                       ctx->stream, Y, W2, F, T, D, tri_count(D), nch, chunk_frames, part, 2, 0,
+                       ctx->stream, Y, Wr, F, T, D, tri_count(D), nch, chunk_frames, part, rows, 0,
                        MsegPlan{});
-    GSS_LAUNCH_CHECK(ctx, "wcov_kernel");
-    return GSS_OK;
-}
-
-// Three weight rows [target, interferer, noise] (the LCMV): the three-row instantiations of the
-// same kernel, chosen by the channel count as above.  W = (F, 3, T); part = (F, nch, 3, NE).
-int psd3_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W3,
-                      int nch, int chunk_frames, cplx *part) {
-    const size_t lds = wcov_lds_layout(D, 3).total;
-    const wcov_fn_t fn = D <= 4 ? wcov_kernel<3, false, false, false, 1>
-                         : D <= 12 ? wcov_kernel<3, false, false, false, 3>
-                         : D <= 24 ? wcov_kernel<3, false, false, false, 6> : wcov_kernel<3, false, false>;
-    GSS_TRY(raise_lds_limit(ctx, fn, lds));
-    hipLaunchKernelGGL(fn, dim3(xcd_grid(nch, F)), dim3(256), lds, ctx->stream, Y, W3, F, T, D,
-                       tri_count(D), nch, chunk_frames, part, 3, 0, MsegPlan{});
     GSS_LAUNCH_CHECK(ctx, "wcov_kernel");
     return GSS_OK;
 }

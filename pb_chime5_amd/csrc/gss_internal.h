@@ -137,6 +137,16 @@ __host__ __device__ __forceinline__ int tri_index(int d1, int d2, int D) {
     return d1 * D - (d1 * (d1 - 1)) / 2 + (d2 - d1);
 }
 __host__ __device__ __forceinline__ int tri_count(int D) { return D * (D + 1) / 2; }
+// Its inverse: packed index e -> (d1 <= d2).
+__device__ __forceinline__ void tri_unpack(int e, int D, int &d1, int &d2) {
+    int rem = e;
+    d1 = 0;
+    while (rem >= D - d1) {
+        rem -= D - d1;
+        ++d1;
+    }
+    d2 = d1 + rem;
+}
 
 // ---------------------------------------------------------------- context
 struct ProfEntry {
@@ -324,6 +334,16 @@ struct ProfScope {
                             hipGetErrorString(_e));                               \
     } while (0)
 
+// A kernel that asks for more than 64 KB of dynamic LDS has to be told so before its launch.
+template <typename Kern>
+int raise_lds_limit(gss_ctx *ctx, Kern kern, size_t lds) {
+    if (lds > 64 * 1024)
+        GSS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds));
+    return GSS_OK;
+}
+
 // ---------------------------------------------------------------- stage launchers
 // (device pointers, workspace from the arena, asynchronous on ctx->stream)
 size_t wpe_workspace_bytes(int F, int64_t T, int D, int taps, int delay);
@@ -471,14 +491,11 @@ int cacgmm_link_run(gss_ctx *ctx, const double *prev, int64_t T_prev, int64_t pr
 int cacgmm_link_gather_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
                            const int32_t *mapping, double *out);
 
-// S > 1: S targets' weights (S, F, 2, T) -> partials (S, F, nch, 2, NE), one launch
-int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W2,
-                     int nch, int chunk_frames, cplx *part, int S = 1);
-
-// The same pass with three weight rows (the LCMV's target, interferer and noise masks):
-// W3 (F, 3, T) -> part (F, nch, 3, NE), the three-row instantiation of the kernel
-int psd3_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *W3,
-                      int nch, int chunk_frames, cplx *part);
+// PSD pass of the beamformers: `rows` weight rows per frequency, 2 [target, distortion] or 3
+// [target, interferer, noise] (the LCMV): Wr (F, rows, T) -> part (F, nch, rows, NE).
+// S > 1: S targets' weights (S, F, rows, T) -> partials (S, F, nch, rows, NE), one launch
+int psd_partials_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *Wr,
+                     int rows, int nch, int chunk_frames, cplx *part, int S = 1);
 
 size_t mvdr_workspace_bytes(int F, int64_t T, int D, int S = 1);
 // targets: the multi-target tail of gss_enhance_observation_targets -- masks (S,F,T) in,

@@ -57,40 +57,45 @@ __global__ void masks_targets_kernel(const double *__restrict__ gamma, int F, in
     }
 }
 
-// Pack the two masks into the (F, 2, T) weight layout of the shared covariance
-// kernel (cacgmm.hip: wcov_kernel) and sum them over time.  grid (F, S), block 256: target
-// blockIdx.y packs its own (F,T) masks into its own (F, 2, T) block and (F, 2) sums.
-__global__ __launch_bounds__(256) void mask_pack_kernel(const double *__restrict__ mx,
-                                                        const double *__restrict__ mn, int64_t T,
-                                                        double *__restrict__ W2,
+// Pack ROWS masks into the (F, ROWS, T) weight layout of the shared covariance kernel
+// (cacgmm.hip: wcov_kernel) and sum them over time: two rows [target, distortion] for the MVDR,
+// three [target, interferer, noise] for the LCMV.  grid (F, S), block 256: target blockIdx.y
+// packs its own (F,T) masks into its own (F, ROWS, T) block and (F, ROWS) sums.
+template <int ROWS>
+struct MaskRows {
+    const double *m[ROWS];     // (S,F,T) each
+};
+template <int ROWS>
+__global__ __launch_bounds__(256) void mask_pack_kernel(MaskRows<ROWS> rows, int64_t T,
+                                                        double *__restrict__ Wr,
                                                         double *__restrict__ msum) {
-    __shared__ double red[8];
+    __shared__ double red[4 * ROWS];
     const int f = blockIdx.x, tid = threadIdx.x;
-    {
-        const int64_t F = gridDim.x, s = blockIdx.y;
-        mx += s * F * T;
-        mn += s * F * T;
-        W2 += s * F * 2 * T;
-        msum += s * F * 2;
-    }
-    double sx = 0.0, sn = 0.0;
+    const int64_t F = gridDim.x, s = blockIdx.y;
+    Wr += s * F * ROWS * T;
+    msum += s * F * ROWS;
+    double sum[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) sum[r] = 0.0;
     for (int64_t t = tid; t < T; t += blockDim.x) {
-        const double a = mx[(int64_t)f * T + t], b = mn[(int64_t)f * T + t];
-        W2[((int64_t)f * 2) * T + t] = a;
-        W2[((int64_t)f * 2 + 1) * T + t] = b;
-        sx += a;
-        sn += b;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const double a = rows.m[r][(s * F + f) * T + t];
+            Wr[((int64_t)f * ROWS + r) * T + t] = a;
+            sum[r] += a;
+        }
     }
-    sx = wave_sum(sx);
-    sn = wave_sum(sn);
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) sum[r] = wave_sum(sum[r]);
     if ((tid & 63) == 0) {
-        red[tid >> 6] = sx;
-        red[4 + (tid >> 6)] = sn;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) red[4 * r + (tid >> 6)] = sum[r];
     }
     __syncthreads();
     if (tid == 0) {
-        msum[f * 2] = (red[0] + red[1]) + (red[2] + red[3]);
-        msum[f * 2 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r)
+            msum[f * ROWS + r] = (red[4 * r] + red[4 * r + 1]) + (red[4 * r + 2] + red[4 * r + 3]);
     }
 }
 
@@ -105,19 +110,257 @@ __device__ __forceinline__ cplx c_div(cplx a, cplx b) {
     return c_make((a.x * r + a.y) / den, (a.y * r - a.x) / den);
 }
 
-// Per frequency (one workgroup of MVDR_NT threads): Phi_X, Phi_N from the partial sums;
-// Psi = solve(Phi_N, Phi_X) by LU with partial pivoting, pseudo-inverse (lstsq) fallback on an
-// exactly singular Phi_N; W = Psi / max(Re tr Psi, eps); per-reference-channel SNR terms.
-// Every element of every step is computed by exactly the expressions a single wave used until
-// round 5 (the rank-1 update of an LU step, the products of the SNR terms are element-wise), so
-// the result does not depend on the thread count: four waves take the 23 x 47 element update of
-// the first step in 5 trips instead of 17 -- the kernel was one wave's latency chain per
-// frequency (120 us for ~10 000 instructions), not work.  Pivot search, back substitution (one
-// right-hand side per lane) and the Jacobi fallback stay with wave 0.
+// ------------------------------------------------------------------ the solve of a beamformer
+// The steps mvdr_solve_kernel and lcmv_solve_kernel are made of (gev_solve_kernel takes the first
+// few).  One workgroup of MVDR_NT threads per frequency works on an LDS block `aug` of D rows with
+// leading dimension ld (2 D or 3 D) of which `used` columns are in use: the D x D matrix, then
+// D-wide right-hand blocks.  Every element of every step is computed by exactly the expressions a
+// single wave used until round 5 (the rank-1 update of an LU step, the products of the SNR terms
+// are element-wise), so the result does not depend on the thread count: four waves take the
+// 23 x 47 element update of the first step in 5 trips instead of 17 -- the kernel was one wave's
+// latency chain per frequency (120 us for ~10 000 instructions), not work.  Pivot search, back
+// substitution (one right-hand side per lane) and the Jacobi fallback stay with wave 0.
+// The build contracts within a statement (-ffp-contract=on): an arithmetic statement below is
+// not to be split, merged or reordered, and no sum changes its order.
 #ifndef GSS_MVDR_NT
 #define GSS_MVDR_NT 256        // (tools/build_variant.sh NAME -DGSS_MVDR_NT=64: the same bits from one wave)
 #endif
 constexpr int MVDR_NT = GSS_MVDR_NT;
+
+// Element e of the ROWS packed matrices of frequency f, each summed over the nch chunks in
+// ascending order: part (F, nch, ROWS, NE), the partial sums of the PSD pass.
+template <int ROWS>
+__device__ __forceinline__ void partials_sum(const cplx *__restrict__ part, int f, int nch, int NE,
+                                             int e, cplx (&v)[ROWS]) {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) v[r] = c_make(0.0, 0.0);
+    for (int c = 0; c < nch; ++c) {
+        const cplx *pp = part + ((int64_t)f * nch + c) * ROWS * NE;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) v[r] = c_add(v[r], pp[r * NE + e]);
+    }
+}
+
+// Element e = (d1, d2) of Phi_X and Phi_N from the two-row partial sums: S / max(s, 1e-10) with
+// an exactly real diagonal.
+__device__ __forceinline__ void phi_pair(const cplx *__restrict__ part, int f, int nch, int NE,
+                                         int e, bool diagonal, double dx, double dn, cplx &vx,
+                                         cplx &vn) {
+    cplx v[2];
+    partials_sum<2>(part, f, nch, NE, e, v);
+    vx = c_make(v[0].x / dx, v[0].y / dx);
+    vn = c_make(v[1].x / dn, v[1].y / dn);
+    if (diagonal) {
+        vx.y = 0.0;
+        vn.y = 0.0;
+    }
+}
+
+// v to (d1, d2) and its conjugate to (d2, d1) of a Hermitian matrix (in this order: a diagonal
+// element ends as conj(v))
+__device__ __forceinline__ void herm_store(cplx *M, int ld, int d1, int d2, cplx v) {
+    M[d1 * ld + d2] = v;
+    M[d2 * ld + d1] = c_conj(v);
+}
+
+// Largest `best` of the 64 lanes with its index `bi`, the lowest index among equal values; the
+// result in every lane.
+__device__ __forceinline__ void wave_argmax_first(double &best, int &bi) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) {
+            best = ob;
+            bi = oi;
+        }
+    }
+}
+
+// LU with partial pivoting (pivot by |re| + |im| like LAPACK izamax) of the left D x D block,
+// applied to all `used` columns: [M | R] -> [U | Z], the multipliers below the diagonal.
+// flags[0]: the pivot row of a step; flags[1]: set on a zero or NaN pivot, where the elimination
+// stops -- the caller zeroes it in front of the barrier that ends its fill.  Returns "singular".
+__device__ __forceinline__ bool lu_eliminate(cplx *aug, int ld, int used, int D, int *flags) {
+    constexpr int NT = MVDR_NT;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const bool wave0 = tid < 64;                   // (D <= 32: one wave holds a column)
+    int &s_piv = flags[0];
+    int &s_singular = flags[1];
+    for (int j = 0; j < D; ++j) {
+        if (wave0) {
+            double best = -1.0;
+            int bi = j;
+            if (lane >= j && lane < D) {
+                const cplx v = aug[lane * ld + j];
+                best = fabs(v.x) + fabs(v.y);
+                bi = lane;
+            }
+            wave_argmax_first(best, bi);
+            if (lane == 0) {
+                s_piv = bi;
+                if (!(best > 0.0)) s_singular = 1;   // zero or NaN pivot
+            }
+        }
+        __syncthreads();
+        if (s_singular) break;
+        const int p = s_piv;
+        if (p != j) {
+            for (int col = tid; col < used; col += NT) {
+                const cplx t = aug[j * ld + col];
+                aug[j * ld + col] = aug[p * ld + col];
+                aug[p * ld + col] = t;
+            }
+        }
+        __syncthreads();
+        const cplx piv = aug[j * ld + j];
+        const int rows = D - j - 1, cols = used - j - 1;
+        // multipliers first (column j), then the rank-1 update
+        for (int i = tid; i < rows; i += NT) {
+            const int r = j + 1 + i;
+            aug[r * ld + j] = c_div(aug[r * ld + j], piv);
+        }
+        __syncthreads();
+        for (int it = tid; it < rows * cols; it += NT) {
+            const int i = it / cols, cidx = it - i * cols;
+            const int r = j + 1 + i, col = j + 1 + cidx;
+            const cplx l = aug[r * ld + j], u = aug[j * ld + col];
+            cplx v = aug[r * ld + col];
+            v.x -= l.x * u.x - l.y * u.y;
+            v.y -= l.x * u.y + l.y * u.x;
+            aug[r * ld + col] = v;
+        }
+        __syncthreads();
+    }
+    return s_singular != 0;
+}
+
+// Back substitution U X = Z in place, one right-hand side per lane (nrhs <= 58: wave 0).
+__device__ __forceinline__ void back_substitute(cplx *aug, int ld, int D, int nrhs) {
+    const int tid = threadIdx.x;
+    if (tid < nrhs) {
+        const int col = D + tid;
+        for (int j = D - 1; j >= 0; --j) {
+            cplx v = aug[j * ld + col];
+            for (int k = j + 1; k < D; ++k) {
+                const cplx u = aug[j * ld + k], x = aug[k * ld + col];
+                v.x -= u.x * x.x - u.y * x.y;
+                v.y -= u.x * x.y + u.y * x.x;
+            }
+            aug[j * ld + col] = c_div(v, aug[j * ld + j]);
+        }
+    }
+    __syncthreads();
+}
+
+// np.linalg.lstsq(M, R) for an exactly singular M: the minimum-norm solution via the Hermitian
+// eigendecomposition, singular values below eps * D * max dropped.  The block holds [M | R] as
+// filled (the elimination has overwritten it: the caller fills it again, with a barrier, before
+// this); every right-hand block is replaced by its solution, the left block is used up.
+// JA, JV: m x m each (m = D rounded up to even); *s_cut: a double in LDS.
+__device__ __forceinline__ void min_norm_solve(cplx *aug, int ld, int used, int D, int m, cplx *JA,
+                                               cplx *JV, double *s_cut) {
+    constexpr int NT = MVDR_NT;
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int idx = tid; idx < m * m; idx += NT) {
+        const int i = idx / m, jx = idx - i * m;
+        JA[idx] = (i < D && jx < D) ? aug[i * ld + jx] : c_make(0.0, 0.0);
+    }
+    __syncthreads();
+    if (tid < 64) {
+        jacobi_eigh_wave(JA, JV, m, lane, 20);
+        double lmax = 0.0;
+        for (int i = lane; i < D; i += 64) lmax = fmax(lmax, fabs(JA[i * m + i].x));
+        lmax = wave_max(lmax);
+        if (lane == 0) *s_cut = 2.220446049250313e-16 * (double)D * lmax;
+    }
+    __syncthreads();
+    const double cut = *s_cut;
+    // each right-hand side R in turn: tmp = diag(1/l) V^H R -> the left block, V tmp -> R
+    for (int c0 = D; c0 < used; c0 += D) {
+        for (int it = tid; it < D * D; it += NT) {
+            const int j = it / D, col = it - j * D;
+            cplx v = c_make(0.0, 0.0);
+            for (int i = 0; i < D; ++i) c_cfma(v, JV[i * m + j], aug[i * ld + c0 + col]);
+            const double l = JA[j * m + j].x;
+            const double il = fabs(l) > cut ? 1.0 / l : 0.0;
+            aug[j * ld + col] = c_scale(v, il);
+        }
+        __syncthreads();
+        for (int it = tid; it < D * D; it += NT) {
+            const int i = it / D, col = it - i * D;
+            cplx v = c_make(0.0, 0.0);
+            for (int j = 0; j < D; ++j) c_fma(v, JV[i * m + j], aug[j * ld + col]);
+            aug[i * ld + c0 + col] = v;
+        }
+        __syncthreads();
+    }
+}
+
+// W = Psi / max(Re tr Psi, eps), Psi the D x D block at column c0: to the left block (where the
+// SNR terms read it) and to Wf (D,D) in global memory.  *s_den: a double in LDS.
+// (every thread reads its elements of Psi before anyone overwrites the left block: the two are
+// disjoint)
+__device__ __forceinline__ void trace_normalise(cplx *aug, int ld, int c0, int D, double eps,
+                                                double *s_den, cplx *__restrict__ Wf) {
+    constexpr int NT = MVDR_NT;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < 64) {
+        double tr = 0.0;
+        for (int i = lane; i < D; i += 64) tr += aug[i * ld + c0 + i].x;
+        tr = wave_sum(tr);
+        if (lane == 0) *s_den = fmax(tr, eps);
+    }
+    __syncthreads();
+    const double dentr = *s_den;
+    for (int it = tid; it < D * D; it += NT) {
+        const int i = it / D, col = it - i * D;
+        const cplx v = aug[i * ld + c0 + col];
+        const cplx wv = c_make(v.x / dentr, v.y / dentr);
+        aug[i * ld + col] = wv;
+        Wf[it] = wv;
+    }
+}
+
+// SNR terms per reference channel r: w_r^H Phi_X w_r and w_r^H Phi_D w_r -> snr_f (D,2), W in
+// the left block (behind a barrier of the caller's).  The products T_X = Phi_X W (-> the block
+// at column cx) and T_D = Phi_D W (-> JA) are spread over the whole workgroup; the sums over e
+// and then over d run in the same order as one lane per r would take them.
+// (reads: W in the left block, Phi_X / Phi_D in global memory; writes: the block at cx and JA --
+// disjoint, no barrier inside the first loop)
+__device__ __forceinline__ void snr_terms(cplx *aug, int ld, int cx, int D, int m, cplx *JA,
+                                          const cplx *PhiX, const cplx *PhiD,
+                                          cplx *__restrict__ snr_f) {
+    constexpr int NT = MVDR_NT;
+    const int tid = threadIdx.x;
+    for (int it = tid; it < D * D; it += NT) {
+        const int d = it / D, r = it - d * D;
+        cplx tx = c_make(0.0, 0.0), tn = c_make(0.0, 0.0);
+        for (int e = 0; e < D; ++e) {
+            const cplx we = aug[e * ld + r];
+            c_fma(tx, PhiX[d * D + e], we);
+            c_fma(tn, PhiD[d * D + e], we);
+        }
+        aug[d * ld + cx + r] = tx;
+        JA[d * m + r] = tn;
+    }
+    __syncthreads();
+    if (tid < D) {
+        const int r = tid;
+        cplx num = c_make(0.0, 0.0), den = c_make(0.0, 0.0);
+        for (int d = 0; d < D; ++d) {
+            const cplx wd = aug[d * ld + r];
+            c_cfma(num, wd, aug[d * ld + cx + r]);
+            c_cfma(den, wd, JA[d * m + r]);
+        }
+        snr_f[r * 2] = num;
+        snr_f[r * 2 + 1] = den;
+    }
+}
+
+// Per frequency: Phi_X, Phi_N from the partial sums; Psi = solve(Phi_N, Phi_X) by LU with partial
+// pivoting, pseudo-inverse (lstsq) fallback on an exactly singular Phi_N; W = Psi / max(Re tr Psi,
+// eps); per-reference-channel SNR terms.
 __global__ __launch_bounds__(MVDR_NT) void mvdr_solve_kernel(
     const cplx *__restrict__ part, const double *__restrict__ msum, int nch, int D, double eps,
     cplx *__restrict__ Phi /* (F,2,D,D) */, cplx *__restrict__ W /* (F,D,D) */,
@@ -140,204 +383,41 @@ __global__ __launch_bounds__(MVDR_NT) void mvdr_solve_kernel(
     cplx *JV = JA + m * m;                         // m * m
     // flags live in the dynamic region too: a static __shared__ in front of it
     // would break its 16-byte alignment
-    int *flags = reinterpret_cast<int *>(JV + m * m);
-    int &s_piv = flags[0];
-    int &s_singular = flags[1];
-    double &s_dentr = *reinterpret_cast<double *>(flags + 2);
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const bool wave0 = tid < 64;                   // (D <= 32: one wave holds a column)
+    int *flags = reinterpret_cast<int *>(JV + m * m);        // lu_eliminate's two
+    double *s_val = reinterpret_cast<double *>(flags + 2);   // the cut, then the denominator
+    const int f = blockIdx.x, tid = threadIdx.x;
 
     const double sx = msum[f * 2], sn = msum[f * 2 + 1];
     const double dx = fmax(sx, 1e-10), dn = fmax(sn, 1e-10);
     cplx *PhiX = Phi + (int64_t)f * 2 * D * D;
     cplx *PhiN = PhiX + D * D;
-    for (int e = tid; e < NE; e += NT) {
-        // invert the packed index
-        int d1 = 0, rem = e;
-        while (rem >= D - d1) {
-            rem -= D - d1;
-            ++d1;
+    // (called again on a singular matrix: the elimination has overwritten the block by then)
+    auto fill = [&]() {
+        for (int e = tid; e < NE; e += NT) {
+            int d1, d2;
+            tri_unpack(e, D, d1, d2);
+            cplx vx, vn;
+            phi_pair(part, f, nch, NE, e, d1 == d2, dx, dn, vx, vn);
+            herm_store(PhiX, D, d1, d2, vx);
+            herm_store(PhiN, D, d1, d2, vn);
+            herm_store(aug, W2, d1, d2, vn);
+            herm_store(aug + D, W2, d1, d2, vx);
         }
-        const int d2 = d1 + rem;
-        cplx vx = c_make(0.0, 0.0), vn = c_make(0.0, 0.0);
-        for (int c = 0; c < nch; ++c) {
-            const cplx *pp = part + ((int64_t)f * nch + c) * 2 * NE;
-            vx = c_add(vx, pp[e]);
-            vn = c_add(vn, pp[NE + e]);
-        }
-        vx = c_make(vx.x / dx, vx.y / dx);
-        vn = c_make(vn.x / dn, vn.y / dn);
-        if (d1 == d2) {
-            vx.y = 0.0;
-            vn.y = 0.0;
-        }
-        PhiX[d1 * D + d2] = vx;
-        PhiX[d2 * D + d1] = c_conj(vx);
-        PhiN[d1 * D + d2] = vn;
-        PhiN[d2 * D + d1] = c_conj(vn);
-        aug[d1 * W2 + d2] = vn;
-        aug[d2 * W2 + d1] = c_conj(vn);
-        aug[d1 * W2 + D + d2] = vx;
-        aug[d2 * W2 + D + d1] = c_conj(vx);
-    }
-    if (tid == 0) s_singular = 0;
+    };
+    fill();
+    if (tid == 0) flags[1] = 0;
     __syncthreads();
-
-    // ---- LU with partial pivoting (pivot by |re| + |im| like LAPACK izamax)
-    for (int j = 0; j < D; ++j) {
-        if (wave0) {
-            double best = -1.0;
-            int bi = j;
-            if (lane >= j && lane < D) {
-                const cplx v = aug[lane * W2 + j];
-                best = fabs(v.x) + fabs(v.y);
-                bi = lane;
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(best, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (ob > best || (ob == best && oi < bi)) {
-                    best = ob;
-                    bi = oi;
-                }
-            }
-            if (lane == 0) {
-                s_piv = bi;
-                if (!(best > 0.0)) s_singular = 1;   // zero or NaN pivot
-            }
-        }
-        __syncthreads();
-        if (s_singular) break;
-        const int p = s_piv;
-        if (p != j) {
-            for (int col = tid; col < W2; col += NT) {
-                const cplx t = aug[j * W2 + col];
-                aug[j * W2 + col] = aug[p * W2 + col];
-                aug[p * W2 + col] = t;
-            }
-        }
-        __syncthreads();
-        const cplx piv = aug[j * W2 + j];
-        const int rows = D - j - 1, cols = W2 - j - 1;
-        // multipliers first (column j), then the rank-1 update
-        for (int i = tid; i < rows; i += NT) {
-            const int r = j + 1 + i;
-            aug[r * W2 + j] = c_div(aug[r * W2 + j], piv);
-        }
-        __syncthreads();
-        for (int it = tid; it < rows * cols; it += NT) {
-            const int i = it / cols, cidx = it - i * cols;
-            const int r = j + 1 + i, col = j + 1 + cidx;
-            const cplx l = aug[r * W2 + j], u = aug[j * W2 + col];
-            cplx v = aug[r * W2 + col];
-            v.x -= l.x * u.x - l.y * u.y;
-            v.y -= l.x * u.y + l.y * u.x;
-            aug[r * W2 + col] = v;
-        }
-        __syncthreads();
-    }
-    const bool singular = s_singular != 0;
-    if (!singular) {
-        // back substitution U Psi = Z, one right-hand side per lane
-        if (tid < D) {
-            const int col = D + tid;
-            for (int j = D - 1; j >= 0; --j) {
-                cplx v = aug[j * W2 + col];
-                for (int k = j + 1; k < D; ++k) {
-                    const cplx u = aug[j * W2 + k], x = aug[k * W2 + col];
-                    v.x -= u.x * x.x - u.y * x.y;
-                    v.y -= u.x * x.y + u.y * x.x;
-                }
-                aug[j * W2 + col] = c_div(v, aug[j * W2 + j]);
-            }
-        }
-        __syncthreads();
+    if (!lu_eliminate(aug, W2, W2, D, flags)) {
+        back_substitute(aug, W2, D, D);
     } else {
-        // np.linalg.lstsq(Phi_N, Phi_X): minimum-norm solution via the Hermitian
-        // eigendecomposition; singular values below eps * D * max are dropped.
-        for (int idx = tid; idx < m * m; idx += NT) {
-            const int i = idx / m, jx = idx - i * m;
-            JA[idx] = (i < D && jx < D) ? PhiN[i * D + jx] : c_make(0.0, 0.0);
-        }
+        fill();
         __syncthreads();
-        if (wave0) {
-            jacobi_eigh_wave(JA, JV, m, lane, 20);
-            double lmax = 0.0;
-            for (int i = lane; i < D; i += 64) lmax = fmax(lmax, fabs(JA[i * m + i].x));
-            lmax = wave_max(lmax);
-            if (lane == 0) s_dentr = 2.220446049250313e-16 * (double)D * lmax;
-        }
-        __syncthreads();
-        const double cut = s_dentr;
-        // Psi = V diag(1/l) V^H Phi_X   (two small products through `aug`)
-        // step 1: tmp = V^H Phi_X  -> aug[:, 0:D]
-        for (int it = tid; it < D * D; it += NT) {
-            const int j = it / D, col = it - j * D;
-            cplx v = c_make(0.0, 0.0);
-            for (int i = 0; i < D; ++i) c_cfma(v, JV[i * m + j], PhiX[i * D + col]);
-            const double l = JA[j * m + j].x;
-            const double il = fabs(l) > cut ? 1.0 / l : 0.0;
-            aug[j * W2 + col] = c_scale(v, il);
-        }
-        __syncthreads();
-        for (int it = tid; it < D * D; it += NT) {
-            const int i = it / D, col = it - i * D;
-            cplx v = c_make(0.0, 0.0);
-            for (int j = 0; j < D; ++j) c_fma(v, JV[i * m + j], aug[j * W2 + col]);
-            aug[i * W2 + D + col] = v;
-        }
-        __syncthreads();
+        min_norm_solve(aug, W2, W2, D, m, JA, JV, s_val);
     }
-    // Psi = aug[:, D:2D].  W = Psi / max(Re tr Psi, eps)
-    if (wave0) {
-        double tr = 0.0;
-        for (int i = lane; i < D; i += 64) tr += aug[i * W2 + D + i].x;
-        tr = wave_sum(tr);
-        if (lane == 0) s_dentr = fmax(tr, eps);
-    }
+    // Psi = aug[:, D:2D]
+    trace_normalise(aug, W2, D, D, eps, s_val, W + (int64_t)f * D * D);
     __syncthreads();
-    const double dentr = s_dentr;
-    cplx *Wf = W + (int64_t)f * D * D;
-    // (every thread reads its elements of Psi before anyone overwrites the left half: the two
-    // halves are disjoint, W goes to the left one)
-    for (int it = tid; it < D * D; it += NT) {
-        const int i = it / D, col = it - i * D;
-        const cplx v = aug[i * W2 + D + col];
-        const cplx wv = c_make(v.x / dentr, v.y / dentr);
-        aug[i * W2 + col] = wv;   // keep W in the left half for the SNR terms
-        Wf[it] = wv;
-    }
-    __syncthreads();
-    // SNR terms per reference channel r: w_r^H Phi_X w_r and w_r^H Phi_N w_r.  The products
-    // T_X = Phi_X W (-> right half of aug) and T_N = Phi_N W (-> JA) are spread over the whole
-    // workgroup; the sums over e and then over d run in the same order as one lane per r would
-    // take them.
-    // (reads: W in the left half of aug, Phi_X / Phi_N in global memory; writes: the right half
-    // and JA -- disjoint, no barrier inside)
-    for (int it = tid; it < D * D; it += NT) {
-        const int d = it / D, r = it - d * D;
-        cplx tx = c_make(0.0, 0.0), tn = c_make(0.0, 0.0);
-        for (int e = 0; e < D; ++e) {
-            const cplx we = aug[e * W2 + r];
-            c_fma(tx, PhiX[d * D + e], we);
-            c_fma(tn, PhiN[d * D + e], we);
-        }
-        aug[d * W2 + D + r] = tx;
-        JA[d * m + r] = tn;
-    }
-    __syncthreads();
-    if (tid < D) {
-        const int r = tid;
-        cplx num = c_make(0.0, 0.0), den = c_make(0.0, 0.0);
-        for (int d = 0; d < D; ++d) {
-            const cplx wd = aug[d * W2 + r];
-            c_cfma(num, wd, aug[d * W2 + D + r]);
-            c_cfma(den, wd, JA[d * m + r]);
-        }
-        snr[((int64_t)f * D + r) * 2] = num;
-        snr[((int64_t)f * D + r) * 2 + 1] = den;
-    }
+    snr_terms(aug, W2, D, D, m, JA, PhiX, PhiN, snr + (int64_t)f * D * 2);
 }
 
 // GEV beamformer (beamforming_wrapper.py:77-89 -> pb_bss get_gev_vector): principal
@@ -380,28 +460,12 @@ __global__ __launch_bounds__(64) void gev_solve_kernel(const cplx *__restrict__ 
     }
     __syncthreads();
     for (int e = lane; e < NE; e += 64) {
-        int d1 = 0, rem = e;
-        while (rem >= D - d1) {
-            rem -= D - d1;
-            ++d1;
-        }
-        const int d2 = d1 + rem;
-        cplx vx = c_make(0.0, 0.0), vn = c_make(0.0, 0.0);
-        for (int c = 0; c < nch; ++c) {
-            const cplx *pp = part + ((int64_t)f * nch + c) * 2 * NE;
-            vx = c_add(vx, pp[e]);
-            vn = c_add(vn, pp[NE + e]);
-        }
-        vx = c_make(vx.x / dx, vx.y / dx);
-        vn = c_make(vn.x / dn, vn.y / dn);
-        if (d1 == d2) {
-            vx.y = 0.0;
-            vn.y = 0.0;
-        }
-        PhiX[d1 * D + d2] = vx;
-        PhiX[d2 * D + d1] = c_conj(vx);
-        PhiN[d1 * D + d2] = vn;
-        PhiN[d2 * D + d1] = c_conj(vn);
+        int d1, d2;
+        tri_unpack(e, D, d1, d2);
+        cplx vx, vn;
+        phi_pair(part, f, nch, NE, e, d1 == d2, dx, dn, vx, vn);
+        herm_store(PhiX, D, d1, d2, vx);
+        herm_store(PhiN, D, d1, d2, vn);
         Ln[d2 * m + d1] = c_conj(vn);          // lower triangle
         if (d1 == d2) Ln[d1 * m + d1] = vn;
     }
@@ -454,15 +518,7 @@ __global__ __launch_bounds__(64) void gev_solve_kernel(const cplx *__restrict__ 
     // largest eigenvalue (first index on ties)
     double best = lane < D ? JA[lane * m + lane].x : -INFINITY;
     int bi = lane < D ? lane : 1 << 30;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) {
-            best = ob;
-            bi = oi;
-        }
-    }
+    wave_argmax_first(best, bi);
     // w = Linv^H u :  w[d] = sum_{i >= d} conj(Linv[i][d]) u[i]
     for (int idx = lane; idx < D * D; idx += 64) {
         const int d = idx / D, col = idx - d * D;
@@ -861,15 +917,7 @@ __global__ __launch_bounds__(64) void lcmv_pick_kernel(const double *__restrict_
             bi = lane;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) {
-            best = ob;
-            bi = oi;
-        }
-    }
+    wave_argmax_first(best, bi);
     if (lane == 0) pick[0] = best > 0.0 ? bi : -1;
 }
 
@@ -904,55 +952,18 @@ __global__ void masks3_kernel(const double *__restrict__ gamma, int F, int K, in
     mn[idx] = n;
 }
 
-// mask_pack_kernel for three masks: (F, 3, T) weights [target, interferer, noise] and (F, 3)
-// sums, in its summation order.  grid (F), block 256.
-__global__ __launch_bounds__(256) void mask_pack3_kernel(const double *__restrict__ mx,
-                                                         const double *__restrict__ mi,
-                                                         const double *__restrict__ mn, int64_t T,
-                                                         double *__restrict__ W3,
-                                                         double *__restrict__ msum) {
-    __shared__ double red[12];
-    const int f = blockIdx.x, tid = threadIdx.x;
-    double sx = 0.0, si = 0.0, sn = 0.0;
-    for (int64_t t = tid; t < T; t += blockDim.x) {
-        const double a = mx[(int64_t)f * T + t], b = mi[(int64_t)f * T + t],
-                     c = mn[(int64_t)f * T + t];
-        W3[((int64_t)f * 3) * T + t] = a;
-        W3[((int64_t)f * 3 + 1) * T + t] = b;
-        W3[((int64_t)f * 3 + 2) * T + t] = c;
-        sx += a;
-        si += b;
-        sn += c;
-    }
-    sx = wave_sum(sx);
-    si = wave_sum(si);
-    sn = wave_sum(sn);
-    if ((tid & 63) == 0) {
-        red[tid >> 6] = sx;
-        red[4 + (tid >> 6)] = si;
-        red[8 + (tid >> 6)] = sn;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        msum[f * 3] = (red[0] + red[1]) + (red[2] + red[3]);
-        msum[f * 3 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
-        msum[f * 3 + 2] = (red[8] + red[9]) + (red[10] + red[11]);
-    }
-}
-
 // Souden's LCMV with one null (Souden, Benesty, Affes 2010, eq. 51), per frequency (one
-// workgroup of MVDR_NT threads, shaped like mvdr_solve_kernel):
+// workgroup of MVDR_NT threads, made of the steps mvdr_solve_kernel is made of):
 //   Phi_m = S_m / max(s_m, 1e-10) for m in {X, I, N};  A = solve(Phi_N, Phi_I),
 //   B = solve(Phi_N, Phi_X) from ONE factorisation of the D x 3D block [Phi_N | Phi_I | Phi_X];
 //   g_in = tr A,  g = g_in tr B - tr(A B),  W = (g_in B - A B) / max(Re g, eps);
 //   distortion matrix Phi_D = Phi_I + Phi_N.
 // A frequency whose interferer mask sums to less than min_mass takes the MVDR of the merged
 // mask instead: Phi_D = (S_I + S_N) / max(s_I + s_N, 1e-10), the D x 2D block [Phi_D | Phi_X],
-// W = Psi / max(Re tr Psi, eps) -- every element by mvdr_solve_kernel's expressions -- and is
-// counted in *fallbacks.  s_I is known before the factorisation: a frequency factors one matrix.
-// LU with partial pivoting, the minimum-norm (lstsq) answer on an exactly singular matrix and the
-// SNR terms are mvdr_solve_kernel's.  Out: Phi (F,2,D,D) = [Phi_X, Phi_D], W (F,D,D), snr
-// (F,D,2): what mvdr_ref_kernel and mvdr_apply_kernel read.
+// W = Psi / max(Re tr Psi, eps) -- the functions mvdr_solve_kernel calls, on the same block --
+// and is counted in *fallbacks.  s_I is known before the factorisation: a frequency factors one
+// matrix.  Out: Phi (F,2,D,D) = [Phi_X, Phi_D], W (F,D,D), snr (F,D,2): what mvdr_ref_kernel and
+// mvdr_apply_kernel read.
 __global__ __launch_bounds__(MVDR_NT) void lcmv_solve_kernel(
     const cplx *__restrict__ part /* (F,nch,3,NE) */, const double *__restrict__ msum /* (F,3) */,
     int nch, int D, double eps, double min_mass, cplx *__restrict__ Phi, cplx *__restrict__ W,
@@ -966,11 +977,8 @@ __global__ __launch_bounds__(MVDR_NT) void lcmv_solve_kernel(
     cplx *JA = aug + D * W3;                       // m * m
     cplx *JV = JA + m * m;                         // m * m
     int *flags = reinterpret_cast<int *>(JV + m * m);   // (in the dynamic region: its alignment)
-    int &s_piv = flags[0];
-    int &s_singular = flags[1];
     double *s_val = reinterpret_cast<double *>(flags + 2);   // 3 doubles
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const bool wave0 = tid < 64;                   // (D <= 32: one wave holds a column)
 
     const double sx = msum[f * 3], si = msum[f * 3 + 1], sn = msum[f * 3 + 2];
     const bool fall = si < min_mass;
@@ -985,19 +993,11 @@ __global__ __launch_bounds__(MVDR_NT) void lcmv_solve_kernel(
     // (called again on a singular matrix: the elimination has overwritten the block by then)
     auto fill = [&]() {
         for (int e = tid; e < NE; e += NT) {
-            int d1 = 0, rem = e;
-            while (rem >= D - d1) {
-                rem -= D - d1;
-                ++d1;
-            }
-            const int d2 = d1 + rem;
-            cplx vx = c_make(0.0, 0.0), vi = c_make(0.0, 0.0), vn = c_make(0.0, 0.0);
-            for (int c = 0; c < nch; ++c) {
-                const cplx *pp = part + ((int64_t)f * nch + c) * 3 * NE;
-                vx = c_add(vx, pp[e]);
-                vi = c_add(vi, pp[NE + e]);
-                vn = c_add(vn, pp[2 * NE + e]);
-            }
+            int d1, d2;
+            tri_unpack(e, D, d1, d2);
+            cplx v[3];
+            partials_sum<3>(part, f, nch, NE, e, v);
+            cplx vx = v[0], vi = v[1], vn = v[2];
             vx = c_make(vx.x / dx, vx.y / dx);
             cplx vd;
             if (fall) {
@@ -1015,150 +1015,27 @@ __global__ __launch_bounds__(MVDR_NT) void lcmv_solve_kernel(
                 vn.y = 0.0;
                 vd.y = 0.0;
             }
-            PhiX[d1 * D + d2] = vx;
-            PhiX[d2 * D + d1] = c_conj(vx);
-            PhiD[d1 * D + d2] = vd;
-            PhiD[d2 * D + d1] = c_conj(vd);
-            aug[d1 * W3 + d2] = vn;
-            aug[d2 * W3 + d1] = c_conj(vn);
-            if (!fall) {
-                aug[d1 * W3 + D + d2] = vi;
-                aug[d2 * W3 + D + d1] = c_conj(vi);
-            }
-            aug[d1 * W3 + cx + d2] = vx;
-            aug[d2 * W3 + cx + d1] = c_conj(vx);
+            herm_store(PhiX, D, d1, d2, vx);
+            herm_store(PhiD, D, d1, d2, vd);
+            herm_store(aug, W3, d1, d2, vn);
+            if (!fall) herm_store(aug + D, W3, d1, d2, vi);
+            herm_store(aug + cx, W3, d1, d2, vx);
         }
     };
     fill();
-    if (tid == 0) s_singular = 0;
+    if (tid == 0) flags[1] = 0;
     __syncthreads();
-
-    // ---- LU with partial pivoting (pivot by |re| + |im| like LAPACK izamax)
-    for (int j = 0; j < D; ++j) {
-        if (wave0) {
-            double best = -1.0;
-            int bi = j;
-            if (lane >= j && lane < D) {
-                const cplx v = aug[lane * W3 + j];
-                best = fabs(v.x) + fabs(v.y);
-                bi = lane;
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(best, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (ob > best || (ob == best && oi < bi)) {
-                    best = ob;
-                    bi = oi;
-                }
-            }
-            if (lane == 0) {
-                s_piv = bi;
-                if (!(best > 0.0)) s_singular = 1;   // zero or NaN pivot
-            }
-        }
-        __syncthreads();
-        if (s_singular) break;
-        const int p = s_piv;
-        if (p != j) {
-            for (int col = tid; col < used; col += NT) {
-                const cplx t = aug[j * W3 + col];
-                aug[j * W3 + col] = aug[p * W3 + col];
-                aug[p * W3 + col] = t;
-            }
-        }
-        __syncthreads();
-        const cplx piv = aug[j * W3 + j];
-        const int rows = D - j - 1, cols = used - j - 1;
-        for (int i = tid; i < rows; i += NT) {
-            const int r = j + 1 + i;
-            aug[r * W3 + j] = c_div(aug[r * W3 + j], piv);
-        }
-        __syncthreads();
-        for (int it = tid; it < rows * cols; it += NT) {
-            const int i = it / cols, cidx = it - i * cols;
-            const int r = j + 1 + i, col = j + 1 + cidx;
-            const cplx l = aug[r * W3 + j], u = aug[j * W3 + col];
-            cplx v = aug[r * W3 + col];
-            v.x -= l.x * u.x - l.y * u.y;
-            v.y -= l.x * u.y + l.y * u.x;
-            aug[r * W3 + col] = v;
-        }
-        __syncthreads();
-    }
-    const bool singular = s_singular != 0;
-    if (!singular) {
-        // back substitution, one right-hand side per lane (nrhs <= 58: wave 0)
-        if (tid < nrhs) {
-            const int col = D + tid;
-            for (int j = D - 1; j >= 0; --j) {
-                cplx v = aug[j * W3 + col];
-                for (int k = j + 1; k < D; ++k) {
-                    const cplx u = aug[j * W3 + k], x = aug[k * W3 + col];
-                    v.x -= u.x * x.x - u.y * x.y;
-                    v.y -= u.x * x.y + u.y * x.x;
-                }
-                aug[j * W3 + col] = c_div(v, aug[j * W3 + j]);
-            }
-        }
-        __syncthreads();
+    if (!lu_eliminate(aug, W3, used, D, flags)) {
+        back_substitute(aug, W3, D, nrhs);
     } else {
-        // np.linalg.lstsq(M, R): minimum-norm solution via the Hermitian eigendecomposition;
-        // singular values below eps * D * max are dropped (mvdr_solve_kernel's branch)
         fill();
         __syncthreads();
-        for (int idx = tid; idx < m * m; idx += NT) {
-            const int i = idx / m, jx = idx - i * m;
-            JA[idx] = (i < D && jx < D) ? aug[i * W3 + jx] : c_make(0.0, 0.0);
-        }
-        __syncthreads();
-        if (wave0) {
-            jacobi_eigh_wave(JA, JV, m, lane, 20);
-            double lmax = 0.0;
-            for (int i = lane; i < D; i += 64) lmax = fmax(lmax, fabs(JA[i * m + i].x));
-            lmax = wave_max(lmax);
-            if (lane == 0) s_val[0] = 2.220446049250313e-16 * (double)D * lmax;
-        }
-        __syncthreads();
-        const double cut = s_val[0];
-        // each right-hand side R in turn: tmp = diag(1/l) V^H R -> the left block, V tmp -> R
-        for (int c0 = D; c0 < used; c0 += D) {
-            for (int it = tid; it < D * D; it += NT) {
-                const int j = it / D, col = it - j * D;
-                cplx v = c_make(0.0, 0.0);
-                for (int i = 0; i < D; ++i) c_cfma(v, JV[i * m + j], aug[i * W3 + c0 + col]);
-                const double l = JA[j * m + j].x;
-                const double il = fabs(l) > cut ? 1.0 / l : 0.0;
-                aug[j * W3 + col] = c_scale(v, il);
-            }
-            __syncthreads();
-            for (int it = tid; it < D * D; it += NT) {
-                const int i = it / D, col = it - i * D;
-                cplx v = c_make(0.0, 0.0);
-                for (int j = 0; j < D; ++j) c_fma(v, JV[i * m + j], aug[j * W3 + col]);
-                aug[i * W3 + c0 + col] = v;
-            }
-            __syncthreads();
-        }
+        min_norm_solve(aug, W3, used, D, m, JA, JV, s_val);
     }
     cplx *Wf = W + (int64_t)f * D * D;
     if (fall) {
-        // Psi = aug[:, D:2D].  W = Psi / max(Re tr Psi, eps)
-        if (wave0) {
-            double tr = 0.0;
-            for (int i = lane; i < D; i += 64) tr += aug[i * W3 + D + i].x;
-            tr = wave_sum(tr);
-            if (lane == 0) s_val[0] = fmax(tr, eps);
-        }
-        __syncthreads();
-        const double dentr = s_val[0];
-        for (int it = tid; it < D * D; it += NT) {
-            const int i = it / D, col = it - i * D;
-            const cplx v = aug[i * W3 + D + col];
-            const cplx wv = c_make(v.x / dentr, v.y / dentr);
-            aug[i * W3 + col] = wv;   // W stays in the left block for the SNR terms
-            Wf[it] = wv;
-        }
+        // Psi = aug[:, D:2D]
+        trace_normalise(aug, W3, D, D, eps, s_val, Wf);
     } else {
         // A = aug[:, D:2D], B = aug[:, 2D:3D]; A B -> JA, spread over the workgroup
         for (int it = tid; it < D * D; it += NT) {
@@ -1170,7 +1047,7 @@ __global__ __launch_bounds__(MVDR_NT) void lcmv_solve_kernel(
         __syncthreads();
         // the traces: lane i holds the i-th diagonal entries, summed over the wave in wave_sum's
         // fixed order
-        if (wave0) {
+        if (tid < 64) {
             cplx a = c_make(0.0, 0.0), b = c_make(0.0, 0.0), ab = c_make(0.0, 0.0);
             if (lane < D) {
                 a = aug[lane * W3 + D + lane];
@@ -1199,31 +1076,7 @@ __global__ __launch_bounds__(MVDR_NT) void lcmv_solve_kernel(
         }
     }
     __syncthreads();
-    // SNR terms per reference channel r: w_r^H Phi_X w_r and w_r^H Phi_D w_r, as in
-    // mvdr_solve_kernel (T_X -> the block at cx, T_D -> JA)
-    for (int it = tid; it < D * D; it += NT) {
-        const int d = it / D, r = it - d * D;
-        cplx tx = c_make(0.0, 0.0), tn = c_make(0.0, 0.0);
-        for (int e = 0; e < D; ++e) {
-            const cplx we = aug[e * W3 + r];
-            c_fma(tx, PhiX[d * D + e], we);
-            c_fma(tn, PhiD[d * D + e], we);
-        }
-        aug[d * W3 + cx + r] = tx;
-        JA[d * m + r] = tn;
-    }
-    __syncthreads();
-    if (tid < D) {
-        const int r = tid;
-        cplx num = c_make(0.0, 0.0), den = c_make(0.0, 0.0);
-        for (int d = 0; d < D; ++d) {
-            const cplx wd = aug[d * W3 + r];
-            c_cfma(num, wd, aug[d * W3 + cx + r]);
-            c_cfma(den, wd, JA[d * m + r]);
-        }
-        snr[((int64_t)f * D + r) * 2] = num;
-        snr[((int64_t)f * D + r) * 2 + 1] = den;
-    }
+    snr_terms(aug, W3, cx, D, m, JA, PhiX, PhiD, snr + (int64_t)f * D * 2);
 }
 
 int psd_chunks(int F, int64_t T, int *chunk_frames) {
@@ -1235,16 +1088,32 @@ int psd_chunks(int F, int64_t T, int *chunk_frames) {
     return (int)((tiles + tpc - 1) / tpc);
 }
 
+// The frames [lo_end, hi_begin) the context zeroing keeps, by the Python slice semantics of
+// masks[:, :sf] = 0; if ef > 0: masks[:, -ef:] = 0 (drop == 0: all of them).
+void context_range(int64_t T, int drop, int64_t sf, int64_t ef, int64_t *lo_end,
+                   int64_t *hi_begin) {
+    *lo_end = 0;
+    *hi_begin = T;
+    if (drop) {
+        *lo_end = sf >= 0 ? (sf < T ? sf : T) : (T + sf > 0 ? T + sf : 0);
+        if (ef > 0) *hi_begin = T - ef > 0 ? T - ef : 0;
+    }
+}
+
+// Dynamic LDS of mvdr_solve_kernel (blocks = 2) and lcmv_solve_kernel (3): the D x blocks D
+// block, JA and JV (m x m each), the two flags and three doubles.
+size_t solve_lds_bytes(int D, int blocks) {
+    const int m = D + (D & 1);
+    return (sizeof(cplx) * ((size_t)D * blocks * D + 2 * (size_t)m * m) + 32 + 15) / 16 * 16;
+}
+
 }  // namespace
 
 int masks_from_posteriors_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T,
                               int target, int drop, int64_t sf, int64_t ef, double *mx,
                               double *mn) {
-    int64_t lo_end = 0, hi_begin = T;
-    if (drop) {
-        lo_end = sf >= 0 ? (sf < T ? sf : T) : (T + sf > 0 ? T + sf : 0);
-        if (ef > 0) hi_begin = T - ef > 0 ? T - ef : 0;
-    }
+    int64_t lo_end, hi_begin;
+    context_range(T, drop, sf, ef, &lo_end, &hi_begin);
     GSS_PROF(ctx, "masks");
     const int64_t total = (int64_t)F * T;
     hipLaunchKernelGGL(masks_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
@@ -1259,15 +1128,8 @@ int masks_targets_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T
     TargetMaskArgs a{};
     a.S = S;
     for (int s = 0; s < S; ++s) {
-        // (masks_from_posteriors_run's range for each target)
-        int64_t lo_end = 0, hi_begin = T;
-        if (drop) {
-            lo_end = sf[s] >= 0 ? (sf[s] < T ? sf[s] : T) : (T + sf[s] > 0 ? T + sf[s] : 0);
-            if (ef[s] > 0) hi_begin = T - ef[s] > 0 ? T - ef[s] : 0;
-        }
         a.target[s] = targets[s];
-        a.zero_lo_end[s] = lo_end;
-        a.zero_hi_begin[s] = hi_begin;
+        context_range(T, drop, sf[s], ef[s], &a.zero_lo_end[s], &a.zero_hi_begin[s]);
     }
     GSS_PROF(ctx, "masks_targets");
     const int64_t total = (int64_t)F * T;
@@ -1306,6 +1168,27 @@ size_t mvdr_workspace_bytes(int F, int64_t T, int D, int S) {
     return ws.bytes + 4096;
 }
 
+// The tail of a one-target call (mvdr_run, lcmv_run): the reference channel from the SNR terms
+// (pick_ref; the GEV's solve has named column 0 already), then BAN and the filtering.
+static int ref_apply_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const BfWork &k,
+                         bool pick_ref, int forced_ref, int ban, cplx *Xhat,
+                         int32_t *ref_channel) {
+    if (pick_ref) {
+        GSS_PROF(ctx, "mvdr_ref");
+        hipLaunchKernelGGL(mvdr_ref_kernel, dim3(1), dim3(MVDR_REF_NT),
+                           sizeof(cplx) * MVDR_REF_CHUNK * (size_t)D * 2, ctx->stream, k.snr, F, D,
+                           1e-10, forced_ref, k.ref);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_ref_kernel");
+    }
+    GSS_PROF(ctx, "mvdr_apply");
+    const int chunk = 256;
+    hipLaunchKernelGGL(mvdr_apply_kernel<false>, dim3((unsigned)((T + chunk - 1) / chunk), F),
+                       dim3(256), 0, ctx->stream, Y, k.W, k.Phi, k.ref, F, T, D, ban, chunk, Xhat,
+                       ref_channel, ctx->status_dev, (int64_t)0, (const int32_t *)nullptr);
+    GSS_LAUNCH_CHECK(ctx, "mvdr_apply_kernel");
+    return GSS_OK;
+}
+
 int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
              const double *mn, int ban, cplx *Xhat, int32_t *ref_channel, int gev,
              int forced_ref, int S, bool targets) {
@@ -1321,19 +1204,16 @@ int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double 
     ctx->last_targets = targets ? S : 0;
     {
         GSS_PROF(ctx, targets ? "psd_targets" : "psd");
-        hipLaunchKernelGGL(mask_pack_kernel, dim3(F, S), dim3(256), 0, ctx->stream, mx, mn, T, W2,
-                           msum);
+        hipLaunchKernelGGL(mask_pack_kernel<2>, dim3(F, S), dim3(256), 0, ctx->stream,
+                           MaskRows<2>{{mx, mn}}, T, W2, msum);
         GSS_LAUNCH_CHECK(ctx, "mask_pack_kernel");
-        GSS_TRY(psd_partials_run(ctx, Y, F, T, D, W2, nch, cf, part, S));
+        GSS_TRY(psd_partials_run(ctx, Y, F, T, D, W2, 2, nch, cf, part, S));
     }
     if (gev) {
         GSS_PROF(ctx, targets ? "gev_solve_targets" : "gev_solve");
         const int m = D + (D & 1);
         const size_t lds = (sizeof(cplx) * 4 * (size_t)m * m + 15) / 16 * 16;
-        if (lds > 64 * 1024)
-            GSS_HIP_CHECK(ctx, hipFuncSetAttribute(
-                                   reinterpret_cast<const void *>(gev_solve_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        GSS_TRY(raise_lds_limit(ctx, gev_solve_kernel, lds));
         if (S == 1) {
             GSS_HIP_CHECK(ctx, hipMemsetAsync(ref, 0, sizeof(int32_t), ctx->stream));
             GSS_HIP_CHECK(ctx, hipMemsetAsync(ref + 1, 0x7f, sizeof(int32_t), ctx->stream));
@@ -1347,37 +1227,23 @@ int mvdr_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double 
                            nch, D, Phi, W, ref);
         GSS_LAUNCH_CHECK(ctx, "gev_solve_kernel");
     } else {
-        {
-            GSS_PROF(ctx, targets ? "mvdr_solve_targets" : "mvdr_solve");
-            const int m = D + (D & 1);
-            const size_t lds = (sizeof(cplx) * ((size_t)D * 2 * D + 2 * (size_t)m * m) +
-                                32 + 15) / 16 * 16;
-            if (lds > 64 * 1024)
-                GSS_HIP_CHECK(ctx, hipFuncSetAttribute(
-                                       reinterpret_cast<const void *>(mvdr_solve_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(mvdr_solve_kernel, dim3(F, S), dim3(MVDR_NT), lds, ctx->stream, part,
-                               msum, nch, D, 1e-10, Phi, W, snr);
-            GSS_LAUNCH_CHECK(ctx, "mvdr_solve_kernel");
-        }
-        {
-            GSS_PROF(ctx, targets ? "mvdr_ref_targets" : "mvdr_ref");
-            hipLaunchKernelGGL(mvdr_ref_kernel, dim3(S), dim3(MVDR_REF_NT),
-                               sizeof(cplx) * MVDR_REF_CHUNK * (size_t)D * 2, ctx->stream, snr, F, D, 1e-10,
-                               forced_ref, ref);
-            GSS_LAUNCH_CHECK(ctx, "mvdr_ref_kernel");
-        }
+        GSS_PROF(ctx, targets ? "mvdr_solve_targets" : "mvdr_solve");
+        const size_t lds = solve_lds_bytes(D, 2);
+        GSS_TRY(raise_lds_limit(ctx, mvdr_solve_kernel, lds));
+        hipLaunchKernelGGL(mvdr_solve_kernel, dim3(F, S), dim3(MVDR_NT), lds, ctx->stream, part,
+                           msum, nch, D, 1e-10, Phi, W, snr);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_solve_kernel");
+    }
+    if (!targets) return ref_apply_run(ctx, Y, F, T, D, k, !gev, forced_ref, ban, Xhat, ref_channel);
+    if (!gev) {
+        GSS_PROF(ctx, "mvdr_ref_targets");
+        hipLaunchKernelGGL(mvdr_ref_kernel, dim3(S), dim3(MVDR_REF_NT),
+                           sizeof(cplx) * MVDR_REF_CHUNK * (size_t)D * 2, ctx->stream, snr, F, D, 1e-10,
+                           forced_ref, ref);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_ref_kernel");
     }
     const int chunk = 256;
     const dim3 grid((unsigned)((T + chunk - 1) / chunk), F);
-    if (!targets) {
-        GSS_PROF(ctx, "mvdr_apply");
-        hipLaunchKernelGGL(mvdr_apply_kernel<false>, grid, dim3(256), 0, ctx->stream, Y, W, Phi, ref, F, T,
-                           D, ban, chunk, Xhat, ref_channel, ctx->status_dev, (int64_t)0,
-                           (const int32_t *)nullptr);
-        GSS_LAUNCH_CHECK(ctx, "mvdr_apply_kernel");
-        return GSS_OK;
-    }
     GSS_PROF(ctx, "mvdr_apply_targets");
     int32_t *const status = ctx->status_dev + GSS_STATUS_TARGETS;
 #define GSS_APPLY_TARGETS(SB)                                                                    \
@@ -1472,7 +1338,7 @@ int mvdr_segments_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, cons
         hipLaunchKernelGGL(mask_pack_segments_kernel, dim3(g.B, F), dim3(256), 0, ctx->stream, mx,
                            mn, T, g.L, W2, msum);
         GSS_LAUNCH_CHECK(ctx, "mask_pack_segments_kernel");
-        GSS_TRY(psd_partials_run(ctx, Y, F, T, D, W2, g.nch, g.cf, part));
+        GSS_TRY(psd_partials_run(ctx, Y, F, T, D, W2, 2, g.nch, g.cf, part));
     }
     {
         GSS_PROF(ctx, "mvdr_window_segments");
@@ -1491,12 +1357,8 @@ int mvdr_segments_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, cons
     {
         // mvdr_solve_kernel's (F, S) grid with the B segments as its "targets", one chunk each
         GSS_PROF(ctx, "mvdr_solve_segments");
-        const int m = D + (D & 1);
-        const size_t lds = (sizeof(cplx) * ((size_t)D * 2 * D + 2 * (size_t)m * m) + 32 + 15) / 16 * 16;
-        if (lds > 64 * 1024)
-            GSS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(mvdr_solve_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)lds));
+        const size_t lds = solve_lds_bytes(D, 2);
+        GSS_TRY(raise_lds_limit(ctx, mvdr_solve_kernel, lds));
         hipLaunchKernelGGL(mvdr_solve_kernel, dim3(F, g.B), dim3(MVDR_NT), lds, ctx->stream, wpart,
                            wmsum, 1, D, 1e-10, Phi, W, snr);
         GSS_LAUNCH_CHECK(ctx, "mvdr_solve_kernel");
@@ -1543,12 +1405,8 @@ size_t lcmv_masks_workspace_bytes(int F, int K) {
 int lcmv_masks_run(gss_ctx *ctx, const double *gamma, int F, int K, int64_t T, int target,
                    const gss_bf_lcmv &bf, int drop, int64_t sf, int64_t ef, double *mx, double *mi,
                    double *mn, int32_t *interferer) {
-    // (masks_from_posteriors_run's range)
-    int64_t lo_end = 0, hi_begin = T;
-    if (drop) {
-        lo_end = sf >= 0 ? (sf < T ? sf : T) : (T + sf > 0 ? T + sf : 0);
-        if (ef > 0) hi_begin = T - ef > 0 ? T - ef : 0;
-    }
+    int64_t lo_end, hi_begin;
+    context_range(T, drop, sf, ef, &lo_end, &hi_begin);
     Workspace ws(ctx);
     const LcmvMaskWork k = lcmv_masks_blocks(ws, F, K);
     GSS_TRY(ws.status("lcmv masks"));
@@ -1584,46 +1442,26 @@ int lcmv_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double 
     Workspace ws(ctx);
     const BfWork k = bf_blocks(ws, F, T, D, 1, 3);
     GSS_TRY(ws.status("lcmv"));
-    const int nch = k.nch, cf = k.cf;
-    cplx *part = k.part, *Phi = k.Phi, *W = k.W, *snr = k.snr;
-    double *msum = k.msum, *W3 = k.Wr;
-    int32_t *ref = k.ref, *const fallbacks = ref + 2;
+    int32_t *const fallbacks = k.ref + 2;
     ctx->last_targets = 0;
     GSS_HIP_CHECK(ctx, hipMemsetAsync(fallbacks, 0, sizeof(int32_t), ctx->stream));
     {
         GSS_PROF(ctx, "psd3");
-        hipLaunchKernelGGL(mask_pack3_kernel, dim3(F), dim3(256), 0, ctx->stream, mx, mi, mn, T, W3,
-                           msum);
-        GSS_LAUNCH_CHECK(ctx, "mask_pack3_kernel");
-        GSS_TRY(psd3_partials_run(ctx, Y, F, T, D, W3, nch, cf, part));
+        hipLaunchKernelGGL(mask_pack_kernel<3>, dim3(F), dim3(256), 0, ctx->stream,
+                           MaskRows<3>{{mx, mi, mn}}, T, k.Wr, k.msum);
+        GSS_LAUNCH_CHECK(ctx, "mask_pack_kernel");
+        GSS_TRY(psd_partials_run(ctx, Y, F, T, D, k.Wr, 3, k.nch, k.cf, k.part));
     }
     {
         GSS_PROF(ctx, "lcmv_solve");
-        const int m = D + (D & 1);
-        const size_t lds = (sizeof(cplx) * ((size_t)D * 3 * D + 2 * (size_t)m * m) + 32 + 15) / 16 * 16;
-        if (lds > 64 * 1024)
-            GSS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(lcmv_solve_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)lds));
-        hipLaunchKernelGGL(lcmv_solve_kernel, dim3(F), dim3(MVDR_NT), lds, ctx->stream, part, msum,
-                           nch, D, 1e-10, min_mass, Phi, W, snr, fallbacks);
+        const size_t lds = solve_lds_bytes(D, 3);
+        GSS_TRY(raise_lds_limit(ctx, lcmv_solve_kernel, lds));
+        hipLaunchKernelGGL(lcmv_solve_kernel, dim3(F), dim3(MVDR_NT), lds, ctx->stream, k.part,
+                           k.msum, k.nch, D, 1e-10, min_mass, k.Phi, k.W, k.snr, fallbacks);
         GSS_LAUNCH_CHECK(ctx, "lcmv_solve_kernel");
         // the count of this call -> the context's status word
         GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_LCMV_FALLBACKS, fallbacks,
                                           sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    {
-        GSS_PROF(ctx, "mvdr_ref");
-        hipLaunchKernelGGL(mvdr_ref_kernel, dim3(1), dim3(MVDR_REF_NT),
-                           sizeof(cplx) * MVDR_REF_CHUNK * (size_t)D * 2, ctx->stream, snr, F, D, 1e-10,
-                           forced_ref, ref);
-        GSS_LAUNCH_CHECK(ctx, "mvdr_ref_kernel");
-    }
-    GSS_PROF(ctx, "mvdr_apply");
-    const int chunk = 256;
-    hipLaunchKernelGGL(mvdr_apply_kernel<false>, dim3((unsigned)((T + chunk - 1) / chunk), F),
-                       dim3(256), 0, ctx->stream, Y, W, Phi, ref, F, T, D, ban, chunk, Xhat,
-                       ref_channel, ctx->status_dev, (int64_t)0, (const int32_t *)nullptr);
-    GSS_LAUNCH_CHECK(ctx, "mvdr_apply_kernel");
-    return GSS_OK;
+    return ref_apply_run(ctx, Y, F, T, D, k, true, forced_ref, ban, Xhat, ref_channel);
 }

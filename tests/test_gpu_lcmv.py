@@ -178,6 +178,29 @@ def test_a_dead_channel_takes_the_minimum_norm_solution(gpu_ctx):
         assert rel_err(got, want) <= bar
 
 
+@pytest.mark.parametrize('ban', [False, True])
+def test_the_fallback_on_a_dead_channel_gives_the_bits_of_the_mvdr(gpu_ctx, ban):
+    """An empty interferer mask (every frequency falls back) and a dead channel (the merged matrix
+    is exactly singular): the block is filled a second time with the merged sums and takes the
+    minimum-norm branch.  The merged sums are S_N + 0 and s_N + 0, so the MVDR of (X, N) is the
+    same arithmetic: equal bits, the same chosen channel.  On the CPU the reference
+    (lcmv_reference.py) is finite on this scene and chooses channel 5."""
+    from pb_chime5_amd import ops
+    D, T, F, dead = 6, 130, 3, 2
+    Y, xm, im, nm, _ = lr.scene(np.random.default_rng(6130), D, T, F)
+    Y[dead] = 0.0
+    im = np.zeros_like(im)
+    got, ref, fallbacks = ops.lcmv_souden_from_masks(
+        Y, xm, im, nm, ban=ban, min_mass=1.0, return_ref_channel=True, return_fallbacks=True,
+        ctx=gpu_ctx)
+    want, wref = ops.mvdr_souden_from_masks(Y, xm, nm, ban=ban, return_ref_channel=True,
+                                            ctx=gpu_ctx)
+    assert fallbacks == F == gpu_ctx.last_lcmv_fallbacks()
+    assert np.all(np.isfinite(got))
+    assert ref == wref
+    assert np.array_equal(got, want)
+
+
 # ------------------------------------------------------------------ 5. pick and masks
 def _posteriors():
     """K = 5 posteriors (K,T,F), target 1, the noise class last; masses 2 > 3 > 0 > 4."""
