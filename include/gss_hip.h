@@ -96,7 +96,9 @@ typedef enum {
  * gss_mvdr_online_state and gss_bf_online descriptors.  So were gss_cacgmm_online_init,
  * gss_cacgmm_online, gss_cacgmm_online_model, gss_last_cacgmm_online_fallbacks and
  * gss_enhance_observation_gss_online with the gss_cacgmm_online_state and gss_em_online
- * descriptors. */
+ * descriptors.  So were gss_stream_init, gss_stream_num_frames, gss_stream_num_samples_out,
+ * gss_stream_flush_samples, gss_stft_stream, gss_istft_stream and gss_stream_block with the
+ * gss_stream_state and gss_stream_cfg descriptors. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -1065,6 +1067,87 @@ int gss_enhance_observation_gss_online(gss_ctx *ctx, const gss_params *params,
                                        int64_t end_context_samples,
                                        const gss_em_online *em, const gss_bf_online *bf,
                                        double *out_dev, const gss_debug_taps *taps);
+
+/* ---- sample-block stream ------------------------------------------------------
+ * Samples in, samples out, in blocks of any length, with every state carried by the caller: the
+ * offline path with stft_fading = 1 cut at arbitrary sample positions.  (Entry points only, looked
+ * up by the binding: revision still 7.)  With W = size and H = shift (H divides W, H < W):
+ *    before the first sample the history is W - H zeros (the leading fading pad);
+ *    after M samples floor(M / H) frames exist, frame t covers the samples [t H - (W - H), t H + H);
+ *    after M samples max(0, floor(M / H) H - (W - H)) output samples have been emitted: the
+ *    algorithmic latency is W - H + (M mod H) samples;
+ *    the frame activity of frame t is the OR of the activity samples its window covers, clipped to
+ *    the samples that exist (gss_activity_time_to_frequency);
+ *    every output sample is the sum, started from 0.0, of its frames in ascending t (gss_istft).
+ * The caller ends a stream by feeding gss_stream_flush_samples() zeros (no activity) and cutting
+ * the output to the M samples that went in; the frames of the flushed stream are exactly those
+ * of gss_stft(fading = 1) on the whole signal.  The stream has no utterance context. */
+typedef struct {
+    double *x_hist;            /* (D, size): the last `size` samples per channel, oldest first */
+    uint8_t *act_hist;         /* (K, size): their activity; NULL (and K = 0): an unguided stream */
+    double *ola_tail;          /* (size - shift): the partial overlap-add sums the next frames complete */
+    int64_t received;          /* samples fed to the analysis side (host counters, advanced by  */
+    int64_t frames_out;        /* the calls) and frames taken by the synthesis side             */
+    int32_t D, K, size, shift;
+} gss_stream_state;            /* caller-owned, like gss_cacgmm_online_state */
+
+typedef struct {
+    double wpe_alpha;          /* the forgetting factors of the three online stages */
+    double em_forget;
+    double bf_forget;
+    int32_t ref_channel;       /* >= 0: a stream has no window to choose one over */
+} gss_stream_cfg;
+
+/* Pure geometry, no launches.  Frames that n more samples complete after `received`; output
+ * samples they finish; zeros that end a stream of `received` samples. */
+int64_t gss_stream_num_frames(int64_t received, int64_t n, int size, int shift);
+int64_t gss_stream_num_samples_out(int64_t received, int64_t n, int size, int shift);
+int64_t gss_stream_flush_samples(int64_t received, int size, int shift);
+
+/* Zeroes the buffers and the counters.  GSS_ERR_INVALID: a NULL state, x_hist or ola_tail,
+ * act_hist NULL with K > 0 (or the reverse), size / shift other than gss_set_windows()'s.
+ * GSS_ERR_UNSUPPORTED: shift == size, D outside [1, GSS_MAX_CHANNELS], K > GSS_MAX_CLASSES. */
+int gss_stream_init(gss_ctx *ctx, gss_stream_state *state);
+
+/* The analysis side.  x (D,n) float64 (in_type 0) or int16 PCM (in_type 1, times 2^-15: the
+ * history is float64 either way, so a PCM stream has the bits of the float64 stream of the same
+ * values), act (K,n) uint8 or NULL for an unguided stream -> the Tn = gss_stream_num_frames()
+ * frames the block completes, Y (F,Tn,D) and act_frames (K,Tn); the state advanced.  The frames
+ * have the bits of gss_stft(fading = 1) on the whole signal.  n = 0 is a no-op.
+ * GSS_ERR_INVALID before any launch: the errors of gss_stream_init, a NULL pointer, in_type other
+ * than 0 / 1, n < 0, act_dev given to an unguided state or missing for a guided one. */
+int gss_stft_stream(gss_ctx *ctx, const void *x_dev, int in_type, const uint8_t *act_dev, int64_t n,
+                    gss_stream_state *state, gss_cplx *Y_dev, uint8_t *act_frames_dev);
+
+/* The synthesis side.  X (Tn,F), the next Tn frames -> the output samples they finish,
+ * gss_stream_num_samples_out() of them (the leading W - H are dropped once); every frame is
+ * transformed on its own, so the samples do not depend on where the blocks were cut (gss_istft
+ * pairs frames 2b and 2b + 1 in one transform: equal to rounding, not to the bit).  Tn = 0 is a
+ * no-op.  GSS_ERR_INVALID: the errors of gss_stream_init, a NULL pointer, Tn < 0, more frames
+ * than the analysis side has produced. */
+int gss_istft_stream(gss_ctx *ctx, const gss_cplx *X_dev, int64_t Tn, gss_stream_state *state,
+                     double *out_dev);
+
+/* One block through the whole front-end, every stage with the caller's state: gss_stft_stream ->
+ * gss_wpe_online (params->wpe; wpe_taps, wpe_delay, wpe_arrays from params) -> gss_cacgmm_online
+ * with the block's frame activity as the mask (act_dev NULL: no mask, a state made from a model)
+ * -> gss_masks_from_posteriors with no frames zeroed -> gss_mvdr_online with BAN -> postfilter ->
+ * gss_istft_stream.  out receives gss_stream_num_samples_out() samples; the taps cover the block's
+ * Tn frames.  Of params the call reads stft_size, stft_shift, wpe, wpe_taps, wpe_delay, wpe_arrays
+ * and postfilter; stft_fading must be 1 and bf 0 (GSS_ERR_UNSUPPORTED).  `wpe` is NULL exactly
+ * when params->wpe == 0.  D is the stream state's, K the CACGMM state's.  n = 0 is a no-op.
+ * gss_last_mvdr_online_fallbacks, gss_last_cacgmm_online_fallbacks and gss_last_ref_channel work
+ * afterwards (a block that completes no frame leaves them).
+ * Every argument error returns before any launch, with all four states and `out` untouched:
+ * GSS_ERR_INVALID for a NULL pointer, n < 0, a state whose F / D / K differs from the stream's,
+ * ref_channel outside [0, D), target_index outside [0, K), a forgetting factor outside (0, 1], a
+ * WPE state with params->wpe == 0 or none with params->wpe != 0, and the errors of
+ * gss_stft_stream. */
+int gss_stream_block(gss_ctx *ctx, const gss_params *params, const gss_stream_cfg *cfg,
+                     gss_stream_state *state, const gss_wpe_online_state *wpe,
+                     gss_cacgmm_online_state *em, gss_mvdr_online_state *bf, const void *x_dev,
+                     int in_type, const uint8_t *act_dev, int64_t n, int target_index,
+                     double *out_dev, const gss_debug_taps *taps);
 
 /* gss_enhance_observation plus gss_posterior_activity on the pipeline's own post-WPE observation
  * and its posteriors before context zeroing (what the taps Obs_ftd and gamma show), nothing

@@ -113,6 +113,21 @@ class GssWpeOnlineCfg(ctypes.Structure):
     _fields_ = [('alpha', ctypes.c_double)]
 
 
+class GssStreamState(ctypes.Structure):
+    """gss_stream_state: the last `size` samples (D,size) and activity bytes (K,size) of a
+    sample-block stream, the overlap-add tail (size - shift), in HBM, and the host counters."""
+    _fields_ = [('x_hist', c_void_p), ('act_hist', c_void_p), ('ola_tail', c_void_p),
+                ('received', c_int64), ('frames_out', c_int64), ('D', ctypes.c_int32),
+                ('K', ctypes.c_int32), ('size', ctypes.c_int32), ('shift', ctypes.c_int32)]
+
+
+class GssStreamCfg(ctypes.Structure):
+    """gss_stream_cfg: the forgetting factors of the three online stages of a stream block and
+    the beamformer's reference channel."""
+    _fields_ = [('wpe_alpha', ctypes.c_double), ('em_forget', ctypes.c_double),
+                ('bf_forget', ctypes.c_double), ('ref_channel', ctypes.c_int32)]
+
+
 class GssChannelSelect(ctypes.Structure):
     """gss_channel_select: the band table and the settings of the envelope-variance channel
     selection."""
@@ -247,6 +262,19 @@ SIGNATURES = {
     'gss_last_cacgmm_online_fallbacks': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_enhance_observation_gss_online': _fused(ctypes.POINTER(GssEmOnline),
                                                  ctypes.POINTER(GssBfOnline)),
+    'gss_stream_num_frames': (c_int64, [c_int64, c_int64, c_int, c_int]),
+    'gss_stream_num_samples_out': (c_int64, [c_int64, c_int64, c_int, c_int]),
+    'gss_stream_flush_samples': (c_int64, [c_int64, c_int, c_int]),
+    'gss_stream_init': (c_int, [c_void_p, ctypes.POINTER(GssStreamState)]),
+    'gss_stft_stream': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                                ctypes.POINTER(GssStreamState), c_void_p, c_void_p]),
+    'gss_istft_stream': (c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(GssStreamState),
+                                 c_void_p]),
+    'gss_stream_block': (c_int, [c_void_p, ctypes.POINTER(GssParams), ctypes.POINTER(GssStreamCfg),
+                                 ctypes.POINTER(GssStreamState), ctypes.POINTER(GssWpeOnlineState),
+                                 ctypes.POINTER(GssCacgmmOnlineState),
+                                 ctypes.POINTER(GssMvdrOnlineState), c_void_p, c_int, c_void_p,
+                                 c_int64, c_int, c_void_p, _TAPS]),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,

@@ -20,7 +20,7 @@ LIB_PATH = LIB_DIR / 'libgss_hip.so'
 SOURCES = ['gss_api.hip', 'stft.hip', 'wpe.hip', 'cacgmm.hip', 'cacgmm_model.hip', 'cacgmm_prior.hip',
            'cacgmm_align.hip', 'cacgmm_link.hip', 'mvdr.hip',
            'chsel.hip', 'posterior_activity.hip', 'wpd.hip', 'wpe_online.hip', 'mvdr_online.hip',
-           'cacgmm_online.hip']
+           'cacgmm_online.hip', 'stream.hip']
 HEADERS = ['gss_internal.h', 'cacgmm_perm.h', 'jacobi.h', 'dense_wave.h', '../../include/gss_hip.h']
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs.  Without it the compiler
 # puts loop-carried accumulators in VGPRs but the MFMA destination in AGPRs and copies

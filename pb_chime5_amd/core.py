@@ -1143,6 +1143,70 @@ class Enhancer:
         return [i for i, k in enumerate(ex_array_activity.keys())
                 if k != speaker_id and k not in garbage]
 
+    def stream(self, num_channels, speakers=None, target=None, *, model=None, ref_channel=0,
+               fused=True):
+        """A `streaming.StreamingEnhancer` with this enhancer's settings: samples in and out in
+        blocks of any length, the three online stages with carried states.  ``speakers``: the
+        names of the classes in activity order (``target`` one of them; `process` then also
+        takes the activity as a dict of per-sample tracks) or a class count (``target`` an
+        index); or ``model=`` a fitted `CACGMM` for an unguided stream (``target`` an index).
+        NotImplementedError, naming the setting, for everything the stream is not built for: it
+        needs gss_online and bf_online (bf='mvdrSouden_ban'), wpe_online wherever WPE runs and
+        stft_fading, and has no channel selection, segments, interferer nulling or WPD."""
+        from .streaming import StreamingEnhancer
+
+        def refuse(setting, why):
+            raise NotImplementedError(f'stream with {setting}: {why}')
+        if not self._fusable():
+            refuse('custom blocks', 'the stream runs the library\'s own online stages')
+        if self._bf_wpd() is not None:
+            refuse(f'bf={self.bf_block.type!r}', 'the WPD beamformer has no online form')
+        if self.bf_block.type != 'mvdrSouden_ban':
+            refuse(f'bf={self.bf_block.type!r}', "only 'mvdrSouden_ban' has an online form")
+        if self.channel_keep is not None:
+            refuse('channel_keep', 'the selection ranks the channels of a whole window')
+        if self._bf_segments() is not None:
+            refuse('bf_segment_frames', 'the segment-wise beamformer needs the whole window')
+        if self._bf_null():
+            refuse('bf_null_interferer', 'the interferer-nulling beamformer needs the whole window')
+        if not self.stft_fading:
+            refuse('stft_fading=False', 'a stream is the faded STFT')
+        if self._gss_online() is None:
+            refuse('gss_online=False', 'the iterated EM needs the whole window')
+        if self._bf_online() is None:
+            refuse('bf_online=False', 'the whole-window beamformer needs the whole window')
+        if self.wpe_block is not None and self._wpe_online() is None:
+            refuse('wpe_online=False', 'the offline WPE needs the whole window')
+        names = None
+        if model is None:
+            if speakers is None:
+                raise ValueError('speakers: the names in activity order or a class count '
+                                 '(or model=)')
+            if ops._is_integer(speakers):
+                num_classes = int(speakers)
+            else:
+                names = list(speakers)
+                num_classes = len(names)
+                if target not in names:
+                    raise ValueError(f'target={target!r} is not one of speakers={names!r}')
+                target = names.index(target)
+        else:
+            if speakers is not None:
+                raise ValueError('speakers with model=: the stream is unguided')
+            num_classes = None
+        if target is None:
+            raise ValueError('target: the class to extract')
+        w, gss, bf = self.wpe_block, self._gss_online(), self._bf_online()
+        return StreamingEnhancer(
+            num_channels, num_classes, model=model, target=target, ref_channel=ref_channel,
+            stft_size=self.stft_size, stft_shift=self.stft_shift, wpe=w is not None,
+            wpe_taps=w.taps if w else 10, wpe_delay=w.delay if w else 2,
+            wpe_alpha=w.alpha if w else ops.WPE_ONLINE_ALPHA,
+            wpe_arrays=self.wpe_arrays(None, num_channels) if w else 1,
+            gss_forget=gss['forget'], gss_prior_mass=gss['prior_mass'], bf_forget=bf['forget'],
+            bf_loading=bf['loading'], postfilter=self.bf_block.postfilter, fused=fused,
+            speakers=names, ctx=self._ctx() if self.device_id is not None else None)
+
     def _params(self):
         w = self.wpe_block
         return ops.make_params(

@@ -2538,3 +2538,208 @@ extern "C" int gss_enhance_observation_host(gss_ctx *ctx, const gss_params *p,
     ctx->error = keep;
     return st;
 }
+
+// ------------------------------------------------------------------ sample-block stream
+// The stream state against the context's windows, before any launch.
+static int check_stream_state(gss_ctx *ctx, const char *what, const gss_stream_state *s) {
+    GSS_REQUIRE(ctx, s, GSS_ERR_INVALID, "%s: state is NULL", what);
+    GSS_TRY(check_windows(ctx));
+    GSS_REQUIRE(ctx, s->x_hist, GSS_ERR_INVALID, "%s: state->x_hist is NULL", what);
+    GSS_REQUIRE(ctx, s->ola_tail, GSS_ERR_INVALID, "%s: state->ola_tail is NULL", what);
+    GSS_REQUIRE(ctx, s->size == ctx->stft_size && s->shift == ctx->stft_shift, GSS_ERR_INVALID,
+                "%s: state of stft %d/%d, gss_set_windows() has %d/%d", what, (int)s->size,
+                (int)s->shift, ctx->stft_size, ctx->stft_shift);
+    GSS_REQUIRE(ctx, s->shift < s->size, GSS_ERR_UNSUPPORTED,
+                "%s: shift = size = %d, a stream needs overlapping frames", what, (int)s->size);
+    GSS_REQUIRE(ctx, s->D >= 1 && s->D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
+                "%s: state->D = %d outside [1, %d]", what, (int)s->D, GSS_MAX_CHANNELS);
+    GSS_REQUIRE(ctx, s->K >= 0 && s->K <= GSS_MAX_CLASSES, GSS_ERR_UNSUPPORTED,
+                "%s: state->K = %d outside [0, %d]", what, (int)s->K, GSS_MAX_CLASSES);
+    GSS_REQUIRE(ctx, (s->K > 0) == (s->act_hist != nullptr), GSS_ERR_INVALID,
+                "%s: state->act_hist and state->K = %d disagree", what, (int)s->K);
+    GSS_REQUIRE(ctx, s->received >= 0 && s->frames_out >= 0 &&
+                         s->frames_out <= s->received / s->shift,
+                GSS_ERR_INVALID, "%s: state counters received = %lld, frames_out = %lld", what,
+                (long long)s->received, (long long)s->frames_out);
+    return GSS_OK;
+}
+
+extern "C" int gss_stream_init(gss_ctx *ctx, gss_stream_state *state) {
+    GSS_ENTER(ctx);
+    GSS_TRY(check_stream_state(ctx, "gss_stream_init", state));
+    return stream_init_run(ctx, state);
+}
+
+// The analysis arguments of a block, before any launch (act NULL: no activity in this call).
+static int check_stream_input(gss_ctx *ctx, const char *what, const void *x, int in_type,
+                              const uint8_t *act, int64_t n, const gss_stream_state *s) {
+    GSS_TRY(check_stream_state(ctx, what, s));
+    GSS_REQUIRE(ctx, x, GSS_ERR_INVALID, "%s: x_dev is NULL", what);
+    GSS_REQUIRE(ctx, in_type == 0 || in_type == 1, GSS_ERR_INVALID, "%s: sample type %d", what,
+                in_type);
+    GSS_REQUIRE(ctx, n >= 0, GSS_ERR_INVALID, "%s: n = %lld is negative", what, (long long)n);
+    GSS_REQUIRE(ctx, !act || s->act_hist, GSS_ERR_INVALID,
+                "%s: act_dev given, the state carries no activity (state->K = 0)", what);
+    GSS_REQUIRE(ctx, act || !s->act_hist, GSS_ERR_INVALID,
+                "%s: act_dev is NULL, the state carries the activity of %d classes", what, (int)s->K);
+    const int64_t Tn = gss_stream_num_frames(s->received, n, s->size, s->shift);
+    GSS_REQUIRE(ctx, Tn < 2147483647, GSS_ERR_UNSUPPORTED, "%s: too many frames", what);
+    GSS_TRY(check_stft_bins(ctx, s->size / 2 + 1, Tn, s->D));
+    return GSS_OK;
+}
+
+extern "C" int gss_stft_stream(gss_ctx *ctx, const void *x, int in_type, const uint8_t *act,
+                               int64_t n, gss_stream_state *state, gss_cplx *Y, uint8_t *actf) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_stft_stream";
+    GSS_TRY(check_stream_input(ctx, what, x, in_type, act, n, state));
+    GSS_REQUIRE(ctx, Y, GSS_ERR_INVALID, "%s: Y_dev is NULL", what);
+    GSS_REQUIRE(ctx, !act || actf, GSS_ERR_INVALID, "%s: act_frames_dev is NULL", what);
+    if (n == 0) return GSS_OK;
+    const int64_t Tn = gss_stream_num_frames(state->received, n, state->size, state->shift);
+    GSS_TRY(arena_reserve(ctx, stream_stft_workspace_bytes(Tn, state->D, state->K, state->size,
+                                                           state->shift)));
+    return stream_stft_run(ctx, x, in_type, act, n, state, reinterpret_cast<cplx *>(Y), actf);
+}
+
+extern "C" int gss_istft_stream(gss_ctx *ctx, const gss_cplx *X, int64_t Tn, gss_stream_state *state,
+                                double *out) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_istft_stream";
+    GSS_TRY(check_stream_state(ctx, what, state));
+    GSS_REQUIRE(ctx, X, GSS_ERR_INVALID, "%s: X_dev is NULL", what);
+    GSS_REQUIRE(ctx, out, GSS_ERR_INVALID, "%s: out_dev is NULL", what);
+    GSS_REQUIRE(ctx, Tn >= 0, GSS_ERR_INVALID, "%s: Tn = %lld is negative", what, (long long)Tn);
+    GSS_REQUIRE(ctx, state->frames_out + Tn <= state->received / state->shift, GSS_ERR_INVALID,
+                "%s: Tn = %lld frames after %lld, the stream has analysed %lld", what, (long long)Tn,
+                (long long)state->frames_out, (long long)(state->received / state->shift));
+    if (Tn == 0) return GSS_OK;
+    GSS_TRY(arena_reserve(ctx, stream_istft_workspace_bytes(Tn, state->size, state->shift)));
+    return stream_istft_run(ctx, reinterpret_cast<const cplx *>(X), Tn, state, out);
+}
+
+// The buffers of one block of the stream, taken first; every stage runs above them.
+struct StreamBlockBuffers {
+    cplx *Y, *X;        // the block's STFT and the WPE output; no WPE: X is Y
+    uint8_t *actf;      // (K,Tn), NULL for an unguided stream
+    double *gamma, *mx, *mn;
+    cplx *Xhat;         // (Tn,F)
+    int32_t *ref;
+};
+static StreamBlockBuffers stream_block_blocks(Workspace &ws, bool wpe, bool guided, int F, int64_t Tn,
+                                              int D, int K) {
+    const size_t ft = (size_t)F * Tn;
+    StreamBlockBuffers b;
+    b.Y = ws.take<cplx>(ft * D, "stream Y");
+    b.X = wpe ? ws.take<cplx>(ft * D, "stream X") : b.Y;
+    b.actf = guided ? ws.take<uint8_t>((size_t)K * Tn, "stream frame activity") : nullptr;
+    b.gamma = ws.take<double>(ft * K, "stream gamma");
+    b.mx = ws.take<double>(ft, "stream target mask");
+    b.mn = ws.take<double>(ft, "stream distortion mask");
+    b.Xhat = ws.take<cplx>(ft, "stream Xhat");
+    b.ref = ws.take<int32_t>(4, "stream ref");
+    return b;
+}
+
+static size_t stream_block_workspace(const gss_params *p, bool guided, int F, int64_t Tn, int D,
+                                     int K) {
+    size_t stage = stream_stft_workspace_bytes(Tn, D, guided ? K : 0, p->stft_size, p->stft_shift);
+    if (Tn == 0) return stage + (1 << 16);
+    Workspace ws;
+    stream_block_blocks(ws, p->wpe != 0, guided, F, Tn, D, K);
+    if (p->wpe)
+        stage = std::max(stage, wpe_online_workspace_bytes(F, Tn, wpe_arrays_of(p), D / wpe_arrays_of(p),
+                                                           p->wpe_taps, p->wpe_delay, false));
+    stage = std::max(stage, cacgmm_online_workspace_bytes(F, K, D, false));
+    stage = std::max(stage, mvdr_online_workspace_bytes(F, Tn, D, false, false));
+    stage = std::max(stage, stream_istft_workspace_bytes(Tn, p->stft_size, p->stft_shift));
+    return ws.bytes + 4096 + stage + (1 << 16);
+}
+
+extern "C" int gss_stream_block(gss_ctx *ctx, const gss_params *p, const gss_stream_cfg *cfg,
+                                gss_stream_state *st, const gss_wpe_online_state *wpe,
+                                gss_cacgmm_online_state *em, gss_mvdr_online_state *bf, const void *x,
+                                int in_type, const uint8_t *act, int64_t n, int target, double *out,
+                                const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *const what = "gss_stream_block";
+    GSS_REQUIRE(ctx, cfg, GSS_ERR_INVALID, "%s: cfg is NULL", what);
+    GSS_REQUIRE(ctx, em, GSS_ERR_INVALID, "%s: the CACGMM state is NULL", what);
+    GSS_REQUIRE(ctx, bf, GSS_ERR_INVALID, "%s: the MVDR state is NULL", what);
+    GSS_REQUIRE(ctx, out, GSS_ERR_INVALID, "%s: out_dev is NULL", what);
+    GSS_TRY(check_windows(ctx));
+    GSS_TRY(check_params(ctx, p));
+    GSS_REQUIRE(ctx, p->stft_fading == 1, GSS_ERR_UNSUPPORTED,
+                "%s: stft_fading = %d, a stream is the faded STFT", what, p->stft_fading);
+    GSS_REQUIRE(ctx, p->bf == 0, GSS_ERR_UNSUPPORTED,
+                "%s: bf=%d, only 0 ('mvdrSouden_ban') has an online form", what, p->bf);
+    GSS_TRY(check_stream_input(ctx, what, x, in_type, act, n, st));
+    const int D = st->D, K = em->K, F = p->stft_size / 2 + 1;
+    const bool guided = act != nullptr;
+    GSS_TRY(check_em_online_shape(ctx, what, F, K, D));
+    GSS_TRY(check_cacgmm_online_state(ctx, what, em, F, K, D));
+    GSS_REQUIRE(ctx, !guided || st->K == K, GSS_ERR_INVALID,
+                "%s: the stream carries the activity of %d classes, the CACGMM state has %d", what,
+                (int)st->K, K);
+    GSS_TRY(check_mvdr_online_state(ctx, what, bf, F, D));
+    GSS_TRY(check_target_index(ctx, target, K));
+    const gss_em_online em_cfg{cfg->em_forget, 1.0};
+    GSS_TRY(check_em_online(ctx, what, &em_cfg));
+    const gss_bf_online bf_cfg{cfg->bf_forget, 1.0, cfg->ref_channel, 0, 1.0};
+    GSS_REQUIRE(ctx, cfg->ref_channel >= 0, GSS_ERR_INVALID,
+                "%s: ref_channel = %d, a stream has no window to choose one over", what,
+                (int)cfg->ref_channel);
+    GSS_TRY(check_bf_online(ctx, what, &bf_cfg, D));
+    GSS_REQUIRE(ctx, (wpe != nullptr) == (p->wpe != 0), GSS_ERR_INVALID,
+                "%s: params->wpe = %d %s a WPE state", what, p->wpe, wpe ? "with" : "without");
+    const int A = wpe_arrays_of(p);
+    if (p->wpe) {
+        GSS_TRY(check_wpe_online_state(ctx, what, wpe));
+        GSS_TRY(check_wpe_arrays(ctx, p, D));
+        GSS_TRY(check_wpe_online(ctx, what, F, A, D / A, p->wpe_taps, p->wpe_delay, cfg->wpe_alpha));
+    }
+    if (n == 0) return GSS_OK;
+
+    const int64_t Tn = gss_stream_num_frames(st->received, n, p->stft_size, p->stft_shift);
+    GSS_TRY(arena_reserve(ctx, stream_block_workspace(p, guided, F, Tn, D, K)));
+    if (Tn == 0)    // the samples enter the history, no frame is complete yet
+        return stream_stft_run(ctx, x, in_type, act, n, st, nullptr, nullptr);
+    Workspace ws(ctx);
+    const StreamBlockBuffers b = stream_block_blocks(ws, p->wpe != 0, guided, F, Tn, D, K);
+    GSS_TRY(ws.status(what));
+    const size_t mark = ctx->arena_off;
+    GSS_TRY(stream_stft_run(ctx, x, in_type, act, n, st, b.Y, b.actf));
+    GSS_TRY(arena_release(ctx, mark));
+    // no solve in this call: clear the pivot count an earlier utterance left behind
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + GSS_STATUS_WPE_ZERO_PIVOTS, 0,
+                                      sizeof(int32_t), ctx->stream));
+    if (p->wpe) {
+        GSS_TRY(wpe_online_run(ctx, b.Y, F, Tn, A, D / A, p->wpe_taps, p->wpe_delay, cfg->wpe_alpha,
+                               reinterpret_cast<cplx *>(wpe->inv_cov_dev),
+                               reinterpret_cast<cplx *>(wpe->filter_dev),
+                               reinterpret_cast<cplx *>(wpe->history_dev), b.X,
+                               gss_variant_set("wpe_online_mem")));
+        GSS_TRY(arena_release(ctx, mark));
+    }
+    const EmGuide guide = guided ? em_guide_from_activity(b.actf, Tn) : EmGuide{};
+    GSS_TRY(cacgmm_online_run(ctx, b.X, F, Tn, D, guide, K, cfg->em_forget, 1.0,
+                              reinterpret_cast<cplx *>(em->s), em->n, b.gamma));
+    GSS_TRY(arena_release(ctx, mark));
+    GSS_TRY(masks_from_posteriors_run(ctx, b.gamma, F, K, Tn, target, /*drop=*/0, 0, 0, b.mx, b.mn));
+    GSS_TRY(mvdr_online_run(ctx, b.X, F, Tn, D, b.mx, b.mn, /*ban=*/1, cfg->bf_forget, 1.0,
+                            cfg->ref_channel, reinterpret_cast<cplx *>(bf->phi_x),
+                            reinterpret_cast<cplx *>(bf->phi_n), b.Xhat, 1, F, nullptr, b.ref));
+    GSS_TRY(arena_release(ctx, mark));
+    if (p->postfilter == 1) GSS_TRY(mask_mul_run(ctx, b.Xhat, b.mx, F, Tn));
+    GSS_TRY(stream_istft_run(ctx, b.Xhat, Tn, st, out));
+    if (taps) {
+        GSS_TRY(copy_tap(ctx, taps->Obs_ftd, b.X, sizeof(cplx) * (size_t)F * Tn * D));
+        if (guided) GSS_TRY(copy_tap(ctx, taps->act_frames, b.actf, (size_t)K * Tn));
+        GSS_TRY(copy_tap(ctx, taps->gamma, b.gamma, sizeof(double) * (size_t)F * K * Tn));
+        GSS_TRY(copy_tap(ctx, taps->target_mask, b.mx, sizeof(double) * (size_t)F * Tn));
+        GSS_TRY(copy_tap(ctx, taps->distortion_mask, b.mn, sizeof(double) * (size_t)F * Tn));
+        GSS_TRY(copy_tap(ctx, taps->Xhat, b.Xhat, sizeof(cplx) * (size_t)F * Tn));
+        GSS_TRY(copy_tap(ctx, taps->ref_channel, b.ref, sizeof(int32_t)));
+    }
+    return GSS_OK;
+}

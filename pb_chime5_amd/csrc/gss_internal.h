@@ -546,6 +546,9 @@ int stft_run(gss_ctx *ctx, const void *x, int in_type, int D, int64_t N, int fad
 int istft_run(gss_ctx *ctx, const cplx *X, int64_t T, int fading, double *x, int S = 1);
 int activity_run(gss_ctx *ctx, const uint8_t *act, int K, int64_t N, int fading,
                  uint8_t *out);
+// X (T,F) -> frm (T, size) windowed inverse frames, one transform per frame: a frame's samples do
+// not depend on its neighbours in the call (istft_run pairs frames 2b and 2b + 1)
+int istft_single_frames_run(gss_ctx *ctx, const cplx *X, int64_t T, double *frm);
 int channel_pick_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int mode,
                      cplx *Xhat);  // mode 1: 'ch2', 2: 'sum'
 int mask_mul_run(gss_ctx *ctx, cplx *Xhat, const double *mask_ft, int F, int64_t T);
@@ -626,6 +629,18 @@ int cacgmm_online_to_model_run(gss_ctx *ctx, const cplx *S, const double *n, int
                                const EmModel &m);
 int cacgmm_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const EmGuide &guide,
                       int K, double beta, double prior_mass, cplx *S, double *n, double *gamma);
+
+// Sample-block stream (stream.hip; include/gss_hip.h: gss_stft_stream, gss_istft_stream).  The
+// state and the arguments have been validated by the entry point; the host counters of the state
+// are advanced by the run.  stft: n >= 1 samples -> Tn = gss_stream_num_frames() frames Y (F,Tn,D)
+// and, with an activity, actf (K,Tn).  istft: X (Tn,F), Tn >= 1 -> gss_stream_num_samples_out()
+// samples.  Workspace from the arena (stream_*_workspace_bytes).
+size_t stream_stft_workspace_bytes(int64_t Tn, int D, int K, int size, int shift);
+size_t stream_istft_workspace_bytes(int64_t Tn, int size, int shift);
+int stream_init_run(gss_ctx *ctx, gss_stream_state *st);
+int stream_stft_run(gss_ctx *ctx, const void *x, int in_type, const uint8_t *act, int64_t n,
+                    gss_stream_state *st, cplx *Y, uint8_t *actf);
+int stream_istft_run(gss_ctx *ctx, const cplx *X, int64_t Tn, gss_stream_state *st, double *out);
 
 int selftest_mfma_run(gss_ctx *ctx);
 

@@ -218,6 +218,34 @@ __global__ __launch_bounds__(FFT_THREADS) void istft_frames_kernel(
     }
 }
 
+// Inverse of ONE frame per workgroup: frame t of X (T,F) -> frm (T, size), synthesis-windowed.
+// istft_frames_kernel puts two frames through one complex transform and each leaks ~1e-16 into its
+// partner, so a frame's samples depend on which frame it is paired with; a stream that is cut into
+// blocks at arbitrary frames (stream.hip) needs every frame to come out the same whatever its
+// neighbours in the call are.  Z = A alone: the real part of the transform.
+__global__ __launch_bounds__(FFT_THREADS) void istft_frame_kernel(
+    const cplx *__restrict__ X, int size, int log2n, const double *__restrict__ syn,
+    const cplx *__restrict__ twiddle, double *__restrict__ frm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    cplx *s = reinterpret_cast<cplx *>(smem);   // size
+    cplx *tw = s + size;                         // size / 2
+    const int F = size / 2 + 1;
+    const int64_t t = blockIdx.x;
+    for (int i = threadIdx.x; i < size / 2; i += blockDim.x) tw[i] = twiddle[i];
+    for (int k = threadIdx.x; k < size; k += blockDim.x) {
+        const int f = k <= size / 2 ? k : size - k;
+        cplx a = X[t * F + f];
+        if (f == 0 || f == size / 2) a.y = 0.0;
+        if (k > size / 2) a.y = -a.y;
+        s[bitrev(k, log2n)] = a;
+    }
+    __syncthreads();
+    fft_lds(s, size, log2n, 1, tw, true);
+    const double scale = 1.0 / (double)size;
+    for (int i = threadIdx.x; i < size; i += blockDim.x)
+        frm[t * size + i] = syn[i] * (s[i].x * scale);
+}
+
 // ---- any even window length (not a power of two): direct DFT.  The reference's default is
 // 1024 and every BASELINE config uses it; get_enhancer(stft_size=...) (core.py:577) takes any
 // length though, so other sizes get a plain O(size^2) transform per frame -- a few ms per
@@ -527,6 +555,24 @@ int istft_run(gss_ctx *ctx, const cplx *X, int64_t T, int fading, double *x, int
                            ctx->stream, frm, T, size, shift, pad, n_out, x);
         GSS_LAUNCH_CHECK(ctx, "istft_ola_kernel");
     }
+    return GSS_OK;
+}
+
+// X (T,F) -> frm (T, size): the windowed inverse frames, every frame transformed on its own
+int istft_single_frames_run(gss_ctx *ctx, const cplx *X, int64_t T, double *frm) {
+    const int size = ctx->stft_size;
+    GSS_PROF(ctx, "istft_single_frames");
+    if ((size & (size - 1)) != 0) {     // (the direct DFT already takes one frame per workgroup)
+        const size_t lds = sizeof(cplx) * (size / 2 + size / 2 + 1);
+        hipLaunchKernelGGL(istft_dft_kernel, dim3((unsigned)T, 1), dim3(FFT_THREADS), lds, ctx->stream,
+                           X, T, size, ctx->win_synthesis, ctx->twiddle, frm);
+        GSS_LAUNCH_CHECK(ctx, "istft_dft_kernel");
+        return GSS_OK;
+    }
+    const size_t lds = sizeof(cplx) * (size + size / 2);
+    hipLaunchKernelGGL(istft_frame_kernel, dim3((unsigned)T), dim3(FFT_THREADS), lds, ctx->stream, X,
+                       size, ilog2(size), ctx->win_synthesis, ctx->twiddle, frm);
+    GSS_LAUNCH_CHECK(ctx, "istft_frame_kernel");
     return GSS_OK;
 }
 

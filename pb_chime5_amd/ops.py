@@ -33,6 +33,10 @@ here                        reference call (file:line)
 ``cacgmm_posteriors_online`` / ``OnlineCACGMMState`` / ``enhance_observation_gss_online``
                             the recursive (online) EM of the mixture model: running sums that
                             forget, causal posteriors and a carried state (not in the reference)
+``StreamState`` / ``stft_stream`` / ``istft_stream`` / ``stream_block`` / ``masks_from_posteriors``
+                            the two ends of a sample-block stream with a carried state and one
+                            block through the three online stages (not in the reference; the
+                            front door is ``streaming.StreamingEnhancer``)
 ``lcmv_souden_from_masks``  beamform_lcmv_souden_from_masks (beamforming_wrapper.py:127-171)
 ``lcmv_masks_from_posteriors`` / ``enhance_observation_lcmv``
                             the interferer-nulling LCMV fed from the posteriors
@@ -56,7 +60,8 @@ from . import _capi
 from ._capi import (Context, GssBfLcmv, GssBfSegments, GssBfWpd, GssCacgmmModel,
                     GssCacgmmOnlineState, GssChannelSelect, GssEmOnline,
                     GssBfOnline, GssDebugTaps, GssGuidance, GssMvdrOnlineState, GssParams,
-                    GssWpeOnlineCfg, GssWpeOnlineState, c_void_p, default_context)
+                    GssStreamCfg, GssStreamState, GssWpeOnlineCfg, GssWpeOnlineState, c_void_p,
+                    default_context)
 from .cacgmm import CACGMM
 
 _BF_CODES = {'mvdrSouden_ban': 0, 'ch2': 1, 'sum': 2, 'gev_ban': 3}
@@ -2992,3 +2997,282 @@ def separate_observation(obs, initialization, *, params=None, window=None, debug
     if debug:
         out.append(_debug_details(win, bufs, win.K))
     return tuple(out)
+
+
+# --------------------------------------------------------------------------
+# sample-block stream (gss_stream_state; include/gss_hip.h)
+# --------------------------------------------------------------------------
+def _check_stream_geometry(size, shift):
+    for name, value in (('size', size), ('shift', shift)):
+        if not _is_integer(value) or value < 1:
+            raise ValueError(f'{name}={value!r}: a positive integer')
+    if size % shift != 0:
+        raise ValueError(f'shift={shift} does not divide size={size}')
+
+
+def _check_stream_count(value, name):
+    if not _is_integer(value) or value < 0:
+        raise ValueError(f'{name}={value!r}: a non-negative integer')
+    return int(value)
+
+
+def stream_num_frames(received, n, size, shift):
+    """Frames that ``n`` more samples complete after ``received`` samples of a stream:
+    floor((received + n) / shift) - floor(received / shift) (gss_stream_num_frames)."""
+    _check_stream_geometry(size, shift)
+    return int(_capi.load_library().gss_stream_num_frames(
+        _check_stream_count(received, 'received'), _check_stream_count(n, 'n'), size, shift))
+
+
+def stream_num_samples_out(received, n, size, shift):
+    """Output samples that ``n`` more samples finish after ``received``: the growth of
+    max(0, floor(M / shift) * shift - (size - shift)) (gss_stream_num_samples_out)."""
+    _check_stream_geometry(size, shift)
+    return int(_capi.load_library().gss_stream_num_samples_out(
+        _check_stream_count(received, 'received'), _check_stream_count(n, 'n'), size, shift))
+
+
+def stream_flush_samples(received, size, shift):
+    """Zeros that end a stream of ``received`` samples: afterwards its frames are those of
+    `stft` (fading=True) on the whole signal (gss_stream_flush_samples)."""
+    _check_stream_geometry(size, shift)
+    return int(_capi.load_library().gss_stream_flush_samples(
+        _check_stream_count(received, 'received'), size, shift))
+
+
+def check_stream(num_channels, num_classes, size, shift):
+    """The sizes of a stream -- the one place that validates them.  ValueError naming the
+    argument: ``num_channels`` an integer in [1, 32], ``num_classes`` an integer in [0, 8] (0: an
+    unguided stream, no activity), ``shift`` dividing ``size``.  NotImplementedError:
+    ``shift`` == ``size`` (a stream needs overlapping frames), a ``size`` the STFT is not built
+    for."""
+    if not _is_integer(num_channels) or not 1 <= num_channels <= _MAX_CHANNELS:
+        raise ValueError(f'num_channels={num_channels!r}: an integer in [1, {_MAX_CHANNELS}]')
+    if not _is_integer(num_classes) or not 0 <= num_classes <= _ONLINE_MAX_CLASSES:
+        raise ValueError(f'num_classes={num_classes!r}: an integer in [0, {_ONLINE_MAX_CLASSES}]')
+    _check_stream_geometry(size, shift)
+    if size % 2 or not 4 <= size <= 4096:
+        raise NotImplementedError(f'size={size}: an even length in [4, 4096]')
+    if shift == size:
+        raise NotImplementedError(f'shift == size == {size}: a stream needs overlapping frames')
+    return int(num_channels), int(num_classes), int(size), int(shift)
+
+
+class StreamState(_OnlineState):
+    """The state of the two ends of a sample-block stream in HBM (gss_stream_state), caller-owned
+    like an `OnlineWPEState`: ``x_hist`` (D,size) float64, the last samples; ``act_hist`` (K,size)
+    uint8, their activity (absent for K = 0, an unguided stream); ``ola_tail`` (size - shift), the
+    partial overlap-add sums; and the host counters ``received`` and ``frames_out``."""
+    _sizes = 'D, K, size, shift'
+    dtypes = {'x_hist': np.float64, 'act_hist': np.uint8, 'ola_tail': np.float64}
+
+    def __init__(self, ctx, D, K, size, shift):
+        super().__init__(ctx, D, K, size, shift)
+        self.D, self.K, self.size, self.shift = self.key
+        self._struct = GssStreamState(
+            x_hist=self.bufs['x_hist'].ptr,
+            act_hist=self.bufs['act_hist'].ptr if self.K else None,
+            ola_tail=self.bufs['ola_tail'].ptr, received=0, frames_out=0, D=self.D, K=self.K,
+            size=self.size, shift=self.shift)
+
+    @staticmethod
+    def _shapes(D, K, size, shift):
+        shapes = {'x_hist': (D, size), 'ola_tail': (size - shift,)}
+        if K:
+            shapes['act_hist'] = (K, size)
+        return shapes
+
+    def struct(self):
+        """The ONE struct of this state: the library advances its counters."""
+        return self._struct
+
+    received = property(lambda self: int(self._struct.received))
+    frames_out = property(lambda self: int(self._struct.frames_out))
+
+    @classmethod
+    def fresh(cls, D, K, size=1024, shift=256, *, window=None, ctx=None):
+        """Zeros: the leading fading pad, no sample yet (gss_stream_init)."""
+        check_stream(D, K, size, shift)
+        ctx = ctx or default_context()
+        _prepare_windows(ctx, size, shift, window)
+        state = cls(ctx, D, K, size, shift)
+        ctx._check(ctx.lib.gss_stream_init(ctx.handle, ctypes.byref(state._struct)),
+                   'gss_stream_init')
+        return state
+
+    def to_host(self):
+        """The buffers by name plus 'size', 'shift', 'received' and 'frames_out': everything
+        `from_host` needs (synchronises)."""
+        return dict(super().to_host(), size=self.size, shift=self.shift, received=self.received,
+                    frames_out=self.frames_out)
+
+    @classmethod
+    def from_host(cls, host, *, ctx=None):
+        """A device state from the dict of `to_host` (in any context).  ValueError for shapes or
+        counters that do not fit each other."""
+        x = np.asarray(host['x_hist'])
+        if x.ndim != 2:
+            raise ValueError(f'x_hist: shape {x.shape} is not (D,size)')
+        size, shift = int(host['size']), int(host['shift'])
+        K = np.asarray(host['act_hist']).shape[0] if 'act_hist' in host else 0
+        check_stream(x.shape[0], K, size, shift)
+        received = _check_stream_count(host['received'], 'received')
+        frames_out = _check_stream_count(host['frames_out'], 'frames_out')
+        if frames_out > received // shift:
+            raise ValueError(f'frames_out={frames_out} after received={received} samples: at most '
+                             f'{received // shift} frames exist')
+        state = cls._from_host(host, (x.shape[0], K, size, shift), ctx,
+                               lambda shape: f'{shape} (size={size}, shift={shift})')
+        state._struct.received, state._struct.frames_out = received, frames_out
+        return state
+
+
+def _stream_block_to_device(ctx, block, activity, state):
+    """A block (D,n) float64 / int16 and its activity (K,n) or None against ``state``:
+    (x_d, in_type, act_d, n)."""
+    block = np.asarray(block)
+    if block.ndim != 2 or block.shape[0] != state.D:
+        raise ValueError(f'block: shape {block.shape} is not (D,n) = ({state.D},n)')
+    pcm = block.dtype == np.int16
+    if not pcm:
+        block = np.asarray(block, dtype=np.float64)
+    n = block.shape[1]
+    if (activity is None) != (state.K == 0):
+        raise ValueError('activity: missing for a stream that carries one' if activity is None
+                         else 'activity: given to an unguided stream (num_classes = 0)')
+    act_d = None
+    if activity is not None:
+        activity = np.asarray(activity)
+        if activity.shape != (state.K, n):
+            raise ValueError(f'activity: shape {activity.shape} is not (K,n) = ({state.K},{n})')
+        act_d = ctx.to_device((activity != 0).astype(np.uint8)) if n else None
+    return (ctx.to_device(block) if n else None), int(pcm), act_d, n
+
+
+def stft_stream(block, activity=None, *, state, window=None):
+    """The analysis side of a stream (gss_stft_stream): the next ``block`` (D,n) of samples,
+    float64 or int16 PCM, and its ``activity`` (K,n) (None for an unguided stream) -> the frames
+    the block completes, (D,Tn,F) complex128, and their frame activity (K,Tn) bool or None.
+    ``state``: a `StreamState`, advanced IN PLACE.  Over all blocks the frames have the bits of
+    `stft` (fading=True) on the whole signal."""
+    if not isinstance(state, StreamState):
+        raise ValueError(f'state: {type(state).__name__} is not a StreamState')
+    ctx = state.ctx
+    x_d, in_type, act_d, n = _stream_block_to_device(ctx, block, activity, state)
+    D, K, F = state.D, state.K, state.size // 2 + 1
+    Tn = stream_num_frames(state.received, n, state.size, state.shift)
+    if n == 0:
+        return np.zeros((D, 0, F), np.complex128), (np.zeros((K, 0), bool) if K else None)
+    _prepare_windows(ctx, state.size, state.shift, window)
+    Y_d = ctx.empty(max(16 * F * Tn * D, 16))
+    a_d = ctx.empty(max(K * Tn, 16))
+    ctx._check(ctx.lib.gss_stft_stream(
+        ctx.handle, c_void_p(x_d.ptr), in_type, c_void_p(act_d.ptr) if act_d else None, n,
+        ctypes.byref(state.struct()), c_void_p(Y_d.ptr), c_void_p(a_d.ptr)), 'gss_stft_stream')
+    if Tn == 0:
+        ctx.synchronize()      # (the block's device copy is read until then)
+        return np.zeros((D, 0, F), np.complex128), (np.zeros((K, 0), bool) if K else None)
+    Y = _ftd_to_host_dtf(ctx, Y_d, D, Tn, F)
+    return Y, (ctx.to_host(a_d, (K, Tn), np.uint8).astype(bool) if K else None)
+
+
+def istft_stream(stft_signal, *, state, window=None):
+    """The synthesis side of a stream (gss_istft_stream): the next frames (Tn,F) -> the samples
+    they finish, `stream_num_samples_out` of them.  ``state``: the `StreamState` whose analysis
+    side produced the frames, advanced IN PLACE.  Every frame is transformed on its own: the
+    samples do not depend on where the blocks were cut."""
+    if not isinstance(state, StreamState):
+        raise ValueError(f'state: {type(state).__name__} is not a StreamState')
+    X = np.asarray(stft_signal, dtype=np.complex128)
+    F = state.size // 2 + 1
+    if X.ndim != 2 or X.shape[1] != F:
+        raise ValueError(f'stft_signal: shape {X.shape} is not (Tn,F) = (Tn,{F})')
+    Tn = X.shape[0]
+    if Tn == 0:
+        return np.zeros(0)
+    ctx, pad = state.ctx, state.size - state.shift
+    m = (max(0, (state.frames_out + Tn) * state.shift - pad)
+         - max(0, state.frames_out * state.shift - pad))
+    _prepare_windows(ctx, state.size, state.shift, window)
+    X_d = ctx.to_device(X)
+    o_d = ctx.empty(max(8 * m, 16))
+    ctx._check(ctx.lib.gss_istft_stream(ctx.handle, c_void_p(X_d.ptr), Tn,
+                                        ctypes.byref(state.struct()), c_void_p(o_d.ptr)),
+               'gss_istft_stream')
+    return ctx.to_host(o_d, (m,), np.float64)
+
+
+def stream_block(block, activity=None, *, params, stream, em_state, bf_state, wpe_state=None,
+                 target_index=0, ref_channel=0, wpe_alpha=WPE_ONLINE_ALPHA,
+                 em_forget=GSS_ONLINE_FORGET, bf_forget=BF_ONLINE_FORGET, window=None,
+                 debug=False):
+    """One block of a stream through the whole front-end as ONE library call (gss_stream_block):
+    `stft_stream` -> `wpe_online_dtf` -> `cacgmm_posteriors_online` masked by the block's frame
+    activity -> masks with no frames zeroed -> `mvdr_souden_online_from_masks` with BAN ->
+    postfilter -> `istft_stream`, every stage with the caller's state, all four advanced IN
+    PLACE.  ``wpe_state`` is None exactly when ``params.wpe`` is 0.  Returns (samples, details):
+    the samples the block finishes, and with ``debug`` the taps over the block's frames (else
+    None), with 'fallbacks' = (online MVDR, online CACGMM) counts of the block."""
+    if not isinstance(stream, StreamState):
+        raise ValueError(f'stream: {type(stream).__name__} is not a StreamState')
+    ctx = stream.ctx
+    for name, state, cls in (('em_state', em_state, OnlineCACGMMState),
+                             ('bf_state', bf_state, OnlineMVDRState),
+                             ('wpe_state', wpe_state, OnlineWPEState)):
+        if state is None and name == 'wpe_state':
+            continue
+        if not isinstance(state, cls):
+            raise ValueError(f'{name}: {type(state).__name__} is not an {cls.__name__}')
+        if state.ctx is not ctx:
+            raise ValueError(f'{name}: it lives in another context than the stream')
+    x_d, in_type, act_d, n = _stream_block_to_device(ctx, block, activity, stream)
+    if n == 0:
+        return np.zeros(0), None
+    D, K, F = stream.D, em_state.K, stream.size // 2 + 1
+    Tn = stream_num_frames(stream.received, n, stream.size, stream.shift)
+    m = stream_num_samples_out(stream.received, n, stream.size, stream.shift)
+    _prepare_windows(ctx, stream.size, stream.shift, window)
+    o_d = ctx.empty(max(8 * m, 16))
+    utt = SimpleNamespace(ctx=ctx, D=D, K=K, T=Tn, params=params)
+    bufs, taps = _debug_taps(utt) if debug and Tn > 0 else (None, None)
+    cfg = GssStreamCfg(wpe_alpha=float(wpe_alpha), em_forget=float(em_forget),
+                       bf_forget=float(bf_forget), ref_channel=int(ref_channel))
+    ctx._check(ctx.lib.gss_stream_block(
+        ctx.handle, ctypes.byref(params), ctypes.byref(cfg), ctypes.byref(stream.struct()),
+        ctypes.byref(wpe_state.struct()) if wpe_state is not None else None,
+        ctypes.byref(em_state.struct()), ctypes.byref(bf_state.struct()), c_void_p(x_d.ptr),
+        in_type, c_void_p(act_d.ptr) if act_d else None, n, int(target_index), c_void_p(o_d.ptr),
+        ctypes.byref(taps) if taps is not None else None), 'gss_stream_block')
+    samples = ctx.to_host(o_d, (m,), np.float64)
+    if m == 0:
+        ctx.synchronize()      # (the block's device copies are read until then)
+    if bufs is None:
+        return samples, None
+    if act_d is None:
+        del bufs['act_frames']
+    details = _debug_details(utt, bufs)
+    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+    details['ref_channel'] = int(details['ref_channel'])
+    details['fallbacks'] = (ctx.last_mvdr_online_fallbacks(), ctx.last_cacgmm_online_fallbacks())
+    return samples, details
+
+
+def masks_from_posteriors(posterior, target_index, *, ctx=None):
+    """Target and distortion mask from the posteriors with no frames zeroed
+    (gss_masks_from_posteriors, drop_context = 0): posterior (K,T,F) -> (X_mask, N_mask) (T,F),
+    the target's row and the sum of the others -- the masks of a stream, which has no context."""
+    g = np.asarray(posterior, dtype=np.float64)
+    if g.ndim != 3:
+        raise ValueError(f'posterior: shape {g.shape} is not (K,T,F)')
+    K, T, F = g.shape
+    if not _is_integer(target_index) or not 0 <= target_index < K:
+        raise ValueError(f'target_index={target_index!r}: an integer in [0, {K})')
+    if T == 0 or F == 0:
+        return np.zeros((T, F)), np.zeros((T, F))
+    ctx = ctx or default_context()
+    g_d = ctx.to_device(g.transpose(2, 0, 1))                       # (F,K,T)
+    bufs = [ctx.empty(8 * F * T) for _ in range(2)]
+    ctx._check(ctx.lib.gss_masks_from_posteriors(
+        ctx.handle, c_void_p(g_d.ptr), F, K, T, int(target_index), 0, 0, 0,
+        *(c_void_p(b.ptr) for b in bufs)), 'gss_masks_from_posteriors')
+    return tuple(np.ascontiguousarray(ctx.to_host(b, (F, T), np.float64).T) for b in bufs)

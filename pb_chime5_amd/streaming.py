@@ -1,0 +1,261 @@
+"""Samples in, samples out, in blocks of any length: the three online stages (online WPE, online
+CACGMM, online MVDR) between the two ends of a stream, every state carried from block to block.
+
+A stream is the offline path with ``stft_fading=True`` cut at arbitrary sample positions
+(include/gss_hip.h, "sample-block stream"): after M samples floor(M / shift) frames exist and
+max(0, floor(M / shift) * shift - (size - shift)) samples have come out, so the algorithmic
+latency is below one window.  Whatever the cuts, the samples, the taps and the final states have
+the bits of the stream fed as one block.  A stream has no utterance context: no frames are zeroed
+in the masks, and the beamformer's reference channel is fixed by the caller.
+"""
+import numpy as np
+
+from . import ops
+from ._capi import default_context
+from .cacgmm import CACGMM
+
+
+class StreamingEnhancer:
+    """One target of one stream.
+
+    ``num_channels`` and ``num_classes`` (the rows of the activity handed to `process`), or
+    ``model=`` a fitted `cacgmm.CACGMM`: the mixture model continues from it (mass
+    ``gss_prior_mass``) and the stream is unguided -- `process` takes no activity.  ``target``:
+    the class to extract; ``ref_channel``: the beamformer's reference channel.  ``wpe_arrays`` =
+    A > 1: the online WPE per array of num_channels / A consecutive channels.  ``fused=False``
+    runs every block through the stage operators of `ops` in the place of the one library call;
+    the bits are the same.  ``speakers``: the names of the classes in activity order, for an
+    activity handed to `process` as a dict.  Nothing touches the GPU before the first block.
+    """
+
+    def __init__(self, num_channels=None, num_classes=None, *, model=None, target=0, ref_channel=0,
+                 stft_size=1024, stft_shift=256, window=None, wpe=True, wpe_taps=10, wpe_delay=2,
+                 wpe_alpha=ops.WPE_ONLINE_ALPHA, wpe_arrays=1,
+                 gss_forget=ops.GSS_ONLINE_FORGET, gss_prior_mass=ops.GSS_ONLINE_PRIOR_MASS,
+                 bf_forget=ops.BF_ONLINE_FORGET, bf_loading=ops.BF_ONLINE_LOADING,
+                 postfilter=None, fused=True, speakers=None, ctx=None):
+        if model is not None:
+            if not isinstance(model, CACGMM):
+                raise ValueError(f'model: a CACGMM, not {type(model).__name__}')
+            F, K, D = model.shape
+            if F != stft_size // 2 + 1:
+                raise ValueError(f'model: {F} frequencies, stft_size={stft_size} has '
+                                 f'{stft_size // 2 + 1}')
+            for name, given, has in (('num_channels', num_channels, D),
+                                     ('num_classes', num_classes, K)):
+                if given is not None and given != has:
+                    raise ValueError(f'{name}={given!r} but the model has {has}')
+            num_channels, num_classes = D, K
+        for name, value in (('num_channels', num_channels), ('num_classes', num_classes)):
+            if value is None:
+                raise ValueError(f'{name}: needed without a model')
+        if not ops._is_integer(num_classes) or num_classes < 1:
+            raise ValueError(f'num_classes={num_classes!r}: a positive integer')
+        D, _, size, shift = ops.check_stream(num_channels, 0, stft_size, stft_shift)
+        K = int(num_classes)
+        if not ops._is_integer(target) or not 0 <= target < K:
+            raise ValueError(f'target={target!r}: an integer in [0, {K})')
+        if fused is not True and fused is not False:
+            raise ValueError(f'fused={fused!r}: True or False')
+        if wpe is not True and wpe is not False:
+            raise ValueError(f'wpe={wpe!r}: True or False')
+        self.wpe_arrays, self.wpe_channels = 1, D
+        if wpe:
+            self.wpe_arrays, self.wpe_channels = ops.check_wpe_online(wpe_taps, wpe_delay, wpe_alpha,
+                                                                      D, wpe_arrays)
+        self.gss_forget, self.gss_prior_mass = ops.check_gss_online(gss_forget, gss_prior_mass, K, D)
+        self.bf_forget, self.bf_loading, self.ref_channel = ops.check_bf_online(
+            bf_forget, bf_loading, ref_channel, D)
+        if self.ref_channel < 0:
+            raise ValueError(f'ref_channel={ref_channel!r}: a stream has no window to choose a '
+                             f'channel over, an integer in [0, {D})')
+        self.params = ops.make_params(
+            stft_size=size, stft_shift=shift, stft_fading=True, wpe=wpe, wpe_taps=wpe_taps,
+            wpe_delay=wpe_delay, bf='mvdrSouden_ban', postfilter=postfilter,
+            wpe_arrays=self.wpe_arrays if wpe else 0)
+        self.D, self.K, self.F, self.size, self.shift = D, K, size // 2 + 1, size, shift
+        self.target, self.wpe, self.wpe_taps, self.wpe_delay = int(target), wpe, wpe_taps, wpe_delay
+        self.wpe_alpha, self.postfilter, self.fused = float(wpe_alpha), postfilter, fused
+        self.model, self.window = model, window
+        self.guided = model is None
+        if speakers is not None:
+            speakers = list(speakers)
+            if len(speakers) != K or len(set(speakers)) != K:
+                raise ValueError(f'speakers={speakers!r}: {K} different names')
+        self.speakers = speakers
+        self.ctx = ctx
+        self.reset()
+
+    # ------------------------------------------------------------------ state
+    def reset(self):
+        """Back to the start of a stream: fresh states (the mixture model from ``model`` again),
+        the counters and the fallback counts at zero."""
+        self.stream = self.wpe_state = self.em_state = self.bf_state = None
+        self.samples_in = self.samples_out = 0
+        self.fallbacks = {'mvdr': 0, 'cacgmm': 0}
+        self.flushed = False
+
+    def _states(self):
+        """The four states, made on the GPU when the first block (or a checkpoint) needs them."""
+        if self.stream is not None:
+            return
+        self.ctx = self.ctx or default_context()
+        ctx, F, D, K = self.ctx, self.F, self.D, self.K
+        self.stream = ops.StreamState.fresh(D, K if self.guided else 0, self.size, self.shift,
+                                            window=self.window, ctx=ctx)
+        self.wpe_state = (ops.OnlineWPEState.fresh(F, self.wpe_arrays, self.wpe_channels,
+                                                   self.wpe_taps, self.wpe_delay, ctx=ctx)
+                          if self.wpe else None)
+        self.em_state = (ops.OnlineCACGMMState.fresh(F, K, D, self.gss_prior_mass, ctx=ctx)
+                         if self.guided else
+                         ops.OnlineCACGMMState.from_model(self.model, self.gss_prior_mass, ctx=ctx))
+        # (no frames: a stream has none yet, p_f = 1)
+        self.bf_state = ops.OnlineMVDRState.fresh(F, D, self.bf_loading, ctx=ctx)
+
+    @property
+    def latency_samples(self):
+        """Samples that went in and have not come out: size - shift + (samples_in mod shift)."""
+        return self.samples_in - self.samples_out
+
+    def to_host(self):
+        """A checkpoint of the stream: the four states (`from_host` restores them, in any
+        context) and the counters."""
+        self._states()
+        return {'stream': self.stream.to_host(), 'em': self.em_state.to_host(),
+                'bf': self.bf_state.to_host(),
+                'wpe': self.wpe_state.to_host() if self.wpe else None,
+                'samples_in': self.samples_in, 'samples_out': self.samples_out,
+                'fallbacks': dict(self.fallbacks), 'flushed': self.flushed}
+
+    def from_host(self, host):
+        """Continue from a checkpoint of `to_host` (of a stream with this one's settings).
+        ValueError when its shapes are another stream's."""
+        self._states()
+        ctx = self.ctx
+        stream = ops.StreamState.from_host(host['stream'], ctx=ctx)
+        em = ops.OnlineCACGMMState.from_host(host['em'], ctx=ctx)
+        bf = ops.OnlineMVDRState.from_host(host['bf'], ctx=ctx)
+        if (host['wpe'] is not None) != self.wpe:
+            raise ValueError('checkpoint: its WPE state and wpe=%r disagree' % self.wpe)
+        wpe = ops.OnlineWPEState.from_host(host['wpe'], ctx=ctx) if self.wpe else None
+        for name, state, key in (
+                ('stream', stream, self.stream.key), ('em', em, self.em_state.key),
+                ('bf', bf, self.bf_state.key),
+                ('wpe', wpe, self.wpe_state.key if self.wpe else None)):
+            if state is not None and state.key != key:
+                raise ValueError(f'checkpoint: {name} state built for ({state._sizes}) = '
+                                 f'{state.key}, this stream has {key}')
+        self.stream, self.em_state, self.bf_state, self.wpe_state = stream, em, bf, wpe
+        self.samples_in, self.samples_out = int(host['samples_in']), int(host['samples_out'])
+        self.fallbacks = dict(host['fallbacks'])
+        self.flushed = bool(host['flushed'])
+        return self
+
+    # ------------------------------------------------------------------ blocks
+    def _activity(self, activity, n):
+        if not self.guided:
+            if activity is not None:
+                raise ValueError('activity: the stream continues a model and takes none')
+            return None
+        if activity is None:
+            raise ValueError('activity: missing -- a stream started fresh has identical classes '
+                             'and only the activity tells them apart (or start from model=)')
+        if isinstance(activity, dict):
+            if self.speakers is None:
+                raise ValueError('activity: a dict needs the stream\'s speakers= names')
+            if set(activity) != set(self.speakers):
+                raise ValueError(f'activity: tracks of {sorted(activity)}, the stream has '
+                                 f'{sorted(self.speakers)}')
+            tracks = [np.asarray(activity[name]) for name in self.speakers]
+            for name, track in zip(self.speakers, tracks):
+                if track.shape != (n,):
+                    raise ValueError(f'activity[{name!r}]: shape {track.shape} is not (n,) = ({n},)')
+            activity = np.stack(tracks)
+        activity = np.asarray(activity)
+        if activity.shape != (self.K, n):
+            raise ValueError(f'activity: shape {activity.shape} is not (K,n) = ({self.K},{n})')
+        return activity != 0
+
+    def process(self, block, activity=None, debug=False):
+        """The next ``block`` (D,n) of samples, float64 or int16 PCM, with its ``activity`` (K,n)
+        (or a dict of K per-sample tracks in class order) -> the samples the block finishes,
+        (m,) float64; with ``debug`` (samples, details) with the taps over the block's frames
+        (None when the block completes no frame)."""
+        if self.flushed:
+            raise RuntimeError('process after flush: the stream has ended, call reset()')
+        block = np.asarray(block)
+        if block.ndim != 2 or block.shape[0] != self.D:
+            raise ValueError(f'block: shape {block.shape} is not (D,n) = ({self.D},n)')
+        samples, details = self._block(block, self._activity(activity, block.shape[1]), debug)
+        self.samples_in += block.shape[1]
+        self.samples_out += len(samples)
+        return (samples, details) if debug else samples
+
+    def flush(self, debug=False):
+        """End the stream: the zeros that complete its last frames go in (inactive), the rest
+        comes out, cut so that samples_out == samples_in.  `process` is an error afterwards
+        until `reset`."""
+        if self.flushed:
+            raise RuntimeError('flush after flush: the stream has ended, call reset()')
+        if self.samples_in == 0:        # nothing went in: nothing comes out
+            self.flushed = True
+            return (np.zeros(0), None) if debug else np.zeros(0)
+        n = ops.stream_flush_samples(self.samples_in, self.size, self.shift)
+        samples, details = self._block(np.zeros((self.D, n)),
+                                       np.zeros((self.K, n), bool) if self.guided else None, debug)
+        samples = samples[:self.samples_in - self.samples_out]
+        self.samples_out += len(samples)
+        self.flushed = True
+        return (samples, details) if debug else samples
+
+    def _block(self, block, activity, debug):
+        if block.shape[1] == 0:
+            return np.zeros(0), None
+        self._states()
+        Tn = ops.stream_num_frames(self.stream.received, block.shape[1], self.size, self.shift)
+        if self.fused:
+            samples, details = ops.stream_block(
+                block, activity, params=self.params, stream=self.stream, em_state=self.em_state,
+                bf_state=self.bf_state, wpe_state=self.wpe_state, target_index=self.target,
+                ref_channel=self.ref_channel, wpe_alpha=self.wpe_alpha, em_forget=self.gss_forget,
+                bf_forget=self.bf_forget, window=self.window, debug=debug)
+            if Tn > 0:
+                counts = (details['fallbacks'] if details is not None else
+                          (self.ctx.last_mvdr_online_fallbacks(),
+                           self.ctx.last_cacgmm_online_fallbacks()))
+                self.fallbacks['mvdr'] += counts[0]
+                self.fallbacks['cacgmm'] += counts[1]
+            return samples, details
+        return self._block_stages(block, activity, debug)
+
+    def _block_stages(self, block, activity, debug):
+        """The block through the stage operators, each with its explicit state."""
+        Y, act_frames = ops.stft_stream(block, activity, state=self.stream, window=self.window)
+        if Y.shape[1] == 0:
+            return np.zeros(0), None
+        Obs = Y
+        if self.wpe:
+            Obs = ops.wpe_online_dtf(Y, self.wpe_taps, self.wpe_delay, self.wpe_alpha,
+                                     arrays=self.wpe_arrays, state=self.wpe_state)
+        posterior, em_fallbacks = ops.cacgmm_posteriors_online(
+            Obs, act_frames, forget=self.gss_forget, state=self.em_state, return_fallbacks=True)
+        target_mask, distortion_mask = ops.masks_from_posteriors(posterior, self.target,
+                                                                 ctx=self.ctx)
+        X_hat, bf_fallbacks = ops.mvdr_souden_online_from_masks(
+            Obs, target_mask, distortion_mask, ban=True, forget=self.bf_forget,
+            ref_channel=self.ref_channel, state=self.bf_state, return_fallbacks=True)
+        if self.postfilter == 'mask_mul':
+            # (re * m, im * m as the library's postfilter, not a complex product)
+            X_hat = (X_hat.view(np.float64).reshape(X_hat.shape + (2,))
+                     * target_mask[..., None]).reshape(X_hat.shape[0], -1).view(np.complex128)
+        samples = ops.istft_stream(X_hat, state=self.stream, window=self.window)
+        self.fallbacks['mvdr'] += bf_fallbacks
+        self.fallbacks['cacgmm'] += em_fallbacks
+        details = None
+        if debug:
+            details = {'Obs': Obs, 'posterior': posterior, 'target_mask': target_mask,
+                       'distortion_mask': distortion_mask, 'X_hat': X_hat,
+                       'ref_channel': self.ref_channel, 'fallbacks': (bf_fallbacks, em_fallbacks)}
+            if act_frames is not None:
+                details['acitivity_freq'] = act_frames
+        return samples, details

@@ -1,0 +1,311 @@
+"""NumPy reference of the sample-block stream: the two ends of a stream --
+the carried history, block-wise `oracle.stft`, the frame activity with history, the overlap-add in
+ascending frame order onto a carried tail, the flush -- and the stream composed with the references
+of the three online stages, plus the scenes and partitions the CPU and the GPU tests share.  Every
+reference run is computed once per session and shared, read-only."""
+import functools
+
+import numpy as np
+
+import gss_oracle as oracle
+import online_cacgmm_reference as cr
+import online_mvdr_reference as mref
+import online_wpe_reference as wref
+
+TOL = 1e-10                 # gamma, X_hat and the final states, relative to the largest magnitude
+X_TOL = 1e-4                # |x_hat| against the composed oracle: the pipeline bar
+ISTFT_TOL = 1e-12           # the bar of test_istft_matches_oracle
+STABILITY_MARGIN = 100.0    # the reference itself must move at least this much less than a bar
+
+# the settings of every cell (choices, as in the stages' own pipeline tests)
+SETTINGS = dict(wpe_alpha=0.999, gss_forget=0.99, gss_prior_mass=1.0, bf_forget=0.99,
+                bf_loading=1e-2, ref_channel=0, target=0)
+
+# (W, H, D, A, taps, delay, K, N, wpe)
+CELLS = {
+    'a': (64, 16, 4, 1, 2, 1, 3, 1500, True),       # baseline
+    'b': (64, 16, 5, 1, 2, 1, 2, 700, True),        # odd D: a half-empty channel pair in the STFT
+    'c': (64, 16, 8, 2, 2, 1, 3, 900, True),        # per-array WPE
+    'd': (64, 16, 8, 1, 10, 2, 3, 900, True),       # taps C = 80 > 64: the WPE state in HBM
+    'e': (48, 12, 4, 1, 2, 1, 3, 600, True),        # the direct-DFT kernels
+    'f': (64, 16, 24, 6, 2, 1, 5, 800, True),       # NR = 3 in the CACGMM and MVDR sweeps
+    'g': (1024, 256, 4, 1, 2, 2, 3, 12000, True),   # synthetic.tiny
+    'h': (64, 16, 4, 1, 2, 1, 3, 1500, False),      # no WPE stage
+}
+# The first seed of range(8) at which gamma, X_hat and the final states of the composed reference
+# move at least STABILITY_MARGIN x less than TOL, and |x_hat| that much less than X_TOL, when every
+# sample moves in its last bit (`python tests/stream_reference.py` re-derives the table).
+SEEDS = {}
+
+
+def seed_of(name):
+    return SEEDS.get(name, 0)
+
+
+# ------------------------------------------------------------------ geometry (section 1 of the issue)
+def num_frames(received, n, size, shift):
+    return (received + n) // shift - received // shift
+
+
+def emitted(received, size, shift):
+    return max(0, received // shift * shift - (size - shift))
+
+
+def num_samples_out(received, n, size, shift):
+    return emitted(received + n, size, shift) - emitted(received, size, shift)
+
+
+def flush_samples(received, size, shift):
+    return oracle.stft_frames(received, size, shift, fading=True) * shift - received
+
+
+# ------------------------------------------------------------------ the two ends
+class RefStream:
+    """The analysis and the synthesis end of a stream with their carried state."""
+
+    def __init__(self, D, K, size, shift):
+        self.D, self.K, self.size, self.shift = D, K, size, shift
+        self.x_hist = np.zeros((D, size))
+        self.act_hist = np.zeros((K, size), bool)
+        self.tail = np.zeros(size - shift)
+        self.received = self.frames_out = 0
+
+    def stft(self, block, activity=None):
+        """(D,n) samples, (K,n) activity -> Y (D,Tn,F), frame activity (K,Tn)."""
+        W, H, M = self.size, self.shift, self.received
+        block = np.asarray(block, np.float64)
+        n = block.shape[1]
+        act = np.zeros((self.K, n), bool) if activity is None else np.asarray(activity) != 0
+        Tn = num_frames(M, n, W, H)
+        x = np.concatenate([self.x_hist, block], axis=1)        # the samples [M - W, M + n)
+        a = np.concatenate([self.act_hist, act], axis=1)
+        self.x_hist, self.act_hist, self.received = x[:, -W:], a[:, -W:], M + n
+        F = W // 2 + 1
+        if Tn == 0:
+            return np.zeros((self.D, 0, F), np.complex128), np.zeros((self.K, 0), bool)
+        lo = M // H * H - (W - H) - (M - W)                     # the first frame's first sample
+        hi = lo + (Tn - 1) * H + W
+        Y = oracle.stft(x[:, lo:hi], W, H, fading=False, pad=False)
+        actf = oracle.segment_axis(a[:, lo:hi], W, H, end='cut').any(axis=-1)
+        assert Y.shape[1] == Tn == actf.shape[1]
+        return Y, actf
+
+    def istft(self, X):
+        """(Tn,F) -> the samples these frames finish."""
+        W, H, t0 = self.size, self.shift, self.frames_out
+        Tn = X.shape[0]
+        if Tn == 0:
+            return np.zeros(0)
+        syn = oracle.biorthogonal_window(oracle.blackman_periodic(W), H)
+        frames = syn * np.fft.irfft(X, n=W, axis=-1)[..., :W]
+        acc = np.zeros(Tn * H + W - H)
+        acc[:W - H] = self.tail                                  # the partial sums, started from 0.0
+        for t in range(Tn):
+            acc[t * H:t * H + W] += frames[t]
+        self.tail, self.frames_out = acc[Tn * H:].copy(), t0 + Tn
+        drop = max(0, (W - H) - t0 * H)                          # the leading fading pad, once
+        return acc[drop:Tn * H].copy() if drop < Tn * H else np.zeros(0)
+
+
+def blocks_of(N, cuts):
+    """Block lengths -> (begin, end) pairs covering [0, N)."""
+    bounds = np.concatenate([[0], np.cumsum(cuts)])
+    assert bounds[-1] == N, (bounds[-1], N)
+    return list(zip(bounds[:-1], bounds[1:]))
+
+
+def random_cuts(N, seed, pieces=7):
+    rng = np.random.default_rng([seed, N])
+    marks = np.sort(rng.integers(0, N + 1, pieces - 1))
+    return tuple(int(v) for v in np.diff(np.concatenate([[0], marks, [N]])))
+
+
+def partitions(name):
+    """The partitions of a cell's N samples: one block, the border cases, seeded random cuts (and
+    for cell a one frame per call)."""
+    W, H, D, A, taps, delay, K, N, wpe = CELLS[name]
+    head = (1, H - 1, H, H + 1, 0, W - 1, W)
+    out = {'one': (N,), 'borders': head + (N - sum(head),), 'random': random_cuts(N, 3)}
+    if name == 'a':
+        out['hops'] = (H,) * (N // H) + ((N % H,) if N % H else ())
+    return out
+
+
+def stream_stft(x, activity, size, shift, cuts):
+    """x (D,N), activity (K,N) in blocks of ``cuts`` and flushed -> Y (D,T,F), frame activity
+    (K,T)."""
+    D, N = x.shape
+    st = RefStream(D, activity.shape[0], size, shift)
+    Ys, As = [], []
+    for a, b in blocks_of(N, cuts):
+        Y, f = st.stft(x[:, a:b], activity[:, a:b])
+        Ys.append(Y), As.append(f)
+    Y, f = st.stft(np.zeros((D, flush_samples(N, size, shift))))
+    Ys.append(Y), As.append(f)
+    return np.concatenate(Ys, axis=1), np.concatenate(As, axis=1)
+
+
+def stream_istft(X, N, size, shift, frame_cuts):
+    """X (T,F) in runs of ``frame_cuts`` frames -> the N samples of the flushed stream."""
+    st = RefStream(1, 0, size, shift)
+    st.received = X.shape[0] * shift
+    out = [st.istft(X[a:b]) for a, b in blocks_of(X.shape[0], frame_cuts)]
+    return np.concatenate(out)[:N]
+
+
+# ------------------------------------------------------------------ scenes
+@functools.lru_cache(maxsize=None)
+def scene(name, seed=0):
+    """Cell g: `synthetic.tiny`.  The others, after `online_cacgmm_reference.scene` in the time
+    domain: K - 1 speakers, white noise through a random 6-tap filter per channel, each on in
+    random turns of 8 hops (60 %), plus a last class that is always on: sensor noise of standard
+    deviation 0.3.  -> x (D,N) float64, activity (K,N) bool per sample, read-only."""
+    W, H, D, A, taps, delay, K, N, wpe = CELLS[name]
+    if name == 'g':
+        from pb_chime5_amd import synthetic
+        u = synthetic.tiny(seed=seed, num_channels=D, num_samples=N)
+        x = np.array(u.obs, np.float64)
+        activity = np.asarray(u.activity_array)[:, :N] != 0
+        assert x.shape == (D, N) and activity.shape == (K, N), (x.shape, activity.shape)
+    else:
+        rng = np.random.default_rng([seed, W, D, K, N])
+        x = 0.3 * rng.standard_normal((D, N))
+        activity = np.ones((K, N), bool)
+        for k in range(K - 1):
+            on = np.repeat(rng.random(-(-N // (8 * H))) < 0.6, 8 * H)[:N]
+            src = rng.standard_normal(N) * on
+            fir = rng.standard_normal((D, 6))
+            x += np.stack([np.convolve(src, h)[:N] for h in fir])
+            activity[k] = on
+    x.setflags(write=False)
+    activity.setflags(write=False)
+    return x, activity
+
+
+# ------------------------------------------------------------------ the composition
+def fresh_states(name):
+    W, H, D, A, taps, delay, K, N, wpe = CELLS[name]
+    F, s = W // 2 + 1, SETTINGS
+    return dict(wpe=wref.fresh_state(F, A, D // A, taps, delay) if wpe else None,
+                em=cr.fresh_state(F, K, D, s['gss_prior_mass']),
+                bf=mref.fresh_state(F, D, s['bf_loading']))
+
+
+def stages(name, Y, actf, states, em_mask=True):
+    """Frames Y (D,T,F) with their activity (K,T) through the references of the three online
+    stages from ``states`` (not modified) -> taps (Obs (F,T,D), gamma (F,K,T), the masks (F,T),
+    X_hat (T,F), fallbacks) and the states afterwards."""
+    W, H, D, A, taps, delay, K, N, wpe = CELLS[name]
+    s = SETTINGS
+    X = Y.transpose(2, 1, 0)
+    new = dict(wpe=None)
+    if wpe:
+        X, new['wpe'] = wref.online_wpe(X, taps, delay, s['wpe_alpha'], arrays=A, state=states['wpe'])
+    gamma, new['em'], fb_em = cr.online_cacgmm(X, actf if em_mask else None, s['gss_forget'],
+                                               states['em'])
+    mx = gamma[:, s['target']]
+    mn = np.zeros_like(mx)
+    for k in range(gamma.shape[1]):
+        if k != s['target']:
+            mn = mn + gamma[:, k]
+    Xhat, _, new['bf'], fb_bf = mref.online_mvdr(X, mx, mn, s['bf_forget'], s['ref_channel'], True,
+                                                 state=states['bf'])
+    taps_ = dict(Obs=X, gamma=gamma, target_mask=mx, distortion_mask=mn,
+                 X_hat=np.ascontiguousarray(Xhat.T), fallbacks=(fb_bf, fb_em))
+    return taps_, new
+
+
+def compose_whole(name, x, activity):
+    """The references on the whole signal: `oracle.stft`, the stages once, `oracle.istft`."""
+    W, H = CELLS[name][:2]
+    N = x.shape[1]
+    Y = oracle.stft(x, W, H, fading=True)
+    actf = oracle.activity_time_to_frequency(activity, W, H, True)[:, :Y.shape[1]]
+    taps, states = stages(name, Y, actf, fresh_states(name))
+    return oracle.istft(taps['X_hat'], W, H, fading=True)[:N], taps, states
+
+
+def compose_stream(name, x, activity, cuts):
+    """The same in blocks of ``cuts`` samples with every state carried, flushed."""
+    W, H, D = CELLS[name][:3]
+    N = x.shape[1]
+    st = RefStream(D, activity.shape[0], W, H)
+    states = fresh_states(name)
+    out, all_taps = [], []
+    feed = [(x[:, a:b], activity[:, a:b]) for a, b in blocks_of(N, cuts)]
+    feed.append((np.zeros((D, flush_samples(N, W, H))), None))
+    for blk, act in feed:
+        Y, actf = st.stft(blk, act)
+        if Y.shape[1] == 0:
+            continue
+        taps, states = stages(name, Y, actf, states)
+        out.append(st.istft(taps['X_hat']))
+        all_taps.append(taps)
+    axis = dict(Obs=1, gamma=2, target_mask=1, distortion_mask=1, X_hat=0)
+    taps = {k: np.concatenate([t[k] for t in all_taps], axis=a) for k, a in axis.items()}
+    taps['fallbacks'] = tuple(sum(t['fallbacks'][i] for t in all_taps) for i in range(2))
+    return np.concatenate(out)[:N], taps, states
+
+
+def _freeze(value):
+    if isinstance(value, dict):
+        for v in value.values():
+            _freeze(v)
+    elif isinstance(value, np.ndarray):
+        value.setflags(write=False)
+    return value
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, seed=0):
+    """x_hat (N,), the taps and the final states of the cell's scene, composed on the whole
+    signal."""
+    x, activity = scene(name, seed)
+    return _freeze(compose_whole(name, x, activity))
+
+
+def rel_err(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    scale = float(np.max(np.abs(b))) if b.size else 0.0
+    return float(np.max(np.abs(a - b))) / scale if scale else float(np.max(np.abs(a), initial=0.0))
+
+
+def abs_rel_err(a, b):
+    return float(np.max(np.abs(np.abs(a) - np.abs(b))) / np.max(np.abs(b)))
+
+
+def state_arrays(states):
+    """{'wpe.P': array, ...} of the states that exist."""
+    return {f'{stage}.{k}': v for stage, st in states.items() if st is not None
+            for k, v in st.items()}
+
+
+def reference_movement(name, seed=0):
+    """How far the composed reference moves under a last-bit change of every sample: (the largest
+    relative movement of gamma, X_hat and the final states, the movement of |x_hat|)."""
+    x, activity = scene(name, seed)
+    xh, taps, states = reference(name, seed)
+    xb, tb, sb = compose_whole(name, cr.last_bit(x, np.random.default_rng(12345)), activity)
+    a, b = state_arrays(states), state_arrays(sb)
+    moved = max([rel_err(tb['gamma'], taps['gamma']), rel_err(tb['X_hat'], taps['X_hat'])]
+                + [rel_err(b[k], a[k]) for k in a])
+    return moved, abs_rel_err(xb, xh)
+
+
+def is_stable(name, seed):
+    moved, x_moved = reference_movement(name, seed)
+    return moved * STABILITY_MARGIN <= TOL and x_moved * STABILITY_MARGIN <= X_TOL
+
+
+def choose_seed(name, seeds=range(8)):
+    for seed in seeds:
+        if is_stable(name, seed):
+            return seed
+    raise AssertionError(f'no stable scene for cell {name}')
+
+
+if __name__ == '__main__':
+    for name in CELLS:
+        seed = choose_seed(name)
+        moved, x_moved = reference_movement(name, seed)
+        print(f"    '{name}': {seed},   # moves {moved:.1e}, |x_hat| {x_moved:.1e}")
