@@ -10,6 +10,16 @@
 //   OUTPUT gamma[f,k,t]                 -- the model of the frames before t: causal
 //   ||y|| == 0: the state stays as it is; else with g_k = clip(gamma_k, 1e-10, 1 - 1e-10)
 //   S_k <- beta S_k + g_k D z z^H / max(q_k, 10 tiny),   n_k <- beta n_k + g_k
+//   the rank guard: with d = max(0, max_i (S_k)_ii) of the updated S_k and p the smallest pivot
+//             of the frame's factorisation, every (S_k)_ii += (1 - beta) COL_RANK_EPS d phi,
+//             phi = exp(-p / (COL_RANK_GATE d))  (0 below exp(-745), without a factor, at d = 0)
+//             (a class that wins almost no frame has an effective frame count below D and S_k
+//              loses rank: the gate is exactly 0 on a well-conditioned class and rises smoothly
+//              to 1 as p / d falls to COL_RANK_GATE, which keeps cond(S_k) near 1e11 at worst)
+//   the scale pin: when the binary exponent e of the largest diagonal entry, d + its guard, is
+//             outside [-COL_SCALE_BAND, COL_SCALE_BAND]: S_k <- 2^-e S_k (n_k stays: only
+//             ln det B_k + D ln q_k enters gamma, and that does not see the scale of S_k)
+//   Both are functions of the state and the frame alone; a maximum and a power of two are exact.
 // One persistent workgroup per frequency walks the frames, one wave per class.  Wave k keeps the
 // upper triangle of S_k in registers for the whole call, on the 8 x 8 lane grid of
 // chol_inverse_sweep (dense_wave.h): per frame it copies the registers, runs the sweep (U and
@@ -25,6 +35,29 @@
 #include "dense_wave.h"
 
 namespace {
+
+// The method's constants (tests/online_cacgmm_reference.py has the same).
+// Band: the exponents the parity cells, the stream cells and the pipeline scene reach without
+// the pin lie in [-34, 11].
+constexpr double COL_RANK_EPS = 1e-10;
+constexpr double COL_RANK_GATE = 1e-9;
+constexpr int COL_SCALE_BAND = 64;
+
+// The largest of 64 values that are all >= 0, on the DPP network in wave_sum's pattern (0, which
+// a lane outside a shift or a mask reads, is the identity); exact, so the same in any order.
+__device__ __forceinline__ double wave_max_nonneg(double v) {
+    double s = fmax(v, dpp_shifted<0x111, 0xf, 0xf>(v));     // row_shr:1
+    s = fmax(s, dpp_shifted<0x112, 0xf, 0xf>(v));            // row_shr:2
+    s = fmax(s, dpp_shifted<0x113, 0xf, 0xf>(v));            // row_shr:3
+    s = fmax(s, dpp_shifted<0x114, 0xf, 0xe>(s));            // row_shr:4, banks 1-3
+    s = fmax(s, dpp_shifted<0x118, 0xf, 0xc>(s));            // row_shr:8, banks 2-3
+    s = fmax(s, dpp_shifted<0x142, 0xa, 0xf>(s));            // row_bcast:15 into rows 1, 3
+    s = fmax(s, dpp_shifted<0x143, 0xc, 0xf>(s));            // row_bcast:31 into rows 2, 3
+    const unsigned long long u = __double_as_longlong(s);
+    const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)u, 63);
+    const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(u >> 32), 63);
+    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
 
 struct ColArgs {
     const cplx *Y;              // (F, T, D)
@@ -81,6 +114,7 @@ __global__ __launch_bounds__(512) void cacgmm_online_kernel(ColArgs a) {
     cplx *Sg = a.S + ((int64_t)f * K + k) * D * D;
     double *gam = a.gamma + (int64_t)f * K * T;
     const double beta = a.beta, Dd = (double)D;
+    const double guard = (1.0 - beta) * COL_RANK_EPS;
 
     cplx reg[NR][NR];
     col_load<NR>(Sg, reg, D, tx, ty);
@@ -107,7 +141,7 @@ __global__ __launch_bounds__(512) void cacgmm_online_kernel(ColArgs a) {
             for (int bi = 0; bi < NR; ++bi) tmp[ai][bi] = reg[ai][bi];
         wave_sync();
         const bool ok = chol_inverse_sweep<8, NR, true>(tmp, D, M, ld, dinv, tx, ty);
-        double q, l;
+        double q, l, pivot = 0.0;   // the smallest pivot, from the largest 1 / U_jj
         if (ok) {   // decided by the pivots alone, the same in every lane
             // M: row i holds W[i][j] / dinv[i] for j < i, the pivot at j = i;  W[i][i] = dinv[i]
             double r = 0.0, lg = 0.0;
@@ -119,6 +153,8 @@ __global__ __launch_bounds__(512) void cacgmm_online_kernel(ColArgs a) {
                 lg = log(M[lane * ld + lane].x);
             }
             q = fmax(n * wave_sum(r), GSS_TINY);
+            const double umax = wave_max_nonneg(row ? dinv[lane] : 0.0);
+            pivot = 1.0 / (umax * umax);
             l = wave_sum(lg) - Dd * log(n);
         } else {
             ++nfall;
@@ -161,6 +197,34 @@ __global__ __launch_bounds__(512) void cacgmm_online_kernel(ColArgs a) {
                     }
                 }
             n = fma(beta, n, g);
+            // the rank guard and the scale pin, from the largest diagonal entry (lanes tx == ty)
+            double d = 0.0;     // (a state without a positive diagonal entry gets no guard)
+#pragma unroll
+            for (int ai = 0; ai < NR; ++ai)
+                if (tx == ty && ty + 8 * ai < D) d = fmax(d, reg[ai][ai].x);
+            d = wave_max_nonneg(d);
+            double phi = 0.0;
+            if (ok && d > 0.0) {    // the same in every lane
+                const double x = pivot / (COL_RANK_GATE * d);
+                if (x < 745.0) phi = exp(-x);
+            }
+            const double add = guard * d * phi;
+#pragma unroll
+            for (int ai = 0; ai < NR; ++ai)
+                if (tx == ty && ty + 8 * ai < D) reg[ai][ai].x += add;
+            const double dtop = d + add;     // the bits of the largest entry after the guard
+            const int ef = (int)((__double_as_longlong(dtop) >> 52) & 0x7ff);
+            if (dtop > 0.0 && ef != 0 && ef != 0x7ff) {     // normal and finite
+                const int e = ef - 1022;                   // frexp's exponent
+                if (e > COL_SCALE_BAND || e < -COL_SCALE_BAND) {
+                    const double sc = ldexp(1.0, -min(max(e, -1000), 1000));
+#pragma unroll
+                    for (int ai = 0; ai < NR; ++ai)
+#pragma unroll
+                        for (int bi = ai; bi < NR; ++bi)
+                            reg[ai][bi] = c_make(reg[ai][bi].x * sc, reg[ai][bi].y * sc);
+                }
+            }
         }
         wave_sync();    // zb and M are rewritten by the next frame
     }

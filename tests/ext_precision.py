@@ -273,3 +273,70 @@ def em_yardstick(obs_f, activity, iterations, iterations_post, oracle_posteriors
                                          iterations_post=iterations_post)[..., 0]
         d = max(d, float(np.max(np.abs(moved - oracle_posteriors))))
     return d
+
+
+# ---------------------------------------------------------------- online CACGMM
+def online_cacgmm(Y, mask, beta, prior_mass, rank_eps, rank_gate, gate_cut, band):
+    """The guarded and pinned frame recursion of tests/online_cacgmm_reference.py (online_cacgmm,
+    guard_and_pin) from a fresh state in 80-bit extended precision, with its own Cholesky
+    factorisation and forward substitution: Y (F,T,D) complex128, mask (K,T) bool -> gamma
+    (F,K,T) float64 and the number of failed factorisations.  The referee for the starved-class
+    cell, where cond(S_k) x eps_float64 is 1e-5 and two float64 programs cannot be held to each
+    other."""
+    tiny = LD(np.finfo(np.float64).tiny)
+    Y = np.asarray(Y)
+    F, T, D = Y.shape
+    mask = np.asarray(mask, bool)
+    K = mask.shape[0]
+    y = Y.astype(CLD)
+    nrm = np.sqrt(np.sum(y.real ** 2 + y.imag ** 2, axis=-1))
+    Z = y / np.maximum(nrm, tiny)[..., None]
+    S = np.zeros((F, K, D, D), CLD)
+    S[..., np.arange(D), np.arange(D)] = LD(prior_mass)
+    n = np.full((F, K), LD(prior_mass))
+    beta, Dl = LD(beta), LD(D)
+    guard = (1 - beta) * LD(rank_eps)
+    gamma = np.zeros((F, K, T))
+    failed = 0
+    for t in range(T):
+        z = Z[:, t]                                                        # (F,D)
+        # S = L L^H and x = L^-1 z, column by column, for all (f, k) at once
+        L = np.zeros_like(S)
+        x = np.zeros((F, K, D), CLD)
+        logdet = np.zeros((F, K), LD)
+        ok = np.ones((F, K), bool)
+        pivot = np.full((F, K), LD(np.inf))
+        for j in range(D):
+            d2 = S[..., j, j].real - np.sum(np.abs(L[..., j, :j]) ** 2, axis=-1)
+            ok &= d2 > 0
+            pivot = np.minimum(pivot, d2)
+            d = np.sqrt(np.where(d2 > 0, d2, LD(1)))
+            L[..., j, j] = d
+            L[..., j + 1:, j] = (S[..., j + 1:, j] - np.einsum('fkij,fkj->fki', L[..., j + 1:, :j],
+                                                               L[..., j, :j].conj())) / d[..., None]
+            x[..., j] = (z[:, None, j] - np.sum(L[..., j, :j] * x[..., :j], axis=-1)) / d
+            logdet += 2 * np.log(d)
+        failed += int(np.sum(~ok))
+        unit = np.sum(np.abs(z) ** 2, axis=-1)[:, None]
+        q = np.maximum(np.where(ok, n * np.sum(np.abs(x) ** 2, axis=-1), unit), tiny)
+        lp = -Dl * np.log(q) - np.where(ok, logdet - Dl * np.log(n), LD(0))
+        aff = np.exp(lp - lp.max(axis=-1, keepdims=True)) * (n / n.sum(axis=-1, keepdims=True))
+        aff = aff * mask[None, :, t]
+        aff = aff / np.maximum(aff.sum(axis=-1, keepdims=True), tiny)
+        gamma[:, :, t] = aff.astype(np.float64)
+        g = np.clip(aff, LD(1e-10), 1 - LD(1e-10))
+        c = g * Dl / np.maximum(q, 10 * tiny)
+        Sn = beta * S + c[..., None, None] * (z[:, None, :, None] * z.conj()[:, None, None, :])
+        diag = np.maximum(np.max(Sn[..., np.arange(D), np.arange(D)].real, axis=-1), LD(0))
+        x = pivot / (LD(rank_gate) * np.where(diag > 0, diag, LD(1)))
+        phi = np.where(ok & (diag > 0) & (x < gate_cut), np.exp(-np.minimum(x, LD(gate_cut))), LD(0))
+        add = guard * diag * phi
+        Sn[..., np.arange(D), np.arange(D)] += add[..., None]
+        top = diag + add
+        e = np.frexp(top)[1]
+        hit = (top >= tiny) & (np.abs(e) > band)
+        Sn = np.where(hit[..., None, None], np.ldexp(LD(1), -np.clip(e, -1000, 1000))[..., None, None] * Sn, Sn)
+        live = (nrm[:, t] != 0)
+        S = np.where(live[:, None, None, None], Sn, S)
+        n = np.where(live[:, None], beta * n + g, n)
+    return gamma, failed

@@ -1,8 +1,10 @@
 """NumPy reference of the online CACGMM (gss_cacgmm_online): the frame recursion as DESIGN.md
 section 25 writes it -- the recursive EM of the complex angular central Gaussian mixture on
 exponentially forgetting running sums, float64, np.linalg.cholesky for the factor and
-np.linalg.solve for the quadratic form --, the closed form of the sums, and the scenes the CPU and
-the GPU tests share.  Every reference run is computed once per session and shared, read-only."""
+np.linalg.solve for the quadratic form, with the rank guard and the scale pin of section 26 (and
+without them under ``plain=True``: the recursion as it was, kept to prove that the starved cell
+bites) --, the closed form of the sums, and the scenes the CPU and the GPU tests share.  Every
+reference run is computed once per session and shared, read-only."""
 import functools
 
 import numpy as np
@@ -16,6 +18,21 @@ CLOSED_FORM_TOL = 1e-9
 ROUND_TRIP_TOL = 1e-9       # from_model(to_model()) against the state
 AFF_EPS = 1e-10             # the fit's affiliation_eps
 X_TOL = 1e-4                # |x_hat| rel err of the end-to-end tests (tests/test_gpu_pipeline.py)
+# The method's constants (csrc/cacgmm_online.hip has the same).  After the update of a live frame,
+# with d = max(0, the largest diagonal entry of the updated S_k) and p = the smallest pivot of the
+# Cholesky factorisation the frame's E-step made of S_k (the squared diagonal of L): the rank guard
+# adds (1 - beta) RANK_EPS d phi to every diagonal entry, phi = exp(-p / (RANK_GATE d)) (0 where
+# that argument is below -745, where S_k had no factor or d = 0) -- a smooth gate that is exactly
+# 0 on every well-conditioned class and 1 on a class that has lost rank; and when the binary
+# exponent (np.frexp's) of the largest entry then lies outside [-SCALE_BAND, SCALE_BAND], S_k is
+# multiplied by the power of two that brings it to 0.
+# Exponents reached with the pin off, watched after every frame: CELLS -34 .. 10, the 64-point
+# stream cells 0 .. 11, the pipeline scene 0 .. 8 (test_the_band_is_never_reached_by_the_short_cells
+# holds the first two inside +-40); the long cells reach -39 and, at forget 0.95, -126.
+RANK_EPS = 1e-10
+RANK_GATE = 1e-9
+GATE_CUT = 745.0
+SCALE_BAND = 64
 
 
 def fresh_state(F, K, D, prior_mass):
@@ -54,8 +71,9 @@ def mask_fkt(mask, F, K, T):
     return np.broadcast_to(m, (F, K, T))
 
 
-def frame_posterior(S, n, z, m):
-    """One E-step: S (F,K,D,D), n (F,K), z (F,D) unit norm, m (F,K) -> gamma (F,K), q (F,K), ok."""
+def frame_posterior(S, n, z, m, with_pivot=False):
+    """One E-step: S (F,K,D,D), n (F,K), z (F,D) unit norm, m (F,K) -> gamma (F,K), q (F,K), ok
+    (and with ``with_pivot`` the smallest pivot of every factorisation, (F,K))."""
     D = z.shape[-1]
     L, ok = _cholesky(S)
     x = np.linalg.solve(L, np.broadcast_to(z[:, None, :, None], S.shape[:3] + (1,)))[..., 0]
@@ -70,15 +88,53 @@ def frame_posterior(S, n, z, m):
         aff = aff * pi
         aff = aff * m
         aff = aff / np.maximum(np.sum(aff, axis=-1, keepdims=True), TINY)
+    if with_pivot:
+        return aff, q, ok, np.min(np.real(np.einsum('fkdd->fkd', L)) ** 2, axis=-1)
     return aff, q, ok
 
 
-def online_cacgmm(Y, mask, beta, state, record=False):
+def max_diagonal(S):
+    """max(0, the largest diagonal entry), NaN entries passed over (fmax)."""
+    return np.fmax(np.fmax.reduce(np.real(np.einsum('...dd->...d', S)), axis=-1), 0.0)
+
+
+def scale_exponents(S):
+    """np.frexp's exponent of the largest diagonal entry of every S_k."""
+    return np.frexp(max_diagonal(S))[1]
+
+
+def guard_and_pin(S, beta, pivot, ok, band=SCALE_BAND):
+    """The rank guard and the scale pin on the freshly updated S (..., D, D); ``pivot`` (...) the
+    smallest pivot of the factorisation of S before the update, ``ok`` whether there was one
+    -> S, the classes that were rescaled (...), the gate phi of every class (...)."""
+    D = S.shape[-1]
+    d = max_diagonal(S)
+    with np.errstate(all='ignore'):
+        x = pivot / (RANK_GATE * np.where(d > 0, d, 1.0))
+        phi = np.where(ok & (d > 0) & (x < GATE_CUT), np.exp(-np.minimum(x, GATE_CUT)), 0.0)
+    add = ((1 - beta) * RANK_EPS) * d * phi
+    S = S.copy()
+    S[..., np.arange(D), np.arange(D)] += add[..., None]
+    top = d + add                                   # the largest entry after the guard, its bits
+    with np.errstate(invalid='ignore'):
+        e = np.frexp(top)[1]
+        hit = np.isfinite(top) & (top >= TINY) & (np.abs(e) > band)
+    if np.any(hit):
+        S = np.where(hit[..., None, None], np.ldexp(1.0, -np.clip(e, -1000, 1000))[..., None, None] * S, S)
+    return S, hit, phi
+
+
+def online_cacgmm(Y, mask, beta, state, record=False, plain=False, watch=None, band=SCALE_BAND,
+                  watch_every=100, pins=None, gates=None):
     """Y (F,T,D), mask None / (K,T) / (F,K,T), the state to start from (not modified) -> gamma
     (F,K,T), the state after the T frames, the number of fallback (frequency, frame, class)
     triples; with ``record`` also the clipped affiliations g and the q that entered the sums,
     both (F,K,T), and the frames that were skipped as zeros (F,T).  The loop over the frames is
-    the recursion, vectorised over frequencies and classes."""
+    the recursion, vectorised over frequencies and classes.  ``plain``: without the rank guard
+    and the scale pin.  ``watch(t, S, n)`` is called after the update of every
+    ``watch_every``-th frame; ``pins``: a list that receives the (frame, frequency, class) of
+    every rescaling; ``gates``: a list that receives the gate phi (F,K) of every frame (0 where
+    the frame is digital silence)."""
     Y = np.asarray(Y, np.complex128)
     F, T, D = Y.shape
     st = copy_state(state)
@@ -92,16 +148,25 @@ def online_cacgmm(Y, mask, beta, state, record=False):
     fallbacks = 0
     for t in range(T):
         z = Z[:, :, t]
-        aff, q, ok = frame_posterior(S, n, z, m[:, :, t])
+        aff, q, ok, pivot = frame_posterior(S, n, z, m[:, :, t], with_pivot=True)
         gamma[:, :, t] = aff
         fallbacks += int(np.sum(~ok))
         g = np.clip(aff, AFF_EPS, 1 - AFF_EPS)
         zz = z[:, None, :, None] * z.conj()[:, None, None, :]
         upd = (g * D / np.maximum(q, 10 * TINY))[:, :, None, None] * zz
         lv = live[:, t]
-        S = np.where(lv[:, None, None, None], beta * S + upd, S)
+        Sn = beta * S + upd
+        if not plain:
+            Sn, hit, phi = guard_and_pin(Sn, beta, pivot, ok, band)
+            if gates is not None:
+                gates.append(np.where(lv[:, None], phi, 0.0))
+            if pins is not None:
+                pins.extend((t, int(f), int(k)) for f, k in zip(*np.nonzero(hit & lv[:, None])))
+        S = np.where(lv[:, None, None, None], Sn, S)
         n = np.where(lv[:, None], beta * n + g, n)
         gs[:, :, t], qs[:, :, t] = g, q
+        if watch is not None and (t + 1) % watch_every == 0:
+            watch(t + 1, S, n)
     out = gamma, dict(s=S, n=n), fallbacks
     return out + (gs, qs, live) if record else out
 
@@ -198,6 +263,24 @@ MODEL_MASS = 50.0
 # and n move at least STABILITY_MARGIN x less than TOL when every sample moves in its last bit
 # (`python tests/online_cacgmm_reference.py` re-derives the table).
 SEEDS = {(24, 5, 0.995, 1.0, 2, 120): 2, (24, 5, 0.98, 0.01, 2, 120): 2}
+# the long cells under the same rule (on them the gate of the rank guard stays at 0, so these are
+# the movements of the plain recursion):
+#    (4, 4, 0.99, 1.0, 2, 6000): 0,   # moves 9.7e-13, cond(S) up to 2.7e+02
+#    (12, 4, 0.99, 1.0, 1, 5000): 1,   # moves 2.6e-13, cond(S) up to 7.9e+02   (seed 0: 3.7e-12)
+#    (24, 5, 0.99, 1.0, 1, 4000): no seed of range(8) allows TOL: 5.2e-12, 9.4e-11, 1.07e-12, 5.3e-12,
+#                                 2.7e-12, 3.7e-12, 6.8e-12, 5.0e-12.  It keeps the seed that moves
+#                                 least, 2, and its bar is 100 x that movement, rounded up: 1.1e-10
+#    (4, 3, 0.95, 1.0, 2, 4000): 3,   # moves 1.1e-13, cond(S) up to 4.7e+02   (seeds 0 - 2 move more)
+LONG_SEEDS = {(12, 4, 0.99, 1.0, 1, 5000): 1, (24, 5, 0.99, 1.0, 1, 4000): 2, (4, 3, 0.95, 1.0, 2, 4000): 3}
+LONG_BARS = {(24, 5, 0.99, 1.0, 1, 4000): 1.1e-10}
+LONG_BAR_CAP = 1e-8
+
+
+def long_tol(cell):
+    """The bar of a long cell: TOL, or 100 x the movement of its kept seed where no seed allows
+    TOL (never above LONG_BAR_CAP)."""
+    return LONG_BARS.get(cell, TOL)
+
 
 
 def crandn(rng, *shape):
@@ -306,8 +389,8 @@ def fallback_case(kind):
     of either sign, so neither LAPACK's verdict nor any other is a property of the method; after
     D frames S_1 has full rank and the class no longer falls back at all.)
     'every': the same scene with the last channel dead: the last diagonal entry of S_1 stays
-    exactly 0, its pivot is exactly 0 in every order of summation, and class 1 falls back on
-    every frame."""
+    exactly 0 (a class without a factor gets no guard), its pivot is exactly 0 in every order of
+    summation, and class 1 falls back on every frame."""
     D, K, beta, prior_mass, F, T = FALLBACK_CELL
     Y, activity = scene(FALLBACK_CELL)
     if kind == 'first':
@@ -318,6 +401,160 @@ def fallback_case(kind):
     state = fresh_state(F, K, D, prior_mass)
     state['s'][:, 1] = 0
     return Y, activity, state, beta, F * Y.shape[1]
+
+
+# ------------------------------------------------------------------ long horizons
+# the bar of a long cell is TOL where a seed of range(8) allows it (`long_tol`)
+LONG_CELLS = [
+    (4, 4, 0.99, 1.0, 2, 6000),         # NR = 1
+    (12, 4, 0.99, 1.0, 1, 5000),        # NR = 2
+    (24, 5, 0.99, 1.0, 1, 4000),        # NR = 3
+    (4, 3, 0.95, 1.0, 2, 4000),         # the fast scale drift: the pin fires
+]
+LONG_BLOCK = 625
+PIN_CELL = (4, 3, 0.95, 1.0, 2, 4000)
+
+
+def long_seed_of(cell):
+    return LONG_SEEDS.get(cell, 0)
+
+
+@functools.lru_cache(maxsize=None)
+def long_pins(cell):
+    """The (frame, frequency, class) at which the reference rescales an S_k, in order."""
+    D, K, beta, prior_mass, F, T = cell
+    Y, activity = scene(cell, long_seed_of(cell))
+    pins = []
+    online_cacgmm(Y, activity, beta, fresh_state(F, K, D, prior_mass), pins=pins)
+    return tuple(pins)
+
+
+def long_partitions(cell):
+    """'blocks': LONG_BLOCK frames each (and the rest); 'ragged': one frame, a prime, a long
+    block, the rest -- for a cell whose scale pin fires, cut so that the first rescaling happens
+    on the LAST frame of a block and the second one on the FIRST frame of a block (the others
+    fall inside blocks)."""
+    T = cell[-1]
+    blocks = (LONG_BLOCK,) * (T // LONG_BLOCK) + ((T % LONG_BLOCK,) if T % LONG_BLOCK else ())
+    frames = sorted({t for t, _, _ in long_pins(cell)})
+    if len(frames) >= 2 and frames[0] > 2:
+        cuts = [1, frames[0] + 1, frames[1]]
+    else:
+        cuts = [1, 998, 998 + 2 * LONG_BLOCK + 3]
+    bounds = [0] + cuts + [T]
+    ragged = tuple(b - a for a, b in zip(bounds[:-1], bounds[1:]))
+    assert sum(ragged) == T and min(ragged) > 0
+    return dict(blocks=blocks, ragged=ragged)
+
+
+# ------------------------------------------------------------------ the starved class
+# A class that is allowed in most frames and wins almost none of them: its effective frame count
+# stays far below D, S_k loses rank, and the plain recursion loses the Cholesky factor.  The
+# recipe: a 10 s scene of K - 1 speakers in half-second turns through 8-tap filters, faded STFT
+# 1024 / 256, frames 3 to 627 of bins 100 and 400 replayed 12 times.
+STARVED = dict(D=4, K=4, beta=0.99, prior_mass=1.0, seed=4, samples=160000, turn=8000, stft_size=1024,
+               stft_shift=256, bins=(100, 400), frames=(3, 628), replays=12)
+STARVED_COND = 1e12         # cond(S_k) of the guarded reference, every 100 frames, stays below
+STARVED_REFEREE_TOL = 1e-6  # the float64 reference against the extended-precision referee
+
+
+def turn_scene(rng, D, K, samples, turn):
+    """x (D,samples) and the activity (K,samples): K - 1 speakers, white noise through a random
+    8-tap filter per channel, on (60 %) in random turns, a last class that is always on, sensor
+    noise at 0.1."""
+    act = np.ones((K, samples), bool)
+    x = 0.1 * rng.standard_normal((D, samples))
+    for k in range(K - 1):
+        act[k] = np.repeat(rng.random(-(-samples // turn)) < 0.6, turn)[:samples]
+        src = rng.standard_normal(samples) * act[k]
+        x += np.stack([np.convolve(src, h)[:samples] for h in rng.standard_normal((D, 8))])
+    return x, act
+
+
+@functools.lru_cache(maxsize=None)
+def starved_scene():
+    """-> Y (F,T,D) with F = 2, T = 7500, the frame activity (K,T) bool; read-only."""
+    p = STARVED
+    x, act = turn_scene(np.random.default_rng(p['seed']), p['D'], p['K'], p['samples'], p['turn'])
+    Yfull = oracle.stft(x, p['stft_size'], p['stft_shift'], fading=True)          # (D,T,F)
+    actf = oracle.activity_time_to_frequency(act, p['stft_size'], p['stft_shift'], True,
+                                             stft_pad=True)[:, :Yfull.shape[1]]
+    lo, hi = p['frames']
+    Y = np.ascontiguousarray(Yfull[..., list(p['bins'])].transpose(2, 1, 0))[:, lo:hi]
+    Y = np.concatenate([Y] * p['replays'], axis=1)
+    activity = np.concatenate([np.asarray(actf[:, lo:hi]) != 0] * p['replays'], axis=1)
+    Y.setflags(write=False)
+    activity.setflags(write=False)
+    return Y, activity
+
+
+@functools.lru_cache(maxsize=None)
+def starved_reference(plain=False):
+    """gamma, the final state, the fallback count and the largest cond(S_k) seen every 100
+    frames."""
+    p = STARVED
+    Y, activity = starved_scene()
+    worst = [0.0]
+
+    def watch(t, S, n):
+        with np.errstate(all='ignore'):
+            worst[0] = max(worst[0], float(np.max(np.linalg.cond(S))))
+    gamma, st, fallbacks = online_cacgmm(Y, activity, p['beta'],
+                                         fresh_state(Y.shape[0], p['K'], p['D'], p['prior_mass']),
+                                         plain=plain, watch=watch)
+    for a in (gamma, st['s'], st['n']):
+        a.setflags(write=False)
+    return gamma, st, fallbacks, worst[0]
+
+
+@functools.lru_cache(maxsize=None)
+def starved_gates():
+    """The largest gate phi over frequencies and classes at every frame of the starved cell in
+    the guarded reference, (T,)."""
+    p = STARVED
+    Y, activity = starved_scene()
+    gates = []
+    online_cacgmm(Y, activity, p['beta'], fresh_state(Y.shape[0], p['K'], p['D'], p['prior_mass']),
+                  gates=gates)
+    return np.max(np.array(gates), axis=(1, 2))
+
+
+def starved_partitions():
+    """'blocks': LONG_BLOCK frames each; 'ragged': one frame, then cuts in the first run of three
+    frames on which the guard is well alive (phi > 0.1) -- one cut before its middle frame and one after
+    it, so that a block of ONE live frame has live frames on both sides -- and the rest."""
+    T = starved_scene()[0].shape[1]
+    live = starved_gates() > 0.1
+    run = np.nonzero(live[:-2] & live[1:-1] & live[2:])[0]
+    assert len(run) and run[0] > 1
+    t = int(run[0]) + 1
+    bounds = [0, 1, t, t + 1, T]
+    blocks = (LONG_BLOCK,) * (T // LONG_BLOCK) + ((T % LONG_BLOCK,) if T % LONG_BLOCK else ())
+    return dict(blocks=blocks, ragged=tuple(b - a for a, b in zip(bounds[:-1], bounds[1:])))
+
+
+@functools.lru_cache(maxsize=None)
+def starved_referee():
+    """gamma of the guarded recursion in 80-bit extended precision, the number of failed
+    factorisations."""
+    import ext_precision as xp
+    p = STARVED
+    Y, activity = starved_scene()
+    gamma, failed = xp.online_cacgmm(Y, activity, p['beta'], p['prior_mass'], RANK_EPS, RANK_GATE,
+                                     GATE_CUT, SCALE_BAND)
+    gamma.setflags(write=False)
+    return gamma, failed
+
+
+SCALE_EXPONENTS = (-600, -200, 200, 600)
+
+
+def scaled_state(state):
+    """S_k multiplied by 2^e_k, e_k from SCALE_EXPONENTS, another one per class (and shifted by one
+    place per frequency)."""
+    F, K = state['n'].shape
+    e = np.array([[SCALE_EXPONENTS[(k + f) % len(SCALE_EXPONENTS)] for k in range(K)] for f in range(F)])
+    return dict(s=state['s'] * np.ldexp(1.0, e)[..., None, None], n=state['n'].copy())
 
 
 # ------------------------------------------------------------------ the evidence
@@ -451,7 +688,11 @@ def pipe_movement(bf_online=False, wpe_online=False, scene_seed=None):
 
 
 if __name__ == '__main__':
-    for cell in CELLS:
+    for cell in CELLS + LONG_CELLS:
+        if cell in LONG_BARS:
+            print(f'    {cell}: seeds 0 - 7 move '
+                  + ', '.join(f'{reference_movement(cell, seed):.2e}' for seed in range(8)))
+            continue
         seed = choose_seed(cell)
         cond = condition_numbers(reference(cell, seed)[1])
         print(f'    {cell}: {seed},   # moves {reference_movement(cell, seed):.1e}, '

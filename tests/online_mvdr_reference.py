@@ -146,6 +146,16 @@ EVIDENCE_BOUND = 0.8        # a condition, not a measurement
 # tests/online_mvdr_reference.py` re-derives the table).
 SEEDS = {(4, 0.5, 1.0, 2, 100): 1}
 EVIDENCE_SEED = 0           # the seed rule for it: the ratio of the reference is <= 0.75
+# Long horizons, the same format, variants and seed rule (LONG_SEEDS: the seeds that are not 0):
+#    (4, 0.99, 1e-2, 2, 6000): 0,   # moves 4.4e-14, cond(Phi_N) 5.5e+02
+#    (24, 0.995, 1.0, 1, 3000): 0,   # moves 5.0e-13, cond(Phi_N) 6.7e+03
+LONG_CELLS = [(4, 0.99, 1e-2, 2, 6000), (24, 0.995, 1.0, 1, 3000)]
+LONG_BLOCK = 625
+LONG_SEEDS = {}
+
+
+def long_blocks(T):
+    return (LONG_BLOCK,) * (T // LONG_BLOCK) + ((T % LONG_BLOCK,) if T % LONG_BLOCK else ())
 
 
 def crandn(rng, *shape):
@@ -183,7 +193,7 @@ def last_bit(a, rng):
 
 
 def seed_of(cell):
-    return SEEDS.get(cell, 0)
+    return LONG_SEEDS.get(cell, 0) if cell in LONG_CELLS else SEEDS.get(cell, 0)
 
 
 def variants(cell):
@@ -355,7 +365,7 @@ if __name__ == '__main__':
     from pathlib import Path
     sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
     sys.path.insert(0, str(Path(__file__).resolve().parent.parent / 'oracle'))
-    for cell in CELLS:
+    for cell in CELLS + LONG_CELLS:
         seed = choose_seed(cell)
         print(f'    {cell}: {seed},   # moves {reference_movement(cell, seed):.1e}')
     for seed in range(4):

@@ -133,6 +133,21 @@ CLOSED_FORM_TOL = 1e-9
 SEEDS = {}
 
 
+# Long horizons, the same format.  The third cell's last channel is scaled by 1e-7 (the
+# eigenvalues of P then span fifteen decades).  Seeds by the rule above:
+#    (1, 4, 10, 2, 0.999, 1, 6000): 0,   # moves 2.5e-15; P, G vs the closed form 8.7e-14, 1.1e-14
+#    (1, 12, 10, 2, 0.999, 1, 1500): 0,   # moves 1.0e-14; 5.6e-14, 9.1e-15
+#    (1, 4, 3, 2, 0.99, 2, 6000): 0,   # moves 8.8e-16; 7.0e-15, 2.4e-15; eigenvalues of P 4.9e-03 .. 1.1e+12
+LONG_CELLS = [
+    (1, 4, 10, 2, 0.999, 1, 6000),          # on-chip form, n = 40
+    (1, 12, 10, 2, 0.999, 1, 1500),         # memory form, n = 120
+    (1, 4, 3, 2, 0.99, 2, 6000),            # one channel at 1e-7 of the others
+]
+LONG_CHANNEL_GAIN = {(1, 4, 3, 2, 0.99, 2, 6000): 1e-7}
+LONG_BLOCK = 625
+LONG_SEEDS = {}
+
+
 def crandn(rng, *shape):
     return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
 
@@ -151,6 +166,45 @@ def scene(cell, seed=0):
         Y += np.einsum('ftd,fde->fte', S[:, 8 - lag:T + 8 - lag], mix)
     Y.setflags(write=False)
     return Y
+
+
+def long_seed_of(cell):
+    return LONG_SEEDS.get(cell, 0)
+
+
+@functools.lru_cache(maxsize=None)
+def long_scene(cell, seed=0):
+    """The scene of a long cell: `scene`, its last channel scaled by LONG_CHANNEL_GAIN."""
+    Y = scene(cell, seed)
+    if cell in LONG_CHANNEL_GAIN:
+        Y = Y.copy()
+        Y[:, :, -1] *= LONG_CHANNEL_GAIN[cell]
+        Y.setflags(write=False)
+    return Y
+
+
+@functools.lru_cache(maxsize=None)
+def long_reference(cell, seed=0):
+    A, C, taps, delay, alpha, F, T = cell
+    return _freeze(*online_wpe(long_scene(cell, seed), taps, delay, alpha, A))
+
+
+@functools.lru_cache(maxsize=None)
+def long_closed_form(cell, seed=0):
+    A, C, taps, delay, alpha, F, T = cell
+    return closed_form(long_scene(cell, seed), taps, delay, alpha, A)
+
+
+def long_reference_movement(cell, seed=0):
+    A, C, taps, delay, alpha, F, T = cell
+    X, st = long_reference(cell, seed)
+    Xb, stb = online_wpe(last_bit(long_scene(cell, seed), np.random.default_rng(12345)), taps,
+                         delay, alpha, A)
+    return max(rel_err(Xb, X), rel_err(stb['G'], st['G']), rel_err(stb['P'], st['P']))
+
+
+def long_blocks(T):
+    return (LONG_BLOCK,) * (T // LONG_BLOCK) + ((T % LONG_BLOCK,) if T % LONG_BLOCK else ())
 
 
 def last_bit(a, rng):
@@ -287,6 +341,16 @@ if __name__ == '__main__':
     for cell in CELLS:
         seed = choose_seed(cell)
         print(f'    {cell}: {seed},   # moves {reference_movement(cell, seed):.1e}')
+    for cell in LONG_CELLS:
+        for seed in range(8):
+            moved = long_reference_movement(cell, seed)
+            if moved * STABILITY_MARGIN <= TOL:
+                break
+        P, G = long_closed_form(cell, seed)
+        st = long_reference(cell, seed)[1]
+        print(f'    {cell}: {seed},   # moves {moved:.1e}; P, G vs the closed form '
+              f'{rel_err(st["P"], P):.1e}, {rel_err(st["G"], G):.1e}; eigenvalues of P '
+              f'{np.linalg.eigvalsh(st["P"]).min():.1e} .. {np.linalg.eigvalsh(st["P"]).max():.1e}')
     for cell in EVIDENCE_CELLS:
         print(f'    evidence {cell}: second-half energy out / in {evidence_ratio(cell):.2f}')
     for arrays in (1, 2):

@@ -182,6 +182,25 @@ def scene(name, seed=0):
     return x, activity
 
 
+# The long stream: the starved-class recipe of online_cacgmm_reference (STARVED) at STFT 64 / 16 --
+# 10 000 samples of K - 1 speakers in turns of 500 samples, replayed 13 times: 8 128 frames.  On its
+# frames the recursion WITHOUT the rank guard loses Cholesky factors (test_online_cacgmm_api).
+LONG = dict(W=64, H=16, D=4, K=4, taps=2, delay=1, seed=0, samples=10000, turn=500, replays=13,
+            block=10000)
+
+
+@functools.lru_cache(maxsize=None)
+def long_scene():
+    """-> x (D,N) float64, activity (K,N) bool per sample, N = 130 000, read-only."""
+    p = LONG
+    x, act = cr.turn_scene(np.random.default_rng(p['seed']), p['D'], p['K'], p['samples'], p['turn'])
+    x = np.concatenate([x] * p['replays'], axis=1)
+    act = np.concatenate([act] * p['replays'], axis=1)
+    x.setflags(write=False)
+    act.setflags(write=False)
+    return x, act
+
+
 # ------------------------------------------------------------------ the composition
 def fresh_states(name):
     W, H, D, A, taps, delay, K, N, wpe = CELLS[name]

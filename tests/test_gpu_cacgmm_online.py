@@ -175,6 +175,170 @@ def test_no_mask_from_a_fresh_state_never_separates(gpu_ctx):
             assert np.all(gamma == 0.5)
 
 
+# ------------------------------------------------------------------ long horizons
+def _long_device(ctx, cell):
+    """gamma, the state and the fallback count after the long cell's scene in ONE call; once."""
+    from pb_chime5_amd import ops
+    key = ('long', cell)
+    if key not in _RUNS:
+        D, K, beta, prior_mass, F, T = cell
+        Y, activity = cr.scene(cell, cr.long_seed_of(cell))
+        state = ops.OnlineCACGMMState.fresh(F, K, D, prior_mass, ctx=ctx)
+        gamma, fallbacks = _run(ctx, Y, activity, beta, state, return_fallbacks=True)
+        host = state.to_host()
+        for a in (gamma, host['s'], host['n']):
+            a.setflags(write=False)
+        _RUNS[key] = gamma, host, fallbacks
+    return _RUNS[key]
+
+
+@pytest.mark.parametrize('cell', cr.LONG_CELLS, ids=str)
+def test_long_cells_against_the_reference(gpu_ctx, cell):
+    """Thousands of frames in one call: gamma, S and n within the cell's bar (long_tol: TOL, and
+    1.1e-10 for the one cell in which no seed allows TOL) of the reference, no fallback
+    on either side, gamma finite and summing to 1 over the classes wherever a class is allowed,
+    the handed-out S exactly Hermitian and inside the scale band."""
+    D, K, beta, prior_mass, F, T = cell
+    gamma, host, fallbacks = _long_device(gpu_ctx, cell)
+    gr, st, fr = cr.reference(cell, cr.long_seed_of(cell))
+    errs = dict(gamma=rel_err(gamma, gr), s=rel_err(host['s'], st['s']), n=rel_err(host['n'], st['n']))
+    print(f'{cell}: rel err {errs}, fallbacks {fallbacks} / {fr}, pins {len(cr.long_pins(cell))}')
+    assert fallbacks == 0 and fr == 0
+    assert max(errs.values()) < cr.long_tol(cell), (cell, errs)
+    _, activity = cr.scene(cell, cr.long_seed_of(cell))
+    on = activity.any(axis=0)
+    assert np.all(np.isfinite(gamma))
+    assert np.max(np.abs(gamma.sum(axis=1)[:, on] - 1.0)) <= 1e-12
+    S = host['s']
+    assert np.array_equal(S, S.conj().swapaxes(-1, -2))
+    assert np.all(S[..., np.arange(D), np.arange(D)].imag == 0) and np.all(host['n'] > 0)
+    assert np.all(np.abs(cr.scale_exponents(S)) <= cr.SCALE_BAND)
+    if cell == cr.PIN_CELL:
+        assert len(cr.long_pins(cell)) >= 2
+
+
+@pytest.mark.parametrize('cell', cr.LONG_CELLS, ids=str)
+def test_long_cells_in_blocks_give_the_bits_of_the_single_call(gpu_ctx, cell):
+    """Blocks of 625 frames and one ragged partition (online_cacgmm_reference.long_partitions: in
+    the cell whose scale pin fires, one rescaling on the last frame of a block and one on the
+    first) through one state; in the 625-frame run the state is saved with to_host in the middle
+    and restored into a new state that carries on."""
+    from pb_chime5_amd import ops
+    D, K, beta, prior_mass, F, T = cell
+    gamma1, host1, _ = _long_device(gpu_ctx, cell)
+    Y, activity = cr.scene(cell, cr.long_seed_of(cell))
+    for name, cuts in cr.long_partitions(cell).items():
+        bounds = np.concatenate([[0], np.cumsum(cuts)])
+        assert bounds[-1] == T
+        state = ops.OnlineCACGMMState.fresh(F, K, D, prior_mass, ctx=gpu_ctx)
+        outs, total = [], 0
+        for i, (a, b) in enumerate(zip(bounds[:-1], bounds[1:])):
+            if name == 'blocks' and i == len(cuts) // 2:
+                state = ops.OnlineCACGMMState.from_host(state.to_host(), ctx=gpu_ctx)
+            g, fb = _run(gpu_ctx, Y[:, a:b], activity[:, a:b], beta, state, return_fallbacks=True)
+            outs.append(g)
+            total += fb
+        assert total == 0, name
+        assert np.array_equal(np.concatenate(outs, axis=-1), gamma1), name
+        host = state.to_host()
+        for k in ('s', 'n'):
+            assert np.array_equal(host[k], host1[k]), (name, k)
+
+
+def test_scale_invariance(gpu_ctx):
+    """A state handed in with S_k multiplied by 2^e_k, e_k from {-600, -200, 200, 600} and another
+    one per class: the gamma of the unscaled run within TOL; after the call every class's
+    largest diagonal entry is back inside the band and n is the unscaled run's."""
+    from pb_chime5_amd import ops
+    cell = cr.CELLS[0]
+    D, K, beta, prior_mass, F, T = cell
+    assert T == 150
+    Y, activity = cr.scene(cell, cr.seed_of(cell))
+    state = ops.OnlineCACGMMState.fresh(F, K, D, prior_mass, ctx=gpu_ctx)
+    _run(gpu_ctx, Y[:, :20], activity[:, :20], beta, state)
+    mid = state.to_host()
+    want = _run(gpu_ctx, Y[:, 20:], activity[:, 20:], beta, state)
+    n_want = state.to_host()['n']
+    scaled = ops.OnlineCACGMMState.from_host(cr.scaled_state(mid), ctx=gpu_ctx)
+    assert np.abs(cr.scale_exponents(scaled.to_host()['s'])).min() > 100
+    gamma, fallbacks = _run(gpu_ctx, Y[:, 20:], activity[:, 20:], beta, scaled, return_fallbacks=True)
+    after = scaled.to_host()
+    gr = cr.online_cacgmm(Y[:, 20:], activity[:, 20:], beta, mid)[0]
+    errs = rel_err(gamma, want), rel_err(gamma, gr), rel_err(after['n'], n_want)
+    print(f'scaled state: gamma vs the unscaled run {errs[0]:.1e}, vs the reference {errs[1]:.1e}, '
+          f'n {errs[2]:.1e}; exponents after {cr.scale_exponents(after["s"]).tolist()}')
+    assert fallbacks == 0 and max(errs) < cr.TOL, errs
+    assert np.all(np.abs(cr.scale_exponents(after['s'])) <= cr.SCALE_BAND)
+
+
+def _starved_device(ctx):
+    """gamma, the state and the fallback count after the starved cell in ONE call; once."""
+    from pb_chime5_amd import ops
+    if 'starved' not in _RUNS:
+        p = cr.STARVED
+        Y, activity = cr.starved_scene()
+        state = ops.OnlineCACGMMState.fresh(Y.shape[0], p['K'], p['D'], p['prior_mass'], ctx=ctx)
+        gamma, fallbacks = _run(ctx, Y, activity, p['beta'], state, return_fallbacks=True)
+        host = state.to_host()
+        for a in (gamma, host['s'], host['n']):
+            a.setflags(write=False)
+        _RUNS['starved'] = gamma, host, fallbacks
+    return _RUNS['starved']
+
+
+def test_the_starved_class_keeps_its_factor(gpu_ctx):
+    """The starved cell (online_cacgmm_reference.STARVED), the one cell in which the gate of the
+    rank guard is not 0: no fallback on the device or in the reference, and -- cond(S_k) x eps is
+    1e-5 here, so not at TOL -- the device's gamma within 5 x the float64 reference's own distance
+    from the 80-bit referee, plus 1e-9, of that referee.  That bar is mostly its 1e-9; so that an
+    error in the device's pivot or gate shows, the device is also held to the reference at 100 x
+    the reference's own distance from the referee (two float64 programs of one recursion whose
+    exact course the referee gives)."""
+    gamma, host, fallbacks = _starved_device(gpu_ctx)
+    gr, st, fr, cond = cr.starved_reference()
+    referee, failed = cr.starved_referee()
+    ref_dist = float(np.max(np.abs(gr - referee)))
+    dev_dist = float(np.max(np.abs(gamma - referee)))
+    dev_ref = float(np.max(np.abs(gamma - gr)))
+    print(f'starved cell: reference vs referee {ref_dist:.1e}, device vs referee {dev_dist:.1e}, '
+          f'device vs reference {dev_ref:.1e}; fallbacks {fallbacks} / {fr}, '
+          f'cond(S_k) of the reference up to {cond:.1e}')
+    assert fallbacks == 0 and fr == 0 and failed == 0
+    assert cond <= cr.STARVED_COND and ref_dist <= cr.STARVED_REFEREE_TOL
+    assert np.all(np.isfinite(gamma))
+    assert dev_dist <= 5 * ref_dist + 1e-9
+    assert dev_ref <= 100 * ref_dist
+    assert np.array_equal(host['s'], host['s'].conj().swapaxes(-1, -2))
+    assert np.max(np.linalg.cond(host['s'])) <= cr.STARVED_COND
+
+
+def test_the_starved_cell_in_blocks_gives_the_bits_of_the_single_call(gpu_ctx):
+    """The rank guard across block borders (test_online_cacgmm_api proves that its gate is above
+    0.1 on both sides of the cuts): blocks of 625 frames, with the state saved by to_host and
+    restored in the middle, and the ragged partition with a one-frame block among live frames."""
+    from pb_chime5_amd import ops
+    p = cr.STARVED
+    Y, activity = cr.starved_scene()
+    F, T, D = Y.shape
+    gamma1, host1, _ = _starved_device(gpu_ctx)
+    for name, cuts in cr.starved_partitions().items():
+        bounds = np.concatenate([[0], np.cumsum(cuts)])
+        assert bounds[-1] == T
+        state = ops.OnlineCACGMMState.fresh(F, p['K'], D, p['prior_mass'], ctx=gpu_ctx)
+        outs, total = [], 0
+        for i, (a, b) in enumerate(zip(bounds[:-1], bounds[1:])):
+            if name == 'blocks' and i == 9:         # the cut at 5 625, where the guard is live
+                state = ops.OnlineCACGMMState.from_host(state.to_host(), ctx=gpu_ctx)
+            g, fb = _run(gpu_ctx, Y[:, a:b], activity[:, a:b], p['beta'], state, return_fallbacks=True)
+            outs.append(g)
+            total += fb
+        assert total == 0, name
+        assert np.array_equal(np.concatenate(outs, axis=-1), gamma1), name
+        host = state.to_host()
+        for k in ('s', 'n'):
+            assert np.array_equal(host[k], host1[k]), (name, k)
+
+
 # ------------------------------------------------------------------ the state
 @pytest.mark.parametrize('cell', [cr.CELLS[0], cr.CELLS[3], cr.CELLS[8], cr.CELLS[10]], ids=str)
 def test_handed_out_state_is_exactly_hermitian(gpu_ctx, cell):

@@ -60,6 +60,71 @@ def test_against_the_reference(gpu_ctx, cell):
         assert max(errs.values()) < mr.TOL, (cell, ban, ref, errs)
 
 
+# ------------------------------------------------------------------ long horizons
+def _long_device(ctx, cell, ban, ref):
+    """X, W, the state and the fallback count after the long cell's scene in ONE call; once."""
+    from pb_chime5_amd import ops
+    key = ('long', cell, ban, ref)
+    if key not in _RUNS:
+        D, beta, loading, F, T = cell
+        Y, mx, mn, _ = mr.scene(cell, mr.seed_of(cell))
+        state = ops.OnlineMVDRState.fresh(F, D, loading, mr.to_dtf(Y), ctx=ctx)
+        X, W = _run(ctx, Y, mx, mn, cell, ban, ref, state)
+        fallbacks = ctx.last_mvdr_online_fallbacks()
+        host = state.to_host()
+        for a in (X, W, host['phi_x'], host['phi_n']):
+            a.setflags(write=False)
+        _RUNS[key] = X, W, host, fallbacks
+    return _RUNS[key]
+
+
+@pytest.mark.parametrize('cell', mr.LONG_CELLS, ids=str)
+def test_long_cells_against_the_reference(gpu_ctx, cell):
+    """Thousands of frames in one call, every variant: X, W and the state at TOL, no fallback on
+    either side, the state exactly Hermitian and its closed form."""
+    D, beta, loading, F, T = cell
+    Y, mx, mn, _ = mr.scene(cell, mr.seed_of(cell))
+    phi_x, phi_n = mr.closed_form(Y, mx, mn, beta, mr.loading_delta(Y, loading))
+    for ban, ref in mr.variants(cell):
+        X, W, host, fallbacks = _long_device(gpu_ctx, cell, ban, ref)
+        Xr, Wr, st, fr = mr.reference(cell, ban, ref, mr.seed_of(cell))
+        assert fallbacks == 0 and fr == 0
+        errs = dict(X=rel_err(X, Xr), W=rel_err(W, Wr), phi_x=rel_err(host['phi_x'], st['phi_x']),
+                    phi_n=rel_err(host['phi_n'], st['phi_n']))
+        print(f'{cell} ban={ban} ref={ref}: rel err {errs}')
+        assert np.all(np.isfinite(X)) and np.all(np.isfinite(W))
+        assert max(errs.values()) < mr.TOL, (cell, ban, ref, errs)
+        for k in ('phi_x', 'phi_n'):
+            P = host[k]
+            assert np.array_equal(P, P.conj().swapaxes(-1, -2)), k
+            assert np.all(P[..., np.arange(D), np.arange(D)].imag == 0), k
+        closed = rel_err(host['phi_x'], phi_x), rel_err(host['phi_n'], phi_n)
+        assert max(closed) < mr.CLOSED_FORM_TOL, closed
+    print(f'{cell}: device Phi_X, Phi_N vs closed form {closed}')
+
+
+@pytest.mark.parametrize('cell', mr.LONG_CELLS, ids=str)
+def test_long_cells_in_blocks_give_the_bits_of_the_single_call(gpu_ctx, cell):
+    from pb_chime5_amd import ops
+    D, beta, loading, F, T = cell
+    ban, ref = True, D - 1
+    X1, W1, host1, _ = _long_device(gpu_ctx, cell, ban, ref)
+    Y, mx, mn, _ = mr.scene(cell, mr.seed_of(cell))
+    state = ops.OnlineMVDRState.fresh(F, D, loading, mr.to_dtf(Y), ctx=gpu_ctx)
+    bounds = np.concatenate([[0], np.cumsum(mr.long_blocks(T))])
+    assert bounds[-1] == T
+    outs, total = [], 0
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        outs.append(_run(gpu_ctx, Y[:, a:b], mx[:, a:b], mn[:, a:b], cell, ban, ref, state))
+        total += gpu_ctx.last_mvdr_online_fallbacks()
+    assert total == 0
+    assert np.array_equal(np.concatenate([o[0] for o in outs], axis=1), X1)
+    assert np.array_equal(np.concatenate([o[1] for o in outs], axis=1), W1)
+    host = state.to_host()
+    for k in ('phi_x', 'phi_n'):
+        assert np.array_equal(host[k], host1[k]), k
+
+
 # ------------------------------------------------------------------ blocks, determinism
 @pytest.mark.parametrize('cell', mr.CHUNK_CELLS, ids=str)
 def test_blocks_through_one_state_equal_the_single_call(gpu_ctx, cell):

@@ -212,6 +212,41 @@ def test_parity_with_the_composed_references(gpu_ctx, name):
     assert x_err < sr.X_TOL
 
 
+def test_a_long_stream_keeps_every_factor(gpu_ctx):
+    """8 128 frames of the starved-class scene (stream_reference.long_scene) in blocks of 10 000
+    samples: no stage falls back, the output is finite, and the fused block has the bits of the
+    stage operators."""
+    from pb_chime5_amd.streaming import StreamingEnhancer
+    p, s = sr.LONG, sr.SETTINGS
+    x, activity = sr.long_scene()
+    N = x.shape[1]
+    cuts = (p['block'],) * (N // p['block'])
+    assert sum(cuts) == N
+    res = {}
+    for fused in (True, False):
+        enh = StreamingEnhancer(p['D'], p['K'], target=s['target'], ref_channel=s['ref_channel'],
+                                stft_size=p['W'], stft_shift=p['H'], wpe=True, wpe_taps=p['taps'],
+                                wpe_delay=p['delay'], wpe_alpha=s['wpe_alpha'], wpe_arrays=1,
+                                gss_forget=s['gss_forget'], gss_prior_mass=s['gss_prior_mass'],
+                                bf_forget=s['bf_forget'], bf_loading=s['bf_loading'], fused=fused,
+                                ctx=gpu_ctx)
+        outs = [enh.process(x[:, a:b], activity[:, a:b]) for a, b in sr.blocks_of(N, cuts)]
+        outs.append(enh.flush())
+        res[fused] = dict(x_hat=np.concatenate(outs), states=states_of(enh),
+                          fallbacks=dict(enh.fallbacks))
+        assert enh.samples_out == enh.samples_in == N
+        assert all(v == 0 for v in enh.fallbacks.values()), (fused, enh.fallbacks)
+    x_hat = res[True]['x_hat']
+    assert x_hat.shape == (N,) and np.all(np.isfinite(x_hat)) and np.any(x_hat != 0)
+    assert all(np.all(np.isfinite(v)) for v in res[True]['states'].values()
+               if v.dtype.kind in 'fc')
+    S = res[True]['states']['em.s']
+    print(f'long stream: {oracle.stft_frames(N, p["W"], p["H"], fading=True)} frames, fallbacks {res[True]["fallbacks"]}, '
+          f'cond(S_k) at the end up to {np.max(np.linalg.cond(S)):.1e}, n_k down to '
+          f'{res[True]["states"]["em.n"].min():.3f}')
+    same_bits(res[True], res[False], 'long stream fused vs stages')
+
+
 # ------------------------------------------------------------------ 5. edges
 def test_an_empty_block_is_a_no_op(gpu_ctx):
     x, activity = sr.scene('a')

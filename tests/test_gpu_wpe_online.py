@@ -90,6 +90,65 @@ def test_memory_form_forced_on_the_onchip_cells(gpu_ctx, monkeypatch, cell):
     assert np.array_equal(host['history'], hosto['history'])
 
 
+# ------------------------------------------------------------------ long horizons
+def _long_device(ctx, cell):
+    """X and the state after the long cell's scene in ONE call, in the form n selects; once."""
+    from pb_chime5_amd import ops
+    key = ('long', cell)
+    if key not in _RUNS:
+        A, C, taps, delay, alpha, F, T = cell
+        state = ops.OnlineWPEState.fresh(F, A, C, taps, delay, ctx=ctx)
+        X = _run(ctx, wr.long_scene(cell, wr.long_seed_of(cell)), cell, state)
+        host = state.to_host()
+        for a in (X, host['inv_cov'], host['filter'], host['history']):
+            a.setflags(write=False)
+        _RUNS[key] = X, host
+    return _RUNS[key]
+
+
+@pytest.mark.parametrize('cell', wr.LONG_CELLS, ids=str)
+def test_long_cells_against_the_reference_and_the_closed_form(gpu_ctx, monkeypatch, cell):
+    """Thousands of frames: X, P and G against the reference at TOL, P and G of BOTH sides against
+    the weighted least-squares problem at CLOSED_FORM_TOL, the handed-out P exactly Hermitian."""
+    monkeypatch.delenv('GSS_VARIANT', raising=False)
+    A, C, taps, delay, alpha, F, T = cell
+    X, host = _long_device(gpu_ctx, cell)
+    Xr, st = wr.long_reference(cell, wr.long_seed_of(cell))
+    errs = dict(X=rel_err(X, Xr), G=rel_err(host['filter'], st['G']),
+                P=rel_err(host['inv_cov'], st['P']))
+    print(f'{cell}: rel err {errs}')
+    assert np.all(np.isfinite(X))
+    assert max(errs.values()) < wr.TOL, (cell, errs)
+    assert np.array_equal(host['history'], st['hist'])
+    P, G = wr.long_closed_form(cell, wr.long_seed_of(cell))
+    closed = dict(device_G=rel_err(host['filter'], G), device_P=rel_err(host['inv_cov'], P),
+                  reference_G=rel_err(st['G'], G), reference_P=rel_err(st['P'], P))
+    print(f'{cell}: vs the closed form {closed}')
+    assert max(closed.values()) < wr.CLOSED_FORM_TOL, closed
+    Pd = host['inv_cov']
+    n = Pd.shape[-1]
+    assert np.array_equal(Pd, Pd.conj().swapaxes(-1, -2))
+    assert np.all(Pd[..., np.arange(n), np.arange(n)].imag == 0)
+
+
+@pytest.mark.parametrize('cell', wr.LONG_CELLS, ids=str)
+def test_long_cells_in_blocks_give_the_bits_of_the_single_call(gpu_ctx, monkeypatch, cell):
+    from pb_chime5_amd import ops
+    monkeypatch.delenv('GSS_VARIANT', raising=False)
+    A, C, taps, delay, alpha, F, T = cell
+    X1, host1 = _long_device(gpu_ctx, cell)
+    Y = wr.long_scene(cell, wr.long_seed_of(cell))
+    state = ops.OnlineWPEState.fresh(F, A, C, taps, delay, ctx=gpu_ctx)
+    bounds = np.concatenate([[0], np.cumsum(wr.long_blocks(T))])
+    assert bounds[-1] == T
+    X = np.concatenate([_run(gpu_ctx, Y[:, a:b], cell, state)
+                        for a, b in zip(bounds[:-1], bounds[1:])], axis=1)
+    assert np.array_equal(X, X1)
+    host = state.to_host()
+    for k in ('inv_cov', 'filter', 'history'):
+        assert np.array_equal(host[k], host1[k]), k
+
+
 def test_a_throwaway_state_gives_the_same_output(gpu_ctx, monkeypatch):
     for form in FORMS:
         cell = wr.ONCHIP_CELLS[0]

@@ -72,10 +72,13 @@ def test_reference_zero_target_mask_and_fallbacks():
 def test_parity_scenes_are_stable():
     """The rule that keeps a seed: the reference itself moves at least STABILITY_MARGIN x less
     than the bar under a last-bit change of every sample and mask value."""
-    for cell in mr.CELLS:
+    for cell in mr.CELLS + mr.LONG_CELLS:
         moved = mr.reference_movement(cell, mr.seed_of(cell))
         assert moved * mr.STABILITY_MARGIN <= mr.TOL, (cell, moved)
     assert max(c[0] for c in mr.CELLS) == 32
+    assert mr.LONG_CELLS == [(4, 0.99, 1e-2, 2, 6000), (24, 0.995, 1.0, 1, 3000)]
+    for cell in mr.LONG_CELLS:
+        assert all(mr.reference(cell, ban, ref, mr.seed_of(cell))[3] == 0 for ban, ref in mr.variants(cell))
 
 
 def test_the_online_form_follows_a_moving_target():

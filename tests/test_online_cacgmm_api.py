@@ -144,6 +144,135 @@ def test_parity_scenes_are_stable():
         assert cr.reference(cell, cr.seed_of(cell))[2] == 0
     assert max(c[0] for c in cr.CELLS) == 32 and max(c[1] for c in cr.CELLS) == 8
     assert cr.CELLS[:2] == [(4, 3, 0.99, 1.0, 3, 150), (1, 2, 0.9, 1.0, 1, 5)] and len(cr.CELLS) == 16
+    for cell in cr.LONG_CELLS:
+        moved = cr.reference_movement(cell, cr.long_seed_of(cell))
+        print(f'{cell}: seed {cr.long_seed_of(cell)} moves {moved:.1e}')
+        assert moved * cr.STABILITY_MARGIN <= cr.long_tol(cell), (cell, moved)
+        assert cr.TOL <= cr.long_tol(cell) <= cr.LONG_BAR_CAP
+        assert cr.reference(cell, cr.long_seed_of(cell))[2] == 0
+    assert cr.LONG_CELLS == [(4, 4, 0.99, 1.0, 2, 6000), (12, 4, 0.99, 1.0, 1, 5000),
+                             (24, 5, 0.99, 1.0, 1, 4000), (4, 3, 0.95, 1.0, 2, 4000)]
+
+
+# ------------------------------------------------------------------ long horizons
+def test_long_reference_in_blocks_equals_one_call_and_the_pin_fires_on_a_border():
+    """The cell whose scale drifts: the reference rescales a class at least twice, the ragged
+    partition puts one rescaling on the last frame of a block and one on the first, and both
+    partitions give the bits of the single call."""
+    cell = cr.PIN_CELL
+    assert cell in cr.LONG_CELLS
+    D, K, beta, prior_mass, F, T = cell
+    Y, activity = cr.scene(cell, cr.long_seed_of(cell))
+    gamma1, st1, _ = cr.reference(cell, cr.long_seed_of(cell))
+    frames = sorted({t for t, _, _ in cr.long_pins(cell)})
+    parts = cr.long_partitions(cell)
+    ends = np.cumsum(parts['ragged'])
+    assert len(frames) >= 2 and frames[0] + 1 in ends and frames[1] in ends
+    inner = np.cumsum(parts['blocks'])
+    assert not any(t in inner or t + 1 in inner for t in frames)      # inside the 625-blocks
+    assert np.all(np.abs(cr.scale_exponents(st1['s'])) <= cr.SCALE_BAND)
+
+    def step(Yb, ab, state):
+        return cr.online_cacgmm(Yb, ab, beta, state)[:2]
+    for name, cuts in parts.items():
+        gamma, st = cr.in_blocks(Y, activity, cr.fresh_state(F, K, D, prior_mass), cuts, step)
+        assert np.array_equal(gamma, gamma1), name
+        assert np.array_equal(st['s'], st1['s']) and np.array_equal(st['n'], st1['n']), name
+    # without the pin the same cell leaves the band (and float64's normal range is 1022 wide)
+    lo = [0]
+
+    def watch(t, S, n):
+        lo[0] = min(lo[0], int(cr.scale_exponents(S).min()))
+    cr.online_cacgmm(Y, activity, beta, cr.fresh_state(F, K, D, prior_mass), watch=watch, band=10 ** 6)
+    print(f'{cell}: the exponent reaches {lo[0]} without the pin')
+    assert lo[0] < -cr.SCALE_BAND
+
+
+def test_the_band_is_never_reached_by_the_short_cells():
+    """The extremes that justify SCALE_BAND: with the pin off, the exponent of the largest
+    diagonal entry, watched after every frame, stays inside +-40 on every parity cell, every
+    64-point stream cell and the pipeline scene -- so the pin changes no existing cell."""
+    import gss_oracle as oracle
+    import stream_reference as sr
+    ext = {}
+
+    def run(what, Y, activity, beta, state):
+        def watch(t, S, n):
+            e = cr.scale_exponents(S)
+            lo, hi = ext.get(what, (0, 0))
+            ext[what] = min(lo, int(e.min())), max(hi, int(e.max()))
+        cr.online_cacgmm(Y, activity, beta, state, watch=watch, watch_every=1, band=10 ** 6)
+    for cell in cr.CELLS:
+        D, K, beta, prior_mass, F, T = cell
+        Y, activity = cr.scene(cell, cr.seed_of(cell))
+        run('CELLS', Y, activity, beta, cr.fresh_state(F, K, D, prior_mass))
+    for name, c in sr.CELLS.items():
+        if c[0] > 64:
+            continue
+        x, activity = sr.scene(name, sr.seed_of(name))
+        Obs = sr.reference(name, sr.seed_of(name))[1]['Obs']
+        actf = oracle.activity_time_to_frequency(activity, c[0], c[1], True)[:, :Obs.shape[1]]
+        run('stream', Obs, actf, sr.SETTINGS['gss_forget'], sr.fresh_states(name)['em'])
+    # the pipeline scene: the oracle's stages up to the mixture model, whose frames go through `run`
+    pp, u = cr.PIPE, cr.pipe_scene()
+
+    def gss_fn(Obs, acitivity_freq, iterations, iterations_post):
+        Y = cr.to_ftd(Obs)
+        act = np.asarray(acitivity_freq)[:, :Y.shape[1]]
+        state = cr.fresh_state(Y.shape[0], act.shape[0], Y.shape[2], pp['prior_mass'])
+        run('pipeline', Y, act, pp['forget'], state)
+        return cr.to_ktf(cr.online_cacgmm(Y, act, pp['forget'], state)[0])
+    oracle.enhance_observation(u.obs, u.activity_array, u.target_index, u.ex, wpe_taps=pp['wpe_taps'],
+                               wpe_delay=pp['wpe_delay'], stft_size=pp['stft_size'],
+                               stft_shift=pp['stft_shift'], gss_fn=gss_fn)
+    print(f'exponents without the pin: {ext}')
+    assert sorted(ext) == ['CELLS', 'pipeline', 'stream']
+    for what, (lo, hi) in ext.items():
+        assert -40 <= lo and hi <= 40, (what, lo, hi)
+
+
+def test_reference_is_scale_invariant():
+    """S_k handed in multiplied by 2^e_k, another e_k per class: the same gamma within TOL, and
+    every class back inside the band after the call."""
+    cell = cr.CELLS[0]
+    D, K, beta, prior_mass, F, T = cell
+    Y, activity = cr.scene(cell, cr.seed_of(cell))
+    _, mid, _ = cr.online_cacgmm(Y[:, :20], activity[:, :20], beta, cr.fresh_state(F, K, D, prior_mass))
+    want, _, _ = cr.online_cacgmm(Y[:, 20:], activity[:, 20:], beta, mid)
+    scaled = cr.scaled_state(mid)
+    assert np.abs(cr.scale_exponents(scaled['s'])).min() > 100
+    gamma, st, fallbacks = cr.online_cacgmm(Y[:, 20:], activity[:, 20:], beta, scaled)
+    err = cr.rel_err(gamma, want)
+    print(f'scaled state: gamma moves {err:.1e}')
+    assert fallbacks == 0 and err < cr.TOL
+    assert np.all(np.abs(cr.scale_exponents(st['s'])) <= cr.SCALE_BAND)
+    assert np.array_equal(st['n'].shape, mid['n'].shape) and cr.rel_err(st['n'], cr.online_cacgmm(
+        Y[:, 20:], activity[:, 20:], beta, mid)[1]['n']) < cr.TOL
+
+
+# ------------------------------------------------------------------ the starved class
+def test_the_starved_cell_breaks_the_plain_recursion_and_not_the_guarded_one():
+    """Plain (the recursion without guard and pin): within 8 000 frames cond(S_k) passes 1e15 and
+    np.linalg.cholesky fails.  Guarded: no fallback, cond(S_k) sampled every 100 frames stays
+    at or below STARVED_COND, and the float64 reference lies within STARVED_REFEREE_TOL of the
+    80-bit referee -- the condition under which the device may be held to the referee."""
+    import ext_precision as xp
+    p = cr.STARVED
+    Y, activity = cr.starved_scene()
+    assert Y.shape == (2, 7500, p['D']) and Y.shape[1] <= 8000
+    _, st, fallbacks, cond = cr.starved_reference(plain=True)
+    print(f'plain: {fallbacks} fallbacks, cond(S_k) up to {cond:.1e}, n {np.round(st["n"], 3).tolist()}')
+    assert fallbacks >= 1 and cond > 1e15
+    gamma, st, fallbacks, cond = cr.starved_reference()
+    print(f'guarded: {fallbacks} fallbacks, cond(S_k) up to {cond:.1e}')
+    assert fallbacks == 0 and cond <= cr.STARVED_COND
+    assert st['n'].min() < 0.5 < p['D']                 # a class whose mass is far below D
+    on = activity.any(axis=0)
+    assert np.all(np.isfinite(gamma)) and np.allclose(gamma.sum(axis=1)[:, on], 1.0, atol=1e-12)
+    referee, failed = cr.starved_referee()
+    dist = float(np.max(np.abs(gamma - referee)))
+    print(f'guarded float64 reference vs the 80-bit referee: {dist:.1e}')
+    assert failed == 0 and dist <= cr.STARVED_REFEREE_TOL
 
 
 def test_the_continued_model_follows_a_moving_speaker():
@@ -153,6 +282,51 @@ def test_the_continued_model_follows_a_moving_speaker():
     ratio = cr.evidence_ratio()
     print(f'continued / frozen error: {ratio:.3f}')
     assert ratio <= 0.75 < cr.EVIDENCE_BOUND
+
+
+def test_the_starved_reference_in_blocks_equals_one_call_with_the_guard_live_on_the_cuts():
+    """The rank guard across block borders: in the starved cell the gate phi is above 0.1 on the
+    frame before and the frame after the later 625-frame cuts and around both cuts of the ragged
+    partition's one-frame block, and both partitions give the bits of the single call."""
+    p = cr.STARVED
+    Y, activity = cr.starved_scene()
+    F, T, D = Y.shape
+    gamma1, st1, _, _ = cr.starved_reference()
+    gates = cr.starved_gates()
+    parts = cr.starved_partitions()
+    cuts = np.cumsum(parts['blocks'])[:-1]
+    alive = [int(c) for c in cuts if gates[c - 1] > 0.1 and gates[c] > 0.1]
+    print(f'starved cell: phi up to {gates.max():.2f}, above 0 on {int((gates > 0).sum())} frames; '
+          f'625-frame cuts with phi > 0.1 on both sides: {alive}; ragged {parts["ragged"]}')
+    assert len(alive) >= 3
+    a, b = np.cumsum(parts['ragged'])[1:3]
+    assert b == a + 1 and min(gates[a - 1], gates[a], gates[b]) > 0.1
+
+    def step(Yb, ab, state):
+        return cr.online_cacgmm(Yb, ab, p['beta'], state)[:2]
+    for name, cut in parts.items():
+        gamma, st = cr.in_blocks(Y, activity, cr.fresh_state(F, p['K'], D, p['prior_mass']), cut, step)
+        assert np.array_equal(gamma, gamma1), name
+        assert np.array_equal(st['s'], st1['s']) and np.array_equal(st['n'], st1['n']), name
+
+
+def test_the_long_stream_scene_breaks_the_plain_recursion_and_not_the_guarded_one():
+    """The frames of stream_reference.long_scene (no WPE in front): the recursion without the
+    guard loses factors, the guarded one loses none."""
+    import gss_oracle as oracle
+    import stream_reference as sr
+    p = sr.LONG
+    x, act = sr.long_scene()
+    Y = oracle.stft(x, p['W'], p['H'], fading=True)
+    actf = oracle.activity_time_to_frequency(act, p['W'], p['H'], True)[:, :Y.shape[1]] != 0
+    Y = cr.to_ftd(Y)
+    F, T, D = Y.shape
+    assert 8000 <= T <= 8200
+    counts = [cr.online_cacgmm(Y, actf, sr.SETTINGS['gss_forget'],
+                               cr.fresh_state(F, p['K'], D, sr.SETTINGS['gss_prior_mass']), plain=plain)[2]
+              for plain in (True, False)]
+    print(f'long stream scene: fallbacks plain {counts[0]}, guarded {counts[1]}')
+    assert counts[0] >= 1 and counts[1] == 0
 
 
 # ------------------------------------------------------------------ the C surface

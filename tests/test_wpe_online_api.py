@@ -99,6 +99,21 @@ def test_parity_scenes_are_stable():
         assert moved * wr.STABILITY_MARGIN <= wr.TOL, (cell, moved)
     assert wr.ONCHIP_CELLS[-1][1] * wr.ONCHIP_CELLS[-1][2] == wr.ONCHIP_MAX_N
     assert wr.MEMORY_CELLS[0][1] * wr.MEMORY_CELLS[0][2] == wr.ONCHIP_MAX_N + 1
+    for cell in wr.LONG_CELLS:
+        moved = wr.long_reference_movement(cell, wr.long_seed_of(cell))
+        assert moved * wr.STABILITY_MARGIN <= wr.TOL, (cell, moved)
+    assert [c[1] * c[2] for c in wr.LONG_CELLS] == [40, 120, 12]
+
+
+def test_long_reference_is_its_closed_form():
+    """After thousands of frames the recursion still solves its weighted least-squares problem,
+    also with one channel at 1e-7 of the others."""
+    for cell in wr.LONG_CELLS:
+        st = wr.long_reference(cell, wr.long_seed_of(cell))[1]
+        P, G = wr.long_closed_form(cell, wr.long_seed_of(cell))
+        errs = wr.rel_err(st['P'], P), wr.rel_err(st['G'], G)
+        print(f'{cell}: P, G vs the closed form {errs}')
+        assert max(errs) < wr.CLOSED_FORM_TOL, (cell, errs)
 
 
 # ------------------------------------------------------------------ the C surface
