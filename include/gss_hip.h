@@ -98,7 +98,9 @@ typedef enum {
  * gss_enhance_observation_gss_online with the gss_cacgmm_online_state and gss_em_online
  * descriptors.  So were gss_stream_init, gss_stream_num_frames, gss_stream_num_samples_out,
  * gss_stream_flush_samples, gss_stft_stream, gss_istft_stream and gss_stream_block with the
- * gss_stream_state and gss_stream_cfg descriptors. */
+ * gss_stream_state and gss_stream_cfg descriptors.  So were gss_mvdr_online_targets,
+ * gss_last_mvdr_online_fallbacks_targets, gss_istft_stream_targets and gss_stream_block_targets
+ * (they take the existing descriptors as they are). */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -1148,6 +1150,59 @@ int gss_stream_block(gss_ctx *ctx, const gss_params *params, const gss_stream_cf
                      gss_cacgmm_online_state *em, gss_mvdr_online_state *bf, const void *x_dev,
                      int in_type, const uint8_t *act_dev, int64_t n, int target_index,
                      double *out_dev, const gss_debug_taps *taps);
+
+/* ---- several targets of one stream ---------------------------------------------
+ * S speakers of one stream from one analysis, one online WPE and one online CACGMM: only the
+ * beamformer and the synthesis differ per target.  (Entry points only: revision still 7.)
+ *
+ * gss_mvdr_online for S targets in one launch, one wave per (frequency, target), the masks formed
+ * from the posteriors gamma (F,K,T) as gss_masks_from_posteriors with drop_context = 0 does:
+ * target s has the bits of gss_mvdr_online on the masks of class targets[s].  `targets` is a host
+ * array of S distinct class indices, `states` a host array of S caller-owned states, each advanced
+ * in place.  postfilter = 1: Xhat times the target mask (params->postfilter = 1 of the fused
+ * calls).  mask_x_dev / mask_n_dev: (S,F,T), either may be NULL (no mask table exists then);
+ * Xhat (S,T,F); W (S,F,T,D) or NULL.  T = 0 is a no-op.  The reference channel is
+ * cfg->ref_channel >= 0 (cfg->loading is not read: the states exist).
+ * gss_last_mvdr_online_fallbacks_targets gives the fallback frames per target afterwards,
+ * gss_last_mvdr_online_fallbacks their sum.
+ * GSS_ERR_INVALID before any launch, every state untouched: a NULL table or pointer, S outside
+ * [1, GSS_CACGMM_ONLINE_MAX_CLASSES], a target outside [0, K), the same target twice, two states
+ * sharing a buffer, a state whose F / D differs from the call's, ref_channel < 0, and the errors
+ * of gss_mvdr_online's cfg.  GSS_ERR_UNSUPPORTED: K outside [1, GSS_CACGMM_ONLINE_MAX_CLASSES]. */
+int gss_mvdr_online_targets(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                            const double *gamma_dev, int K, const int32_t *targets, int S, int ban,
+                            const gss_bf_online *cfg, const gss_mvdr_online_state *states,
+                            int postfilter, double *mask_x_dev, double *mask_n_dev,
+                            gss_cplx *Xhat_dev, gss_cplx *W_dev);
+
+/* counts_host[s], s < S: the fallback frames of target s of the last gss_mvdr_online_targets /
+ * gss_stream_block_targets call.  GSS_ERR_INVALID: NULL, S outside [1, that call's S]. */
+int gss_last_mvdr_online_fallbacks_targets(gss_ctx *ctx, int64_t *counts_host, int S);
+
+/* gss_istft_stream for S signals in one set of launches: X (S,Tn,F) -> out (S,m) with
+ * m = gss_stream_num_samples_out(); row s has the bits of gss_istft_stream on X[s].  The
+ * overlap-add tails are the caller's buffer tails_dev (S, size - shift), zero at the start of a
+ * stream; the state's own ola_tail is neither read nor written, its frames_out advances once.
+ * GSS_ERR_INVALID: the errors of gss_istft_stream, tails_dev NULL or the state's ola_tail, S outside
+ * [1, GSS_CACGMM_ONLINE_MAX_CLASSES]. */
+int gss_istft_stream_targets(gss_ctx *ctx, const gss_cplx *X_dev, int64_t Tn, int S,
+                             gss_stream_state *state, double *tails_dev, double *out_dev);
+
+/* gss_stream_block for S targets: its body up to the posteriors, then gss_mvdr_online_targets
+ * (BAN, the postfilter in its epilogue, no mask launch) and gss_istft_stream_targets.  `bf` is a
+ * host array of S states, tails_dev (S, size - shift) the targets' overlap-add tails, out (S,m).
+ * Row s has the bits of gss_stream_block with target_index = targets[s]; the stream, WPE and
+ * CACGMM states those of any such call.  Of the taps target_mask, distortion_mask and Xhat hold S
+ * consecutive per-target blocks and ref_channel S words, as in gss_enhance_observation_targets.
+ * Every argument error returns before any launch, with all states, the tails and `out` untouched:
+ * the errors and codes of gss_stream_block, and GSS_ERR_INVALID for those of
+ * gss_mvdr_online_targets' targets and states and of gss_istft_stream_targets' tails. */
+int gss_stream_block_targets(gss_ctx *ctx, const gss_params *params, const gss_stream_cfg *cfg,
+                             gss_stream_state *state, const gss_wpe_online_state *wpe,
+                             gss_cacgmm_online_state *em, const gss_mvdr_online_state *bf,
+                             double *tails_dev, const void *x_dev, int in_type,
+                             const uint8_t *act_dev, int64_t n, const int32_t *targets, int S,
+                             double *out_dev, const gss_debug_taps *taps);
 
 /* gss_enhance_observation plus gss_posterior_activity on the pipeline's own post-WPE observation
  * and its posteriors before context zeroing (what the taps Obs_ftd and gamma show), nothing

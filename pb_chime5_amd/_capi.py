@@ -275,6 +275,23 @@ SIGNATURES = {
                                  ctypes.POINTER(GssCacgmmOnlineState),
                                  ctypes.POINTER(GssMvdrOnlineState), c_void_p, c_int, c_void_p,
                                  c_int64, c_int, c_void_p, _TAPS]),
+    'gss_mvdr_online_targets': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int,
+                                        ctypes.POINTER(ctypes.c_int32), c_int, c_int,
+                                        ctypes.POINTER(GssBfOnline),
+                                        ctypes.POINTER(GssMvdrOnlineState), c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    'gss_last_mvdr_online_fallbacks_targets': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                                       c_int]),
+    'gss_istft_stream_targets': (c_int, [c_void_p, c_void_p, c_int64, c_int,
+                                         ctypes.POINTER(GssStreamState), c_void_p, c_void_p]),
+    'gss_stream_block_targets': (c_int, [c_void_p, ctypes.POINTER(GssParams),
+                                         ctypes.POINTER(GssStreamCfg),
+                                         ctypes.POINTER(GssStreamState),
+                                         ctypes.POINTER(GssWpeOnlineState),
+                                         ctypes.POINTER(GssCacgmmOnlineState),
+                                         ctypes.POINTER(GssMvdrOnlineState), c_void_p, c_void_p,
+                                         c_int, c_void_p, c_int64, ctypes.POINTER(ctypes.c_int32),
+                                         c_int, c_void_p, _TAPS]),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,
@@ -603,6 +620,14 @@ class Context:
         """(frequency, frame) pairs of the last online MVDR on this context whose noise matrix had
         no Cholesky factor (synchronises)."""
         return self._last('gss_last_mvdr_online_fallbacks', ctypes.c_int64)
+
+    def last_mvdr_online_fallbacks_targets(self, S):
+        """The same per target of the last online MVDR targets call on this context, a list of S
+        counts (synchronises)."""
+        out = (ctypes.c_int64 * int(S))()
+        self._check(self.lib.gss_last_mvdr_online_fallbacks_targets(self.handle, out, int(S)),
+                    'gss_last_mvdr_online_fallbacks_targets')
+        return [int(v) for v in out]
 
     def last_cacgmm_online_fallbacks(self):
         """(frequency, frame, class) triples of the last online CACGMM on this context whose S_k had

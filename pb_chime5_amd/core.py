@@ -1144,12 +1144,14 @@ class Enhancer:
                 if k != speaker_id and k not in garbage]
 
     def stream(self, num_channels, speakers=None, target=None, *, model=None, ref_channel=0,
-               fused=True):
+               fused=True, targets=None):
         """A `streaming.StreamingEnhancer` with this enhancer's settings: samples in and out in
         blocks of any length, the three online stages with carried states.  ``speakers``: the
         names of the classes in activity order (``target`` one of them; `process` then also
         takes the activity as a dict of per-sample tracks) or a class count (``target`` an
         index); or ``model=`` a fitted `CACGMM` for an unguided stream (``target`` an index).
+        ``targets`` in the place of ``target``: several of them, names or indices like it, all
+        extracted in one pass -- `process` and `flush` then return (S, m).
         NotImplementedError, naming the setting, for everything the stream is not built for: it
         needs gss_online and bf_online (bf='mvdrSouden_ban'), wpe_online wherever WPE runs and
         stft_fading, and has no channel selection, segments, interferer nulling or WPD."""
@@ -1187,18 +1189,31 @@ class Enhancer:
             else:
                 names = list(speakers)
                 num_classes = len(names)
-                if target not in names:
-                    raise ValueError(f'target={target!r} is not one of speakers={names!r}')
-                target = names.index(target)
+                if targets is not None:
+                    if isinstance(targets, (str, bytes)) or not hasattr(targets, '__iter__'):
+                        raise ValueError(f'targets={targets!r}: a sequence of names of '
+                                         f'speakers={names!r}')
+                    targets = list(targets)
+                    for name in targets:
+                        if name not in names:
+                            raise ValueError(f'targets: {name!r} is not one of speakers={names!r}')
+                    targets = [names.index(name) for name in targets]
+                else:
+                    if target not in names:
+                        raise ValueError(f'target={target!r} is not one of speakers={names!r}')
+                    target = names.index(target)
         else:
             if speakers is not None:
                 raise ValueError('speakers with model=: the stream is unguided')
             num_classes = None
-        if target is None:
+        if targets is not None and target is not None:
+            raise ValueError('targets together with target: one of the two')
+        if target is None and targets is None:
             raise ValueError('target: the class to extract')
+        which = dict(target=target) if targets is None else dict(targets=targets)
         w, gss, bf = self.wpe_block, self._gss_online(), self._bf_online()
         return StreamingEnhancer(
-            num_channels, num_classes, model=model, target=target, ref_channel=ref_channel,
+            num_channels, num_classes, model=model, ref_channel=ref_channel, **which,
             stft_size=self.stft_size, stft_shift=self.stft_shift, wpe=w is not None,
             wpe_taps=w.taps if w else 10, wpe_delay=w.delay if w else 2,
             wpe_alpha=w.alpha if w else ops.WPE_ONLINE_ALPHA,

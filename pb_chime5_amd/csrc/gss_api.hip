@@ -2656,13 +2656,12 @@ static size_t stream_block_workspace(const gss_params *p, bool guided, int F, in
     return ws.bytes + 4096 + stage + (1 << 16);
 }
 
-extern "C" int gss_stream_block(gss_ctx *ctx, const gss_params *p, const gss_stream_cfg *cfg,
-                                gss_stream_state *st, const gss_wpe_online_state *wpe,
-                                gss_cacgmm_online_state *em, gss_mvdr_online_state *bf, const void *x,
-                                int in_type, const uint8_t *act, int64_t n, int target, double *out,
-                                const gss_debug_taps *taps) {
-    GSS_ENTER_VARIANTS(ctx);
-    const char *const what = "gss_stream_block";
+// The argument rules gss_stream_block and gss_stream_block_targets share, before any launch, in
+// two halves around the rules of the beamformer states and the targets.
+static int check_stream_block_head(gss_ctx *ctx, const char *what, const gss_params *p,
+                                   const gss_stream_cfg *cfg, const gss_stream_state *st,
+                                   const gss_cacgmm_online_state *em, const void *bf, const void *x,
+                                   int in_type, const uint8_t *act, int64_t n, const double *out) {
     GSS_REQUIRE(ctx, cfg, GSS_ERR_INVALID, "%s: cfg is NULL", what);
     GSS_REQUIRE(ctx, em, GSS_ERR_INVALID, "%s: the CACGMM state is NULL", what);
     GSS_REQUIRE(ctx, bf, GSS_ERR_INVALID, "%s: the MVDR state is NULL", what);
@@ -2675,14 +2674,18 @@ extern "C" int gss_stream_block(gss_ctx *ctx, const gss_params *p, const gss_str
                 "%s: bf=%d, only 0 ('mvdrSouden_ban') has an online form", what, p->bf);
     GSS_TRY(check_stream_input(ctx, what, x, in_type, act, n, st));
     const int D = st->D, K = em->K, F = p->stft_size / 2 + 1;
-    const bool guided = act != nullptr;
     GSS_TRY(check_em_online_shape(ctx, what, F, K, D));
     GSS_TRY(check_cacgmm_online_state(ctx, what, em, F, K, D));
-    GSS_REQUIRE(ctx, !guided || st->K == K, GSS_ERR_INVALID,
+    GSS_REQUIRE(ctx, !act || st->K == K, GSS_ERR_INVALID,
                 "%s: the stream carries the activity of %d classes, the CACGMM state has %d", what,
                 (int)st->K, K);
-    GSS_TRY(check_mvdr_online_state(ctx, what, bf, F, D));
-    GSS_TRY(check_target_index(ctx, target, K));
+    return GSS_OK;
+}
+
+static int check_stream_block_tail(gss_ctx *ctx, const char *what, const gss_params *p,
+                                   const gss_stream_cfg *cfg, const gss_stream_state *st,
+                                   const gss_wpe_online_state *wpe) {
+    const int D = st->D, F = p->stft_size / 2 + 1;
     const gss_em_online em_cfg{cfg->em_forget, 1.0};
     GSS_TRY(check_em_online(ctx, what, &em_cfg));
     const gss_bf_online bf_cfg{cfg->bf_forget, 1.0, cfg->ref_channel, 0, 1.0};
@@ -2692,12 +2695,29 @@ extern "C" int gss_stream_block(gss_ctx *ctx, const gss_params *p, const gss_str
     GSS_TRY(check_bf_online(ctx, what, &bf_cfg, D));
     GSS_REQUIRE(ctx, (wpe != nullptr) == (p->wpe != 0), GSS_ERR_INVALID,
                 "%s: params->wpe = %d %s a WPE state", what, p->wpe, wpe ? "with" : "without");
-    const int A = wpe_arrays_of(p);
     if (p->wpe) {
+        const int A = wpe_arrays_of(p);
         GSS_TRY(check_wpe_online_state(ctx, what, wpe));
         GSS_TRY(check_wpe_arrays(ctx, p, D));
         GSS_TRY(check_wpe_online(ctx, what, F, A, D / A, p->wpe_taps, p->wpe_delay, cfg->wpe_alpha));
     }
+    return GSS_OK;
+}
+
+extern "C" int gss_stream_block(gss_ctx *ctx, const gss_params *p, const gss_stream_cfg *cfg,
+                                gss_stream_state *st, const gss_wpe_online_state *wpe,
+                                gss_cacgmm_online_state *em, gss_mvdr_online_state *bf, const void *x,
+                                int in_type, const uint8_t *act, int64_t n, int target, double *out,
+                                const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *const what = "gss_stream_block";
+    GSS_TRY(check_stream_block_head(ctx, what, p, cfg, st, em, bf, x, in_type, act, n, out));
+    const int D = st->D, K = em->K, F = p->stft_size / 2 + 1;
+    const bool guided = act != nullptr;
+    GSS_TRY(check_mvdr_online_state(ctx, what, bf, F, D));
+    GSS_TRY(check_target_index(ctx, target, K));
+    GSS_TRY(check_stream_block_tail(ctx, what, p, cfg, st, wpe));
+    const int A = wpe_arrays_of(p);
     if (n == 0) return GSS_OK;
 
     const int64_t Tn = gss_stream_num_frames(st->received, n, p->stft_size, p->stft_shift);
@@ -2740,6 +2760,212 @@ extern "C" int gss_stream_block(gss_ctx *ctx, const gss_params *p, const gss_str
         GSS_TRY(copy_tap(ctx, taps->distortion_mask, b.mn, sizeof(double) * (size_t)F * Tn));
         GSS_TRY(copy_tap(ctx, taps->Xhat, b.Xhat, sizeof(cplx) * (size_t)F * Tn));
         GSS_TRY(copy_tap(ctx, taps->ref_channel, b.ref, sizeof(int32_t)));
+    }
+    return GSS_OK;
+}
+
+// ------------------------------------------------------------------ S targets of one stream
+// The targets and their beamformer states, before any launch: 1 <= S <= 8 distinct classes of
+// [0, K), S states of the call's F and D, no buffer handed in twice.
+static int check_online_targets(gss_ctx *ctx, const char *what, const int32_t *targets, int S, int K,
+                                const gss_mvdr_online_state *states, int F, int D) {
+    GSS_REQUIRE(ctx, S >= 1 && S <= GSS_CACGMM_ONLINE_MAX_CLASSES, GSS_ERR_INVALID,
+                "%s: S = %d outside [1, %d]", what, S, GSS_CACGMM_ONLINE_MAX_CLASSES);
+    GSS_REQUIRE(ctx, targets, GSS_ERR_INVALID, "%s: targets is NULL", what);
+    GSS_REQUIRE(ctx, states, GSS_ERR_INVALID, "%s: the MVDR states are NULL", what);
+    for (int s = 0; s < S; ++s) {
+        GSS_TRY(check_target_index(ctx, targets[s], K));
+        for (int r = 0; r < s; ++r)
+            GSS_REQUIRE(ctx, targets[r] != targets[s], GSS_ERR_INVALID,
+                        "%s: target %d is given twice (targets[%d] and targets[%d])", what,
+                        (int)targets[s], r, s);
+        GSS_TRY(check_mvdr_online_state(ctx, what, &states[s], F, D));
+        for (int r = 0; r < s; ++r)
+            GSS_REQUIRE(ctx, states[r].phi_x != states[s].phi_x && states[r].phi_x != states[s].phi_n &&
+                                 states[r].phi_n != states[s].phi_x && states[r].phi_n != states[s].phi_n,
+                        GSS_ERR_INVALID, "%s: states[%d] and states[%d] share a buffer", what, r, s);
+    }
+    return GSS_OK;
+}
+
+struct OnlineTargetStates {
+    cplx *phi_x[GSS_CACGMM_ONLINE_MAX_CLASSES], *phi_n[GSS_CACGMM_ONLINE_MAX_CLASSES];
+    OnlineTargetStates(const gss_mvdr_online_state *states, int S) {
+        for (int s = 0; s < S; ++s) {
+            phi_x[s] = reinterpret_cast<cplx *>(states[s].phi_x);
+            phi_n[s] = reinterpret_cast<cplx *>(states[s].phi_n);
+        }
+    }
+};
+
+extern "C" int gss_mvdr_online_targets(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                                       const double *gamma, int K, const int32_t *targets, int S,
+                                       int ban, const gss_bf_online *cfg,
+                                       const gss_mvdr_online_state *states, int postfilter,
+                                       double *mx, double *mn, gss_cplx *Xhat, gss_cplx *W) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_mvdr_online_targets";
+    GSS_REQUIRE(ctx, Y, GSS_ERR_INVALID, "%s: Y_dev is NULL", what);
+    GSS_REQUIRE(ctx, gamma, GSS_ERR_INVALID, "%s: gamma_dev is NULL", what);
+    GSS_REQUIRE(ctx, Xhat, GSS_ERR_INVALID, "%s: Xhat_dev is NULL", what);
+    GSS_REQUIRE(ctx, T >= 0, GSS_ERR_INVALID, "%s: T = %lld is negative", what, (long long)T);
+    GSS_REQUIRE(ctx, postfilter == 0 || postfilter == 1, GSS_ERR_INVALID, "%s: postfilter = %d", what,
+                postfilter);
+    GSS_TRY(check_em_online_shape(ctx, what, F, K, D));
+    GSS_TRY(check_bf_online(ctx, what, cfg, D));
+    GSS_REQUIRE(ctx, cfg->ref_channel >= 0, GSS_ERR_INVALID,
+                "%s: ref_channel = %d, the targets of a stream have no window to choose one over",
+                what, (int)cfg->ref_channel);
+    GSS_TRY(check_online_targets(ctx, what, targets, S, K, states, F, D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
+    GSS_REQUIRE(ctx, !W || (int64_t)S * F * T * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "%s: S * F * T * D is 2^31 or more", what);
+    if (T == 0) return GSS_OK;
+    GSS_TRY(arena_reserve(ctx, mvdr_online_targets_workspace_bytes(F, S)));
+    const OnlineTargetStates st(states, S);
+    return mvdr_online_targets_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, gamma, K, targets,
+                                   S, ban != 0, cfg->forget, cfg->ref_channel, st.phi_x, st.phi_n,
+                                   postfilter, mx, mn, reinterpret_cast<cplx *>(Xhat),
+                                   reinterpret_cast<cplx *>(W), nullptr);
+}
+
+extern "C" int gss_last_mvdr_online_fallbacks_targets(gss_ctx *ctx, int64_t *counts, int S) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_last_mvdr_online_fallbacks_targets";
+    GSS_REQUIRE(ctx, counts, GSS_ERR_INVALID, "%s: NULL", what);
+    GSS_REQUIRE(ctx, S >= 1 && S <= ctx->last_online_targets, GSS_ERR_INVALID,
+                "%s: S = %d, the last online MVDR targets call had %d target(s)", what, S,
+                ctx->last_online_targets);
+    GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int s = 0; s < S; ++s)
+        counts[s] = __atomic_load_n(ctx->status_host + GSS_STATUS_MVDR_ONLINE_TARGETS + s,
+                                    __ATOMIC_ACQUIRE);
+    return GSS_OK;
+}
+
+extern "C" int gss_istft_stream_targets(gss_ctx *ctx, const gss_cplx *X, int64_t Tn, int S,
+                                        gss_stream_state *state, double *tails, double *out) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_istft_stream_targets";
+    GSS_TRY(check_stream_state(ctx, what, state));
+    GSS_REQUIRE(ctx, X, GSS_ERR_INVALID, "%s: X_dev is NULL", what);
+    GSS_REQUIRE(ctx, tails, GSS_ERR_INVALID, "%s: tails_dev is NULL", what);
+    GSS_REQUIRE(ctx, out, GSS_ERR_INVALID, "%s: out_dev is NULL", what);
+    GSS_REQUIRE(ctx, S >= 1 && S <= GSS_CACGMM_ONLINE_MAX_CLASSES, GSS_ERR_INVALID,
+                "%s: S = %d outside [1, %d]", what, S, GSS_CACGMM_ONLINE_MAX_CLASSES);
+    GSS_REQUIRE(ctx, tails != state->ola_tail, GSS_ERR_INVALID,
+                "%s: tails_dev is the stream state's own ola_tail", what);
+    GSS_REQUIRE(ctx, Tn >= 0, GSS_ERR_INVALID, "%s: Tn = %lld is negative", what, (long long)Tn);
+    GSS_REQUIRE(ctx, state->frames_out + Tn <= state->received / state->shift, GSS_ERR_INVALID,
+                "%s: Tn = %lld frames after %lld, the stream has analysed %lld", what, (long long)Tn,
+                (long long)state->frames_out, (long long)(state->received / state->shift));
+    GSS_REQUIRE(ctx, (int64_t)S * Tn < 2147483647, GSS_ERR_UNSUPPORTED, "%s: too many frames", what);
+    if (Tn == 0) return GSS_OK;
+    GSS_TRY(arena_reserve(ctx, stream_istft_targets_workspace_bytes(Tn, S, state->size, state->shift)));
+    return stream_istft_targets_run(ctx, reinterpret_cast<const cplx *>(X), Tn, S, state, tails, out);
+}
+
+// The buffers of one block of a stream of S targets, taken first; no mask table without the taps.
+struct StreamTargetsBuffers {
+    cplx *Y, *X;        // the block's STFT and the WPE output; no WPE: X is Y
+    uint8_t *actf;      // (K,Tn), NULL for an unguided stream
+    double *gamma;
+    double *mx, *mn;    // (S,F,Tn) each, NULL without the taps
+    cplx *Xhat;         // (S,Tn,F)
+    int32_t *ref;       // (S,)
+};
+static StreamTargetsBuffers stream_targets_blocks(Workspace &ws, bool wpe, bool guided, bool masks,
+                                                  int F, int64_t Tn, int D, int K, int S) {
+    const size_t ft = (size_t)F * Tn;
+    StreamTargetsBuffers b;
+    b.Y = ws.take<cplx>(ft * D, "stream Y");
+    b.X = wpe ? ws.take<cplx>(ft * D, "stream X") : b.Y;
+    b.actf = guided ? ws.take<uint8_t>((size_t)K * Tn, "stream frame activity") : nullptr;
+    b.gamma = ws.take<double>(ft * K, "stream gamma");
+    b.mx = masks ? ws.take<double>(ft * S, "stream target masks") : nullptr;
+    b.mn = masks ? ws.take<double>(ft * S, "stream distortion masks") : nullptr;
+    b.Xhat = ws.take<cplx>(ft * S, "stream Xhat of the targets");
+    b.ref = ws.take<int32_t>(GSS_CACGMM_ONLINE_MAX_CLASSES, "stream refs");
+    return b;
+}
+
+static size_t stream_targets_workspace(const gss_params *p, bool guided, bool masks, int F, int64_t Tn,
+                                       int D, int K, int S) {
+    size_t stage = stream_stft_workspace_bytes(Tn, D, guided ? K : 0, p->stft_size, p->stft_shift);
+    if (Tn == 0) return stage + (1 << 16);
+    Workspace ws;
+    stream_targets_blocks(ws, p->wpe != 0, guided, masks, F, Tn, D, K, S);
+    if (p->wpe)
+        stage = std::max(stage, wpe_online_workspace_bytes(F, Tn, wpe_arrays_of(p), D / wpe_arrays_of(p),
+                                                           p->wpe_taps, p->wpe_delay, false));
+    stage = std::max(stage, cacgmm_online_workspace_bytes(F, K, D, false));
+    stage = std::max(stage, mvdr_online_targets_workspace_bytes(F, S));
+    stage = std::max(stage, stream_istft_targets_workspace_bytes(Tn, S, p->stft_size, p->stft_shift));
+    return ws.bytes + 4096 + stage + (1 << 16);
+}
+
+extern "C" int gss_stream_block_targets(gss_ctx *ctx, const gss_params *p, const gss_stream_cfg *cfg,
+                                        gss_stream_state *st, const gss_wpe_online_state *wpe,
+                                        gss_cacgmm_online_state *em,
+                                        const gss_mvdr_online_state *bf, double *tails, const void *x,
+                                        int in_type, const uint8_t *act, int64_t n,
+                                        const int32_t *targets, int S, double *out,
+                                        const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *const what = "gss_stream_block_targets";
+    GSS_TRY(check_stream_block_head(ctx, what, p, cfg, st, em, bf, x, in_type, act, n, out));
+    GSS_REQUIRE(ctx, tails, GSS_ERR_INVALID, "%s: tails_dev is NULL", what);
+    GSS_REQUIRE(ctx, tails != st->ola_tail, GSS_ERR_INVALID,
+                "%s: tails_dev is the stream state's own ola_tail", what);
+    const int D = st->D, K = em->K, F = p->stft_size / 2 + 1;
+    const bool guided = act != nullptr;
+    GSS_TRY(check_online_targets(ctx, what, targets, S, K, bf, F, D));
+    GSS_TRY(check_stream_block_tail(ctx, what, p, cfg, st, wpe));
+    const int A = wpe_arrays_of(p);
+    if (n == 0) return GSS_OK;
+
+    const int64_t Tn = gss_stream_num_frames(st->received, n, p->stft_size, p->stft_shift);
+    GSS_REQUIRE(ctx, (int64_t)S * Tn < 2147483647, GSS_ERR_UNSUPPORTED, "%s: too many frames", what);
+    const bool masks = taps && (taps->target_mask || taps->distortion_mask);
+    GSS_TRY(arena_reserve(ctx, stream_targets_workspace(p, guided, masks, F, Tn, D, K, S)));
+    if (Tn == 0)    // the samples enter the history, no frame is complete yet
+        return stream_stft_run(ctx, x, in_type, act, n, st, nullptr, nullptr);
+    Workspace ws(ctx);
+    const StreamTargetsBuffers b = stream_targets_blocks(ws, p->wpe != 0, guided, masks, F, Tn, D, K, S);
+    GSS_TRY(ws.status(what));
+    const size_t mark = ctx->arena_off;
+    GSS_TRY(stream_stft_run(ctx, x, in_type, act, n, st, b.Y, b.actf));
+    GSS_TRY(arena_release(ctx, mark));
+    // no solve in this call: clear the pivot count an earlier utterance left behind
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + GSS_STATUS_WPE_ZERO_PIVOTS, 0,
+                                      sizeof(int32_t), ctx->stream));
+    if (p->wpe) {
+        GSS_TRY(wpe_online_run(ctx, b.Y, F, Tn, A, D / A, p->wpe_taps, p->wpe_delay, cfg->wpe_alpha,
+                               reinterpret_cast<cplx *>(wpe->inv_cov_dev),
+                               reinterpret_cast<cplx *>(wpe->filter_dev),
+                               reinterpret_cast<cplx *>(wpe->history_dev), b.X,
+                               gss_variant_set("wpe_online_mem")));
+        GSS_TRY(arena_release(ctx, mark));
+    }
+    const EmGuide guide = guided ? em_guide_from_activity(b.actf, Tn) : EmGuide{};
+    GSS_TRY(cacgmm_online_run(ctx, b.X, F, Tn, D, guide, K, cfg->em_forget, 1.0,
+                              reinterpret_cast<cplx *>(em->s), em->n, b.gamma));
+    GSS_TRY(arena_release(ctx, mark));
+    const OnlineTargetStates states(bf, S);
+    GSS_TRY(mvdr_online_targets_run(ctx, b.X, F, Tn, D, b.gamma, K, targets, S, /*ban=*/1,
+                                    cfg->bf_forget, cfg->ref_channel, states.phi_x, states.phi_n,
+                                    p->postfilter == 1, b.mx, b.mn, b.Xhat, nullptr, b.ref));
+    GSS_TRY(arena_release(ctx, mark));
+    GSS_TRY(stream_istft_targets_run(ctx, b.Xhat, Tn, S, st, tails, out));
+    if (taps) {
+        const size_t ft = (size_t)F * Tn;
+        GSS_TRY(copy_tap(ctx, taps->Obs_ftd, b.X, sizeof(cplx) * ft * D));
+        if (guided) GSS_TRY(copy_tap(ctx, taps->act_frames, b.actf, (size_t)K * Tn));
+        GSS_TRY(copy_tap(ctx, taps->gamma, b.gamma, sizeof(double) * ft * K));
+        GSS_TRY(copy_tap(ctx, taps->target_mask, b.mx, sizeof(double) * ft * S));
+        GSS_TRY(copy_tap(ctx, taps->distortion_mask, b.mn, sizeof(double) * ft * S));
+        GSS_TRY(copy_tap(ctx, taps->Xhat, b.Xhat, sizeof(cplx) * ft * S));
+        GSS_TRY(copy_tap(ctx, taps->ref_channel, b.ref, sizeof(int32_t) * S));
     }
     return GSS_OK;
 }

@@ -220,6 +220,9 @@ struct gss_ctx {
     int32_t *status_host = nullptr;
     int32_t *status_dev = nullptr;
     int last_targets = 0;   // S of the last beamformer run when it was a targets call, else 0
+    // [GSS_STATUS_MVDR_ONLINE_TARGETS + s]: fallback frames of target s of the last online MVDR
+    // targets call (mvdr_online_targets_run, which leaves their sum in [8])
+    int last_online_targets = 0;   // S of that call, 0 = none yet
     // [GSS_STATUS_CHANNELS + j]: the j-th channel (ascending) the last channel selection kept,
     // written by chsel_pick_kernel
     int last_selected = 0;  // n of the last channel selection on this context, 0 = none yet
@@ -246,7 +249,8 @@ struct gss_ctx {
 #define GSS_STATUS_CACGMM_ONLINE_BAD_MODEL 10                     // classes of the last model -> state conversion without a Cholesky factor
 #define GSS_STATUS_TARGETS 16                                   // first per-target word
 #define GSS_STATUS_CHANNELS 40                                   // first selected-channel word
-#define GSS_STATUS_BYTES (4 * (GSS_STATUS_CHANNELS + GSS_MAX_CHANNELS))
+#define GSS_STATUS_MVDR_ONLINE_TARGETS (GSS_STATUS_CHANNELS + GSS_MAX_CHANNELS)   // fallback frames per target of the last online MVDR targets call
+#define GSS_STATUS_BYTES (4 * (GSS_STATUS_MVDR_ONLINE_TARGETS + GSS_CACGMM_ONLINE_MAX_CLASSES))
 static_assert(GSS_STATUS_TARGETS + GSS_MAX_CLASSES + 1 <= GSS_STATUS_CHANNELS, "status words overlap");
 
 int gss_fail(gss_ctx *ctx, int code, const char *fmt, ...);
@@ -615,6 +619,17 @@ int mvdr_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const 
                     const double *mn, int ban, double beta, double loading, int ref, cplx *phi_x,
                     cplx *phi_n, cplx *X, int64_t xs_f, int64_t xs_t, cplx *W,
                     int32_t *ref_out = nullptr);
+// S targets of one stream from the posteriors gamma (F,K,T): phi_x / phi_n the S callers' states,
+// X (S,T,F), the masks mx / mn (S,F,T) or NULL, W (S,F,T,D) or NULL, ref_out (S,) or NULL.
+// postfilter: X times the target mask.  The fallback frames go to the words
+// GSS_STATUS_MVDR_ONLINE_TARGETS + s, their sum to GSS_STATUS_MVDR_ONLINE_FALLBACKS.  T >= 1,
+// ref >= 0, 1 <= S <= GSS_CACGMM_ONLINE_MAX_CLASSES.
+size_t mvdr_online_targets_workspace_bytes(int F, int S);
+int mvdr_online_targets_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
+                            const double *gamma, int K, const int32_t *targets, int S, int ban,
+                            double beta, int ref, cplx *const *phi_x, cplx *const *phi_n,
+                            int postfilter, double *mx, double *mn, cplx *X, cplx *W,
+                            int32_t *ref_out);
 
 // Online CACGMM (cacgmm_online.hip; include/gss_hip.h: gss_cacgmm_online).  Y (F,T,D), the mask of
 // `guide` (its initialisation is not read) -> gamma (F,K,T); S (F,K,D,D), n (F,K) the caller's
@@ -641,6 +656,11 @@ int stream_init_run(gss_ctx *ctx, gss_stream_state *st);
 int stream_stft_run(gss_ctx *ctx, const void *x, int in_type, const uint8_t *act, int64_t n,
                     gss_stream_state *st, cplx *Y, uint8_t *actf);
 int stream_istft_run(gss_ctx *ctx, const cplx *X, int64_t Tn, gss_stream_state *st, double *out);
+// S signals of one stream: X (S,Tn,F) -> out (S,m), the overlap-add tails (S, size - shift) the
+// caller's; st->ola_tail is neither read nor written, st->frames_out advances once.
+size_t stream_istft_targets_workspace_bytes(int64_t Tn, int S, int size, int shift);
+int stream_istft_targets_run(gss_ctx *ctx, const cplx *X, int64_t Tn, int S, gss_stream_state *st,
+                             double *tails, double *out);
 
 int selftest_mfma_run(gss_ctx *ctx);
 

@@ -237,6 +237,209 @@ __global__ __launch_bounds__(64) void mvdr_online_kernel(MolArgs a) {
     if (lane == 0 && nfall) atomicAdd(a.fallbacks, nfall);
 }
 
+// S targets of one stream (gss_mvdr_online_targets).
+struct MolTargetsArgs {
+    const cplx *Y;           // (F, T, D)
+    const double *gamma;     // (F, K, T): the posteriors, the masks are formed here
+    cplx *phi_x[GSS_CACGMM_ONLINE_MAX_CLASSES], *phi_n[GSS_CACGMM_ONLINE_MAX_CLASSES];  // (F, D, D) each
+    int32_t target[GSS_CACGMM_ONLINE_MAX_CLASSES];
+    double *mx, *mn;         // (S, F, T) or NULL: the masks, for the debug taps only
+    cplx *X;                 // (S, T, F)
+    cplx *W;                 // (S, F, T, D) or NULL
+    int32_t *fallbacks;      // (S, F): the fallback frames of every wave
+    int32_t *status;         // status word of the reference channel
+    int32_t *ref_out;        // (S,) the reference channel used, or NULL
+    int64_t T;
+    int F, D, K, ref, ban, postfilter;
+    double beta;
+};
+
+// grid (F, S): one wave per (frequency, target), no LDS and no barrier shared between the waves
+// of a frequency.  The frame body is mvdr_online_kernel's, statement for statement (kept apart so
+// that the one-target kernel's code object does not move): target s has the bits of that kernel
+// on the masks of class target[s].  What differs is around it: the masks come from the posteriors
+// -- a = gamma[target], b = the sum over k != target in ascending k from 0.0, masks_kernel's
+// expressions --, whose K values of frame t + 1 are fetched while frame t's chain runs; the
+// postfilter 'mask_mul' (re a, im a: mask_mul_kernel's product) is applied to the stored value;
+// X is (S, T, F).
+template <int NR>
+__global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int ld = 8 * NR + 1;
+    constexpr int KMAX = GSS_CACGMM_ONLINE_MAX_CLASSES;
+    const int D = a.D, K = a.K, F = a.F;
+    cplx *PX = reinterpret_cast<cplx *>(smem);
+    cplx *PN = PX + D * ld;
+    cplx *M = PN + D * ld;
+    cplx *yb = M + D * ld;      // 8 NR each
+    cplx *cb = yb + 8 * NR;
+    cplx *wb = cb + 8 * NR;
+    double *dinv = reinterpret_cast<double *>(wb + 8 * NR);
+    const int f = blockIdx.x, s = blockIdx.y, lane = threadIdx.x;
+    const int tx = lane & 7, ty = lane >> 3;
+    const bool row = lane < D;
+    const int64_t T = a.T;
+    const cplx zero = c_make(0.0, 0.0);
+    const int target = a.target[s], ref = a.ref;
+    const cplx *Yf = a.Y + (int64_t)f * T * D;
+    const double *gf = a.gamma + (int64_t)f * K * T;
+    const int64_t sf = (int64_t)s * F + f;
+    double *mxf = a.mx ? a.mx + sf * T : nullptr, *mnf = a.mn ? a.mn + sf * T : nullptr;
+    cplx *Xs = a.X + (int64_t)s * T * F + f;
+    cplx *Wf = a.W ? a.W + sf * T * D : nullptr;
+    cplx *gx = a.phi_x[s] + (int64_t)f * D * D, *gn = a.phi_n[s] + (int64_t)f * D * D;
+
+    if (f == 0 && lane == 0) {
+        if (s == 0) __hip_atomic_store(a.status, ref, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (a.ref_out) a.ref_out[s] = ref;
+    }
+    mol_load(gx, PX, D, ld, lane);
+    mol_load(gn, PN, D, ld, lane);
+    wave_sync();
+
+    const double beta = a.beta;
+    cplx y_next = row ? Yf[lane] : zero;
+    double g_next[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) g_next[k] = k < K ? gf[(int64_t)k * T] : 0.0;
+    int nfall = 0;
+    for (int64_t t = 0; t < T; ++t) {
+        const cplx y = y_next;
+        double ma = 0.0, mb = 0.0;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                if (k == target) ma = g_next[k];
+                else mb += g_next[k];
+            }
+        if (row) yb[lane] = y;
+        if (t + 1 < T) {
+            if (row) y_next = Yf[(t + 1) * D + lane];
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k)
+                if (k < K) g_next[k] = gf[(int64_t)k * T + t + 1];
+        }
+        wave_sync();
+        // the two running sums; the sweep's tile is the upper triangle of the new Phi_N
+        cplx reg[NR][NR];
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai)
+#pragma unroll
+            for (int bi = 0; bi < NR; ++bi) {
+                const int i = ty + 8 * ai, k = tx + 8 * bi;
+                reg[ai][bi] = zero;
+                if (i < D && k < D) {
+                    const cplx o = c_outer(yb[i], yb[k]);
+                    const cplx px = PX[i * ld + k], pn = PN[i * ld + k];
+                    PX[i * ld + k] = c_make(fma(beta, px.x, ma * o.x), fma(beta, px.y, ma * o.y));
+                    const cplx nn = c_make(fma(beta, pn.x, mb * o.x), fma(beta, pn.y, mb * o.y));
+                    PN[i * ld + k] = nn;
+                    if (k >= i) reg[ai][bi] = nn;
+                }
+            }
+        wave_sync();
+        const bool ok = chol_inverse_sweep<8, NR, true>(reg, D, M, ld, dinv, tx, ty);
+        cplx w = zero, x = zero;
+        if (!ok) {   // decided by the pivots alone, the same in every lane
+            ++nfall;
+        } else {
+            double trp = 0.0;
+#pragma unroll
+            for (int ai = 0; ai < NR; ++ai) {
+                const int i = ty + 8 * ai;
+                if (i < D) {
+                    cplx acc[NR];
+#pragma unroll
+                    for (int bi = 0; bi <= ai; ++bi) acc[bi] = zero;
+                    for (int j = 0; j < i; ++j) {
+                        const cplx m = M[i * ld + j];
+#pragma unroll
+                        for (int bi = 0; bi <= ai; ++bi) c_fma(acc[bi], m, PX[j * ld + min(tx + 8 * bi, D - 1)]);
+                    }
+                    const double d2 = dinv[i] * dinv[i];
+#pragma unroll
+                    for (int bi = 0; bi <= ai; ++bi) {
+                        const int k = tx + 8 * bi;
+                        if (k <= i) {
+                            const cplx bu = c_add(acc[bi], PX[i * ld + k]);
+                            const cplx m = k < i ? M[i * ld + k] : c_make(1.0, 0.0);
+                            trp = fma(d2, fma(bu.x, m.x, bu.y * m.y), trp);
+                        }
+                    }
+                }
+            }
+            if (row) {
+                cplx acc = zero;
+                for (int j = 0; j < lane; ++j) c_fma(acc, M[lane * ld + j], PX[j * ld + ref]);
+                acc = c_add(acc, PX[lane * ld + ref]);
+                cb[lane] = c_scale(acc, dinv[lane] * dinv[lane]);
+            }
+            const double tr = wave_sum(trp);
+            wave_sync();
+            if (row) {
+                cplx acc = cb[lane];
+                for (int i = lane + 1; i < D; ++i) c_cfma(acc, M[i * ld + lane], cb[i]);
+                w = c_scale(acc, 1.0 / fmax(tr, 1e-10));
+            }
+            if (a.ban) {
+                if (row) wb[lane] = w;
+                wave_sync();
+                cplx v = zero;
+                if (row)
+                    for (int k = 0; k < D; ++k) c_cfma(v, PN[k * ld + lane], wb[k]);
+                const double vv = wave_sum(fma(v.x, v.x, v.y * v.y));
+                cplx wv = zero;
+                c_cfma(wv, w, v);
+                const double wr = wave_sum(wv.x), wi = wave_sum(wv.y);
+                const double den = hypot(wr, wi);
+                w = c_scale(w, den == 0.0 ? 0.0 : sqrt(vv) / den);
+            }
+            cplx p = zero;
+            c_cfma(p, w, y);
+            x = c_make(wave_sum(p.x), wave_sum(p.y));
+        }
+        if (lane == 0) {
+            Xs[t * F] = a.postfilter ? c_scale(x, ma) : x;
+            if (mxf) mxf[t] = ma;
+            if (mnf) mnf[t] = mb;
+        }
+        if (Wf && row) Wf[t * D + lane] = w;
+    }
+    wave_sync();
+    for (int idx = lane; idx < D * D; idx += 64) {
+        const int r = idx / D, c = idx - r * D;
+        gx[idx] = PX[r * ld + c];
+        gn[idx] = PN[r * ld + c];
+    }
+    if (lane == 0) a.fallbacks[sf] = nfall;   // every wave writes its own word: no atomic, no memset
+}
+
+// counts (S, F) -> words[1 + s] = the sum over f of target s, words[0] = the sum over the targets.
+// One workgroup: thread j sums the values j, j + 256, ... of a target, a fixed tree adds the 256
+// partial sums.
+__global__ __launch_bounds__(256) void mvdr_online_targets_count_kernel(
+    const int32_t *__restrict__ counts, int F, int S, int32_t *__restrict__ words) {
+    __shared__ int32_t part[256];
+    const int tid = threadIdx.x;
+    int32_t total = 0;
+    for (int s = 0; s < S; ++s) {
+        int32_t acc = 0;
+        for (int f = tid; f < F; f += 256) acc += counts[(int64_t)s * F + f];
+        part[tid] = acc;
+        __syncthreads();
+        for (int h = 128; h > 0; h >>= 1) {
+            if (tid < h) part[tid] += part[tid + h];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            words[1 + s] = part[0];
+            total += part[0];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) words[0] = total;
+}
+
 size_t mol_lds_bytes(int D) {
     const size_t nr = (size_t)(D + 7) / 8, ld = 8 * nr + 1;
     return sizeof(cplx) * (3 * (size_t)D * ld + 3 * 8 * nr) + sizeof(double) * 8 * nr;
@@ -328,5 +531,75 @@ int mvdr_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const 
     // the count of this call -> the context's status word
     GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_MVDR_ONLINE_FALLBACKS, words,
                                       sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return GSS_OK;
+}
+
+// the counters of a targets call: one word per wave, and their sums: [0] over everything,
+// [1 + s] of target s
+struct MolTargetsWork {
+    int32_t *counts, *words;
+};
+static MolTargetsWork mol_targets_blocks(Workspace &ws, int F, int S) {
+    MolTargetsWork k;
+    k.counts = ws.take<int32_t>((size_t)S * F, "online mvdr targets counts");
+    k.words = ws.take<int32_t>(1 + GSS_CACGMM_ONLINE_MAX_CLASSES, "online mvdr targets words");
+    return k;
+}
+
+size_t mvdr_online_targets_workspace_bytes(int F, int S) {
+    Workspace ws;
+    mol_targets_blocks(ws, F, S);
+    return ws.bytes + 4096;
+}
+
+// S targets (1 <= S <= GSS_CACGMM_ONLINE_MAX_CLASSES) from the posteriors gamma (F,K,T), each
+// with the caller's state, advanced in place.  X (S,T,F); mx / mn (S,F,T) or NULL; W (S,F,T,D)
+// or NULL; ref_out (S,) or NULL.  The arguments have been validated by the entry point (T >= 1,
+// ref >= 0).
+int mvdr_online_targets_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
+                            const double *gamma, int K, const int32_t *targets, int S, int ban,
+                            double beta, int ref, cplx *const *phi_x, cplx *const *phi_n,
+                            int postfilter, double *mx, double *mn, cplx *X, cplx *W,
+                            int32_t *ref_out) {
+    Workspace ws(ctx);
+    const MolTargetsWork k = mol_targets_blocks(ws, F, S);
+    GSS_TRY(ws.status("online mvdr targets"));
+    int32_t *words = k.words;
+    ctx->last_targets = 0;
+    ctx->last_online_targets = S;
+    MolTargetsArgs a{};
+    a.Y = Y, a.gamma = gamma, a.mx = mx, a.mn = mn, a.X = X, a.W = W;
+    a.fallbacks = k.counts, a.status = ctx->status_dev, a.ref_out = ref_out;
+    a.T = T, a.F = F, a.D = D, a.K = K, a.ref = ref, a.ban = ban, a.postfilter = postfilter;
+    a.beta = beta;
+    for (int s = 0; s < S; ++s) a.phi_x[s] = phi_x[s], a.phi_n[s] = phi_n[s], a.target[s] = targets[s];
+    {
+        GSS_PROF(ctx, "mvdr_online_targets");
+        const size_t lds = mol_lds_bytes(D);
+#define GSS_MOL_LAUNCH(NR)                                                                         \
+    do {                                                                                           \
+        if (lds > 48 * 1024)                                                                       \
+            GSS_HIP_CHECK(ctx, hipFuncSetAttribute(                                                \
+                                   reinterpret_cast<const void *>(mvdr_online_targets_kernel<NR>), \
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));         \
+        hipLaunchKernelGGL(mvdr_online_targets_kernel<NR>, dim3(F, S), dim3(64), lds, ctx->stream, \
+                           a);                                                                     \
+    } while (0)
+        if (D <= 8) GSS_MOL_LAUNCH(1);
+        else if (D <= 16) GSS_MOL_LAUNCH(2);
+        else if (D <= 24) GSS_MOL_LAUNCH(3);
+        else GSS_MOL_LAUNCH(4);
+#undef GSS_MOL_LAUNCH
+        GSS_LAUNCH_CHECK(ctx, "mvdr_online_targets_kernel");
+        hipLaunchKernelGGL(mvdr_online_targets_count_kernel, dim3(1), dim3(256), 0, ctx->stream,
+                           k.counts, F, S, words);
+        GSS_LAUNCH_CHECK(ctx, "mvdr_online_targets_count_kernel");
+    }
+    // the counts of this call -> the context's status words: the sum where the one-target call
+    // leaves its count, then one word per target
+    GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_MVDR_ONLINE_FALLBACKS, words,
+                                      sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_MVDR_ONLINE_TARGETS, words + 1,
+                                      sizeof(int32_t) * S, hipMemcpyDeviceToHost, ctx->stream));
     return GSS_OK;
 }

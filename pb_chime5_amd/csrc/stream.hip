@@ -95,7 +95,7 @@ __global__ __launch_bounds__(STAGE_THREADS) void stream_history_kernel(
 // istft_ola_kernel does over all frames.  q < Tn H: no later frame reaches p, the sample is
 // finished and goes out unless it lies in the leading fading pad (p < W - H); the others are the
 // new tail, written to tail_new (tail is read by other threads).
-__global__ __launch_bounds__(256) void stream_ola_kernel(
+__device__ __forceinline__ void stream_ola_sample(
     const double *__restrict__ frm, int64_t t0, int64_t Tn, int size, int shift,
     const double *__restrict__ tail, double *__restrict__ tail_new, int64_t first_out,
     double *__restrict__ out) {
@@ -116,6 +116,25 @@ __global__ __launch_bounds__(256) void stream_ola_kernel(
         out[p - pad - first_out] = acc;
 }
 
+__global__ __launch_bounds__(256) void stream_ola_kernel(
+    const double *__restrict__ frm, int64_t t0, int64_t Tn, int size, int shift,
+    const double *__restrict__ tail, double *__restrict__ tail_new, int64_t first_out,
+    double *__restrict__ out) {
+    stream_ola_sample(frm, t0, Tn, size, shift, tail, tail_new, first_out, out);
+}
+
+// The same for S signals, grid.y = s: frm (S,Tn,size), tail / tail_new (S, size - shift), out
+// (S, m).  Signal s is stream_ola_kernel on its own rows.
+__global__ __launch_bounds__(256) void stream_ola_targets_kernel(
+    const double *__restrict__ frm, int64_t t0, int64_t Tn, int size, int shift,
+    const double *__restrict__ tail, double *__restrict__ tail_new, int64_t first_out, int64_t m,
+    double *__restrict__ out) {
+    const int64_t s = blockIdx.y;
+    const int pad = size - shift;
+    stream_ola_sample(frm + s * Tn * size, t0, Tn, size, shift, tail + s * pad, tail_new + s * pad,
+                      first_out, out + s * m);
+}
+
 struct StreamStftWork {
     double *xs;     // (D, L)
     uint8_t *as;    // (K, L), NULL without an activity
@@ -130,13 +149,13 @@ StreamStftWork stream_stft_blocks(Workspace &ws, int64_t Tn, int D, int K, int s
 }
 
 struct StreamIstftWork {
-    double *frm;        // (Tn, size)
-    double *tail_new;   // (size - shift)
+    double *frm;        // (S Tn, size)
+    double *tail_new;   // (S, size - shift)
 };
-StreamIstftWork stream_istft_blocks(Workspace &ws, int64_t Tn, int size, int shift) {
+StreamIstftWork stream_istft_blocks(Workspace &ws, int64_t Tn, int size, int shift, int S = 1) {
     StreamIstftWork k;
-    k.frm = ws.take<double>((size_t)Tn * size, "stream istft frames");
-    k.tail_new = ws.take<double>((size_t)(size - shift), "stream new tail");
+    k.frm = ws.take<double>((size_t)S * Tn * size, "stream istft frames");
+    k.tail_new = ws.take<double>((size_t)S * (size - shift), "stream new tail");
     return k;
 }
 
@@ -151,6 +170,12 @@ size_t stream_stft_workspace_bytes(int64_t Tn, int D, int K, int size, int shift
 size_t stream_istft_workspace_bytes(int64_t Tn, int size, int shift) {
     Workspace ws;
     if (Tn > 0) stream_istft_blocks(ws, Tn, size, shift);
+    return ws.bytes + 4096;
+}
+
+size_t stream_istft_targets_workspace_bytes(int64_t Tn, int S, int size, int shift) {
+    Workspace ws;
+    if (Tn > 0) stream_istft_blocks(ws, Tn, size, shift, S);
     return ws.bytes + 4096;
 }
 
@@ -247,6 +272,31 @@ int stream_istft_run(gss_ctx *ctx, const cplx *X, int64_t Tn, gss_stream_state *
     if (W > H)
         GSS_HIP_CHECK(ctx, hipMemcpyAsync(st->ola_tail, k.tail_new, sizeof(double) * (W - H),
                                           hipMemcpyDeviceToDevice, ctx->stream));
+    st->frames_out = t0 + Tn;
+    return GSS_OK;
+}
+
+// The S Tn frames go through istft_single_frames_run as one batch (every frame on its own: frame
+// (s, t) has the bits it has in a call of signal s alone), then one overlap-add launch.
+int stream_istft_targets_run(gss_ctx *ctx, const cplx *X, int64_t Tn, int S, gss_stream_state *st,
+                             double *tails, double *out) {
+    const int W = st->size, H = st->shift;
+    const int64_t t0 = st->frames_out;
+    Workspace ws(ctx);
+    const StreamIstftWork k = stream_istft_blocks(ws, Tn, W, H, S);
+    GSS_TRY(ws.status("gss_istft_stream_targets"));
+    GSS_TRY(istft_single_frames_run(ctx, X, (int64_t)S * Tn, k.frm));
+    {
+        GSS_PROF(ctx, "stream_ola_targets");
+        const int64_t total = Tn * H + (W - H);
+        const int64_t first = stream_emitted(t0, W, H), m = stream_emitted(t0 + Tn, W, H) - first;
+        hipLaunchKernelGGL(stream_ola_targets_kernel, dim3((unsigned)((total + 255) / 256), S),
+                           dim3(256), 0, ctx->stream, k.frm, t0, Tn, W, H, tails, k.tail_new, first,
+                           m, out);
+        GSS_LAUNCH_CHECK(ctx, "stream_ola_targets_kernel");
+    }
+    GSS_HIP_CHECK(ctx, hipMemcpyAsync(tails, k.tail_new, sizeof(double) * S * (W - H),
+                                      hipMemcpyDeviceToDevice, ctx->stream));
     st->frames_out = t0 + Tn;
     return GSS_OK;
 }

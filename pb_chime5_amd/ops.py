@@ -37,6 +37,9 @@ here                        reference call (file:line)
                             the two ends of a sample-block stream with a carried state and one
                             block through the three online stages (not in the reference; the
                             front door is ``streaming.StreamingEnhancer``)
+``StreamTails`` / ``mvdr_souden_online_targets`` / ``istft_stream_targets`` / ``stream_block_targets``
+                            the same for several targets of one stream from one pass (not in
+                            the reference; ``StreamingEnhancer(targets=...)``)
 ``lcmv_souden_from_masks``  beamform_lcmv_souden_from_masks (beamforming_wrapper.py:127-171)
 ``lcmv_masks_from_posteriors`` / ``enhance_observation_lcmv``
                             the interferer-nulling LCMV fed from the posteriors
@@ -3254,6 +3257,220 @@ def stream_block(block, activity=None, *, params, stream, em_state, bf_state, wp
     details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
     details['ref_channel'] = int(details['ref_channel'])
     details['fallbacks'] = (ctx.last_mvdr_online_fallbacks(), ctx.last_cacgmm_online_fallbacks())
+    return samples, details
+
+
+# --------------------------------------------------------------------------
+# several targets of one stream (gss_stream_block_targets)
+# --------------------------------------------------------------------------
+def check_online_targets(targets, num_classes=None):
+    """The targets of a multi-target stream -- the one place that validates them.  ValueError:
+    not a sequence, empty, more than 8, not integers, one given twice, one outside
+    [0, num_classes).  Returns them as a tuple of ints."""
+    if isinstance(targets, (str, bytes)) or not hasattr(targets, '__len__'):
+        raise ValueError(f'targets={targets!r}: a sequence of class indices')
+    values = list(targets)
+    if not 1 <= len(values) <= _ONLINE_MAX_CLASSES:
+        raise ValueError(f'targets={targets!r}: 1 to {_ONLINE_MAX_CLASSES} class indices')
+    for t in values:
+        if not _is_integer(t) or t < 0 or (num_classes is not None and t >= num_classes):
+            raise ValueError(f'targets={targets!r}: {t!r} is not an integer in [0, '
+                             f'{"num_classes" if num_classes is None else num_classes})')
+    if len(set(int(t) for t in values)) != len(values):
+        raise ValueError(f'targets={targets!r}: a class is given twice')
+    return tuple(int(t) for t in values)
+
+
+class StreamTails(_OnlineState):
+    """The overlap-add tails of the S signals of a multi-target stream in HBM, caller-owned:
+    ``tails`` (S, size - shift) float64, zero at the start of a stream."""
+    _sizes = 'S, size - shift'
+    dtypes = {'tails': np.float64}
+
+    def __init__(self, ctx, S, pad):
+        super().__init__(ctx, S, pad)
+        self.S, self.pad = self.key
+
+    @staticmethod
+    def _shapes(S, pad):
+        return {'tails': (S, pad)}
+
+    @property
+    def ptr(self):
+        return self.bufs['tails'].ptr
+
+    @classmethod
+    def fresh(cls, S, size=1024, shift=256, *, ctx=None):
+        check_stream(1, 0, size, shift)
+        if not _is_integer(S) or not 1 <= S <= _ONLINE_MAX_CLASSES:
+            raise ValueError(f'S={S!r}: an integer in [1, {_ONLINE_MAX_CLASSES}]')
+        return cls.from_host({'tails': np.zeros((S, size - shift))}, ctx=ctx)
+
+    @classmethod
+    def from_host(cls, host, *, ctx=None):
+        tails = np.asarray(host['tails'])
+        if tails.ndim != 2 or not 1 <= tails.shape[0] <= _ONLINE_MAX_CLASSES or tails.shape[1] < 1:
+            raise ValueError(f'tails: shape {tails.shape} is not (S, size - shift)')
+        return cls._from_host(host, tails.shape, ctx)
+
+
+def _check_target_states(states, S, key, ctx, name='states'):
+    """S different `OnlineMVDRState`s built for ``key`` = (F, D), all in ``ctx`` (None: the
+    first one's).  Returns the context and the ctypes array of their structs."""
+    states = list(states) if hasattr(states, '__iter__') else None
+    if states is None or len(states) != S:
+        raise ValueError(f'{name}: a sequence of {S} OnlineMVDRState, one per target')
+    for state in states:
+        ctx = _state_context(state, OnlineMVDRState, key, ctx)
+    if len({id(state) for state in states}) != S:
+        raise ValueError(f'{name}: the same state for two targets')
+    return ctx, (GssMvdrOnlineState * S)(*(state.struct() for state in states))
+
+
+def mvdr_souden_online_targets(Y, posterior, targets, *, states, forget=BF_ONLINE_FORGET,
+                               ref_channel=0, ban=False, postfilter=None, return_fallbacks=False,
+                               return_filters=False):
+    """The online MVDR for S targets in one launch (gss_mvdr_online_targets): Y (D,T,F), the
+    posteriors (K,T,F), ``targets`` S distinct class indices, ``states`` S `OnlineMVDRState`s,
+    each advanced IN PLACE -> X_hat (S,T,F) complex128.  The masks are formed on the device as
+    `masks_from_posteriors` forms them; row s has the bits of `mvdr_souden_online_from_masks` on
+    the masks of class targets[s] with states[s] (times the target mask with
+    ``postfilter='mask_mul'``).  Then with ``return_filters`` the filters (S,T,F,D), then with
+    ``return_fallbacks`` the list of S fallback counts."""
+    Y = np.asarray(Y)
+    if Y.ndim != 3:
+        raise ValueError(f'Y: shape {Y.shape} is not (D,T,F)')
+    D, T, F = Y.shape
+    g = np.asarray(posterior, dtype=np.float64)
+    if g.ndim != 3 or g.shape[1:] != (T, F):
+        raise ValueError(f'posterior: shape {g.shape} is not (K,T,F) = (K,{T},{F})')
+    K = g.shape[0]
+    if not 1 <= K <= _ONLINE_MAX_CLASSES:
+        raise ValueError(f'posterior: {K} classes, 1 to {_ONLINE_MAX_CLASSES} are supported')
+    if not np.all(np.isfinite(g)) or np.any(g < 0):
+        raise ValueError('posterior: a value is negative or not finite')
+    targets = check_online_targets(targets, K)
+    S = len(targets)
+    forget, _, ref_channel = check_bf_online(forget, BF_ONLINE_LOADING, ref_channel, D)
+    if ref_channel < 0:
+        raise ValueError(f'ref_channel={ref_channel!r}: an integer in [0, {D})')
+    if postfilter not in (None, 'mask_mul'):
+        raise ValueError(f"postfilter={postfilter!r}: None or 'mask_mul'")
+    ctx, structs = _check_target_states(states, S, (F, D), None)
+    fallbacks = [0] * S
+    if T == 0 or F == 0:
+        X_hat, W = np.zeros((S, T, F), np.complex128), np.zeros((S, T, F, D), np.complex128)
+    else:
+        Y_d, _ = _obs_to_device_ftd(ctx, Y)
+        g_d = ctx.to_device(g.transpose(2, 0, 1))                       # (F,K,T)
+        X_d = ctx.empty(16 * S * F * T)
+        W_d = ctx.empty(16 * S * F * T * D) if return_filters else None
+        cfg = _bf_online_cfg(forget, BF_ONLINE_LOADING, ref_channel)
+        ctx._check(ctx.lib.gss_mvdr_online_targets(
+            ctx.handle, c_void_p(Y_d.ptr), F, T, D, c_void_p(g_d.ptr), K,
+            (ctypes.c_int32 * S)(*targets), S, int(bool(ban)), ctypes.byref(cfg), structs,
+            int(postfilter == 'mask_mul'), None, None, c_void_p(X_d.ptr),
+            c_void_p(W_d.ptr) if W_d is not None else None), 'gss_mvdr_online_targets')
+        X_hat = ctx.to_host(X_d, (S, T, F), np.complex128)
+        W = (np.ascontiguousarray(ctx.to_host(W_d, (S, F, T, D), np.complex128)
+                                  .transpose(0, 2, 1, 3)) if return_filters else None)
+        if return_fallbacks:
+            fallbacks = ctx.last_mvdr_online_fallbacks_targets(S)
+    out = (X_hat,) + ((W,) if return_filters else ()) + ((fallbacks,) if return_fallbacks else ())
+    return out if len(out) > 1 else X_hat
+
+
+def istft_stream_targets(stft_signal, *, state, tails, window=None):
+    """`istft_stream` for S signals in one set of launches (gss_istft_stream_targets): the next
+    frames (S,Tn,F) -> (S,m), row s with the bits of `istft_stream` on stft_signal[s].  ``state``:
+    the `StreamState` of the analysis side, its frame counter advanced once, its own tail left
+    alone; ``tails``: the `StreamTails` of the S signals, advanced IN PLACE."""
+    if not isinstance(state, StreamState):
+        raise ValueError(f'state: {type(state).__name__} is not a StreamState')
+    if not isinstance(tails, StreamTails):
+        raise ValueError(f'tails: {type(tails).__name__} is not a StreamTails')
+    X = np.asarray(stft_signal, dtype=np.complex128)
+    F = state.size // 2 + 1
+    if X.ndim != 3 or X.shape[2] != F:
+        raise ValueError(f'stft_signal: shape {X.shape} is not (S,Tn,F) = (S,Tn,{F})')
+    S, Tn = X.shape[:2]
+    if tails.key != (S, state.size - state.shift):
+        raise ValueError(f'tails: built for ({tails._sizes}) = {tails.key}, the call has '
+                         f'{(S, state.size - state.shift)}')
+    if tails.ctx is not state.ctx:
+        raise ValueError('tails: they live in another context than the stream')
+    if Tn == 0:
+        return np.zeros((S, 0))
+    ctx, pad = state.ctx, state.size - state.shift
+    m = (max(0, (state.frames_out + Tn) * state.shift - pad)
+         - max(0, state.frames_out * state.shift - pad))
+    _prepare_windows(ctx, state.size, state.shift, window)
+    X_d = ctx.to_device(X)
+    o_d = ctx.empty(max(8 * S * m, 16))
+    ctx._check(ctx.lib.gss_istft_stream_targets(
+        ctx.handle, c_void_p(X_d.ptr), Tn, S, ctypes.byref(state.struct()), c_void_p(tails.ptr),
+        c_void_p(o_d.ptr)), 'gss_istft_stream_targets')
+    return ctx.to_host(o_d, (S, m), np.float64)
+
+
+def stream_block_targets(block, activity=None, *, params, stream, em_state, bf_states, tails,
+                         target_indices, wpe_state=None, ref_channel=0,
+                         wpe_alpha=WPE_ONLINE_ALPHA, em_forget=GSS_ONLINE_FORGET,
+                         bf_forget=BF_ONLINE_FORGET, window=None, debug=False):
+    """`stream_block` for S targets as ONE library call (gss_stream_block_targets): the analysis,
+    the online WPE and the online CACGMM once, then `mvdr_souden_online_targets` with BAN and the
+    postfilter and `istft_stream_targets`.  ``bf_states``: S `OnlineMVDRState`s, ``tails``: the
+    `StreamTails`, all advanced IN PLACE.  Returns (samples (S,m), details): row s has the bits of
+    `stream_block` with target_indices[s]; with ``debug`` the per-target taps are stacked over S as
+    in `enhance_observation_targets`, 'fallbacks' = (online MVDR summed over the targets, online
+    CACGMM) and 'fallbacks_targets' the online MVDR's per target."""
+    if not isinstance(stream, StreamState):
+        raise ValueError(f'stream: {type(stream).__name__} is not a StreamState')
+    ctx = stream.ctx
+    for name, state, cls in (('em_state', em_state, OnlineCACGMMState),
+                             ('wpe_state', wpe_state, OnlineWPEState),
+                             ('tails', tails, StreamTails)):
+        if state is None and name == 'wpe_state':
+            continue
+        if not isinstance(state, cls):
+            raise ValueError(f'{name}: {type(state).__name__} is not an {cls.__name__}')
+        if state.ctx is not ctx:
+            raise ValueError(f'{name}: it lives in another context than the stream')
+    D, K, F = stream.D, em_state.K, stream.size // 2 + 1
+    targets = check_online_targets(target_indices, K)
+    S = len(targets)
+    _, structs = _check_target_states(bf_states, S, (F, D), ctx, 'bf_states')
+    if tails.key != (S, stream.size - stream.shift):
+        raise ValueError(f'tails: built for ({tails._sizes}) = {tails.key}, the call has '
+                         f'{(S, stream.size - stream.shift)}')
+    x_d, in_type, act_d, n = _stream_block_to_device(ctx, block, activity, stream)
+    if n == 0:
+        return np.zeros((S, 0)), None
+    Tn = stream_num_frames(stream.received, n, stream.size, stream.shift)
+    m = stream_num_samples_out(stream.received, n, stream.size, stream.shift)
+    _prepare_windows(ctx, stream.size, stream.shift, window)
+    o_d = ctx.empty(max(8 * S * m, 16))
+    utt = SimpleNamespace(ctx=ctx, D=D, K=K, T=Tn, params=params)
+    bufs, taps = _debug_taps(utt, S) if debug and Tn > 0 else (None, None)
+    cfg = GssStreamCfg(wpe_alpha=float(wpe_alpha), em_forget=float(em_forget),
+                       bf_forget=float(bf_forget), ref_channel=int(ref_channel))
+    ctx._check(ctx.lib.gss_stream_block_targets(
+        ctx.handle, ctypes.byref(params), ctypes.byref(cfg), ctypes.byref(stream.struct()),
+        ctypes.byref(wpe_state.struct()) if wpe_state is not None else None,
+        ctypes.byref(em_state.struct()), structs, c_void_p(tails.ptr), c_void_p(x_d.ptr), in_type,
+        c_void_p(act_d.ptr) if act_d else None, n, (ctypes.c_int32 * S)(*targets), S,
+        c_void_p(o_d.ptr), ctypes.byref(taps) if taps is not None else None),
+        'gss_stream_block_targets')
+    samples = ctx.to_host(o_d, (S, m), np.float64)
+    if m == 0:
+        ctx.synchronize()      # (the block's device copies are read until then)
+    if bufs is None:
+        return samples, None
+    if act_d is None:
+        del bufs['act_frames']
+    details = _debug_details(utt, bufs, S)
+    details['fallbacks'] = (ctx.last_mvdr_online_fallbacks(), ctx.last_cacgmm_online_fallbacks())
+    details['fallbacks_targets'] = ctx.last_mvdr_online_fallbacks_targets(S)
     return samples, details
 
 

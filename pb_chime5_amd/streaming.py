@@ -16,7 +16,7 @@ from .cacgmm import CACGMM
 
 
 class StreamingEnhancer:
-    """One target of one stream.
+    """One target of one stream, or with ``targets`` several of them from one pass.
 
     ``num_channels`` and ``num_classes`` (the rows of the activity handed to `process`), or
     ``model=`` a fitted `cacgmm.CACGMM`: the mixture model continues from it (mass
@@ -25,7 +25,12 @@ class StreamingEnhancer:
     A > 1: the online WPE per array of num_channels / A consecutive channels.  ``fused=False``
     runs every block through the stage operators of `ops` in the place of the one library call;
     the bits are the same.  ``speakers``: the names of the classes in activity order, for an
-    activity handed to `process` as a dict.  Nothing touches the GPU before the first block.
+    activity handed to `process` as a dict.  ``targets``: a sequence of S distinct class indices
+    in the place of ``target`` -- the analysis, the online WPE and the online CACGMM run once for
+    all of them, `process` and `flush` return (S, m), row s with the bits of the stream of
+    ``target=targets[s]``; the per-target taps of ``debug`` are stacked over S and
+    ``fallbacks['mvdr_targets']`` lists the beamformer's fallback frames per target
+    (``fallbacks['mvdr']`` is their sum).  Nothing touches the GPU before the first block.
     """
 
     def __init__(self, num_channels=None, num_classes=None, *, model=None, target=0, ref_channel=0,
@@ -33,7 +38,7 @@ class StreamingEnhancer:
                  wpe_alpha=ops.WPE_ONLINE_ALPHA, wpe_arrays=1,
                  gss_forget=ops.GSS_ONLINE_FORGET, gss_prior_mass=ops.GSS_ONLINE_PRIOR_MASS,
                  bf_forget=ops.BF_ONLINE_FORGET, bf_loading=ops.BF_ONLINE_LOADING,
-                 postfilter=None, fused=True, speakers=None, ctx=None):
+                 postfilter=None, fused=True, speakers=None, targets=None, ctx=None):
         if model is not None:
             if not isinstance(model, CACGMM):
                 raise ValueError(f'model: a CACGMM, not {type(model).__name__}')
@@ -55,6 +60,12 @@ class StreamingEnhancer:
         K = int(num_classes)
         if not ops._is_integer(target) or not 0 <= target < K:
             raise ValueError(f'target={target!r}: an integer in [0, {K})')
+        if targets is not None:
+            if target != 0:
+                raise ValueError(f'targets={targets!r} together with target={target!r}: one of '
+                                 'the two')
+            targets = ops.check_online_targets(targets, K)
+        self.targets = targets
         if fused is not True and fused is not False:
             raise ValueError(f'fused={fused!r}: True or False')
         if wpe is not True and wpe is not False:
@@ -91,8 +102,11 @@ class StreamingEnhancer:
         """Back to the start of a stream: fresh states (the mixture model from ``model`` again),
         the counters and the fallback counts at zero."""
         self.stream = self.wpe_state = self.em_state = self.bf_state = None
+        self.bf_states = self.tails = self.tail_streams = None
         self.samples_in = self.samples_out = 0
         self.fallbacks = {'mvdr': 0, 'cacgmm': 0}
+        if self.targets is not None:
+            self.fallbacks['mvdr_targets'] = [0] * len(self.targets)
         self.flushed = False
 
     def _states(self):
@@ -110,7 +124,23 @@ class StreamingEnhancer:
                          if self.guided else
                          ops.OnlineCACGMMState.from_model(self.model, self.gss_prior_mass, ctx=ctx))
         # (no frames: a stream has none yet, p_f = 1)
-        self.bf_state = ops.OnlineMVDRState.fresh(F, D, self.bf_loading, ctx=ctx)
+        if self.targets is None:
+            self.bf_state = ops.OnlineMVDRState.fresh(F, D, self.bf_loading, ctx=ctx)
+            return
+        S = len(self.targets)
+        self.bf_states = [ops.OnlineMVDRState.fresh(F, D, self.bf_loading, ctx=ctx)
+                          for _ in range(S)]
+        self.tails = ops.StreamTails.fresh(S, self.size, self.shift, ctx=ctx)
+        self._tail_streams()
+
+    def _tail_streams(self):
+        """fused=False: a `StreamState` per target for `istft_stream`, which keeps its tail there;
+        every other part of these states is left alone (``tails`` is the record)."""
+        self.tail_streams = None
+        if not self.fused:
+            self.tail_streams = [ops.StreamState.fresh(1, 0, self.size, self.shift,
+                                                       window=self.window, ctx=self.ctx)
+                                 for _ in self.targets]
 
     @property
     def latency_samples(self):
@@ -121,33 +151,69 @@ class StreamingEnhancer:
         """A checkpoint of the stream: the four states (`from_host` restores them, in any
         context) and the counters."""
         self._states()
-        return {'stream': self.stream.to_host(), 'em': self.em_state.to_host(),
-                'bf': self.bf_state.to_host(),
+        if self.targets is None:
+            bf = {'bf': self.bf_state.to_host()}
+        else:       # the S beamformer states stacked, the tails and whose they are
+            states = [state.to_host() for state in self.bf_states]
+            bf = {'bf': {k: np.stack([h[k] for h in states]) for k in states[0]},
+                  'tails': self.tails.to_host()['tails'], 'targets': list(self.targets)}
+        return {'stream': self.stream.to_host(), 'em': self.em_state.to_host(), **bf,
                 'wpe': self.wpe_state.to_host() if self.wpe else None,
                 'samples_in': self.samples_in, 'samples_out': self.samples_out,
-                'fallbacks': dict(self.fallbacks), 'flushed': self.flushed}
+                'fallbacks': {k: list(v) if isinstance(v, list) else v
+                              for k, v in self.fallbacks.items()},
+                'flushed': self.flushed}
 
     def from_host(self, host):
         """Continue from a checkpoint of `to_host` (of a stream with this one's settings).
         ValueError when its shapes are another stream's."""
+        if ('targets' in host) != (self.targets is not None):
+            raise ValueError('checkpoint: of a stream %s targets=, this stream is %s one'
+                             % (('with', 'without') if 'targets' in host else ('without', 'with')))
+        if self.targets is not None and tuple(host['targets']) != self.targets:
+            raise ValueError(f'checkpoint: of targets={tuple(host["targets"])}, this stream has '
+                             f'targets={self.targets}')
         self._states()
         ctx = self.ctx
         stream = ops.StreamState.from_host(host['stream'], ctx=ctx)
         em = ops.OnlineCACGMMState.from_host(host['em'], ctx=ctx)
-        bf = ops.OnlineMVDRState.from_host(host['bf'], ctx=ctx)
+        if self.targets is None:
+            bfs = [ops.OnlineMVDRState.from_host(host['bf'], ctx=ctx)]
+        else:
+            S = len(self.targets)
+            stacked = {k: np.asarray(v) for k, v in host['bf'].items()}
+            if any(v.ndim != 4 or v.shape[0] != S for v in stacked.values()):
+                raise ValueError(f'checkpoint: bf states of shapes '
+                                 f'{[v.shape for v in stacked.values()]}, not (S,F,D,D) with S = {S}')
+            bfs = [ops.OnlineMVDRState.from_host({k: v[s] for k, v in stacked.items()}, ctx=ctx)
+                   for s in range(S)]
+            tails = ops.StreamTails.from_host({'tails': host['tails']}, ctx=ctx)
+            if tails.key != self.tails.key:
+                raise ValueError(f'checkpoint: tails built for ({tails._sizes}) = {tails.key}, '
+                                 f'this stream has {self.tails.key}')
+        bf = bfs[0]
         if (host['wpe'] is not None) != self.wpe:
             raise ValueError('checkpoint: its WPE state and wpe=%r disagree' % self.wpe)
         wpe = ops.OnlineWPEState.from_host(host['wpe'], ctx=ctx) if self.wpe else None
         for name, state, key in (
                 ('stream', stream, self.stream.key), ('em', em, self.em_state.key),
-                ('bf', bf, self.bf_state.key),
+                ('bf', bf, (self.F, self.D)),
                 ('wpe', wpe, self.wpe_state.key if self.wpe else None)):
             if state is not None and state.key != key:
                 raise ValueError(f'checkpoint: {name} state built for ({state._sizes}) = '
                                  f'{state.key}, this stream has {key}')
-        self.stream, self.em_state, self.bf_state, self.wpe_state = stream, em, bf, wpe
+        self.stream, self.em_state, self.wpe_state = stream, em, wpe
+        if self.targets is None:
+            self.bf_state = bf
+        else:
+            self.bf_states, self.tails = bfs, tails
+            if not self.fused:      # the per-target tails of the stage path, from the record
+                self._tail_streams()
+                for s, state in enumerate(self.tail_streams):
+                    ctx.upload(state.bufs['ola_tail'], np.ascontiguousarray(host['tails'][s]))
         self.samples_in, self.samples_out = int(host['samples_in']), int(host['samples_out'])
-        self.fallbacks = dict(host['fallbacks'])
+        self.fallbacks = {k: list(v) if isinstance(v, (list, tuple)) else v
+                          for k, v in host['fallbacks'].items()}
         self.flushed = bool(host['flushed'])
         return self
 
@@ -179,8 +245,8 @@ class StreamingEnhancer:
     def process(self, block, activity=None, debug=False):
         """The next ``block`` (D,n) of samples, float64 or int16 PCM, with its ``activity`` (K,n)
         (or a dict of K per-sample tracks in class order) -> the samples the block finishes,
-        (m,) float64; with ``debug`` (samples, details) with the taps over the block's frames
-        (None when the block completes no frame)."""
+        (m,) float64 -- (S, m) with ``targets`` --; with ``debug`` (samples, details) with the
+        taps over the block's frames (None when the block completes no frame)."""
         if self.flushed:
             raise RuntimeError('process after flush: the stream has ended, call reset()')
         block = np.asarray(block)
@@ -188,7 +254,7 @@ class StreamingEnhancer:
             raise ValueError(f'block: shape {block.shape} is not (D,n) = ({self.D},n)')
         samples, details = self._block(block, self._activity(activity, block.shape[1]), debug)
         self.samples_in += block.shape[1]
-        self.samples_out += len(samples)
+        self.samples_out += samples.shape[-1]
         return (samples, details) if debug else samples
 
     def flush(self, debug=False):
@@ -199,20 +265,36 @@ class StreamingEnhancer:
             raise RuntimeError('flush after flush: the stream has ended, call reset()')
         if self.samples_in == 0:        # nothing went in: nothing comes out
             self.flushed = True
-            return (np.zeros(0), None) if debug else np.zeros(0)
+            return (self._no_samples(), None) if debug else self._no_samples()
         n = ops.stream_flush_samples(self.samples_in, self.size, self.shift)
         samples, details = self._block(np.zeros((self.D, n)),
                                        np.zeros((self.K, n), bool) if self.guided else None, debug)
-        samples = samples[:self.samples_in - self.samples_out]
-        self.samples_out += len(samples)
+        samples = samples[..., :self.samples_in - self.samples_out]
+        self.samples_out += samples.shape[-1]
         self.flushed = True
         return (samples, details) if debug else samples
 
+    def _no_samples(self):
+        return np.zeros(0) if self.targets is None else np.zeros((len(self.targets), 0))
+
     def _block(self, block, activity, debug):
         if block.shape[1] == 0:
-            return np.zeros(0), None
+            return self._no_samples(), None
         self._states()
         Tn = ops.stream_num_frames(self.stream.received, block.shape[1], self.size, self.shift)
+        if self.targets is not None:
+            if not self.fused:
+                return self._block_stages_targets(block, activity, debug)
+            samples, details = ops.stream_block_targets(
+                block, activity, params=self.params, stream=self.stream, em_state=self.em_state,
+                bf_states=self.bf_states, tails=self.tails, wpe_state=self.wpe_state,
+                target_indices=self.targets, ref_channel=self.ref_channel,
+                wpe_alpha=self.wpe_alpha, em_forget=self.gss_forget, bf_forget=self.bf_forget,
+                window=self.window, debug=debug)
+            if Tn > 0:
+                self._count(self.ctx.last_mvdr_online_fallbacks_targets(len(self.targets)),
+                            self.ctx.last_cacgmm_online_fallbacks())
+            return samples, details
         if self.fused:
             samples, details = ops.stream_block(
                 block, activity, params=self.params, stream=self.stream, em_state=self.em_state,
@@ -256,6 +338,61 @@ class StreamingEnhancer:
             details = {'Obs': Obs, 'posterior': posterior, 'target_mask': target_mask,
                        'distortion_mask': distortion_mask, 'X_hat': X_hat,
                        'ref_channel': self.ref_channel, 'fallbacks': (bf_fallbacks, em_fallbacks)}
+            if act_frames is not None:
+                details['acitivity_freq'] = act_frames
+        return samples, details
+
+    def _count(self, bf_targets, em_fallbacks):
+        self.fallbacks['mvdr'] += sum(bf_targets)
+        self.fallbacks['cacgmm'] += em_fallbacks
+        self.fallbacks['mvdr_targets'] = [a + b for a, b in
+                                          zip(self.fallbacks['mvdr_targets'], bf_targets)]
+
+    def _block_stages_targets(self, block, activity, debug):
+        """The block of S targets through the existing single-target stage operators: the front
+        once, then masks, beamformer and synthesis per target, each with its explicit state."""
+        Y, act_frames = ops.stft_stream(block, activity, state=self.stream, window=self.window)
+        if Y.shape[1] == 0:
+            return self._no_samples(), None
+        Obs = Y
+        if self.wpe:
+            Obs = ops.wpe_online_dtf(Y, self.wpe_taps, self.wpe_delay, self.wpe_alpha,
+                                     arrays=self.wpe_arrays, state=self.wpe_state)
+        posterior, em_fallbacks = ops.cacgmm_posteriors_online(
+            Obs, act_frames, forget=self.gss_forget, state=self.em_state, return_fallbacks=True)
+        frames_out, rows = self.stream.frames_out, []
+        for s, target in enumerate(self.targets):
+            target_mask, distortion_mask = ops.masks_from_posteriors(posterior, target, ctx=self.ctx)
+            X_hat, fallbacks = ops.mvdr_souden_online_from_masks(
+                Obs, target_mask, distortion_mask, ban=True, forget=self.bf_forget,
+                ref_channel=self.ref_channel, state=self.bf_states[s], return_fallbacks=True)
+            if self.postfilter == 'mask_mul':
+                X_hat = (X_hat.view(np.float64).reshape(X_hat.shape + (2,))
+                         * target_mask[..., None]).reshape(X_hat.shape[0], -1).view(np.complex128)
+            # The synthesis of target s on a state of its own, kept only so that the existing
+            # `istft_stream` can be reused: its tail lives there, its counters follow the stream's.
+            # This writes through `StreamState.struct()`, which hands out the state's ONE
+            # persistent struct (a copy would leave the library reading the old counters).
+            tail = self.tail_streams[s]
+            tail.struct().received, tail.struct().frames_out = self.stream.received, frames_out
+            samples = ops.istft_stream(X_hat, state=tail, window=self.window)
+            rows.append((samples, target_mask, distortion_mask, X_hat, fallbacks))
+        # (no `istft_stream` ran on the stream's own state: its frame counter is advanced here,
+        # once, and the per-target tails are copied into ``tails``, the record a checkpoint keeps)
+        self.stream.struct().frames_out = frames_out + Y.shape[1]
+        self.ctx.upload(self.tails.bufs['tails'],
+                        np.stack([t.to_host()['ola_tail'] for t in self.tail_streams]))
+        self._count([r[4] for r in rows], em_fallbacks)
+        samples = np.stack([r[0] for r in rows])
+        details = None
+        if debug:
+            details = {'Obs': Obs, 'posterior': posterior,
+                       'target_mask': np.stack([r[1] for r in rows]),
+                       'distortion_mask': np.stack([r[2] for r in rows]),
+                       'X_hat': np.stack([r[3] for r in rows]),
+                       'ref_channel': np.full(len(rows), self.ref_channel),
+                       'fallbacks': (sum(r[4] for r in rows), em_fallbacks),
+                       'fallbacks_targets': [r[4] for r in rows]}
             if act_frames is not None:
                 details['acitivity_freq'] = act_frames
         return samples, details
