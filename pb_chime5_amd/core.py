@@ -1256,15 +1256,11 @@ class Enhancer:
         if self.bf_drop_context:
             start_ctx, end_ctx = start_end_context_samples(ex)
         params = self._params()     # raises NotImplementedError for unknown bf / postfilter
-        # one utterance at a time (this method is the loop body of core.py:363-392): the fused
-        # call may put half of the WPE stage's frequencies on the context's second stream
-        ctx = self._ctx()
-        ctx.set_utterances_in_flight(1)
         segments = self._bf_segments()
-        select = self._channel_select()
         online = self._wpe_online()
         bf_online = self._bf_online()
         gss_online = self._gss_online()
+        # (the refusals come before the context: a machine without a GPU says the same)
         if gss_online is not None and online is not None and bf_online is None:
             raise NotImplementedError(
                 'gss_online with wpe_online but without bf_online in the fused call (the online '
@@ -1274,11 +1270,16 @@ class Enhancer:
             # (the fused online call takes no second descriptor; the stage path combines)
             for name, on in (('bf_segment_frames', segments is not None),
                              ('bf_null_interferer', self._bf_null()),
-                             ('channel_keep', select is not None)):
+                             ('channel_keep', self.channel_keep is not None)):
                 if on:
                     raise NotImplementedError(
                         f'wpe_online with {name} in the fused call: pass fused=False for the '
                         'stage path')
+        # one utterance at a time (this method is the loop body of core.py:363-392): the fused
+        # call may put half of the WPE stage's frequencies on the context's second stream
+        ctx = self._ctx()
+        ctx.set_utterances_in_flight(1)
+        select = self._channel_select()
         try:
             if gss_online is not None:
                 # (every online stage in one call: the MVDR's descriptor carries the WPE's alpha)
