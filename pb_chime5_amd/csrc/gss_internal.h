@@ -648,16 +648,15 @@ int cacgmm_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, cons
 // Sample-block stream (stream.hip; include/gss_hip.h: gss_stft_stream, gss_istft_stream).  The
 // state and the arguments have been validated by the entry point; the host counters of the state
 // are advanced by the run.  stft: n >= 1 samples -> Tn = gss_stream_num_frames() frames Y (F,Tn,D)
-// and, with an activity, actf (K,Tn).  istft: X (Tn,F), Tn >= 1 -> gss_stream_num_samples_out()
-// samples.  Workspace from the arena (stream_*_workspace_bytes).
+// and, with an activity, actf (K,Tn).  istft: X (S,Tn,F), Tn >= 1 -> out (S,m), m =
+// gss_stream_num_samples_out() samples of each of the S signals of one stream, with the caller's
+// overlap-add tails (S, size - shift); st->frames_out advances once, st->ola_tail is touched only
+// where it is handed in as the tails (S = 1: the synthesis of a one-signal stream).  Workspace
+// from the arena (stream_*_workspace_bytes).
 size_t stream_stft_workspace_bytes(int64_t Tn, int D, int K, int size, int shift);
-size_t stream_istft_workspace_bytes(int64_t Tn, int size, int shift);
 int stream_init_run(gss_ctx *ctx, gss_stream_state *st);
 int stream_stft_run(gss_ctx *ctx, const void *x, int in_type, const uint8_t *act, int64_t n,
                     gss_stream_state *st, cplx *Y, uint8_t *actf);
-int stream_istft_run(gss_ctx *ctx, const cplx *X, int64_t Tn, gss_stream_state *st, double *out);
-// S signals of one stream: X (S,Tn,F) -> out (S,m), the overlap-add tails (S, size - shift) the
-// caller's; st->ola_tail is neither read nor written, st->frames_out advances once.
 size_t stream_istft_targets_workspace_bytes(int64_t Tn, int S, int size, int shift);
 int stream_istft_targets_run(gss_ctx *ctx, const cplx *X, int64_t Tn, int S, gss_stream_state *st,
                              double *tails, double *out);

@@ -21,6 +21,8 @@
 // Both sums keep the FULL Hermitian matrix; (i, j) and (j, i) are updated with operations that
 // commute with conjugation (c_outer, real scalings), so the lower triangle stays the exact
 // conjugate of the upper one and the diagonal exactly real.  No floating-point atomics.
+//
+// The frame is written once, mol_frame<NR>; the two kernels below are the I/O around it.
 #include "dense_wave.h"
 
 namespace {
@@ -73,6 +75,25 @@ __global__ __launch_bounds__(256) void mvdr_online_init_kernel(const cplx *__res
     }
 }
 
+// The LDS of one wave: Phi_X, Phi_N and the sweep's rows M, each D rows of ld = 8 NR + 1 complex
+// values (odd: the lanes that walk a column fall on different 16-byte slots), y, B[:, ref], w and
+// the sweep's 1 / U_jj (mol_lds_bytes).
+template <int NR>
+struct MolLds {
+    static constexpr int ld = 8 * NR + 1;
+    cplx *PX, *PN, *M, *yb, *cb, *wb;
+    double *dinv;
+    __device__ __forceinline__ MolLds(char *smem, int D) {
+        PX = reinterpret_cast<cplx *>(smem);
+        PN = PX + D * ld;
+        M = PN + D * ld;
+        yb = M + D * ld;      // 8 NR each
+        cb = yb + 8 * NR;
+        wb = cb + 8 * NR;
+        dinv = reinterpret_cast<double *>(wb + 8 * NR);
+    }
+};
+
 // A state handed in is read from its upper triangle and the real part of its diagonal.
 __device__ __forceinline__ void mol_load(const cplx *__restrict__ g, cplx *m, int D, int ld, int lane) {
     for (int idx = lane; idx < D * D; idx += 64) {
@@ -83,23 +104,125 @@ __device__ __forceinline__ void mol_load(const cplx *__restrict__ g, cplx *m, in
     }
 }
 
-// One wave per frequency; lane (ty, tx) = (lane >> 3, lane & 7) owns the entries (ty + 8 a,
-// tx + 8 b) of both sums and of the sweep's register tile.  LDS: Phi_X, Phi_N and the sweep's
-// rows M, each D rows of ld = 8 NR + 1 complex values (odd: the lanes that walk a column fall on
-// different 16-byte slots), y, B[:, ref], w and the sweep's 1 / U_jj.  y and the two mask values
-// of frame t + 1 are fetched while frame t's dependent chain runs.
+// The two sums after the call's frames -> the state, the full matrices.
+template <int NR>
+__device__ __forceinline__ void mol_store(const MolLds<NR> &s, cplx *__restrict__ gx,
+                                          cplx *__restrict__ gn, int D, int lane) {
+    constexpr int ld = MolLds<NR>::ld;
+    for (int idx = lane; idx < D * D; idx += 64) {
+        const int r = idx / D, c = idx - r * D;
+        gx[idx] = s.PX[r * ld + c];
+        gn[idx] = s.PN[r * ld + c];
+    }
+}
+
+// One frame of one wave: y (lane < D holds y[lane]; also in s.yb, published by a wave_sync) with
+// the mask values ma, mb -> the filter w (lane < D holds w[lane]) and x = w^H y.  Lane (ty, tx) =
+// (lane >> 3, lane & 7) owns the entries (ty + 8 a, tx + 8 b) of both sums and of the sweep's
+// register tile.  false: a fallback frame, w = 0 and x = 0, the sums advanced all the same.
+template <int NR>
+__device__ __forceinline__ bool mol_frame(const MolLds<NR> &s, cplx y, double ma, double mb,
+                                          double beta, int ref, int ban, int D, int lane, int tx,
+                                          int ty, cplx &w, cplx &x) {
+    constexpr int ld = MolLds<NR>::ld;
+    cplx *const PX = s.PX, *const PN = s.PN, *const M = s.M;
+    cplx *const yb = s.yb, *const cb = s.cb, *const wb = s.wb;
+    double *const dinv = s.dinv;
+    const bool row = lane < D;
+    const cplx zero = c_make(0.0, 0.0);
+    // the two running sums; the sweep's tile is the upper triangle of the new Phi_N
+    cplx reg[NR][NR];
+#pragma unroll
+    for (int ai = 0; ai < NR; ++ai)
+#pragma unroll
+        for (int bi = 0; bi < NR; ++bi) {
+            const int i = ty + 8 * ai, k = tx + 8 * bi;
+            reg[ai][bi] = zero;
+            if (i < D && k < D) {
+                const cplx o = c_outer(yb[i], yb[k]);
+                const cplx px = PX[i * ld + k], pn = PN[i * ld + k];
+                PX[i * ld + k] = c_make(fma(beta, px.x, ma * o.x), fma(beta, px.y, ma * o.y));
+                const cplx nn = c_make(fma(beta, pn.x, mb * o.x), fma(beta, pn.y, mb * o.y));
+                PN[i * ld + k] = nn;
+                if (k >= i) reg[ai][bi] = nn;
+            }
+        }
+    wave_sync();
+    const bool ok = chol_inverse_sweep<8, NR, true>(reg, D, M, ld, dinv, tx, ty);
+    w = zero, x = zero;
+    if (ok) {   // decided by the pivots alone, the same in every lane
+        // M: row i holds W[i][k] / dinv[i] for k < i; W[i][i] = dinv[i].
+        // B[i][k] = dinv[i] (sum_{j<i} M[i][j] Phi_X[j][k] + Phi_X[i][k])
+        double trp = 0.0;
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai) {
+            const int i = ty + 8 * ai;
+            if (i < D) {
+                cplx acc[NR];
+#pragma unroll
+                for (int bi = 0; bi <= ai; ++bi) acc[bi] = zero;
+                for (int j = 0; j < i; ++j) {
+                    const cplx m = M[i * ld + j];
+#pragma unroll
+                    for (int bi = 0; bi <= ai; ++bi) c_fma(acc[bi], m, PX[j * ld + min(tx + 8 * bi, D - 1)]);
+                }
+                const double d2 = dinv[i] * dinv[i];
+#pragma unroll
+                for (int bi = 0; bi <= ai; ++bi) {
+                    const int k = tx + 8 * bi;
+                    if (k <= i) {
+                        const cplx bu = c_add(acc[bi], PX[i * ld + k]);
+                        const cplx m = k < i ? M[i * ld + k] : c_make(1.0, 0.0);
+                        trp = fma(d2, fma(bu.x, m.x, bu.y * m.y), trp);
+                    }
+                }
+            }
+        }
+        // cb[i] = dinv[i] B[i][ref]
+        if (row) {
+            cplx acc = zero;
+            for (int j = 0; j < lane; ++j) c_fma(acc, M[lane * ld + j], PX[j * ld + ref]);
+            acc = c_add(acc, PX[lane * ld + ref]);
+            cb[lane] = c_scale(acc, dinv[lane] * dinv[lane]);
+        }
+        const double tr = wave_sum(trp);
+        wave_sync();
+        // w[k] = sum_{i >= k} conj(W[i][k]) B[i][ref] / max(tr, eps)
+        if (row) {
+            cplx acc = cb[lane];
+            for (int i = lane + 1; i < D; ++i) c_cfma(acc, M[i * ld + lane], cb[i]);
+            w = c_scale(acc, 1.0 / fmax(tr, 1e-10));
+        }
+        if (ban) {
+            if (row) wb[lane] = w;
+            wave_sync();
+            cplx v = zero;     // (Phi_N w)[i], from column i of the Hermitian matrix
+            if (row)
+                for (int k = 0; k < D; ++k) c_cfma(v, PN[k * ld + lane], wb[k]);
+            const double vv = wave_sum(fma(v.x, v.x, v.y * v.y));
+            cplx wv = zero;
+            c_cfma(wv, w, v);
+            const double wr = wave_sum(wv.x), wi = wave_sum(wv.y);
+            // eps = 0 as upstream, but a filter that is exactly zero (no target mass yet: the
+            // context frames of every window) stays zero where upstream divides 0 by 0
+            const double den = hypot(wr, wi);
+            w = c_scale(w, den == 0.0 ? 0.0 : sqrt(vv) / den);
+        }
+        cplx p = zero;
+        c_cfma(p, w, y);
+        x = c_make(wave_sum(p.x), wave_sum(p.y));
+    }
+    return ok;
+}
+
+// One wave per frequency.  The masks are the caller's, X is strided, the reference channel may
+// come from a whole-window pass (ref_dev; none found: NaN, the state untouched).  y and the two
+// mask values of frame t + 1 are fetched while frame t's dependent chain runs.
 template <int NR>
 __global__ __launch_bounds__(64) void mvdr_online_kernel(MolArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int ld = 8 * NR + 1;
     const int D = a.D;
-    cplx *PX = reinterpret_cast<cplx *>(smem);
-    cplx *PN = PX + D * ld;
-    cplx *M = PN + D * ld;
-    cplx *yb = M + D * ld;      // 8 NR each
-    cplx *cb = yb + 8 * NR;
-    cplx *wb = cb + 8 * NR;
-    double *dinv = reinterpret_cast<double *>(wb + 8 * NR);
+    const MolLds<NR> s(smem, D);
     const int f = blockIdx.x, lane = threadIdx.x;
     const int tx = lane & 7, ty = lane >> 3;
     const bool row = lane < D;
@@ -123,8 +246,8 @@ __global__ __launch_bounds__(64) void mvdr_online_kernel(MolArgs a) {
             for (int64_t i = lane; i < T * D; i += 64) Wf[i] = c_make(qnan, qnan);
         return;
     }
-    mol_load(gx, PX, D, ld, lane);
-    mol_load(gn, PN, D, ld, lane);
+    mol_load(gx, s.PX, D, s.ld, lane);
+    mol_load(gn, s.PN, D, s.ld, lane);
     wave_sync();
 
     const double beta = a.beta;
@@ -134,106 +257,20 @@ __global__ __launch_bounds__(64) void mvdr_online_kernel(MolArgs a) {
     for (int64_t t = 0; t < T; ++t) {
         const cplx y = y_next;
         const double ma = ma_next, mb = mb_next;
-        if (row) yb[lane] = y;
+        if (row) s.yb[lane] = y;
         if (t + 1 < T) {
             if (row) y_next = Yf[(t + 1) * D + lane];
             ma_next = mxf[t + 1];
             mb_next = mnf[t + 1];
         }
         wave_sync();
-        // the two running sums; the sweep's tile is the upper triangle of the new Phi_N
-        cplx reg[NR][NR];
-#pragma unroll
-        for (int ai = 0; ai < NR; ++ai)
-#pragma unroll
-            for (int bi = 0; bi < NR; ++bi) {
-                const int i = ty + 8 * ai, k = tx + 8 * bi;
-                reg[ai][bi] = zero;
-                if (i < D && k < D) {
-                    const cplx o = c_outer(yb[i], yb[k]);
-                    const cplx px = PX[i * ld + k], pn = PN[i * ld + k];
-                    PX[i * ld + k] = c_make(fma(beta, px.x, ma * o.x), fma(beta, px.y, ma * o.y));
-                    const cplx nn = c_make(fma(beta, pn.x, mb * o.x), fma(beta, pn.y, mb * o.y));
-                    PN[i * ld + k] = nn;
-                    if (k >= i) reg[ai][bi] = nn;
-                }
-            }
-        wave_sync();
-        const bool ok = chol_inverse_sweep<8, NR, true>(reg, D, M, ld, dinv, tx, ty);
-        cplx w = zero, x = zero;
-        if (!ok) {   // decided by the pivots alone, the same in every lane
-            ++nfall;
-        } else {
-            // M: row i holds W[i][k] / dinv[i] for k < i; W[i][i] = dinv[i].
-            // B[i][k] = dinv[i] (sum_{j<i} M[i][j] Phi_X[j][k] + Phi_X[i][k])
-            double trp = 0.0;
-#pragma unroll
-            for (int ai = 0; ai < NR; ++ai) {
-                const int i = ty + 8 * ai;
-                if (i < D) {
-                    cplx acc[NR];
-#pragma unroll
-                    for (int bi = 0; bi <= ai; ++bi) acc[bi] = zero;
-                    for (int j = 0; j < i; ++j) {
-                        const cplx m = M[i * ld + j];
-#pragma unroll
-                        for (int bi = 0; bi <= ai; ++bi) c_fma(acc[bi], m, PX[j * ld + min(tx + 8 * bi, D - 1)]);
-                    }
-                    const double d2 = dinv[i] * dinv[i];
-#pragma unroll
-                    for (int bi = 0; bi <= ai; ++bi) {
-                        const int k = tx + 8 * bi;
-                        if (k <= i) {
-                            const cplx bu = c_add(acc[bi], PX[i * ld + k]);
-                            const cplx m = k < i ? M[i * ld + k] : c_make(1.0, 0.0);
-                            trp = fma(d2, fma(bu.x, m.x, bu.y * m.y), trp);
-                        }
-                    }
-                }
-            }
-            // cb[i] = dinv[i] B[i][ref]
-            if (row) {
-                cplx acc = zero;
-                for (int j = 0; j < lane; ++j) c_fma(acc, M[lane * ld + j], PX[j * ld + ref]);
-                acc = c_add(acc, PX[lane * ld + ref]);
-                cb[lane] = c_scale(acc, dinv[lane] * dinv[lane]);
-            }
-            const double tr = wave_sum(trp);
-            wave_sync();
-            // w[k] = sum_{i >= k} conj(W[i][k]) B[i][ref] / max(tr, eps)
-            if (row) {
-                cplx acc = cb[lane];
-                for (int i = lane + 1; i < D; ++i) c_cfma(acc, M[i * ld + lane], cb[i]);
-                w = c_scale(acc, 1.0 / fmax(tr, 1e-10));
-            }
-            if (a.ban) {
-                if (row) wb[lane] = w;
-                wave_sync();
-                cplx v = zero;     // (Phi_N w)[i], from column i of the Hermitian matrix
-                if (row)
-                    for (int k = 0; k < D; ++k) c_cfma(v, PN[k * ld + lane], wb[k]);
-                const double vv = wave_sum(fma(v.x, v.x, v.y * v.y));
-                cplx wv = zero;
-                c_cfma(wv, w, v);
-                const double wr = wave_sum(wv.x), wi = wave_sum(wv.y);
-                // eps = 0 as upstream, but a filter that is exactly zero (no target mass yet: the
-                // context frames of every window) stays zero where upstream divides 0 by 0
-                const double den = hypot(wr, wi);
-                w = c_scale(w, den == 0.0 ? 0.0 : sqrt(vv) / den);
-            }
-            cplx p = zero;
-            c_cfma(p, w, y);
-            x = c_make(wave_sum(p.x), wave_sum(p.y));
-        }
+        cplx w, x;
+        if (!mol_frame<NR>(s, y, ma, mb, beta, ref, a.ban, D, lane, tx, ty, w, x)) ++nfall;
         if (lane == 0) Xf[t * a.xs_t] = x;
         if (Wf && row) Wf[t * D + lane] = w;
     }
     wave_sync();
-    for (int idx = lane; idx < D * D; idx += 64) {
-        const int r = idx / D, c = idx - r * D;
-        gx[idx] = PX[r * ld + c];
-        gn[idx] = PN[r * ld + c];
-    }
+    mol_store<NR>(s, gx, gn, D, lane);
     if (lane == 0 && nfall) atomicAdd(a.fallbacks, nfall);
 }
 
@@ -255,26 +292,18 @@ struct MolTargetsArgs {
 };
 
 // grid (F, S): one wave per (frequency, target), no LDS and no barrier shared between the waves
-// of a frequency.  The frame body is mvdr_online_kernel's, statement for statement (kept apart so
-// that the one-target kernel's code object does not move): target s has the bits of that kernel
-// on the masks of class target[s].  What differs is around it: the masks come from the posteriors
-// -- a = gamma[target], b = the sum over k != target in ascending k from 0.0, masks_kernel's
-// expressions --, whose K values of frame t + 1 are fetched while frame t's chain runs; the
-// postfilter 'mask_mul' (re a, im a: mask_mul_kernel's product) is applied to the stored value;
-// X is (S, T, F).
+// of a frequency.  The frame is mol_frame, the one mvdr_online_kernel runs: target s has the bits
+// of that kernel on the masks of class target[s].  What differs is around it: the masks come from
+// the posteriors -- a = gamma[target], b = the sum over k != target in ascending k from 0.0,
+// masks_kernel's expressions --, whose K values of frame t + 1 are fetched while frame t's chain
+// runs; the postfilter 'mask_mul' (re a, im a: mask_mul_kernel's product) is applied to the
+// stored value; X is (S, T, F); every wave has a count word of its own.
 template <int NR>
 __global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int ld = 8 * NR + 1;
     constexpr int KMAX = GSS_CACGMM_ONLINE_MAX_CLASSES;
     const int D = a.D, K = a.K, F = a.F;
-    cplx *PX = reinterpret_cast<cplx *>(smem);
-    cplx *PN = PX + D * ld;
-    cplx *M = PN + D * ld;
-    cplx *yb = M + D * ld;      // 8 NR each
-    cplx *cb = yb + 8 * NR;
-    cplx *wb = cb + 8 * NR;
-    double *dinv = reinterpret_cast<double *>(wb + 8 * NR);
+    const MolLds<NR> l(smem, D);
     const int f = blockIdx.x, s = blockIdx.y, lane = threadIdx.x;
     const int tx = lane & 7, ty = lane >> 3;
     const bool row = lane < D;
@@ -293,8 +322,8 @@ __global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs 
         if (s == 0) __hip_atomic_store(a.status, ref, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (a.ref_out) a.ref_out[s] = ref;
     }
-    mol_load(gx, PX, D, ld, lane);
-    mol_load(gn, PN, D, ld, lane);
+    mol_load(gx, l.PX, D, l.ld, lane);
+    mol_load(gn, l.PN, D, l.ld, lane);
     wave_sync();
 
     const double beta = a.beta;
@@ -312,7 +341,7 @@ __global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs 
                 if (k == target) ma = g_next[k];
                 else mb += g_next[k];
             }
-        if (row) yb[lane] = y;
+        if (row) l.yb[lane] = y;
         if (t + 1 < T) {
             if (row) y_next = Yf[(t + 1) * D + lane];
 #pragma unroll
@@ -320,84 +349,8 @@ __global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs 
                 if (k < K) g_next[k] = gf[(int64_t)k * T + t + 1];
         }
         wave_sync();
-        // the two running sums; the sweep's tile is the upper triangle of the new Phi_N
-        cplx reg[NR][NR];
-#pragma unroll
-        for (int ai = 0; ai < NR; ++ai)
-#pragma unroll
-            for (int bi = 0; bi < NR; ++bi) {
-                const int i = ty + 8 * ai, k = tx + 8 * bi;
-                reg[ai][bi] = zero;
-                if (i < D && k < D) {
-                    const cplx o = c_outer(yb[i], yb[k]);
-                    const cplx px = PX[i * ld + k], pn = PN[i * ld + k];
-                    PX[i * ld + k] = c_make(fma(beta, px.x, ma * o.x), fma(beta, px.y, ma * o.y));
-                    const cplx nn = c_make(fma(beta, pn.x, mb * o.x), fma(beta, pn.y, mb * o.y));
-                    PN[i * ld + k] = nn;
-                    if (k >= i) reg[ai][bi] = nn;
-                }
-            }
-        wave_sync();
-        const bool ok = chol_inverse_sweep<8, NR, true>(reg, D, M, ld, dinv, tx, ty);
-        cplx w = zero, x = zero;
-        if (!ok) {   // decided by the pivots alone, the same in every lane
-            ++nfall;
-        } else {
-            double trp = 0.0;
-#pragma unroll
-            for (int ai = 0; ai < NR; ++ai) {
-                const int i = ty + 8 * ai;
-                if (i < D) {
-                    cplx acc[NR];
-#pragma unroll
-                    for (int bi = 0; bi <= ai; ++bi) acc[bi] = zero;
-                    for (int j = 0; j < i; ++j) {
-                        const cplx m = M[i * ld + j];
-#pragma unroll
-                        for (int bi = 0; bi <= ai; ++bi) c_fma(acc[bi], m, PX[j * ld + min(tx + 8 * bi, D - 1)]);
-                    }
-                    const double d2 = dinv[i] * dinv[i];
-#pragma unroll
-                    for (int bi = 0; bi <= ai; ++bi) {
-                        const int k = tx + 8 * bi;
-                        if (k <= i) {
-                            const cplx bu = c_add(acc[bi], PX[i * ld + k]);
-                            const cplx m = k < i ? M[i * ld + k] : c_make(1.0, 0.0);
-                            trp = fma(d2, fma(bu.x, m.x, bu.y * m.y), trp);
-                        }
-                    }
-                }
-            }
-            if (row) {
-                cplx acc = zero;
-                for (int j = 0; j < lane; ++j) c_fma(acc, M[lane * ld + j], PX[j * ld + ref]);
-                acc = c_add(acc, PX[lane * ld + ref]);
-                cb[lane] = c_scale(acc, dinv[lane] * dinv[lane]);
-            }
-            const double tr = wave_sum(trp);
-            wave_sync();
-            if (row) {
-                cplx acc = cb[lane];
-                for (int i = lane + 1; i < D; ++i) c_cfma(acc, M[i * ld + lane], cb[i]);
-                w = c_scale(acc, 1.0 / fmax(tr, 1e-10));
-            }
-            if (a.ban) {
-                if (row) wb[lane] = w;
-                wave_sync();
-                cplx v = zero;
-                if (row)
-                    for (int k = 0; k < D; ++k) c_cfma(v, PN[k * ld + lane], wb[k]);
-                const double vv = wave_sum(fma(v.x, v.x, v.y * v.y));
-                cplx wv = zero;
-                c_cfma(wv, w, v);
-                const double wr = wave_sum(wv.x), wi = wave_sum(wv.y);
-                const double den = hypot(wr, wi);
-                w = c_scale(w, den == 0.0 ? 0.0 : sqrt(vv) / den);
-            }
-            cplx p = zero;
-            c_cfma(p, w, y);
-            x = c_make(wave_sum(p.x), wave_sum(p.y));
-        }
+        cplx w, x;
+        if (!mol_frame<NR>(l, y, ma, mb, beta, ref, a.ban, D, lane, tx, ty, w, x)) ++nfall;
         if (lane == 0) {
             Xs[t * F] = a.postfilter ? c_scale(x, ma) : x;
             if (mxf) mxf[t] = ma;
@@ -406,11 +359,7 @@ __global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs 
         if (Wf && row) Wf[t * D + lane] = w;
     }
     wave_sync();
-    for (int idx = lane; idx < D * D; idx += 64) {
-        const int r = idx / D, c = idx - r * D;
-        gx[idx] = PX[r * ld + c];
-        gn[idx] = PN[r * ld + c];
-    }
+    mol_store<NR>(l, gx, gn, D, lane);
     if (lane == 0) a.fallbacks[sf] = nfall;   // every wave writes its own word: no atomic, no memset
 }
 
@@ -444,6 +393,20 @@ size_t mol_lds_bytes(int D) {
     const size_t nr = (size_t)(D + 7) / 8, ld = 8 * nr + 1;
     return sizeof(cplx) * (3 * (size_t)D * ld + 3 * 8 * nr) + sizeof(double) * 8 * nr;
 }
+
+// One wave per workgroup of `grid` with the LDS of D channels, the form NR = ceil(D / 8) of
+// `kernels` = {<1>, <2>, <3>, <4>}.
+template <typename Args>
+int mol_launch(gss_ctx *ctx, void (*const (&kernels)[4])(Args), dim3 grid, int D, const Args &a) {
+    const size_t lds = mol_lds_bytes(D);
+    void (*const kernel)(Args) = kernels[(D - 1) / 8];
+    if (lds > 48 * 1024)
+        GSS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, grid, dim3(64), lds, ctx->stream, a);
+    return GSS_OK;
+}
+#define GSS_MOL_KERNELS(kernel) {kernel<1>, kernel<2>, kernel<3>, kernel<4>}
 
 }  // namespace
 
@@ -508,24 +471,11 @@ int mvdr_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const 
         GSS_TRY(arena_release(ctx, mark));
         ref_dev = words + 1;
     }
-    MolArgs a{Y, mx, mn, phi_x, phi_n, X, xs_f, xs_t, W, ref_dev, words, ctx->status_dev, ref_out,
-              T, D, ref, ban, beta};
+    const MolArgs a{Y, mx, mn, phi_x, phi_n, X, xs_f, xs_t, W, ref_dev, words, ctx->status_dev,
+                    ref_out, T, D, ref, ban, beta};
     {
         GSS_PROF(ctx, "mvdr_online");
-        const size_t lds = mol_lds_bytes(D);
-#define GSS_MOL_LAUNCH(NR)                                                                         \
-    do {                                                                                           \
-        if (lds > 48 * 1024)                                                                       \
-            GSS_HIP_CHECK(ctx, hipFuncSetAttribute(                                                \
-                                   reinterpret_cast<const void *>(mvdr_online_kernel<NR>),         \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));         \
-        hipLaunchKernelGGL(mvdr_online_kernel<NR>, dim3(F), dim3(64), lds, ctx->stream, a);        \
-    } while (0)
-        if (D <= 8) GSS_MOL_LAUNCH(1);
-        else if (D <= 16) GSS_MOL_LAUNCH(2);
-        else if (D <= 24) GSS_MOL_LAUNCH(3);
-        else GSS_MOL_LAUNCH(4);
-#undef GSS_MOL_LAUNCH
+        GSS_TRY(mol_launch(ctx, GSS_MOL_KERNELS(mvdr_online_kernel), dim3(F), D, a));
         GSS_LAUNCH_CHECK(ctx, "mvdr_online_kernel");
     }
     // the count of this call -> the context's status word
@@ -555,7 +505,8 @@ size_t mvdr_online_targets_workspace_bytes(int F, int S) {
 // S targets (1 <= S <= GSS_CACGMM_ONLINE_MAX_CLASSES) from the posteriors gamma (F,K,T), each
 // with the caller's state, advanced in place.  X (S,T,F); mx / mn (S,F,T) or NULL; W (S,F,T,D)
 // or NULL; ref_out (S,) or NULL.  The arguments have been validated by the entry point (T >= 1,
-// ref >= 0).
+// ref >= 0), which also records S for gss_last_mvdr_online_fallbacks_targets where the call is
+// one of S targets for its caller (the one-target stream block runs this with S = 1).
 int mvdr_online_targets_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
                             const double *gamma, int K, const int32_t *targets, int S, int ban,
                             double beta, int ref, cplx *const *phi_x, cplx *const *phi_n,
@@ -566,7 +517,6 @@ int mvdr_online_targets_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D
     GSS_TRY(ws.status("online mvdr targets"));
     int32_t *words = k.words;
     ctx->last_targets = 0;
-    ctx->last_online_targets = S;
     MolTargetsArgs a{};
     a.Y = Y, a.gamma = gamma, a.mx = mx, a.mn = mn, a.X = X, a.W = W;
     a.fallbacks = k.counts, a.status = ctx->status_dev, a.ref_out = ref_out;
@@ -575,21 +525,7 @@ int mvdr_online_targets_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D
     for (int s = 0; s < S; ++s) a.phi_x[s] = phi_x[s], a.phi_n[s] = phi_n[s], a.target[s] = targets[s];
     {
         GSS_PROF(ctx, "mvdr_online_targets");
-        const size_t lds = mol_lds_bytes(D);
-#define GSS_MOL_LAUNCH(NR)                                                                         \
-    do {                                                                                           \
-        if (lds > 48 * 1024)                                                                       \
-            GSS_HIP_CHECK(ctx, hipFuncSetAttribute(                                                \
-                                   reinterpret_cast<const void *>(mvdr_online_targets_kernel<NR>), \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));         \
-        hipLaunchKernelGGL(mvdr_online_targets_kernel<NR>, dim3(F, S), dim3(64), lds, ctx->stream, \
-                           a);                                                                     \
-    } while (0)
-        if (D <= 8) GSS_MOL_LAUNCH(1);
-        else if (D <= 16) GSS_MOL_LAUNCH(2);
-        else if (D <= 24) GSS_MOL_LAUNCH(3);
-        else GSS_MOL_LAUNCH(4);
-#undef GSS_MOL_LAUNCH
+        GSS_TRY(mol_launch(ctx, GSS_MOL_KERNELS(mvdr_online_targets_kernel), dim3(F, S), D, a));
         GSS_LAUNCH_CHECK(ctx, "mvdr_online_targets_kernel");
         hipLaunchKernelGGL(mvdr_online_targets_count_kernel, dim3(1), dim3(256), 0, ctx->stream,
                            k.counts, F, S, words);

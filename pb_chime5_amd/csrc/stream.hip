@@ -116,15 +116,8 @@ __device__ __forceinline__ void stream_ola_sample(
         out[p - pad - first_out] = acc;
 }
 
-__global__ __launch_bounds__(256) void stream_ola_kernel(
-    const double *__restrict__ frm, int64_t t0, int64_t Tn, int size, int shift,
-    const double *__restrict__ tail, double *__restrict__ tail_new, int64_t first_out,
-    double *__restrict__ out) {
-    stream_ola_sample(frm, t0, Tn, size, shift, tail, tail_new, first_out, out);
-}
-
-// The same for S signals, grid.y = s: frm (S,Tn,size), tail / tail_new (S, size - shift), out
-// (S, m).  Signal s is stream_ola_kernel on its own rows.
+// grid.y = s, one of S signals: frm (S,Tn,size), tail / tail_new (S, size - shift), out (S, m).
+// Every signal is summed on its own rows, whatever S.
 __global__ __launch_bounds__(256) void stream_ola_targets_kernel(
     const double *__restrict__ frm, int64_t t0, int64_t Tn, int size, int shift,
     const double *__restrict__ tail, double *__restrict__ tail_new, int64_t first_out, int64_t m,
@@ -152,7 +145,7 @@ struct StreamIstftWork {
     double *frm;        // (S Tn, size)
     double *tail_new;   // (S, size - shift)
 };
-StreamIstftWork stream_istft_blocks(Workspace &ws, int64_t Tn, int size, int shift, int S = 1) {
+StreamIstftWork stream_istft_blocks(Workspace &ws, int64_t Tn, int size, int shift, int S) {
     StreamIstftWork k;
     k.frm = ws.take<double>((size_t)S * Tn * size, "stream istft frames");
     k.tail_new = ws.take<double>((size_t)S * (size - shift), "stream new tail");
@@ -164,12 +157,6 @@ StreamIstftWork stream_istft_blocks(Workspace &ws, int64_t Tn, int size, int shi
 size_t stream_stft_workspace_bytes(int64_t Tn, int D, int K, int size, int shift) {
     Workspace ws;
     if (Tn > 0) stream_stft_blocks(ws, Tn, D, K, size, shift);
-    return ws.bytes + 4096;
-}
-
-size_t stream_istft_workspace_bytes(int64_t Tn, int size, int shift) {
-    Workspace ws;
-    if (Tn > 0) stream_istft_blocks(ws, Tn, size, shift);
     return ws.bytes + 4096;
 }
 
@@ -254,30 +241,9 @@ int stream_stft_run(gss_ctx *ctx, const void *x, int in_type, const uint8_t *act
     return GSS_OK;
 }
 
-int stream_istft_run(gss_ctx *ctx, const cplx *X, int64_t Tn, gss_stream_state *st, double *out) {
-    const int W = st->size, H = st->shift;
-    const int64_t t0 = st->frames_out;
-    Workspace ws(ctx);
-    const StreamIstftWork k = stream_istft_blocks(ws, Tn, W, H);
-    GSS_TRY(ws.status("gss_istft_stream"));
-    GSS_TRY(istft_single_frames_run(ctx, X, Tn, k.frm));
-    {
-        GSS_PROF(ctx, "stream_ola");
-        const int64_t total = Tn * H + (W - H);
-        hipLaunchKernelGGL(stream_ola_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                           ctx->stream, k.frm, t0, Tn, W, H, st->ola_tail, k.tail_new,
-                           stream_emitted(t0, W, H), out);
-        GSS_LAUNCH_CHECK(ctx, "stream_ola_kernel");
-    }
-    if (W > H)
-        GSS_HIP_CHECK(ctx, hipMemcpyAsync(st->ola_tail, k.tail_new, sizeof(double) * (W - H),
-                                          hipMemcpyDeviceToDevice, ctx->stream));
-    st->frames_out = t0 + Tn;
-    return GSS_OK;
-}
-
 // The S Tn frames go through istft_single_frames_run as one batch (every frame on its own: frame
-// (s, t) has the bits it has in a call of signal s alone), then one overlap-add launch.
+// (s, t) has the bits it has in a call of signal s alone), then one overlap-add launch.  The one
+// synthesis: a one-signal stream is S = 1 with tails = st->ola_tail.
 int stream_istft_targets_run(gss_ctx *ctx, const cplx *X, int64_t Tn, int S, gss_stream_state *st,
                              double *tails, double *out) {
     const int W = st->size, H = st->shift;

@@ -3179,30 +3179,97 @@ def stft_stream(block, activity=None, *, state, window=None):
     return Y, (ctx.to_host(a_d, (K, Tn), np.uint8).astype(bool) if K else None)
 
 
+def _istft_stream_call(stft_signal, state, window, targets=False, tails=None):
+    """What `istft_stream` (frames (Tn,F)) and `istft_stream_targets` (``targets``: frames
+    (S,Tn,F) and their `StreamTails`) share: the checks, the sample count and the call of the
+    entry of either -> (S,m)."""
+    if not isinstance(state, StreamState):
+        raise ValueError(f'state: {type(state).__name__} is not a StreamState')
+    if targets and not isinstance(tails, StreamTails):
+        raise ValueError(f'tails: {type(tails).__name__} is not a StreamTails')
+    X = np.asarray(stft_signal, dtype=np.complex128)
+    F, lead = state.size // 2 + 1, '(S,Tn,' if targets else '(Tn,'
+    if X.ndim != (3 if targets else 2) or X.shape[-1] != F:
+        raise ValueError(f'stft_signal: shape {X.shape} is not {lead}F) = {lead}{F})')
+    S, Tn = X.shape[:2] if targets else (1, X.shape[0])
+    ctx, pad = state.ctx, state.size - state.shift
+    if targets:
+        if tails.key != (S, pad):
+            raise ValueError(f'tails: built for ({tails._sizes}) = {tails.key}, the call has '
+                             f'{(S, pad)}')
+        if tails.ctx is not ctx:
+            raise ValueError('tails: they live in another context than the stream')
+    if Tn == 0:
+        return np.zeros((S, 0))
+    m = (max(0, (state.frames_out + Tn) * state.shift - pad)
+         - max(0, state.frames_out * state.shift - pad))
+    _prepare_windows(ctx, state.size, state.shift, window)
+    X_d = ctx.to_device(X)
+    o_d = ctx.empty(max(8 * S * m, 16))
+    if targets:
+        ctx._check(ctx.lib.gss_istft_stream_targets(
+            ctx.handle, c_void_p(X_d.ptr), Tn, S, ctypes.byref(state.struct()),
+            c_void_p(tails.ptr), c_void_p(o_d.ptr)), 'gss_istft_stream_targets')
+    else:
+        ctx._check(ctx.lib.gss_istft_stream(ctx.handle, c_void_p(X_d.ptr), Tn,
+                                            ctypes.byref(state.struct()), c_void_p(o_d.ptr)),
+                   'gss_istft_stream')
+    return ctx.to_host(o_d, (S, m), np.float64)
+
+
 def istft_stream(stft_signal, *, state, window=None):
     """The synthesis side of a stream (gss_istft_stream): the next frames (Tn,F) -> the samples
     they finish, `stream_num_samples_out` of them.  ``state``: the `StreamState` whose analysis
     side produced the frames, advanced IN PLACE.  Every frame is transformed on its own: the
     samples do not depend on where the blocks were cut."""
-    if not isinstance(state, StreamState):
-        raise ValueError(f'state: {type(state).__name__} is not a StreamState')
-    X = np.asarray(stft_signal, dtype=np.complex128)
-    F = state.size // 2 + 1
-    if X.ndim != 2 or X.shape[1] != F:
-        raise ValueError(f'stft_signal: shape {X.shape} is not (Tn,F) = (Tn,{F})')
-    Tn = X.shape[0]
-    if Tn == 0:
-        return np.zeros(0)
-    ctx, pad = state.ctx, state.size - state.shift
-    m = (max(0, (state.frames_out + Tn) * state.shift - pad)
-         - max(0, state.frames_out * state.shift - pad))
-    _prepare_windows(ctx, state.size, state.shift, window)
-    X_d = ctx.to_device(X)
-    o_d = ctx.empty(max(8 * m, 16))
-    ctx._check(ctx.lib.gss_istft_stream(ctx.handle, c_void_p(X_d.ptr), Tn,
-                                        ctypes.byref(state.struct()), c_void_p(o_d.ptr)),
-               'gss_istft_stream')
-    return ctx.to_host(o_d, (m,), np.float64)
+    return _istft_stream_call(stft_signal, state, window)[0]
+
+
+def _stream_block_call(entry, block, activity, params, stream, em_state, wpe_state, states,
+                       bf_args, cfg, window, debug):
+    """What `stream_block` and `stream_block_targets` share around the library call ``entry``:
+    the checks of ``stream`` and of ``states`` ((name, state, class), in this order), then
+    ``bf_args()``, the caller's own checks of its targets and beamformer states -> (S, the
+    entry's arguments after the CACGMM state, those after n); the block on the device, the
+    counts, the windows, the taps, ``cfg`` = (wpe_alpha, em_forget, bf_forget, ref_channel), the
+    call and the download.  Returns (samples (S,m), details of `_debug_details` or None)."""
+    if not isinstance(stream, StreamState):
+        raise ValueError(f'stream: {type(stream).__name__} is not a StreamState')
+    ctx = stream.ctx
+    for name, state, cls in states:
+        if state is None and name == 'wpe_state':
+            continue
+        if not isinstance(state, cls):
+            raise ValueError(f'{name}: {type(state).__name__} is not an {cls.__name__}')
+        if state.ctx is not ctx:
+            raise ValueError(f'{name}: it lives in another context than the stream')
+    S, bf_head, bf_tail = bf_args()
+    x_d, in_type, act_d, n = _stream_block_to_device(ctx, block, activity, stream)
+    if n == 0:
+        return np.zeros((S, 0)), None
+    Tn = stream_num_frames(stream.received, n, stream.size, stream.shift)
+    m = stream_num_samples_out(stream.received, n, stream.size, stream.shift)
+    _prepare_windows(ctx, stream.size, stream.shift, window)
+    o_d = ctx.empty(max(8 * S * m, 16))
+    utt = SimpleNamespace(ctx=ctx, D=stream.D, K=em_state.K, T=Tn, params=params)
+    bufs, taps = _debug_taps(utt, S) if debug and Tn > 0 else (None, None)
+    wpe_alpha, em_forget, bf_forget, ref_channel = cfg
+    cfg = GssStreamCfg(wpe_alpha=float(wpe_alpha), em_forget=float(em_forget),
+                       bf_forget=float(bf_forget), ref_channel=int(ref_channel))
+    ctx._check(getattr(ctx.lib, entry)(
+        ctx.handle, ctypes.byref(params), ctypes.byref(cfg), ctypes.byref(stream.struct()),
+        ctypes.byref(wpe_state.struct()) if wpe_state is not None else None,
+        ctypes.byref(em_state.struct()), *bf_head, c_void_p(x_d.ptr), in_type,
+        c_void_p(act_d.ptr) if act_d else None, n, *bf_tail, c_void_p(o_d.ptr),
+        ctypes.byref(taps) if taps is not None else None), entry)
+    samples = ctx.to_host(o_d, (S, m), np.float64)
+    if m == 0:
+        ctx.synchronize()      # (the block's device copies are read until then)
+    if bufs is None:
+        return samples, None
+    if act_d is None:
+        del bufs['act_frames']
+    return samples, _debug_details(utt, bufs, S)
 
 
 def stream_block(block, activity=None, *, params, stream, em_state, bf_state, wpe_state=None,
@@ -3216,48 +3283,19 @@ def stream_block(block, activity=None, *, params, stream, em_state, bf_state, wp
     PLACE.  ``wpe_state`` is None exactly when ``params.wpe`` is 0.  Returns (samples, details):
     the samples the block finishes, and with ``debug`` the taps over the block's frames (else
     None), with 'fallbacks' = (online MVDR, online CACGMM) counts of the block."""
-    if not isinstance(stream, StreamState):
-        raise ValueError(f'stream: {type(stream).__name__} is not a StreamState')
-    ctx = stream.ctx
-    for name, state, cls in (('em_state', em_state, OnlineCACGMMState),
-                             ('bf_state', bf_state, OnlineMVDRState),
-                             ('wpe_state', wpe_state, OnlineWPEState)):
-        if state is None and name == 'wpe_state':
-            continue
-        if not isinstance(state, cls):
-            raise ValueError(f'{name}: {type(state).__name__} is not an {cls.__name__}')
-        if state.ctx is not ctx:
-            raise ValueError(f'{name}: it lives in another context than the stream')
-    x_d, in_type, act_d, n = _stream_block_to_device(ctx, block, activity, stream)
-    if n == 0:
-        return np.zeros(0), None
-    D, K, F = stream.D, em_state.K, stream.size // 2 + 1
-    Tn = stream_num_frames(stream.received, n, stream.size, stream.shift)
-    m = stream_num_samples_out(stream.received, n, stream.size, stream.shift)
-    _prepare_windows(ctx, stream.size, stream.shift, window)
-    o_d = ctx.empty(max(8 * m, 16))
-    utt = SimpleNamespace(ctx=ctx, D=D, K=K, T=Tn, params=params)
-    bufs, taps = _debug_taps(utt) if debug and Tn > 0 else (None, None)
-    cfg = GssStreamCfg(wpe_alpha=float(wpe_alpha), em_forget=float(em_forget),
-                       bf_forget=float(bf_forget), ref_channel=int(ref_channel))
-    ctx._check(ctx.lib.gss_stream_block(
-        ctx.handle, ctypes.byref(params), ctypes.byref(cfg), ctypes.byref(stream.struct()),
-        ctypes.byref(wpe_state.struct()) if wpe_state is not None else None,
-        ctypes.byref(em_state.struct()), ctypes.byref(bf_state.struct()), c_void_p(x_d.ptr),
-        in_type, c_void_p(act_d.ptr) if act_d else None, n, int(target_index), c_void_p(o_d.ptr),
-        ctypes.byref(taps) if taps is not None else None), 'gss_stream_block')
-    samples = ctx.to_host(o_d, (m,), np.float64)
-    if m == 0:
-        ctx.synchronize()      # (the block's device copies are read until then)
-    if bufs is None:
-        return samples, None
-    if act_d is None:
-        del bufs['act_frames']
-    details = _debug_details(utt, bufs)
-    details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
-    details['ref_channel'] = int(details['ref_channel'])
-    details['fallbacks'] = (ctx.last_mvdr_online_fallbacks(), ctx.last_cacgmm_online_fallbacks())
-    return samples, details
+    samples, details = _stream_block_call(
+        'gss_stream_block', block, activity, params, stream, em_state, wpe_state,
+        (('em_state', em_state, OnlineCACGMMState), ('bf_state', bf_state, OnlineMVDRState),
+         ('wpe_state', wpe_state, OnlineWPEState)),
+        lambda: (1, [ctypes.byref(bf_state.struct())], [int(target_index)]),
+        (wpe_alpha, em_forget, bf_forget, ref_channel), window, debug)
+    if details is not None:
+        ctx = stream.ctx
+        details.update({k: v[0] for k, v in details.items() if k in _PER_TARGET})
+        details['ref_channel'] = int(details['ref_channel'])
+        details['fallbacks'] = (ctx.last_mvdr_online_fallbacks(),
+                                ctx.last_cacgmm_online_fallbacks())
+    return samples[0], details
 
 
 # --------------------------------------------------------------------------
@@ -3385,32 +3423,7 @@ def istft_stream_targets(stft_signal, *, state, tails, window=None):
     frames (S,Tn,F) -> (S,m), row s with the bits of `istft_stream` on stft_signal[s].  ``state``:
     the `StreamState` of the analysis side, its frame counter advanced once, its own tail left
     alone; ``tails``: the `StreamTails` of the S signals, advanced IN PLACE."""
-    if not isinstance(state, StreamState):
-        raise ValueError(f'state: {type(state).__name__} is not a StreamState')
-    if not isinstance(tails, StreamTails):
-        raise ValueError(f'tails: {type(tails).__name__} is not a StreamTails')
-    X = np.asarray(stft_signal, dtype=np.complex128)
-    F = state.size // 2 + 1
-    if X.ndim != 3 or X.shape[2] != F:
-        raise ValueError(f'stft_signal: shape {X.shape} is not (S,Tn,F) = (S,Tn,{F})')
-    S, Tn = X.shape[:2]
-    if tails.key != (S, state.size - state.shift):
-        raise ValueError(f'tails: built for ({tails._sizes}) = {tails.key}, the call has '
-                         f'{(S, state.size - state.shift)}')
-    if tails.ctx is not state.ctx:
-        raise ValueError('tails: they live in another context than the stream')
-    if Tn == 0:
-        return np.zeros((S, 0))
-    ctx, pad = state.ctx, state.size - state.shift
-    m = (max(0, (state.frames_out + Tn) * state.shift - pad)
-         - max(0, state.frames_out * state.shift - pad))
-    _prepare_windows(ctx, state.size, state.shift, window)
-    X_d = ctx.to_device(X)
-    o_d = ctx.empty(max(8 * S * m, 16))
-    ctx._check(ctx.lib.gss_istft_stream_targets(
-        ctx.handle, c_void_p(X_d.ptr), Tn, S, ctypes.byref(state.struct()), c_void_p(tails.ptr),
-        c_void_p(o_d.ptr)), 'gss_istft_stream_targets')
-    return ctx.to_host(o_d, (S, m), np.float64)
+    return _istft_stream_call(stft_signal, state, window, True, tails)
 
 
 def stream_block_targets(block, activity=None, *, params, stream, em_state, bf_states, tails,
@@ -3424,53 +3437,26 @@ def stream_block_targets(block, activity=None, *, params, stream, em_state, bf_s
     `stream_block` with target_indices[s]; with ``debug`` the per-target taps are stacked over S as
     in `enhance_observation_targets`, 'fallbacks' = (online MVDR summed over the targets, online
     CACGMM) and 'fallbacks_targets' the online MVDR's per target."""
-    if not isinstance(stream, StreamState):
-        raise ValueError(f'stream: {type(stream).__name__} is not a StreamState')
-    ctx = stream.ctx
-    for name, state, cls in (('em_state', em_state, OnlineCACGMMState),
-                             ('wpe_state', wpe_state, OnlineWPEState),
-                             ('tails', tails, StreamTails)):
-        if state is None and name == 'wpe_state':
-            continue
-        if not isinstance(state, cls):
-            raise ValueError(f'{name}: {type(state).__name__} is not an {cls.__name__}')
-        if state.ctx is not ctx:
-            raise ValueError(f'{name}: it lives in another context than the stream')
-    D, K, F = stream.D, em_state.K, stream.size // 2 + 1
-    targets = check_online_targets(target_indices, K)
-    S = len(targets)
-    _, structs = _check_target_states(bf_states, S, (F, D), ctx, 'bf_states')
-    if tails.key != (S, stream.size - stream.shift):
-        raise ValueError(f'tails: built for ({tails._sizes}) = {tails.key}, the call has '
-                         f'{(S, stream.size - stream.shift)}')
-    x_d, in_type, act_d, n = _stream_block_to_device(ctx, block, activity, stream)
-    if n == 0:
-        return np.zeros((S, 0)), None
-    Tn = stream_num_frames(stream.received, n, stream.size, stream.shift)
-    m = stream_num_samples_out(stream.received, n, stream.size, stream.shift)
-    _prepare_windows(ctx, stream.size, stream.shift, window)
-    o_d = ctx.empty(max(8 * S * m, 16))
-    utt = SimpleNamespace(ctx=ctx, D=D, K=K, T=Tn, params=params)
-    bufs, taps = _debug_taps(utt, S) if debug and Tn > 0 else (None, None)
-    cfg = GssStreamCfg(wpe_alpha=float(wpe_alpha), em_forget=float(em_forget),
-                       bf_forget=float(bf_forget), ref_channel=int(ref_channel))
-    ctx._check(ctx.lib.gss_stream_block_targets(
-        ctx.handle, ctypes.byref(params), ctypes.byref(cfg), ctypes.byref(stream.struct()),
-        ctypes.byref(wpe_state.struct()) if wpe_state is not None else None,
-        ctypes.byref(em_state.struct()), structs, c_void_p(tails.ptr), c_void_p(x_d.ptr), in_type,
-        c_void_p(act_d.ptr) if act_d else None, n, (ctypes.c_int32 * S)(*targets), S,
-        c_void_p(o_d.ptr), ctypes.byref(taps) if taps is not None else None),
-        'gss_stream_block_targets')
-    samples = ctx.to_host(o_d, (S, m), np.float64)
-    if m == 0:
-        ctx.synchronize()      # (the block's device copies are read until then)
-    if bufs is None:
-        return samples, None
-    if act_d is None:
-        del bufs['act_frames']
-    details = _debug_details(utt, bufs, S)
-    details['fallbacks'] = (ctx.last_mvdr_online_fallbacks(), ctx.last_cacgmm_online_fallbacks())
-    details['fallbacks_targets'] = ctx.last_mvdr_online_fallbacks_targets(S)
+    def bf_args():
+        targets = check_online_targets(target_indices, em_state.K)
+        S = len(targets)
+        _, structs = _check_target_states(bf_states, S, (stream.size // 2 + 1, stream.D),
+                                          stream.ctx, 'bf_states')
+        if tails.key != (S, stream.size - stream.shift):
+            raise ValueError(f'tails: built for ({tails._sizes}) = {tails.key}, the call has '
+                             f'{(S, stream.size - stream.shift)}')
+        return S, [structs, c_void_p(tails.ptr)], [(ctypes.c_int32 * S)(*targets), S]
+
+    samples, details = _stream_block_call(
+        'gss_stream_block_targets', block, activity, params, stream, em_state, wpe_state,
+        (('em_state', em_state, OnlineCACGMMState), ('wpe_state', wpe_state, OnlineWPEState),
+         ('tails', tails, StreamTails)),
+        bf_args, (wpe_alpha, em_forget, bf_forget, ref_channel), window, debug)
+    if details is not None:
+        ctx = stream.ctx
+        details['fallbacks'] = (ctx.last_mvdr_online_fallbacks(),
+                                ctx.last_cacgmm_online_fallbacks())
+        details['fallbacks_targets'] = ctx.last_mvdr_online_fallbacks_targets(samples.shape[0])
     return samples, details
 
 

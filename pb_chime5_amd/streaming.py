@@ -101,8 +101,7 @@ class StreamingEnhancer:
     def reset(self):
         """Back to the start of a stream: fresh states (the mixture model from ``model`` again),
         the counters and the fallback counts at zero."""
-        self.stream = self.wpe_state = self.em_state = self.bf_state = None
-        self.bf_states = self.tails = self.tail_streams = None
+        self.stream = self.wpe_state = self.em_state = self.bf_states = self.tails = None
         self.samples_in = self.samples_out = 0
         self.fallbacks = {'mvdr': 0, 'cacgmm': 0}
         if self.targets is not None:
@@ -124,23 +123,14 @@ class StreamingEnhancer:
                          if self.guided else
                          ops.OnlineCACGMMState.from_model(self.model, self.gss_prior_mass, ctx=ctx))
         # (no frames: a stream has none yet, p_f = 1)
-        if self.targets is None:
-            self.bf_state = ops.OnlineMVDRState.fresh(F, D, self.bf_loading, ctx=ctx)
-            return
-        S = len(self.targets)
         self.bf_states = [ops.OnlineMVDRState.fresh(F, D, self.bf_loading, ctx=ctx)
-                          for _ in range(S)]
-        self.tails = ops.StreamTails.fresh(S, self.size, self.shift, ctx=ctx)
-        self._tail_streams()
+                          for _ in self._classes()]
+        if self.targets is not None:
+            self.tails = ops.StreamTails.fresh(len(self.targets), self.size, self.shift, ctx=ctx)
 
-    def _tail_streams(self):
-        """fused=False: a `StreamState` per target for `istft_stream`, which keeps its tail there;
-        every other part of these states is left alone (``tails`` is the record)."""
-        self.tail_streams = None
-        if not self.fused:
-            self.tail_streams = [ops.StreamState.fresh(1, 0, self.size, self.shift,
-                                                       window=self.window, ctx=self.ctx)
-                                 for _ in self.targets]
+    def _classes(self):
+        """The classes extracted, one beamformer state each."""
+        return (self.target,) if self.targets is None else self.targets
 
     @property
     def latency_samples(self):
@@ -152,7 +142,7 @@ class StreamingEnhancer:
         context) and the counters."""
         self._states()
         if self.targets is None:
-            bf = {'bf': self.bf_state.to_host()}
+            bf = {'bf': self.bf_states[0].to_host()}
         else:       # the S beamformer states stacked, the tails and whose they are
             states = [state.to_host() for state in self.bf_states]
             bf = {'bf': {k: np.stack([h[k] for h in states]) for k in states[0]},
@@ -202,15 +192,9 @@ class StreamingEnhancer:
             if state is not None and state.key != key:
                 raise ValueError(f'checkpoint: {name} state built for ({state._sizes}) = '
                                  f'{state.key}, this stream has {key}')
-        self.stream, self.em_state, self.wpe_state = stream, em, wpe
-        if self.targets is None:
-            self.bf_state = bf
-        else:
-            self.bf_states, self.tails = bfs, tails
-            if not self.fused:      # the per-target tails of the stage path, from the record
-                self._tail_streams()
-                for s, state in enumerate(self.tail_streams):
-                    ctx.upload(state.bufs['ola_tail'], np.ascontiguousarray(host['tails'][s]))
+        self.stream, self.em_state, self.wpe_state, self.bf_states = stream, em, wpe, bfs
+        if self.targets is not None:
+            self.tails = tails
         self.samples_in, self.samples_out = int(host['samples_in']), int(host['samples_out'])
         self.fallbacks = {k: list(v) if isinstance(v, (list, tuple)) else v
                           for k, v in host['fallbacks'].items()}
@@ -281,76 +265,42 @@ class StreamingEnhancer:
         if block.shape[1] == 0:
             return self._no_samples(), None
         self._states()
+        if not self.fused:
+            return self._block_stages(block, activity, debug)
         Tn = ops.stream_num_frames(self.stream.received, block.shape[1], self.size, self.shift)
+        shared = dict(params=self.params, stream=self.stream, em_state=self.em_state,
+                      wpe_state=self.wpe_state, ref_channel=self.ref_channel,
+                      wpe_alpha=self.wpe_alpha, em_forget=self.gss_forget,
+                      bf_forget=self.bf_forget, window=self.window, debug=debug)
         if self.targets is not None:
-            if not self.fused:
-                return self._block_stages_targets(block, activity, debug)
             samples, details = ops.stream_block_targets(
-                block, activity, params=self.params, stream=self.stream, em_state=self.em_state,
-                bf_states=self.bf_states, tails=self.tails, wpe_state=self.wpe_state,
-                target_indices=self.targets, ref_channel=self.ref_channel,
-                wpe_alpha=self.wpe_alpha, em_forget=self.gss_forget, bf_forget=self.bf_forget,
-                window=self.window, debug=debug)
+                block, activity, bf_states=self.bf_states, tails=self.tails,
+                target_indices=self.targets, **shared)
             if Tn > 0:
                 self._count(self.ctx.last_mvdr_online_fallbacks_targets(len(self.targets)),
                             self.ctx.last_cacgmm_online_fallbacks())
             return samples, details
-        if self.fused:
-            samples, details = ops.stream_block(
-                block, activity, params=self.params, stream=self.stream, em_state=self.em_state,
-                bf_state=self.bf_state, wpe_state=self.wpe_state, target_index=self.target,
-                ref_channel=self.ref_channel, wpe_alpha=self.wpe_alpha, em_forget=self.gss_forget,
-                bf_forget=self.bf_forget, window=self.window, debug=debug)
-            if Tn > 0:
-                counts = (details['fallbacks'] if details is not None else
-                          (self.ctx.last_mvdr_online_fallbacks(),
-                           self.ctx.last_cacgmm_online_fallbacks()))
-                self.fallbacks['mvdr'] += counts[0]
-                self.fallbacks['cacgmm'] += counts[1]
-            return samples, details
-        return self._block_stages(block, activity, debug)
-
-    def _block_stages(self, block, activity, debug):
-        """The block through the stage operators, each with its explicit state."""
-        Y, act_frames = ops.stft_stream(block, activity, state=self.stream, window=self.window)
-        if Y.shape[1] == 0:
-            return np.zeros(0), None
-        Obs = Y
-        if self.wpe:
-            Obs = ops.wpe_online_dtf(Y, self.wpe_taps, self.wpe_delay, self.wpe_alpha,
-                                     arrays=self.wpe_arrays, state=self.wpe_state)
-        posterior, em_fallbacks = ops.cacgmm_posteriors_online(
-            Obs, act_frames, forget=self.gss_forget, state=self.em_state, return_fallbacks=True)
-        target_mask, distortion_mask = ops.masks_from_posteriors(posterior, self.target,
-                                                                 ctx=self.ctx)
-        X_hat, bf_fallbacks = ops.mvdr_souden_online_from_masks(
-            Obs, target_mask, distortion_mask, ban=True, forget=self.bf_forget,
-            ref_channel=self.ref_channel, state=self.bf_state, return_fallbacks=True)
-        if self.postfilter == 'mask_mul':
-            # (re * m, im * m as the library's postfilter, not a complex product)
-            X_hat = (X_hat.view(np.float64).reshape(X_hat.shape + (2,))
-                     * target_mask[..., None]).reshape(X_hat.shape[0], -1).view(np.complex128)
-        samples = ops.istft_stream(X_hat, state=self.stream, window=self.window)
-        self.fallbacks['mvdr'] += bf_fallbacks
-        self.fallbacks['cacgmm'] += em_fallbacks
-        details = None
-        if debug:
-            details = {'Obs': Obs, 'posterior': posterior, 'target_mask': target_mask,
-                       'distortion_mask': distortion_mask, 'X_hat': X_hat,
-                       'ref_channel': self.ref_channel, 'fallbacks': (bf_fallbacks, em_fallbacks)}
-            if act_frames is not None:
-                details['acitivity_freq'] = act_frames
+        samples, details = ops.stream_block(block, activity, bf_state=self.bf_states[0],
+                                            target_index=self.target, **shared)
+        if Tn > 0:
+            counts = (details['fallbacks'] if details is not None else
+                      (self.ctx.last_mvdr_online_fallbacks(),
+                       self.ctx.last_cacgmm_online_fallbacks()))
+            self._count([counts[0]], counts[1])
         return samples, details
 
     def _count(self, bf_targets, em_fallbacks):
         self.fallbacks['mvdr'] += sum(bf_targets)
         self.fallbacks['cacgmm'] += em_fallbacks
-        self.fallbacks['mvdr_targets'] = [a + b for a, b in
-                                          zip(self.fallbacks['mvdr_targets'], bf_targets)]
+        if self.targets is not None:
+            self.fallbacks['mvdr_targets'] = [a + b for a, b in
+                                              zip(self.fallbacks['mvdr_targets'], bf_targets)]
 
-    def _block_stages_targets(self, block, activity, debug):
-        """The block of S targets through the existing single-target stage operators: the front
-        once, then masks, beamformer and synthesis per target, each with its explicit state."""
+    def _block_stages(self, block, activity, debug):
+        """The block through the stage operators, each with its explicit state: the front once,
+        then masks, beamformer and postfilter per target through the single-target operators,
+        then the synthesis of the stream (`istft_stream`, or `istft_stream_targets` with the
+        tails of a stream with ``targets``)."""
         Y, act_frames = ops.stft_stream(block, activity, state=self.stream, window=self.window)
         if Y.shape[1] == 0:
             return self._no_samples(), None
@@ -360,39 +310,36 @@ class StreamingEnhancer:
                                      arrays=self.wpe_arrays, state=self.wpe_state)
         posterior, em_fallbacks = ops.cacgmm_posteriors_online(
             Obs, act_frames, forget=self.gss_forget, state=self.em_state, return_fallbacks=True)
-        frames_out, rows = self.stream.frames_out, []
-        for s, target in enumerate(self.targets):
+        rows = []
+        for target, state in zip(self._classes(), self.bf_states):
             target_mask, distortion_mask = ops.masks_from_posteriors(posterior, target, ctx=self.ctx)
             X_hat, fallbacks = ops.mvdr_souden_online_from_masks(
                 Obs, target_mask, distortion_mask, ban=True, forget=self.bf_forget,
-                ref_channel=self.ref_channel, state=self.bf_states[s], return_fallbacks=True)
+                ref_channel=self.ref_channel, state=state, return_fallbacks=True)
             if self.postfilter == 'mask_mul':
+                # (re * m, im * m as the library's postfilter, not a complex product)
                 X_hat = (X_hat.view(np.float64).reshape(X_hat.shape + (2,))
                          * target_mask[..., None]).reshape(X_hat.shape[0], -1).view(np.complex128)
-            # The synthesis of target s on a state of its own, kept only so that the existing
-            # `istft_stream` can be reused: its tail lives there, its counters follow the stream's.
-            # This writes through `StreamState.struct()`, which hands out the state's ONE
-            # persistent struct (a copy would leave the library reading the old counters).
-            tail = self.tail_streams[s]
-            tail.struct().received, tail.struct().frames_out = self.stream.received, frames_out
-            samples = ops.istft_stream(X_hat, state=tail, window=self.window)
-            rows.append((samples, target_mask, distortion_mask, X_hat, fallbacks))
-        # (no `istft_stream` ran on the stream's own state: its frame counter is advanced here,
-        # once, and the per-target tails are copied into ``tails``, the record a checkpoint keeps)
-        self.stream.struct().frames_out = frames_out + Y.shape[1]
-        self.ctx.upload(self.tails.bufs['tails'],
-                        np.stack([t.to_host()['ola_tail'] for t in self.tail_streams]))
-        self._count([r[4] for r in rows], em_fallbacks)
-        samples = np.stack([r[0] for r in rows])
-        details = None
-        if debug:
-            details = {'Obs': Obs, 'posterior': posterior,
-                       'target_mask': np.stack([r[1] for r in rows]),
-                       'distortion_mask': np.stack([r[2] for r in rows]),
-                       'X_hat': np.stack([r[3] for r in rows]),
+            rows.append((target_mask, distortion_mask, X_hat, fallbacks))
+        target_mask, distortion_mask, X_hat, bf_fallbacks = (list(column) for column in zip(*rows))
+        if self.targets is None:
+            samples = ops.istft_stream(X_hat[0], state=self.stream, window=self.window)
+            details = {'target_mask': target_mask[0], 'distortion_mask': distortion_mask[0],
+                       'X_hat': X_hat[0], 'ref_channel': self.ref_channel,
+                       'fallbacks': (bf_fallbacks[0], em_fallbacks)}
+        else:
+            X_hat = np.stack(X_hat)
+            samples = ops.istft_stream_targets(X_hat, state=self.stream, tails=self.tails,
+                                               window=self.window)
+            details = {'target_mask': np.stack(target_mask),
+                       'distortion_mask': np.stack(distortion_mask), 'X_hat': X_hat,
                        'ref_channel': np.full(len(rows), self.ref_channel),
-                       'fallbacks': (sum(r[4] for r in rows), em_fallbacks),
-                       'fallbacks_targets': [r[4] for r in rows]}
-            if act_frames is not None:
-                details['acitivity_freq'] = act_frames
+                       'fallbacks': (sum(bf_fallbacks), em_fallbacks),
+                       'fallbacks_targets': bf_fallbacks}
+        self._count(bf_fallbacks, em_fallbacks)
+        if not debug:
+            return samples, None
+        details.update(Obs=Obs, posterior=posterior)
+        if act_frames is not None:
+            details['acitivity_freq'] = act_frames
         return samples, details

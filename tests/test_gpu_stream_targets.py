@@ -183,6 +183,15 @@ def test_one_target_in_a_list_is_the_single_target_stream(gpu_ctx):
     row_is_the_single_stream(multi, 0, one, 'S = 1')
 
 
+@pytest.mark.parametrize('part', ['hops', 'borders'])
+def test_one_target_in_a_list_is_the_single_target_stream_whatever_the_cuts(gpu_ctx, part):
+    """In blocks of one hop and in uneven ones: samples, X_hat, masks and the beamformer sums of
+    a ``targets=(t,)`` stream are those of the ``target=t`` stream, its tails[0] that one's
+    ola_tail (both are the S = 1 form of one block path)."""
+    multi, one = run(gpu_ctx, 'a', part, targets=(1,)), run(gpu_ctx, 'a', part, target=1)
+    row_is_the_single_stream(multi, 0, one, f'S = 1, {part}')
+
+
 def test_the_rows_follow_the_order_of_the_targets(gpu_ctx):
     a, b = run(gpu_ctx, 'a', targets=(2, 0)), run(gpu_ctx, 'a', targets=(0, 2))
     for k in PER_TARGET + ('x_hat',):

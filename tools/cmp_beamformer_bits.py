@@ -8,10 +8,14 @@ a bit, or the one-wave solve of `bash tools/build_variant.sh mvdr_nt64 -DGSS_MVD
 library and once under OTHER_LIBRARY (GSS_HIP_LIBRARY), each in a process of its own; outputs and
 reference channels are compared byte for byte.  Cases: MVDR-Souden + BAN with 4 - 29 channels and
 with a dead channel (the minimum-norm path); the LCMV stage nulling, with one fallback frequency,
-with a dead channel, and falling back on a dead channel; segments; three targets; GEV.
+with a dead channel, and falling back on a dead channel; segments; three targets; GEV; the online
+MVDR for one and for several targets at 4, 12, 24 and 32 channels in two unequal blocks, with
+and without BAN and the postfilter, with the filters and the final sums; the stream synthesis for
+one and for several signals; a fused stream of one target and of several on two cells, cut
+unevenly, with every tap, the final states, the tails and the fallback counts.
 Exit status 1 when an array differs."""
 import os, sys, subprocess, tempfile
-sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
+sys.path.insert(0, '.'); sys.path.insert(0, 'tests'); sys.path.insert(0, 'oracle')
 import numpy as np
 
 
@@ -59,7 +63,83 @@ def cases():
         out[f'targets {bf}'] = ops.enhance_observation_targets(
             u.obs, u.activity_array, [2, 0, 1], [0, 512, 1024], 2048, wpe=True, wpe_taps=4,
             bss_iterations=5, bf=bf)
+    stream_cases(out)
     return out
+
+
+def stream_cases(out):
+    """The online MVDR and the two stream block paths: every form NR = 1..4 of both kernels."""
+    import online_mvdr_reference as mref
+    import stream_reference as sr
+    import stream_targets_reference as tr
+    from pb_chime5_amd import ops
+    from pb_chime5_amd.streaming import StreamingEnhancer
+    F, T, K, targets = 5, 40, 3, (2, 0)
+    for D in (4, 12, 24, 32):
+        rng = np.random.default_rng([D, F, T])
+        Y = mref.crandn(rng, D, T, F)
+        gamma = rng.random((K, T, F)) + 0.05
+        gamma /= gamma.sum(axis=0)
+        for ban in (False, True):
+            kw = dict(forget=0.97, ref_channel=D - 1, ban=ban, return_filters=True)
+            one = ops.OnlineMVDRState.fresh(F, D, 1e-2)
+            runs = {None: [ops.OnlineMVDRState.fresh(F, D, 1e-2) for _ in targets],
+                    'mask_mul': [ops.OnlineMVDRState.fresh(F, D, 1e-2) for _ in targets]}
+            for a, b in ((0, 13), (13, T)):
+                mx, mn = ops.masks_from_posteriors(gamma[:, a:b], targets[0])
+                X, W = ops.mvdr_souden_online_from_masks(Y[:, a:b], mx, mn, state=one, **kw)
+                out[f'online one {D} ban={ban} X{a}'], out[f'online one {D} ban={ban} W{a}'] = X, W
+                for postfilter, states in runs.items():
+                    X, W = ops.mvdr_souden_online_targets(Y[:, a:b], gamma[:, a:b], targets,
+                                                          states=states, postfilter=postfilter, **kw)
+                    name = f'online targets {D} ban={ban} {postfilter}'
+                    out[f'{name} X{a}'], out[f'{name} W{a}'] = X, W
+            for name, state in [('one', one)] + [(f'targets {p} {s}', st) for p, states in runs.items()
+                                                 for s, st in enumerate(states)]:
+                for k, v in state.to_host().items():
+                    out[f'online {name} {D} ban={ban} {k}'] = np.asarray(v)
+
+    W, H, S, T = 64, 16, 3, 24
+    X = tr.reference('a', tr.seed_of('a'))[1]['X_hat'][:S, :T]
+    X = X + 1j * np.arange(1, S + 1)[:, None, None] * X
+    state, tails = ops.StreamState.fresh(1, 0, W, H), ops.StreamTails.fresh(S, W, H)
+    single = ops.StreamState.fresh(1, 0, W, H)
+    for st in (state, single):
+        ops.stft_stream(np.zeros((1, T * H)), None, state=st)
+    for i, (a, b) in enumerate(sr.blocks_of(T, (1, 2, 0, 7, T - 10))):
+        out[f'istft targets {i}'] = ops.istft_stream_targets(X[:, a:b], state=state, tails=tails)
+        out[f'istft one {i}'] = ops.istft_stream(X[0, a:b], state=single)
+    out['istft tails'] = tails.to_host()['tails']
+    out['istft ola_tail'] = single.to_host()['ola_tail']
+
+    s = tr.SETTINGS
+    for cell in ('a', 'm'):
+        Wc, Hc, D, A, taps, delay, K, N, wpe = tr.CELLS[cell]
+        x, activity = tr.scene(cell, tr.seed_of(cell))
+        for postfilter in (None, 'mask_mul'):
+            for mode in (dict(target=1), dict(targets=tr.TARGETS[cell])):
+                enh = StreamingEnhancer(
+                    D, K, ref_channel=s['ref_channel'], stft_size=Wc, stft_shift=Hc, wpe=wpe,
+                    wpe_taps=taps, wpe_delay=delay, wpe_alpha=s['wpe_alpha'], wpe_arrays=A,
+                    gss_forget=s['gss_forget'], gss_prior_mass=s['gss_prior_mass'],
+                    bf_forget=s['bf_forget'], bf_loading=s['bf_loading'], postfilter=postfilter,
+                    **mode)
+                name = f'stream {cell} {postfilter} {sorted(mode)[0]}'
+                blocks = sr.blocks_of(N, tr.partitions(cell)['borders'])
+                for i, (a, b) in enumerate(list(blocks) + [(None, None)]):
+                    y, d = (enh.flush(debug=True) if a is None else
+                            enh.process(x[:, a:b], activity[:, a:b], debug=True))
+                    out[f'{name} samples {i}'] = y
+                    for k, v in (d or {}).items():
+                        out[f'{name} {k} {i}'] = np.asarray(v)
+                host = enh.to_host()
+                for stage in ('stream', 'wpe', 'em', 'bf'):
+                    for k, v in (host[stage] or {}).items():
+                        out[f'{name} {stage}.{k}'] = np.asarray(v)
+                if 'tails' in host:
+                    out[f'{name} tails'] = np.asarray(host['tails'])
+                for k, v in enh.fallbacks.items():
+                    out[f'{name} fallbacks {k}'] = np.asarray(v)
 
 
 if len(sys.argv) == 3 and sys.argv[1] == '--run':
