@@ -21,7 +21,7 @@ SOURCES = ['gss_api.hip', 'stft.hip', 'wpe.hip', 'cacgmm.hip', 'cacgmm_model.hip
            'cacgmm_align.hip', 'cacgmm_link.hip', 'mvdr.hip',
            'chsel.hip', 'posterior_activity.hip', 'wpd.hip', 'wpe_online.hip', 'mvdr_online.hip',
            'cacgmm_online.hip', 'stream.hip']
-HEADERS = ['gss_internal.h', 'cacgmm_perm.h', 'jacobi.h', 'dense_wave.h', '../../include/gss_hip.h']
+HEADERS = ['gss_internal.h', 'cacgmm_estep.h', 'cacgmm_perm.h', 'jacobi.h', 'dense_wave.h', '../../include/gss_hip.h']
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs.  Without it the compiler
 # puts loop-carried accumulators in VGPRs but the MFMA destination in AGPRs and copies
 # every accumulator there and back (plus a wait for the MFMA result) in each k step of

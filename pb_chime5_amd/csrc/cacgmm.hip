@@ -22,7 +22,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "gss_internal.h"
+#include "cacgmm_estep.h"
 #include "dense_wave.h"
 #include "jacobi.h"
 
@@ -30,9 +30,6 @@ namespace {
 
 #ifndef GSS_CHOL_PRIO
 #define GSS_CHOL_PRIO 1       // the same in em_chol (loads 3, sweep 2, product 0): -2 %
-#endif
-#ifndef GSS_ESTEP_PRIO
-#define GSS_ESTEP_PRIO 1      // wave priority falling with progress in the register-form E-step
 #endif
 constexpr int EM_TILE = 64;          // frames per tile (one per lane of a wave)
 constexpr int EM_TS = EM_TILE + 1;   // padded LDS row stride (complex elements)
@@ -202,33 +199,20 @@ __global__ __launch_bounds__(256) void em_estep_kernel(EmArgs a, const cplx *__r
         const int64_t t = t0 + tl;
         const bool valid = t < c1;
         if (MODE == MODE_FIRST) {
-            if (a.init != nullptr) {
-                // fit(initialization=array): the affiliations as given, not renormalised
-                const double *initf = a.init + (int64_t)f * a.init_fstride;
+            // (every wave forms all K values of the frame and keeps its own stripe: four times
+            // the loads of a striped read, in one launch per EM; `act` is always readable)
+            const int64_t tc = valid ? t : T - 1;
+            bool on[K];
+            double gk[K];
 #pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const int k = g + 4 * s;
-                    if (k < K && valid) {
-                        const double gk = initf[(int64_t)k * a.init_stride + t];
-                        sg[s] += gk;
-                        a.W[((int64_t)f * K + k) * T + t] = gk;      // quadratic form = 1
-                    }
-                }
-                continue;
-            }
-            // GSS initialisation (core.py:156-160): where(act == 0, 1e-10, act) / sum_k
-            double ssum = 0.0;
+            for (int k = 0; k < K; ++k) on[k] = actf[(int64_t)k * a.act_stride + tc] != 0;
+            first_affiliations<K>(a.init ? a.init + (int64_t)f * a.init_fstride + tc : nullptr,
+                                  a.init_stride, on, gk);
 #pragma unroll
-            for (int k = 0; k < K; ++k)
-                ssum += (valid && actf[(int64_t)k * a.act_stride + t]) ? 1.0 : 1e-10;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int k = g + 4 * s;
-                if (k < K && valid) {
-                    const double v = actf[(int64_t)k * a.act_stride + t] ? 1.0 : 1e-10;
-                    const double gk = v / ssum;
-                    sg[s] += gk;
-                    a.W[((int64_t)f * K + k) * T + t] = gk;          // quadratic form = 1
+            for (int k = 0; k < K; ++k) {           // (k static: gk stays in registers)
+                if ((k & 3) == g && valid) {
+                    sg[k / 4] += gk[k];
+                    a.W[((int64_t)f * K + k) * T + t] = gk[k];       // quadratic form = 1
                 }
             }
             continue;
@@ -239,7 +223,9 @@ __global__ __launch_bounds__(256) void em_estep_kernel(EmArgs a, const cplx *__r
 
         // ---- quadratic forms.  Wave g takes the row pairs (p, D-1-p), p = g, g+4, ...
         // (every pair holds D+1 entries: balanced); y_row stays in registers, the
-        // model row is read with wave-uniform (scalar) loads.
+        // model row is read with wave-uniform (scalar) loads.  (Its own walk, not
+        // quad_forms_lds: that one gives a lane the whole triangle, this one a quarter of it
+        // to each of four waves, whose partial sums meet in LDS.)
         double q[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) q[k] = 0.0;
@@ -382,6 +368,8 @@ __device__ __forceinline__ bool frequency_has_zero_frames(const int *__restrict_
     return __any(z != 0);
 }
 
+// The walk, the posterior (ratio form) and the epilogue are quad_forms_reg, posterior_ratio and
+// estep_finish of cacgmm_estep.h.
 template <int K, int D, int MODE>
 __global__ __launch_bounds__(256) void em_estep_reg_kernel(EmArgs a, const cplx *__restrict__ Mq,
                                                            const cplx *__restrict__ Yn) {
@@ -398,155 +386,31 @@ __global__ __launch_bounds__(256) void em_estep_reg_kernel(EmArgs a, const cplx 
     const int64_t t = ((int64_t)tile * wpb + wave) * 64 + lane;
     const bool valid = t < T;
     const int64_t tc = valid ? t : T - 1;
-    const cplx *Mf = Mq + (int64_t)f * NE * K;
     const cplx *yf = Yn + (int64_t)f * D * T + tc;
 
-#if GSS_ESTEP_PRIO
-    __builtin_amdgcn_s_setprio(3);
-#endif
+    estep_priority<3>();
     cplx y[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) y[d] = yf[(int64_t)d * T];
-
     double q[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) q[k] = 0.0;
-    // Walk the packed upper triangle with a ring of model rows: the row of entry e + P
-    // is requested (scalar loads, wave uniform) before entry e is evaluated, and a
-    // scheduling barrier per entry keeps the compiler from hoisting every row of the
-    // fully unrolled triangle to the top (which would spill thousands of SGPRs).
-    constexpr int P = 2, RING = P + 1;
-    cplx ring[RING][K];
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-#pragma unroll
-        for (int k = 0; k < K; ++k) ring[j][k] = Mf[j * K + k];
-    int e = 0;
-#pragma unroll
-    for (int d1 = 0; d1 < D; ++d1) {
-#pragma unroll
-        for (int d2 = d1; d2 < D; ++d2) {
-            if (e + P < NE) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) ring[(e + P) % RING][k] = Mf[(e + P) * K + k];
-            }
-            const double pr = y[d1].x * y[d2].x + y[d1].y * y[d2].y;
-            if (d1 == d2) {
-                // (the imaginary parts of a diagonal entry and of its product are zero: skipping
-                // them changes no bit of q)
-#pragma unroll
-                for (int k = 0; k < K; ++k) q[k] = fma(ring[e % RING][k].x, pr, q[k]);
-            } else {
-                const double pim = y[d1].y * y[d2].x - y[d1].x * y[d2].y;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const cplx m = ring[e % RING][k];
-                    q[k] = fma(m.x, pr, q[k]);
-                    q[k] = fma(m.y, pim, q[k]);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            ++e;
-#if GSS_ESTEP_PRIO
-            // priority falls with the wave's progress: the waves of a SIMD converge instead
-            // of finishing oldest first, and the end of the launch is not a row of single
-            // waves finishing alone
-            if (e == NE / 4) __builtin_amdgcn_s_setprio(2);
-            if (e == NE / 2) __builtin_amdgcn_s_setprio(1);
-            if (e == 3 * NE / 4) __builtin_amdgcn_s_setprio(0);
-#endif
-        }
-    }
-    // Posterior  pi_k exp(-D ln q_k - ln det_k) / sum  without a logarithm per frame: relative
-    // to the class with the smallest q it is  (q_min / q_k)^D c_k  with
-    // c_k = pi_k exp(ln det_min - ln det_k)  -- the common factor cancels in the normalisation.
-    // c_k is one exponential per class and WAVE (lane k computes it, an SGPR pair hands it to
-    // all lanes) instead of K logarithms and K exponentials per FRAME: the transcendental
-    // functions were 600 of the kernel's 5200 instructions per wave, and the integer power is
-    // the more accurate form (24 roundings against the 1e-13 of exp(500 +- ...)).  One
-    // reciprocal per class serves the ratio and the M-step weight gamma / q, one more the
-    // normalisation.  A frame whose terms all underflow (sum < 1e-280: the classes' ln det
-    // hundreds apart AND the q ratios against them) takes the log form below, which is also
-    // the form of em_estep_kernel.
-    // (The walk sits at the 128 registers of four waves per SIMD and at the SGPR limit, and
-    // nothing orders the epilogue's loads after it: activity bytes, ln det, pi -- or the lane
-    // masks made of them -- were moved above the walk and spilled its ring of model rows lane
-    // by lane (5 x slower).  So their addresses depend on the walk's result: `dep` is 0
-    // unless q is NaN.)
-    const int dep = q[0] != q[0] ? 1 : 0;
-    const int tcl = (int)tc - dep;
-    auto lane_bcast = [](double x, int k) {
-        const unsigned long long u = __double_as_longlong(x);
-        const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)u, k);
-        const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(u >> 32), k);
-        return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-    };
-    double cls, ldl, pil;
-    {
-        const int kk = (lane < K ? lane : K - 1) - (lane > 0 ? dep : 0);
-        ldl = a.logdet[f * K + kk];
-        pil = a.pi[f * K + kk];
-        double ldmin = INFINITY;
-#pragma unroll
-        for (int k = 0; k < K; ++k) ldmin = fmin(ldmin, lane_bcast(ldl, k));
-        cls = pil * exp(ldmin - ldl);
-    }
-    double qmin = INFINITY;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        q[k] = fmax(fabs(q[k]), GSS_TINY);
-        qmin = fmin(qmin, q[k]);
-    }
-    uint8_t act[K];
+    quad_forms_reg<K, D>(y, Mq + (int64_t)f * NE * K, q);
+
+    int64_t tcl = tc;
+    int kk = lane < K ? lane : K - 1;
+    hold_below_walk(q[0], tcl, kk);
+    const double ldl = a.logdet[f * K + kk];
+    const double pil = a.pi[f * K + kk];
+    bool on[K];
 #pragma unroll
     for (int k = 0; k < K; ++k)
-        act[k] = a.act[(int64_t)f * a.act_fstride + (int64_t)k * a.act_stride + (tcl < 0 ? 0 : tcl)];
-    double v[K], iq[K], ssum = 0.0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        iq[k] = 1.0 / q[k];
-        const double r = qmin * iq[k];
-        double p = 1.0, b = r;            // r^D by squaring (D is a template parameter)
-#pragma unroll
-        for (int bit = D; bit > 0; bit >>= 1) {
-            if (bit & 1) p = p * b;
-            b = b * b;
-        }
-        v[k] = p * lane_bcast(cls, k);
-        v[k] = (!a.masked || (valid && act[k])) ? v[k] : 0.0;
-        ssum += v[k];
-    }
-    if (ssum < 1e-280) {
-        double lp[K], mx = -INFINITY;
-        ssum = 0.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            lp[k] = -(double)D * log(q[k]) - lane_bcast(ldl, k);
-            mx = fmax(mx, lp[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            v[k] = exp(lp[k] - mx) * lane_bcast(pil, k);
-            v[k] = (!a.masked || (valid && act[k])) ? v[k] : 0.0;
-            ssum += v[k];
-        }
-    }
-    const double is = 1.0 / fmax(ssum, GSS_TINY);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double gam = v[k] * is;
-        if (a.aff_eps != 0.0) gam = fmin(fmax(gam, a.aff_eps), 1.0 - a.aff_eps);
-        if (MODE == MODE_PREDICT) {
-            if (valid) a.gamma[((int64_t)f * K + k) * T + t] = gam;
-        } else {
-            // gamma / max(q, 10 tiny)
-            if (valid)
-                a.W[((int64_t)f * K + k) * T + t] =
-                    gam * (q[k] < 10.0 * GSS_TINY ? 1.0 / (10.0 * GSS_TINY) : iq[k]);
-            const double tot = wave_sum(valid ? gam : 0.0);
-            if (lane == 0) a.Sg[(((int64_t)f * ntile + tile) * wpb + wave) * K + k] = tot;
-        }
-    }
+        // (always readable and always read: no branch)
+        on[k] = a.act[(int64_t)f * a.act_fstride + (int64_t)k * a.act_stride + tcl] != 0;
+    double v[K], iq[K];
+    const double is = posterior_ratio<K, D>(q, iq, v, ldl, pil, on, a.masked);
+    estep_finish<K, MODE == MODE_PREDICT, true, false>(
+            v, is, q, iq, a.aff_eps, valid, lane, T, (int64_t)f * K, t,
+            MODE == MODE_PREDICT ? a.gamma : a.W, nullptr,
+            a.Sg + (((int64_t)f * ntile + tile) * wpb + wave) * K);
 }
 
 // ------------------------------------------------------------------ M-step
@@ -1946,26 +1810,6 @@ int launch_estep_reg(gss_ctx *ctx, int mode, const EmArgs &a, const cplx *Mq, co
     return GSS_OK;
 }
 
-// Channel / class counts with a register-form E-step.
-// D = 4 x arrays (all microphones), 2 x arrays (outer microphones) or 4 (reference array)
-// for the 5 and 6 array sessions of the corpus.
-bool estep_reg_supported(int D, int K) {
-    return (D == 24 || D == 20 || D == 12 || D == 10 || D == 4) && K >= 2 && K <= 6;
-}
-
-template <int D>
-int launch_estep_reg_k(gss_ctx *ctx, int K, int mode, const EmArgs &a, const cplx *Mq,
-                       const cplx *Yn, int F) {
-    switch (K) {
-        case 2: return launch_estep_reg<2, D>(ctx, mode, a, Mq, Yn, F);
-        case 3: return launch_estep_reg<3, D>(ctx, mode, a, Mq, Yn, F);
-        case 4: return launch_estep_reg<4, D>(ctx, mode, a, Mq, Yn, F);
-        case 5: return launch_estep_reg<5, D>(ctx, mode, a, Mq, Yn, F);
-        case 6: return launch_estep_reg<6, D>(ctx, mode, a, Mq, Yn, F);
-    }
-    return gss_fail(ctx, GSS_ERR_UNSUPPORTED, "cacgmm: K=%d", K);
-}
-
 // The tiled M-step kernel for (KW classes, D channels): with the next tile prefetched for
 // D <= mstep_prefetch_d (12), and staging exactly ceil(D / 4) elements per thread where that is
 // one of the corpus' channel counts.
@@ -2042,21 +1886,6 @@ int launch_mstep(gss_ctx *ctx, const EmArgs &a, const cplx *Yn, int F, int K, in
         GSS_K_CASE(1, CALL) GSS_K_CASE(2, CALL) GSS_K_CASE(3, CALL) GSS_K_CASE(4, CALL)     \
         GSS_K_CASE(5, CALL) GSS_K_CASE(6, CALL) GSS_K_CASE(7, CALL) GSS_K_CASE(8, CALL)     \
     }
-// pb_bss: assert K < 20 (CACGMMTrainer.fit)
-#define GSS_K_SWITCH19(K, CALL)                                            \
-    switch (K) {                                                           \
-        GSS_K_CASE(1, CALL) GSS_K_CASE(2, CALL) GSS_K_CASE(3, CALL) GSS_K_CASE(4, CALL)     \
-        GSS_K_CASE(5, CALL) GSS_K_CASE(6, CALL) GSS_K_CASE(7, CALL) GSS_K_CASE(8, CALL)     \
-        GSS_K_CASE(9, CALL) GSS_K_CASE(10, CALL) GSS_K_CASE(11, CALL) GSS_K_CASE(12, CALL) \
-        GSS_K_CASE(13, CALL) GSS_K_CASE(14, CALL) GSS_K_CASE(15, CALL) GSS_K_CASE(16, CALL) \
-        GSS_K_CASE(17, CALL) GSS_K_CASE(18, CALL) GSS_K_CASE(19, CALL)                     \
-    }
-
-int launch_estep_k(gss_ctx *ctx, int K, int mode, const EmArgs &a, const cplx *Mq, int F) {
-    GSS_K_SWITCH19(K, launch_estep<KK>(ctx, mode, a, Mq, F));
-    return gss_fail(ctx, GSS_ERR_UNSUPPORTED, "cacgmm: K=%d", K);
-}
-
 int launch_mstep_group(gss_ctx *ctx, int KW, const EmArgs &a, const cplx *Yn, int F, int K,
                        int k0) {
     GSS_K_SWITCH8(KW, launch_mstep<KK>(ctx, a, Yn, F, K, k0));
@@ -2384,16 +2213,15 @@ int cacgmm_schedule_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, co
         }
         if (reg && mode != MODE_FIRST) {
             a.Sg = b.Sg_reg;
-            switch (D) {
-                case 24: return launch_estep_reg_k<24>(ctx, K, mode, a, b.Mq, b.Yn, b.F);
-                case 20: return launch_estep_reg_k<20>(ctx, K, mode, a, b.Mq, b.Yn, b.F);
-                case 12: return launch_estep_reg_k<12>(ctx, K, mode, a, b.Mq, b.Yn, b.F);
-                case 10: return launch_estep_reg_k<10>(ctx, K, mode, a, b.Mq, b.Yn, b.F);
-                default: return launch_estep_reg_k<4>(ctx, K, mode, a, b.Mq, b.Yn, b.F);
-            }
+            return dispatch_reg_shape(ctx, D, K, [&](auto d, auto k) {
+                return launch_estep_reg<decltype(k)::value, decltype(d)::value>(ctx, mode, a, b.Mq,
+                                                                                b.Yn, b.F);
+            });
         }
         a.Sg = b.Sg_lds;
-        return launch_estep_k(ctx, K, mode, a, b.Mq, b.F);
+        return dispatch_classes(ctx, K, [&](auto k) {
+            return launch_estep<decltype(k)::value>(ctx, mode, a, b.Mq, b.F);
+        });
     };
     auto eig = [&](EmBlock &b) -> int {
         EmArgs &a = b.a;

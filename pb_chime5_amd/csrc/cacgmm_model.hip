@@ -7,7 +7,7 @@
 // scalar load).  The public form is the dense Hermitian B_k^-1 (F, K, D, D) with both triangles.
 // Going from one to the other is a factor 2 on the off-diagonals -- exact in binary floating
 // point -- so export followed by import gives back the bits the EM left.
-#include "gss_internal.h"
+#include "cacgmm_estep.h"
 
 namespace {
 
@@ -70,15 +70,9 @@ __global__ __launch_bounds__(256) void model_export_kernel(const cplx *__restric
 
 // ------------------------------------------------------------------ log-likelihood
 // ln sum_k pi_k m_kt exp(-D ln q_kt - ln det B_k) per frame.  One lane per frame, one wave per
-// workgroup, no barrier and no exchange between lanes: a lane parks the D values of its frame
-// (from the unit-normalised (F, D, T) copy: coalesced loads) in its own 16-byte column of LDS
-// -- consecutive lanes on consecutive slots, conflict free as ds_read_b128 -- because the channel
-// index of the walk is a run-time value and registers cannot be indexed.  The walk over the
-// packed triangle is the E-step's: P_de = y_d conj(y_e), 4 real FMAs per (entry, class) against
-// the doubled off-diagonals, the K model values of an entry wave-uniform (scalar loads through
-// the __restrict__ pointer, so the model costs no LDS or vector-memory bandwidth), in the entry
-// order of em_estep_reg_kernel.  Every frame is written by exactly one lane: no atomics, the same
-// call gives the same bits.
+// workgroup; the frame comes from the unit-normalised (F, D, T) copy (coalesced loads) and goes
+// through quad_forms_lds (cacgmm_estep.h), the entry order of every E-step.  Every frame is
+// written by exactly one lane: no atomics, the same call gives the same bits.
 template <int K>
 __global__ __launch_bounds__(64) void cacgmm_loglik_kernel(
         const cplx *__restrict__ Yn, const cplx *__restrict__ Mq, const double *__restrict__ logdet,
@@ -97,30 +91,7 @@ __global__ __launch_bounds__(64) void cacgmm_loglik_kernel(
     for (int d = 0; d < D; ++d) ys[d * 64 + lane] = yf[(int64_t)d * T];
 
     double q[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) q[k] = 0.0;
-    const cplx *mrow = Mq + (int64_t)f * tri_count(D) * K;
-    for (int d1 = 0; d1 < D; ++d1) {
-        const cplx y1 = ys[d1 * 64 + lane];
-        {
-            const double pr = y1.x * y1.x + y1.y * y1.y;
-#pragma unroll
-            for (int k = 0; k < K; ++k) q[k] = fma(mrow[k].x, pr, q[k]);
-            mrow += K;
-        }
-        for (int d2 = d1 + 1; d2 < D; ++d2) {
-            const cplx y2 = ys[d2 * 64 + lane];
-            const double pr = y1.x * y2.x + y1.y * y2.y;
-            const double pim = y1.y * y2.x - y1.x * y2.y;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const cplx m = mrow[k];
-                q[k] = fma(m.x, pr, q[k]);
-                q[k] = fma(m.y, pim, q[k]);
-            }
-            mrow += K;
-        }
-    }
+    quad_forms_lds<K>(ys, lane, D, Mq + (int64_t)f * tri_count(D) * K, q);
     // max-shifted log-sum-exp, the shift over the classes that are on: a class the mask turns off
     // may exceed every active one by more than exp() can span (floored eigenvalues at D = 24)
     double lp[K], mx = -INFINITY;
@@ -178,16 +149,8 @@ int cacgmm_loglik_run(gss_ctx *ctx, const cplx *Yn, const cplx *Mq, const double
                       const double *pi, const uint8_t *act, int64_t act_stride,
                       int64_t act_fstride, int masked, int F, int64_t T, int D, int K,
                       double *loglik) {
-#define GSS_LL_CASE(N)                                                                          \
-    case N:                                                                                     \
-        return launch_loglik<N>(ctx, Yn, Mq, logdet, pi, act, act_stride, act_fstride, masked, F, T, \
-                                D, loglik);
-    switch (K) {
-        GSS_LL_CASE(1) GSS_LL_CASE(2) GSS_LL_CASE(3) GSS_LL_CASE(4) GSS_LL_CASE(5)
-        GSS_LL_CASE(6) GSS_LL_CASE(7) GSS_LL_CASE(8) GSS_LL_CASE(9) GSS_LL_CASE(10)
-        GSS_LL_CASE(11) GSS_LL_CASE(12) GSS_LL_CASE(13) GSS_LL_CASE(14) GSS_LL_CASE(15)
-        GSS_LL_CASE(16) GSS_LL_CASE(17) GSS_LL_CASE(18) GSS_LL_CASE(19)
-    }
-#undef GSS_LL_CASE
-    return gss_fail(ctx, GSS_ERR_UNSUPPORTED, "cacgmm: K=%d", K);
+    return dispatch_classes(ctx, K, [&](auto k) {
+        return launch_loglik<decltype(k)::value>(ctx, Yn, Mq, logdet, pi, act, act_stride,
+                                                 act_fstride, masked, F, T, D, loglik);
+    });
 }

@@ -9,7 +9,7 @@
 //   em_estep_prior_kernel   the E-step that multiplies by prior[k, t] and hands the M-step three
 //   (and its register form) things: W = gamma / max(q, 10 tiny), the gamma itself (the prior
 //                           update reads it) and the per-(f, tile, k) sums of gamma (em_chol's
-//                           denominator);
+//                           denominator), built from the pieces of cacgmm_estep.h;
 //   prior_partial_kernel /  prior[k, t] = (1 / F) sum_f gamma[f, k, t]: a column sum over an
 //   prior_finish_kernel     (F, K T) array, slices of frequencies summed side by side and then
 //                           added in order.
@@ -17,28 +17,22 @@
 // model update still writes is not read by anything here.
 #include <algorithm>
 
-#include "gss_internal.h"
+#include "cacgmm_estep.h"
 
 namespace {
 
 // ------------------------------------------------------------------ E-step with a per-frame prior
-// One lane per frame, one wave per workgroup, no barrier and no exchange between lanes before the
-// sums of gamma -- the form of cacgmm_loglik_kernel: a lane parks the D values of its frame (from
-// the unit-normalised (F, D, T) copy: coalesced loads) in its own 16-byte column of LDS, because
-// the channel index of the walk is a run-time value and registers cannot be indexed; consecutive
-// lanes sit on consecutive slots (conflict free as ds_read_b128).  The walk over the packed
-// triangle is the E-step's: P_de = y_d conj(y_e), 4 real FMAs per (entry, class) against the
-// doubled off-diagonals, the K model values of an entry wave-uniform (scalar loads through the
-// __restrict__ pointer).  The K prior values of a frame are prior[k * T + t]: coalesced over the
-// lanes.  The softmax is the log form of em_estep_kernel (max over ALL classes, as pb_bss takes
-// it before the mask is multiplied in), in registers.
+// One lane per frame, one wave per workgroup; the frame comes from the unit-normalised (F, D, T)
+// copy (coalesced loads) and goes through quad_forms_lds (cacgmm_estep.h).  The K prior values of
+// a frame are prior[k * T + t]: coalesced over the lanes.  The softmax is the log form of
+// em_estep_kernel (max over ALL classes, as pb_bss takes it before the mask is multiplied in), in
+// registers.
 //   EM_PRIOR_FIRST    the initialisation as the affiliation (q = 1): W = gamma = init[f, k, t],
 //                     or where(mask, 1, 1e-10) / sum_k when only a mask is given; no model read
 //   EM_PRIOR_FIT      W, gamma and the sums of gamma
 //   EM_PRIOR_PREDICT  the posteriors only
 // Sums of gamma: one record per (f, 64-frame tile), Sg[(f * ntile + tile) * K + k] -- the layout
-// em_chol_kernel / em_eigh_kernel read with sg_nch = ntile.  Every element is written by exactly
-// one lane: no atomics, the same call gives the same bits.
+// em_chol_kernel / em_eigh_kernel read with sg_nch = ntile.
 template <int K, int MODE>
 __global__ __launch_bounds__(64) void em_estep_prior_kernel(EmPriorArgs a,
                                                             const cplx *__restrict__ Yn,
@@ -58,66 +52,28 @@ __global__ __launch_bounds__(64) void em_estep_prior_kernel(EmPriorArgs a,
     const int64_t tc = valid ? t : T - 1;
     const uint8_t *actf = a.act + (int64_t)f * a.act_fstride + tc;
     double *Sgf = a.Sg + ((int64_t)f * ntile + tile) * K;
+    bool on[K];
+    double q[K], v[K];
 
     if (MODE == EM_PRIOR_FIRST) {
-        double g[K];
-        if (a.init != nullptr) {
-            // fit(initialization=array): the affiliations as given, not renormalised
-            const double *initf = a.init + (int64_t)f * a.init_fstride + tc;
-#pragma unroll
-            for (int k = 0; k < K; ++k) g[k] = initf[(int64_t)k * a.init_stride];
-        } else {
-            // GSS initialisation (core.py:156-160): where(act == 0, 1e-10, act) / sum_k
-            double ssum = 0.0;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                g[k] = actf[(int64_t)k * a.act_stride] ? 1.0 : 1e-10;
-                ssum += g[k];
-            }
-#pragma unroll
-            for (int k = 0; k < K; ++k) g[k] = g[k] / ssum;
-        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            if (valid) {
-                a.W[((int64_t)f * K + k) * T + t] = g[k];        // quadratic form = 1
-                a.G[((int64_t)f * K + k) * T + t] = g[k];
-            }
-            const double tot = wave_sum(valid ? g[k] : 0.0);
-            if (lane == 0) Sgf[k] = tot;
+            on[k] = actf[(int64_t)k * a.act_stride] != 0;
+            q[k] = 1.0;                              // the quadratic form of the first iteration
         }
+        // W = G = the affiliations as they are: estep_finish with norm = 1, q = 1 and no clip
+        // divides by 1.0 and by max(1, 10 tiny) = 1.0, both exact for every double
+        first_affiliations<K>(a.init ? a.init + (int64_t)f * a.init_fstride + tc : nullptr,
+                              a.init_stride, on, v);
+        estep_finish<K, false, false, true>(v, 1.0, q, q, 0.0, valid, lane, T, (int64_t)f * K, t,
+                                            a.W, a.G, Sgf);
         return;
     }
 
     const cplx *yf = Yn + (int64_t)f * D * T + tc;
     for (int d = 0; d < D; ++d) ys[d * 64 + lane] = yf[(int64_t)d * T];
-
-    double q[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) q[k] = 0.0;
-    const cplx *mrow = Mq + (int64_t)f * tri_count(D) * K;
-    for (int d1 = 0; d1 < D; ++d1) {
-        const cplx y1 = ys[d1 * 64 + lane];
-        {
-            const double pr = y1.x * y1.x + y1.y * y1.y;
-#pragma unroll
-            for (int k = 0; k < K; ++k) q[k] = fma(mrow[k].x, pr, q[k]);
-            mrow += K;
-        }
-        for (int d2 = d1 + 1; d2 < D; ++d2) {
-            const cplx y2 = ys[d2 * 64 + lane];
-            const double pr = y1.x * y2.x + y1.y * y2.y;
-            const double pim = y1.y * y2.x - y1.x * y2.y;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const cplx m = mrow[k];
-                q[k] = fma(m.x, pr, q[k]);
-                q[k] = fma(m.y, pim, q[k]);
-            }
-            mrow += K;
-        }
-    }
-    double v[K], mx = -INFINITY;
+    quad_forms_lds<K>(ys, lane, D, Mq + (int64_t)f * tri_count(D) * K, q);
+    double mx = -INFINITY;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         q[k] = fmax(fabs(q[k]), GSS_TINY);
@@ -131,36 +87,20 @@ __global__ __launch_bounds__(64) void em_estep_prior_kernel(EmPriorArgs a,
         if (a.masked) v[k] *= actf[(int64_t)k * a.act_stride] ? 1.0 : 0.0;
         ssum += v[k];
     }
-    ssum = fmax(ssum, GSS_TINY);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double gam = v[k] / ssum;
-        if (a.aff_eps != 0.0) gam = fmin(fmax(gam, a.aff_eps), 1.0 - a.aff_eps);
-        if (MODE == EM_PRIOR_PREDICT) {
-            if (valid) a.gamma[((int64_t)f * K + k) * T + t] = gam;
-        } else {
-            if (valid) {
-                a.W[((int64_t)f * K + k) * T + t] = gam / fmax(q[k], 10.0 * GSS_TINY);
-                a.G[((int64_t)f * K + k) * T + t] = gam;
-            }
-            const double tot = wave_sum(valid ? gam : 0.0);
-            if (lane == 0) Sgf[k] = tot;
-        }
-    }
+    estep_finish<K, MODE == EM_PRIOR_PREDICT, false, true>(
+            v, fmax(ssum, GSS_TINY), q, q, a.aff_eps, valid, lane, T, (int64_t)f * K, t,
+            MODE == EM_PRIOR_PREDICT ? a.gamma : a.W, a.G, Sgf);
 }
 
 // ------------------------------------------------------------------ the same, register form
-// For the channel counts of the corpus (D = 24, 20, 12, 10, 4) and 2 <= K <= 6 -- the shapes for
-// which the per-frequency EM has em_estep_reg_kernel -- the frame's D values stay in registers
-// and the packed triangle is walked fully unrolled: the walk of em_estep_reg_kernel (a ring of
-// model rows requested two entries ahead as scalar loads, a scheduling barrier per entry, wave
-// priority falling with progress), one wave per workgroup.  The LDS form above holds D KB per
+// For the shapes of estep_reg_supported the frame's D values stay in registers and the walk is
+// quad_forms_reg (cacgmm_estep.h), one wave per workgroup.  The LDS form above holds D KB per
 // wave, six waves on a CU at D = 24, and exposes every scalar load (cacgmm_loglik_kernel, the
-// same shape, takes 4.4 E-step launches for an E-step's arithmetic).  The softmax is the
-// ratio form of that kernel,  (q_min / q_k)^D exp(ln det_min - ln det_k) prior[k, t]  -- the
-// common factor cancels in the normalisation --, with the log form where every term underflows.
-// The epilogue's loads are ordered after the walk (see `tcl` below) so that the compiler cannot
-// move them above it, where they would spill its ring, and the epilogue is one basic block.
+// same shape, takes 4.4 E-step launches for an E-step's arithmetic).  The softmax is the ratio
+// form of posterior_ratio,  (q_min / q_k)^D exp(ln det_min - ln det_k) prior[k, t],  with the
+// log form where every term underflows, and the epilogue that of estep_finish -- both in this
+// kernel's own text: through the shared functions the D = 4 instantiations were 3 % slower
+// (DESIGN.md, section 28).
 template <int K, int D, int MODE>
 __global__ __launch_bounds__(64) void em_estep_prior_reg_kernel(EmPriorArgs a,
                                                                  const cplx *__restrict__ Yn,
@@ -176,63 +116,18 @@ __global__ __launch_bounds__(64) void em_estep_prior_reg_kernel(EmPriorArgs a,
     const int64_t t = (int64_t)tile * 64 + lane;
     const bool valid = t < T;
     const int64_t tc = valid ? t : T - 1;
-    const cplx *Mf = Mq + (int64_t)f * NE * K;
     const cplx *yf = Yn + (int64_t)f * D * T + tc;
 
-    __builtin_amdgcn_s_setprio(3);
+    estep_priority<3>();
     cplx y[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) y[d] = yf[(int64_t)d * T];
-
     double q[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) q[k] = 0.0;
-    constexpr int P = 2, RING = P + 1;
-    cplx ring[RING][K];
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-#pragma unroll
-        for (int k = 0; k < K; ++k) ring[j][k] = Mf[j * K + k];
-    int e = 0;
-#pragma unroll
-    for (int d1 = 0; d1 < D; ++d1) {
-#pragma unroll
-        for (int d2 = d1; d2 < D; ++d2) {
-            if (e + P < NE) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) ring[(e + P) % RING][k] = Mf[(e + P) * K + k];
-            }
-            const double pr = y[d1].x * y[d2].x + y[d1].y * y[d2].y;
-            if (d1 == d2) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) q[k] = fma(ring[e % RING][k].x, pr, q[k]);
-            } else {
-                const double pim = y[d1].y * y[d2].x - y[d1].x * y[d2].y;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const cplx m = ring[e % RING][k];
-                    q[k] = fma(m.x, pr, q[k]);
-                    q[k] = fma(m.y, pim, q[k]);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            ++e;
-            if (e == NE / 4) __builtin_amdgcn_s_setprio(2);
-            if (e == NE / 2) __builtin_amdgcn_s_setprio(1);
-            if (e == 3 * NE / 4) __builtin_amdgcn_s_setprio(0);
-        }
-    }
-    // (the indices of the epilogue's loads pass through an empty statement that also names the
-    // walk's result: their values are untouched, and nothing that uses them can move above it)
+    quad_forms_reg<K, D>(y, Mq + (int64_t)f * NE * K, q);
+
     int64_t tcl = tc;
     int kk = lane < K ? lane : K - 1;
-    asm volatile("" : "+v"(tcl), "+v"(kk) : "v"(q[0]));
-    auto lane_bcast = [](double x, int k) {
-        const unsigned long long u = __double_as_longlong(x);
-        const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)u, k);
-        const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(u >> 32), k);
-        return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-    };
+    hold_below_walk(q[0], tcl, kk);
     // lane k: ln det_k and exp(ln det_min - ln det_k), handed to all lanes through SGPR pairs
     double els, ldl;
     {
@@ -253,8 +148,7 @@ __global__ __launch_bounds__(64) void em_estep_prior_reg_kernel(EmPriorArgs a,
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         pk[k] = prior[(int64_t)k * T + tcl];
-        // (always readable and always read: a branch here splits the epilogue into blocks and the
-        // walk's scalar loads are then all hoisted to the top -- thousands of SGPR spills)
+        // (always readable and always read: no branch)
         on[k] = a.act[(int64_t)f * a.act_fstride + (int64_t)k * a.act_stride + tcl] != 0;
     }
     double v[K], iq[K], ssum = 0.0;
@@ -320,18 +214,6 @@ int launch_estep_prior_reg(gss_ctx *ctx, const EmPriorArgs &a, int mode) {
     }
     GSS_LAUNCH_CHECK(ctx, "em_estep_prior_reg_kernel");
     return GSS_OK;
-}
-
-template <int D>
-int launch_estep_prior_reg_k(gss_ctx *ctx, const EmPriorArgs &a, int K, int mode) {
-    switch (K) {
-        case 2: return launch_estep_prior_reg<2, D>(ctx, a, mode);
-        case 3: return launch_estep_prior_reg<3, D>(ctx, a, mode);
-        case 4: return launch_estep_prior_reg<4, D>(ctx, a, mode);
-        case 5: return launch_estep_prior_reg<5, D>(ctx, a, mode);
-        case 6: return launch_estep_prior_reg<6, D>(ctx, a, mode);
-    }
-    return gss_fail(ctx, GSS_ERR_UNSUPPORTED, "cacgmm: K=%d", K);
 }
 
 template <int K>
@@ -412,28 +294,15 @@ size_t cacgmm_prior_workspace_bytes(int F, int64_t T, int K) {
 
 int cacgmm_prior_estep_run(gss_ctx *ctx, const EmPriorArgs &a, int K, int mode) {
     // (GSS_VARIANT=estep_lds: the LDS form at every shape, as for the per-frequency E-step)
-    if (mode != EM_PRIOR_FIRST && K >= 2 && K <= 6 && !gss_variant_set("estep_lds")) {
-        switch (a.D) {
-            case 24: return launch_estep_prior_reg_k<24>(ctx, a, K, mode);
-            case 20: return launch_estep_prior_reg_k<20>(ctx, a, K, mode);
-            case 12: return launch_estep_prior_reg_k<12>(ctx, a, K, mode);
-            case 10: return launch_estep_prior_reg_k<10>(ctx, a, K, mode);
-            case 4: return launch_estep_prior_reg_k<4>(ctx, a, K, mode);
-        }
-    }
+    if (mode != EM_PRIOR_FIRST && estep_reg_supported(a.D, K) && !gss_variant_set("estep_lds"))
+        return dispatch_reg_shape(ctx, a.D, K, [&](auto d, auto k) {
+            return launch_estep_prior_reg<decltype(k)::value, decltype(d)::value>(ctx, a, mode);
+        });
     GSS_REQUIRE(ctx, sizeof(cplx) * 64 * (size_t)a.D <= 64 * 1024, GSS_ERR_UNSUPPORTED,
                 "cacgmm (shared prior): D=%d", a.D);
-#define GSS_PRIOR_CASE(N) \
-    case N: return launch_estep_prior<N>(ctx, a, mode);
-    switch (K) {
-        GSS_PRIOR_CASE(1) GSS_PRIOR_CASE(2) GSS_PRIOR_CASE(3) GSS_PRIOR_CASE(4) GSS_PRIOR_CASE(5)
-        GSS_PRIOR_CASE(6) GSS_PRIOR_CASE(7) GSS_PRIOR_CASE(8) GSS_PRIOR_CASE(9) GSS_PRIOR_CASE(10)
-        GSS_PRIOR_CASE(11) GSS_PRIOR_CASE(12) GSS_PRIOR_CASE(13) GSS_PRIOR_CASE(14)
-        GSS_PRIOR_CASE(15) GSS_PRIOR_CASE(16) GSS_PRIOR_CASE(17) GSS_PRIOR_CASE(18)
-        GSS_PRIOR_CASE(19)
-    }
-#undef GSS_PRIOR_CASE
-    return gss_fail(ctx, GSS_ERR_UNSUPPORTED, "cacgmm: K=%d", K);
+    return dispatch_classes(ctx, K, [&](auto k) {
+        return launch_estep_prior<decltype(k)::value>(ctx, a, mode);
+    });
 }
 
 int cacgmm_prior_update_run(gss_ctx *ctx, const EmPriorWork &w, int nf, int K, int64_t T) {

@@ -98,6 +98,13 @@ __device__ __forceinline__ double dpp_shifted(double v) {
     const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, ROW_MASK, BANK_MASK, true);
     return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
+// lane k's value (k wave uniform), handed to all lanes through an SGPR pair
+__device__ __forceinline__ double lane_bcast(double x, int k) {
+    const unsigned long long u = __double_as_longlong(x);
+    const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)u, k);
+    const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(u >> 32), k);
+    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
 __device__ __forceinline__ double wave_sum(double v) {
     double s = v + dpp_shifted<0x111, 0xf, 0xf>(v);      // row_shr:1
     s += dpp_shifted<0x112, 0xf, 0xf>(v);                // row_shr:2
@@ -106,10 +113,7 @@ __device__ __forceinline__ double wave_sum(double v) {
     s += dpp_shifted<0x118, 0xf, 0xc>(s);                // row_shr:8, banks 2-3
     s += dpp_shifted<0x142, 0xa, 0xf>(s);                // row_bcast:15 into rows 1, 3
     s += dpp_shifted<0x143, 0xc, 0xf>(s);                // row_bcast:31 into rows 2, 3
-    const unsigned long long u = __double_as_longlong(s);
-    const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)u, 63);
-    const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(u >> 32), 63);
-    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+    return lane_bcast(s, 63);
 }
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll

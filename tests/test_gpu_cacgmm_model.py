@@ -475,3 +475,53 @@ def test_gss_block_keeps_the_learned_model(gpu_ctx, D, T, F, K, iters, post, wei
         assert np.max(np.abs(again - got)) < 1e-7
     else:
         assert np.array_equal(again, got)
+
+
+# ------------------------------------------------------------------ 11. the log-form fall-back
+@pytest.mark.parametrize('D', [24, 4])
+def test_predict_takes_the_log_form_where_the_ratio_form_underflows(gpu_ctx, D):
+    """The register-form E-step takes the posterior as (q_min / q_k)^D pi_k exp(ln det_min -
+    ln det_k) and falls back to the log form where the sum of those terms is below 1e-280
+    (posterior_ratio, csrc/cacgmm_estep.h).  A hand-made model -- the entry checks pointers only,
+    precision and ln det need not be consistent -- whose classes are 330 decades apart both ways:
+    precision_1 ~ I against precision_2 ~ 10^(330 / D) I and ln det_2 = -330 ln 10 + ln 3, so that
+    in the ratio form BOTH terms of every frame underflow to zero (0 / tiny = 0 for both classes)
+    while the log form gives posteriors near (3 pi_1, pi_2) / (3 pi_1 + pi_2), moved per frame
+    by the diagonals.  Frequency 1 carries an ordinary, consistent model instead, so one launch
+    runs both branches.  Reference: the log form in NumPy; bar: 1e-7, what this module holds
+    cacgmm_predict to (the rounding of ln q and of the 760-nat terms is below 1e-12)."""
+    from pb_chime5_amd import ops
+    from pb_chime5_amd.cacgmm import CACGMM
+    K, F, T = 2, 3, 70
+    rng = np.random.default_rng(D)
+    Y = rng.standard_normal((D, T, F)) + 1j * rng.standard_normal((D, T, F))
+    scale = 10.0 ** (330.0 / D)
+    precision = np.zeros((F, K, D, D), complex)
+    log_det = np.zeros((F, K))
+    for f in (0, 2):
+        precision[f, 0] = np.diag(rng.uniform(0.9, 1.1, D))
+        precision[f, 1] = scale * np.diag(rng.uniform(0.9, 1.1, D))
+        log_det[f] = 0.0, -330.0 * np.log(10.0) + np.log(3.0)
+    for k in range(K):
+        A = rng.standard_normal((D, D)) + 1j * rng.standard_normal((D, D))
+        precision[1, k] = A @ A.conj().T + np.eye(D)
+        log_det[1, k] = -np.linalg.slogdet(precision[1, k])[1]
+    weight = np.tile([0.4, 0.6], (F, 1))
+
+    yn = Y / np.linalg.norm(Y, axis=0, keepdims=True)
+    q = np.abs(np.einsum('dtf,fkde,etf->fkt', yn.conj(), precision, yn))           # (F,K,T)
+    with np.errstate(under='ignore'):
+        ratio = ((q.min(axis=1, keepdims=True) / q) ** D
+                 * (weight * np.exp(log_det.min(axis=1, keepdims=True) - log_det))[:, :, None])
+    assert np.all(ratio[[0, 2]].sum(axis=1) < 1e-280)       # every frame there takes the branch
+    assert np.all(ratio[1].sum(axis=0) >= 1e-280)           # and no frame here
+    lp = -D * np.log(q) - log_det[:, :, None]
+    want = weight[:, :, None] * np.exp(lp - lp.max(axis=1, keepdims=True))
+    want = (want / want.sum(axis=1, keepdims=True)).transpose(1, 2, 0)              # (K,T,F)
+    assert 0.05 < want[:, :, [0, 2]].min() and want[:, :, [0, 2]].max() < 0.95
+
+    got = ops.cacgmm_predict(CACGMM(precision, log_det, weight), Y, ctx=gpu_ctx)
+    err = np.max(np.abs(got - want), axis=(0, 1))
+    print(f'D={D}: predict vs the NumPy log form, per frequency {err}')
+    assert got.shape == (K, T, F)
+    assert np.max(err) < 1e-7

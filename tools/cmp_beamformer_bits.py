@@ -5,8 +5,8 @@
 OTHER_LIBRARY is another build of the library: the parent commit's, when a change must not move
 a bit, or the one-wave solve of `bash tools/build_variant.sh mvdr_nt64 -DGSS_MVDR_NT=64`
 (pb_chime5_amd/lib/variants/libgss_mvdr_nt64.so).  Every case runs once under the package's own
-library and once under OTHER_LIBRARY (GSS_HIP_LIBRARY), each in a process of its own; outputs and
-reference channels are compared byte for byte.  Cases: MVDR-Souden + BAN with 4 - 29 channels and
+library and once under OTHER_LIBRARY (GSS_HIP_LIBRARY), each in a process of its own (cmp_bits.py);
+outputs and reference channels are compared byte for byte.  Cases: MVDR-Souden + BAN with 4 - 29 channels and
 with a dead channel (the minimum-norm path); the LCMV stage nulling, with one fallback frequency,
 with a dead channel, and falling back on a dead channel; segments; three targets; GEV; the online
 MVDR for one and for several targets at 4, 12, 24 and 32 channels in two unequal blocks, with
@@ -14,9 +14,10 @@ and without BAN and the postfilter, with the filters and the final sums; the str
 one and for several signals; a fused stream of one target and of several on two cells, cut
 unevenly, with every tap, the final states, the tails and the fallback counts.
 Exit status 1 when an array differs."""
-import os, sys, subprocess, tempfile
+import sys
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests'); sys.path.insert(0, 'oracle')
 import numpy as np
+from cmp_bits import main
 
 
 def cases():
@@ -142,22 +143,4 @@ def stream_cases(out):
                     out[f'{name} fallbacks {k}'] = np.asarray(v)
 
 
-if len(sys.argv) == 3 and sys.argv[1] == '--run':
-    np.savez(sys.argv[2], **cases())
-elif len(sys.argv) == 2:
-    me = os.path.abspath(__file__)
-    with tempfile.TemporaryDirectory() as tmp:
-        a, b = os.path.join(tmp, 'a.npz'), os.path.join(tmp, 'b.npz')
-        subprocess.run([sys.executable, me, '--run', a], check=True)
-        subprocess.run([sys.executable, me, '--run', b], check=True,
-                       env=dict(os.environ, GSS_HIP_LIBRARY=os.path.abspath(sys.argv[1])))
-        A, B = np.load(a), np.load(b)
-        different = 0
-        for k in A.files:
-            same = A[k].tobytes() == B[k].tobytes()
-            different += not same
-            print(k, 'bit-identical' if same else 'DIFFERENT max %.3e' % np.nanmax(np.abs(A[k] - B[k])), 'nan' if np.isnan(A[k]).any() else '')
-        print(f'{len(A.files)} arrays, {different} different')
-        sys.exit(1 if different else 0)
-else:
-    sys.exit(__doc__)
+main(__file__, __doc__, cases)
