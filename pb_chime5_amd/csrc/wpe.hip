@@ -172,34 +172,49 @@ struct CorrTile {
 //   re(a conj b) = t1 + t2,   im(a conj b) = t3 - t1 + t2
 // -- three real MFMAs per tile and k-step instead of four.
 // KSTEPS: k-steps of the chunk that are run (frames 0 .. 4 KSTEPS - 1 of the window).
+// Remainder groups (TS = 2, P tiles of 17 - 28 channels; MASK bits 4 - 5 = RG = 1 .. 3): the
+// second column sub-tile holds D - 16 <= 12 columns of P and runs as RG groups of 4 columns on
+// v_mfma_f64_4x4x4_4b_f64, whose four blocks are the four 4-row groups of the row sub-tile --
+// the A fragment (and the k lane of the weights) is the large form's, see wpe_apply_kernel; B
+// is one LDS read per group.  The sum of group g lives in element g of the sub-tile's
+// accumulators: row 4 ((lane >> 2) & 3) + (lane >> 4), column 16 + 4 g + (lane & 3).
+constexpr int corr_rg(int TS, int MASK) { return TS == 2 ? (MASK >> 4) & 3 : 0; }
+
 template <int TS, int MASK, int KSTEPS = CORR_KT / 4>
 __device__ __forceinline__ void corr_chunk(const cplx *S, const double *wS, int D,
                                            const CorrTile &tl, v4d (&t1)[TS][TS],
                                            v4d (&t2)[TS][TS], v4d (&t3)[TS][TS]) {
     const int lane = threadIdx.x & 63;
     const int li = lane & 15, lk = lane >> 4;
+    constexpr int RG = corr_rg(TS, MASK), NG = RG > 0 ? RG : 1;
     auto need = [](int a, int b) { return ((MASK >> (a * TS + b)) & 1) != 0; };
     auto need_row = [&](int a) {
         bool r = false;
         for (int b = 0; b < TS; ++b) r = r || need(a, b);
         return r;
     };
-    auto need_col = [&](int b) {
+    auto need_col = [&](int b) {        // (as a 16-column B fragment)
         bool r = false;
         for (int a = 0; a < TS; ++a) r = r || need(a, b);
-        return r;
+        return r && !(RG > 0 && b == 1);
     };
     const int ksteps = KSTEPS;
     // operands of k-step ks+1 are fetched from LDS while the MFMAs of ks run
     cplx a_cur[TS], b_cur[TS], a_nxt[TS], b_nxt[TS];
+    cplx g_cur[NG], g_nxt[NG];
     double w_cur, w_nxt = 0.0;
+    const int goff = tl.col_off + 16 + (lane & 3);
     {
         const cplx *base = S + lk * D + li;
         w_cur = wS[lk];
 #pragma unroll
         for (int m = 0; m < TS; ++m) {
             a_cur[m] = base[tl.row_off + 16 * m];
-            b_cur[m] = base[tl.col_off + 16 * m];
+            b_cur[m] = need_col(m) || RG == 0 ? base[tl.col_off + 16 * m] : c_make(0.0, 0.0);
+        }
+        if constexpr (RG > 0) {
+#pragma unroll
+            for (int g = 0; g < RG; ++g) g_cur[g] = S[lk * D + goff + 4 * g];
         }
     }
     // (one-sub-tile waves are not unrolled all the way: hoisting 16 k-steps of operand
@@ -215,6 +230,10 @@ __device__ __forceinline__ void corr_chunk(const cplx *S, const double *wS, int 
             for (int m = 0; m < TS; ++m) {
                 a_nxt[m] = need_row(m) ? base[tl.row_off + 16 * m] : c_make(0.0, 0.0);
                 b_nxt[m] = need_col(m) ? base[tl.col_off + 16 * m] : c_make(0.0, 0.0);
+            }
+            if constexpr (RG > 0) {
+#pragma unroll
+                for (int g = 0; g < RG; ++g) g_nxt[g] = S[kf * D + goff + 4 * g];
             }
         }
         double ar[TS], ai[TS], as[TS], br[TS], bi[TS], bd[TS];
@@ -232,6 +251,18 @@ __device__ __forceinline__ void corr_chunk(const cplx *S, const double *wS, int 
 #pragma unroll
             for (int b = 0; b < TS; ++b) {
                 if (!need(a, b)) continue;
+                if constexpr (RG > 0) {
+                    if (b == 1) {
+#pragma unroll
+                        for (int g = 0; g < RG; ++g) {
+                            const double gr = g_cur[g].x, gi = g_cur[g].y;
+                            t1[a][1][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(ar[a], gr, t1[a][1][g], 0, 0, 0);
+                            t2[a][1][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(ai[a], gi, t2[a][1][g], 0, 0, 0);
+                            t3[a][1][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(as[a], gr - gi, t3[a][1][g], 0, 0, 0);
+                        }
+                        continue;
+                    }
+                }
                 t1[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[a], br[b], t1[a][b], 0, 0, 0);
                 t2[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[a], bi[b], t2[a][b], 0, 0, 0);
                 t3[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[a], bd[b], t3[a][b], 0, 0, 0);
@@ -240,6 +271,10 @@ __device__ __forceinline__ void corr_chunk(const cplx *S, const double *wS, int 
         for (int m = 0; m < TS; ++m) {
             a_cur[m] = a_nxt[m];
             b_cur[m] = b_nxt[m];
+        }
+        if constexpr (RG > 0) {
+#pragma unroll
+            for (int g = 0; g < RG; ++g) g_cur[g] = g_nxt[g];
         }
         w_cur = w_nxt;
     }
@@ -265,8 +300,11 @@ __device__ __forceinline__ void corr_store(const CorrTile &tl, int f, int n, int
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 if (!need(a, b)) continue;
-                const int r = tl.row_off + 16 * a + lk + 4 * reg;
-                const int cc = tl.col_off + 16 * b + li;
+                constexpr int RG = corr_rg(TS, MASK);
+                const bool small = RG > 0 && b == 1;      // element reg = remainder group reg
+                if (small && reg >= RG) continue;
+                const int r = tl.row_off + 16 * a + (small ? 4 * ((lane >> 2) & 3) + lk : lk + 4 * reg);
+                const int cc = tl.col_off + 16 * b + (small ? 4 * reg + (lane & 3) : li);
                 const cplx v = RAW ? c_make(t1[a][b][reg], t3[a][b][reg])
                                    : c_make(t1[a][b][reg] + t2[a][b][reg],
                                             (t3[a][b][reg] - t1[a][b][reg]) + t2[a][b][reg]);
@@ -379,7 +417,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && STG1 < 8) ? 4 : 1) void wpe_co
 #define CORR_CASE(M) \
     case M: corr_tile_body<TS, M, NW, STG1>(Yf, wf, T, D, n, c, frames_lds, S, wS, tl, active, f, R, P); break
     if (TS == 2) {
-        switch (mask) {
+        switch (mask & 15) {       // (remainder groups, bits 4 - 5: the persistent kernel only)
             CORR_CASE(1);
             CORR_CASE(3);
             CORR_CASE(5);
@@ -754,17 +792,31 @@ __global__ __launch_bounds__(64 * NW) void wpe_corr_persist_kernel(
         corr_item_dma<M, NW, BLOCKED>(T, D, n, c, win, S0, w0, tl, active, f, next < 0 ? -1 : next >> 12, \
                                  b, issue, ring_slot, fetched, R, P);                             \
         break
-        switch (mask) {
+        // whole P tiles of 17 - 28 channels: 1 - 3 remainder groups in the second column sub-tile
+        // (the chunk-wise sums keep the full tile: their two extra accumulators per sub-tile
+        // leave no registers for it at two workgroups per CU)
+#define CORR_CASE_RG(RG)                                                                          \
+    case 15 + 16 * RG:                                                                            \
+        if constexpr (!BLOCKED)                                                                   \
+            corr_item_dma<15 + 16 * RG, NW, false>(T, D, n, c, win, S0, w0, tl, active, f,        \
+                                                   next < 0 ? -1 : next >> 12, b, issue,          \
+                                                   ring_slot, fetched, R, P);                     \
+        break
+        switch (BLOCKED ? mask & 15 : mask) {
             CORR_CASE(1);
             CORR_CASE(3);
             CORR_CASE(5);
             CORR_CASE(11);
+            CORR_CASE_RG(1);
+            CORR_CASE_RG(2);
+            CORR_CASE_RG(3);
             default:
                 corr_item_dma<15, NW, BLOCKED>(T, D, n, c, win, S0, w0, tl, active, f,
                                           next < 0 ? -1 : next >> 12, b, issue, ring_slot, fetched,
                                           R, P);
         }
 #undef CORR_CASE
+#undef CORR_CASE_RG
         item = next;
 #ifdef GSS_CORR_TRACE
         if (threadIdx.x == 0 && blockIdx.x < 8192) {
@@ -1378,11 +1430,19 @@ __global__ __launch_bounds__(256, 3) void chol_backsolve_kernel(const cplx *__re
 // advances by 4), and every wrap is three VALU instructions that the MFMA pipe waits for.
 // TAIL: rows r >= n have to be masked -- n is not a multiple of 8 (the loop runs two k-steps per
 // trip, so an odd k-step count executes one k-step past the end).
-template <int TA, int NB, int NWV = 4, int WRAPS = 4, bool TAIL = true>
-__global__ __launch_bounds__(64 * NWV) void wpe_apply_kernel(const cplx *__restrict__ Y,
-                                                        const cplx *__restrict__ G, int F,
-                                                        int64_t T, int D, int n, int c,
-                                                        cplx *__restrict__ X) {
+// RG (remainder groups, NB = 2 only): the second channel tile holds r = D - 16 <= 12 channels,
+// and a 16x16x4 MFMA on it is mostly empty.  With RG = ceil(r / 4) > 0 that tile runs as RG
+// column groups of 4 channels on v_mfma_f64_4x4x4_4b_f64 -- four independent 4 x 4 x 4 blocks
+// in a quarter of the issue time (16 cycles against 65, tools/micro/mfma_f64_bench.hip).  The
+// four blocks are the four 4-frame groups of the row tile: A[i][k] of block q sits in lane
+// i + 4 q + 16 k, which IS the large form's A fragment (row 4 q + i of 16), so the window
+// operands are shared and nothing else is read from LDS.  B[k][j] of block q sits in lane
+// j + 4 q + 16 k: every block wants the same four channels, one more G load per group.
+// D[i][j] of block q comes out in lane j + 4 q + 16 i, one double per lane.
+template <int TA, int NB, int NWV, int WRAPS, bool TAIL, int RG>
+__device__ __forceinline__ void wpe_apply_body(const cplx *__restrict__ Y,
+                                               const cplx *__restrict__ G, int F, int64_t T, int D,
+                                               int n, int c, cplx *__restrict__ X) {
     constexpr int WAVE_FRAMES = 16 * TA, WG_FRAMES = NWV * WAVE_FRAMES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     cplx *S = reinterpret_cast<cplx *>(smem);   // (WG_FRAMES + c + 2) * DP
@@ -1421,15 +1481,22 @@ __global__ __launch_bounds__(64 * NWV) void wpe_apply_kernel(const cplx *__restr
     // (no barrier below: a wave whose frames all lie past the last one -- two of the 32 wave
     // tiles at T = 941 -- leaves its SIMD to the other workgroup's wave)
     if (t0 + wf0 >= T) return;
-    v4d acc_re[TA][NB], acc_im[TA][NB], acc_t2[TA][NB];
+    static_assert(RG == 0 || NB == 2, "remainder groups replace the second of two channel tiles");
+    constexpr int NBL = RG > 0 ? 1 : NB;         // channel tiles on the 16x16x4 form
+    constexpr int NG = RG > 0 ? RG : 1;          // (arrays of length 0 are not C++)
+    v4d acc_re[TA][NBL], acc_im[TA][NBL], acc_t2[TA][NBL];
+    double sml_re[TA][NG], sml_im[TA][NG], sml_t2[TA][NG];
 #pragma unroll
-    for (int a = 0; a < TA; ++a)
+    for (int a = 0; a < TA; ++a) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
+        for (int b = 0; b < NBL; ++b) {
             acc_re[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
             acc_im[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
             acc_t2[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
         }
+#pragma unroll
+        for (int g = 0; g < NG; ++g) sml_re[a][g] = sml_im[a][g] = sml_t2[a][g] = 0.0;
+    }
     // Two k-steps per trip with ping-pong operand registers: G rows (global, L2 resident)
     // and window fragments (LDS) of k-step ks + 1 are requested before the MFMAs of ks are
     // issued and first touched a k-step later, so neither latency sits between two groups
@@ -1445,16 +1512,18 @@ __global__ __launch_bounds__(64 * NWV) void wpe_apply_kernel(const cplx *__restr
     // element offset per channel tile, + 4 D per k-step, clamped to the last row (k-steps
     // past the end are requested and never used).  Window: lin = (r / D) DP + r % D of the
     // running row r = 4 ks + lk, + 4 per k-step, + DP - D when r % D wraps.
-    int goff[NB], goff_max[NB];
+    // (slots NBL ..: the remainder groups, channels 16 + 4 g + (lane & 3) in every block)
+    constexpr int NBG = NBL + RG;
+    int goff[NBG], goff_max[NBG];
 #pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int col = min(16 * b + li, D - 1);
+    for (int b = 0; b < NBG; ++b) {
+        const int col = min(b < NBL ? 16 * b + li : 16 + 4 * (b - NBL) + (lane & 3), D - 1);
         goff[b] = min(lk, n - 1) * D + col;
         goff_max[b] = (n - 1) * D + col;
     }
-    auto load_g = [&](int, cplx (&g)[NB]) {      // (k-steps are requested in order)
+    auto load_g = [&](int, cplx (&g)[NBG]) {     // (k-steps are requested in order)
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
+        for (int b = 0; b < NBG; ++b) {
             g[b] = Gf[goff[b]];
             goff[b] = min(goff[b] + 4 * D, goff_max[b]);
         }
@@ -1475,36 +1544,44 @@ __global__ __launch_bounds__(64 * NWV) void wpe_apply_kernel(const cplx *__restr
             lin += wrap ? DP - D : 0;
         }
     };
-    auto step = [&](int ks, const cplx (&g)[NB], const cplx (&u)[TA]) {
+    auto step = [&](int ks, const cplx (&g)[NBG], const cplx (&u)[TA]) {
         const bool ok = !TAIL || 4 * ks + lk < n;
-        double ur[TA], ui[TA], gr[NB], gi[NB];
+        double ur[TA], ui[TA], gr[NBG], gi[NBG];
 #pragma unroll
         for (int a = 0; a < TA; ++a) {
             ur[a] = ok ? u[a].x : 0.0;
             ui[a] = ok ? u[a].y : 0.0;
         }
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
+        for (int b = 0; b < NBG; ++b) {
             gr[b] = g[b].x;
             gi[b] = g[b].y;
         }
         // u * conj(g)
         // acc_re = t1, acc_t2 = t2, acc_im = t3
-        double us[TA], gd[NB];
+        double us[TA], gd[NBG];
 #pragma unroll
         for (int a = 0; a < TA; ++a) us[a] = ur[a] + ui[a];
 #pragma unroll
-        for (int b = 0; b < NB; ++b) gd[b] = gr[b] - gi[b];
+        for (int b = 0; b < NBG; ++b) gd[b] = gr[b] - gi[b];
 #pragma unroll
-        for (int a = 0; a < TA; ++a)
+        for (int a = 0; a < TA; ++a) {
 #pragma unroll
-            for (int b = 0; b < NB; ++b) {
+            for (int b = 0; b < NBL; ++b) {
                 acc_re[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(ur[a], gr[b], acc_re[a][b], 0, 0, 0);
                 acc_t2[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(ui[a], gi[b], acc_t2[a][b], 0, 0, 0);
                 acc_im[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(us[a], gd[b], acc_im[a][b], 0, 0, 0);
             }
+#pragma unroll
+            for (int g = 0; g < RG; ++g) {
+                const int b = NBL + g;
+                sml_re[a][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(ur[a], gr[b], sml_re[a][g], 0, 0, 0);
+                sml_t2[a][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(ui[a], gi[b], sml_t2[a][g], 0, 0, 0);
+                sml_im[a][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(us[a], gd[b], sml_im[a][g], 0, 0, 0);
+            }
+        }
     };
-    cplx g0[NB], g1[NB], u0[TA], u1[TA];
+    cplx g0[NBG], g1[NBG], u0[TA], u1[TA];
     load_g(0, g0);
     load_u(u0);
     for (int ks = 0; ks < ksteps; ks += 2) {
@@ -1525,7 +1602,7 @@ __global__ __launch_bounds__(64 * NWV) void wpe_apply_kernel(const cplx *__restr
 #pragma unroll
     for (int a = 0; a < TA; ++a)
 #pragma unroll
-        for (int b = 0; b < NB; ++b)
+        for (int b = 0; b < NBL; ++b)
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 const int fl = wf0 + 16 * a + lk + 4 * reg;
@@ -1538,6 +1615,38 @@ __global__ __launch_bounds__(64 * NWV) void wpe_apply_kernel(const cplx *__restr
                     X[((int64_t)f * T + t) * D + d] = c_make(y.x - pre, y.y - pim);
                 }
             }
+    // remainder groups: block q = 4-frame group, row = lane >> 4 of it, col = lane & 3
+#pragma unroll
+    for (int a = 0; a < TA; ++a)
+#pragma unroll
+        for (int g = 0; g < RG; ++g) {
+            const int fl = wf0 + 16 * a + 4 * ((lane >> 2) & 3) + (lane >> 4);
+            const int d = 16 + 4 * g + (lane & 3);
+            const int64_t t = t0 + fl;
+            if (d < D && t < T) {
+                const cplx y = S[(fl + c) * DP + d];
+                const double pre = sml_re[a][g] + sml_t2[a][g];
+                const double pim = (sml_im[a][g] - sml_re[a][g]) + sml_t2[a][g];
+                X[((int64_t)f * T + t) * D + d] = c_make(y.x - pre, y.y - pim);
+            }
+        }
+}
+
+template <int TA, int NB, int NWV = 4, int WRAPS = 4, bool TAIL = true>
+__global__ __launch_bounds__(64 * NWV) void wpe_apply_kernel(const cplx *__restrict__ Y,
+                                                        const cplx *__restrict__ G, int F,
+                                                        int64_t T, int D, int n, int c,
+                                                        cplx *__restrict__ X) {
+    wpe_apply_body<TA, NB, NWV, WRAPS, TAIL, 0>(Y, G, F, T, D, n, c, X);
+}
+
+// 17 - 28 channels: two channel tiles, the second as RG = 1 .. 3 remainder groups
+template <int TA, int RG, bool TAIL>
+__global__ __launch_bounds__(256) void wpe_apply_rg_kernel(const cplx *__restrict__ Y,
+                                                           const cplx *__restrict__ G, int F,
+                                                           int64_t T, int D, int n, int c,
+                                                           cplx *__restrict__ X) {
+    wpe_apply_body<TA, 2, 4, 1, TAIL, RG>(Y, G, F, T, D, n, c, X);
 }
 
 // ------------------------------------------------------------------ apply, frame phases packed into N
@@ -1822,6 +1931,12 @@ __global__ void mfma_selftest_kernel(double *out) {
         const int row = lk + 4 * reg, col = li;
         out[row * 16 + col] = acc[reg];
     }
+    // v_mfma_f64_4x4x4_4b_f64, all four blocks and every k: A[q][i][k] in lane i + 4 q + 16 k,
+    // B[q][k][j] in lane j + 4 q + 16 k, D[q][i][j] in lane j + 4 q + 16 i
+    // A[q][i][k] = 1 + i + 4 q + 16 k, B[q][k][j] = 100 (1 + j + 4 q + 16 k)
+    double d = 0.0;
+    d = __builtin_amdgcn_mfma_f64_4x4x4f64((double)(lane + 1), 100.0 * (double)(lane + 1), d, 0, 0, 0);
+    out[256 + lane] = d;
 }
 
 // ------------------------------------------------------------------ per-array regroup
@@ -1884,7 +1999,15 @@ int wpe_arrays_regroup_run(gss_ctx *ctx, const cplx *src, int F, int64_t T, int 
     return GSS_OK;
 }
 
-static int corr_tiles(int n, int D, int c, int ct, std::vector<CorrTile> &tiles) {
+// MFMA issue time of a wave's tile in units of one 4x4x4_4b instruction per product (a 16 x 16
+// sub-tile: 4; a remainder group of a P tile: 1 per needed row sub-tile)
+static int corr_tile_cost(const CorrTile &t) {
+    const int rg = (t.mask >> 4) & 3;
+    if (rg == 0) return 4 * __builtin_popcount(t.mask & 15);
+    return 4 * __builtin_popcount(t.mask & 5) + rg * __builtin_popcount(t.mask & 10);
+}
+
+static int corr_tiles(int n, int D, int c, int ct, bool small_p, std::vector<CorrTile> &tiles) {
     // R: every ct x ct tile that reaches the upper triangle; P: all rows x D columns.
     // mask = the 16 x 16 sub-tiles that hold at least one needed entry.
     const int ts = ct / 16;
@@ -1917,11 +2040,16 @@ static int corr_tiles(int n, int D, int c, int ct, std::vector<CorrTile> &tiles)
             }
     if (!p_folded)
         for (int r0 = 0; r0 < n; r0 += ct)
-            for (int c0 = 0; c0 < D; c0 += ct)
-                tiles.push_back({r0, c * D + c0, 1, mask_of(r0, c0, D, false)});
+            for (int c0 = 0; c0 < D; c0 += ct) {
+                int m = mask_of(r0, c0, D, false);
+                // 32 x 32 tiles, 17 - 28 channels: the D - 16 columns of the second column
+                // sub-tile as groups of 4 on the 4-block MFMA (mask bits 4 - 5: their number)
+                if (small_p && ct == 32 && m == 15 && D > 16 && D <= 28) m |= ((D - 16 + 3) / 4) << 4;
+                tiles.push_back({r0, c * D + c0, 1, m});
+            }
     // heaviest first, so that the four waves of a workgroup carry similar loads
     std::stable_sort(tiles.begin(), tiles.end(), [](const CorrTile &x, const CorrTile &y) {
-        return __builtin_popcount(x.mask) > __builtin_popcount(y.mask);
+        return corr_tile_cost(x) > corr_tile_cost(y);
     });
     return (int)tiles.size();
 }
@@ -2046,7 +2174,11 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
         corr_ts = e == 1 ? 1 : 2;
         corr_pairs = e == 3;
     }
-    const int ntiles = corr_pairs ? corr_tiles_pairs(n, D, c, tiles) : corr_tiles(n, D, c, 16 * corr_ts, tiles);
+    // GSS_VARIANT remainder_full_tile: the half-empty channel tile of 17 - 28 channels as a full
+    // 16-column MFMA tile in the correlation's P tiles and in the filter application
+    const bool remainder_full_tile = gss_variant_set("remainder_full_tile");
+    const int ntiles = corr_pairs ? corr_tiles_pairs(n, D, c, tiles)
+                                  : corr_tiles(n, D, c, 16 * corr_ts, !remainder_full_tile, tiles);
     // trailing-update tiles: 16 x 16, every tile that reaches the upper triangle (larger
     // register tiles -- 2 x 2, 1 x 2, 2 x 1 MFMA tiles per wave -- measured slower: the update
     // is bound by the read-modify-write of the trailing matrix and wants many small
@@ -2086,7 +2218,7 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
                 "wpe: taps*D=%d too large", n);
     static_assert(sizeof(CorrTile) == sizeof(UpdTile), "tile structs share one buffer");
     if (ctx->wpe_tiles_key[0] != taps || ctx->wpe_tiles_key[1] != delay ||
-        ctx->wpe_tiles_key[2] != D || ctx->wpe_tiles_key[3] != corr_ts + (fold_diag ? 0 : 16) + (corr_pairs ? 32 : 0)) {
+        ctx->wpe_tiles_key[2] != D || ctx->wpe_tiles_key[3] != corr_ts + (fold_diag ? 0 : 16) + (corr_pairs ? 32 : 0) + (remainder_full_tile ? 64 : 0)) {
         GSS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         if (!ctx->wpe_tiles)
             GSS_HIP_CHECK(ctx, hipMalloc(&ctx->wpe_tiles, sizeof(CorrTile) * (1024 + 4096 + 1 + 64)));
@@ -2102,7 +2234,7 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
         ctx->wpe_tiles_key[0] = taps;
         ctx->wpe_tiles_key[1] = delay;
         ctx->wpe_tiles_key[2] = D;
-        ctx->wpe_tiles_key[3] = corr_ts + (fold_diag ? 0 : 16) + (corr_pairs ? 32 : 0);
+        ctx->wpe_tiles_key[3] = corr_ts + (fold_diag ? 0 : 16) + (corr_pairs ? 32 : 0) + (remainder_full_tile ? 64 : 0);
     }
     CorrTile *tiles_dev = reinterpret_cast<CorrTile *>(ctx->wpe_tiles);
     UpdTile *upd_dev = reinterpret_cast<UpdTile *>(tiles_dev + 1024);
@@ -2188,6 +2320,16 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
         else
             apply_fn = D <= 16 ? wpe_apply_kernel<apply_ta, 1, 4, 1, true>
                                : wpe_apply_kernel<apply_ta, 2, 4, 1, true>;
+        // 17 - 28 channels: the second channel tile as 1 - 3 groups of 4 channels on the 4-block
+        // MFMA (GSS_VARIANT remainder_full_tile: the full 16-column tile as before)
+        using apply_t = decltype(apply_fn);
+        static const apply_t table_rg[2][3] = {
+            {wpe_apply_rg_kernel<apply_ta, 1, false>, wpe_apply_rg_kernel<apply_ta, 2, false>,
+             wpe_apply_rg_kernel<apply_ta, 3, false>},
+            {wpe_apply_rg_kernel<apply_ta, 1, true>, wpe_apply_rg_kernel<apply_ta, 2, true>,
+             wpe_apply_rg_kernel<apply_ta, 3, true>}};
+        if (D > 16 && D <= 28 && !remainder_full_tile)
+            apply_fn = table_rg[n % 8 == 0 ? 0 : 1][(D - 16 + 3) / 4 - 1];
     }
     const size_t apply_lds = sizeof(cplx) * (size_t)(apply_frames + c + 2) * (D | 1);
     // frame phases packed into the N dimension (wpe_apply_packed_kernel): pick the number of
@@ -2294,7 +2436,7 @@ int wpe_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, int taps, int 
     if (corr_persist) {
         // heavy groups: the heaviest wave needs 3 or 4 of its tile's 4 sub-tiles
         for (int g = 0; g < corr_queue.ngroups; ++g)
-            if (__builtin_popcount(tiles[g * corr_nw].mask) >= 3) corr_queue.gh = g + 1;
+            if (corr_tile_cost(tiles[g * corr_nw]) >= 12) corr_queue.gh = g + 1;
         if (corr_dma_lds > 64 * 1024)
             GSS_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(corr_persist_fn),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2408,9 +2550,9 @@ int wpe_copy_zero_pivots(gss_ctx *ctx) {
 
 int selftest_mfma_run(gss_ctx *ctx) {
     double *out = nullptr;
-    GSS_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void **>(&out), sizeof(double) * 256));
+    GSS_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void **>(&out), sizeof(double) * 320));
     hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, ctx->stream, out);
-    double host[256];
+    double host[320];
     hipError_t e = hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     (void)hipFree(out);
@@ -2423,5 +2565,17 @@ int selftest_mfma_run(gss_ctx *ctx) {
                                 "f64 MFMA fragment layout mismatch at (%d,%d): got %g want %g", i,
                                 j, host[i * 16 + j], want);
         }
+    for (int q = 0; q < 4; ++q)
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) {
+                double want = 0.0;
+                for (int k = 0; k < 4; ++k)
+                    want += (double)(1 + i + 4 * q + 16 * k) * 100.0 * (double)(1 + j + 4 * q + 16 * k);
+                const double got = host[256 + j + 4 * q + 16 * i];
+                if (got != want)
+                    return gss_fail(ctx, GSS_ERR_UNSUPPORTED,
+                                    "f64 4x4x4 MFMA fragment layout mismatch at block %d (%d,%d): got %g want %g",
+                                    q, i, j, got, want);
+            }
     return GSS_OK;
 }

@@ -76,6 +76,12 @@ def kernel_work(name, *, F, T, D, K, taps, N, iterations=20):
         c = (n // D) + 1 if D else 0          # delay 2: c = taps + 1 frames back
         if D <= 12 and (c * D) // 16 == (c * D + D - 1) // 16 == sub - 1:
             subtiles = sub * (sub + 1) // 2   # P sits in R's last column tile (one array)
+        if 16 < D <= 28 and subtiles > 48:
+            # 32 x 32 tiles: the D - 16 columns of P's second column sub-tile run as groups of 4
+            # on the 4-block MFMA in every whole P tile (both row sub-tiles needed: r0 + 16 < n):
+            # a group issues a quarter of a sub-tile's flops
+            whole = max(0, -(-(n - 16) // 32))
+            subtiles -= 2 * whole * (1 - -(-(D - 16) // 4) / 4.0)
         # frames the MFMAs run over: chunks of 64 (16 k-steps); the persistent 32 x 32 kernel
         # (more than 48 sub-tiles) runs a last chunk of at most 48 frames in groups of 16
         rem = T % 64
