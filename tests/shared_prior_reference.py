@@ -5,10 +5,17 @@ and the `gss_block_batched` flow around it.  Scenes, their stability under a las
 the input, and the 'bins consistent' measure of the issue live here too, so that the CPU and the
 GPU tests share them.  Every reference run is computed once per session and shared."""
 import functools
+import sys
+from pathlib import Path
 
 import numpy as np
 
-import gss_oracle as oracle
+_HERE = Path(__file__).resolve().parent
+for _p in (str(_HERE.parent), str(_HERE.parent / 'oracle')):    # (run as a script: no conftest)
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import gss_oracle as oracle            # noqa: E402
 
 EM_TOL = 1e-7               # tests/test_gpu_specialisations.py: max |posterior - oracle|
 STABILITY_MARGIN = 100.0    # the oracle itself must move at least this much less than the bar
@@ -123,6 +130,25 @@ FORMS = ('blind', 'random', 'weak')
 # tests/test_gpu_specialisations.py names those of the per-frequency EM: F = 2, five full tiles
 # and a ragged one, weakly guided
 REG_CELLS = [(D, 327, 2, K, 2, 1) for D in (4, 10, 12, 20, 24) for K in (2, 3, 4, 5, 6)]
+# every instantiation of the LDS-form E-step (K = 1..19; first, fit and predict launch in every
+# cell: two iterations and an unmasked predict) at one unspecialised D <= 12 and one above 12,
+# as EM_SWEEP_CELLS of tests/test_gpu_specialisations.py does for the per-frequency EM: F = 2,
+# and every point source has D + 8 frames of its own (`em_default_frames` there).  K = 1 launches
+# its three instantiations but cannot fail on values: the posterior of a single class is 1.
+LDS_D, LDS_K = (7, 17), tuple(range(1, 20))
+
+
+def lds_frames(D, K):
+    need, T = K * (D + 8) - 1, 327
+    while T <= need:
+        T += 64
+    return T
+
+
+LDS_CELLS = [(D, lds_frames(D, K), 2, K, 2, 1) for D in LDS_D for K in LDS_K]
+# the unguided (K,T) start in a handful of them: both D, K either side of the eight-class groups
+LDS_BLIND_CELLS = [c for c in LDS_CELLS if (c[0], c[3]) in ((7, 2), (7, 9), (7, 19), (17, 8),
+                                                            (17, 11), (17, 16))]
 # the mask-only start (no initialisation: the 1 : 1e-10 table is derived on the device), with a
 # (K,T) mask for every frequency and with an (F,K,T) one
 MASK_ONLY_CELLS = [CELLS[0], CELLS[2], CELLS[5]]
@@ -130,7 +156,8 @@ MASK_ONLY_CELLS = [CELLS[0], CELLS[2], CELLS[5]]
 # posteriors and prior move at least STABILITY_MARGIN x less than EM_TOL when every input sample
 # moves in its last bit (`python tests/shared_prior_reference.py` re-derives the table).  Seed 0
 # passed in all 24: the reference moves by 1.4e-17 ... 8.3e-11 (the largest at D = 24, random
-# start), so the table is empty.
+# start), so the table is empty.  Seed 0 passed in the 38 + 6 LDS-form cells too: the reference
+# moves by 5.4e-15 ... 1.3e-11 (the largest at D = 17, K = 13, weak), exactly 0 at K = 1.
 SEEDS = {}
 
 
@@ -306,9 +333,6 @@ def blind_movement(scene_seed=None):
 
 
 if __name__ == '__main__':
-    import sys
-    from pathlib import Path
-    sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
     for cell in CELLS:
         for form in FORMS:
             seed = choose_seed(cell, form)
@@ -316,6 +340,9 @@ if __name__ == '__main__':
     for cell in REG_CELLS:
         print(f'    ({cell}, weak): {choose_seed(cell, "weak")},   # moves '
               f'{reference_movement(cell, "weak", choose_seed(cell, "weak")):.1e}')
+    for cell, form in [(c, 'weak') for c in LDS_CELLS] + [(c, 'blind') for c in LDS_BLIND_CELLS]:
+        seed = choose_seed(cell, form)
+        print(f'    ({cell}, {form!r}): {seed},   # moves {reference_movement(cell, form, seed):.1e}')
     for cell in MASK_ONLY_CELLS:
         for per_f in (False, True):
             print(f'    mask only {cell} per_frequency={per_f}: moves '

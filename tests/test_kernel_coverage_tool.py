@@ -65,3 +65,41 @@ def test_diff_names_what_a_trace_never_launched(lib, tmp_path):
         '"Kernel_Name"\n"void (anonymous namespace)::em_onchip4_kernel<4>(OnchipArgs)"\n')
     both = _run('diff', trace, more, '--lib', lib)
     assert 'em_onchip4_kernel: 2 of 5 never launched' in both
+    # --write-launched: the sorted names of the library's launched instantiations, nothing else
+    # (the copy of the kernel from another library that the trace may hold is left out)
+    (more / '8_kernel_trace.csv').write_text(
+        '"Kernel_Name"\n"void at::native::vectorized_elementwise_kernel<4>(int)"\n')
+    out_file = tmp_path / 'launched.txt'
+    again = _run('diff', trace, more, '--lib', lib, '--write-launched', out_file)
+    assert again.splitlines()[1:3] == both.splitlines()[1:3]
+    assert out_file.read_text() == ('em_onchip4_kernel<2>\nem_onchip4_kernel<3>\n'
+                                    'em_onchip4_kernel<4>\ntri_table_kernel\n')
+
+
+# ------------------------------------------------------------------ the record of the suite
+LAUNCHED = REPO / 'tests' / 'golden' / 'kernels_launched.txt'
+UNREACHABLE = REPO / 'tests' / 'golden' / 'kernels_unreachable.txt'
+# entries of kernels_unreachable.txt when the list was written (tests/KERNEL_COVERAGE.md names the
+# reason of each): the list may shrink, it must not grow
+MAX_UNREACHABLE = 14
+
+
+def _names(path):
+    lines = path.read_text().splitlines()
+    assert lines == sorted(set(lines)) and all(line == line.strip() != '' for line in lines), path
+    return set(lines)
+
+
+def test_every_instantiation_is_launched_by_the_gpu_suite_or_listed_as_unreachable(lib):
+    """tests/golden/kernels_launched.txt is what a kernel trace of the whole GPU suite launched
+    (`diff --write-launched`, tests/KERNEL_COVERAGE.md), kernels_unreachable.txt what no entry
+    point can reach.  Together they are the library: a change that adds an instantiation fails
+    here until a GPU test launches it and the suite is traced again."""
+    names = set(_run('list', '--lib', lib).splitlines())
+    launched, unreachable = _names(LAUNCHED), _names(UNREACHABLE)
+    assert not launched & unreachable, sorted(launched & unreachable)
+    assert len(unreachable) <= MAX_UNREACHABLE
+    missing = sorted(names - launched - unreachable)
+    assert not missing, f'{len(missing)} instantiations no GPU test is known to launch: {missing}'
+    gone = sorted((launched | unreachable) - names)
+    assert not gone, f'{len(gone)} recorded names are no longer in the library: {gone}'

@@ -3,12 +3,15 @@
 
     python tools/kernel_coverage.py list [--lib LIB]
     python tools/kernel_coverage.py diff TRACE.csv [TRACE.csv | DIR ...] [--lib LIB]
+                                         [--write-launched FILE]
 
 ``list`` prints every kernel instantiation of the gfx950 code object inside libgss_hip.so,
 demangled, with its template arguments, one per line.  ``diff`` reads the kernel-trace CSV(s) of
 a profiler run (``rocprofv3 --kernel-trace --output-format csv``: the column ``Kernel_Name``; a
 directory is searched for ``*kernel_trace.csv``) and prints the instantiations that were never
-launched, grouped by template.
+launched, grouped by template; ``--write-launched FILE`` also writes the sorted names of the
+library's instantiations that were launched, one per line and nothing else (the record kept as
+tests/golden/kernels_launched.txt).
 
 Host only: the code object is unbundled with clang-offload-bundler, its kernel-descriptor
 symbols (``<kernel>.kd``) are read with readelf and demangled with c++filt.  Names are all this
@@ -172,6 +175,8 @@ def main(argv=None):
     p_diff = sub.add_parser('diff', help='instantiations a traced run never launched')
     p_diff.add_argument('trace', nargs='+', help='kernel-trace CSV files or directories of them')
     p_diff.add_argument('--lib', default=str(DEFAULT_LIB))
+    p_diff.add_argument('--write-launched', metavar='FILE',
+                        help='write the sorted names of the launched instantiations to FILE')
     args = ap.parse_args(argv)
 
     names = kernel_names(args.lib)
@@ -181,6 +186,8 @@ def main(argv=None):
         return 0
     launched = launched_names(args.trace)
     ours = set(names)
+    if args.write_launched:
+        Path(args.write_launched).write_text(''.join(f'{n}\n' for n in sorted(launched & ours)))
     groups = unreached(names, launched)
     missing = sum(len(v) for v in groups.values())
     print(f'{len(names)} instantiations in the library, {len(launched & ours)} launched, '
