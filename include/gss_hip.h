@@ -100,7 +100,9 @@ typedef enum {
  * gss_stream_flush_samples, gss_stft_stream, gss_istft_stream and gss_stream_block with the
  * gss_stream_state and gss_stream_cfg descriptors.  So were gss_mvdr_online_targets,
  * gss_last_mvdr_online_fallbacks_targets, gss_istft_stream_targets and gss_stream_block_targets
- * (they take the existing descriptors as they are). */
+ * (they take the existing descriptors as they are).  So were gss_mvdr_online_hold_init,
+ * gss_mvdr_online_lookahead, gss_mvdr_online_lookahead_targets, gss_mvdr_online_release and
+ * gss_stream_block_lookahead with the gss_mvdr_online_hold descriptor. */
 #define GSS_ABI_VERSION 7
 int gss_abi_version(void);
 
@@ -701,7 +703,8 @@ int gss_wpe_online(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int A,
  *    ban:  v = Phi_N w;  w <- w sqrt(v^H v) / |w^H v|       (eps = 0 as upstream, except that
  *                     |w^H v| = 0 -- a zero filter: no target mass yet, as in the context frames
  *                     of every window -- leaves w = 0 where upstream divides 0 by 0)
- *    Xhat[f,t] = w^H y          the sums INCLUDE frame t: causal, zero look-ahead
+ *    Xhat[f,t] = w^H y          the sums INCLUDE frame t: look-ahead L, default 0 (the entries
+ *                     below; L >= 1: gss_mvdr_online_lookahead further down)
  * A fresh state is Phi_X = 0, Phi_N = loading * p_f * I, where p_f is the mean of |Y[f,t,d]|^2
  * over the frames and channels handed to the initialisation (1 when there are none, or when
  * that mean is exactly 0). */
@@ -1203,6 +1206,82 @@ int gss_stream_block_targets(gss_ctx *ctx, const gss_params *params, const gss_s
                              double *tails_dev, const void *x_dev, int in_type,
                              const uint8_t *act_dev, int64_t n, const int32_t *targets, int S,
                              double *out_dev, const gss_debug_taps *taps);
+
+/* ---- online MVDR with a filter look-ahead of L frames ----------------------------
+ * A fixed lag: frame g is filtered with the filter of frame g + L, which has already seen what
+ * follows g -- a speaker's onset above all.  (Entry points only: revision still 7.)  Frames are
+ * numbered g = 0, 1, ... over the life of a delay line; w_g is the filter gss_mvdr_online solves at
+ * frame g.  The recursion, the fallback rule and BAN are those of gss_mvdr_online, the running
+ * sums after any sequence of calls have the bits they have without a look-ahead, and fallback
+ * frames are counted when a frame ENTERS.  With G the frames that had entered at the release:
+ *    Xhat[g] = w_{min(g + L, G - 1)}^H y_g       (a fallback frame at g + L: Xhat[g] = 0)
+ *    the filter row g is w_{min(g + L, G - 1)};  postfilter: times the target mask of frame g
+ * A call of T frames on a line that holds h frames (0 <= h <= L) releases max(0, h + T - L)
+ * frames, in order, and leaves min(L, h + T) held; gss_mvdr_online_release releases the held
+ * frames with the filter of the last frame that entered, empties the line and leaves the sums.
+ * The line is the caller's, one per target: every wave reads and writes only its own. */
+#define GSS_MVDR_ONLINE_MAX_LOOKAHEAD 64   /* a choice: one second at 16 kHz / 256 */
+typedef struct {
+    gss_cplx *frames;          /* (F, L, D): the held frames, oldest first */
+    double *mask;              /* (F, L): their target-mask values (read by the postfilter) */
+    gss_cplx *filter;          /* (F, D): the filter of the last frame that entered */
+    int32_t F, D, L;
+    int32_t held;              /* host counter, advanced by the calls: frames held, 0 .. L */
+} gss_mvdr_online_hold;        /* caller-owned; separate from gss_mvdr_online_state */
+
+/* Zeroes the three buffers and `held`.  GSS_ERR_INVALID: a NULL hold or buffer, F < 1, L outside
+ * [1, GSS_MVDR_ONLINE_MAX_LOOKAHEAD].  GSS_ERR_UNSUPPORTED: D outside [1, GSS_MAX_CHANNELS]. */
+int gss_mvdr_online_hold_init(gss_ctx *ctx, gss_mvdr_online_hold *hold);
+
+/* gss_mvdr_online with the look-ahead hold->L.  `state` is required (a line outlives a call, so
+ * there is no thrown-away state).  Xhat (F,R) and W (F,R,D) or NULL with
+ * R = max(0, hold->held + T - hold->L) rows, which *frames_out receives (it may be NULL).  T = 0 is
+ * a no-op.  GSS_ERR_INVALID before any launch, the state and the line untouched: the errors of
+ * gss_mvdr_online, a NULL state or hold or hold buffer, hold->F / D other than F / D, hold->L
+ * outside [1, GSS_MVDR_ONLINE_MAX_LOOKAHEAD], hold->held outside [0, hold->L],
+ * cfg->ref_channel = -1 (the whole-window choice is per call). */
+int gss_mvdr_online_lookahead(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                              const double *mask_x_dev, const double *mask_n_dev, int ban,
+                              const gss_bf_online *cfg, gss_mvdr_online_state *state,
+                              gss_mvdr_online_hold *hold, gss_cplx *Xhat_dev, gss_cplx *W_dev,
+                              int64_t *frames_out);
+
+/* gss_mvdr_online_targets with a look-ahead: `holds` is a host array of S lines of one L and one
+ * `held`, no buffer shared.  Row s has the bits of gss_mvdr_online_lookahead on the masks of class
+ * targets[s]; the postfilter multiplies by the target mask of the OUTPUT frame.  Xhat (S,R,F),
+ * W (S,F,R,D) or NULL; mask_x_dev / mask_n_dev (S,F,T) or NULL: the masks of the call's T frames.
+ * The errors of gss_mvdr_online_targets and of gss_mvdr_online_lookahead's hold. */
+int gss_mvdr_online_lookahead_targets(gss_ctx *ctx, const gss_cplx *Y_dev, int F, int64_t T, int D,
+                                      const double *gamma_dev, int K, const int32_t *targets,
+                                      int S, int ban, const gss_bf_online *cfg,
+                                      const gss_mvdr_online_state *states,
+                                      gss_mvdr_online_hold *holds, int postfilter,
+                                      double *mask_x_dev, double *mask_n_dev, gss_cplx *Xhat_dev,
+                                      gss_cplx *W_dev, int64_t *frames_out);
+
+/* The end of S lines (S = 1: the line of gss_mvdr_online_lookahead): the h = holds[0].held frames
+ * with the last filter -> Xhat (S,h,F), W (S,F,h,D) or NULL; *frames_out = h.  Nothing held:
+ * nothing is launched.  GSS_ERR_INVALID: the hold errors above, Xhat_dev NULL with h > 0,
+ * postfilter other than 0 / 1. */
+int gss_mvdr_online_release(gss_ctx *ctx, gss_mvdr_online_hold *holds, int S, int postfilter,
+                            gss_cplx *Xhat_dev, gss_cplx *W_dev, int64_t *frames_out);
+
+/* gss_stream_block_targets (S >= 1) with a look-ahead: its body up to the posteriors, then
+ * gss_mvdr_online_lookahead_targets (BAN, the postfilter in its epilogue) and the synthesis of the
+ * frames released -- with `release` != 0 also gss_mvdr_online_release and the synthesis of the
+ * frames it releases: the last block of a stream.  out (S,m): the m samples those frames finish,
+ * counted from state->frames_out, which *samples_out receives (it may be NULL; the caller sizes
+ * `out` for gss_stream_num_samples_out() of the block plus, with `release`, L * shift more).  n = 0
+ * with `release` only ends the lines.  The taps target_mask, distortion_mask, gamma and Obs_ftd
+ * cover the block's frames, Xhat the frames released (S consecutive blocks).  The errors and
+ * codes of gss_stream_block_targets and of gss_mvdr_online_lookahead_targets' holds. */
+int gss_stream_block_lookahead(gss_ctx *ctx, const gss_params *params, const gss_stream_cfg *cfg,
+                               gss_stream_state *state, const gss_wpe_online_state *wpe,
+                               gss_cacgmm_online_state *em, const gss_mvdr_online_state *bf,
+                               gss_mvdr_online_hold *holds, double *tails_dev, const void *x_dev,
+                               int in_type, const uint8_t *act_dev, int64_t n,
+                               const int32_t *targets, int S, int release, double *out_dev,
+                               int64_t *samples_out, const gss_debug_taps *taps);
 
 /* gss_enhance_observation plus gss_posterior_activity on the pipeline's own post-WPE observation
  * and its posteriors before context zeroing (what the taps Obs_ftd and gamma show), nothing

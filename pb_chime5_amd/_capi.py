@@ -88,6 +88,15 @@ class GssMvdrOnlineState(ctypes.Structure):
                 ('D', ctypes.c_int32)]
 
 
+class GssMvdrOnlineHold(ctypes.Structure):
+    """gss_mvdr_online_hold: the delay line of the online MVDR's look-ahead -- the held frames
+    (F,L,D), their target-mask values (F,L) and the last filter (F,D) in HBM, and the host counter
+    `held`, which the library advances."""
+    _fields_ = [('frames', c_void_p), ('mask', c_void_p), ('filter', c_void_p),
+                ('F', ctypes.c_int32), ('D', ctypes.c_int32), ('L', ctypes.c_int32),
+                ('held', ctypes.c_int32)]
+
+
 class GssBfOnline(ctypes.Structure):
     """gss_bf_online: the online MVDR's forgetting factor, the loading of a fresh state and the
     reference channel (-1: the window's); wpe_online / wpe_alpha are read by the fused entry."""
@@ -292,6 +301,31 @@ SIGNATURES = {
                                          ctypes.POINTER(GssMvdrOnlineState), c_void_p, c_void_p,
                                          c_int, c_void_p, c_int64, ctypes.POINTER(ctypes.c_int32),
                                          c_int, c_void_p, _TAPS]),
+    'gss_mvdr_online_hold_init': (c_int, [c_void_p, ctypes.POINTER(GssMvdrOnlineHold)]),
+    'gss_mvdr_online_lookahead': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p,
+                                          c_void_p, c_int, ctypes.POINTER(GssBfOnline),
+                                          ctypes.POINTER(GssMvdrOnlineState),
+                                          ctypes.POINTER(GssMvdrOnlineHold), c_void_p, c_void_p,
+                                          ctypes.POINTER(c_int64)]),
+    'gss_mvdr_online_lookahead_targets': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
+                                                  c_void_p, c_int, ctypes.POINTER(ctypes.c_int32),
+                                                  c_int, c_int, ctypes.POINTER(GssBfOnline),
+                                                  ctypes.POINTER(GssMvdrOnlineState),
+                                                  ctypes.POINTER(GssMvdrOnlineHold), c_int,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  ctypes.POINTER(c_int64)]),
+    'gss_mvdr_online_release': (c_int, [c_void_p, ctypes.POINTER(GssMvdrOnlineHold), c_int, c_int,
+                                        c_void_p, c_void_p, ctypes.POINTER(c_int64)]),
+    'gss_stream_block_lookahead': (c_int, [c_void_p, ctypes.POINTER(GssParams),
+                                           ctypes.POINTER(GssStreamCfg),
+                                           ctypes.POINTER(GssStreamState),
+                                           ctypes.POINTER(GssWpeOnlineState),
+                                           ctypes.POINTER(GssCacgmmOnlineState),
+                                           ctypes.POINTER(GssMvdrOnlineState),
+                                           ctypes.POINTER(GssMvdrOnlineHold), c_void_p, c_void_p,
+                                           c_int, c_void_p, c_int64,
+                                           ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_void_p,
+                                           ctypes.POINTER(c_int64), _TAPS]),
     'gss_last_ref_channel': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'gss_last_wpe_zero_pivots': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'gss_gev': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,

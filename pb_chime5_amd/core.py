@@ -1144,14 +1144,16 @@ class Enhancer:
                 if k != speaker_id and k not in garbage]
 
     def stream(self, num_channels, speakers=None, target=None, *, model=None, ref_channel=0,
-               fused=True, targets=None):
+               fused=True, targets=None, lookahead=0):
         """A `streaming.StreamingEnhancer` with this enhancer's settings: samples in and out in
         blocks of any length, the three online stages with carried states.  ``speakers``: the
         names of the classes in activity order (``target`` one of them; `process` then also
         takes the activity as a dict of per-sample tracks) or a class count (``target`` an
         index); or ``model=`` a fitted `CACGMM` for an unguided stream (``target`` an index).
         ``targets`` in the place of ``target``: several of them, names or indices like it, all
-        extracted in one pass -- `process` and `flush` then return (S, m).
+        extracted in one pass -- `process` and `flush` then return (S, m).  ``lookahead``: the
+        frames the beamformer's filter looks ahead (`StreamingEnhancer`; a stream's setting only:
+        `get_enhancer` has no such keyword and the windowed path no such form).
         NotImplementedError, naming the setting, for everything the stream is not built for: it
         needs gss_online and bf_online (bf='mvdrSouden_ban'), wpe_online wherever WPE runs and
         stft_fading, and has no channel selection, segments, interferer nulling or WPD."""
@@ -1220,7 +1222,8 @@ class Enhancer:
             wpe_arrays=self.wpe_arrays(None, num_channels) if w else 1,
             gss_forget=gss['forget'], gss_prior_mass=gss['prior_mass'], bf_forget=bf['forget'],
             bf_loading=bf['loading'], postfilter=self.bf_block.postfilter, fused=fused,
-            speakers=names, ctx=self._ctx() if self.device_id is not None else None)
+            speakers=names, lookahead=lookahead,
+            ctx=self._ctx() if self.device_id is not None else None)
 
     def _params(self):
         w = self.wpe_block

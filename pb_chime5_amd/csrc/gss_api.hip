@@ -2816,6 +2816,34 @@ static size_t stream_block_workspace(const gss_params *p, bool guided, bool mask
     return ws.bytes + 4096 + stage + (1 << 16);
 }
 
+// The stages of a block that do not depend on the targets, above the block's buffers: the
+// analysis, the online WPE and the online CACGMM -> b.X and the posteriors b.gamma.
+static int stream_block_front(gss_ctx *ctx, const gss_params *p, const gss_stream_cfg *cfg,
+                              gss_stream_state *st, const gss_wpe_online_state *wpe,
+                              gss_cacgmm_online_state *em, const void *x, int in_type,
+                              const uint8_t *act, int64_t n, int64_t Tn, const StreamBlockBuffers &b,
+                              size_t mark) {
+    const int D = st->D, K = em->K, F = p->stft_size / 2 + 1;
+    const int A = wpe_arrays_of(p);
+    GSS_TRY(stream_stft_run(ctx, x, in_type, act, n, st, b.Y, b.actf));
+    GSS_TRY(arena_release(ctx, mark));
+    // no solve in this call: clear the pivot count an earlier utterance left behind
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + GSS_STATUS_WPE_ZERO_PIVOTS, 0,
+                                      sizeof(int32_t), ctx->stream));
+    if (p->wpe) {
+        GSS_TRY(wpe_online_run(ctx, b.Y, F, Tn, A, D / A, p->wpe_taps, p->wpe_delay, cfg->wpe_alpha,
+                               reinterpret_cast<cplx *>(wpe->inv_cov_dev),
+                               reinterpret_cast<cplx *>(wpe->filter_dev),
+                               reinterpret_cast<cplx *>(wpe->history_dev), b.X,
+                               gss_variant_set("wpe_online_mem")));
+        GSS_TRY(arena_release(ctx, mark));
+    }
+    const EmGuide guide = act ? em_guide_from_activity(b.actf, Tn) : EmGuide{};
+    GSS_TRY(cacgmm_online_run(ctx, b.X, F, Tn, D, guide, K, cfg->em_forget, 1.0,
+                              reinterpret_cast<cplx *>(em->s), em->n, b.gamma));
+    return arena_release(ctx, mark);
+}
+
 // One block of a stream for S targets (the arguments validated by the entry): the analysis, the
 // online WPE and the online CACGMM once, then the beamformer and one synthesis for the S targets.
 // gss_stream_block is S = 1 with tails = the stream state's own ola_tail and `one_target`: its
@@ -2831,7 +2859,6 @@ static int stream_block_impl(gss_ctx *ctx, const char *what, const gss_params *p
                              bool one_target) {
     const int D = st->D, K = em->K, F = p->stft_size / 2 + 1;
     const bool guided = act != nullptr;
-    const int A = wpe_arrays_of(p);
     if (n == 0) return GSS_OK;
 
     const int64_t Tn = gss_stream_num_frames(st->received, n, p->stft_size, p->stft_shift);
@@ -2844,23 +2871,7 @@ static int stream_block_impl(gss_ctx *ctx, const char *what, const gss_params *p
     const StreamBlockBuffers b = stream_block_blocks(ws, p->wpe != 0, guided, masks, F, Tn, D, K, S);
     GSS_TRY(ws.status(what));
     const size_t mark = ctx->arena_off;
-    GSS_TRY(stream_stft_run(ctx, x, in_type, act, n, st, b.Y, b.actf));
-    GSS_TRY(arena_release(ctx, mark));
-    // no solve in this call: clear the pivot count an earlier utterance left behind
-    GSS_HIP_CHECK(ctx, hipMemsetAsync(ctx->status_dev + GSS_STATUS_WPE_ZERO_PIVOTS, 0,
-                                      sizeof(int32_t), ctx->stream));
-    if (p->wpe) {
-        GSS_TRY(wpe_online_run(ctx, b.Y, F, Tn, A, D / A, p->wpe_taps, p->wpe_delay, cfg->wpe_alpha,
-                               reinterpret_cast<cplx *>(wpe->inv_cov_dev),
-                               reinterpret_cast<cplx *>(wpe->filter_dev),
-                               reinterpret_cast<cplx *>(wpe->history_dev), b.X,
-                               gss_variant_set("wpe_online_mem")));
-        GSS_TRY(arena_release(ctx, mark));
-    }
-    const EmGuide guide = guided ? em_guide_from_activity(b.actf, Tn) : EmGuide{};
-    GSS_TRY(cacgmm_online_run(ctx, b.X, F, Tn, D, guide, K, cfg->em_forget, 1.0,
-                              reinterpret_cast<cplx *>(em->s), em->n, b.gamma));
-    GSS_TRY(arena_release(ctx, mark));
+    GSS_TRY(stream_block_front(ctx, p, cfg, st, wpe, em, x, in_type, act, n, Tn, b, mark));
     const OnlineTargetStates bf(states, S);
     if (one_target) {
         GSS_TRY(masks_from_posteriors_run(ctx, b.gamma, F, K, Tn, targets[0], /*drop=*/0, 0, 0, b.mx,
@@ -2926,4 +2937,251 @@ extern "C" int gss_stream_block_targets(gss_ctx *ctx, const gss_params *p, const
         ctx->last_online_targets = S;
     return stream_block_impl(ctx, what, p, cfg, st, wpe, em, x, in_type, act, n, targets, S, bf, tails,
                              out, taps, /*one_target=*/false);
+}
+
+// ------------------------------------------------------------------ online MVDR with a look-ahead
+// A delay line (or S of them), before any launch: the buffers, the sizes of the call, L within the
+// bound, the host counter within [0, L]; S lines share L and `held` and no buffer.
+static int check_mvdr_online_holds(gss_ctx *ctx, const char *what, const gss_mvdr_online_hold *holds,
+                                   int S, int F, int D) {
+    GSS_REQUIRE(ctx, holds, GSS_ERR_INVALID, "%s: hold is NULL", what);
+    for (int s = 0; s < S; ++s) {
+        const gss_mvdr_online_hold &h = holds[s];
+        GSS_REQUIRE(ctx, h.frames, GSS_ERR_INVALID, "%s: hold->frames is NULL", what);
+        GSS_REQUIRE(ctx, h.mask, GSS_ERR_INVALID, "%s: hold->mask is NULL", what);
+        GSS_REQUIRE(ctx, h.filter, GSS_ERR_INVALID, "%s: hold->filter is NULL", what);
+        GSS_REQUIRE(ctx, h.frames != h.filter, GSS_ERR_INVALID,
+                    "%s: hold->frames and hold->filter alias", what);
+        GSS_REQUIRE(ctx, h.F == F && h.D == D, GSS_ERR_INVALID,
+                    "%s: hold of F = %d, D = %d in a call of F = %d, D = %d", what, (int)h.F, (int)h.D,
+                    F, D);
+        GSS_REQUIRE(ctx, h.L >= 1 && h.L <= GSS_MVDR_ONLINE_MAX_LOOKAHEAD, GSS_ERR_INVALID,
+                    "%s: hold->L = %d outside [1, %d]", what, (int)h.L, GSS_MVDR_ONLINE_MAX_LOOKAHEAD);
+        GSS_REQUIRE(ctx, h.held >= 0 && h.held <= h.L, GSS_ERR_INVALID,
+                    "%s: hold->held = %d outside [0, %d]", what, (int)h.held, (int)h.L);
+        GSS_REQUIRE(ctx, h.L == holds[0].L && h.held == holds[0].held, GSS_ERR_INVALID,
+                    "%s: holds[%d] has L = %d, held = %d, holds[0] L = %d, held = %d", what, s,
+                    (int)h.L, (int)h.held, (int)holds[0].L, (int)holds[0].held);
+        for (int r = 0; r < s; ++r)
+            GSS_REQUIRE(ctx, holds[r].frames != h.frames && holds[r].mask != h.mask &&
+                                 holds[r].filter != h.filter && holds[r].frames != h.filter &&
+                                 holds[r].filter != h.frames,
+                        GSS_ERR_INVALID, "%s: holds[%d] and holds[%d] share a buffer", what, r, s);
+    }
+    return GSS_OK;
+}
+
+static int check_lookahead_ref(gss_ctx *ctx, const char *what, const gss_bf_online *cfg) {
+    GSS_REQUIRE(ctx, cfg->ref_channel >= 0, GSS_ERR_INVALID,
+                "%s: ref_channel = %d, the whole-window choice is per call and a delay line outlives "
+                "a call", what, (int)cfg->ref_channel);
+    return GSS_OK;
+}
+
+extern "C" int gss_mvdr_online_hold_init(gss_ctx *ctx, gss_mvdr_online_hold *hold) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_mvdr_online_hold_init";
+    GSS_REQUIRE(ctx, hold, GSS_ERR_INVALID, "%s: hold is NULL", what);
+    GSS_REQUIRE(ctx, hold->F >= 1, GSS_ERR_INVALID, "%s: F = %d is smaller than 1", what, (int)hold->F);
+    GSS_REQUIRE(ctx, hold->D >= 1 && hold->D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
+                "%s: D = %d outside [1, %d]", what, (int)hold->D, GSS_MAX_CHANNELS);
+    gss_mvdr_online_hold probe = *hold;
+    probe.held = 0;
+    GSS_TRY(check_mvdr_online_holds(ctx, what, &probe, 1, hold->F, hold->D));
+    return mvdr_online_hold_init_run(ctx, hold);
+}
+
+extern "C" int gss_mvdr_online_lookahead(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T, int D,
+                                         const double *mx, const double *mn, int ban,
+                                         const gss_bf_online *cfg, gss_mvdr_online_state *state,
+                                         gss_mvdr_online_hold *hold, gss_cplx *Xhat, gss_cplx *W,
+                                         int64_t *frames_out) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_mvdr_online_lookahead";
+    GSS_REQUIRE(ctx, Y, GSS_ERR_INVALID, "%s: Y_dev is NULL", what);
+    GSS_REQUIRE(ctx, mx, GSS_ERR_INVALID, "%s: mask_x_dev is NULL", what);
+    GSS_REQUIRE(ctx, mn, GSS_ERR_INVALID, "%s: mask_n_dev is NULL", what);
+    GSS_REQUIRE(ctx, F >= 1, GSS_ERR_INVALID, "%s: F = %d is smaller than 1", what, F);
+    GSS_REQUIRE(ctx, T >= 0, GSS_ERR_INVALID, "%s: T = %lld is negative", what, (long long)T);
+    GSS_TRY(check_bf_online(ctx, what, cfg, D));
+    GSS_TRY(check_lookahead_ref(ctx, what, cfg));
+    GSS_REQUIRE(ctx, state, GSS_ERR_INVALID, "%s: state is NULL, a delay line needs the caller's",
+                what);
+    GSS_TRY(check_mvdr_online_state(ctx, what, state, F, D));
+    GSS_TRY(check_mvdr_online_holds(ctx, what, hold, 1, F, D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
+    const int64_t R = mvdr_online_lookahead_rows(hold, T);
+    GSS_REQUIRE(ctx, Xhat || R == 0, GSS_ERR_INVALID, "%s: Xhat_dev is NULL", what);
+    if (frames_out) *frames_out = R;
+    if (T == 0) return GSS_OK;
+    GSS_TRY(arena_reserve(ctx, mvdr_online_lookahead_workspace_bytes(F, 1)));
+    return mvdr_online_lookahead_run(ctx, reinterpret_cast<const cplx *>(Y), F, T, D, mx, mn,
+                                     ban != 0, cfg->forget, cfg->ref_channel,
+                                     reinterpret_cast<cplx *>(state->phi_x),
+                                     reinterpret_cast<cplx *>(state->phi_n), hold,
+                                     reinterpret_cast<cplx *>(Xhat), reinterpret_cast<cplx *>(W));
+}
+
+extern "C" int gss_mvdr_online_lookahead_targets(gss_ctx *ctx, const gss_cplx *Y, int F, int64_t T,
+                                                 int D, const double *gamma, int K,
+                                                 const int32_t *targets, int S, int ban,
+                                                 const gss_bf_online *cfg,
+                                                 const gss_mvdr_online_state *states,
+                                                 gss_mvdr_online_hold *holds, int postfilter,
+                                                 double *mx, double *mn, gss_cplx *Xhat, gss_cplx *W,
+                                                 int64_t *frames_out) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_mvdr_online_lookahead_targets";
+    GSS_REQUIRE(ctx, Y, GSS_ERR_INVALID, "%s: Y_dev is NULL", what);
+    GSS_REQUIRE(ctx, gamma, GSS_ERR_INVALID, "%s: gamma_dev is NULL", what);
+    GSS_REQUIRE(ctx, T >= 0, GSS_ERR_INVALID, "%s: T = %lld is negative", what, (long long)T);
+    GSS_REQUIRE(ctx, postfilter == 0 || postfilter == 1, GSS_ERR_INVALID, "%s: postfilter = %d", what,
+                postfilter);
+    GSS_TRY(check_em_online_shape(ctx, what, F, K, D));
+    GSS_TRY(check_bf_online(ctx, what, cfg, D));
+    GSS_TRY(check_lookahead_ref(ctx, what, cfg));
+    GSS_TRY(check_online_targets(ctx, what, targets, S, K, states, F, D));
+    GSS_TRY(check_mvdr_online_holds(ctx, what, holds, S, F, D));
+    GSS_TRY(check_stft_bins(ctx, F, T, D));
+    const int64_t R = mvdr_online_lookahead_rows(holds, T);
+    GSS_REQUIRE(ctx, Xhat || R == 0, GSS_ERR_INVALID, "%s: Xhat_dev is NULL", what);
+    GSS_REQUIRE(ctx, !W || (int64_t)S * F * R * D < (1LL << 31), GSS_ERR_UNSUPPORTED,
+                "%s: S * F * R * D is 2^31 or more", what);
+    if (frames_out) *frames_out = R;
+    if (T == 0) return GSS_OK;
+    GSS_TRY(arena_reserve(ctx, mvdr_online_lookahead_workspace_bytes(F, S)));
+    ctx->last_online_targets = S;
+    const OnlineTargetStates st(states, S);
+    return mvdr_online_lookahead_targets_run(
+        ctx, reinterpret_cast<const cplx *>(Y), F, T, D, gamma, K, targets, S, ban != 0, cfg->forget,
+        cfg->ref_channel, st.phi_x, st.phi_n, holds, postfilter, mx, mn,
+        reinterpret_cast<cplx *>(Xhat), R, reinterpret_cast<cplx *>(W), nullptr);
+}
+
+extern "C" int gss_mvdr_online_release(gss_ctx *ctx, gss_mvdr_online_hold *holds, int S,
+                                       int postfilter, gss_cplx *Xhat, gss_cplx *W,
+                                       int64_t *frames_out) {
+    GSS_ENTER(ctx);
+    const char *const what = "gss_mvdr_online_release";
+    GSS_REQUIRE(ctx, S >= 1 && S <= GSS_CACGMM_ONLINE_MAX_CLASSES, GSS_ERR_INVALID,
+                "%s: S = %d outside [1, %d]", what, S, GSS_CACGMM_ONLINE_MAX_CLASSES);
+    GSS_REQUIRE(ctx, postfilter == 0 || postfilter == 1, GSS_ERR_INVALID, "%s: postfilter = %d", what,
+                postfilter);
+    GSS_REQUIRE(ctx, holds, GSS_ERR_INVALID, "%s: hold is NULL", what);
+    GSS_REQUIRE(ctx, holds[0].F >= 1, GSS_ERR_INVALID, "%s: F = %d is smaller than 1", what,
+                (int)holds[0].F);
+    GSS_REQUIRE(ctx, holds[0].D >= 1 && holds[0].D <= GSS_MAX_CHANNELS, GSS_ERR_UNSUPPORTED,
+                "%s: D = %d outside [1, %d]", what, (int)holds[0].D, GSS_MAX_CHANNELS);
+    GSS_TRY(check_mvdr_online_holds(ctx, what, holds, S, holds[0].F, holds[0].D));
+    const int64_t h = holds[0].held;
+    GSS_REQUIRE(ctx, Xhat || h == 0, GSS_ERR_INVALID, "%s: Xhat_dev is NULL", what);
+    if (frames_out) *frames_out = h;
+    return mvdr_online_release_run(ctx, holds, S, postfilter, reinterpret_cast<cplx *>(Xhat), h,
+                                   reinterpret_cast<cplx *>(W));
+}
+
+// The buffers of a look-ahead block: those of stream_block_blocks for the block's Tn frames, but
+// Xhat holds the rows the block RELEASES (at most Tn + L per target).
+static StreamBlockBuffers stream_lookahead_blocks(Workspace &ws, bool wpe, bool guided, bool masks,
+                                                  int F, int64_t Tn, int64_t rows, int D, int K,
+                                                  int S) {
+    const size_t ft = (size_t)F * Tn;
+    StreamBlockBuffers b{};
+    if (Tn > 0) {
+        b.Y = ws.take<cplx>(ft * D, "stream Y");
+        b.X = wpe ? ws.take<cplx>(ft * D, "stream X") : b.Y;
+        b.actf = guided ? ws.take<uint8_t>((size_t)K * Tn, "stream frame activity") : nullptr;
+        b.gamma = ws.take<double>(ft * K, "stream gamma");
+        b.mx = masks ? ws.take<double>(ft * S, "stream target masks") : nullptr;
+        b.mn = masks ? ws.take<double>(ft * S, "stream distortion masks") : nullptr;
+    }
+    b.Xhat = rows > 0 ? ws.take<cplx>((size_t)F * rows * S, "stream Xhat released") : nullptr;
+    b.ref = ws.take<int32_t>(GSS_CACGMM_ONLINE_MAX_CLASSES, "stream refs");
+    return b;
+}
+
+extern "C" int gss_stream_block_lookahead(gss_ctx *ctx, const gss_params *p, const gss_stream_cfg *cfg,
+                                          gss_stream_state *st, const gss_wpe_online_state *wpe,
+                                          gss_cacgmm_online_state *em,
+                                          const gss_mvdr_online_state *states,
+                                          gss_mvdr_online_hold *holds, double *tails, const void *x,
+                                          int in_type, const uint8_t *act, int64_t n,
+                                          const int32_t *targets, int S, int release, double *out,
+                                          int64_t *samples_out, const gss_debug_taps *taps) {
+    GSS_ENTER_VARIANTS(ctx);
+    const char *const what = "gss_stream_block_lookahead";
+    GSS_TRY(check_stream_block_head(ctx, what, p, cfg, st, em, states, x, in_type, act, n, out));
+    GSS_REQUIRE(ctx, tails, GSS_ERR_INVALID, "%s: tails_dev is NULL", what);
+    GSS_REQUIRE(ctx, tails != st->ola_tail, GSS_ERR_INVALID,
+                "%s: tails_dev is the stream state's own ola_tail", what);
+    GSS_REQUIRE(ctx, release == 0 || release == 1, GSS_ERR_INVALID, "%s: release = %d", what, release);
+    const int D = st->D, K = em->K, F = p->stft_size / 2 + 1;
+    GSS_TRY(check_online_targets(ctx, what, targets, S, K, states, F, D));
+    GSS_TRY(check_mvdr_online_holds(ctx, what, holds, S, F, D));
+    GSS_TRY(check_stream_block_tail(ctx, what, p, cfg, st, wpe));
+    const bool guided = act != nullptr;
+    const int64_t Tn = gss_stream_num_frames(st->received, n, p->stft_size, p->stft_shift);
+    const int64_t R = mvdr_online_lookahead_rows(holds, Tn);
+    const int64_t after = std::min<int64_t>(holds[0].L, (int64_t)holds[0].held + Tn);
+    const int64_t rows = R + (release ? after : 0);
+    GSS_REQUIRE(ctx, (int64_t)S * (Tn + rows) < 2147483647, GSS_ERR_UNSUPPORTED,
+                "%s: too many frames", what);
+    if (samples_out)
+        *samples_out = gss_stream_num_samples_out(st->frames_out * (int64_t)p->stft_shift,
+                                                  rows * (int64_t)p->stft_shift, p->stft_size,
+                                                  p->stft_shift);
+    if (n == 0 && rows == 0) return GSS_OK;
+
+    const bool masks = taps && (taps->target_mask || taps->distortion_mask);
+    {
+        size_t stage = stream_stft_workspace_bytes(Tn, D, guided ? K : 0, p->stft_size, p->stft_shift);
+        Workspace ws;
+        stream_lookahead_blocks(ws, p->wpe != 0, guided, masks, F, Tn, rows, D, K, S);
+        if (Tn > 0) {
+            if (p->wpe)
+                stage = std::max(stage, wpe_online_workspace_bytes(F, Tn, wpe_arrays_of(p),
+                                                                   D / wpe_arrays_of(p), p->wpe_taps,
+                                                                   p->wpe_delay, false));
+            stage = std::max(stage, cacgmm_online_workspace_bytes(F, K, D, false));
+            stage = std::max(stage, mvdr_online_lookahead_workspace_bytes(F, S));
+        }
+        stage = std::max(stage, stream_istft_targets_workspace_bytes(rows, S, p->stft_size, p->stft_shift));
+        GSS_TRY(arena_reserve(ctx, ws.bytes + 4096 + stage + (1 << 16)));
+    }
+    if (Tn > 0) ctx->last_online_targets = S;
+    Workspace ws(ctx);
+    const StreamBlockBuffers b =
+        stream_lookahead_blocks(ws, p->wpe != 0, guided, masks, F, Tn, rows, D, K, S);
+    GSS_TRY(ws.status(what));
+    const size_t mark = ctx->arena_off;
+    if (Tn == 0 && n > 0) {   // the samples enter the history, no frame is complete yet
+        GSS_TRY(stream_stft_run(ctx, x, in_type, act, n, st, nullptr, nullptr));
+        GSS_TRY(arena_release(ctx, mark));
+    }
+    if (Tn > 0) {
+        GSS_TRY(stream_block_front(ctx, p, cfg, st, wpe, em, x, in_type, act, n, Tn, b, mark));
+        const OnlineTargetStates bf(states, S);
+        GSS_TRY(mvdr_online_lookahead_targets_run(ctx, b.X, F, Tn, D, b.gamma, K, targets, S,
+                                                  /*ban=*/1, cfg->bf_forget, cfg->ref_channel,
+                                                  bf.phi_x, bf.phi_n, holds, p->postfilter == 1, b.mx,
+                                                  b.mn, b.Xhat, rows, nullptr, b.ref));
+        GSS_TRY(arena_release(ctx, mark));
+    }
+    if (release)
+        GSS_TRY(mvdr_online_release_run(ctx, holds, S, p->postfilter == 1,
+                                        b.Xhat ? b.Xhat + (size_t)R * F : nullptr, rows, nullptr));
+    if (rows > 0) GSS_TRY(stream_istft_targets_run(ctx, b.Xhat, rows, S, st, tails, out));
+    if (taps) {
+        const size_t ft = (size_t)F * Tn;
+        if (Tn > 0) {
+            GSS_TRY(copy_tap(ctx, taps->Obs_ftd, b.X, sizeof(cplx) * ft * D));
+            if (guided) GSS_TRY(copy_tap(ctx, taps->act_frames, b.actf, (size_t)K * Tn));
+            GSS_TRY(copy_tap(ctx, taps->gamma, b.gamma, sizeof(double) * ft * K));
+            GSS_TRY(copy_tap(ctx, taps->target_mask, b.mx, sizeof(double) * ft * S));
+            GSS_TRY(copy_tap(ctx, taps->distortion_mask, b.mn, sizeof(double) * ft * S));
+            GSS_TRY(copy_tap(ctx, taps->ref_channel, b.ref, sizeof(int32_t) * S));
+        }
+        if (rows > 0) GSS_TRY(copy_tap(ctx, taps->Xhat, b.Xhat, sizeof(cplx) * F * rows * S));
+    }
+    return GSS_OK;
 }

@@ -634,6 +634,27 @@ int mvdr_online_targets_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D
                             double beta, int ref, cplx *const *phi_x, cplx *const *phi_n,
                             int postfilter, double *mx, double *mn, cplx *X, cplx *W,
                             int32_t *ref_out);
+// Look-ahead L (gss_mvdr_online_lookahead*): the two calls above with frame g filtered by the
+// filter of frame g + L through the caller's delay line(s).  A call of T >= 1 frames writes
+// R = mvdr_online_lookahead_rows() rows: X (F,R) and W (F,R,D) of the masks form, rows [0, R) of
+// every target of X (S,Xrows,F) and W (S,F,R,D) of the posteriors form.  release: the held frames
+// with the last filter -> rows [0, held) of X (S,Xrows,F), W (S,F,held,D); the sums untouched.
+// The runs advance the lines' host counter `held`.  The fallback frames go where the calls above
+// leave them.  The S lines have the call's F, D, one L and one `held` (validated by the entry).
+size_t mvdr_online_lookahead_workspace_bytes(int F, int S);
+int64_t mvdr_online_lookahead_rows(const gss_mvdr_online_hold *hold, int64_t T);
+int mvdr_online_hold_init_run(gss_ctx *ctx, gss_mvdr_online_hold *hold);
+int mvdr_online_lookahead_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
+                              const double *mn, int ban, double beta, int ref, cplx *phi_x,
+                              cplx *phi_n, gss_mvdr_online_hold *hold, cplx *X, cplx *W);
+int mvdr_online_lookahead_targets_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
+                                      const double *gamma, int K, const int32_t *targets, int S,
+                                      int ban, double beta, int ref, cplx *const *phi_x,
+                                      cplx *const *phi_n, gss_mvdr_online_hold *holds, int postfilter,
+                                      double *mx, double *mn, cplx *X, int64_t Xrows, cplx *W,
+                                      int32_t *ref_out);
+int mvdr_online_release_run(gss_ctx *ctx, gss_mvdr_online_hold *holds, int S, int postfilter, cplx *X,
+                            int64_t Xrows, cplx *W);
 
 // Online CACGMM (cacgmm_online.hip; include/gss_hip.h: gss_cacgmm_online).  Y (F,T,D), the mask of
 // `guide` (its initialisation is not read) -> gamma (F,K,T); S (F,K,D,D), n (F,K) the caller's

@@ -7,7 +7,8 @@
 //   frame is counted, the update above stays)
 //   w = (Phi_N^-1 Phi_X)[:, ref] / max(Re trace(Phi_N^-1 Phi_X), 1e-10)
 //   ban:  v = Phi_N w,  w <- w sqrt(v^H v) / |w^H v|   (w^H v = 0, a zero filter: w stays 0)
-//   X[f,t] = w^H y                       (the sums include frame t: causal, no look-ahead)
+//   X[f,t] = w^H y                       (the sums include frame t: look-ahead L, default 0 --
+//                                         L >= 1: the look-ahead kernels further down)
 // Only the two running sums are a recurrence in time, but the factorisation of frame t needs the
 // sums of frame t, so one persistent wave per frequency walks the frames of the call with both
 // matrices in LDS.  Per frame: the rank-one update on the 8 x 8 lane grid, chol_inverse_sweep
@@ -22,10 +23,63 @@
 // commute with conjugation (c_outer, real scalings), so the lower triangle stays the exact
 // conjugate of the upper one and the diagonal exactly real.  No floating-point atomics.
 //
-// The frame is written once, mol_frame<NR>; the two kernels below are the I/O around it.
+// The frame is written once, mol_frame<NR>; the kernels below are the I/O around it.
 #include "dense_wave.h"
 
 namespace {
+
+// ---- look-ahead L (gss_mvdr_online_lookahead*) --------------------------
+// Frame g is filtered with the filter of frame g + L.  mol_frame takes the frame that enters the
+// sums from LDS (s.yb) and the frame the filter is applied to as a register argument, so with
+// L > 0 the two kernels hand it two different frames and the frame body, the sums and every filter
+// keep their bits.  A wave then walks the sequence "the h frames the line holds, then the T frames
+// of the call": at step t frame t of the call enters, element j = h + t - L of the sequence is
+// filtered into output row j (j < 0: the line is still filling, the result is dropped).
+//
+// The line of one (target, frequency): the held frames (L, D) oldest first, their target-mask
+// values (L) and the filter of the last frame that entered (D).  Every wave reads and writes only
+// its own line.
+struct MolHold {
+    cplx *frames;    // (F, L, D)
+    double *mask;    // (F, L)
+    cplx *filter;    // (F, D)
+};
+
+struct MolLine {
+    const cplx *Yf;      // the call's frames of this frequency (T, D)
+    const double *mf;    // their target-mask values (T)
+    cplx *Hf;            // the held frames (L, D)
+    double *hm;          // their target-mask values (L)
+    cplx *wl;            // the last filter (D)
+    int64_t T;
+    int h, L, D;
+    __device__ __forceinline__ cplx frame(int64_t i, int lane) const {
+        return i < h ? Hf[i * D + lane] : Yf[(i - h) * D + lane];
+    }
+    __device__ __forceinline__ double mask(int64_t i) const { return i < h ? hm[i] : mf[i - h]; }
+};
+
+// After the call's frames: the last filter, and the new line -- the last n = min(L, h + T)
+// elements of the sequence.  With T < L the line shifts in place: slot i takes element
+// i + (h + T - n) >= i, every lane moves its own channel in ascending i (lane 0 the mask values),
+// so a value is read before its slot is written.
+__device__ __forceinline__ void mol_line_store(const MolLine &q, cplx w, int lane) {
+    const int64_t total = q.h + q.T;
+    const int n = (int)(total < q.L ? total : q.L);
+    const int64_t base = total - n;
+    if (lane < q.D) {
+        q.wl[lane] = w;
+        for (int i = 0; i < n; ++i) {
+            const cplx v = q.frame(base + i, lane);
+            q.Hf[i * q.D + lane] = v;
+        }
+    }
+    if (lane == 0)
+        for (int i = 0; i < n; ++i) {
+            const double v = q.mask(base + i);
+            q.hm[i] = v;
+        }
+}
 
 struct MolArgs {
     const cplx *Y;           // (F, T, D)
@@ -41,6 +95,9 @@ struct MolArgs {
     int64_t T;
     int D, ref, ban;
     double beta;
+    MolHold hold;            // the delay line; read only with L > 0
+    int64_t R;               // rows of W per frequency: T without a look-ahead
+    int L, held;             // the look-ahead and the frames the line holds; L = 0: none
 };
 
 // p_f = mean |Y[f]|^2 over the T D values handed in (1 when there are none or the mean is 0),
@@ -217,10 +274,14 @@ __device__ __forceinline__ bool mol_frame(const MolLds<NR> &s, cplx y, double ma
 
 // One wave per frequency.  The masks are the caller's, X is strided, the reference channel may
 // come from a whole-window pass (ref_dev; none found: NaN, the state untouched).  y and the two
-// mask values of frame t + 1 are fetched while frame t's dependent chain runs.
-template <int NR>
-__global__ __launch_bounds__(64) void mvdr_online_kernel(MolArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// mask values of frame t + 1 are fetched while frame t's dependent chain runs.  With a look-ahead
+// (L > 0) the frame that enters and the frame the filter is applied to differ: the second one,
+// element j + 1 of the line's sequence, has an address known a step ahead and is fetched beside
+// the first, off the dependent chain.  The walk is compiled twice, LOOK = false being the loop
+// without a line -- one frame fetched, the filter applied to it, no row index, no line -- and the
+// kernel picks one by a.L, the same in every wave of the grid.
+template <int NR, bool LOOK>
+__device__ __forceinline__ void mol_walk(const MolArgs &a, char *smem) {
     const int D = a.D;
     const MolLds<NR> s(smem, D);
     const int f = blockIdx.x, lane = threadIdx.x;
@@ -231,8 +292,11 @@ __global__ __launch_bounds__(64) void mvdr_online_kernel(MolArgs a) {
     const cplx *Yf = a.Y + (int64_t)f * T * D;
     const double *mxf = a.mx + (int64_t)f * T, *mnf = a.mn + (int64_t)f * T;
     cplx *Xf = a.X + (int64_t)f * a.xs_f;
-    cplx *Wf = a.W ? a.W + (int64_t)f * T * D : nullptr;
+    cplx *Wf = a.W ? a.W + (int64_t)f * a.R * D : nullptr;
     cplx *gx = a.phi_x + (int64_t)f * D * D, *gn = a.phi_n + (int64_t)f * D * D;
+    const int L = LOOK ? a.L : 0, h = LOOK ? a.held : 0;
+    const MolLine q{Yf, mxf, a.hold.frames + (int64_t)f * L * D, a.hold.mask + (int64_t)f * L,
+                    a.hold.filter + (int64_t)f * D, T, h, L, D};   // LOOK only
 
     const int ref = a.ref_dev ? a.ref_dev[0] : a.ref;
     if (f == 0 && lane == 0) {
@@ -251,27 +315,54 @@ __global__ __launch_bounds__(64) void mvdr_online_kernel(MolArgs a) {
     wave_sync();
 
     const double beta = a.beta;
-    cplx y_next = row ? Yf[lane] : zero;
+    int64_t j = (int64_t)h - L;      // LOOK: the element of the sequence step t filters
+    cplx y_next = zero;
+    if (row) y_next = Yf[lane];
+    cplx d_next = zero;              // LOOK: the delayed frame
+    if constexpr (LOOK)
+        if (row && j >= 0) d_next = q.frame(j, lane);
     double ma_next = mxf[0], mb_next = mnf[0];
     int nfall = 0;
+    cplx wl = zero;                  // LOOK: the last filter
     for (int64_t t = 0; t < T; ++t) {
-        const cplx y = y_next;
+        const cplx e = y_next;
         const double ma = ma_next, mb = mb_next;
-        if (row) s.yb[lane] = y;
+        if (row) s.yb[lane] = e;
         if (t + 1 < T) {
             if (row) y_next = Yf[(t + 1) * D + lane];
             ma_next = mxf[t + 1];
             mb_next = mnf[t + 1];
         }
-        wave_sync();
         cplx w, x;
-        if (!mol_frame<NR>(s, y, ma, mb, beta, ref, a.ban, D, lane, tx, ty, w, x)) ++nfall;
-        if (lane == 0) Xf[t * a.xs_t] = x;
-        if (Wf && row) Wf[t * D + lane] = w;
+        if constexpr (LOOK) {
+            const cplx y = d_next;
+            if (t + 1 < T && row && j + 1 >= 0) d_next = q.frame(j + 1, lane);
+            wave_sync();
+            if (!mol_frame<NR>(s, y, ma, mb, beta, ref, a.ban, D, lane, tx, ty, w, x)) ++nfall;
+            if (j >= 0) {            // j < 0: the line is still filling, the result is dropped
+                if (lane == 0) Xf[j * a.xs_t] = x;
+                if (Wf && row) Wf[j * D + lane] = w;
+            }
+            wl = w;
+            ++j;
+        } else {
+            wave_sync();
+            if (!mol_frame<NR>(s, e, ma, mb, beta, ref, a.ban, D, lane, tx, ty, w, x)) ++nfall;
+            if (lane == 0) Xf[t * a.xs_t] = x;
+            if (Wf && row) Wf[t * D + lane] = w;
+        }
     }
     wave_sync();
     mol_store<NR>(s, gx, gn, D, lane);
+    if constexpr (LOOK) mol_line_store(q, wl, lane);
     if (lane == 0 && nfall) atomicAdd(a.fallbacks, nfall);
+}
+
+template <int NR>
+__global__ __launch_bounds__(64) void mvdr_online_kernel(MolArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (a.L > 0) mol_walk<NR, true>(a, smem);
+    else mol_walk<NR, false>(a, smem);
 }
 
 // S targets of one stream (gss_mvdr_online_targets).
@@ -289,6 +380,10 @@ struct MolTargetsArgs {
     int64_t T;
     int F, D, K, ref, ban, postfilter;
     double beta;
+    MolHold hold[GSS_CACGMM_ONLINE_MAX_CLASSES];   // the delay lines; read only with L > 0
+    int64_t R, Xrows;        // rows of W, and of X, per target: T without a look-ahead
+    int L, held;             // the look-ahead and the frames every line holds; L = 0: none
+    int release;             // the end of the lines: nothing enters, the held frames leave
 };
 
 // grid (F, S): one wave per (frequency, target), no LDS and no barrier shared between the waves
@@ -297,10 +392,12 @@ struct MolTargetsArgs {
 // the posteriors -- a = gamma[target], b = the sum over k != target in ascending k from 0.0,
 // masks_kernel's expressions --, whose K values of frame t + 1 are fetched while frame t's chain
 // runs; the postfilter 'mask_mul' (re a, im a: mask_mul_kernel's product) is applied to the
-// stored value; X is (S, T, F); every wave has a count word of its own.
-template <int NR>
-__global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// stored value; X is (S, T, F); every wave has a count word of its own.  With a look-ahead the
+// walk is mvdr_online_kernel's, the postfilter takes the target mask the line carries with the
+// output frame, and X is (S, Xrows, F); `release` ends the lines: nothing enters and no sum is
+// touched, the held frames leave with the filter of the last frame that entered.
+template <int NR, bool LOOK>
+__device__ __forceinline__ void mol_walk_targets(const MolTargetsArgs &a, char *smem) {
     constexpr int KMAX = GSS_CACGMM_ONLINE_MAX_CLASSES;
     const int D = a.D, K = a.K, F = a.F;
     const MolLds<NR> l(smem, D);
@@ -314,8 +411,25 @@ __global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs 
     const double *gf = a.gamma + (int64_t)f * K * T;
     const int64_t sf = (int64_t)s * F + f;
     double *mxf = a.mx ? a.mx + sf * T : nullptr, *mnf = a.mn ? a.mn + sf * T : nullptr;
-    cplx *Xs = a.X + (int64_t)s * T * F + f;
-    cplx *Wf = a.W ? a.W + sf * T * D : nullptr;
+    cplx *Xs = a.X + (int64_t)s * a.Xrows * F + f;
+    cplx *Wf = a.W ? a.W + sf * a.R * D : nullptr;
+    const int L = LOOK ? a.L : 0, h = LOOK ? a.held : 0;
+    const MolHold &line = a.hold[LOOK ? s : 0];                     // LOOK only
+    const MolLine q{Yf, gf + (int64_t)target * T, line.frames + (int64_t)f * L * D,
+                    line.mask + (int64_t)f * L, line.filter + (int64_t)f * D, T, h, L, D};
+    if (LOOK && a.release) {   // the held frames with the last filter: mol_frame's product and sum
+        cplx w = zero;
+        if (row) w = q.wl[lane];
+        for (int i = 0; i < h; ++i) {
+            cplx y = zero, p = zero;
+            if (row) y = q.Hf[i * D + lane];
+            c_cfma(p, w, y);
+            const cplx x = c_make(wave_sum(p.x), wave_sum(p.y));
+            if (lane == 0) Xs[(int64_t)i * F] = a.postfilter ? c_scale(x, q.hm[i]) : x;
+            if (Wf && row) Wf[i * D + lane] = w;
+        }
+        return;
+    }
     cplx *gx = a.phi_x[s] + (int64_t)f * D * D, *gn = a.phi_n[s] + (int64_t)f * D * D;
 
     if (f == 0 && lane == 0) {
@@ -327,13 +441,23 @@ __global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs 
     wave_sync();
 
     const double beta = a.beta;
-    cplx y_next = row ? Yf[lane] : zero;
+    int64_t j = (int64_t)h - L;      // LOOK: the element of the sequence step t filters
+    cplx y_next = zero;
+    if (row) y_next = Yf[lane];
+    cplx d_next = zero;              // LOOK: the delayed frame and its target mask
+    double p_next = 0.0;
+    if constexpr (LOOK)
+        if (j >= 0) {
+            if (row) d_next = q.frame(j, lane);
+            p_next = q.mask(j);
+        }
     double g_next[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) g_next[k] = k < K ? gf[(int64_t)k * T] : 0.0;
     int nfall = 0;
+    cplx wl = zero;                  // LOOK: the last filter
     for (int64_t t = 0; t < T; ++t) {
-        const cplx y = y_next;
+        const cplx e = y_next;
         double ma = 0.0, mb = 0.0;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k)
@@ -341,26 +465,54 @@ __global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs 
                 if (k == target) ma = g_next[k];
                 else mb += g_next[k];
             }
-        if (row) l.yb[lane] = y;
+        if (row) l.yb[lane] = e;
         if (t + 1 < T) {
             if (row) y_next = Yf[(t + 1) * D + lane];
 #pragma unroll
             for (int k = 0; k < KMAX; ++k)
                 if (k < K) g_next[k] = gf[(int64_t)k * T + t + 1];
         }
-        wave_sync();
         cplx w, x;
-        if (!mol_frame<NR>(l, y, ma, mb, beta, ref, a.ban, D, lane, tx, ty, w, x)) ++nfall;
-        if (lane == 0) {
-            Xs[t * F] = a.postfilter ? c_scale(x, ma) : x;
-            if (mxf) mxf[t] = ma;
-            if (mnf) mnf[t] = mb;
+        if constexpr (LOOK) {
+            const cplx y = d_next;
+            const double pm = p_next;
+            if (t + 1 < T && j + 1 >= 0) {
+                if (row) d_next = q.frame(j + 1, lane);
+                p_next = q.mask(j + 1);
+            }
+            wave_sync();
+            if (!mol_frame<NR>(l, y, ma, mb, beta, ref, a.ban, D, lane, tx, ty, w, x)) ++nfall;
+            if (lane == 0) {
+                // the postfilter takes the target mask of the OUTPUT frame j, which the line carries
+                if (j >= 0) Xs[j * F] = a.postfilter ? c_scale(x, pm) : x;
+                if (mxf) mxf[t] = ma;
+                if (mnf) mnf[t] = mb;
+            }
+            if (Wf && row && j >= 0) Wf[j * D + lane] = w;
+            wl = w;
+            ++j;
+        } else {
+            wave_sync();
+            if (!mol_frame<NR>(l, e, ma, mb, beta, ref, a.ban, D, lane, tx, ty, w, x)) ++nfall;
+            if (lane == 0) {
+                Xs[t * F] = a.postfilter ? c_scale(x, ma) : x;
+                if (mxf) mxf[t] = ma;
+                if (mnf) mnf[t] = mb;
+            }
+            if (Wf && row) Wf[t * D + lane] = w;
         }
-        if (Wf && row) Wf[t * D + lane] = w;
     }
     wave_sync();
     mol_store<NR>(l, gx, gn, D, lane);
+    if constexpr (LOOK) mol_line_store(q, wl, lane);
     if (lane == 0) a.fallbacks[sf] = nfall;   // every wave writes its own word: no atomic, no memset
+}
+
+template <int NR>
+__global__ __launch_bounds__(64) void mvdr_online_targets_kernel(MolTargetsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (a.L > 0) mol_walk_targets<NR, true>(a, smem);
+    else mol_walk_targets<NR, false>(a, smem);
 }
 
 // counts (S, F) -> words[1 + s] = the sum over f of target s, words[0] = the sum over the targets.
@@ -472,7 +624,7 @@ int mvdr_online_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const 
         ref_dev = words + 1;
     }
     const MolArgs a{Y, mx, mn, phi_x, phi_n, X, xs_f, xs_t, W, ref_dev, words, ctx->status_dev,
-                    ref_out, T, D, ref, ban, beta};
+                    ref_out, T, D, ref, ban, beta, MolHold{}, T, 0, 0};
     {
         GSS_PROF(ctx, "mvdr_online");
         GSS_TRY(mol_launch(ctx, GSS_MOL_KERNELS(mvdr_online_kernel), dim3(F), D, a));
@@ -496,6 +648,19 @@ static MolTargetsWork mol_targets_blocks(Workspace &ws, int F, int S) {
     return k;
 }
 
+// the per-wave counts -> the context's status words: the sum where the one-target call leaves
+// its count, then one word per target
+static int mol_counts_to_status(gss_ctx *ctx, const MolTargetsWork &k, int F, int S) {
+    hipLaunchKernelGGL(mvdr_online_targets_count_kernel, dim3(1), dim3(256), 0, ctx->stream, k.counts,
+                       F, S, k.words);
+    GSS_LAUNCH_CHECK(ctx, "mvdr_online_targets_count_kernel");
+    GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_MVDR_ONLINE_FALLBACKS, k.words,
+                                      sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_MVDR_ONLINE_TARGETS, k.words + 1,
+                                      sizeof(int32_t) * S, hipMemcpyDeviceToHost, ctx->stream));
+    return GSS_OK;
+}
+
 size_t mvdr_online_targets_workspace_bytes(int F, int S) {
     Workspace ws;
     mol_targets_blocks(ws, F, S);
@@ -515,27 +680,118 @@ int mvdr_online_targets_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D
     Workspace ws(ctx);
     const MolTargetsWork k = mol_targets_blocks(ws, F, S);
     GSS_TRY(ws.status("online mvdr targets"));
-    int32_t *words = k.words;
     ctx->last_targets = 0;
     MolTargetsArgs a{};
     a.Y = Y, a.gamma = gamma, a.mx = mx, a.mn = mn, a.X = X, a.W = W;
     a.fallbacks = k.counts, a.status = ctx->status_dev, a.ref_out = ref_out;
     a.T = T, a.F = F, a.D = D, a.K = K, a.ref = ref, a.ban = ban, a.postfilter = postfilter;
-    a.beta = beta;
+    a.beta = beta, a.R = T, a.Xrows = T;
     for (int s = 0; s < S; ++s) a.phi_x[s] = phi_x[s], a.phi_n[s] = phi_n[s], a.target[s] = targets[s];
     {
         GSS_PROF(ctx, "mvdr_online_targets");
         GSS_TRY(mol_launch(ctx, GSS_MOL_KERNELS(mvdr_online_targets_kernel), dim3(F, S), D, a));
         GSS_LAUNCH_CHECK(ctx, "mvdr_online_targets_kernel");
-        hipLaunchKernelGGL(mvdr_online_targets_count_kernel, dim3(1), dim3(256), 0, ctx->stream,
-                           k.counts, F, S, words);
-        GSS_LAUNCH_CHECK(ctx, "mvdr_online_targets_count_kernel");
+        GSS_TRY(mol_counts_to_status(ctx, k, F, S));
     }
-    // the counts of this call -> the context's status words: the sum where the one-target call
-    // leaves its count, then one word per target
-    GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_MVDR_ONLINE_FALLBACKS, words,
+    return GSS_OK;
+}
+
+// ---- look-ahead: the runs ------------------------------------------------------------------
+size_t mvdr_online_lookahead_workspace_bytes(int F, int S) {
+    return mvdr_online_targets_workspace_bytes(F, S);
+}
+
+static MolHold mol_hold(const gss_mvdr_online_hold &h) {
+    return MolHold{reinterpret_cast<cplx *>(h.frames), h.mask, reinterpret_cast<cplx *>(h.filter)};
+}
+
+int64_t mvdr_online_lookahead_rows(const gss_mvdr_online_hold *hold, int64_t T) {
+    const int64_t r = (int64_t)hold->held + T - hold->L;
+    return r > 0 ? r : 0;
+}
+
+// the line's host counter after T more frames
+static void mol_hold_advance(gss_mvdr_online_hold *holds, int S, int64_t T) {
+    for (int s = 0; s < S; ++s) {
+        const int64_t total = (int64_t)holds[s].held + T;
+        holds[s].held = (int32_t)(total < holds[s].L ? total : holds[s].L);
+    }
+}
+
+int mvdr_online_hold_init_run(gss_ctx *ctx, gss_mvdr_online_hold *hold) {
+    const size_t F = (size_t)hold->F, L = (size_t)hold->L, D = (size_t)hold->D;
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(hold->frames, 0, sizeof(cplx) * F * L * D, ctx->stream));
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(hold->mask, 0, sizeof(double) * F * L, ctx->stream));
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(hold->filter, 0, sizeof(cplx) * F * D, ctx->stream));
+    hold->held = 0;
+    return GSS_OK;
+}
+
+int mvdr_online_lookahead_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D, const double *mx,
+                              const double *mn, int ban, double beta, int ref, cplx *phi_x,
+                              cplx *phi_n, gss_mvdr_online_hold *hold, cplx *X, cplx *W) {
+    Workspace ws(ctx);
+    const MolWork k = mol_blocks(ws, F, D, false);
+    GSS_TRY(ws.status("online mvdr look-ahead"));
+    ctx->last_targets = 0;
+    GSS_HIP_CHECK(ctx, hipMemsetAsync(k.words, 0, sizeof(int32_t) * 4, ctx->stream));
+    const int64_t R = mvdr_online_lookahead_rows(hold, T);
+    const MolArgs a{Y, mx, mn, phi_x, phi_n, X, R, 1, W, nullptr, k.words, ctx->status_dev, nullptr,
+                    T, D, ref, ban, beta, mol_hold(*hold), R, hold->L, hold->held};
+    {
+        GSS_PROF(ctx, "mvdr_online_lookahead");
+        GSS_TRY(mol_launch(ctx, GSS_MOL_KERNELS(mvdr_online_kernel), dim3(F), D, a));
+        GSS_LAUNCH_CHECK(ctx, "mvdr_online_kernel");
+    }
+    GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_MVDR_ONLINE_FALLBACKS, k.words,
                                       sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GSS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->status_host + GSS_STATUS_MVDR_ONLINE_TARGETS, words + 1,
-                                      sizeof(int32_t) * S, hipMemcpyDeviceToHost, ctx->stream));
+    mol_hold_advance(hold, 1, T);
+    return GSS_OK;
+}
+
+int mvdr_online_lookahead_targets_run(gss_ctx *ctx, const cplx *Y, int F, int64_t T, int D,
+                                      const double *gamma, int K, const int32_t *targets, int S,
+                                      int ban, double beta, int ref, cplx *const *phi_x,
+                                      cplx *const *phi_n, gss_mvdr_online_hold *holds, int postfilter,
+                                      double *mx, double *mn, cplx *X, int64_t Xrows, cplx *W,
+                                      int32_t *ref_out) {
+    Workspace ws(ctx);
+    const MolTargetsWork k = mol_targets_blocks(ws, F, S);
+    GSS_TRY(ws.status("online mvdr look-ahead targets"));
+    ctx->last_targets = 0;
+    MolTargetsArgs a{};
+    a.Y = Y, a.gamma = gamma, a.mx = mx, a.mn = mn, a.X = X, a.W = W;
+    a.fallbacks = k.counts, a.status = ctx->status_dev, a.ref_out = ref_out;
+    a.T = T, a.R = mvdr_online_lookahead_rows(holds, T), a.Xrows = Xrows;
+    a.F = F, a.D = D, a.K = K, a.ref = ref, a.ban = ban, a.postfilter = postfilter;
+    a.L = holds[0].L, a.held = holds[0].held, a.beta = beta;
+    for (int s = 0; s < S; ++s) {
+        a.phi_x[s] = phi_x[s], a.phi_n[s] = phi_n[s], a.target[s] = targets[s];
+        a.hold[s] = mol_hold(holds[s]);
+    }
+    {
+        GSS_PROF(ctx, "mvdr_online_lookahead_targets");
+        GSS_TRY(mol_launch(ctx, GSS_MOL_KERNELS(mvdr_online_targets_kernel), dim3(F, S), D, a));
+        GSS_LAUNCH_CHECK(ctx, "mvdr_online_targets_kernel");
+        GSS_TRY(mol_counts_to_status(ctx, k, F, S));
+    }
+    mol_hold_advance(holds, S, T);
+    return GSS_OK;
+}
+
+int mvdr_online_release_run(gss_ctx *ctx, gss_mvdr_online_hold *holds, int S, int postfilter, cplx *X,
+                            int64_t Xrows, cplx *W) {
+    const int h = holds[0].held;
+    if (h > 0) {
+        MolTargetsArgs a{};
+        for (int s = 0; s < S; ++s) a.hold[s] = mol_hold(holds[s]);
+        a.X = X, a.W = W, a.Xrows = Xrows, a.R = h;
+        a.F = holds[0].F, a.D = holds[0].D, a.L = holds[0].L, a.held = h, a.postfilter = postfilter;
+        a.release = 1;
+        GSS_PROF(ctx, "mvdr_online_release");
+        GSS_TRY(mol_launch(ctx, GSS_MOL_KERNELS(mvdr_online_targets_kernel), dim3(a.F, S), a.D, a));
+        GSS_LAUNCH_CHECK(ctx, "mvdr_online_targets_kernel");
+    }
+    for (int s = 0; s < S; ++s) holds[s].held = 0;
     return GSS_OK;
 }

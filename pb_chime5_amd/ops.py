@@ -62,7 +62,8 @@ import numpy as np
 from . import _capi
 from ._capi import (Context, GssBfLcmv, GssBfSegments, GssBfWpd, GssCacgmmModel,
                     GssCacgmmOnlineState, GssChannelSelect, GssEmOnline,
-                    GssBfOnline, GssDebugTaps, GssGuidance, GssMvdrOnlineState, GssParams,
+                    GssBfOnline, GssDebugTaps, GssGuidance, GssMvdrOnlineHold, GssMvdrOnlineState,
+                    GssParams,
                     GssStreamCfg, GssStreamState, GssWpeOnlineCfg, GssWpeOnlineState, c_void_p,
                     default_context)
 from .cacgmm import CACGMM
@@ -1276,6 +1277,203 @@ class OnlineMVDRState(_OnlineState):
         return cls._from_host(host, (F, D), ctx)
 
 
+BF_ONLINE_MAX_LOOKAHEAD = 64   # include/gss_hip.h: GSS_MVDR_ONLINE_MAX_LOOKAHEAD, a choice
+
+
+def check_bf_lookahead(lookahead=0, ref_channel=0):
+    """The look-ahead of the online MVDR -- the one place that validates it, before any device
+    work.  ValueError naming the argument: ``lookahead`` an integer in [0, 64]; with a look-ahead
+    ``ref_channel`` = -1 is refused (the whole-window choice is per call, a delay line outlives a
+    call).  Returns the look-ahead as an int."""
+    if not _is_integer(lookahead) or not 0 <= lookahead <= BF_ONLINE_MAX_LOOKAHEAD:
+        raise ValueError(f'lookahead={lookahead!r}: an integer in [0, {BF_ONLINE_MAX_LOOKAHEAD}]')
+    if lookahead > 0 and ref_channel == -1:
+        raise ValueError('ref_channel=-1 with lookahead > 0: the whole-window choice is per call, '
+                         'a delay line outlives a call')
+    return int(lookahead)
+
+
+class OnlineMVDRHold(_OnlineState):
+    """The delay line of the online MVDR's look-ahead in HBM (gss_mvdr_online_hold), caller-owned
+    and separate from the `OnlineMVDRState`: the held frames (F,L,D) oldest first, their
+    target-mask values (F,L), the filter of the last frame that entered (F,D), and the host counter
+    ``held`` in [0, L], which the calls advance."""
+    _sizes = 'F, D, L'
+    dtypes = {'mask': np.float64}
+
+    def __init__(self, ctx, F, D, L):
+        super().__init__(ctx, F, D, L)
+        self.F, self.D, self.L = self.key
+        self.held = 0
+
+    @staticmethod
+    def _shapes(F, D, L):
+        return {'frames': (F, L, D), 'mask': (F, L), 'filter': (F, D)}
+
+    def struct(self):
+        return GssMvdrOnlineHold(frames=self.bufs['frames'].ptr, mask=self.bufs['mask'].ptr,
+                                 filter=self.bufs['filter'].ptr, F=self.F, D=self.D, L=self.L,
+                                 held=self.held)
+
+    @classmethod
+    def fresh(cls, F, D, L, *, ctx=None):
+        """An empty line of zeros (gss_mvdr_online_hold_init)."""
+        if not _is_integer(F) or F < 1:
+            raise ValueError(f'F={F!r}: a positive integer')
+        check_bf_online(num_channels=D)
+        if check_bf_lookahead(L) < 1:
+            raise ValueError(f'lookahead={L!r}: a delay line holds at least one frame')
+        ctx = ctx or default_context()
+        hold = cls(ctx, F, D, L)
+        ctx._check(ctx.lib.gss_mvdr_online_hold_init(ctx.handle, ctypes.byref(hold.struct())),
+                   'gss_mvdr_online_hold_init')
+        return hold
+
+    def to_host(self):
+        """{'frames', 'mask', 'filter'} as NumPy arrays plus 'held': everything `from_host` needs
+        (synchronises)."""
+        return dict(super().to_host(), held=self.held)
+
+    @classmethod
+    def from_host(cls, host, *, ctx=None):
+        """A device line from the dict of `to_host` (in any context).  ValueError for shapes or a
+        counter that do not fit each other."""
+        frames = np.asarray(host['frames'])
+        if frames.ndim != 3:
+            raise ValueError(f'frames: shape {frames.shape} is not (F,L,D)')
+        F, L, D = frames.shape
+        if F < 1:
+            raise ValueError(f'frames: shape {frames.shape} has no frequency')
+        check_bf_online(num_channels=D)
+        if check_bf_lookahead(L) < 1:
+            raise ValueError(f'frames: shape {frames.shape} holds no frame')
+        held = host['held']
+        if not _is_integer(held) or not 0 <= held <= L:
+            raise ValueError(f'held={held!r}: an integer in [0, {L}]')
+        hold = cls._from_host(host, (F, D, L), ctx)
+        hold.held = int(held)
+        return hold
+
+
+def _check_holds(holds, S, key, ctx, name='hold'):
+    """S different `OnlineMVDRHold`s built for ``key`` = (F, D, L) that hold equally many frames,
+    all in ``ctx`` (None: the first one's).  Returns the context and the list."""
+    holds = [holds] if isinstance(holds, OnlineMVDRHold) else (
+        list(holds) if hasattr(holds, '__iter__') else None)
+    if holds is None or len(holds) != S:
+        raise ValueError(f'{name}: {S} OnlineMVDRHold, one per target')
+    for hold in holds:
+        if not isinstance(hold, OnlineMVDRHold):
+            raise ValueError(f'{name}: {type(hold).__name__} is not an OnlineMVDRHold')
+        if hold.key != key:
+            raise ValueError(f'{name}: built for ({hold._sizes}) = {hold.key}, the call has {key}')
+        if ctx is not None and ctx is not hold.ctx:
+            raise ValueError(f'{name}: it lives in another context than the call')
+        ctx = hold.ctx
+    if len({id(hold) for hold in holds}) != S:
+        raise ValueError(f'{name}: the same line for two targets')
+    if len({hold.held for hold in holds}) != 1:
+        raise ValueError(f'{name}: the lines hold {[hold.held for hold in holds]} frames')
+    return ctx, holds
+
+
+def _hold_structs(holds):
+    return (GssMvdrOnlineHold * len(holds))(*(hold.struct() for hold in holds))
+
+
+def _holds_advance(holds, structs):
+    """The host counters the library advanced -> the Python objects."""
+    for hold, struct in zip(holds, structs):
+        hold.held = int(struct.held)
+
+
+def mvdr_online_release(hold, *, postfilter=None, return_filters=False):
+    """The end of a delay line (gss_mvdr_online_release): the h held frames, filtered with the
+    filter of the last frame that entered -> (h,F) complex128 for one `OnlineMVDRHold`, (S,h,F)
+    for a sequence of S (times their own target-mask values with ``postfilter='mask_mul'``), then
+    with ``return_filters`` the filters (h,F,D) / (S,h,F,D).  The line is empty afterwards, the
+    running sums are not touched; with nothing held nothing is launched."""
+    single = isinstance(hold, OnlineMVDRHold)
+    if not single and (not hasattr(hold, '__len__') or len(hold) < 1
+                       or not isinstance(hold[0], OnlineMVDRHold)):
+        raise ValueError('hold: an OnlineMVDRHold or a sequence of them')
+    if postfilter not in (None, 'mask_mul'):
+        raise ValueError(f"postfilter={postfilter!r}: None or 'mask_mul'")
+    first = hold if single else hold[0]
+    S = 1 if single else len(hold)
+    ctx, holds = _check_holds(hold, S, first.key, None)
+    F, D, h = first.F, first.D, first.held
+    if h == 0:
+        X, W = np.zeros((S, 0, F), np.complex128), np.zeros((S, 0, F, D), np.complex128)
+    else:
+        structs = _hold_structs(holds)
+        X_d = ctx.empty(16 * S * h * F)
+        W_d = ctx.empty(16 * S * F * h * D) if return_filters else None
+        ctx._check(ctx.lib.gss_mvdr_online_release(
+            ctx.handle, structs, S, int(postfilter == 'mask_mul'), c_void_p(X_d.ptr),
+            c_void_p(W_d.ptr) if W_d is not None else None, None), 'gss_mvdr_online_release')
+        _holds_advance(holds, structs)
+        X = ctx.to_host(X_d, (S, h, F), np.complex128)
+        W = (np.ascontiguousarray(ctx.to_host(W_d, (S, F, h, D), np.complex128)
+                                  .transpose(0, 2, 1, 3)) if return_filters else None)
+    if single:
+        X, W = X[0], (W[0] if W is not None else None)
+    return (X, W) if return_filters else X
+
+
+def _mvdr_online_lookahead(Y, X_mask, N_mask, ban, forget, loading, ref_channel, L, state, hold,
+                           return_filters, return_fallbacks, ctx):
+    """`mvdr_souden_online_from_masks` with a look-ahead L >= 1 (gss_mvdr_online_lookahead)."""
+    D, T, F = Y.shape
+    one_shot = hold is None
+    if not one_shot:
+        if state is None:
+            raise ValueError('state: a delay line needs the state it belongs to (hold= without '
+                             'state=)')
+        ctx = _check_holds(hold, 1, (F, D, L), ctx)[0]
+    ctx = _state_context(state, OnlineMVDRState, (F, D), ctx) or default_context()
+    fallbacks = 0
+    if T == 0 or F == 0:
+        X_hat, W = np.zeros((0, F), np.complex128), np.zeros((0, F, D), np.complex128)
+    else:
+        if state is None:
+            state = OnlineMVDRState.fresh(F, D, loading, Y, ctx=ctx)
+        if one_shot:
+            hold = OnlineMVDRHold.fresh(F, D, L, ctx=ctx)
+        R = max(0, hold.held + T - L)
+        Y_d, _ = _obs_to_device_ftd(ctx, Y)
+        mx = _mask_to_device_ft(ctx, X_mask, T, F)
+        mn = _mask_to_device_ft(ctx, N_mask, T, F)
+        X_d = ctx.empty(max(16 * F * R, 16))
+        W_d = ctx.empty(max(16 * F * R * D, 16)) if return_filters else None
+        cfg = _bf_online_cfg(forget, loading, ref_channel)
+        struct = hold.struct()
+        ctx._check(ctx.lib.gss_mvdr_online_lookahead(
+            ctx.handle, c_void_p(Y_d.ptr), F, T, D, c_void_p(mx.ptr), c_void_p(mn.ptr),
+            int(bool(ban)), ctypes.byref(cfg), ctypes.byref(state.struct()), ctypes.byref(struct),
+            c_void_p(X_d.ptr), c_void_p(W_d.ptr) if W_d is not None else None, None),
+            'gss_mvdr_online_lookahead')
+        _holds_advance([hold], [struct])
+        if R:
+            X_hat = np.ascontiguousarray(ctx.to_host(X_d, (F, R), np.complex128).T)
+        else:
+            X_hat = np.zeros((0, F), np.complex128)
+        W = None
+        if return_filters:
+            W = (np.ascontiguousarray(ctx.to_host(W_d, (F, R, D), np.complex128).transpose(1, 0, 2))
+                 if R else np.zeros((0, F, D), np.complex128))
+        if return_fallbacks:
+            fallbacks = ctx.last_mvdr_online_fallbacks()
+        if one_shot:
+            tail = mvdr_online_release(hold, return_filters=return_filters)
+            if return_filters:
+                X_hat, W = np.concatenate([X_hat, tail[0]]), np.concatenate([W, tail[1]])
+            else:
+                X_hat = np.concatenate([X_hat, tail])
+    out = (X_hat,) + ((W,) if return_filters else ()) + ((fallbacks,) if return_fallbacks else ())
+    return out if len(out) > 1 else X_hat
+
+
 def _check_online_mask(mask, name, T, F):
     mask = np.asarray(mask, dtype=np.float64)
     if mask.shape != (T, F):
@@ -1287,24 +1485,39 @@ def _check_online_mask(mask, name, T, F):
 
 def mvdr_souden_online_from_masks(Y, X_mask, N_mask, ban=False, *, forget=BF_ONLINE_FORGET,
                                   loading=BF_ONLINE_LOADING, ref_channel=0, state=None,
-                                  return_filters=False, return_fallbacks=False, ctx=None):
+                                  return_filters=False, return_fallbacks=False, ctx=None,
+                                  lookahead=0, hold=None):
     """The online MVDR (gss_mvdr_online): Y (D,T,F), 2-D masks (T,F) -> X_hat (T,F) complex128.
     Both PSD matrices are running sums that forget at the rate ``forget``; the filter of frame t
-    is solved from the sums INCLUDING frame t (causal, no look-ahead).  ``state``: an
+    is solved from the sums INCLUDING frame t (look-ahead ``lookahead``, default 0).  ``state``: an
     `OnlineMVDRState` to continue from, advanced IN PLACE by the T frames (feeding a recording in
     blocks through one state gives the bits of one call); None: a fresh state initialised from
     ``Y`` with ``loading``, thrown away.  ``ref_channel`` = -1: the whole-window beamformer's
     choice over the call's frames (not causal; AssertionError when an SNR is not finite, like
     there).  Returns X_hat, then with ``return_filters`` the filters (T,F,D), then with
     ``return_fallbacks`` the number of (frequency, frame) pairs whose noise matrix had no Cholesky
-    factor (their X_hat and filter are 0)."""
+    factor (their X_hat and filter are 0).
+
+    ``lookahead`` = L >= 1 (gss_mvdr_online_lookahead): frame g is filtered with the filter of
+    frame g + L -- L frames of latency for a filter that has already seen what follows, a
+    speaker's onset above all; the sums, the filters and the fallback counts are those of L = 0.
+    ``hold`` None: the one-shot form, the call plus the release of its line -> (T,F), the last L
+    frames with the filter of frame T - 1.  ``hold``: an `OnlineMVDRHold` built for (F,D,L),
+    advanced IN PLACE with ``state`` (required): the call returns the max(0, held + T - L) frames
+    it releases, `mvdr_online_release` ends the line.  ``ref_channel`` = -1 is refused."""
     Y = np.asarray(Y)
     if Y.ndim != 3:
         raise ValueError(f'Y: shape {Y.shape} is not (D,T,F)')
     D, T, F = Y.shape
     forget, loading, ref_channel = check_bf_online(forget, loading, ref_channel, D)
+    lookahead = check_bf_lookahead(lookahead, ref_channel)
+    if hold is not None and lookahead == 0:
+        raise ValueError('hold: a delay line with lookahead=0')
     X_mask = _check_online_mask(X_mask, 'X_mask', T, F)
     N_mask = _check_online_mask(N_mask, 'N_mask', T, F)
+    if lookahead:
+        return _mvdr_online_lookahead(Y, X_mask, N_mask, ban, forget, loading, ref_channel,
+                                      lookahead, state, hold, return_filters, return_fallbacks, ctx)
     ctx = _state_context(state, OnlineMVDRState, (F, D), ctx) or default_context()
     fallbacks = 0
     if T == 0 or F == 0:
@@ -3367,14 +3580,19 @@ def _check_target_states(states, S, key, ctx, name='states'):
 
 def mvdr_souden_online_targets(Y, posterior, targets, *, states, forget=BF_ONLINE_FORGET,
                                ref_channel=0, ban=False, postfilter=None, return_fallbacks=False,
-                               return_filters=False):
+                               return_filters=False, lookahead=0, hold=None):
     """The online MVDR for S targets in one launch (gss_mvdr_online_targets): Y (D,T,F), the
     posteriors (K,T,F), ``targets`` S distinct class indices, ``states`` S `OnlineMVDRState`s,
     each advanced IN PLACE -> X_hat (S,T,F) complex128.  The masks are formed on the device as
     `masks_from_posteriors` forms them; row s has the bits of `mvdr_souden_online_from_masks` on
     the masks of class targets[s] with states[s] (times the target mask with
     ``postfilter='mask_mul'``).  Then with ``return_filters`` the filters (S,T,F,D), then with
-    ``return_fallbacks`` the list of S fallback counts."""
+    ``return_fallbacks`` the list of S fallback counts.
+
+    ``lookahead`` = L >= 1 (gss_mvdr_online_lookahead_targets): as in
+    `mvdr_souden_online_from_masks`; the postfilter multiplies by the target mask of the OUTPUT
+    frame.  ``hold`` None: the one-shot form -> (S,T,F); ``hold``: S `OnlineMVDRHold`s built for
+    (F,D,L), advanced IN PLACE -> the (S, max(0, held + T - L), F) frames released."""
     Y = np.asarray(Y)
     if Y.ndim != 3:
         raise ValueError(f'Y: shape {Y.shape} is not (D,T,F)')
@@ -3395,8 +3613,45 @@ def mvdr_souden_online_targets(Y, posterior, targets, *, states, forget=BF_ONLIN
     if postfilter not in (None, 'mask_mul'):
         raise ValueError(f"postfilter={postfilter!r}: None or 'mask_mul'")
     ctx, structs = _check_target_states(states, S, (F, D), None)
+    lookahead = check_bf_lookahead(lookahead, ref_channel)
+    if hold is not None and lookahead == 0:
+        raise ValueError('hold: delay lines with lookahead=0')
     fallbacks = [0] * S
-    if T == 0 or F == 0:
+    if lookahead:
+        holds = None if hold is None else _check_holds(hold, S, (F, D, lookahead), ctx)[1]
+        X_hat, W = np.zeros((S, 0, F), np.complex128), np.zeros((S, 0, F, D), np.complex128)
+        if T > 0 and F > 0:
+            one_shot = holds is None
+            if one_shot:
+                holds = [OnlineMVDRHold.fresh(F, D, lookahead, ctx=ctx) for _ in range(S)]
+            R = max(0, holds[0].held + T - lookahead)
+            Y_d, _ = _obs_to_device_ftd(ctx, Y)
+            g_d = ctx.to_device(g.transpose(2, 0, 1))                       # (F,K,T)
+            X_d = ctx.empty(max(16 * S * F * R, 16))
+            W_d = ctx.empty(max(16 * S * F * R * D, 16)) if return_filters else None
+            cfg = _bf_online_cfg(forget, BF_ONLINE_LOADING, ref_channel)
+            lines = _hold_structs(holds)
+            ctx._check(ctx.lib.gss_mvdr_online_lookahead_targets(
+                ctx.handle, c_void_p(Y_d.ptr), F, T, D, c_void_p(g_d.ptr), K,
+                (ctypes.c_int32 * S)(*targets), S, int(bool(ban)), ctypes.byref(cfg), structs, lines,
+                int(postfilter == 'mask_mul'), None, None, c_void_p(X_d.ptr),
+                c_void_p(W_d.ptr) if W_d is not None else None, None),
+                'gss_mvdr_online_lookahead_targets')
+            _holds_advance(holds, lines)
+            if R:
+                X_hat = ctx.to_host(X_d, (S, R, F), np.complex128)
+                if return_filters:
+                    W = np.ascontiguousarray(ctx.to_host(W_d, (S, F, R, D), np.complex128)
+                                             .transpose(0, 2, 1, 3))
+            if return_fallbacks:
+                fallbacks = ctx.last_mvdr_online_fallbacks_targets(S)
+            if one_shot:
+                tail = mvdr_online_release(holds, postfilter=postfilter,
+                                           return_filters=return_filters)
+                if return_filters:
+                    tail, W = tail[0], np.concatenate([W, tail[1]], axis=1)
+                X_hat = np.concatenate([X_hat, tail], axis=1)
+    elif T == 0 or F == 0:
         X_hat, W = np.zeros((S, T, F), np.complex128), np.zeros((S, T, F, D), np.complex128)
     else:
         Y_d, _ = _obs_to_device_ftd(ctx, Y)
@@ -3458,6 +3713,106 @@ def stream_block_targets(block, activity=None, *, params, stream, em_state, bf_s
                                 ctx.last_cacgmm_online_fallbacks())
         details['fallbacks_targets'] = ctx.last_mvdr_online_fallbacks_targets(samples.shape[0])
     return samples, details
+
+
+def stream_block_lookahead(block, activity=None, *, params, stream, em_state, bf_states, holds,
+                           tails, target_indices, release=False, wpe_state=None, ref_channel=0,
+                           wpe_alpha=WPE_ONLINE_ALPHA, em_forget=GSS_ONLINE_FORGET,
+                           bf_forget=BF_ONLINE_FORGET, window=None, debug=False):
+    """`stream_block_targets` (S >= 1) with a filter look-ahead as ONE library call
+    (gss_stream_block_lookahead): its front up to the posteriors, then
+    `mvdr_souden_online_targets` with ``hold=holds`` (BAN, the postfilter on the mask of the
+    output frame) and `istft_stream_targets` on the frames RELEASED; with ``release`` (the last
+    block of a stream) `mvdr_online_release` follows and its frames are synthesised too -- a block
+    of no samples with ``release`` only ends the lines.  ``holds``: S `OnlineMVDRHold`s, advanced
+    IN PLACE like every other state.  Returns (samples (S,m), details): the samples the released
+    frames finish; with ``debug`` the taps, 'X_hat' over the frames released, the others over the
+    block's frames."""
+    if not isinstance(stream, StreamState):
+        raise ValueError(f'stream: {type(stream).__name__} is not a StreamState')
+    ctx = stream.ctx
+    for name, state, cls in (('em_state', em_state, OnlineCACGMMState),
+                             ('wpe_state', wpe_state, OnlineWPEState), ('tails', tails, StreamTails)):
+        if state is None and name == 'wpe_state':
+            continue
+        if not isinstance(state, cls):
+            raise ValueError(f'{name}: {type(state).__name__} is not an {cls.__name__}')
+        if state.ctx is not ctx:
+            raise ValueError(f'{name}: it lives in another context than the stream')
+    targets = check_online_targets(target_indices, em_state.K)
+    S, F, D, K = len(targets), stream.size // 2 + 1, stream.D, em_state.K
+    _, structs = _check_target_states(bf_states, S, (F, D), ctx, 'bf_states')
+    first = holds if isinstance(holds, OnlineMVDRHold) else (
+        holds[0] if hasattr(holds, '__len__') and len(holds) else None)
+    if not isinstance(first, OnlineMVDRHold):
+        raise ValueError('holds: a sequence of OnlineMVDRHold, one per target')
+    _, holds = _check_holds(holds, S, (F, D, first.L), ctx, 'holds')
+    if tails.key != (S, stream.size - stream.shift):
+        raise ValueError(f'tails: built for ({tails._sizes}) = {tails.key}, the call has '
+                         f'{(S, stream.size - stream.shift)}')
+    x_d, in_type, act_d, n = _stream_block_to_device(ctx, block, activity, stream)
+    L, held = first.L, first.held
+    Tn = stream_num_frames(stream.received, n, stream.size, stream.shift)
+    rows = max(0, held + Tn - L) + (min(L, held + Tn) if release else 0)
+    if n == 0 and rows == 0:
+        return np.zeros((S, 0)), None
+    m = stream_num_samples_out(stream.frames_out * stream.shift, rows * stream.shift, stream.size,
+                               stream.shift)
+    _prepare_windows(ctx, stream.size, stream.shift, window)
+    if n == 0:      # (the entry wants the pointers of a block even where it reads no sample)
+        x_d = ctx.empty(16)
+        act_d = ctx.empty(16) if activity is not None else None
+    o_d = ctx.empty(max(8 * S * m, 16))
+    utt = SimpleNamespace(ctx=ctx, D=D, K=K, T=Tn, params=params)
+    bufs = taps = None
+    if debug and (Tn > 0 or rows > 0):
+        bufs, taps = _debug_taps(utt, S) if Tn > 0 else ({}, GssDebugTaps())
+        bufs['Xhat'] = ctx.empty(max(16 * S * F * rows, 16))
+        taps.Xhat = bufs['Xhat'].ptr
+    cfg = GssStreamCfg(wpe_alpha=float(wpe_alpha), em_forget=float(em_forget),
+                       bf_forget=float(bf_forget), ref_channel=int(ref_channel))
+    lines = _hold_structs(holds)
+    ctx._check(ctx.lib.gss_stream_block_lookahead(
+        ctx.handle, ctypes.byref(params), ctypes.byref(cfg), ctypes.byref(stream.struct()),
+        ctypes.byref(wpe_state.struct()) if wpe_state is not None else None,
+        ctypes.byref(em_state.struct()), structs, lines, c_void_p(tails.ptr), c_void_p(x_d.ptr),
+        in_type, c_void_p(act_d.ptr) if act_d else None, n, (ctypes.c_int32 * S)(*targets), S,
+        int(bool(release)), c_void_p(o_d.ptr), None,
+        ctypes.byref(taps) if taps is not None else None), 'gss_stream_block_lookahead')
+    _holds_advance(holds, lines)
+    samples = ctx.to_host(o_d, (S, m), np.float64)
+    if m == 0:
+        ctx.synchronize()      # (the block's device copies are read until then)
+    if bufs is None:
+        return samples, None
+    X_hat = ctx.to_host(bufs.pop('Xhat'), (S, rows, F), np.complex128)
+    if Tn == 0:
+        return samples, {'X_hat': X_hat}
+    if act_d is None:
+        del bufs['act_frames']
+    details = _debug_details_without_xhat(utt, bufs, S)
+    details['X_hat'] = X_hat
+    details['fallbacks'] = (ctx.last_mvdr_online_fallbacks(), ctx.last_cacgmm_online_fallbacks())
+    details['fallbacks_targets'] = ctx.last_mvdr_online_fallbacks_targets(S)
+    return samples, details
+
+
+def _debug_details_without_xhat(utt, bufs, S):
+    """`_debug_details` of a call whose 'X_hat' tap covers other frames than the rest."""
+    ctx, D, K, T = utt.ctx, utt.D, utt.K, utt.T
+    F = utt.params.stft_size // 2 + 1
+    details = {}
+    if 'act_frames' in bufs:
+        details['acitivity_freq'] = ctx.to_host(bufs['act_frames'], (K, T), np.uint8).astype(bool)
+    return {
+        'Obs': _ftd_to_host_dtf(ctx, bufs['Obs_ftd'], D, T, F),
+        **details,
+        'posterior': ctx.to_host(bufs['gamma'], (F, K, T), np.float64).transpose(1, 2, 0),
+        'target_mask': ctx.to_host(bufs['target_mask'], (S, F, T), np.float64).transpose(0, 2, 1),
+        'distortion_mask': ctx.to_host(bufs['distortion_mask'], (S, F, T),
+                                       np.float64).transpose(0, 2, 1),
+        'ref_channel': ctx.to_host(bufs['ref_channel'], (S,), np.int32).astype(int),
+    }
 
 
 def masks_from_posteriors(posterior, target_index, *, ctx=None):

@@ -7,6 +7,10 @@ max(0, floor(M / shift) * shift - (size - shift)) samples have come out, so the 
 latency is below one window.  Whatever the cuts, the samples, the taps and the final states have
 the bits of the stream fed as one block.  A stream has no utterance context: no frames are zeroed
 in the masks, and the beamformer's reference channel is fixed by the caller.
+
+``lookahead`` = L >= 1 gives the beamformer a filter look-ahead (include/gss_hip.h, "online MVDR
+with a filter look-ahead"): frame g is filtered with the filter of frame g + L, so a block returns
+the samples of the frames it RELEASES and the latency grows by L * shift samples.
 """
 import numpy as np
 
@@ -30,7 +34,11 @@ class StreamingEnhancer:
     all of them, `process` and `flush` return (S, m), row s with the bits of the stream of
     ``target=targets[s]``; the per-target taps of ``debug`` are stacked over S and
     ``fallbacks['mvdr_targets']`` lists the beamformer's fallback frames per target
-    (``fallbacks['mvdr']`` is their sum).  Nothing touches the GPU before the first block.
+    (``fallbacks['mvdr']`` is their sum).  ``lookahead``: an integer in [0, 64], the frames the
+    beamformer's filter looks ahead (0: today's stream); `process` then returns the samples of the
+    frames released, `flush` releases the rest, and with ``debug`` the 'X_hat' tap covers the frames
+    released by the block while the masks, the posteriors and 'Obs' cover the block's frames.
+    Nothing touches the GPU before the first block.
     """
 
     def __init__(self, num_channels=None, num_classes=None, *, model=None, target=0, ref_channel=0,
@@ -38,7 +46,8 @@ class StreamingEnhancer:
                  wpe_alpha=ops.WPE_ONLINE_ALPHA, wpe_arrays=1,
                  gss_forget=ops.GSS_ONLINE_FORGET, gss_prior_mass=ops.GSS_ONLINE_PRIOR_MASS,
                  bf_forget=ops.BF_ONLINE_FORGET, bf_loading=ops.BF_ONLINE_LOADING,
-                 postfilter=None, fused=True, speakers=None, targets=None, ctx=None):
+                 postfilter=None, fused=True, speakers=None, targets=None, lookahead=0,
+                 ctx=None):
         if model is not None:
             if not isinstance(model, CACGMM):
                 raise ValueError(f'model: a CACGMM, not {type(model).__name__}')
@@ -80,6 +89,7 @@ class StreamingEnhancer:
         if self.ref_channel < 0:
             raise ValueError(f'ref_channel={ref_channel!r}: a stream has no window to choose a '
                              f'channel over, an integer in [0, {D})')
+        self.lookahead = ops.check_bf_lookahead(lookahead, self.ref_channel)
         self.params = ops.make_params(
             stft_size=size, stft_shift=shift, stft_fading=True, wpe=wpe, wpe_taps=wpe_taps,
             wpe_delay=wpe_delay, bf='mvdrSouden_ban', postfilter=postfilter,
@@ -102,6 +112,7 @@ class StreamingEnhancer:
         """Back to the start of a stream: fresh states (the mixture model from ``model`` again),
         the counters and the fallback counts at zero."""
         self.stream = self.wpe_state = self.em_state = self.bf_states = self.tails = None
+        self.holds = None
         self.samples_in = self.samples_out = 0
         self.fallbacks = {'mvdr': 0, 'cacgmm': 0}
         if self.targets is not None:
@@ -125,8 +136,12 @@ class StreamingEnhancer:
         # (no frames: a stream has none yet, p_f = 1)
         self.bf_states = [ops.OnlineMVDRState.fresh(F, D, self.bf_loading, ctx=ctx)
                           for _ in self._classes()]
-        if self.targets is not None:
-            self.tails = ops.StreamTails.fresh(len(self.targets), self.size, self.shift, ctx=ctx)
+        if self.targets is not None or self.lookahead:
+            # (a look-ahead stream synthesises through the targets entry, S = 1 included)
+            self.tails = ops.StreamTails.fresh(len(self._classes()), self.size, self.shift, ctx=ctx)
+        if self.lookahead:
+            self.holds = [ops.OnlineMVDRHold.fresh(F, D, self.lookahead, ctx=ctx)
+                          for _ in self._classes()]
 
     def _classes(self):
         """The classes extracted, one beamformer state each."""
@@ -134,7 +149,8 @@ class StreamingEnhancer:
 
     @property
     def latency_samples(self):
-        """Samples that went in and have not come out: size - shift + (samples_in mod shift)."""
+        """Samples that went in and have not come out: size - shift + (samples_in mod shift),
+        and lookahead * shift more once ``lookahead`` frames exist."""
         return self.samples_in - self.samples_out
 
     def to_host(self):
@@ -147,6 +163,9 @@ class StreamingEnhancer:
             states = [state.to_host() for state in self.bf_states]
             bf = {'bf': {k: np.stack([h[k] for h in states]) for k in states[0]},
                   'tails': self.tails.to_host()['tails'], 'targets': list(self.targets)}
+        if self.lookahead:      # the delay lines, and the tails of a one-target stream
+            bf.update(lookahead=self.lookahead, holds=[hold.to_host() for hold in self.holds],
+                      tails=self.tails.to_host()['tails'])
         return {'stream': self.stream.to_host(), 'em': self.em_state.to_host(), **bf,
                 'wpe': self.wpe_state.to_host() if self.wpe else None,
                 'samples_in': self.samples_in, 'samples_out': self.samples_out,
@@ -163,12 +182,26 @@ class StreamingEnhancer:
         if self.targets is not None and tuple(host['targets']) != self.targets:
             raise ValueError(f'checkpoint: of targets={tuple(host["targets"])}, this stream has '
                              f'targets={self.targets}')
+        if int(host.get('lookahead', 0)) != self.lookahead:
+            raise ValueError(f'checkpoint: of lookahead={int(host.get("lookahead", 0))}, this '
+                             f'stream has lookahead={self.lookahead}')
         self._states()
         ctx = self.ctx
+        holds = None
+        if self.lookahead:
+            holds = [ops.OnlineMVDRHold.from_host(h, ctx=ctx) for h in host['holds']]
+            if [hold.key for hold in holds] != [hold.key for hold in self.holds]:
+                raise ValueError(f'checkpoint: delay lines built for {[h.key for h in holds]}, '
+                                 f'this stream has {[h.key for h in self.holds]}')
         stream = ops.StreamState.from_host(host['stream'], ctx=ctx)
         em = ops.OnlineCACGMMState.from_host(host['em'], ctx=ctx)
         if self.targets is None:
             bfs = [ops.OnlineMVDRState.from_host(host['bf'], ctx=ctx)]
+            if self.lookahead:
+                tails = ops.StreamTails.from_host({'tails': host['tails']}, ctx=ctx)
+                if tails.key != self.tails.key:
+                    raise ValueError(f'checkpoint: tails built for ({tails._sizes}) = {tails.key}, '
+                                     f'this stream has {self.tails.key}')
         else:
             S = len(self.targets)
             stacked = {k: np.asarray(v) for k, v in host['bf'].items()}
@@ -193,8 +226,9 @@ class StreamingEnhancer:
                 raise ValueError(f'checkpoint: {name} state built for ({state._sizes}) = '
                                  f'{state.key}, this stream has {key}')
         self.stream, self.em_state, self.wpe_state, self.bf_states = stream, em, wpe, bfs
-        if self.targets is not None:
+        if self.targets is not None or self.lookahead:
             self.tails = tails
+        self.holds = holds
         self.samples_in, self.samples_out = int(host['samples_in']), int(host['samples_out'])
         self.fallbacks = {k: list(v) if isinstance(v, (list, tuple)) else v
                           for k, v in host['fallbacks'].items()}
@@ -230,7 +264,8 @@ class StreamingEnhancer:
         """The next ``block`` (D,n) of samples, float64 or int16 PCM, with its ``activity`` (K,n)
         (or a dict of K per-sample tracks in class order) -> the samples the block finishes,
         (m,) float64 -- (S, m) with ``targets`` --; with ``debug`` (samples, details) with the
-        taps over the block's frames (None when the block completes no frame)."""
+        taps over the block's frames (None when the block completes no frame).  With a
+        look-ahead: the samples of the frames the block releases."""
         if self.flushed:
             raise RuntimeError('process after flush: the stream has ended, call reset()')
         block = np.asarray(block)
@@ -243,8 +278,8 @@ class StreamingEnhancer:
 
     def flush(self, debug=False):
         """End the stream: the zeros that complete its last frames go in (inactive), the rest
-        comes out, cut so that samples_out == samples_in.  `process` is an error afterwards
-        until `reset`."""
+        comes out -- with a look-ahead the delay lines are released --, cut so that
+        samples_out == samples_in.  `process` is an error afterwards until `reset`."""
         if self.flushed:
             raise RuntimeError('flush after flush: the stream has ended, call reset()')
         if self.samples_in == 0:        # nothing went in: nothing comes out
@@ -252,7 +287,8 @@ class StreamingEnhancer:
             return (self._no_samples(), None) if debug else self._no_samples()
         n = ops.stream_flush_samples(self.samples_in, self.size, self.shift)
         samples, details = self._block(np.zeros((self.D, n)),
-                                       np.zeros((self.K, n), bool) if self.guided else None, debug)
+                                       np.zeros((self.K, n), bool) if self.guided else None, debug,
+                                       release=True)
         samples = samples[..., :self.samples_in - self.samples_out]
         self.samples_out += samples.shape[-1]
         self.flushed = True
@@ -261,10 +297,12 @@ class StreamingEnhancer:
     def _no_samples(self):
         return np.zeros(0) if self.targets is None else np.zeros((len(self.targets), 0))
 
-    def _block(self, block, activity, debug):
+    def _block(self, block, activity, debug, release=False):
         if block.shape[1] == 0:
             return self._no_samples(), None
         self._states()
+        if self.lookahead:
+            return self._block_lookahead(block, activity, debug, release)
         if not self.fused:
             return self._block_stages(block, activity, debug)
         Tn = ops.stream_num_frames(self.stream.received, block.shape[1], self.size, self.shift)
@@ -287,6 +325,69 @@ class StreamingEnhancer:
                       (self.ctx.last_mvdr_online_fallbacks(),
                        self.ctx.last_cacgmm_online_fallbacks()))
             self._count([counts[0]], counts[1])
+        return samples, details
+
+    def _block_lookahead(self, block, activity, debug, release):
+        """A block of a look-ahead stream: the one library call, or with ``fused=False`` the stage
+        operators -- the front once, `ops.mvdr_souden_online_targets` with the delay lines,
+        `ops.mvdr_online_release` at the end of the stream, one synthesis of the frames
+        released.  A one-target stream is S = 1 of either."""
+        classes, S = self._classes(), len(self._classes())
+        if self.fused:
+            Tn = ops.stream_num_frames(self.stream.received, block.shape[1], self.size, self.shift)
+            samples, details = ops.stream_block_lookahead(
+                block, activity, params=self.params, stream=self.stream, em_state=self.em_state,
+                bf_states=self.bf_states, holds=self.holds, tails=self.tails,
+                target_indices=classes, release=release, wpe_state=self.wpe_state,
+                ref_channel=self.ref_channel, wpe_alpha=self.wpe_alpha, em_forget=self.gss_forget,
+                bf_forget=self.bf_forget, window=self.window, debug=debug)
+            if Tn > 0:
+                self._count(self.ctx.last_mvdr_online_fallbacks_targets(S),
+                            self.ctx.last_cacgmm_online_fallbacks())
+        else:
+            samples, details = self._lookahead_stages(block, activity, debug, release)
+        if self.targets is None:
+            samples = samples[0]
+            if details is not None:
+                details.update({k: v[0] for k, v in details.items() if k in ops._PER_TARGET})
+                details.pop('fallbacks_targets', None)
+        return samples, details
+
+    def _lookahead_stages(self, block, activity, debug, release):
+        classes, S = self._classes(), len(self._classes())
+        Y, act_frames = ops.stft_stream(block, activity, state=self.stream, window=self.window)
+        X_hat = np.zeros((S, 0, self.F), np.complex128)
+        details = {}
+        if Y.shape[1] > 0:
+            Obs = Y
+            if self.wpe:
+                Obs = ops.wpe_online_dtf(Y, self.wpe_taps, self.wpe_delay, self.wpe_alpha,
+                                         arrays=self.wpe_arrays, state=self.wpe_state)
+            posterior, em_fallbacks = ops.cacgmm_posteriors_online(
+                Obs, act_frames, forget=self.gss_forget, state=self.em_state, return_fallbacks=True)
+            X_hat, bf_fallbacks = ops.mvdr_souden_online_targets(
+                Obs, posterior, classes, states=self.bf_states, forget=self.bf_forget,
+                ref_channel=self.ref_channel, ban=True, postfilter=self.postfilter,
+                return_fallbacks=True, lookahead=self.lookahead, hold=self.holds)
+            self._count(bf_fallbacks, em_fallbacks)
+            if debug:
+                masks = [ops.masks_from_posteriors(posterior, k, ctx=self.ctx) for k in classes]
+                details = {'Obs': Obs, 'posterior': posterior,
+                           'target_mask': np.stack([m[0] for m in masks]),
+                           'distortion_mask': np.stack([m[1] for m in masks]),
+                           'ref_channel': np.full(S, self.ref_channel),
+                           'fallbacks': (sum(bf_fallbacks), em_fallbacks),
+                           'fallbacks_targets': bf_fallbacks}
+                if act_frames is not None:
+                    details['acitivity_freq'] = act_frames
+        if release:
+            X_hat = np.concatenate([X_hat, ops.mvdr_online_release(
+                self.holds, postfilter=self.postfilter)], axis=1)
+        samples = ops.istft_stream_targets(X_hat, state=self.stream, tails=self.tails,
+                                           window=self.window)
+        if not debug or (Y.shape[1] == 0 and X_hat.shape[1] == 0):
+            return samples, None
+        details['X_hat'] = X_hat
         return samples, details
 
     def _count(self, bf_targets, em_fallbacks):

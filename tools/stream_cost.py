@@ -15,7 +15,12 @@ the block's own duration, how many times faster than real time the median is, an
 event times of one profiled fused block (a run of its own after the timed rounds) -- against the
 expectation of DESIGN.md section 26.  Lines are written as they are measured.
 
-    python tools/stream_cost.py [--steps 5] [--rounds 7] [--warmup 1] [--shape all|NAME] [--out FILE]"""
+With ``--lookahead L`` a fourth contender `lookahead` joins: the fused stream with
+``lookahead=L`` (one gss_stream_block_lookahead call per block), and the line gains its ratio to
+`fused`; ``--blocks`` picks the block sizes.
+
+    python tools/stream_cost.py [--steps 5] [--rounds 7] [--warmup 1] [--shape all|NAME] [--out FILE]
+                                [--lookahead L] [--blocks N [N ...]]"""
 import argparse
 import json
 import sys
@@ -52,6 +57,8 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--shape', default='all')
     ap.add_argument('--out', default=str(R / 'profiles' / 'stream_cost.jsonl'))
+    ap.add_argument('--lookahead', type=int, default=0)
+    ap.add_argument('--blocks', type=int, nargs='+', default=list(BLOCKS))
     args = ap.parse_args()
     from pb_chime5_amd._capi import default_context
     ctx = default_context(0)
@@ -60,7 +67,7 @@ def main():
             if args.shape not in ('all', name):
                 continue
             x, act = scene(np.random.default_rng(D), D, K)
-            for block in BLOCKS:
+            for block in args.blocks:
                 fd.write(json.dumps(measure(ctx, args, name, D, K, A, block, x, act)) + '\n')
                 fd.flush()
 
@@ -71,6 +78,8 @@ def measure(ctx, args, name, D, K, A, block, x, act):
     kw = dict(stft_size=SIZE, stft_shift=SHIFT, wpe_taps=TAPS, wpe_delay=DELAY, wpe_arrays=A, ctx=ctx)
     streams = {'fused': StreamingEnhancer(D, K, fused=True, **kw),
                'stages': StreamingEnhancer(D, K, fused=False, **kw)}
+    if args.lookahead:
+        streams['lookahead'] = StreamingEnhancer(D, K, fused=True, lookahead=args.lookahead, **kw)
     at = {v: 0 for v in streams}
 
     def step(v):
@@ -112,6 +121,9 @@ def measure(ctx, args, name, D, K, A, block, x, act):
                 stages_over_fused=round(med['stages'] / med['fused'], 2),
                 kernels_of_one_fused_block_ms={k: dict(calls=v['calls'], ms=round(v['ms'], 4))
                                                for k, v in report.items()})
+    if 'lookahead' in med:
+        line['lookahead'] = args.lookahead
+        line['lookahead_over_fused'] = round(med['lookahead'] / med['fused'], 3)
     if 'whole' in med:
         line['fused_over_whole'] = round(med['fused'] / med['whole'], 3)
     print(json.dumps(line), flush=True)
